@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-run() { echo -n "$1: "; env $1 python bench.py --steps 128 --warmup 16 --no-secondary --no-cpu-baseline 2>/dev/null | python3 -c "
+run() { echo -n "$1: "; env $1 python bench.py --full --steps 128 --warmup 16 --no-secondary --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['config']['repeats']['tokens_per_s'])"; }
 run X=1
 run HIP_FORCE_DEV_KERNARG=1

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-levers}
 mkdir -p "$O"
 cd "$R"
-run() { name=$1; shift; ( env "$@" BAMD_AQL_VERBOSE=1 timeout 300 python bench.py --steps 128 --warmup 16 --no-secondary --no-cpu-baseline > "$O/$name.json" 2> "$O/$name.err" ) < /dev/null
+run() { name=$1; shift; ( env "$@" BAMD_AQL_VERBOSE=1 timeout 300 python bench.py --full --steps 128 --warmup 16 --no-secondary --no-cpu-baseline > "$O/$name.json" 2> "$O/$name.err" ) < /dev/null
         python - "$O/$name.json" "$name" <<'PY'
 import json, sys
 try:

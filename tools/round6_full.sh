@@ -8,6 +8,6 @@ mkdir -p $R/gpurun_out/r6full
 bash $R/tools/profile_round.sh prof_r06
 O=$R/gpurun_out/prof_r06; mkdir -p $O/stats_graph
 cd /tmp && export TMPDIR=/tmp
-( cd $R && BAMD_AQL=0 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_graph -- python bench.py --steps 64 --warmup 8 --no-cpu-baseline --no-secondary ) > $O/bench_under_rocprof_graph.json 2> $O/stats_graph.err < /dev/null
+( cd $R && BAMD_AQL=0 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_graph -- python bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --no-secondary ) > $O/bench_under_rocprof_graph.json 2> $O/stats_graph.err < /dev/null
 find "$O" -name '*_kernel_trace.csv' -delete; find "$O" -name '*.db' -delete
 for f in $(find $O/stats $O/stats_graph -name '*kernel_stats.csv'); do echo "== $f"; head -12 $f | cut -c1-160; done
