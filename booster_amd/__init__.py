@@ -63,6 +63,7 @@ def lib():
         L.bamd_op_mul_mat_batch.argtypes = [ci, vp, ci, ci, vp, ci, vp, cf, vp, vp, ci]
         L.bamd_op_get_row.argtypes = [ci, vp, ci, ci, ci, vp]
         L.bamd_op_attention.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+        L.bamd_op_attention_batch.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         L.bamd_op_rope_row.argtypes = [ci, ci, cf, cf, vp, vp]
         L.bamd_set_aql.argtypes = [ci]; L.bamd_set_aql.restype = None
         L.bamd_aql_runs.argtypes = [vp]
@@ -295,3 +296,17 @@ def op_attention(q, k, v, k_cache, v_cache_t, rope_row, H, Hkv, hd, n_ctx, pos, 
     _chk(lib().bamd_op_attention(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope_row), H, Hkv, hd, n_ctx, pos, int(prefill_mode) | (2 if (long_path or want_probs) else 0),
                                  _p(out), _p(probs)))
     return (out, probs) if want_probs else out
+
+
+def op_attention_batch(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, pos0, impl=0, ld=0):
+    """batched-prefill attention of T = len(q) tokens at positions pos0 ..: q [T][H*hd], k / v [T][Hkv*hd] before RoPE, rope [n_ctx][hd];
+    the caches (uint16, reference layouts) are updated in place; returns out [T][H*hd].  impl 0 = launcher's choice, 1 = VALU, 2 = matrix cores"""
+    q = np.ascontiguousarray(q, np.float32).reshape(-1, H * hd)
+    T = q.shape[0]
+    k = np.ascontiguousarray(k, np.float32).reshape(T, Hkv * hd); v = np.ascontiguousarray(v, np.float32).reshape(T, Hkv * hd)
+    rope = np.ascontiguousarray(rope, np.float32).reshape(n_ctx, hd)
+    assert k_cache.dtype == np.uint16 and v_cache_t.dtype == np.uint16 and k_cache.flags.c_contiguous and v_cache_t.flags.c_contiguous
+    assert k_cache.size == n_ctx * Hkv * hd and v_cache_t.size == n_ctx * Hkv * hd
+    out = np.zeros((T, H * hd), np.float32)
+    _chk(lib().bamd_op_attention_batch(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope), H, Hkv, hd, n_ctx, pos0, T, impl, ld, _p(out)))
+    return out

@@ -603,12 +603,13 @@ static void launch_attn_fused(const bamd_attn_args & a, int gq, dim3 grid, size_
 }
 
 // attention of a micro-batch of T tokens (a.batch = 1, a.ld_qkv / a.ld_out set): KV store for all tokens, then (head, token) workgroups
-int bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s) {
+int bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl) {
     const int ld = a.lds_ld ? a.lds_ld : a.n_ctx;
     if (a.hd > 256 || (a.hd & 63) || (ld & 63) || (size_t) ld * 8 > BAMD_ATTN_LDS_MAX || !a.batch) return 1;
-    if (gq < 1 || gq > 8) return 1;
+    if (gq < 1 || gq > 8 || impl < 0 || impl > 2) return 1;
     BAMD_LAUNCH(kv_store_batch_kernel, dim3(a.Hkv, T), dim3(256), 0, s, a);
-    if (bamd_launch_attention_batch_mfma(a, gq, T, s) == 0) return 0;        // head_dim 128 (beyond 512 positions with a.batch_scratch): the matrix-core kernel (bamd_attention_mfma.hip)
+    if (impl != 1 && bamd_launch_attention_batch_mfma(a, gq, T, s) == 0) return 0;   // head_dim 128 (beyond 512 positions with a.batch_scratch): the matrix-core kernel (bamd_attention_mfma.hip)
+    if (impl == 2) return 1;
     // as many query heads of a KV head per workgroup as have their score rows fit the LDS (ld floats each: the probabilities replace
     // the scores in place); a single head per workgroup runs on attn_fused_kernel (separate rows: 2 x ld floats)
     int gqh = (gq == 2 || gq == 4 || gq == 8) ? gq : 1;          // other ratios (3: Llama-3.2-3B): one query head per workgroup

@@ -1545,6 +1545,51 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention(const fl
     return 0;
 }
 
+// batched-prefill attention of T tokens at positions pos0 .. pos0 + T - 1 through the launcher enqueue_prefill_batch calls (KV store, then the matrix-core
+// or VALU kernels), with the same argument block: q / k / v packed as one [T][H*hd + 2*Hkv*hd] matrix, batch_pos0p1, lds_ld, scratch block
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                                                                const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld,
+                                                                                float * out) {
+    if (need_device()) return 1;
+    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || n_ctx % 32 || H % Hkv || H / Hkv > 8) return fail("bad attention shape");
+    if (T < 1 || T > BAMD_PREFILL_CAP || pos0 < 0 || pos0 + T > n_ctx) return fail("bad micro-batch");
+    if (impl < 0 || impl > 2) return fail("impl must be 0 (launcher's choice), 1 (VALU) or 2 (matrix cores)");
+    const int Ekv = Hkv * hd, E = H * hd, ldq = E + 2 * Ekv, gq = H / Hkv, n_ctx_pad = (n_ctx + 63) / 64 * 64;
+    const int ld_min = std::min((pos0 + T + 63) / 64 * 64, n_ctx_pad);        // attn_lds_ld of the micro-batch's last position
+    if (ld == 0) ld = ld_min;
+    if (ld % 64 || ld < ld_min || ld > n_ctx_pad) return fail("ld must be a multiple of 64 between the padded sequence length and the padded n_ctx");
+    Tmp t; const size_t kvb = (size_t) n_ctx_pad * Ekv * 2;
+    std::vector<float> qkv((size_t) T * ldq);
+    for (int i = 0; i < T; ++i) {
+        memcpy(&qkv[(size_t) i * ldq], q + (size_t) i * E, (size_t) E * 4);
+        memcpy(&qkv[(size_t) i * ldq + E], k + (size_t) i * Ekv, (size_t) Ekv * 4);
+        memcpy(&qkv[(size_t) i * ldq + E + Ekv], v + (size_t) i * Ekv, (size_t) Ekv * 4);
+    }
+    std::vector<uint16_t> kd, vd;
+    kv_to_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
+    bamd_step_state h; memset(&h, 0, sizeof h);                                 // as enqueue_prefill_batch sets it
+    h.pos_base = pos0; h.pos = pos0; h.n_ctx = n_ctx; h.step = T; h.n_kv = std::min(n_ctx, (pos0 + T + 31) / 32 * 32);
+    bamd_attn_args a; memset(&a, 0, sizeof a);
+    a.st = (bamd_step_state *) t.up(&h, sizeof h);
+    float * dqkv = (float *) t.up(qkv.data(), qkv.size() * 4);
+    a.kc = (unsigned short *) t.up(kd.data(), kvb); a.vc = (unsigned short *) t.up(vd.data(), kvb);
+    a.rope = (float *) t.up(rope, (size_t) n_ctx * hd * 4); a.out = (float *) t.up(nullptr, (size_t) T * E * 4);
+    if (!a.st || !dqkv || !a.kc || !a.vc || !a.rope || !a.out) return fail("device alloc/copy failed");
+    a.q = dqkv; a.k = dqkv + E; a.v = dqkv + E + Ekv;
+    a.hd = hd; a.Hkv = Hkv; a.n_ctx = n_ctx_pad; a.kq_scale = 1.0f / sqrtf((float) hd); a.prefill_mode = 1;
+    a.batch = 1; a.ld_qkv = ldq; a.ld_out = E; a.lds_ld = ld; a.batch_pos0p1 = pos0 + 1;
+    const size_t need = hd == 128 && impl != 1 ? bamd_attention_batch_mfma_scratch(Hkv, gq, T, ld) : 0;
+    if (need && !(a.batch_scratch = (float *) t.up(nullptr, need))) return fail("device alloc failed (scratch block)");
+    if (bamd_launch_attention_batch(a, gq, T, nullptr, impl)) return fail(impl == 2 ? "matrix-core kernel: shape not covered" : "batched attention: unsupported shape");
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(out, a.out, (size_t) T * E * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(kd.data(), a.kc, kvb, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(vd.data(), a.vc, kvb, hipMemcpyDeviceToHost));
+    kv_from_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
+    return 0;
+}
+
 // ---- micro-benchmark of one mat-vec launch shape (random resident weights; HIP-event timing of `iters` launches) ----
 extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type, int nrows, int k, int pro, int epi, int mode, int iters,
                                                                         float * us_per_launch) {

@@ -100,7 +100,9 @@ int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type,
                               int epi, int ldo, hipStream_t s);
 int  bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);      // 1 = shape not supported
 void bamd_launch_embed_batch(const int32_t * tokens, int T, const void * embd, int embd_type, int E, int V, float * x, hipStream_t s);
-int  bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s);     // 1 = shape not supported
+// impl: 0 = the matrix-core kernel where it covers the shape, else the VALU kernels (the engine); 1 = the VALU kernels only; 2 = the matrix-core
+// kernel only (1 when it declines the shape — after the KV store).  Op-level tests select the path; the engine passes the default
+int  bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl = 0);     // 1 = shape not supported
 int  bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hipStream_t s);   // the same on the matrix cores (after the KV store); 1 = shape not covered
 size_t bamd_attention_batch_mfma_scratch(int Hkv, int gq, int T, int ld);                         // bytes of a.batch_scratch it needs for sequences of up to ld positions (0: none)
 void bamd_launch_sampler_shortlist(float * logits, const bamd_logit_penalty * pen, int n_pen, const uint8_t * halve_class, int halve,

@@ -211,6 +211,13 @@ int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, flo
 int bamd_op_attention(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
                       const float * rope_row, int H, int Hkv, int hd, int n_ctx, int pos, int prefill_mode, float * out,
                       float * probs_h0);
+/* attention of a micro-batch of T tokens at positions pos0 .. pos0 + T - 1 (llm_build_kv with n_tokens = T, the reference's T > 1 semantics):
+ * q [T][H*hd], k / v [T][Hkv*hd] before RoPE, rope [n_ctx][hd] the (cos,sin) table; the caches (host arrays in the reference's layouts) are updated,
+ * out [T][H*hd].  impl: 0 = the launcher's choice (as the engine calls it), 1 = VALU kernels only, 2 = matrix-core kernel only (error where it
+ * declines the shape).  ld: floats per LDS score row / scratch column, 0 = the engine's choice, else a multiple of 64 from the padded length of
+ * the micro-batch's last position up to the padded n_ctx. */
+int bamd_op_attention_batch(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                            const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld, float * out);
 /* RoPE (cos,sin) table row as built on the host for position pos (ggml_rope_cache_init, ggml.c:14017) */
 int bamd_op_rope_row(int pos, int n_dims, float freq_base, float freq_scale, const float * freq_factors, float * row);
 

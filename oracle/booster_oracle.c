@@ -432,6 +432,57 @@ float bo_vec_dot_f16(int n, const uint16_t * x, const uint16_t * y) {
 }
 
 /* ======================================================================================================
+ * attention of one layer for a micro-batch of T tokens at positions n_past .. n_past + T - 1
+ * ====================================================================================================== */
+void bo_attention(float * q, float * k, const float * v, const float * rope, uint16_t * k_cache, uint16_t * v_cache_t,
+                  int H, int Hkv, int hd, int n_ctx, int n_past, int T, int f16_scores, float * out, int nthreads) {
+    const int E = H * hd, Ekv = Hkv * hd, gq = H / Hkv;
+    /* llama.cpp:14693-14701: n_kv = min(size, max(32, GGML_PAD(cell_max, 32))) — one length for the whole micro-batch */
+    int n_kv = ((n_past + T) + 31) / 32 * 32; if (n_kv < 32) n_kv = 32; if (n_kv > n_ctx) n_kv = n_ctx;
+    const float kq_scale = 1.0f / sqrtf((float) hd);                     /* llama.cpp:8829 */
+    for (int t = 0; t < T; ++t) {                                        /* ggml_rope_ext :8837-8849 */
+        for (int h = 0; h < H; ++h)   bo_rope_apply(q + (size_t) t * E   + h * hd, rope + (size_t) t * hd, hd);
+        for (int h = 0; h < Hkv; ++h) bo_rope_apply(k + (size_t) t * Ekv + h * hd, rope + (size_t) t * hd, hd);
+    }
+    for (int t = 0; t < T; ++t) {                                        /* llm_build_kv_store :7830-7875 */
+        const int cell = n_past + t;
+        for (int i = 0; i < Ekv; ++i) {
+            k_cache[(size_t) cell * Ekv + i] = bo_fp32_to_fp16(k[(size_t) t * Ekv + i]);
+            v_cache_t[(size_t) i * n_ctx + cell] = bo_fp32_to_fp16(v[(size_t) t * Ekv + i]);
+        }
+    }
+    /* llm_build_kqv :8188-8316; every (token, head) is independent */
+#pragma omp parallel num_threads(nthreads > 0 ? nthreads : 1)
+    {
+        float * kq   = (float *) malloc((size_t) n_kv * 4);
+        float * pr   = (float *) malloc((size_t) n_kv * 4);
+        float * mask = (float *) malloc((size_t) n_kv * 4);
+        uint16_t * q16 = (uint16_t *) malloc((size_t) hd * 2);
+#pragma omp for schedule(dynamic)
+        for (int th = 0; th < T * H; ++th) {
+            const int t = th / H, h = th % H, hk = h / gq, pos = n_past + t;
+            for (int i = 0; i < n_kv; ++i) mask[i] = i <= pos ? 0.0f : -INFINITY;   /* llama_set_inputs :14152-14200 */
+            const float * qh = q + (size_t) t * E + h * hd;
+            if (!f16_scores) {
+                /* llamafile_sgemm F16 x F32 (q stays f32 when T == 1) */
+                for (int i = 0; i < n_kv; ++i)
+                    kq[i] = bo_dot_f16_f32_tinyblas(k_cache + (size_t) i * Ekv + hk * hd, qh, hd);
+            } else {
+                /* q rounded to f16 (ggml.c:12345-12372), ggml_vec_dot_f16 */
+                for (int i = 0; i < hd; ++i) q16[i] = bo_fp32_to_fp16(qh[i]);
+                for (int i = 0; i < n_kv; ++i)
+                    kq[i] = bo_vec_dot_f16(hd, k_cache + (size_t) i * Ekv + hk * hd, q16);
+            }
+            bo_soft_max(kq, mask, kq_scale, pr, n_kv);
+            /* kqv = mul_mat(v^T, p): llamafile_sgemm F16 x F32 for every T (p is contiguous) */
+            for (int d = 0; d < hd; ++d)
+                out[(size_t) t * E + h * hd + d] = bo_dot_f16_f32_tinyblas(v_cache_t + (size_t)(hk * hd + d) * n_ctx, pr, n_kv);
+        }
+        free(kq); free(pr); free(mask); free(q16);
+    }
+}
+
+/* ======================================================================================================
  * whole model
  * ====================================================================================================== */
 struct bo_ctx {
@@ -466,11 +517,8 @@ const uint16_t * bo_kv_v(const bo_ctx * c, int il) { return c->v[il]; }
 int bo_decode(bo_ctx * c, const int32_t * tokens, int T, int n_past) {
     const bo_model * m = c->m;
     const int E = m->E, H = m->H, Hkv = m->Hkv, hd = m->hd, F = m->F, V = m->V, n_ctx = c->n_ctx, nth = c->nthreads;
-    const int Ekv = Hkv * hd, gq = H / Hkv;
+    const int Ekv = Hkv * hd;
     if (n_past + T > n_ctx) return 1;
-    /* llama.cpp:14693-14701: n_kv = min(size, max(32, GGML_PAD(cell_max, 32))) */
-    int n_kv = ((n_past + T) + 31) / 32 * 32; if (n_kv < 32) n_kv = 32; if (n_kv > n_ctx) n_kv = n_ctx;
-    const float kq_scale = 1.0f / sqrtf((float) hd);                     /* llama.cpp:8829 */
 
     float * x    = (float *) malloc((size_t) T * E * 4);                 /* residual stream inpL */
     float * cur  = (float *) malloc((size_t) T * E * 4);
@@ -481,11 +529,7 @@ int bo_decode(bo_ctx * c, const int32_t * tokens, int T, int n_past) {
     float * ffi  = (float *) malloc((size_t) T * E * 4);
     float * g    = (float *) malloc((size_t) T * F * 4);
     float * u    = (float *) malloc((size_t) T * F * 4);
-    float * kq   = (float *) malloc((size_t) n_kv * 4);
-    float * pr   = (float *) malloc((size_t) n_kv * 4);
-    float * mask = (float *) malloc((size_t) n_kv * 4);
     float * rc   = (float *) malloc((size_t) T * hd * 4);
-    uint16_t * q16 = (uint16_t *) malloc((size_t) hd * 2);
 
     for (int t = 0; t < T; ++t) {                                        /* llm_build_inp_embd :7802, get_rows ggml.c:13186 */
         bo_dequantize_row(m->t_embd, (const char *) m->tok_embd + (size_t) tokens[t] * bo_row_size(m->t_embd, E), x + (size_t) t * E, E);
@@ -506,44 +550,10 @@ int bo_decode(bo_ctx * c, const int32_t * tokens, int T, int n_past) {
         bo_mul_mat_q(ly->tk, ly->wk, Ekv, E, cur, T, kk, nth);
         bo_mul_mat_q(ly->tv, ly->wv, Ekv, E, cur, T, vv, nth);
         TAP("Vcur", il, vv, (size_t) T * Ekv);
-        for (int t = 0; t < T; ++t) {                                    /* ggml_rope_ext :8837-8849 */
-            for (int h = 0; h < H; ++h)   bo_rope_apply(q  + (size_t) t * E   + h * hd, rc + (size_t) t * hd, hd);
-            for (int h = 0; h < Hkv; ++h) bo_rope_apply(kk + (size_t) t * Ekv + h * hd, rc + (size_t) t * hd, hd);
-        }
+        /* ggml_rope_ext :8837-8849, llm_build_kv_store :7830-7875, llm_build_kqv :8188-8316 (q / k roped in place) */
+        bo_attention(q, kk, vv, rc, c->k[il], c->v[il], H, Hkv, hd, n_ctx, n_past, T, T > 1, att, nth);
         TAP("Qcur", il, q, (size_t) T * E);
         TAP("Kcur", il, kk, (size_t) T * Ekv);
-        for (int t = 0; t < T; ++t) {                                    /* llm_build_kv_store :7830-7875 */
-            const int cell = n_past + t;
-            for (int i = 0; i < Ekv; ++i) {
-                c->k[il][(size_t) cell * Ekv + i] = bo_fp32_to_fp16(kk[(size_t) t * Ekv + i]);
-                c->v[il][(size_t) i * n_ctx + cell] = bo_fp32_to_fp16(vv[(size_t) t * Ekv + i]);
-            }
-        }
-        /* llm_build_kqv :8188-8316 */
-        for (int t = 0; t < T; ++t) {
-            const int pos = n_past + t;
-            for (int i = 0; i < n_kv; ++i) mask[i] = i <= pos ? 0.0f : -INFINITY;   /* llama_set_inputs :14152-14200 */
-            for (int h = 0; h < H; ++h) {
-                const int hk = h / gq;
-                const float * qh = q + (size_t) t * E + h * hd;
-                if (T == 1) {
-                    /* llamafile_sgemm F16 x F32 (q stays f32 when T == 1) */
-                    for (int i = 0; i < n_kv; ++i)
-                        kq[i] = bo_dot_f16_f32_tinyblas(c->k[il] + (size_t) i * Ekv + hk * hd, qh, hd);
-                } else {
-                    /* q rounded to f16 (ggml.c:12345-12372), ggml_vec_dot_f16 */
-                    for (int i = 0; i < hd; ++i) q16[i] = bo_fp32_to_fp16(qh[i]);
-                    for (int i = 0; i < n_kv; ++i)
-                        kq[i] = bo_vec_dot_f16(hd, c->k[il] + (size_t) i * Ekv + hk * hd, q16);
-                }
-                if (t == T - 1 && h == 0) TAP("kq_h0_last", il, kq, n_kv);
-                bo_soft_max(kq, mask, kq_scale, pr, n_kv);
-                if (t == T - 1 && h == 0) TAP("kq_soft_max_h0_last", il, pr, n_kv);
-                /* kqv = mul_mat(v^T, p): llamafile_sgemm F16 x F32 for every T (p is contiguous) */
-                for (int d = 0; d < hd; ++d)
-                    att[(size_t) t * E + h * hd + d] = bo_dot_f16_f32_tinyblas(c->v[il] + (size_t)(hk * hd + d) * n_ctx, pr, n_kv);
-            }
-        }
         TAP("kqv_merged_cont", il, att, (size_t) T * E);
         bo_mul_mat_q(ly->to, ly->wo, E, E, att, T, cur, nth);
         TAP("kqv_out", il, cur, (size_t) T * E);
@@ -581,6 +591,6 @@ int bo_decode(bo_ctx * c, const int32_t * tokens, int T, int n_past) {
         bo_mul_mat_q(m->t_out, m->output, V, E, cur, 1, c->logits, nth);
         TAP("result_output", -1, c->logits, V);
     }
-    free(x); free(cur); free(q); free(kk); free(vv); free(att); free(ffi); free(g); free(u); free(kq); free(pr); free(mask); free(rc); free(q16);
+    free(x); free(cur); free(q); free(kk); free(vv); free(att); free(ffi); free(g); free(u); free(rc);
     return 0;
 }

@@ -64,6 +64,8 @@ def lib():
         L.bo_rope_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.bo_dot_f16_f32_tinyblas.restype = C.c_float; L.bo_dot_f16_f32_tinyblas.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bo_vec_dot_f16.restype = C.c_float; L.bo_vec_dot_f16.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.bo_attention.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.bo_ctx_new.restype = C.c_void_p; L.bo_ctx_new.argtypes = [C.POINTER(BoModel), C.c_int, C.c_int]
         L.bo_ctx_free.argtypes = [C.c_void_p]
         L.bo_ctx_set_tap.argtypes = [C.c_void_p, TAP_FN, C.c_void_p]
@@ -126,6 +128,24 @@ def rope_cache(pos, n_dims, freq_base, freq_scale=1.0, freq_factors=None, ext_fa
     lib().bo_rope_cache(_p(c), pos, n_dims, freq_base, freq_scale, None if ff is None else _p(ff), ext_factor, attn_factor,
                         n_ctx_orig, beta_fast, beta_slow)
     return c
+
+
+def attention(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, n_past, f16_scores, nthreads=None):
+    """llm_build_kv of one layer for the T = len(q) tokens at positions n_past ..: q [T][H*hd], k / v [T][Hkv*hd] f32 before RoPE, rope = the
+    (cos, sin) table [>= n_past + T][hd] or its rows [T][hd] of those positions.  k_cache [n_ctx*Hkv*hd] / v_cache_t [Hkv*hd*n_ctx] (uint16,
+    the reference's layouts) are updated in place.  Returns out [T][H*hd]."""
+    q = np.array(q, np.float32).reshape(-1, H * hd)                      # copies: bo_attention ropes q / k in place
+    T = q.shape[0]
+    k = np.array(k, np.float32).reshape(T, Hkv * hd); v = np.ascontiguousarray(v, np.float32).reshape(T, Hkv * hd)
+    rope = np.asarray(rope, np.float32).reshape(-1, hd)
+    rows = np.ascontiguousarray(rope if rope.shape[0] == T else rope[n_past:n_past + T])
+    assert rows.shape[0] == T and n_past + T <= n_ctx
+    assert k_cache.dtype == np.uint16 and v_cache_t.dtype == np.uint16 and k_cache.flags.c_contiguous and v_cache_t.flags.c_contiguous
+    assert k_cache.size == n_ctx * Hkv * hd and v_cache_t.size == n_ctx * Hkv * hd
+    out = np.zeros((T, H * hd), np.float32)
+    lib().bo_attention(_p(q), _p(k), _p(v), _p(rows), _p(k_cache), _p(v_cache_t), H, Hkv, hd, n_ctx, n_past, T, int(bool(f16_scores)),
+                       _p(out), nthreads or min(16, os.cpu_count() or 1))
+    return out
 
 
 # ---- whole model -----------------------------------------------------------------------------------------

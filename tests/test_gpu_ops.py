@@ -193,7 +193,9 @@ def oracle_attention(po, q, k, v, kc, vc, rope, H, Hkv, hd, n_ctx, pos, prefill)
     return out, probs0
 
 
-@pytest.mark.parametrize("H,Hkv,hd", [(4, 1, 128), (4, 2, 64), (8, 8, 64), (8, 1, 256)])
+@pytest.mark.parametrize("H,Hkv,hd", [(4, 1, 128), (4, 2, 64), (8, 8, 64), (8, 1, 256),
+                                      # odd ratios: the one-launch softmax + P.V declines (spv_ok), so the long path is attn_qk_kernel<G> + attn_softmax_kernel + attn_pv_kernel
+                                      (6, 2, 64), (5, 1, 128), (12, 2, 192), (7, 1, 256)])
 @pytest.mark.parametrize("prefill", [False, True])
 @pytest.mark.parametrize("long_path", [False, True])
 def test_attention(bamd, po, H, Hkv, hd, prefill, long_path):
@@ -270,8 +272,9 @@ def test_attention_long_context_eight_heads_per_kv_head(bamd, po):
 
 @pytest.mark.parametrize("prefill", [False, True])
 def test_attention_long_context(bamd, po, prefill):
-    """the three-kernel path at real long-context sizes: many 64-position tiles per workgroup, the softmax kernel both with its
-    register-cached pass (n_kv <= 8192) and with the multi-pass fallback, the P.V kernel over hundreds of blocks"""
+    """the long-sequence path at real long-context sizes: the score kernel with many 64-position tiles per workgroup, then (gq 4, n_ctx 16384:
+    2 x 64 KB of probability rows fit the LDS) the one-launch softmax + P.V kernel attn_spv_kernel over hundreds of blocks.  The pair
+    attn_softmax_kernel + attn_pv_kernel runs in test_attention_long_context_softmax_pv_pair and for the odd ratios"""
     H, Hkv, hd, n_ctx = 4, 1, 128, 16384
     rng = np.random.default_rng(4242 + prefill)
     Ekv = Hkv * hd
@@ -288,3 +291,36 @@ def test_attention_long_context(bamd, po, prefill):
         assert_bits(gprobs[:wprobs.size], wprobs, "softmax pos %d" % pos)
         assert np.array_equal(kc, kc2) and np.array_equal(vc, vc2), "KV store differs at pos %d" % pos
         assert_bits(got, want, "attention out pos %d" % pos)
+
+
+def _long_context_cases(bamd, po, H, Hkv, hd, n_ctx, positions, prefill, seed):
+    rng = np.random.default_rng(seed)
+    Ekv = Hkv * hd
+    kc = (rng.standard_normal(n_ctx * Ekv) * 0.7).astype(np.float16).view(np.uint16).copy()
+    vc = rng.standard_normal(Ekv * n_ctx).astype(np.float16).view(np.uint16).copy()
+    for pos in positions:
+        q = (rng.standard_normal(H * hd) * 2).astype(np.float32)
+        k = rng.standard_normal(Ekv).astype(np.float32)
+        v = rng.standard_normal(Ekv).astype(np.float32)
+        rope = po.rope_cache(pos, hd, 500000.0)
+        kc2, vc2 = kc.copy(), vc.copy()
+        want, wprobs = oracle_attention(po, q, k, v, kc2, vc2, rope, H, Hkv, hd, n_ctx, pos, prefill)
+        got, gprobs = bamd.op_attention(q, k, v, kc, vc, rope, H, Hkv, hd, n_ctx, pos, prefill_mode=prefill, want_probs=True)
+        assert_bits(gprobs[:wprobs.size], wprobs, "softmax pos %d" % pos)
+        assert np.array_equal(kc, kc2) and np.array_equal(vc, vc2), "KV store differs at pos %d" % pos
+        assert_bits(got, want, "attention out pos %d" % pos)
+
+
+@pytest.mark.parametrize("prefill", [False, True])
+def test_attention_long_context_softmax_pv_pair(bamd, po, prefill):
+    """gq 4 at n_ctx 20480: 2 x 80 KB of probability rows exceed BAMD_SPV_LDS_MAX, so the one-launch softmax + P.V declines and
+    attn_softmax_kernel + attn_pv_kernel run (the only way an even ratio reaches them), the softmax kernel beyond its register-cached pass
+    (n_kv > 8192); a half block at the end (n_kv % 64 == 32)"""
+    _long_context_cases(bamd, po, 4, 1, 128, 20480, (19000, 20479), prefill, 2048 + prefill)
+
+
+@pytest.mark.parametrize("prefill", [False, True])
+def test_attention_long_context_gq3(bamd, po, prefill):
+    """the Llama-3.2-3B ratio (gq 3) decoding past 448 positions: attn_qk_kernel<3> + attn_softmax_kernel + attn_pv_kernel (odd ratios never take
+    the one-launch softmax + P.V; the softmax kernel's register-cached pass), at 4 K positions and at the last cell of the context"""
+    _long_context_cases(bamd, po, 6, 2, 128, 4096, (500, 3001, 4095), prefill, 333 + prefill)
