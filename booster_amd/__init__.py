@@ -59,6 +59,7 @@ def lib():
         L.bamd_bench_matvec.argtypes = [ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)]
         L.bamd_op_quantize_q8_K.argtypes = [vp, i64, vp, cf, vp]
         L.bamd_op_mul_mat_vec.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, vp, ci]
+        L.bamd_op_mul_mat_vec_argmax.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, ci, C.POINTER(C.c_int32)]
         L.bamd_op_ffn_gate_up.argtypes = [ci, vp, vp, ci, ci, vp, vp, cf, vp]
         L.bamd_op_mul_mat_batch.argtypes = [ci, vp, ci, ci, vp, ci, vp, cf, vp, vp, ci]
         L.bamd_op_get_row.argtypes = [ci, vp, ci, ci, ci, vp]
@@ -251,6 +252,17 @@ def op_mul_mat_vec(ttype, w_raw, nrows, k, x, norm_w=None, eps=0.0, residual=Non
     y = np.zeros(nrows, np.float32)
     _chk(lib().bamd_op_mul_mat_vec(ttype, _p(w_raw), nrows, k, _p(x), _p(nw), eps, _p(res), _p(y), mode))
     return y
+
+
+def op_mul_mat_vec_argmax(ttype, w_raw, nrows, k, x, norm_w=None, eps=0.0, mode=0):
+    """the lm_head launch with the greedy arg-max epilogue: (y, the row the epilogue picks); mode 16 forces the generic kernel"""
+    w_raw = np.ascontiguousarray(w_raw, np.uint8)
+    x = np.ascontiguousarray(x, np.float32)
+    nw = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32)
+    y = np.zeros(nrows, np.float32)
+    row = C.c_int32(-1)
+    _chk(lib().bamd_op_mul_mat_vec_argmax(ttype, _p(w_raw), nrows, k, _p(x), _p(nw), eps, _p(y), mode, C.byref(row)))
+    return y, int(row.value)
 
 
 def op_mul_mat_batch(ttype, w_raw, nrows, k, x, norm_w=None, eps=0.0, residual=None, impl=0):

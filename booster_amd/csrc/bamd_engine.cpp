@@ -1404,7 +1404,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_K(cons
 }
 
 static int op_matvec(int type, const void * wA, const void * wB, int nrows, int k, const float * x, const float * norm_w, float eps,
-                     const float * residual, float * y, int epi, int mode) {
+                     const float * residual, float * y, int epi, int mode, unsigned long long * best_key = nullptr) {
     if (need_device()) return 1;
     if (!bamd_is_kquant(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
     const int nrows_pad = (nrows + 7) / 8 * 8;
@@ -1428,11 +1428,20 @@ static int op_matvec(int type, const void * wA, const void * wB, int nrows, int 
     HIPC(hipGetLastError());
     HIPC(hipDeviceSynchronize());
     HIPC(hipMemcpy(y, dy, (size_t) nrows * 4, hipMemcpyDeviceToHost));
+    if (best_key) HIPC(hipMemcpy(best_key, key, 8, hipMemcpyDeviceToHost));
     return 0;
 }
 extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w, float eps,
                                    const float * residual, float * y, int mode) {
     return op_matvec(type, w_raw, nullptr, nrows, k, x, norm_w, eps, residual, y, residual ? BAMD_EPI_ADD : BAMD_EPI_STORE, mode);
+}
+// the lm_head launch (enqueue_lm_head) with its arg-max epilogue; the row is decoded from the key as step_begin_kernel decodes it
+extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec_argmax(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w,
+                                                                                 float eps, float * y, int mode, int32_t * row) {
+    unsigned long long key = 0ull;
+    if (op_matvec(type, w_raw, nullptr, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_ARGMAX, mode, &key)) return 1;
+    *row = key ? (int32_t) (0xffffffffu - (uint32_t) (key & 0xffffffffull)) : -1;
+    return 0;
 }
 // batched mat-mul of T activation rows against one matrix through the prefill kernels: impl 0 = integer-dot kernel, 2 = matrix-core kernel (1 and 3 were the generations removed in round 6)
 extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const float * x, int T, const float * norm_w,

@@ -197,6 +197,10 @@ int bamd_op_quantize_q8_K(const float * x, int64_t k, const float * norm_w, floa
 /* y[nrows] = W . Q8_K(act) (+ residual), W = GGUF-layout blocks [nrows][k] of `type`  (ggml_compute_forward_mul_mat, ggml.c:12277) */
 int bamd_op_mul_mat_vec(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w, float eps,
                         const float * residual, float * y, int mode /* 0 auto, 1 wave-per-row-group, 2 split-K */);
+/* the lm_head launch with the greedy arg-max epilogue (BAMD_EPI_ARGMAX): y as bamd_op_mul_mat_vec without residual, *row = the row the
+ * epilogue picks, which must be the lowest row of largest y (std::max_element).  mode 0: the launcher's choice; mode 16: the generic kernel */
+int bamd_op_mul_mat_vec_argmax(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w, float eps, float * y,
+                               int mode, int32_t * row);
 /* Y[T][nrows] = rows of W . Q8_K(act_t) (+ residual[T][nrows]) for T activation rows x[T][k] through the batched prefill kernels
  * (ggml_compute_forward_mul_mat with ne11 = T): impl 0 = integer-dot kernel (any K-quant), 1 = MFMA kernel (Q4_K, k % 1024 == 0) */
 int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const float * x, int T, const float * norm_w, float eps,

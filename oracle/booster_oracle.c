@@ -334,6 +334,10 @@ float bo_v_silu(float x) {
     const float one_plus = 1.0f + bo_v_expf(neg_x);
     return x / one_plus;
 }
+/* ggml_vec_silu_f32 (ggml.c:2595-2617) for n % 8 == 0: its AVX2 loop only (the scalar tail uses libm expf) */
+void bo_vec_silu(const float * x, float * y, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) y[i] = bo_v_silu(x[i]);
+}
 
 /* ggml.c:13682-13778 ggml_compute_forward_soft_max_f32 + ggml_vec_soft_max_f32 (:2619-2671, AVX2 branch).
  * n must be a multiple of 8 here (n_kv is padded to 32, llama.cpp:14693-14701). mask may be NULL. */

@@ -58,6 +58,7 @@ def lib():
         L.bo_rms_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float]
         L.bo_v_expf.restype = C.c_float; L.bo_v_expf.argtypes = [C.c_float]
         L.bo_v_silu.restype = C.c_float; L.bo_v_silu.argtypes = [C.c_float]
+        L.bo_vec_silu.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.bo_soft_max.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int]
         L.bo_rope_cache.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_float,
                                     C.c_int, C.c_float, C.c_float]
@@ -110,6 +111,15 @@ def rms_norm(x, eps):
     x = np.ascontiguousarray(x, np.float32)
     y = np.empty_like(x)
     lib().bo_rms_norm(_p(x), _p(y), x.size, eps)
+    return y
+
+
+def silu(x):
+    """ggml_v_silu (one AVX2 lane) of every element: what ggml_silu computes for rows whose length is a multiple of 8 (the reference
+    takes the last n % 8 elements of a row through scalar ggml_silu_f32, i.e. libm expf; the decode path's rows are n_ff long)"""
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.empty_like(x)
+    lib().bo_vec_silu(_p(x), _p(y), x.size)
     return y
 
 
