@@ -66,6 +66,8 @@ def lib():
         L.bamd_op_attention.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
         L.bamd_op_attention_batch.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         L.bamd_op_rope_row.argtypes = [ci, ci, cf, cf, vp, vp]
+        L.bamd_op_k_shift.argtypes = [vp, ci, ci, ci, vp, cf, cf, vp, cf, cf, ci]
+        L.bamd_op_attention_cells.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
         L.bamd_set_aql.argtypes = [ci]; L.bamd_set_aql.restype = None
         L.bamd_aql_runs.argtypes = [vp]
         _lib = L
@@ -308,6 +310,32 @@ def op_attention(q, k, v, k_cache, v_cache_t, rope_row, H, Hkv, hd, n_ctx, pos, 
     _chk(lib().bamd_op_attention(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope_row), H, Hkv, hd, n_ctx, pos, int(prefill_mode) | (2 if (long_path or want_probs) else 0),
                                  _p(out), _p(probs)))
     return (out, probs) if want_probs else out
+
+
+def op_k_shift(k_cache, n_ctx, Hkv, hd, delta, freq_base, freq_scale=1.0, freq_factors=None, ext_factor=0.0, attn_factor=1.0, n_ctx_orig=8192):
+    """the K-shift of one layer through the engine's table code and kernel: a COPY of k_cache [n_ctx*Hkv*hd] (uint16, reference layout) with every
+    cell re-rotated by delta[cell]"""
+    kc = np.array(k_cache, np.uint16).reshape(-1)
+    assert kc.size == n_ctx * Hkv * hd
+    d = np.ascontiguousarray(delta, np.int32).reshape(n_ctx)
+    ff = None if freq_factors is None else np.ascontiguousarray(freq_factors, np.float32)
+    _chk(lib().bamd_op_k_shift(_p(kc), n_ctx, Hkv, hd, _p(d), freq_base, freq_scale, _p(ff), ext_factor, attn_factor, n_ctx_orig))
+    return kc
+
+
+def op_attention_cells(q, k, v, k_cache, v_cache_t, rope_row, cellpos, H, Hkv, hd, n_ctx, pos, cell, n_kv, tiles=0):
+    """single-token attention after position edits (shifted-cell score kernel): the token goes to `cell`, cells masked by the position each holds
+    (cellpos [n_ctx], -1 = free), over n_kv cells.  The caches (uint16, reference layouts) are updated in place; returns (out [H*hd], head 0's
+    probabilities [n_kv])"""
+    q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
+    rope_row = np.ascontiguousarray(rope_row, np.float32)
+    cp = np.ascontiguousarray(cellpos, np.int32).reshape(n_ctx)
+    assert k_cache.dtype == np.uint16 and v_cache_t.dtype == np.uint16 and k_cache.flags.c_contiguous and v_cache_t.flags.c_contiguous
+    assert k_cache.size == n_ctx * Hkv * hd and v_cache_t.size == n_ctx * Hkv * hd
+    out = np.zeros(H * hd, np.float32); probs = np.zeros(n_kv, np.float32)
+    _chk(lib().bamd_op_attention_cells(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope_row), _p(cp), cell, n_kv, H, Hkv, hd, n_ctx, pos, tiles,
+                                       _p(out), _p(probs)))
+    return out, probs
 
 
 def op_attention_batch(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, pos0, impl=0, ld=0):

@@ -663,26 +663,34 @@ extern "C" __attribute__((visibility("default"))) int bamd_kv_seq_div(bamd_conte
     HIPC(hipMemcpy(c->cellpos, k.pos.data(), (size_t) c->n_ctx * 4, hipMemcpyHostToDevice));
     return 0;
 }
+// the K-shift's cos / sin table (kv_update, bamd_op_k_shift): row 0 = delta 0 (the reference rotates EVERY cell, most by zero), then the distinct
+// non-zero deltas in ascending order (a context shift: one value; Self-Extend: up to one per cell); idx[cell] = the row of the cell's delta for the
+// n_cells cells (the rest of idx, up to n_idx, row 0); tab[row][hd] = rope_row of the row's delta with the rope parameters given
+static void k_shift_table(const int32_t * delta, int n_cells, int n_idx, int hd, float freq_base, float freq_scale, const float * freq_factors,
+                          float ext_factor, float attn_factor, int n_ctx_orig, std::vector<int32_t> & idx, std::vector<float> & tab) {
+    std::vector<int32_t> vals(1, 0);
+    idx.assign((size_t) n_idx, 0);
+    std::vector<int32_t> sorted(delta, delta + n_cells);
+    std::sort(sorted.begin(), sorted.end());
+    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+    for (int32_t d : sorted) if (d != 0) vals.push_back(d);
+    for (int i = 0; i < n_cells; ++i) {
+        const int32_t d = delta[i];
+        idx[(size_t) i] = d == 0 ? 0 : (int32_t) (std::lower_bound(vals.begin() + 1, vals.end(), d) - vals.begin());
+    }
+    tab.assign(vals.size() * (size_t) hd, 0.0f);
+    for (size_t j = 0; j < vals.size(); ++j)
+        rope_row(tab.data() + j * hd, vals[j], hd, freq_base, freq_scale, freq_factors, ext_factor, attn_factor, n_ctx_orig, 32.0f, 1.0f);
+}
 // llama_kv_cache_update_internal (llama.cpp:15245-15277): apply the pending K-shift to every layer's K cache, clear the deltas
 static int kv_update(bamd_context * c, hipStream_t s) {
     bamd_context::Cells & k = c->cells;
     if (!k.has_shift) return 0;
     bamd_model * m = c->m;
-    std::vector<int32_t> vals(1, 0), idx((size_t) c->n_ctx_pad, 0);     // row 0: delta 0 (the reference rotates EVERY cell, most by zero)
-    {
-        std::vector<int32_t> sorted(k.delta.begin(), k.delta.end());
-        std::sort(sorted.begin(), sorted.end());
-        sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
-        for (int32_t d : sorted) if (d != 0) vals.push_back(d);           // a context shift: one value; Self-Extend: up to one per cell
-        for (int i = 0; i < c->n_ctx; ++i) {
-            const int32_t d = k.delta[(size_t) i];
-            idx[(size_t) i] = d == 0 ? 0 : (int32_t) (std::lower_bound(vals.begin() + 1, vals.end(), d) - vals.begin());
-        }
-    }
-    std::vector<float> tab(vals.size() * (size_t) m->hd);
-    for (size_t j = 0; j < vals.size(); ++j)
-        rope_row(tab.data() + j * m->hd, vals[j], m->hd, m->rope_theta, m->rope_freq_scale, m->rope_freqs.empty() ? nullptr : m->rope_freqs.data(),
-                 m->rope_ext_factor, m->rope_attn_factor, m->rope_n_ctx_orig, 32.0f, 1.0f);   // the parameters of the context's own table (bamd_context_new)
+    std::vector<int32_t> idx;
+    std::vector<float> tab;
+    k_shift_table(k.delta.data(), c->n_ctx, c->n_ctx_pad, m->hd, m->rope_theta, m->rope_freq_scale, m->rope_freqs.empty() ? nullptr : m->rope_freqs.data(),
+                  m->rope_ext_factor, m->rope_attn_factor, m->rope_n_ctx_orig, idx, tab);   // the parameters of the context's own table (bamd_context_new)
     if (!c->shift_idx && dev_alloc(c->allocs, (void **) &c->shift_idx, (size_t) c->n_ctx_pad * 4)) return 1;
     if (!c->shift_tab) { if (dev_alloc(c->allocs, (void **) &c->shift_tab, (size_t) (c->n_ctx + 1) * m->hd * 4)) return 1; c->shift_tab_cap = c->n_ctx + 1; }
     HIPC(hipMemcpyAsync(c->shift_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
@@ -1499,21 +1507,21 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_rope_row(int pos, 
     rope_row(row, pos, n_dims, freq_base, freq_scale, freq_factors, 0.0f, 1.0f, 8192, 32.0f, 1.0f);
     return 0;
 }
-// reference layout <-> chain-major device layout of the KV cache (bamd_device.h, "Attention": kperm / vperm)
+// reference layout <-> chain-major device layout of the KV cache (bamd_device.h, "Attention": kperm / vperm); v_ref null: the K cache only
 static inline int kperm_host(int n) { const int l = n >> 3; return ((l >> 3) << 6) + ((n & 7) << 3) + (l & 7); }
 static void kv_to_device_order(const uint16_t * k_ref, const uint16_t * v_ref, int n_ctx, int n_ctx_pad, int Hkv, int hd, std::vector<uint16_t> & kd, std::vector<uint16_t> & vd) {
     const int Ekv = Hkv * hd;
-    kd.assign((size_t) n_ctx_pad * Ekv, 0); vd.assign((size_t) Ekv * n_ctx_pad, 0);
+    kd.assign((size_t) n_ctx_pad * Ekv, 0); vd.assign(v_ref ? (size_t) Ekv * n_ctx_pad : 0, 0);
     for (int i = 0; i < n_ctx; ++i) for (int h = 0; h < Hkv; ++h) for (int n = 0; n < hd; ++n)
         kd[(size_t) i * Ekv + h * hd + kperm_host(n)] = k_ref[(size_t) i * Ekv + h * hd + n];
-    for (int r = 0; r < Ekv; ++r) for (int p = 0; p < n_ctx; ++p)
+    if (v_ref) for (int r = 0; r < Ekv; ++r) for (int p = 0; p < n_ctx; ++p)
         vd[(size_t) r * n_ctx_pad + (p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3)] = v_ref[(size_t) r * n_ctx + p];
 }
 static void kv_from_device_order(uint16_t * k_ref, uint16_t * v_ref, int n_ctx, int n_ctx_pad, int Hkv, int hd, const std::vector<uint16_t> & kd, const std::vector<uint16_t> & vd) {
     const int Ekv = Hkv * hd;
     for (int i = 0; i < n_ctx; ++i) for (int h = 0; h < Hkv; ++h) for (int n = 0; n < hd; ++n)
         k_ref[(size_t) i * Ekv + h * hd + n] = kd[(size_t) i * Ekv + h * hd + kperm_host(n)];
-    for (int r = 0; r < Ekv; ++r) for (int p = 0; p < n_ctx; ++p)
+    if (v_ref) for (int r = 0; r < Ekv; ++r) for (int p = 0; p < n_ctx; ++p)
         v_ref[(size_t) r * n_ctx + p] = vd[(size_t) r * n_ctx_pad + (p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3)];
 }
 
@@ -1550,6 +1558,78 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention(const fl
         std::vector<float> pp((size_t) n_ctx_pad);
         HIPC(hipMemcpy(pp.data(), a.probs, (size_t) n_ctx_pad * 4, hipMemcpyDeviceToHost));
         for (int p = 0; p < h.n_kv; ++p) probs_h0[p] = pp[(size_t) ((p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3))];
+    }
+    return 0;
+}
+
+// the K-shift of one layer as kv_update runs it: the delta -> (cos, sin) table from k_shift_table, then bamd_launch_k_shift over the chain-major cache
+extern "C" __attribute__((visibility("default"))) int bamd_op_k_shift(uint16_t * k_cache, int n_ctx, int Hkv, int hd, const int32_t * delta, float freq_base,
+                                                                        float freq_scale, const float * freq_factors, float ext_factor, float attn_factor, int n_ctx_orig) {
+    if (need_device()) return 1;
+    if (Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0) return fail("bad K-shift shape");
+    const int Ekv = Hkv * hd, n_ctx_pad = (n_ctx + 63) / 64 * 64;
+    std::vector<int32_t> idx;
+    std::vector<float> tab;
+    k_shift_table(delta, n_ctx, n_ctx_pad, hd, freq_base, freq_scale, freq_factors, ext_factor, attn_factor, n_ctx_orig, idx, tab);
+    std::vector<uint16_t> kd, vd;
+    kv_to_device_order(k_cache, nullptr, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
+    Tmp t; const size_t kb = (size_t) n_ctx_pad * Ekv * 2;
+    unsigned short * kc = (unsigned short *) t.up(kd.data(), kb);
+    int32_t * didx = (int32_t *) t.up(idx.data(), idx.size() * 4); float * dtab = (float *) t.up(tab.data(), tab.size() * 4);
+    if (!kc || !didx || !dtab) return fail("device alloc/copy failed");
+    bamd_launch_k_shift(kc, n_ctx, Hkv, hd, didx, dtab, nullptr);
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(kd.data(), kc, kb, hipMemcpyDeviceToHost));
+    kv_from_device_order(k_cache, nullptr, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
+    return 0;
+}
+
+// the single-token attention after position edits, as bamd_stage_step sets it up when the cells are tracked: step_begin_kernel derives st->cell / st->n_kv
+// from cell_plus1 / n_kv_fixed and leaves the position's (cos, sin) row at rope_cur, the token's cellpos entry is written by a host copy behind the
+// upload of the others, and the shifted-cell instances of the three-launch path run with `tiles` score workgroups per KV head (0: the engine's count)
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention_cells(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                                                                const float * rope_row_h, const int32_t * cellpos, int cell, int n_kv, int H, int Hkv, int hd,
+                                                                                int n_ctx, int pos, int tiles, float * out, float * probs_h0) {
+    if (need_device()) return 1;
+    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || n_ctx % 32 || H % Hkv || H / Hkv > 8) return fail("bad attention shape");
+    if (pos < 0 || pos >= n_ctx || n_kv < 1 || n_kv > n_ctx || cell < 0 || cell >= n_kv || tiles < 0) return fail("bad cell / position / n_kv / tiles");
+    Tmp t; const int Ekv = Hkv * hd, n_ctx_pad = (n_ctx + 63) / 64 * 64; const size_t kvb = (size_t) n_ctx_pad * Ekv * 2;
+    std::vector<float> rope((size_t) n_ctx * hd, 0.f);
+    memcpy(rope.data() + (size_t) pos * hd, rope_row_h, (size_t) hd * 4);
+    std::vector<uint16_t> kd, vd;
+    kv_to_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
+    std::vector<int32_t> cp((size_t) n_ctx_pad, -1);                       // as kv_activate uploads cells.pos
+    memcpy(cp.data(), cellpos, (size_t) n_ctx * 4);
+    bamd_step_state h; memset(&h, 0, sizeof h);                             // as bamd_stage_step sets it for a tracked cell
+    h.pos_base = pos; h.n_ctx = n_ctx; h.cell_plus1 = cell + 1; h.n_kv_fixed = n_kv;
+    const float embd[256] = {0.0f}; const int32_t tok0 = 0;
+    bamd_attn_args a; memset(&a, 0, sizeof a);
+    bamd_step_state * st = (bamd_step_state *) t.up(&h, sizeof h); a.st = st;
+    int32_t * dcp = (int32_t *) t.up(cp.data(), cp.size() * 4); a.cellpos = dcp;
+    const int32_t * forced = (const int32_t *) t.up(&tok0, 4); int32_t * outt = (int32_t *) t.up(nullptr, 64);
+    const void * dembd = t.up(embd, sizeof embd); float * dx = (float *) t.up(nullptr, sizeof embd);
+    a.q = (float *) t.up(q, (size_t) H * hd * 4); a.k = (float *) t.up(k, (size_t) Ekv * 4); a.v = (float *) t.up(v, (size_t) Ekv * 4);
+    a.kc = (unsigned short *) t.up(kd.data(), kvb); a.vc = (unsigned short *) t.up(vd.data(), kvb);
+    a.rope = (float *) t.up(rope.data(), rope.size() * 4); float * rope_cur = (float *) t.up(nullptr, (size_t) hd * 4); a.rope_cur = rope_cur;
+    a.scores = (float *) t.up(nullptr, (size_t) H * n_ctx_pad * 4); a.probs = (float *) t.up(nullptr, (size_t) H * n_ctx_pad * 4); a.out = (float *) t.up(nullptr, (size_t) H * hd * 4);
+    if (!st || !dcp || !forced || !outt || !dembd || !dx || !a.q || !a.k || !a.v || !a.kc || !a.vc || !a.rope || !rope_cur || !a.scores || !a.probs || !a.out)
+        return fail("device alloc/copy failed");
+    HIPC(hipMemcpy(dcp + cell, &pos, 4, hipMemcpyHostToDevice));            // bamd_stage_step: cellpos[cell] = cells.pos[cell] (find_slot stored pos there)
+    bamd_launch_step_begin(st, forced, 1, outt, dembd, BAMD_F32, 256, 1, dx, 1, nullptr, nullptr, nullptr, a.rope, rope_cur, hd);
+    a.hd = hd; a.Hkv = Hkv; a.n_ctx = n_ctx_pad; a.kq_scale = 1.0f / sqrtf((float) hd); a.prefill_mode = 0;
+    if (tiles == 0) tiles = std::min(std::max(n_ctx / 64, 1), 64);         // enqueue_layers' count at the default BAMD_QK_TILES
+    if (bamd_launch_attention(a, H / Hkv, -tiles, nullptr)) return fail("unsupported head configuration");
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(out, a.out, (size_t) H * hd * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(kd.data(), a.kc, kvb, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(vd.data(), a.vc, kvb, hipMemcpyDeviceToHost));
+    kv_from_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
+    if (probs_h0) {
+        std::vector<float> pp((size_t) n_ctx_pad);
+        HIPC(hipMemcpy(pp.data(), a.probs, (size_t) n_ctx_pad * 4, hipMemcpyDeviceToHost));
+        for (int p = 0; p < n_kv; ++p) probs_h0[p] = pp[(size_t) ((p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3))];
     }
     return 0;
 }

@@ -224,6 +224,18 @@ int bamd_op_attention_batch(const float * q, const float * k, const float * v, u
                             const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld, float * out);
 /* RoPE (cos,sin) table row as built on the host for position pos (ggml_rope_cache_init, ggml.c:14017) */
 int bamd_op_rope_row(int pos, int n_dims, float freq_base, float freq_scale, const float * freq_factors, float * row);
+/* the K-shift of one layer (llama_kv_cache_update -> build_k_shift, llama.cpp:15245-15277, :8482-8512) through the engine's own table code and launch:
+ * every cell of k_cache [n_ctx][Hkv*hd] (host, reference layout, updated in place) re-rotated by delta[cell], with these rope parameters (beta_fast 32,
+ * beta_slow 1, as the context's own table); cells with delta 0 included */
+int bamd_op_k_shift(uint16_t * k_cache, int n_ctx, int Hkv, int hd, const int32_t * delta, float freq_base, float freq_scale, const float * freq_factors,
+                    float ext_factor, float attn_factor, int n_ctx_orig);
+/* single-token attention after position edits (bamd_kv_seq_add / _div): as bamd_op_attention, but the token's k / v go to cell `cell`, cellpos
+ * [n_ctx] holds the position of every cell (-1 = free; the token's own entry is set to pos here), a cell is attended when it holds a position <= pos,
+ * over the first n_kv cells; always the three-launch path with `tiles` score workgroups per KV head (0 = the engine's count).  probs_h0 (optional):
+ * [n_kv] probabilities of query head 0 */
+int bamd_op_attention_cells(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t, const float * rope_row,
+                            const int32_t * cellpos, int cell, int n_kv, int H, int Hkv, int hd, int n_ctx, int pos, int tiles, float * out,
+                            float * probs_h0);
 
 #ifdef __cplusplus
 }

@@ -438,6 +438,26 @@ float bo_vec_dot_f16(int n, const uint16_t * x, const uint16_t * y) {
 /* ======================================================================================================
  * attention of one layer for a micro-batch of T tokens at positions n_past .. n_past + T - 1
  * ====================================================================================================== */
+/* llm_build_kqv :8188-8316 for one (token, query head) over n_kv cells of KV head hk, mask[n_kv] already set (0 / -inf).
+ * kq, pr: [n_kv] scratch (pr keeps the probabilities), q16: [hd] scratch */
+static void attend_head(const float * qh, const uint16_t * k_cache, const uint16_t * v_cache_t, int Ekv, int hk, int hd, int n_ctx, int n_kv,
+                        const float * mask, int f16_scores, float kq_scale, float * out_h, float * kq, float * pr, uint16_t * q16) {
+    if (!f16_scores) {
+        /* llamafile_sgemm F16 x F32 (q stays f32 when T == 1) */
+        for (int i = 0; i < n_kv; ++i)
+            kq[i] = bo_dot_f16_f32_tinyblas(k_cache + (size_t) i * Ekv + hk * hd, qh, hd);
+    } else {
+        /* q rounded to f16 (ggml.c:12345-12372), ggml_vec_dot_f16 */
+        for (int i = 0; i < hd; ++i) q16[i] = bo_fp32_to_fp16(qh[i]);
+        for (int i = 0; i < n_kv; ++i)
+            kq[i] = bo_vec_dot_f16(hd, k_cache + (size_t) i * Ekv + hk * hd, q16);
+    }
+    bo_soft_max(kq, mask, kq_scale, pr, n_kv);
+    /* kqv = mul_mat(v^T, p): llamafile_sgemm F16 x F32 for every T (p is contiguous) */
+    for (int d = 0; d < hd; ++d)
+        out_h[d] = bo_dot_f16_f32_tinyblas(v_cache_t + (size_t)(hk * hd + d) * n_ctx, pr, n_kv);
+}
+
 void bo_attention(float * q, float * k, const float * v, const float * rope, uint16_t * k_cache, uint16_t * v_cache_t,
                   int H, int Hkv, int hd, int n_ctx, int n_past, int T, int f16_scores, float * out, int nthreads) {
     const int E = H * hd, Ekv = Hkv * hd, gq = H / Hkv;
@@ -466,24 +486,65 @@ void bo_attention(float * q, float * k, const float * v, const float * rope, uin
         for (int th = 0; th < T * H; ++th) {
             const int t = th / H, h = th % H, hk = h / gq, pos = n_past + t;
             for (int i = 0; i < n_kv; ++i) mask[i] = i <= pos ? 0.0f : -INFINITY;   /* llama_set_inputs :14152-14200 */
-            const float * qh = q + (size_t) t * E + h * hd;
-            if (!f16_scores) {
-                /* llamafile_sgemm F16 x F32 (q stays f32 when T == 1) */
-                for (int i = 0; i < n_kv; ++i)
-                    kq[i] = bo_dot_f16_f32_tinyblas(k_cache + (size_t) i * Ekv + hk * hd, qh, hd);
-            } else {
-                /* q rounded to f16 (ggml.c:12345-12372), ggml_vec_dot_f16 */
-                for (int i = 0; i < hd; ++i) q16[i] = bo_fp32_to_fp16(qh[i]);
-                for (int i = 0; i < n_kv; ++i)
-                    kq[i] = bo_vec_dot_f16(hd, k_cache + (size_t) i * Ekv + hk * hd, q16);
-            }
-            bo_soft_max(kq, mask, kq_scale, pr, n_kv);
-            /* kqv = mul_mat(v^T, p): llamafile_sgemm F16 x F32 for every T (p is contiguous) */
-            for (int d = 0; d < hd; ++d)
-                out[(size_t) t * E + h * hd + d] = bo_dot_f16_f32_tinyblas(v_cache_t + (size_t)(hk * hd + d) * n_ctx, pr, n_kv);
+            attend_head(q + (size_t) t * E + h * hd, k_cache, v_cache_t, Ekv, hk, hd, n_ctx, n_kv, mask, f16_scores, kq_scale,
+                        out + (size_t) t * E + h * hd, kq, pr, q16);
         }
         free(kq); free(pr); free(mask); free(q16);
     }
+}
+
+/* the T = 1 attention after position edits: the token at position pos goes to cell `cell` (find_slot, llama.cpp:3028-3127, has already stored
+ * pos in cellpos[cell]); llama_set_inputs masks every cell that is empty or holds a position > pos (:14152-14200; one sequence, so has_seq_id
+ * is "pos >= 0"); the attention runs over the first n_kv CELLS.  Arithmetic: bo_attention's T == 1 path.  1 = bad cell / n_kv. */
+int bo_attention_cells(float * q, float * k, const float * v, const float * rope, uint16_t * k_cache, uint16_t * v_cache_t, const int32_t * cellpos,
+                       int H, int Hkv, int hd, int n_ctx, int pos, int cell, int n_kv, float * out, float * probs_h0, int nthreads) {
+    const int Ekv = Hkv * hd, gq = H / Hkv;
+    if (cell < 0 || cell >= n_kv || n_kv > n_ctx || cellpos[cell] != pos) return 1;
+    const float kq_scale = 1.0f / sqrtf((float) hd);                     /* llama.cpp:8829 */
+    for (int h = 0; h < H; ++h)   bo_rope_apply(q + h * hd, rope, hd);   /* ggml_rope_ext :8837-8849 */
+    for (int h = 0; h < Hkv; ++h) bo_rope_apply(k + h * hd, rope, hd);
+    for (int i = 0; i < Ekv; ++i) {                                      /* llm_build_kv_store :7830-7875, at the slot's cell */
+        k_cache[(size_t) cell * Ekv + i] = bo_fp32_to_fp16(k[i]);
+        v_cache_t[(size_t) i * n_ctx + cell] = bo_fp32_to_fp16(v[i]);
+    }
+    float * mask = (float *) malloc((size_t) n_kv * 4);
+    for (int i = 0; i < n_kv; ++i) mask[i] = (cellpos[i] < 0 || cellpos[i] > pos) ? -INFINITY : 0.0f;
+#pragma omp parallel num_threads(nthreads > 0 ? nthreads : 1)
+    {
+        float * kq = (float *) malloc((size_t) n_kv * 4);
+        float * pr = (float *) malloc((size_t) n_kv * 4);
+        uint16_t * q16 = (uint16_t *) malloc((size_t) hd * 2);
+#pragma omp for schedule(dynamic)
+        for (int h = 0; h < H; ++h) {
+            attend_head(q + (size_t) h * hd, k_cache, v_cache_t, Ekv, h / gq, hd, n_ctx, n_kv, mask, 0, kq_scale, out + (size_t) h * hd, kq, pr, q16);
+            if (h == 0 && probs_h0) memcpy(probs_h0, pr, (size_t) n_kv * 4);
+        }
+        free(kq); free(pr); free(q16);
+    }
+    free(mask);
+    return 0;
+}
+
+/* build_k_shift (llama.cpp:8482-8512): ggml_rope_ext_inplace over every cell of the f16 K cache [n_ctx][Hkv*hd], positions = the cells' deltas,
+ * i.e. ggml_compute_forward_rope_f16 (ggml.c:14169-14290, NORM mode): the cache of the cell's delta (ggml_rope_cache_init), then per adjacent pair
+ * x0, x1 from f16, x0*cos - x1*sin and x0*sin + x1*cos (separate multiplies, one add each), back to f16.  Every cell, delta 0 included. */
+void bo_k_shift(uint16_t * k_cache, int n_ctx, int Hkv, int hd, const int32_t * delta, float freq_base, float freq_scale, const float * freq_factors,
+                float ext_factor, float attn_factor, int n_ctx_orig, float beta_fast, float beta_slow) {
+    const int Ekv = Hkv * hd;
+    float * cache = (float *) malloc((size_t) hd * 4);
+    for (int c = 0; c < n_ctx; ++c) {
+        bo_rope_cache(cache, delta[c], hd, freq_base, freq_scale, freq_factors, ext_factor, attn_factor, n_ctx_orig, beta_fast, beta_slow);
+        for (int h = 0; h < Hkv; ++h) {
+            uint16_t * row = k_cache + (size_t) c * Ekv + (size_t) h * hd;
+            for (int i0 = 0; i0 < hd; i0 += 2) {
+                const float cos_theta = cache[i0], sin_theta = cache[i0 + 1];
+                const float x0 = bo_fp16_to_fp32(row[i0]), x1 = bo_fp16_to_fp32(row[i0 + 1]);
+                row[i0]     = bo_fp32_to_fp16(x0 * cos_theta - x1 * sin_theta);
+                row[i0 + 1] = bo_fp32_to_fp16(x0 * sin_theta + x1 * cos_theta);
+            }
+        }
+    }
+    free(cache);
 }
 
 /* ======================================================================================================
@@ -495,6 +556,10 @@ struct bo_ctx {
     float * logits;
     float * rope;           /* [n_ctx][hd] lazily built? no: built per call */
     bo_tap_fn tap; void * tap_ud;
+    /* the cell metadata of llama_kv_cache (llama.cpp:2700-2760) for the one sequence; tracked from the first position edit on (until then cell
+     * i holds position i, which is what llama_decode's find_slot gives a caller that never edits positions) */
+    int cells_on, has_shift, head, used, n_cached;
+    int32_t * pos, * delta;
 };
 
 bo_ctx * bo_ctx_new(const bo_model * m, int n_ctx, int nthreads) {
@@ -504,14 +569,94 @@ bo_ctx * bo_ctx_new(const bo_model * m, int n_ctx, int nthreads) {
     const size_t kvn = (size_t) n_ctx * m->Hkv * m->hd;
     for (int il = 0; il < m->L; ++il) { c->k[il] = (uint16_t *) calloc(kvn, 2); c->v[il] = (uint16_t *) calloc(kvn, 2); }   /* llama.cpp:2989-3020 zero-init */
     c->logits = (float *) calloc(m->V, 4);
+    c->pos = (int32_t *) malloc((size_t) n_ctx * 4); c->delta = (int32_t *) calloc((size_t) n_ctx, 4);
     return c;
 }
 void bo_ctx_free(bo_ctx * c) {
     for (int il = 0; il < c->m->L; ++il) { free(c->k[il]); free(c->v[il]); }
-    free(c->k); free(c->v); free(c->logits); free(c);
+    free(c->k); free(c->v); free(c->logits); free(c->pos); free(c->delta); free(c);
 }
 void bo_ctx_set_tap(bo_ctx * c, bo_tap_fn fn, void * ud) { c->tap = fn; c->tap_ud = ud; }
-void bo_kv_clear(bo_ctx * c) { (void) c; /* llama_kv_cache_clear only resets cell metadata (llama.cpp:3230-3245); data stays */ }
+/* llama_kv_cache_clear only resets cell metadata (llama.cpp:3230-3245); data stays */
+void bo_kv_clear(bo_ctx * c) { c->cells_on = 0; c->has_shift = 0; c->head = 0; c->used = 0; c->n_cached = 0; }
+
+/* ---- cell metadata after position edits ---- */
+static void cells_on(bo_ctx * c) {
+    if (c->cells_on) return;
+    const int n = c->n_cached < c->n_ctx ? c->n_cached : c->n_ctx;
+    for (int i = 0; i < c->n_ctx; ++i) { c->pos[i] = i < n ? i : -1; c->delta[i] = 0; }
+    c->used = n; c->head = n >= c->n_ctx ? 0 : n;       /* llama_decode_internal: head += n_tokens, back to 0 at size (llama.cpp:14743-14748) */
+    c->has_shift = 0; c->cells_on = 1;
+}
+/* llama_kv_cache_seq_rm (llama.cpp:3154-3206), one sequence: a cell is empty once its position leaves it */
+void bo_kv_seq_rm(bo_ctx * c, int p0, int p1) {
+    cells_on(c);
+    int new_head = c->n_ctx;
+    if (p0 < 0) p0 = 0;
+    if (p1 < 0) p1 = INT32_MAX;
+    for (int i = 0; i < c->n_ctx; ++i) {
+        if (c->pos[i] >= p0 && c->pos[i] < p1) {
+            if (c->pos[i] >= 0) c->used--;
+            c->pos[i] = -1;
+            if (new_head == c->n_ctx) new_head = i;
+        }
+    }
+    if (new_head != c->n_ctx && new_head < c->head) c->head = new_head;
+}
+/* llama_kv_cache_seq_add (llama.cpp:3268-3314) */
+void bo_kv_seq_add(bo_ctx * c, int p0, int p1, int delta) {
+    cells_on(c);
+    int new_head = c->n_ctx;
+    if (p0 < 0) p0 = 0;
+    if (p1 < 0) p1 = INT32_MAX;
+    if (p0 == p1) return;
+    for (int i = 0; i < c->n_ctx; ++i) {
+        if (c->pos[i] >= 0 && c->pos[i] >= p0 && c->pos[i] < p1) {     /* has_seq_id(0) */
+            c->has_shift = 1;
+            c->pos[i] += delta;
+            c->delta[i] += delta;
+            if (c->pos[i] < 0) {
+                c->used--;
+                c->pos[i] = -1;
+                if (new_head == c->n_ctx) new_head = i;
+            }
+        }
+    }
+    c->head = new_head != c->n_ctx ? new_head : 0;
+}
+/* llama_kv_cache_seq_div (llama.cpp:3316-3349) */
+void bo_kv_seq_div(bo_ctx * c, int p0, int p1, int d) {
+    cells_on(c);
+    if (p0 < 0) p0 = 0;
+    if (p1 < 0) p1 = INT32_MAX;
+    if (p0 == p1) return;
+    for (int i = 0; i < c->n_ctx; ++i) {
+        if (c->pos[i] >= 0 && c->pos[i] >= p0 && c->pos[i] < p1) {
+            c->has_shift = 1;
+            const int32_t p_old = c->pos[i];
+            c->pos[i] /= d;
+            c->delta[i] += c->pos[i] - p_old;
+        }
+    }
+}
+/* llama_kv_cache_find_slot (llama.cpp:3079-3126) for T tokens at positions p0 ..; returns the first cell, -1 = no slot */
+static int find_slot(bo_ctx * c, int T, int p0) {
+    const int size = c->n_ctx;
+    if (T > size) return -1;
+    int n_tested = 0;
+    for (;;) {
+        if (c->head + T > size) { n_tested += size - c->head; c->head = 0; continue; }
+        int found = 1;
+        for (int i = 0; i < T; ++i) {
+            if (c->pos[c->head + i] >= 0) { found = 0; c->head += i + 1; n_tested += i + 1; break; }
+        }
+        if (found) break;
+        if (n_tested >= size) return -1;
+    }
+    for (int i = 0; i < T; ++i) c->pos[c->head + i] = p0 + i;
+    c->used += T;
+    return c->head;
+}
 const float * bo_get_logits(const bo_ctx * c) { return c->logits; }
 const uint16_t * bo_kv_k(const bo_ctx * c, int il) { return c->k[il]; }
 const uint16_t * bo_kv_v(const bo_ctx * c, int il) { return c->v[il]; }
@@ -522,7 +667,28 @@ int bo_decode(bo_ctx * c, const int32_t * tokens, int T, int n_past) {
     const bo_model * m = c->m;
     const int E = m->E, H = m->H, Hkv = m->Hkv, hd = m->hd, F = m->F, V = m->V, n_ctx = c->n_ctx, nth = c->nthreads;
     const int Ekv = Hkv * hd;
-    if (n_past + T > n_ctx) return 1;
+    int cell0 = n_past, n_kv = 0;
+    if (!c->cells_on) {
+        if (n_past + T > n_ctx) return 1;
+        if (c->n_cached < n_past + T) c->n_cached = n_past + T;
+    } else {
+        if (c->has_shift) {                                              /* llama_kv_cache_update_internal :15245-15277 */
+            for (int il = 0; il < m->L; ++il)
+                bo_k_shift(c->k[il], n_ctx, Hkv, hd, c->delta, m->rope_theta, m->rope_freq_scale, m->rope_freqs, 0.0f, 1.0f, m->n_ctx_orig, 32.0f, 1.0f);
+            c->has_shift = 0;
+            memset(c->delta, 0, (size_t) n_ctx * 4);
+        }
+        if (T > 1) {            /* a micro-batch only where find_slot puts the run at head == n_past with every cell i < used holding i */
+            if (c->head != c->used || c->used != n_past) return 1;
+            for (int i = 0; i < n_ctx; ++i) if (c->pos[i] != (i < c->used ? i : -1)) return 1;
+        }
+        if (c->head > c->used + 2 * T) c->head = 0;                      /* :14686-14688 */
+        cell0 = find_slot(c, T, n_past);
+        if (cell0 < 0) return 1;
+        int cell_max = 0;                                                /* llama_kv_cache_cell_max, :14693-14701 */
+        for (int i = n_ctx; i > 0; --i) if (c->pos[i - 1] >= 0) { cell_max = i; break; }
+        n_kv = (cell_max + 31) / 32 * 32; if (n_kv < 32) n_kv = 32; if (n_kv > n_ctx) n_kv = n_ctx;
+    }
 
     float * x    = (float *) malloc((size_t) T * E * 4);                 /* residual stream inpL */
     float * cur  = (float *) malloc((size_t) T * E * 4);
@@ -555,7 +721,9 @@ int bo_decode(bo_ctx * c, const int32_t * tokens, int T, int n_past) {
         bo_mul_mat_q(ly->tv, ly->wv, Ekv, E, cur, T, vv, nth);
         TAP("Vcur", il, vv, (size_t) T * Ekv);
         /* ggml_rope_ext :8837-8849, llm_build_kv_store :7830-7875, llm_build_kqv :8188-8316 (q / k roped in place) */
-        bo_attention(q, kk, vv, rc, c->k[il], c->v[il], H, Hkv, hd, n_ctx, n_past, T, T > 1, att, nth);
+        if (c->cells_on && T == 1)                                       /* the mask by the position each cell holds, :14152-14200 */
+            bo_attention_cells(q, kk, vv, rc, c->k[il], c->v[il], c->pos, H, Hkv, hd, n_ctx, n_past, cell0, n_kv, att, NULL, nth);
+        else bo_attention(q, kk, vv, rc, c->k[il], c->v[il], H, Hkv, hd, n_ctx, n_past, T, T > 1, att, nth);
         TAP("Qcur", il, q, (size_t) T * E);
         TAP("Kcur", il, kk, (size_t) T * Ekv);
         TAP("kqv_merged_cont", il, att, (size_t) T * E);
@@ -596,5 +764,6 @@ int bo_decode(bo_ctx * c, const int32_t * tokens, int T, int n_past) {
         TAP("result_output", -1, c->logits, V);
     }
     free(x); free(cur); free(q); free(kk); free(vv); free(att); free(ffi); free(g); free(u); free(rc);
+    if (c->cells_on) { c->head = cell0 + T; if (c->head >= n_ctx) c->head = 0; }   /* :14743-14748 */
     return 0;
 }

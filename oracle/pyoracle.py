@@ -67,10 +67,17 @@ def lib():
         L.bo_vec_dot_f16.restype = C.c_float; L.bo_vec_dot_f16.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
         L.bo_attention.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.bo_attention_cells.restype = C.c_int
+        L.bo_attention_cells.argtypes = [C.c_void_p] * 7 + [C.c_int] * 7 +[C.c_void_p, C.c_void_p, C.c_int]
+        L.bo_k_shift.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_float, C.c_float,
+                                 C.c_int, C.c_float, C.c_float]
         L.bo_ctx_new.restype = C.c_void_p; L.bo_ctx_new.argtypes = [C.POINTER(BoModel), C.c_int, C.c_int]
         L.bo_ctx_free.argtypes = [C.c_void_p]
         L.bo_ctx_set_tap.argtypes = [C.c_void_p, TAP_FN, C.c_void_p]
         L.bo_kv_clear.argtypes = [C.c_void_p]
+        L.bo_kv_seq_rm.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.bo_kv_seq_add.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.bo_kv_seq_div.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.bo_decode.restype = C.c_int; L.bo_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.bo_get_logits.restype = C.POINTER(C.c_float); L.bo_get_logits.argtypes = [C.c_void_p]
         L.bo_kv_k.restype = C.POINTER(C.c_uint16); L.bo_kv_k.argtypes = [C.c_void_p, C.c_int]
@@ -158,6 +165,35 @@ def attention(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, n_past, f16_
     return out
 
 
+def attention_cells(q, k, v, k_cache, v_cache_t, rope_row, cellpos, H, Hkv, hd, n_ctx, pos, cell, n_kv, nthreads=None):
+    """bo_attention_cells: ONE token at position pos stored in `cell`, attention over the first n_kv cells masked by the position each holds
+    (cellpos [n_ctx], -1 = free; the token's own entry is set to pos here, as find_slot does).  The caches (uint16, reference layouts) are
+    updated in place.  Returns (out [H*hd], query head 0's probabilities [n_kv])."""
+    q = np.array(q, np.float32).reshape(H * hd); k = np.array(k, np.float32).reshape(Hkv * hd)
+    v = np.ascontiguousarray(v, np.float32).reshape(Hkv * hd); rope_row = np.ascontiguousarray(rope_row, np.float32).reshape(hd)
+    cp = np.array(cellpos, np.int32).reshape(n_ctx)
+    cp[cell] = pos
+    assert k_cache.dtype == np.uint16 and v_cache_t.dtype == np.uint16 and k_cache.flags.c_contiguous and v_cache_t.flags.c_contiguous
+    assert k_cache.size == n_ctx * Hkv * hd and v_cache_t.size == n_ctx * Hkv * hd
+    out = np.zeros(H * hd, np.float32); probs = np.zeros(n_kv, np.float32)
+    rc = lib().bo_attention_cells(_p(q), _p(k), _p(v), _p(rope_row), _p(k_cache), _p(v_cache_t), _p(cp), H, Hkv, hd, n_ctx, pos, cell, n_kv,
+                                  _p(out), _p(probs), nthreads or min(16, os.cpu_count() or 1))
+    assert rc == 0, "bo_attention_cells: bad cell / n_kv"
+    return out, probs
+
+
+def k_shift(k_cache, n_ctx, Hkv, hd, delta, freq_base, freq_scale=1.0, freq_factors=None, ext_factor=0.0, attn_factor=1.0, n_ctx_orig=8192,
+            beta_fast=32.0, beta_slow=1.0):
+    """bo_k_shift: a COPY of the f16 K cache [n_ctx*Hkv*hd] (uint16, reference layout) with every cell re-rotated by delta[cell]"""
+    kc = np.array(k_cache, np.uint16).reshape(-1)
+    assert kc.size == n_ctx * Hkv * hd
+    d = np.ascontiguousarray(delta, np.int32).reshape(n_ctx)
+    ff = None if freq_factors is None else np.ascontiguousarray(freq_factors, np.float32)
+    lib().bo_k_shift(_p(kc), n_ctx, Hkv, hd, _p(d), freq_base, freq_scale, None if ff is None else _p(ff), ext_factor, attn_factor, n_ctx_orig,
+                     beta_fast, beta_slow)
+    return kc
+
+
 # ---- whole model -----------------------------------------------------------------------------------------
 class OracleModel:
     """Builds a bo_model from a booster_amd.gguf.GGUFReader (tensor bytes stay mapped)."""
@@ -230,6 +266,26 @@ class OracleContext:
         rc = lib().bo_decode(self.c, _p(t), t.size, n_past)
         assert rc == 0, "bo_decode failed"
         return np.ctypeslib.as_array(lib().bo_get_logits(self.c), shape=(self.model.V,)).copy()
+
+    def kv_seq_rm(self, p0, p1):
+        """llama_kv_cache_seq_rm(ctx, 0, p0, p1)"""
+        lib().bo_kv_seq_rm(self.c, int(p0), int(p1))
+
+    def kv_seq_add(self, p0, p1, delta):
+        """llama_kv_cache_seq_add(ctx, 0, p0, p1, delta)"""
+        lib().bo_kv_seq_add(self.c, int(p0), int(p1), int(delta))
+
+    def kv_seq_div(self, p0, p1, d):
+        """llama_kv_cache_seq_div(ctx, 0, p0, p1, d)"""
+        assert d >= 1
+        lib().bo_kv_seq_div(self.c, int(p0), int(p1), int(d))
+
+    def context_shift(self, n_keep, n_past):
+        """Booster's context shift (cpp/bridge.cpp:487-503); returns the new n_past"""
+        n_discard = (n_past - n_keep) // 2
+        self.kv_seq_rm(n_keep, n_keep + n_discard)
+        self.kv_seq_add(n_keep + n_discard, n_past, -n_discard)
+        return n_past - n_discard
 
     def kv_k(self, il):
         n = self.n_ctx * self.model.Hkv * self.model.hd

@@ -8,6 +8,7 @@ prompt tok[i] = (7919 i + 13) mod V, greedy.  What is committed is DATA ONLY: ar
 logit and a 64-bit digest of all logits per step (tests/golden/fullsize_<cfg>.bgld, a few KB each).
 
     python tests/golden/gen_fullsize_fixtures.py [cfg ...]      cfg in: 8b 8b_prefill2048 70b_stage 70b_full m7q6k_8k shift selfextend yarn l2_7b l32_3b
+                                                                             shift_hd128 selfextend_gq8 shift_yarn
 """
 import hashlib
 import os
@@ -44,8 +45,14 @@ CONFIGS = {
     # query heads per KV head, rope_freqs, and NO output.weight — lm_head runs on the Q6_K token_embd (tied embeddings, llama.cpp:6070-6076)
     "l2_7b": (dict(E=4096, H=32, Hkv=32, L=32, F=11008, V=32000, theta=10000.0, n_ctx_train=4096), 64, 64, 256),
     "l32_3b": (dict(E=3072, H=24, Hkv=8, L=28, F=8192, V=128256, theta=500000.0, rope_freqs=True, tied=True, embd_type=Q6), 64, 64, 256),
+    # the shifted path at real head sizes: head_dim 128 with rope_freqs in the K-shift, shifts past 448 positions (three-launch attention before
+    # and after them); gq 8 x head_dim 128 under Self-Extend (ga_n 4, ga_w 64: many distinct deltas); the K-shift under YaRN (ext_factor 1,
+    # attn_factor 1.25: even the zero-delta cells are scaled by mscale)
+    "shift_hd128": (dict(E=1024, H=8, Hkv=2, L=2, F=768, V=512, theta=500000.0, rope_freqs=True), 300, 700, 640),
+    "selfextend_gq8": (dict(E=1024, H=8, Hkv=1, L=2, F=768, V=512, theta=500000.0), 40, 200, 256),
+    "shift_yarn": (dict(E=512, H=8, Hkv=2, L=3, F=768, V=512, theta=10000.0, n_ctx_train=256, rope_scaling=dict(type="yarn", factor=4.0, orig_ctx=64, attn_factor=1.25)), 40, 150, 96),
 }
-N_KEEP = {"shift": 8, "selfextend": -216}
+N_KEEP = {"shift": 8, "selfextend": -216, "shift_hd128": 4, "selfextend_gq8": -464, "shift_yarn": 8}
 
 
 def type_fn_of(tag, L):
