@@ -11,6 +11,7 @@
 #include "bamd_gguf.h"
 #include "bamd_kernels.h"
 #include "bamd_aql.h"
+#include "bamd_engine_internal.h"
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -25,7 +26,7 @@
 #include <string>
 #include <vector>
 
-static thread_local std::string g_err;
+thread_local std::string g_err;
 // BAMD_PREFILL_BATCH=0: evaluate prompts token by token through the decode kernels instead of the batched kernels (same bits)
 static int g_prefill_batch = [] { const char * e = getenv("BAMD_PREFILL_BATCH"); return (e && e[0] == '0') ? 0 : 1; }();
 // BAMD_PREFILL_MFMA=0: Q4_K mat-muls of the batched prefill on the integer-dot kernel instead of the MFMA kernel (same bits)
@@ -37,25 +38,12 @@ static const int g_prefill_aux = [] { const char * e = getenv("BAMD_PREFILL_AUX"
 // BAMD_STAGE_GRAPH=0: bamd_stage_step enqueues its kernels one by one instead of replaying a captured hipGraph
 static const int g_stage_graph = [] { const char * e = getenv("BAMD_STAGE_GRAPH"); return (e && e[0] == '0') ? 0 : 1; }();
 static const bool g_attn_fused = [] { const char * e = getenv("BAMD_ATTN_FUSED"); return !(e && e[0] == '0'); }();   // default: fused single-launch attention (BAMD_ATTN_FUSED=0: three-kernel path)
-static int fail(const std::string & m) { g_err = m; return 1; }
 // BAMD_AQL=0: the device-side greedy loop replays one hipGraph per step on the context's HIP stream (rounds 1-5) instead of AQL packets with fence scope
 // NONE on the library's own queue (bamd_aql.h).  Same kernels, same bits; BAMD_AQL_VERBOSE=1 says why when the own queue is not used
 static int g_aql = [] { const char * e = getenv("BAMD_AQL"); return (e && e[0] == '0') ? 0 : 1; }();
 extern "C" __attribute__((visibility("default"))) void bamd_set_aql(int on) { g_aql = on ? 1 : 0; }
-#define HIPC(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return 1; } } while (0)
-#define HIPP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return nullptr; } } while (0)
 
 extern "C" __attribute__((visibility("default"))) const char * bamd_last_error(void) { return g_err.c_str(); }
-
-// owners for the short-lived HIP objects of the measurement entry points (an early error return must not leak them)
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-    hipError_t create() { hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
-};
-struct OwnedStream { hipStream_t s = nullptr; ~OwnedStream() { if (s) hipStreamDestroy(s); } };
-struct OwnedDevMem { void * p = nullptr; ~OwnedDevMem() { if (p) hipFree(p); } };
-struct OwnedGraphExec { hipGraphExec_t g = nullptr; ~OwnedGraphExec() { if (g) hipGraphExecDestroy(g); } };
 
 // -------------------------------------------------------------------------------------------------------
 // RoPE table on the host — ggml_rope_cache_init / rope_yarn / ggml_rope_yarn_corr_dims (ggml.c:13994-14041).
@@ -68,7 +56,7 @@ static float rope_yarn_ramp(const float low, const float high, const int i0) {
 static float rope_corr_dim(int n_dims, int n_ctx_orig, float n_rot, float base) {
     return n_dims * logf(n_ctx_orig / (n_rot * 2 * (float) M_PI)) / (2 * logf(base));
 }
-static void rope_row(float * cache, int32_t pos, int n_dims, float freq_base, float freq_scale, const float * freq_factors,
+void rope_row(float * cache, int32_t pos, int n_dims, float freq_base, float freq_scale, const float * freq_factors,
                      float ext_factor, float attn_factor, int n_ctx_orig, float beta_fast, float beta_slow) {
     const float theta_scale = powf(freq_base, -2.0f / n_dims);
     float corr_dims[2];
@@ -106,7 +94,7 @@ struct DevMat {                      // one quantised matrix resident in HBM
 struct DevLayer {
     float * attn_norm = nullptr, * ffn_norm = nullptr;
     DevMat wq, wk, wv, wo, wg, wu, wd;
-    // prefill side tables (bamd_prefill2.hip), built at the first batched evaluation: one per QKV segment as enqueue_prefill_batch merges them, wo, gate, up, down
+    // prefill side tables (bamd_prefill2.hip), built at model load (build_prefill_aux): one per QKV segment (qkv_segments), wo, gate, up, down
     void * aux_qkv[3] = { nullptr, nullptr, nullptr }, * aux_o = nullptr, * aux_g = nullptr, * aux_u = nullptr, * aux_d = nullptr;
 };
 
@@ -128,6 +116,20 @@ struct bamd_model {
     bool aux_ok = false; int64_t aux_bytes = 0; std::string aux_why;      // prefill side tables: all matrices or none (build_prefill_aux)
 };
 
+// ---- one cached replay of "the fixed launch sequence of one step", rebuilt when, and only when, the key of the step at hand differs from the one it was built for.
+// The key is everything a sequence is recorded with: which attention kernels it holds (attn_path) and, for the stage graphs, the pointers it was captured with
+enum AttnPath { ATTN_SPLIT = 0, ATTN_SINGLE = 1, ATTN_CELLS = 2 };   // scores | softmax | P.V;  single-launch kernel;  the split path's shifted-cell kernels (+ slot table)
+struct ReplayKey {
+    AttnPath path = ATTN_SPLIT;
+    const void * token_src = nullptr, * hin = nullptr, * hout = nullptr;        // stage graphs only
+    bool operator==(const ReplayKey & o) const { return path == o.path && token_src == o.token_src && hin == o.hin && hout == o.hout; }
+};
+struct StepReplay {                  // EITHER a hipGraph (capture_graph) OR packets for the library's own queue (record_aql), and the key it was built for
+    hipGraphExec_t exec = nullptr; bamd_aql_graph * aql = nullptr; ReplayKey key;
+    void reset() { if (exec) hipGraphExecDestroy(exec); if (aql) bamd_aql_free(aql); exec = nullptr; aql = nullptr; }
+    void reset_unless(const ReplayKey & k) { if (!(key == k)) reset(); }
+};
+
 struct bamd_context {
     bamd_model * m = nullptr;
     int n_ctx = 0;
@@ -147,9 +149,10 @@ struct bamd_context {
     int32_t * forced = nullptr; int forced_cap = 0;
     int32_t * out_tokens = nullptr; int out_cap = 0;
     hipStream_t stream = nullptr;
-    hipGraphExec_t graph = nullptr; int graph_fused = -1;
-    bamd_aql_graph * aql = nullptr; int aql_key = -1; bool aql_failed = false; int aql_runs = 0;    // the same step as AQL packets for the own queue (bamd_aql.h)
-    bamd_aql_graph * aql_step = nullptr; int aql_step_key = -1; int aql_steps = 0;                 // bamd_stage_step's single-token step on the own queue
+    // every replay of this context: the greedy loop's step as a hipGraph and as packets for the own queue, bamd_stage_step's single host-fed token on the own queue, its stage graphs [want_logits][prefill_mode]
+    StepReplay greedy_graph, greedy_aql, step_aql, stage_graph[2][2];
+    bool aql_failed = false;                     // sticky: a recording of this context could not be turned into packets, both own-queue users stay on their hipGraphs
+    int aql_runs = 0, aql_steps = 0;             // bamd_generate_greedy calls / single-token steps that ran on the own queue (bamd_aql_runs)
     bamd_step_state * inbox = nullptr;           // pinned host memory: the state of that step, read by step_begin_kernel itself (no copy in front of the step)
     unsigned long long * co_gran = nullptr;   // co-launch granules [H * hd] {value, tag} + give-up counter behind them (bamd_colaunch.hip), zero-initialised
     uint32_t * co_err = nullptr;
@@ -161,12 +164,9 @@ struct bamd_context {
     int n_cached = 0;               // positions evaluated so far (highest n_past + n_tokens seen): what the cells hold when tracking starts
     int32_t * cellpos = nullptr;    // device copy of cells.pos (attention mask of the shifted path)
     int32_t * shift_idx = nullptr; float * shift_tab = nullptr; int shift_tab_cap = 0;
-    // stage-step graphs (bamd_stage_step): one per (want_logits, prefill_mode), valid for the pointers it was captured with
-    struct StageGraph { hipGraphExec_t exec = nullptr; const void * token_src = nullptr, * hin = nullptr; void * hout = nullptr; int fused = -1; };
-    StageGraph sgraph[2][2];
-    // batched prefill buffers, [bcap] tokens each (allocated at the first multi-token decode)
     // phase-stamp blocks (bamd_timeline_step, BAMD_TIMING builds): one block of BAMD_TL_SLOT_WORDS u64 per launch
     unsigned long long * tl_base = nullptr; int tl_slot = 0, tl_cap = 0;
+    // batched prefill buffers, [bcap] tokens each (allocated at the first multi-token decode)
     int bcap = 0;
     float * attn_bscr = nullptr; size_t attn_bscr_bytes = 0, attn_bscr_failed = 0;   // score rows of the matrix-core prefill attention beyond BAMD_AM_MAXPOS = 512 positions (grow-only; absent = the VALU kernel runs)
     float * bx = nullptr, * bx2 = nullptr, * bqkv = nullptr, * batt = nullptr, * bh = nullptr; unsigned char * bblob = nullptr, * bblob16 = nullptr;
@@ -414,6 +414,11 @@ static int context_init(bamd_context * c, bamd_model * m, int n_ctx) {
     return 0;
 }
 
+// every replay of the context is void.  For the rare events that change what a sequence was built with beyond its key (cell tracking on / off, a new slot table), never per token
+static void drop_replays(bamd_context * c) {
+    c->greedy_graph.reset(); c->greedy_aql.reset(); c->step_aql.reset();
+    for (auto & row : c->stage_graph) for (StepReplay & r : row) r.reset();
+}
 extern "C" __attribute__((visibility("default"))) bamd_context * bamd_context_new(bamd_model * m, int n_ctx) {
     bamd_context * c = new bamd_context();
     if (context_init(c, m, n_ctx)) { bamd_context_free(c); return nullptr; }
@@ -422,10 +427,8 @@ extern "C" __attribute__((visibility("default"))) bamd_context * bamd_context_ne
 extern "C" __attribute__((visibility("default"))) void bamd_context_free(bamd_context * c) {
     if (!c) return;
     if (c->m) hipSetDevice(c->m->device);
-    if (c->graph) hipGraphExecDestroy(c->graph);
-    bamd_aql_free(c->aql); bamd_aql_free(c->aql_step);
+    drop_replays(c);
     if (c->inbox) hipHostFree(c->inbox);
-    for (auto & row : c->sgraph) for (auto & g : row) if (g.exec) hipGraphExecDestroy(g.exec);
     for (void * p : c->allocs) hipFree(p);
     if (c->logits_host) hipHostFree(c->logits_host);
     if (c->attn_bscr) hipFree(c->attn_bscr);
@@ -457,6 +460,20 @@ static unsigned long long * tl_next(bamd_context * c) {
     return c->tl_base + (size_t) (c->tl_slot++) * BAMD_TL_SLOT_WORDS;
 }
 static void seg_of(bamd_mv_seg & sg, const DevMat & d, float * out) { sg.w = d.stream; sg.out = out; sg.type = d.type; sg.nrows = d.nrows_pad; sg.nvalid = d.nrows; }
+// wq | wk | wv share one allocation and their outputs are contiguous (q | k | v from `out`): equal-typed neighbours are ONE segment, one weight stream.  The only place that rule is written down: the decode step,
+// the batched prefill and the prefill side tables (DevLayer::aux_qkv) take their segments from here.  nrows / nvalid: as seg_of counts the first matrix + the GGUF rows of each one merged into it; rows_pad: stream rows
+static int qkv_segments(const DevLayer & ly, float * out, bamd_mv_seg sg[3], int rows_pad[3] = nullptr) {
+    const DevMat * mats[3] = { &ly.wq, &ly.wk, &ly.wv };
+    int n = 0, off = 0, pad[3];
+    for (int j = 0; j < 3; ++j) {
+        const DevMat & d = *mats[j];
+        if (j && d.type == mats[j - 1]->type) { sg[n - 1].nrows += d.nrows; sg[n - 1].nvalid += d.nrows; pad[n - 1] += d.nrows_pad; }
+        else { seg_of(sg[n], d, out ? out + off : nullptr); pad[n++] = d.nrows_pad; }
+        off += d.nrows;
+    }
+    if (rows_pad) memcpy(rows_pad, pad, sizeof pad);
+    return n;
+}
 
 // enqueue the layers of this stage for the token whose hidden state is in c->x; leaves the result in c->x
 // pos_hi: the highest position this enqueue (or every replay of the graph being captured) will see.  The single-launch attention
@@ -464,6 +481,7 @@ static void seg_of(bamd_mv_seg & sg, const DevMat & d, float * out) { sg.w = d.s
 // 1.85 ms/token at 240, equal at 440, 2.06 vs 1.88 at 740) at any n_ctx (its LDS score rows are sized by the sequence bound, not by n_ctx); longer sequences take the
 // three-kernel path, whose cost is nearly flat up to a few thousand positions.
 static bool attn_fused_for(const bamd_context * c, int pos_hi) { return g_attn_fused && pos_hi < 448 && !c->cells.active; }   // shifted cells: three-launch path (attn_qk_kernel<.., SH>)
+static AttnPath attn_path(const bamd_context * c, int pos_hi) { return attn_fused_for(c, pos_hi) ? ATTN_SINGLE : c->cells.active ? ATTN_CELLS : ATTN_SPLIT; }
 // LDS row length of the single-launch / batched attention kernels for sequences up to position pos_hi: a multiple of 64, independent of n_ctx
 static int attn_lds_ld(const bamd_context * c, int pos_hi) { return std::min((pos_hi + 1 + 63) / 64 * 64, c->n_ctx_pad); }
 static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, StepTimer * tm, int pos_hi) {
@@ -475,11 +493,7 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
         const DevLayer & ly = m->layers[il];
         bamd_mv_args a; memset(&a, 0, sizeof a);
         // 1. q,k,v = W{q,k,v} . Q8_K(rms_norm(x) * attn_norm)          (llama.cpp:8810-8835)
-        seg_of(a.seg[0], ly.wq, c->q); a.nseg = 1;
-        if (ly.wk.type == ly.wq.type) { a.seg[0].nrows += ly.wk.nrows; a.seg[0].nvalid += ly.wk.nrows; }   // streams and outputs are contiguous: extend
-        else { seg_of(a.seg[a.nseg], ly.wk, c->k); a.nseg++; }
-        if (ly.wv.type == ly.wk.type) { a.seg[a.nseg - 1].nrows += ly.wv.nrows; a.seg[a.nseg - 1].nvalid += ly.wv.nrows; }
-        else { seg_of(a.seg[a.nseg], ly.wv, c->v); a.nseg++; }
+        a.nseg = qkv_segments(ly, c->q, a.seg);
         a.x = c->x; a.normw = ly.attn_norm; a.eps = m->eps; a.K = m->E; a.tl = tl_next(c);
         if (tm) tm->begin(s, 0, (double) (ly.wq.bytes + ly.wk.bytes + ly.wv.bytes));
         bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_STORE, m->n_cu, s);
@@ -487,11 +501,10 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
         // 2. RoPE, KV store, softmax(QK^T) V                               (llama.cpp:8837-8849, :8318-8353)
         bamd_attn_args t; memset(&t, 0, sizeof t);
         t.st = c->st; t.q = c->q; t.k = c->k; t.v = c->v; t.kc = c->kc[il]; t.vc = c->vc[il]; t.rope = c->rope; t.rope_cur = c->rope_cur; t.scores = c->scores; t.probs = c->probs; t.out = c->att;
-        t.n_ctx = c->n_ctx_pad; t.hd = m->hd; t.Hkv = m->Hkv;
+        t.hd = m->hd; t.Hkv = m->Hkv; t.n_ctx = c->n_ctx_pad; t.kq_scale = 1.0f / sqrtf((float) m->hd); t.prefill_mode = prefill_mode;
         // the probability rows in global memory are the data path of the softmax | P.V PAIR only (score rows beyond the LDS); the one-launch softmax + P.V keeps them in
         // LDS and wrote them out for the tests' sake — 2 x 31 KB of stores by sixteen of its workgroups, the ones the launch then ended with
         if (bamd_attention_split_is_ik_clean(t, m->H / m->Hkv)) t.probs = nullptr;
-        t.hd = m->hd; t.Hkv = m->Hkv; t.n_ctx = c->n_ctx_pad; t.kq_scale = 1.0f / sqrtf((float) m->hd); t.prefill_mode = prefill_mode;
         // single-launch kernel below 448 positions, three kernels (scores | softmax | P.V) above (attn_fused_for)
         t.lds_ld = std::min(512, c->n_ctx_pad);               // single-launch kernel only (sequences < 448 positions): constant, so captured graphs stay valid as pos advances
         t.cellpos = c->cells.active ? c->cellpos : nullptr;
@@ -548,6 +561,8 @@ static void enqueue_begin(bamd_context * c, int n_forced, int do_embed, hipStrea
                            with_slots ? c->slots : nullptr, with_slots ? c->cellpos : nullptr, c->rope, c->rope_cur, m->hd);
 }
 
+static int enqueue_step(bamd_context * c, hipStream_t s, int pos_hi) { const int rc = enqueue_layers(c, 0, s, nullptr, pos_hi); enqueue_lm_head(c, s, nullptr); return rc; }   // a whole single-stage step behind its step_begin launch
+
 // The tag of a granule hand-over (bamd_colaunch.hip) is (host serial : 12, device step : 12, layer : 8); a word must never already hold the tag a
 // consumer is about to wait for.  The serial runs 1 .. 0xffe (0 is what zero-initialised granules carry, 0xfff is reserved) and every time it wraps ALL granule
 // vectors of the context are overwritten with 0xff bytes — tag 0xffffffff, which no launch produces — in stream order ahead of the launch that reuses serial 1
@@ -571,6 +586,41 @@ static int set_state(bamd_context * c, int pos_base, hipStream_t s, bool keep_ke
     return 0;
 }
 
+// May a step with this attention path run as AQL packets on the library's own queue (bamd_aql.h)?  Only the launch sequences whose kernels keep the inter-kernel rules of bamd_device.h: the single-launch
+// attention path, and the scores | softmax + P.V path of long sequences when its kernels are the clean ones; anything else (shifted cells, score rows beyond the LDS) replays a hipGraph
+static bool aql_allowed(const bamd_context * c, AttnPath path) {
+    if (!g_aql || c->aql_failed || path == ATTN_CELLS) return false;
+    if (path == ATTN_SINGLE) return true;
+    const bamd_model * m = c->m;
+    bamd_attn_args t; memset(&t, 0, sizeof t); t.hd = m->hd; t.Hkv = m->Hkv; t.n_ctx = c->n_ctx_pad;
+    return bamd_attention_split_is_ik_clean(t, m->H / m->Hkv) != 0;
+}
+// enqueue() issues the step's launches while the launchers record instead of launching (BAMD_LAUNCH); the recording becomes packets.  nullptr: this context leaves the own queue alone from here on
+template <typename F> static bamd_aql_graph * record_aql(bamd_context * c, F enqueue) {
+    bamd_aql_recording rec;
+    bamd_aql_rec = &rec;
+    const int rc = enqueue();
+    bamd_aql_rec = nullptr;
+    const char * why = "recording failed";
+    bamd_aql_graph * g = rc ? nullptr : bamd_aql_build(c->m->device, rec, &why);
+    if (!g) { c->aql_failed = true; if (getenv("BAMD_AQL_VERBOSE")) fprintf(stderr, "bamd: own AQL queue not used: %s\n", why ? why : "?"); }
+    return g;
+}
+// enqueue() issues the launches on `s` under stream capture; the graph is instantiated into *exec.  what: the error texts of a failed capture / instantiation (ending in ": ": + the HIP error string)
+struct CaptureTexts { const char * capture, * instantiate; };
+static int capture_fail(const char * text, hipError_t e) { return fail(std::string(text) + (text[strlen(text) - 1] == ' ' ? hipGetErrorString(e) : "")); }
+template <typename F> static int capture_graph(hipStream_t s, F enqueue, hipGraphExec_t * exec, const CaptureTexts & what) {
+    hipGraph_t g = nullptr;
+    HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    hipError_t e = hipStreamEndCapture(s, &g);
+    if (rc || e != hipSuccess) { if (g) hipGraphDestroy(g); return rc ? rc : capture_fail(what.capture, e); }
+    e = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+    hipGraphDestroy(g);
+    if (e != hipSuccess) { *exec = nullptr; return capture_fail(what.instantiate, e); }
+    return 0;
+}
+
 // ---- KV cell bookkeeping after position edits (llama_kv_cache_seq_rm / _seq_add / find_slot / update) ------------------------------------
 // The reference keeps, per cache cell, the position it holds and a pending rotation delta (llama.cpp:2700-2760).  As long as nobody edits
 // positions, cell i holds position i and nothing is tracked here.  Booster's context shift (cpp/bridge.cpp:487-503) is
@@ -586,8 +636,7 @@ static void kv_try_deactivate(bamd_context * c) {
     if (k.head != (k.used >= c->n_ctx ? 0 : k.used)) return;
     k.active = false;
     c->n_cached = k.used;
-    if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
-    for (auto & row : c->sgraph) for (auto & g : row) if (g.exec) { hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+    drop_replays(c);
 }
 static int kv_activate(bamd_context * c) {
     // cell metadata is edited on the host and copied with blocking copies: nothing of this context may be in flight (the caller's stage
@@ -604,7 +653,7 @@ static int kv_activate(bamd_context * c) {
     memcpy(h.data(), k.pos.data(), (size_t) c->n_ctx * 4);
     HIPC(hipMemcpy(c->cellpos, h.data(), h.size() * 4, hipMemcpyHostToDevice));
     k.active = true;
-    if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
+    drop_replays(c);
     return 0;
 }
 extern "C" __attribute__((visibility("default"))) int bamd_kv_seq_rm(bamd_context * c, int p0, int p1) {     // llama_kv_cache_seq_rm(ctx, 0, p0, p1): llama.cpp:3150-3217
@@ -666,7 +715,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_kv_seq_div(bamd_conte
 // the K-shift's cos / sin table (kv_update, bamd_op_k_shift): row 0 = delta 0 (the reference rotates EVERY cell, most by zero), then the distinct
 // non-zero deltas in ascending order (a context shift: one value; Self-Extend: up to one per cell); idx[cell] = the row of the cell's delta for the
 // n_cells cells (the rest of idx, up to n_idx, row 0); tab[row][hd] = rope_row of the row's delta with the rope parameters given
-static void k_shift_table(const int32_t * delta, int n_cells, int n_idx, int hd, float freq_base, float freq_scale, const float * freq_factors,
+void k_shift_table(const int32_t * delta, int n_cells, int n_idx, int hd, float freq_base, float freq_scale, const float * freq_factors,
                           float ext_factor, float attn_factor, int n_ctx_orig, std::vector<int32_t> & idx, std::vector<float> & tab) {
     std::vector<int32_t> vals(1, 0);
     idx.assign((size_t) n_idx, 0);
@@ -722,10 +771,7 @@ static int kv_find_slot(bamd_context * c, int pos, int * cell, int * n_kv) {
     return 0;
 }
 
-extern "C" int bamd_stage_step(bamd_context * c, int32_t token, const void * token_dev, int pos, const void * hidden_in_dev, void * hidden_out_dev, int want_logits,
-                               int prefill_mode, void * hip_stream);
 // ---- batched prefill: a micro-batch of T > 1 tokens through the layers at once (llama_decode with n_tokens > 1) -----------
-#define BAMD_PREFILL_CAP 512            /* the reference's default n_batch / n_ubatch */
 // pos_hi: last position of the micro-batch — its score rows (2 x padded length floats per head) must fit the LDS: 18 432 positions
 static bool prefill_batch_supported(const bamd_context * c, int pos_hi) {
     const bamd_model * m = c->m;
@@ -740,18 +786,16 @@ static bool prefill_batch_supported(const bamd_context * c, int pos_hi) {
 }
 // prefill side tables of every layer matrix (bamd_prefill2.hip), built at model load (round 6; round 5 built them lazily inside the first batched evaluation — a
 // multi-gigabyte allocation after the contexts existed, and a partial failure mixed kernel generations: ADVICE r5).  The QKV segments are the ones
-// enqueue_prefill_batch forms (equal-typed neighbours of the fused wq | wk | wv stream merge into one matrix).  All or nothing.
+// enqueue_prefill_batch launches (qkv_segments).  All or nothing.
 static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     if (!g_prefill_aux) { m->aux_why = "switched off (BAMD_PREFILL_AUX=0)"; return; }
     if (!bamd_prefill_mfma_supported()) { m->aux_why = "the device refuses the matrix-core kernels' LDS size"; return; }
     struct Item { const void * w; int type, nrows, K; void ** slot; };
     std::vector<Item> items;
     for (DevLayer & ly : m->layers) {
-        struct Seg { const void * w; int type, nrows; } seg[3]; int n = 1;
-        seg[0] = { ly.wq.stream, ly.wq.type, ly.wq.nrows_pad };
-        if (ly.wk.type == ly.wq.type) seg[0].nrows += ly.wk.nrows_pad; else seg[n++] = { ly.wk.stream, ly.wk.type, ly.wk.nrows_pad };
-        if (ly.wv.type == ly.wk.type) seg[n - 1].nrows += ly.wv.nrows_pad; else seg[n++] = { ly.wv.stream, ly.wv.type, ly.wv.nrows_pad };
-        for (int i = 0; i < n; ++i) items.push_back({ seg[i].w, seg[i].type, seg[i].nrows, m->E, &ly.aux_qkv[i] });
+        bamd_mv_seg seg[3]; int rows[3];
+        const int n = qkv_segments(ly, nullptr, seg, rows);
+        for (int i = 0; i < n; ++i) items.push_back({ seg[i].w, seg[i].type, rows[i], m->E, &ly.aux_qkv[i] });
         items.push_back({ ly.wo.stream, ly.wo.type, ly.wo.nrows_pad, m->E, &ly.aux_o });
         items.push_back({ ly.wg.stream, ly.wg.type, ly.wg.nrows_pad, m->E, &ly.aux_g });
         items.push_back({ ly.wu.stream, ly.wu.type, ly.wu.nrows_pad, m->E, &ly.aux_u });
@@ -844,11 +888,7 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         bamd_mm_args a; memset(&a, 0, sizeof a);
         // q,k,v                                                            (llama.cpp:8810-8835)
         bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s);
-        seg_of(a.seg[0], ly.wq, c->bqkv); a.nseg = 1;
-        if (ly.wk.type == ly.wq.type) { a.seg[0].nrows += ly.wk.nrows; a.seg[0].nvalid += ly.wk.nrows; }
-        else { seg_of(a.seg[a.nseg], ly.wk, c->bqkv + E); a.nseg++; }
-        if (ly.wv.type == ly.wk.type) { a.seg[a.nseg - 1].nrows += ly.wv.nrows; a.seg[a.nseg - 1].nvalid += ly.wv.nrows; }
-        else { seg_of(a.seg[a.nseg], ly.wv, c->bqkv + E + Ekv); a.nseg++; }
+        a.nseg = qkv_segments(ly, c->bqkv, a.seg);
         a.blob = c->bblob; a.K = E; a.T = T; a.ldo = ldq;
         if (batch_mm(c, a, BAMD_EPI_STORE, T, s, ly.aux_qkv)) return fail("batched mat-mul: unsupported shape");
         // RoPE, KV store, attention with the T>1 semantics                  (llama.cpp:8837-8849, :8318-8353)
@@ -904,23 +944,35 @@ static int co_gave_up(bamd_context * c) {
     memset(c->logits_host + c->m->V, 0, 32);
     return fail("co-launched attention + wo: a workgroup gave up waiting for the attention role (results invalid)");
 }
+// the evaluation in front of this call (a bamd_decode without read-back) was not waited for: now that its stream has been, check what it left
+static int settle_pending(bamd_context * c) { const bool was = c->status_pending; c->status_pending = false; return was ? co_gave_up(c) : 0; }
+// a launch that the runtime rejected (LDS / grid beyond the device's limits, wrong architecture) leaves no other trace
+static int launch_check() { const hipError_t le = hipGetLastError(); return le == hipSuccess ? 0 : fail(std::string("kernel launch failed: ") + hipGetErrorString(le)); }
+// logits and give-up words of the evaluation enqueued on `s` to the host, wait for them, check the words
+static int logits_to_host(bamd_context * c, hipStream_t s) {
+    if (hipMemcpyAsync(c->logits_host, c->logits, (size_t) c->m->V * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return fail("D2H logits");
+    if (status_readback(c, s) != hipSuccess) return fail("D2H co-launch status");
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(std::string("decode failed: ") + hipGetErrorString(e));
+    return co_gave_up(c);
+}
 extern "C" __attribute__((visibility("default"))) int bamd_decode(bamd_context * c, const int32_t * tokens, int n_tokens, int n_past) {
     bamd_model * m = c->m;
-    if (!m->with_embd || !m->with_output) { fail("bamd_decode needs a stage that owns embedding and output"); return 1; }
-    if (!tokens || n_tokens < 1) { fail("n_tokens out of range"); return 1; }
-    if (n_past < 0 || n_past > c->n_ctx - n_tokens) { fail("context overflow"); return 1; }
+    if (!m->with_embd || !m->with_output) return fail("bamd_decode needs a stage that owns embedding and output");
+    if (!tokens || n_tokens < 1) return fail("n_tokens out of range");
+    if (n_past < 0 || n_past > c->n_ctx - n_tokens) return fail("context overflow");
     if (n_tokens > BAMD_PREFILL_CAP && g_prefill_batch) {
         // llama_decode's n_ubatch split (llama.cpp:14615): micro-batches of 512, the logits are those of the last token
         for (int i = 0; i < n_tokens; i += BAMD_PREFILL_CAP)
             if (bamd_decode(c, tokens + i, std::min(BAMD_PREFILL_CAP, n_tokens - i), n_past + i)) return 1;
         return 0;
     }
-    if (n_tokens > c->forced_cap) { fail("n_tokens out of range (token by token evaluation takes at most 4096 per call)"); return 1; }
-    if (hipSetDevice(m->device) != hipSuccess) { fail("hipSetDevice"); return 1; }
+    if (n_tokens > c->forced_cap) return fail("n_tokens out of range (token by token evaluation takes at most 4096 per call)");
+    if (hipSetDevice(m->device) != hipSuccess) return fail("hipSetDevice");
     hipStream_t s = c->stream;
-    if (c->cells.active && n_tokens > 1) { fail("after a context shift (bamd_kv_seq_add) tokens are evaluated one per call"); return 1; }
+    if (c->cells.active && n_tokens > 1) return fail("after a context shift (bamd_kv_seq_add) tokens are evaluated one per call");
     if (!c->cells.active) c->n_cached = std::max(c->n_cached, n_past + n_tokens);
-    if (hipMemcpyAsync(c->forced, tokens, (size_t) n_tokens * 4, hipMemcpyHostToDevice, s) != hipSuccess) { fail("H2D tokens"); return 1; }
+    if (hipMemcpyAsync(c->forced, tokens, (size_t) n_tokens * 4, hipMemcpyHostToDevice, s) != hipSuccess) return fail("H2D tokens");
     if (n_tokens > 1 && n_tokens <= BAMD_PREFILL_CAP && prefill_batch_supported(c, n_past + n_tokens - 1)) {
         // one micro-batch: every layer once for all tokens (each weight record unpacked once per 8 tokens), lm_head for the last
         if (ensure_batch_buffers(c)) return 1;
@@ -938,24 +990,17 @@ extern "C" __attribute__((visibility("default"))) int bamd_decode(bamd_context *
             if (t == n_tokens - 1) enqueue_lm_head(c, s, nullptr);
         }
     }
-    {   // a launch that the runtime rejected (LDS / grid beyond the device's limits, wrong architecture) leaves no other trace
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) { fail(std::string("kernel launch failed: ") + hipGetErrorString(le)); return 1; }
-    }
+    if (launch_check()) return 1;
     c->logits_host_valid = c->logits_readback;
-    if (c->logits_readback && hipMemcpyAsync(c->logits_host, c->logits, (size_t) m->V * 4, hipMemcpyDeviceToHost, s) != hipSuccess) { fail("D2H logits"); return 1; }
-    if (status_readback(c, s) != hipSuccess) { fail("D2H co-launch status"); return 1; }
     if (!c->logits_readback) {
+        if (status_readback(c, s) != hipSuccess) return fail("D2H co-launch status");
         // nothing of this evaluation is read on the host yet (bamd_set_logits_readback(c, 0): the sampler prefilter runs where the lm_head left the logits): do not wait
         // here — the caller's next synchronising call (bamd_logits_shortlist, bamd_get_logits) enqueues behind this evaluation, waits ONCE and checks the status words
         // then.  One host round trip per token instead of two (round 5: 2.31 -> 2.27 ms per token through the bridge at 7850 cached positions)
         c->status_pending = true;
         return 0;
     }
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { fail(std::string("decode failed: ") + hipGetErrorString(e)); return 1; }
-    if (co_gave_up(c)) return 1;
-    return 0;
+    return logits_to_host(c, s);
 }
 // a micro-batch of 2..512 prompt tokens through ONE layer-split stage (bamd_stage_step's batched counterpart): tokens (host) on the
 // stage that owns the embedding, hidden_in_dev [n_tokens][n_embd] f32 elsewhere; hidden_out_dev [n_tokens][n_embd] on every stage but
@@ -976,11 +1021,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_prefill(bamd_co
     if (ensure_batch_buffers(c)) return 1;
     if (enqueue_prefill_batch(c, n_tokens, n_past, s, hidden_in_dev, hidden_out_dev)) return 1;
     if (m->with_output && want_logits) enqueue_lm_head(c, s, nullptr);
-    {   // a launch the runtime rejected (LDS size, grid) leaves no other trace (bamd_decode checks the same way)
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-    }
-    return 0;
+    return launch_check();
 }
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_batch(int on) { g_prefill_batch = on ? 1 : 0; g_prefill_mfma = on == 2 ? 0 : 1; }
 extern "C" __attribute__((visibility("default"))) const float * bamd_get_logits(bamd_context * c) {
@@ -988,7 +1029,7 @@ extern "C" __attribute__((visibility("default"))) const float * bamd_get_logits(
         if (hipSetDevice(c->m->device) != hipSuccess) return nullptr;
         if (hipMemcpyAsync(c->logits_host, c->logits, (size_t) c->m->V * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) return nullptr;
         if (hipStreamSynchronize(c->stream) != hipSuccess) return nullptr;
-        if (c->status_pending) { c->status_pending = false; if (co_gave_up(c)) return nullptr; }
+        if (settle_pending(c)) return nullptr;
         c->logits_host_valid = true;
     }
     return c->logits_host;
@@ -999,8 +1040,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_synchronize(bamd_cont
     HIPC(hipSetDevice(c->m->device));
     const hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(std::string("bamd_synchronize: ") + hipGetErrorString(e));
-    if (c->status_pending) { c->status_pending = false; if (co_gave_up(c)) return 1; }
-    return 0;
+    return settle_pending(c);
 }
 extern "C" __attribute__((visibility("default"))) void bamd_set_logits_readback(bamd_context * c, int on) { c->logits_readback = on != 0; }
 extern "C" __attribute__((visibility("default"))) void * bamd_context_stream(bamd_context * c) { return (void *) c->stream; }
@@ -1014,8 +1054,8 @@ extern "C" __attribute__((visibility("default"))) int bamd_set_logits_test(bamd_
 // ---- sampler prefilter (kernels in bamd_sampler.hip) --------------------------------------------------------
 extern "C" __attribute__((visibility("default"))) int bamd_sampler_tables(bamd_context * c, const uint8_t * halve_class, const float * cutoff_of, int n_vocab) {
     bamd_model * m = c->m;
-    if (n_vocab != m->V || !m->with_output) { fail("bamd_sampler_tables: needs the stage that owns the output layer, n_vocab of the model"); return 1; }
-    if (hipSetDevice(m->device) != hipSuccess) { fail("hipSetDevice"); return 1; }
+    if (n_vocab != m->V || !m->with_output) return fail("bamd_sampler_tables: needs the stage that owns the output layer, n_vocab of the model");
+    if (hipSetDevice(m->device) != hipSuccess) return fail("hipSetDevice");
     if (!c->samp_cls) {
         const size_t out_bytes = sizeof(bamd_shortlist_head) + (size_t) BAMD_SHORTLIST_CAP * 8;
         if (dev_alloc(c->allocs, (void **) &c->samp_cls, (size_t) m->V) || dev_alloc(c->allocs, (void **) &c->samp_cut, (size_t) m->V * 4) ||
@@ -1030,9 +1070,9 @@ extern "C" __attribute__((visibility("default"))) int bamd_sampler_tables(bamd_c
 extern "C" __attribute__((visibility("default"))) int bamd_logits_shortlist(bamd_context * c, const bamd_logit_penalty * pen, int n_pen, int halve,
                                                                             bamd_shortlist_head * head, int32_t * ids, float * vals, void * hip_stream) {
     bamd_model * m = c->m;
-    if (!c->samp_cls) { fail("bamd_logits_shortlist before bamd_sampler_tables"); return 1; }
-    if (n_pen < 0 || n_pen > BAMD_PENALTY_CAP) { fail("bamd_logits_shortlist: too many penalty entries"); return 1; }
-    if (hipSetDevice(m->device) != hipSuccess) { fail("hipSetDevice"); return 1; }
+    if (!c->samp_cls) return fail("bamd_logits_shortlist before bamd_sampler_tables");
+    if (n_pen < 0 || n_pen > BAMD_PENALTY_CAP) return fail("bamd_logits_shortlist: too many penalty entries");
+    if (hipSetDevice(m->device) != hipSuccess) return fail("hipSetDevice");
     hipStream_t s = (hipStream_t) hip_stream;
     const size_t out_bytes = sizeof(bamd_shortlist_head) + (size_t) BAMD_SHORTLIST_CAP * 8;
     if (n_pen) {
@@ -1046,28 +1086,12 @@ extern "C" __attribute__((visibility("default"))) int bamd_logits_shortlist(bamd
     c->logits_host_valid = false;
     HIPC(hipMemcpyAsync(c->samp_out_host, c->samp_out, out_bytes, hipMemcpyDeviceToHost, s));
     hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { fail(std::string("sampler prefilter failed: ") + hipGetErrorString(e)); return 1; }
-    if (c->status_pending) { c->status_pending = false; if (co_gave_up(c)) return 1; }      // the evaluation in front of this call (bamd_decode without read-back) was not waited for
+    if (e != hipSuccess) return fail(std::string("sampler prefilter failed: ") + hipGetErrorString(e));
+    if (settle_pending(c)) return 1;
     memcpy(head, c->samp_out_host, sizeof *head);
     const int n = std::min(std::max(head->count, 0), BAMD_SHORTLIST_CAP);
     memcpy(ids, c->samp_out_host + sizeof(bamd_shortlist_head), (size_t) n * 4);
     memcpy(vals, c->samp_out_host + sizeof(bamd_shortlist_head) + (size_t) BAMD_SHORTLIST_CAP * 4, (size_t) n * 4);
-    return 0;
-}
-
-static int build_graph(bamd_context * c, int pos_hi) {
-    hipStream_t s = c->stream;
-    hipGraph_t g = nullptr;
-    HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    enqueue_begin(c, 0, 1, s, c->cells.active);
-    int rc = enqueue_layers(c, 0, s, nullptr, pos_hi);
-    enqueue_lm_head(c, s, nullptr);
-    hipError_t e = hipStreamEndCapture(s, &g);
-    if (rc) { if (g) hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    e = hipGraphInstantiate(&c->graph, g, nullptr, nullptr, 0);
-    hipGraphDestroy(g);
-    if (e != hipSuccess) return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     return 0;
 }
 
@@ -1086,7 +1110,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_generate_greedy(bamd_
         if (c->slots_cap < n_steps) {
             if (dev_alloc(c->allocs, (void **) &c->slots, (size_t) c->out_cap * 8)) return 1;
             c->slots_cap = c->out_cap;
-            if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }            // (captured with the old pointer)
+            drop_replays(c);                                              // (captured with the old pointer)
         }
         std::vector<int32_t> hs((size_t) n_steps * 2);
         for (int t = 0; t < n_steps; ++t) {
@@ -1097,54 +1121,37 @@ extern "C" __attribute__((visibility("default"))) int bamd_generate_greedy(bamd_
         HIPC(hipMemcpyAsync(c->slots, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, s));
         HIPC(hipStreamSynchronize(s));                                    // (hs is a host temporary)
     } else c->n_cached = std::max(c->n_cached, n_past + n_steps);
-    const int fused = (attn_fused_for(c, attn_hi) ? 1 : (c->cells.active ? 2 : 0));     // 2: the shifted-cell kernels and the slot table (other arguments: recapture)
+    const ReplayKey key = { attn_path(c, attn_hi) };
+    auto enqueue = [&] { enqueue_begin(c, 0, 1, s, c->cells.active); return enqueue_step(c, s, attn_hi); };   // state on the device; the slot table when the cells are tracked
     float ms_steps = 0.f;
     EventPair ev; bool timed_by_events = false;
-    // the step as AQL packets on the library's own queue (bamd_aql.h): the launch sequences whose kernels keep the inter-kernel rules of bamd_device.h — the
-    // single-launch attention path and the scores | softmax + P.V path of long sequences; anything else (shifted cells, score rows beyond the LDS) replays the hipGraph
-    bool aql_path_ok = fused == 1;
-    if (fused == 0) {                                                 // long sequences: scores | softmax + P.V, when its kernels are the inter-kernel-clean ones
-        bamd_attn_args t; memset(&t, 0, sizeof t); t.hd = m->hd; t.Hkv = m->Hkv; t.n_ctx = c->n_ctx_pad;
-        aql_path_ok = bamd_attention_split_is_ik_clean(t, m->H / m->Hkv) != 0;
-    }
-    const bool want_aql = g_aql && aql_path_ok && !c->aql_failed;
-    if (c->aql && (c->aql_key != fused || !want_aql)) { bamd_aql_free(c->aql); c->aql = nullptr; }
-    if (want_aql && !c->aql) {
-        bamd_aql_recording rec;
-        bamd_aql_rec = &rec;
-        enqueue_begin(c, 0, 1, s, false);
-        const int rc = enqueue_layers(c, 0, s, nullptr, attn_hi);
-        enqueue_lm_head(c, s, nullptr);
-        bamd_aql_rec = nullptr;
-        const char * why = "recording failed";
-        if (!rc) c->aql = bamd_aql_build(m->device, rec, &why);
-        if (!c->aql) { c->aql_failed = true; if (getenv("BAMD_AQL_VERBOSE")) fprintf(stderr, "bamd: own AQL queue not used: %s\n", why ? why : "?"); }
-        c->aql_key = fused;
-    }
-    if (c->aql) {
+    // AQL packets on the library's own queue where the attention path allows it, else one hipGraph launch per step on the context's stream
+    StepReplay & own = c->greedy_aql;
+    const bool want_aql = aql_allowed(c, key.path);
+    if (want_aql) own.reset_unless(key); else own.reset();
+    if (want_aql && !own.aql) { own.aql = record_aql(c, enqueue); own.key = key; }
+    if (own.aql) {
         if (set_state(c, n_past, s, true)) return 1;
         HIPC(hipStreamSynchronize(s));                                // the state and everything before it is in memory: the first packet acquires at system scope
         double sec = 0.0; const char * why = nullptr;
-        if (bamd_aql_run(c->aql, n_steps, &sec, &why)) return fail(std::string("own AQL queue: ") + (why ? why : "?"));
+        if (bamd_aql_run(own.aql, n_steps, &sec, &why)) return fail(std::string("own AQL queue: ") + (why ? why : "?"));
         ms_steps = (float) (sec * 1e3); c->aql_runs += 1;
     } else {
-        if (c->graph && c->graph_fused != fused) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
-        if (!c->graph && build_graph(c, attn_hi)) return 1;
-        c->graph_fused = fused;
+        StepReplay & g = c->greedy_graph;
+        g.reset_unless(key);
+        if (!g.exec && capture_graph(s, enqueue, &g.exec, { "hipStreamEndCapture: ", "hipGraphInstantiate: " })) return 1;
+        g.key = key;
         if (set_state(c, n_past, s, true)) return 1;
         HIPC(ev.create()); timed_by_events = true;
         HIPC(hipEventRecord(ev.a, s));
-        for (int t = 0; t < n_steps; ++t) HIPC(hipGraphLaunch(c->graph, s));
+        for (int t = 0; t < n_steps; ++t) HIPC(hipGraphLaunch(g.exec, s));
         HIPC(hipEventRecord(ev.b, s));
     }
     enqueue_begin(c, 0, 0, s);                                        // flush the last arg-max into out_tokens
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(out_tokens, c->out_tokens, (size_t) (n_steps + 1) * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipMemcpyAsync(c->logits_host, c->logits, (size_t) m->V * 4, hipMemcpyDeviceToHost, s));
-    HIPC(status_readback(c, s));
-    HIPC(hipStreamSynchronize(s));
+    if (logits_to_host(c, s)) return 1;
     c->logits_host_valid = true;
-    if (co_gave_up(c)) return 1;
     if (timed_by_events) HIPC(hipEventElapsedTime(&ms_steps, ev.a, ev.b));
     if (elapsed_ms) *elapsed_ms = ms_steps;
     return 0;
@@ -1153,37 +1160,35 @@ extern "C" __attribute__((visibility("default"))) int bamd_generate_greedy(bamd_
 extern "C" __attribute__((visibility("default"))) int bamd_aql_runs(const bamd_context * c) { return c->aql_runs + c->aql_steps; }
 
 // ---- layer-split stage ---------------------------------------------------------------------------------
+// Is this bamd_stage_step call the one the own AQL queue (bamd_aql.h) serves: the whole single-stage step — state from a pinned host inbox, layers, lm_head — as
+// packets with fence scope NONE, one host wait at its end?  That is the caller that owns embedding and output, feeds host tokens on the context's own stream and
+// wants the logits (bamd_decode from the bridge's token loop); layer-split stages, device-side tokens, shifted cells and prefill-mode steps keep the stage graphs
+static bool step_from_inbox(const bamd_context * c, const void * token_dev, const void * hidden_in_dev, const void * hidden_out_dev, int want_logits, int prefill_mode, hipStream_t s) {
+    const bamd_model * m = c->m;
+    return m->with_embd && m->with_output && !token_dev && !hidden_in_dev && !hidden_out_dev && want_logits && !prefill_mode && !c->cells.active && s == c->stream && s != nullptr;
+}
+static bool have_inbox(bamd_context * c) {                 // the pinned host block that step_begin_kernel reads the state of such a step from (allocated at the first one)
+    if (!c->inbox && hipHostMalloc((void **) &c->inbox, sizeof(bamd_step_state)) != hipSuccess) { (void) hipGetLastError(); c->inbox = nullptr; }
+    return c->inbox != nullptr;
+}
 extern "C" __attribute__((visibility("default"))) int bamd_stage_step(bamd_context * c, int32_t token, const void * token_dev, int pos, const void * hidden_in_dev,
                                void * hidden_out_dev, int want_logits, int prefill_mode, void * hip_stream) {
     bamd_model * m = c->m;
     HIPC(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t) hip_stream;            // NULL = the HIP default (null) stream, as for any HIP API
     if (pos < 0 || pos >= c->n_ctx) return fail("position out of range");
-    // ---- own AQL queue (bamd_aql.h): the whole single-stage step — state from a pinned host inbox, layers, lm_head — as packets with fence scope NONE, one host
-    //      wait at its end.  For the caller that owns embedding and output, feeds host tokens on the context's own stream and wants the logits (bamd_decode from
-    //      the bridge's token loop); layer-split stages, device-side tokens, shifted cells and prefill-mode steps keep the stage graphs below ----
-    if (g_aql && !c->aql_failed && m->with_embd && m->with_output && !token_dev && !hidden_in_dev && !hidden_out_dev && want_logits && !prefill_mode &&
-        !c->cells.active && s == c->stream && s != nullptr) {
-        const int fused = attn_fused_for(c, pos) ? 1 : 0;
-        bool ok = fused == 1;
-        if (!ok) { bamd_attn_args t; memset(&t, 0, sizeof t); t.hd = m->hd; t.Hkv = m->Hkv; t.n_ctx = c->n_ctx_pad; ok = bamd_attention_split_is_ik_clean(t, m->H / m->Hkv) != 0; }
-        if (ok && !c->inbox && hipHostMalloc((void **) &c->inbox, sizeof(bamd_step_state)) != hipSuccess) { (void) hipGetLastError(); c->inbox = nullptr; ok = false; }
-        if (ok) {
-            if (c->aql_step && c->aql_step_key != fused) { bamd_aql_free(c->aql_step); c->aql_step = nullptr; }
-            if (!c->aql_step) {
-                bamd_aql_recording rec;
-                bamd_aql_rec = &rec;
+    const ReplayKey own_key = { attn_path(c, pos) };
+    if (step_from_inbox(c, token_dev, hidden_in_dev, hidden_out_dev, want_logits, prefill_mode, s) && aql_allowed(c, own_key.path) && have_inbox(c)) {
+        StepReplay & own = c->step_aql;
+        own.reset_unless(own_key);
+        if (!own.aql) {
+            own.aql = record_aql(c, [&] {
                 bamd_launch_step_begin(c->st, c->forced, 1, c->out_tokens, m->tok_embd.raw, m->tok_embd.type, m->E, m->V, c->x, 1, s, nullptr, nullptr, c->rope, c->rope_cur, m->hd, c->inbox);
-                const int rc = enqueue_layers(c, 0, s, nullptr, pos);
-                enqueue_lm_head(c, s, nullptr);
-                bamd_aql_rec = nullptr;
-                const char * why = "recording failed";
-                if (!rc) c->aql_step = bamd_aql_build(m->device, rec, &why);
-                if (!c->aql_step) { c->aql_failed = true; if (getenv("BAMD_AQL_VERBOSE")) fprintf(stderr, "bamd: own AQL queue not used: %s\n", why ? why : "?"); }
-                c->aql_step_key = fused;
-            }
+                return enqueue_step(c, s, pos);
+            });
+            own.key = own_key;
         }
-        if (ok && c->aql_step) {
+        if (own.aql) {
             if (next_serial(c, s)) return 1;
             c->n_cached = std::max(c->n_cached, pos + 1);
             HIPC(hipStreamSynchronize(s));                               // whatever this context enqueued before (a prompt micro-batch nobody waited for) is done
@@ -1191,7 +1196,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_step(bamd_conte
             memset(in, 0, sizeof *in);
             in->pos_base = pos; in->n_ctx = c->n_ctx; in->serial = c->host_serial; in->token = token;
             const char * why = nullptr;
-            if (bamd_aql_run(c->aql_step, 1, nullptr, &why)) return fail(std::string("own AQL queue: ") + (why ? why : "?"));
+            if (bamd_aql_run(own.aql, 1, nullptr, &why)) return fail(std::string("own AQL queue: ") + (why ? why : "?"));
             c->aql_steps += 1;
             return 0;
         }
@@ -1213,39 +1218,24 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_step(bamd_conte
     else HIPC(hipMemcpyAsync(c->forced, &token, 4, hipMemcpyHostToDevice, s));
     // everything after the two small host copies is a fixed launch sequence for given pointers: replay it as one hipGraph
     // (a stage of 4 layers is ~22 launches at ~8 us of host time each; the layer-split pipeline is host-bound without this)
-    auto enqueue = [&](hipStream_t q) -> int {
-        if (m->with_embd) bamd_launch_step_begin(c->st, forced, 1, c->out_tokens, m->tok_embd.raw, m->tok_embd.type, m->E, m->V, c->x, 1, q, nullptr, nullptr, c->rope, c->rope_cur, m->hd);
+    auto enqueue = [&]() -> int {
+        if (m->with_embd) bamd_launch_step_begin(c->st, forced, 1, c->out_tokens, m->tok_embd.raw, m->tok_embd.type, m->E, m->V, c->x, 1, s, nullptr, nullptr, c->rope, c->rope_cur, m->hd);
         else {
             // no embedding on this stage: still advance the device state (pos, n_kv), then take the hidden state
-            bamd_launch_step_begin(c->st, c->forced, 0, c->out_tokens, nullptr, BAMD_F32, 0, m->V, c->x, 1, q, nullptr, nullptr, c->rope, c->rope_cur, m->hd);
-            HIPC(hipMemcpyAsync(c->x, hidden_in_dev, (size_t) m->E * 4, hipMemcpyDeviceToDevice, q));
+            bamd_launch_step_begin(c->st, c->forced, 0, c->out_tokens, nullptr, BAMD_F32, 0, m->V, c->x, 1, s, nullptr, nullptr, c->rope, c->rope_cur, m->hd);
+            HIPC(hipMemcpyAsync(c->x, hidden_in_dev, (size_t) m->E * 4, hipMemcpyDeviceToDevice, s));
         }
-        if (enqueue_layers(c, prefill_mode, q, nullptr, attn_hi)) return 1;
-        if (m->with_output) { if (want_logits) enqueue_lm_head(c, q, nullptr); }
-        else HIPC(hipMemcpyAsync(hidden_out_dev, c->x, (size_t) m->E * 4, hipMemcpyDeviceToDevice, q));
+        if (enqueue_layers(c, prefill_mode, s, nullptr, attn_hi)) return 1;
+        if (m->with_output) { if (want_logits) enqueue_lm_head(c, s, nullptr); }
+        else HIPC(hipMemcpyAsync(hidden_out_dev, c->x, (size_t) m->E * 4, hipMemcpyDeviceToDevice, s));
         return 0;
     };
-    if (!g_stage_graph || s == nullptr) {                            // the legacy default stream cannot be captured
-        if (enqueue(s)) return 1;
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-        return 0;
-    }
-    bamd_context::StageGraph & sg = c->sgraph[want_logits ? 1 : 0][prefill_mode ? 1 : 0];
-    const int fused = (attn_fused_for(c, attn_hi) ? 1 : (c->cells.active ? 2 : 0));     // 2: the shifted-cell kernels (other arguments: recapture)
-    if (sg.exec && (sg.token_src != (const void *) forced || sg.hin != hidden_in_dev || sg.hout != hidden_out_dev || sg.fused != fused)) { hipGraphExecDestroy(sg.exec); sg.exec = nullptr; }
-    if (!sg.exec) {
-        hipGraph_t g = nullptr;
-        HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue(s);
-        const hipError_t e = hipStreamEndCapture(s, &g);
-        if (rc) { if (g) hipGraphDestroy(g); return rc; }
-        if (e != hipSuccess) return fail(std::string("stage graph capture: ") + hipGetErrorString(e));
-        const hipError_t e2 = hipGraphInstantiate(&sg.exec, g, nullptr, nullptr, 0);
-        hipGraphDestroy(g);
-        if (e2 != hipSuccess) { sg.exec = nullptr; return fail(std::string("stage graph instantiate: ") + hipGetErrorString(e2)); }
-        sg.token_src = forced; sg.hin = hidden_in_dev; sg.hout = hidden_out_dev; sg.fused = fused;
-    }
+    if (!g_stage_graph || s == nullptr) return enqueue() ? 1 : launch_check();   // the legacy default stream cannot be captured
+    StepReplay & sg = c->stage_graph[want_logits ? 1 : 0][prefill_mode ? 1 : 0];
+    const ReplayKey key = { attn_path(c, attn_hi), forced, hidden_in_dev, hidden_out_dev };
+    sg.reset_unless(key);
+    if (!sg.exec && capture_graph(s, enqueue, &sg.exec, { "stage graph capture: ", "stage graph instantiate: " })) return 1;
+    sg.key = key;
     HIPC(hipGraphLaunch(sg.exec, s));
     return 0;
 }
@@ -1274,13 +1264,8 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_argmax(bamd_con
 // host logits of the last bamd_stage_step(want_logits=1) on the last stage; synchronises `hip_stream`
 extern "C" __attribute__((visibility("default"))) const float * bamd_stage_get_logits(bamd_context * c, void * hip_stream) {
     hipStream_t s = (hipStream_t) hip_stream;
-    bamd_model * m = c->m;
-    if (hipSetDevice(m->device) != hipSuccess) return nullptr;
-    if (hipMemcpyAsync(c->logits_host, c->logits, (size_t) m->V * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return nullptr;
-    if (status_readback(c, s) != hipSuccess) return nullptr;
-    if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
-    if (co_gave_up(c)) return nullptr;
-    return c->logits_host;
+    if (hipSetDevice(c->m->device) != hipSuccess) return nullptr;
+    return logits_to_host(c, s) ? nullptr : c->logits_host;
 }
 // raw GGUF access for the tokenizer side of the bridge
 const GgufFile * bamd_model_gguf(const bamd_model * m) { return m->file.get(); }
@@ -1289,7 +1274,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_model_device(const ba
 // ---- measurement -----------------------------------------------------------------------------------------
 // one eager step at position pos with a HIP event pair around every launch; per launch kind (StepTimer::begin) the launch count, the summed
 // event time and the summed algorithmic bytes; entry 7 = what an EMPTY event pair reads on this stream (median of 9)
-static int profile_step_kinds(bamd_context * c, int pos, int * launches, double * ms, double * bytes) {
+extern "C" __attribute__((visibility("default"))) int bamd_profile_step_kinds(bamd_context * c, int pos, int * launches, double * ms, double * bytes) {
     bamd_model * m = c->m;
     if (!m->with_embd || !m->with_output) return fail("profile needs a full single-stage model");
     HIPC(hipSetDevice(m->device));
@@ -1314,23 +1299,19 @@ static int profile_step_kinds(bamd_context * c, int pos, int * launches, double 
     {
         std::vector<float> ov;
         for (int i = 0; i < 9; ++i) {
-            hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
-            hipEventRecord(a, s); hipEventRecord(b, s); hipStreamSynchronize(s);
-            float t = 0.f; hipEventElapsedTime(&t, a, b); ov.push_back(t);
-            hipEventDestroy(a); hipEventDestroy(b);
+            EventPair e; e.create();
+            hipEventRecord(e.a, s); hipEventRecord(e.b, s); hipStreamSynchronize(s);
+            float t = 0.f; hipEventElapsedTime(&t, e.a, e.b); ov.push_back(t);
         }
         std::sort(ov.begin(), ov.end());
         launches[7] = 9; ms[7] = ov[4]; bytes[7] = 0;
     }
     return 0;
 }
-extern "C" __attribute__((visibility("default"))) int bamd_profile_step_kinds(bamd_context * c, int pos, int * launches, double * ms, double * bytes) {
-    return profile_step_kinds(c, pos, launches, ms, bytes);
-}
 // the same folded into three classes: [0] all mat-vec launches, [1] attention, [2] other, [3] the empty event pair
 extern "C" __attribute__((visibility("default"))) int bamd_profile_step(bamd_context * c, int pos, int * launches, double * ms, double * bytes) {
     int l[8]; double t[8], b[8];
-    if (profile_step_kinds(c, pos, l, t, b)) return 1;
+    if (bamd_profile_step_kinds(c, pos, l, t, b)) return 1;
     for (int i = 0; i < 4; ++i) { launches[i] = 0; ms[i] = 0; bytes[i] = 0; }
     const int cls_of[7] = { 0, 1, 2, 0, 0, 0, 0 };
     for (int k = 0; k < 7; ++k) { launches[cls_of[k]] += l[k]; ms[cls_of[k]] += t[k]; bytes[cls_of[k]] += b[k]; }
@@ -1358,367 +1339,16 @@ extern "C" __attribute__((visibility("default"))) int bamd_timeline_step(bamd_co
     int32_t tok = 1;
     HIPC(hipMemcpyAsync(c->forced, &tok, 4, hipMemcpyHostToDevice, s));
     c->tl_base = buf; c->tl_slot = 0; c->tl_cap = cap;
-    hipGraph_t g = nullptr; OwnedGraphExec ge;
-    {
-        const hipError_t eb = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-        if (eb != hipSuccess) { c->tl_base = nullptr; c->tl_slot = 0; c->tl_cap = 0; return fail(std::string("timeline capture: ") + hipGetErrorString(eb)); }
-    }
-    enqueue_begin(c, 1, 1, s);
-    int rc = enqueue_layers(c, 0, s, nullptr, pos);
-    enqueue_lm_head(c, s, nullptr);
-    hipError_t e = hipStreamEndCapture(s, &g);
+    OwnedGraphExec ge;
+    const int rc = capture_graph(s, [&] { enqueue_begin(c, 1, 1, s); return enqueue_step(c, s, pos); }, &ge.g, { "timeline capture failed", "timeline graph instantiate failed" });
     *n_launches = c->tl_slot;
-    c->tl_base = nullptr; c->tl_slot = 0; c->tl_cap = 0;
-    if (rc || e != hipSuccess) { if (g) hipGraphDestroy(g); return rc ? rc : fail("timeline capture failed"); }
-    e = hipGraphInstantiate(&ge.g, g, nullptr, nullptr, 0);
-    hipGraphDestroy(g);
-    if (e != hipSuccess) { ge.g = nullptr; return fail("timeline graph instantiate failed"); }
+    c->tl_base = nullptr; c->tl_slot = 0; c->tl_cap = 0;             // on every exit: the stamps belong to this call's buffer
+    if (rc) return rc;
     for (int r = 0; r < replays; ++r) {
         if (set_state(c, pos, s, false)) return 1;
         HIPC(hipGraphLaunch(ge.g, s));
     }
     HIPC(hipStreamSynchronize(s));
     HIPC(hipMemcpy(out, buf, (size_t) *n_launches * BAMD_TL_SLOT_WORDS * 8, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// -------------------------------------------------------------------------------------------------------
-// op-level entry points (host in / host out): thin wrappers that run the SAME kernels on device 0
-// -------------------------------------------------------------------------------------------------------
-struct Tmp {
-    std::vector<void *> p;
-    ~Tmp() { for (void * x : p) hipFree(x); }
-    void * up(const void * h, size_t n) { void * d = nullptr; if (hipMalloc(&d, n + 4096) != hipSuccess) return nullptr; p.push_back(d); if (h && hipMemcpy(d, h, n, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return d; }
-};
-static int need_device() {
-    if (bamd_device_count() <= 0) return fail("no HIP device available: libbooster_amd has no CPU fallback");
-    HIPC(hipSetDevice(0));
-    return 0;
-}
-static int n_cu0() { hipDeviceProp_t p; if (hipGetDeviceProperties(&p, 0) != hipSuccess) return 256; return p.multiProcessorCount > 0 ? p.multiProcessorCount : 256; }
-
-extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_K(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks) {
-    if (need_device()) return 1;
-    if (k <= 0 || k % 256) return fail("k must be a positive multiple of 256");
-    Tmp t; const size_t ob = (size_t) (k / 256) * 292;
-    float * dx = (float *) t.up(x, (size_t) k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr; void * dout = t.up(nullptr, ob);
-    if (!dx || !dout || (norm_w && !dw)) return fail("device alloc/copy failed");
-    HIPC(hipMemset(dout, 0, ob));
-    bamd_launch_quantize_q8k_test(dx, dw, eps, (int) k, norm_w != nullptr, dout, nullptr);
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(out_blocks, dout, ob, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-static int op_matvec(int type, const void * wA, const void * wB, int nrows, int k, const float * x, const float * norm_w, float eps,
-                     const float * residual, float * y, int epi, int mode, unsigned long long * best_key = nullptr) {
-    if (need_device()) return 1;
-    if (!bamd_is_kquant(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
-    const int nrows_pad = (nrows + 7) / 8 * 8;
-    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
-    void * rawA = t.up(wA, wb), * strA = t.up(nullptr, wbp), * rawB = nullptr, * strB = nullptr;
-    if (wB) { rawB = t.up(wB, wb); strB = t.up(nullptr, wbp); }
-    if (strA) HIPC(hipMemset(strA, 0, wbp));
-    if (strB) HIPC(hipMemset(strB, 0, wbp));
-    float * dx = (float *) t.up(x, (size_t) k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr;
-    float * dres = residual ? (float *) t.up(residual, (size_t) nrows * 4) : nullptr; float * dy = (float *) t.up(nullptr, (size_t) nrows * 4);
-    unsigned long long * key = (unsigned long long *) t.up(nullptr, 8);
-    if (!rawA || !strA || !dx || !dy || !key || (wB && (!rawB || !strB)) || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
-    HIPC(hipMemset(key, 0, 8));
-    bamd_launch_repack(rawA, strA, type, nrows, k, nullptr);
-    if (wB) bamd_launch_repack(rawB, strB, type, nrows, k, nullptr);
-    bamd_mv_args a; memset(&a, 0, sizeof a);
-    a.seg[0].w = strA; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows_pad; a.seg[0].nvalid = nrows; a.nseg = 1;
-    if (wB) { a.seg[1] = a.seg[0]; a.seg[1].w = strB; a.nseg = 2; }
-    a.x = dx; a.normw = dw; a.eps = eps; a.K = k; a.res = dres; a.best_key = key; a.mode = mode;
-    bamd_launch_matvec(a, norm_w ? BAMD_PRO_NORM : BAMD_PRO_PLAIN, epi, n_cu0(), nullptr);
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(y, dy, (size_t) nrows * 4, hipMemcpyDeviceToHost));
-    if (best_key) HIPC(hipMemcpy(best_key, key, 8, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w, float eps,
-                                   const float * residual, float * y, int mode) {
-    return op_matvec(type, w_raw, nullptr, nrows, k, x, norm_w, eps, residual, y, residual ? BAMD_EPI_ADD : BAMD_EPI_STORE, mode);
-}
-// the lm_head launch (enqueue_lm_head) with its arg-max epilogue; the row is decoded from the key as step_begin_kernel decodes it
-extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec_argmax(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w,
-                                                                                 float eps, float * y, int mode, int32_t * row) {
-    unsigned long long key = 0ull;
-    if (op_matvec(type, w_raw, nullptr, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_ARGMAX, mode, &key)) return 1;
-    *row = key ? (int32_t) (0xffffffffu - (uint32_t) (key & 0xffffffffull)) : -1;
-    return 0;
-}
-// batched mat-mul of T activation rows against one matrix through the prefill kernels: impl 0 = integer-dot kernel, 2 = matrix-core kernel (1 and 3 were the generations removed in round 6)
-extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const float * x, int T, const float * norm_w,
-                                                                              float eps, const float * residual, float * y, int impl) {
-    if (need_device()) return 1;
-    if (!bamd_is_kquant(type) || k <= 0 || k % 256 || nrows <= 0 || T <= 0) return fail("bad type/shape");
-    const int nrows_pad = (nrows + 7) / 8 * 8;
-    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
-    void * raw = t.up(w_raw, wb), * str = t.up(nullptr, wbp);
-    float * dx = (float *) t.up(x, (size_t) T * k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr;
-    float * dres = residual ? (float *) t.up(residual, (size_t) T * nrows * 4) : nullptr; float * dy = (float *) t.up(nullptr, (size_t) T * nrows * 4);
-    void * blob = t.up(nullptr, (size_t) T * bamd_blob_bytes(k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
-    if (!raw || !str || !dx || !dy || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
-    HIPC(hipMemset(str, 0, wbp));
-    bamd_launch_repack(raw, str, type, nrows, k, nullptr);
-    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr);
-    if (impl == 2) {                                                // the matrix-core kernel: side table built here, as the engine builds it at model load
-        void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
-        if (!aux) return fail("device alloc failed");
-        bamd_launch_prefill_aux(str, type, nrows_pad, k, aux, nullptr);
-        if (bamd_launch_matmul_mfma2(str, aux, type, nrows, nrows_pad, k, blob16, T, dy, dres, dres ? BAMD_EPI_ADD : BAMD_EPI_STORE, nrows, nullptr)) return fail("MFMA path: unsupported type/shape");
-    } else {
-        bamd_mm_args a; memset(&a, 0, sizeof a);
-        a.seg[0].w = str; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows_pad; a.seg[0].nvalid = nrows; a.nseg = 1;
-        a.blob = (const uint8_t *) blob; a.K = k; a.T = T; a.ldo = nrows; a.res = dres;
-        if (bamd_launch_matmul_batch(a, residual ? BAMD_EPI_ADD : BAMD_EPI_STORE, n_cu0(), nullptr)) return fail("batched mat-mul: unsupported shape");
-    }
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(y, dy, (size_t) T * nrows * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" __attribute__((visibility("default"))) int bamd_op_ffn_gate_up(int type, const void * wg_raw, const void * wu_raw, int nrows, int k, const float * x, const float * norm_w,
-                                   float eps, float * y) {
-    return op_matvec(type, wg_raw, wu_raw, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_SILU_MUL, 0);
-}
-extern "C" __attribute__((visibility("default"))) int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y) {
-    if (need_device()) return 1;
-    if (type != BAMD_F32 && type != BAMD_F16 && !bamd_is_kquant(type)) return fail("bad type");
-    if (k <= 0 || (bamd_is_kquant(type) && k % 256)) return fail("bad row length");
-    if (row < 0 || row >= nrows) return fail("row out of range");
-    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows;
-    void * raw = t.up(w_raw, wb); float * dy = (float *) t.up(nullptr, (size_t) k * 4);
-    bamd_step_state h; memset(&h, 0, sizeof h); h.n_ctx = 32;
-    bamd_step_state * st = (bamd_step_state *) t.up(&h, sizeof h);
-    int32_t * forced = (int32_t *) t.up(&row, 4); int32_t * outt = (int32_t *) t.up(nullptr, 64);
-    if (!raw || !dy || !st || !forced || !outt) return fail("device alloc/copy failed");
-    bamd_launch_step_begin(st, forced, 1, outt, raw, type, k, nrows, dy, 1, nullptr);
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(y, dy, (size_t) k * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" __attribute__((visibility("default"))) int bamd_op_rope_row(int pos, int n_dims, float freq_base, float freq_scale, const float * freq_factors, float * row) {
-    rope_row(row, pos, n_dims, freq_base, freq_scale, freq_factors, 0.0f, 1.0f, 8192, 32.0f, 1.0f);
-    return 0;
-}
-// reference layout <-> chain-major device layout of the KV cache (bamd_device.h, "Attention": kperm / vperm); v_ref null: the K cache only
-static inline int kperm_host(int n) { const int l = n >> 3; return ((l >> 3) << 6) + ((n & 7) << 3) + (l & 7); }
-static void kv_to_device_order(const uint16_t * k_ref, const uint16_t * v_ref, int n_ctx, int n_ctx_pad, int Hkv, int hd, std::vector<uint16_t> & kd, std::vector<uint16_t> & vd) {
-    const int Ekv = Hkv * hd;
-    kd.assign((size_t) n_ctx_pad * Ekv, 0); vd.assign(v_ref ? (size_t) Ekv * n_ctx_pad : 0, 0);
-    for (int i = 0; i < n_ctx; ++i) for (int h = 0; h < Hkv; ++h) for (int n = 0; n < hd; ++n)
-        kd[(size_t) i * Ekv + h * hd + kperm_host(n)] = k_ref[(size_t) i * Ekv + h * hd + n];
-    if (v_ref) for (int r = 0; r < Ekv; ++r) for (int p = 0; p < n_ctx; ++p)
-        vd[(size_t) r * n_ctx_pad + (p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3)] = v_ref[(size_t) r * n_ctx + p];
-}
-static void kv_from_device_order(uint16_t * k_ref, uint16_t * v_ref, int n_ctx, int n_ctx_pad, int Hkv, int hd, const std::vector<uint16_t> & kd, const std::vector<uint16_t> & vd) {
-    const int Ekv = Hkv * hd;
-    for (int i = 0; i < n_ctx; ++i) for (int h = 0; h < Hkv; ++h) for (int n = 0; n < hd; ++n)
-        k_ref[(size_t) i * Ekv + h * hd + n] = kd[(size_t) i * Ekv + h * hd + kperm_host(n)];
-    if (v_ref) for (int r = 0; r < Ekv; ++r) for (int p = 0; p < n_ctx; ++p)
-        v_ref[(size_t) r * n_ctx + p] = vd[(size_t) r * n_ctx_pad + (p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3)];
-}
-
-extern "C" __attribute__((visibility("default"))) int bamd_op_attention(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
-                                 const float * rope_row_h, int H, int Hkv, int hd, int n_ctx, int pos, int prefill_mode, float * out,
-                                 float * probs_h0) {
-    const bool split_path = (prefill_mode & 2) != 0;   // bit 1: force the three-kernel (long-context) path
-    prefill_mode &= 1;
-    if (need_device()) return 1;
-    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || pos < 0 || pos >= n_ctx || n_ctx % 32 || H % Hkv) return fail("bad attention shape");
-    Tmp t; const int Ekv = Hkv * hd; const int n_ctx_pad = (n_ctx + 63) / 64 * 64; const size_t kvb = (size_t) n_ctx_pad * Ekv * 2;
-    std::vector<float> rope((size_t) n_ctx * hd, 0.f);
-    memcpy(rope.data() + (size_t) pos * hd, rope_row_h, (size_t) hd * 4);
-    std::vector<uint16_t> kd, vd;
-    kv_to_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    bamd_step_state h; memset(&h, 0, sizeof h); h.pos = pos; h.n_ctx = n_ctx; h.n_kv = std::min(n_ctx, std::max(32, (pos + 1 + 31) / 32 * 32));
-    bamd_attn_args a; memset(&a, 0, sizeof a);
-    a.st = (bamd_step_state *) t.up(&h, sizeof h);
-    a.q = (float *) t.up(q, (size_t) H * hd * 4); a.k = (float *) t.up(k, (size_t) Ekv * 4); a.v = (float *) t.up(v, (size_t) Ekv * 4);
-    a.kc = (unsigned short *) t.up(kd.data(), kvb); a.vc = (unsigned short *) t.up(vd.data(), kvb);
-    a.rope = (float *) t.up(rope.data(), rope.size() * 4); if (a.rope) a.rope_cur = a.rope + (size_t) pos * hd; a.scores = (float *) t.up(nullptr, (size_t) H * n_ctx_pad * 4);
-    a.probs = (float *) t.up(nullptr, (size_t) H * n_ctx_pad * 4); a.out = (float *) t.up(nullptr, (size_t) H * hd * 4);
-    if (!a.st || !a.q || !a.k || !a.v || !a.kc || !a.vc || !a.rope || !a.scores || !a.probs || !a.out) return fail("device alloc/copy failed");
-    a.hd = hd; a.Hkv = Hkv; a.n_ctx = n_ctx_pad; a.kq_scale = 1.0f / sqrtf((float) hd); a.prefill_mode = prefill_mode;
-    { const int tiles = std::min(std::max(n_ctx / 64, 1), 64);
-      if (bamd_launch_attention(a, H / Hkv, split_path ? -tiles : tiles, nullptr)) return fail("unsupported head configuration"); }
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(out, a.out, (size_t) H * hd * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(kd.data(), a.kc, kvb, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(vd.data(), a.vc, kvb, hipMemcpyDeviceToHost));
-    kv_from_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    if (probs_h0 && split_path) {
-        std::vector<float> pp((size_t) n_ctx_pad);
-        HIPC(hipMemcpy(pp.data(), a.probs, (size_t) n_ctx_pad * 4, hipMemcpyDeviceToHost));
-        for (int p = 0; p < h.n_kv; ++p) probs_h0[p] = pp[(size_t) ((p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3))];
-    }
-    return 0;
-}
-
-// the K-shift of one layer as kv_update runs it: the delta -> (cos, sin) table from k_shift_table, then bamd_launch_k_shift over the chain-major cache
-extern "C" __attribute__((visibility("default"))) int bamd_op_k_shift(uint16_t * k_cache, int n_ctx, int Hkv, int hd, const int32_t * delta, float freq_base,
-                                                                        float freq_scale, const float * freq_factors, float ext_factor, float attn_factor, int n_ctx_orig) {
-    if (need_device()) return 1;
-    if (Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0) return fail("bad K-shift shape");
-    const int Ekv = Hkv * hd, n_ctx_pad = (n_ctx + 63) / 64 * 64;
-    std::vector<int32_t> idx;
-    std::vector<float> tab;
-    k_shift_table(delta, n_ctx, n_ctx_pad, hd, freq_base, freq_scale, freq_factors, ext_factor, attn_factor, n_ctx_orig, idx, tab);
-    std::vector<uint16_t> kd, vd;
-    kv_to_device_order(k_cache, nullptr, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    Tmp t; const size_t kb = (size_t) n_ctx_pad * Ekv * 2;
-    unsigned short * kc = (unsigned short *) t.up(kd.data(), kb);
-    int32_t * didx = (int32_t *) t.up(idx.data(), idx.size() * 4); float * dtab = (float *) t.up(tab.data(), tab.size() * 4);
-    if (!kc || !didx || !dtab) return fail("device alloc/copy failed");
-    bamd_launch_k_shift(kc, n_ctx, Hkv, hd, didx, dtab, nullptr);
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(kd.data(), kc, kb, hipMemcpyDeviceToHost));
-    kv_from_device_order(k_cache, nullptr, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    return 0;
-}
-
-// the single-token attention after position edits, as bamd_stage_step sets it up when the cells are tracked: step_begin_kernel derives st->cell / st->n_kv
-// from cell_plus1 / n_kv_fixed and leaves the position's (cos, sin) row at rope_cur, the token's cellpos entry is written by a host copy behind the
-// upload of the others, and the shifted-cell instances of the three-launch path run with `tiles` score workgroups per KV head (0: the engine's count)
-extern "C" __attribute__((visibility("default"))) int bamd_op_attention_cells(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
-                                                                                const float * rope_row_h, const int32_t * cellpos, int cell, int n_kv, int H, int Hkv, int hd,
-                                                                                int n_ctx, int pos, int tiles, float * out, float * probs_h0) {
-    if (need_device()) return 1;
-    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || n_ctx % 32 || H % Hkv || H / Hkv > 8) return fail("bad attention shape");
-    if (pos < 0 || pos >= n_ctx || n_kv < 1 || n_kv > n_ctx || cell < 0 || cell >= n_kv || tiles < 0) return fail("bad cell / position / n_kv / tiles");
-    Tmp t; const int Ekv = Hkv * hd, n_ctx_pad = (n_ctx + 63) / 64 * 64; const size_t kvb = (size_t) n_ctx_pad * Ekv * 2;
-    std::vector<float> rope((size_t) n_ctx * hd, 0.f);
-    memcpy(rope.data() + (size_t) pos * hd, rope_row_h, (size_t) hd * 4);
-    std::vector<uint16_t> kd, vd;
-    kv_to_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    std::vector<int32_t> cp((size_t) n_ctx_pad, -1);                       // as kv_activate uploads cells.pos
-    memcpy(cp.data(), cellpos, (size_t) n_ctx * 4);
-    bamd_step_state h; memset(&h, 0, sizeof h);                             // as bamd_stage_step sets it for a tracked cell
-    h.pos_base = pos; h.n_ctx = n_ctx; h.cell_plus1 = cell + 1; h.n_kv_fixed = n_kv;
-    const float embd[256] = {0.0f}; const int32_t tok0 = 0;
-    bamd_attn_args a; memset(&a, 0, sizeof a);
-    bamd_step_state * st = (bamd_step_state *) t.up(&h, sizeof h); a.st = st;
-    int32_t * dcp = (int32_t *) t.up(cp.data(), cp.size() * 4); a.cellpos = dcp;
-    const int32_t * forced = (const int32_t *) t.up(&tok0, 4); int32_t * outt = (int32_t *) t.up(nullptr, 64);
-    const void * dembd = t.up(embd, sizeof embd); float * dx = (float *) t.up(nullptr, sizeof embd);
-    a.q = (float *) t.up(q, (size_t) H * hd * 4); a.k = (float *) t.up(k, (size_t) Ekv * 4); a.v = (float *) t.up(v, (size_t) Ekv * 4);
-    a.kc = (unsigned short *) t.up(kd.data(), kvb); a.vc = (unsigned short *) t.up(vd.data(), kvb);
-    a.rope = (float *) t.up(rope.data(), rope.size() * 4); float * rope_cur = (float *) t.up(nullptr, (size_t) hd * 4); a.rope_cur = rope_cur;
-    a.scores = (float *) t.up(nullptr, (size_t) H * n_ctx_pad * 4); a.probs = (float *) t.up(nullptr, (size_t) H * n_ctx_pad * 4); a.out = (float *) t.up(nullptr, (size_t) H * hd * 4);
-    if (!st || !dcp || !forced || !outt || !dembd || !dx || !a.q || !a.k || !a.v || !a.kc || !a.vc || !a.rope || !rope_cur || !a.scores || !a.probs || !a.out)
-        return fail("device alloc/copy failed");
-    HIPC(hipMemcpy(dcp + cell, &pos, 4, hipMemcpyHostToDevice));            // bamd_stage_step: cellpos[cell] = cells.pos[cell] (find_slot stored pos there)
-    bamd_launch_step_begin(st, forced, 1, outt, dembd, BAMD_F32, 256, 1, dx, 1, nullptr, nullptr, nullptr, a.rope, rope_cur, hd);
-    a.hd = hd; a.Hkv = Hkv; a.n_ctx = n_ctx_pad; a.kq_scale = 1.0f / sqrtf((float) hd); a.prefill_mode = 0;
-    if (tiles == 0) tiles = std::min(std::max(n_ctx / 64, 1), 64);         // enqueue_layers' count at the default BAMD_QK_TILES
-    if (bamd_launch_attention(a, H / Hkv, -tiles, nullptr)) return fail("unsupported head configuration");
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(out, a.out, (size_t) H * hd * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(kd.data(), a.kc, kvb, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(vd.data(), a.vc, kvb, hipMemcpyDeviceToHost));
-    kv_from_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    if (probs_h0) {
-        std::vector<float> pp((size_t) n_ctx_pad);
-        HIPC(hipMemcpy(pp.data(), a.probs, (size_t) n_ctx_pad * 4, hipMemcpyDeviceToHost));
-        for (int p = 0; p < n_kv; ++p) probs_h0[p] = pp[(size_t) ((p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3))];
-    }
-    return 0;
-}
-
-// batched-prefill attention of T tokens at positions pos0 .. pos0 + T - 1 through the launcher enqueue_prefill_batch calls (KV store, then the matrix-core
-// or VALU kernels), with the same argument block: q / k / v packed as one [T][H*hd + 2*Hkv*hd] matrix, batch_pos0p1, lds_ld, scratch block
-extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
-                                                                                const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld,
-                                                                                float * out) {
-    if (need_device()) return 1;
-    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || n_ctx % 32 || H % Hkv || H / Hkv > 8) return fail("bad attention shape");
-    if (T < 1 || T > BAMD_PREFILL_CAP || pos0 < 0 || pos0 + T > n_ctx) return fail("bad micro-batch");
-    if (impl < 0 || impl > 2) return fail("impl must be 0 (launcher's choice), 1 (VALU) or 2 (matrix cores)");
-    const int Ekv = Hkv * hd, E = H * hd, ldq = E + 2 * Ekv, gq = H / Hkv, n_ctx_pad = (n_ctx + 63) / 64 * 64;
-    const int ld_min = std::min((pos0 + T + 63) / 64 * 64, n_ctx_pad);        // attn_lds_ld of the micro-batch's last position
-    if (ld == 0) ld = ld_min;
-    if (ld % 64 || ld < ld_min || ld > n_ctx_pad) return fail("ld must be a multiple of 64 between the padded sequence length and the padded n_ctx");
-    Tmp t; const size_t kvb = (size_t) n_ctx_pad * Ekv * 2;
-    std::vector<float> qkv((size_t) T * ldq);
-    for (int i = 0; i < T; ++i) {
-        memcpy(&qkv[(size_t) i * ldq], q + (size_t) i * E, (size_t) E * 4);
-        memcpy(&qkv[(size_t) i * ldq + E], k + (size_t) i * Ekv, (size_t) Ekv * 4);
-        memcpy(&qkv[(size_t) i * ldq + E + Ekv], v + (size_t) i * Ekv, (size_t) Ekv * 4);
-    }
-    std::vector<uint16_t> kd, vd;
-    kv_to_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    bamd_step_state h; memset(&h, 0, sizeof h);                                 // as enqueue_prefill_batch sets it
-    h.pos_base = pos0; h.pos = pos0; h.n_ctx = n_ctx; h.step = T; h.n_kv = std::min(n_ctx, (pos0 + T + 31) / 32 * 32);
-    bamd_attn_args a; memset(&a, 0, sizeof a);
-    a.st = (bamd_step_state *) t.up(&h, sizeof h);
-    float * dqkv = (float *) t.up(qkv.data(), qkv.size() * 4);
-    a.kc = (unsigned short *) t.up(kd.data(), kvb); a.vc = (unsigned short *) t.up(vd.data(), kvb);
-    a.rope = (float *) t.up(rope, (size_t) n_ctx * hd * 4); a.out = (float *) t.up(nullptr, (size_t) T * E * 4);
-    if (!a.st || !dqkv || !a.kc || !a.vc || !a.rope || !a.out) return fail("device alloc/copy failed");
-    a.q = dqkv; a.k = dqkv + E; a.v = dqkv + E + Ekv;
-    a.hd = hd; a.Hkv = Hkv; a.n_ctx = n_ctx_pad; a.kq_scale = 1.0f / sqrtf((float) hd); a.prefill_mode = 1;
-    a.batch = 1; a.ld_qkv = ldq; a.ld_out = E; a.lds_ld = ld; a.batch_pos0p1 = pos0 + 1;
-    const size_t need = hd == 128 && impl != 1 ? bamd_attention_batch_mfma_scratch(Hkv, gq, T, ld) : 0;
-    if (need && !(a.batch_scratch = (float *) t.up(nullptr, need))) return fail("device alloc failed (scratch block)");
-    if (bamd_launch_attention_batch(a, gq, T, nullptr, impl)) return fail(impl == 2 ? "matrix-core kernel: shape not covered" : "batched attention: unsupported shape");
-    HIPC(hipGetLastError());
-    HIPC(hipDeviceSynchronize());
-    HIPC(hipMemcpy(out, a.out, (size_t) T * E * 4, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(kd.data(), a.kc, kvb, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(vd.data(), a.vc, kvb, hipMemcpyDeviceToHost));
-    kv_from_device_order(k_cache, v_cache_t, n_ctx, n_ctx_pad, Hkv, hd, kd, vd);
-    return 0;
-}
-
-// ---- micro-benchmark of one mat-vec launch shape (random resident weights; HIP-event timing of `iters` launches) ----
-extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type, int nrows, int k, int pro, int epi, int mode, int iters,
-                                                                        float * us_per_launch) {
-    if (need_device()) return 1;
-    if (!bamd_is_kquant(type) || k % 256 || nrows % 8) return fail("bad type/shape");
-    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows;
-    std::vector<uint8_t> hw(wb);
-    uint32_t sd = 12345u; for (size_t i = 0; i < wb; ++i) { sd = sd * 1664525u + 1013904223u; hw[i] = (uint8_t) (sd >> 24); }
-    const int bb = bamd_block_bytes(type);
-    for (size_t b = 0; b < wb / bb; ++b) {                    // sane f16 scales (0x1c00 ~ 0.0039)
-        uint8_t * p = hw.data() + b * bb;
-        if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; } else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
-    }
-    std::vector<float> hx((size_t) k); for (int i = 0; i < k; ++i) { sd = sd * 1664525u + 1013904223u; hx[i] = (float) (int) (sd >> 8) / 8388608.0f - 1.0f; }
-    std::vector<float> hn((size_t) k, 1.0f);
-    const size_t wbs = bamd_stream_bytes(type, k, nrows);
-    void * raw = t.up(hw.data(), wb), * strA = t.up(nullptr, wbs), * strB = epi == BAMD_EPI_SILU_MUL ? t.up(nullptr, wbs) : nullptr;
-    float * dx = (float *) t.up(hx.data(), (size_t) k * 4), * dw = (float *) t.up(hn.data(), (size_t) k * 4);
-    float * dres = (float *) t.up(nullptr, (size_t) nrows * 4), * dy = (float *) t.up(nullptr, (size_t) nrows * 4);
-    unsigned long long * key = (unsigned long long *) t.up(nullptr, 8);
-    if (!raw || !strA || !dx || !dw || !dres || !dy || !key) return fail("device alloc/copy failed");
-    HIPC(hipMemset(dres, 0, (size_t) nrows * 4)); HIPC(hipMemset(key, 0, 8));
-    bamd_launch_repack(raw, strA, type, nrows, k, nullptr);
-    if (strB) bamd_launch_repack(raw, strB, type, nrows, k, nullptr);
-    bamd_mv_args a; memset(&a, 0, sizeof a);
-    a.seg[0].w = strA; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows; a.nseg = 1;
-    if (strB) { a.seg[1] = a.seg[0]; a.seg[1].w = strB; a.nseg = 2; }
-    a.x = dx; a.normw = dw; a.eps = 1e-5f; a.K = k; a.res = dres; a.best_key = key; a.mode = mode;
-    const int ncu = n_cu0();
-    if (iters < 1) return fail("iters < 1");
-    OwnedStream os; HIPC(hipStreamCreate(&os.s));
-    hipStream_t s = os.s;
-    for (int i = 0; i < 3; ++i) bamd_launch_matvec(a, pro, epi, ncu, s);
-    HIPC(hipGetLastError());
-    EventPair ev; HIPC(ev.create());
-    HIPC(hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters; ++i) bamd_launch_matvec(a, pro, epi, ncu, s);
-    HIPC(hipEventRecord(ev.b, s));
-    HIPC(hipStreamSynchronize(s));
-    float ms = 0.f; HIPC(hipEventElapsedTime(&ms, ev.a, ev.b));
-    *us_per_launch = ms * 1000.0f / (float) iters;
     return 0;
 }

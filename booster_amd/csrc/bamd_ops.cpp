@@ -1,0 +1,339 @@
+// bamd_ops.cpp — op-level entry points (host in / host out) and the mat-vec micro-benchmark of libbooster_amd.so: thin wrappers that run the SAME kernels as the
+// model runtime (bamd_engine.cpp) on device 0.  They are what the tests and tools call; nothing here touches bamd_model / bamd_context.
+#include "../../include/bamd.h"
+#include "bamd_engine_internal.h"
+#include "bamd_formats.h"
+#include "bamd_kernels.h"
+
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+
+struct Tmp {
+    std::vector<void *> p;
+    ~Tmp() { for (void * x : p) hipFree(x); }
+    void * up(const void * h, size_t n) { void * d = nullptr; if (hipMalloc(&d, n + 4096) != hipSuccess) return nullptr; p.push_back(d); if (h && hipMemcpy(d, h, n, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return d; }
+};
+static int need_device() {
+    if (bamd_device_count() <= 0) return fail("no HIP device available: libbooster_amd has no CPU fallback");
+    HIPC(hipSetDevice(0));
+    return 0;
+}
+// the launches went through and ran: `bytes` of their result at `src` to the host
+static int finish(void * dst, const void * src, size_t bytes) {
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    HIPC(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+static int n_cu0() { hipDeviceProp_t p; if (hipGetDeviceProperties(&p, 0) != hipSuccess) return 256; return p.multiProcessorCount > 0 ? p.multiProcessorCount : 256; }
+
+extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_K(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks) {
+    if (need_device()) return 1;
+    if (k <= 0 || k % 256) return fail("k must be a positive multiple of 256");
+    Tmp t; const size_t ob = (size_t) (k / 256) * 292;
+    float * dx = (float *) t.up(x, (size_t) k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr; void * dout = t.up(nullptr, ob);
+    if (!dx || !dout || (norm_w && !dw)) return fail("device alloc/copy failed");
+    HIPC(hipMemset(dout, 0, ob));
+    bamd_launch_quantize_q8k_test(dx, dw, eps, (int) k, norm_w != nullptr, dout, nullptr);
+    return finish(out_blocks, dout, ob);
+}
+
+static int op_matvec(int type, const void * wA, const void * wB, int nrows, int k, const float * x, const float * norm_w, float eps,
+                     const float * residual, float * y, int epi, int mode, unsigned long long * best_key = nullptr) {
+    if (need_device()) return 1;
+    if (!bamd_is_kquant(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
+    const int nrows_pad = (nrows + 7) / 8 * 8;
+    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
+    void * rawA = t.up(wA, wb), * strA = t.up(nullptr, wbp), * rawB = nullptr, * strB = nullptr;
+    if (wB) { rawB = t.up(wB, wb); strB = t.up(nullptr, wbp); }
+    if (strA) HIPC(hipMemset(strA, 0, wbp));
+    if (strB) HIPC(hipMemset(strB, 0, wbp));
+    float * dx = (float *) t.up(x, (size_t) k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr;
+    float * dres = residual ? (float *) t.up(residual, (size_t) nrows * 4) : nullptr; float * dy = (float *) t.up(nullptr, (size_t) nrows * 4);
+    unsigned long long * key = (unsigned long long *) t.up(nullptr, 8);
+    if (!rawA || !strA || !dx || !dy || !key || (wB && (!rawB || !strB)) || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
+    HIPC(hipMemset(key, 0, 8));
+    bamd_launch_repack(rawA, strA, type, nrows, k, nullptr);
+    if (wB) bamd_launch_repack(rawB, strB, type, nrows, k, nullptr);
+    bamd_mv_args a; memset(&a, 0, sizeof a);
+    a.seg[0].w = strA; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows_pad; a.seg[0].nvalid = nrows; a.nseg = 1;
+    if (wB) { a.seg[1] = a.seg[0]; a.seg[1].w = strB; a.nseg = 2; }
+    a.x = dx; a.normw = dw; a.eps = eps; a.K = k; a.res = dres; a.best_key = key; a.mode = mode;
+    bamd_launch_matvec(a, norm_w ? BAMD_PRO_NORM : BAMD_PRO_PLAIN, epi, n_cu0(), nullptr);
+    if (finish(y, dy, (size_t) nrows * 4)) return 1;
+    if (best_key) HIPC(hipMemcpy(best_key, key, 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w, float eps,
+                                   const float * residual, float * y, int mode) {
+    return op_matvec(type, w_raw, nullptr, nrows, k, x, norm_w, eps, residual, y, residual ? BAMD_EPI_ADD : BAMD_EPI_STORE, mode);
+}
+// the lm_head launch (enqueue_lm_head) with its arg-max epilogue; the row is decoded from the key as step_begin_kernel decodes it
+extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec_argmax(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w,
+                                                                                 float eps, float * y, int mode, int32_t * row) {
+    unsigned long long key = 0ull;
+    if (op_matvec(type, w_raw, nullptr, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_ARGMAX, mode, &key)) return 1;
+    *row = key ? (int32_t) (0xffffffffu - (uint32_t) (key & 0xffffffffull)) : -1;
+    return 0;
+}
+// batched mat-mul of T activation rows against one matrix through the prefill kernels: impl 0 = integer-dot kernel, 2 = matrix-core kernel (1 and 3 were the generations removed in round 6)
+extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const float * x, int T, const float * norm_w,
+                                                                              float eps, const float * residual, float * y, int impl) {
+    if (need_device()) return 1;
+    if (!bamd_is_kquant(type) || k <= 0 || k % 256 || nrows <= 0 || T <= 0) return fail("bad type/shape");
+    const int nrows_pad = (nrows + 7) / 8 * 8;
+    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
+    void * raw = t.up(w_raw, wb), * str = t.up(nullptr, wbp);
+    float * dx = (float *) t.up(x, (size_t) T * k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr;
+    float * dres = residual ? (float *) t.up(residual, (size_t) T * nrows * 4) : nullptr; float * dy = (float *) t.up(nullptr, (size_t) T * nrows * 4);
+    void * blob = t.up(nullptr, (size_t) T * bamd_blob_bytes(k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
+    if (!raw || !str || !dx || !dy || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
+    HIPC(hipMemset(str, 0, wbp));
+    bamd_launch_repack(raw, str, type, nrows, k, nullptr);
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr);
+    if (impl == 2) {                                                // the matrix-core kernel: side table built here, as the engine builds it at model load
+        void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
+        if (!aux) return fail("device alloc failed");
+        bamd_launch_prefill_aux(str, type, nrows_pad, k, aux, nullptr);
+        if (bamd_launch_matmul_mfma2(str, aux, type, nrows, nrows_pad, k, blob16, T, dy, dres, dres ? BAMD_EPI_ADD : BAMD_EPI_STORE, nrows, nullptr)) return fail("MFMA path: unsupported type/shape");
+    } else {
+        bamd_mm_args a; memset(&a, 0, sizeof a);
+        a.seg[0].w = str; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows_pad; a.seg[0].nvalid = nrows; a.nseg = 1;
+        a.blob = (const uint8_t *) blob; a.K = k; a.T = T; a.ldo = nrows; a.res = dres;
+        if (bamd_launch_matmul_batch(a, residual ? BAMD_EPI_ADD : BAMD_EPI_STORE, n_cu0(), nullptr)) return fail("batched mat-mul: unsupported shape");
+    }
+    return finish(y, dy, (size_t) T * nrows * 4);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_op_ffn_gate_up(int type, const void * wg_raw, const void * wu_raw, int nrows, int k, const float * x, const float * norm_w,
+                                   float eps, float * y) {
+    return op_matvec(type, wg_raw, wu_raw, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_SILU_MUL, 0);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y) {
+    if (need_device()) return 1;
+    if (type != BAMD_F32 && type != BAMD_F16 && !bamd_is_kquant(type)) return fail("bad type");
+    if (k <= 0 || (bamd_is_kquant(type) && k % 256)) return fail("bad row length");
+    if (row < 0 || row >= nrows) return fail("row out of range");
+    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows;
+    void * raw = t.up(w_raw, wb); float * dy = (float *) t.up(nullptr, (size_t) k * 4);
+    bamd_step_state h; memset(&h, 0, sizeof h); h.n_ctx = 32;
+    bamd_step_state * st = (bamd_step_state *) t.up(&h, sizeof h);
+    int32_t * forced = (int32_t *) t.up(&row, 4); int32_t * outt = (int32_t *) t.up(nullptr, 64);
+    if (!raw || !dy || !st || !forced || !outt) return fail("device alloc/copy failed");
+    bamd_launch_step_begin(st, forced, 1, outt, raw, type, k, nrows, dy, 1, nullptr);
+    return finish(y, dy, (size_t) k * 4);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_op_rope_row(int pos, int n_dims, float freq_base, float freq_scale, const float * freq_factors, float * row) {
+    rope_row(row, pos, n_dims, freq_base, freq_scale, freq_factors, 0.0f, 1.0f, 8192, 32.0f, 1.0f);
+    return 0;
+}
+
+// reference layout <-> chain-major device layout of the KV cache (bamd_device.h, "Attention": kperm / vperm)
+static inline int kperm_host(int n) { const int l = n >> 3; return ((l >> 3) << 6) + ((n & 7) << 3) + (l & 7); }
+static inline int vperm_host(int p) { return (p & ~63) + ((p & 7) << 3) + ((p & 63) >> 3); }
+
+// What the attention ops (and, for its K half, the K-shift op) share: the temporaries of one call with ONE record of whether every upload worked, the KV cache
+// of one layer carried to the device in chain-major order and back, and the bamd_attn_args fields that every path sets the same way
+struct AttnFixture {
+    Tmp t; bool good = true;
+    const int n_ctx, Hkv, hd, n_ctx_pad; const size_t kvb;
+    std::vector<uint16_t> kd, vd;
+    unsigned short * kc = nullptr, * vc = nullptr;
+    AttnFixture(int n_ctx_, int Hkv_, int hd_) : n_ctx(n_ctx_), Hkv(Hkv_), hd(hd_), n_ctx_pad((n_ctx_ + 63) / 64 * 64), kvb((size_t) n_ctx_pad * Hkv_ * hd_ * 2) {}
+    void * up(const void * h, size_t n) { void * d = t.up(h, n); if (!d) good = false; return d; }
+    bool ok() const { return good; }
+    // reference order -> device order (to_device) or back; v_ref null: the K cache only
+    void reorder(bool to_device, uint16_t * k_ref, uint16_t * v_ref) {
+        const int Ekv = Hkv * hd;
+        for (int i = 0; i < n_ctx; ++i) for (int h = 0; h < Hkv; ++h) for (int n = 0; n < hd; ++n) {
+            uint16_t & r = k_ref[(size_t) i * Ekv + h * hd + n], & d = kd[(size_t) i * Ekv + h * hd + kperm_host(n)];
+            if (to_device) d = r; else r = d;
+        }
+        if (v_ref) for (int r = 0; r < Ekv; ++r) for (int p = 0; p < n_ctx; ++p) {
+            uint16_t & x = v_ref[(size_t) r * n_ctx + p], & d = vd[(size_t) r * n_ctx_pad + vperm_host(p)];
+            if (to_device) d = x; else x = d;
+        }
+    }
+    void kv_up(uint16_t * k_ref, uint16_t * v_ref) {
+        kd.assign((size_t) n_ctx_pad * Hkv * hd, 0); vd.assign(v_ref ? (size_t) n_ctx_pad * Hkv * hd : 0, 0);
+        reorder(true, k_ref, v_ref);
+        kc = (unsigned short *) up(kd.data(), kvb);
+        if (v_ref) vc = (unsigned short *) up(vd.data(), kvb);
+    }
+    int kv_down(uint16_t * k_ref, uint16_t * v_ref) {
+        HIPC(hipMemcpy(kd.data(), kc, kvb, hipMemcpyDeviceToHost));
+        if (v_ref) HIPC(hipMemcpy(vd.data(), vc, kvb, hipMemcpyDeviceToHost));
+        reorder(false, k_ref, v_ref);
+        return 0;
+    }
+    void args(bamd_attn_args & a, int prefill_mode) const { a.kc = kc; a.vc = vc; a.hd = hd; a.Hkv = Hkv; a.n_ctx = n_ctx_pad; a.kq_scale = 1.0f / sqrtf((float) hd); a.prefill_mode = prefill_mode; }
+    void rows(bamd_attn_args & a, int H) { a.scores = (float *) up(nullptr, (size_t) H * n_ctx_pad * 4); a.probs = (float *) up(nullptr, (size_t) H * n_ctx_pad * 4); a.out = (float *) up(nullptr, (size_t) H * hd * 4); }   // single-token paths
+    int down(const bamd_attn_args & a, float * out, size_t out_floats, uint16_t * k_ref, uint16_t * v_ref) { return finish(out, a.out, out_floats * 4) || kv_down(k_ref, v_ref); }   // after the launch
+    // the first n probabilities of query head 0 (stored in V^T position order)
+    int probs_down(const bamd_attn_args & a, int n, float * probs_h0) {
+        std::vector<float> pp((size_t) n_ctx_pad);
+        HIPC(hipMemcpy(pp.data(), a.probs, (size_t) n_ctx_pad * 4, hipMemcpyDeviceToHost));
+        for (int p = 0; p < n; ++p) probs_h0[p] = pp[(size_t) vperm_host(p)];
+        return 0;
+    }
+};
+
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                 const float * rope_row_h, int H, int Hkv, int hd, int n_ctx, int pos, int prefill_mode, float * out,
+                                 float * probs_h0) {
+    const bool split_path = (prefill_mode & 2) != 0;   // bit 1: force the three-kernel (long-context) path
+    prefill_mode &= 1;
+    if (need_device()) return 1;
+    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || pos < 0 || pos >= n_ctx || n_ctx % 32 || H % Hkv) return fail("bad attention shape");
+    AttnFixture f(n_ctx, Hkv, hd); const int Ekv = Hkv * hd;
+    std::vector<float> rope((size_t) n_ctx * hd, 0.f);
+    memcpy(rope.data() + (size_t) pos * hd, rope_row_h, (size_t) hd * 4);
+    bamd_step_state h; memset(&h, 0, sizeof h); h.pos = pos; h.n_ctx = n_ctx; h.n_kv = std::min(n_ctx, std::max(32, (pos + 1 + 31) / 32 * 32));
+    bamd_attn_args a; memset(&a, 0, sizeof a);
+    a.st = (bamd_step_state *) f.up(&h, sizeof h);
+    a.q = (float *) f.up(q, (size_t) H * hd * 4); a.k = (float *) f.up(k, (size_t) Ekv * 4); a.v = (float *) f.up(v, (size_t) Ekv * 4);
+    f.kv_up(k_cache, v_cache_t);
+    a.rope = (float *) f.up(rope.data(), rope.size() * 4); if (a.rope) a.rope_cur = a.rope + (size_t) pos * hd;
+    f.rows(a, H);
+    if (!f.ok()) return fail("device alloc/copy failed");
+    f.args(a, prefill_mode);
+    { const int tiles = std::min(std::max(n_ctx / 64, 1), 64);
+      if (bamd_launch_attention(a, H / Hkv, split_path ? -tiles : tiles, nullptr)) return fail("unsupported head configuration"); }
+    if (f.down(a, out, (size_t) H * hd, k_cache, v_cache_t)) return 1;
+    return probs_h0 && split_path ? f.probs_down(a, h.n_kv, probs_h0) : 0;
+}
+
+// the K-shift of one layer as kv_update runs it: the delta -> (cos, sin) table from k_shift_table, then bamd_launch_k_shift over the chain-major cache
+extern "C" __attribute__((visibility("default"))) int bamd_op_k_shift(uint16_t * k_cache, int n_ctx, int Hkv, int hd, const int32_t * delta, float freq_base,
+                                                                        float freq_scale, const float * freq_factors, float ext_factor, float attn_factor, int n_ctx_orig) {
+    if (need_device()) return 1;
+    if (Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0) return fail("bad K-shift shape");
+    AttnFixture f(n_ctx, Hkv, hd);
+    std::vector<int32_t> idx;
+    std::vector<float> tab;
+    k_shift_table(delta, n_ctx, f.n_ctx_pad, hd, freq_base, freq_scale, freq_factors, ext_factor, attn_factor, n_ctx_orig, idx, tab);
+    f.kv_up(k_cache, nullptr);
+    int32_t * didx = (int32_t *) f.up(idx.data(), idx.size() * 4); float * dtab = (float *) f.up(tab.data(), tab.size() * 4);
+    if (!f.ok()) return fail("device alloc/copy failed");
+    bamd_launch_k_shift(f.kc, n_ctx, Hkv, hd, didx, dtab, nullptr);
+    HIPC(hipGetLastError());
+    HIPC(hipDeviceSynchronize());
+    return f.kv_down(k_cache, nullptr);
+}
+
+// the single-token attention after position edits, as bamd_stage_step sets it up when the cells are tracked: step_begin_kernel derives st->cell / st->n_kv
+// from cell_plus1 / n_kv_fixed and leaves the position's (cos, sin) row at rope_cur, the token's cellpos entry is written by a host copy behind the
+// upload of the others, and the shifted-cell instances of the three-launch path run with `tiles` score workgroups per KV head (0: the engine's count)
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention_cells(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                                                                const float * rope_row_h, const int32_t * cellpos, int cell, int n_kv, int H, int Hkv, int hd,
+                                                                                int n_ctx, int pos, int tiles, float * out, float * probs_h0) {
+    if (need_device()) return 1;
+    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || n_ctx % 32 || H % Hkv || H / Hkv > 8) return fail("bad attention shape");
+    if (pos < 0 || pos >= n_ctx || n_kv < 1 || n_kv > n_ctx || cell < 0 || cell >= n_kv || tiles < 0) return fail("bad cell / position / n_kv / tiles");
+    AttnFixture f(n_ctx, Hkv, hd); const int Ekv = Hkv * hd;
+    std::vector<float> rope((size_t) n_ctx * hd, 0.f);
+    memcpy(rope.data() + (size_t) pos * hd, rope_row_h, (size_t) hd * 4);
+    std::vector<int32_t> cp((size_t) f.n_ctx_pad, -1);                     // as kv_activate uploads cells.pos
+    memcpy(cp.data(), cellpos, (size_t) n_ctx * 4);
+    bamd_step_state h; memset(&h, 0, sizeof h);                             // as bamd_stage_step sets it for a tracked cell
+    h.pos_base = pos; h.n_ctx = n_ctx; h.cell_plus1 = cell + 1; h.n_kv_fixed = n_kv;
+    const float embd[256] = {0.0f}; const int32_t tok0 = 0;
+    bamd_attn_args a; memset(&a, 0, sizeof a);
+    bamd_step_state * st = (bamd_step_state *) f.up(&h, sizeof h); a.st = st;
+    int32_t * dcp = (int32_t *) f.up(cp.data(), cp.size() * 4); a.cellpos = dcp;
+    const int32_t * forced = (const int32_t *) f.up(&tok0, 4); int32_t * outt = (int32_t *) f.up(nullptr, 64);
+    const void * dembd = f.up(embd, sizeof embd); float * dx = (float *) f.up(nullptr, sizeof embd);
+    a.q = (float *) f.up(q, (size_t) H * hd * 4); a.k = (float *) f.up(k, (size_t) Ekv * 4); a.v = (float *) f.up(v, (size_t) Ekv * 4);
+    f.kv_up(k_cache, v_cache_t);
+    a.rope = (float *) f.up(rope.data(), rope.size() * 4); float * rope_cur = (float *) f.up(nullptr, (size_t) hd * 4); a.rope_cur = rope_cur;
+    f.rows(a, H);
+    if (!f.ok()) return fail("device alloc/copy failed");
+    HIPC(hipMemcpy(dcp + cell, &pos, 4, hipMemcpyHostToDevice));            // bamd_stage_step: cellpos[cell] = cells.pos[cell] (find_slot stored pos there)
+    bamd_launch_step_begin(st, forced, 1, outt, dembd, BAMD_F32, 256, 1, dx, 1, nullptr, nullptr, nullptr, a.rope, rope_cur, hd);
+    f.args(a, 0);
+    if (tiles == 0) tiles = std::min(std::max(n_ctx / 64, 1), 64);         // enqueue_layers' count at the default BAMD_QK_TILES
+    if (bamd_launch_attention(a, H / Hkv, -tiles, nullptr)) return fail("unsupported head configuration");
+    if (f.down(a, out, (size_t) H * hd, k_cache, v_cache_t)) return 1;
+    return probs_h0 ? f.probs_down(a, n_kv, probs_h0) : 0;
+}
+
+// batched-prefill attention of T tokens at positions pos0 .. pos0 + T - 1 through the launcher enqueue_prefill_batch calls (KV store, then the matrix-core
+// or VALU kernels), with the same argument block: q / k / v packed as one [T][H*hd + 2*Hkv*hd] matrix, batch_pos0p1, lds_ld, scratch block
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                                                                const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld,
+                                                                                float * out) {
+    if (need_device()) return 1;
+    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || n_ctx % 32 || H % Hkv || H / Hkv > 8) return fail("bad attention shape");
+    if (T < 1 || T > BAMD_PREFILL_CAP || pos0 < 0 || pos0 + T > n_ctx) return fail("bad micro-batch");
+    if (impl < 0 || impl > 2) return fail("impl must be 0 (launcher's choice), 1 (VALU) or 2 (matrix cores)");
+    AttnFixture f(n_ctx, Hkv, hd);
+    const int Ekv = Hkv * hd, E = H * hd, ldq = E + 2 * Ekv, gq = H / Hkv;
+    const int ld_min = std::min((pos0 + T + 63) / 64 * 64, f.n_ctx_pad);      // attn_lds_ld of the micro-batch's last position
+    if (ld == 0) ld = ld_min;
+    if (ld % 64 || ld < ld_min || ld > f.n_ctx_pad) return fail("ld must be a multiple of 64 between the padded sequence length and the padded n_ctx");
+    std::vector<float> qkv((size_t) T * ldq);
+    for (int i = 0; i < T; ++i) {
+        memcpy(&qkv[(size_t) i * ldq], q + (size_t) i * E, (size_t) E * 4);
+        memcpy(&qkv[(size_t) i * ldq + E], k + (size_t) i * Ekv, (size_t) Ekv * 4);
+        memcpy(&qkv[(size_t) i * ldq + E + Ekv], v + (size_t) i * Ekv, (size_t) Ekv * 4);
+    }
+    bamd_step_state h; memset(&h, 0, sizeof h);                                 // as enqueue_prefill_batch sets it
+    h.pos_base = pos0; h.pos = pos0; h.n_ctx = n_ctx; h.step = T; h.n_kv = std::min(n_ctx, (pos0 + T + 31) / 32 * 32);
+    bamd_attn_args a; memset(&a, 0, sizeof a);
+    a.st = (bamd_step_state *) f.up(&h, sizeof h);
+    float * dqkv = (float *) f.up(qkv.data(), qkv.size() * 4);
+    f.kv_up(k_cache, v_cache_t);
+    a.rope = (float *) f.up(rope, (size_t) n_ctx * hd * 4); a.out = (float *) f.up(nullptr, (size_t) T * E * 4);
+    if (!f.ok()) return fail("device alloc/copy failed");
+    a.q = dqkv; a.k = dqkv + E; a.v = dqkv + E + Ekv;
+    f.args(a, 1);
+    a.batch = 1; a.ld_qkv = ldq; a.ld_out = E; a.lds_ld = ld; a.batch_pos0p1 = pos0 + 1;
+    const size_t need = hd == 128 && impl != 1 ? bamd_attention_batch_mfma_scratch(Hkv, gq, T, ld) : 0;
+    if (need && !(a.batch_scratch = (float *) f.up(nullptr, need))) return fail("device alloc failed (scratch block)");
+    if (bamd_launch_attention_batch(a, gq, T, nullptr, impl)) return fail(impl == 2 ? "matrix-core kernel: shape not covered" : "batched attention: unsupported shape");
+    return f.down(a, out, (size_t) T * E, k_cache, v_cache_t);
+}
+
+// ---- micro-benchmark of one mat-vec launch shape (random resident weights; HIP-event timing of `iters` launches) ----
+extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type, int nrows, int k, int pro, int epi, int mode, int iters,
+                                                                        float * us_per_launch) {
+    if (need_device()) return 1;
+    if (!bamd_is_kquant(type) || k % 256 || nrows % 8) return fail("bad type/shape");
+    Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows;
+    std::vector<uint8_t> hw(wb);
+    uint32_t sd = 12345u; for (size_t i = 0; i < wb; ++i) { sd = sd * 1664525u + 1013904223u; hw[i] = (uint8_t) (sd >> 24); }
+    const int bb = bamd_block_bytes(type);
+    for (size_t b = 0; b < wb / bb; ++b) {                    // sane f16 scales (0x1c00 ~ 0.0039)
+        uint8_t * p = hw.data() + b * bb;
+        if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; } else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
+    }
+    std::vector<float> hx((size_t) k); for (int i = 0; i < k; ++i) { sd = sd * 1664525u + 1013904223u; hx[i] = (float) (int) (sd >> 8) / 8388608.0f - 1.0f; }
+    std::vector<float> hn((size_t) k, 1.0f);
+    const size_t wbs = bamd_stream_bytes(type, k, nrows);
+    void * raw = t.up(hw.data(), wb), * strA = t.up(nullptr, wbs), * strB = epi == BAMD_EPI_SILU_MUL ? t.up(nullptr, wbs) : nullptr;
+    float * dx = (float *) t.up(hx.data(), (size_t) k * 4), * dw = (float *) t.up(hn.data(), (size_t) k * 4);
+    float * dres = (float *) t.up(nullptr, (size_t) nrows * 4), * dy = (float *) t.up(nullptr, (size_t) nrows * 4);
+    unsigned long long * key = (unsigned long long *) t.up(nullptr, 8);
+    if (!raw || !strA || !dx || !dw || !dres || !dy || !key) return fail("device alloc/copy failed");
+    HIPC(hipMemset(dres, 0, (size_t) nrows * 4)); HIPC(hipMemset(key, 0, 8));
+    bamd_launch_repack(raw, strA, type, nrows, k, nullptr);
+    if (strB) bamd_launch_repack(raw, strB, type, nrows, k, nullptr);
+    bamd_mv_args a; memset(&a, 0, sizeof a);
+    a.seg[0].w = strA; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows; a.nseg = 1;
+    if (strB) { a.seg[1] = a.seg[0]; a.seg[1].w = strB; a.nseg = 2; }
+    a.x = dx; a.normw = dw; a.eps = 1e-5f; a.K = k; a.res = dres; a.best_key = key; a.mode = mode;
+    const int ncu = n_cu0();
+    if (iters < 1) return fail("iters < 1");
+    OwnedStream os; HIPC(hipStreamCreate(&os.s));
+    hipStream_t s = os.s;
+    for (int i = 0; i < 3; ++i) bamd_launch_matvec(a, pro, epi, ncu, s);
+    HIPC(hipGetLastError());
+    EventPair ev; HIPC(ev.create());
+    HIPC(hipEventRecord(ev.a, s));
+    for (int i = 0; i < iters; ++i) bamd_launch_matvec(a, pro, epi, ncu, s);
+    HIPC(hipEventRecord(ev.b, s));
+    HIPC(hipStreamSynchronize(s));
+    float ms = 0.f; HIPC(hipEventElapsedTime(&ms, ev.a, ev.b));
+    *us_per_launch = ms * 1000.0f / (float) iters;
+    return 0;
+}
