@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("BAMD_LIB") or os.path.join(_HERE, "lib", "libbooster_
 _lib = None
 
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
+Q2_K, Q3_K = 10, 11
 
 
 class BamdError(RuntimeError):

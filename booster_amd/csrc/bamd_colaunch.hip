@@ -32,7 +32,7 @@ __device__ __forceinline__ void wo_role(const bamd_mv_args & a, const ProArgs & 
                                         const bamd_step_state * st, const int il, const int ring_delay_in, uint32_t * err) {
     const int ring_delay = ring_delay_in & 0xff; const bool poll_sleep = (ring_delay_in >> 8) & 1;
     typedef typename RecOf<TYPE>::type REC;
-    constexpr int RECB = TYPE == BAMD_Q4_K ? BAMD_RECB_Q4K : TYPE == BAMD_Q5_K ? BAMD_RECB_Q5K : 1680;
+    constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");
     const int nb = pa.K >> 8;
     const int lane = threadIdx.x & 63, wave = wave_id(), r8 = lane >> 3;
     const int i0 = wave * NBW;
@@ -195,7 +195,7 @@ int bamd_launch_attn_wo(const bamd_attn_args & t, int gq, const bamd_mv_args & w
     const size_t lds = lds_wo > lds_at ? lds_wo : lds_at;
     const dim3 grid(n_cu), block(512);
 #define BAMD_CL(LG_, T_) BAMD_LAUNCH((attn_wo_kernel<LG_, T_>), grid, block, lds, s, t, gq, wo, gran, il, extra, g_ring_delay, err)
-#define BAMD_CL_T(LG_) do { if (type == BAMD_Q4_K) BAMD_CL(LG_, BAMD_Q4_K); else if (type == BAMD_Q5_K) BAMD_CL(LG_, BAMD_Q5_K); else if (type == BAMD_Q6_K) BAMD_CL(LG_, BAMD_Q6_K); else return 1; } while (0)
+#define BAMD_CL_T(LG_) do { if (type == BAMD_Q4_K) BAMD_CL(LG_, BAMD_Q4_K); else if (type == BAMD_Q5_K) BAMD_CL(LG_, BAMD_Q5_K); else if (type == BAMD_Q6_K) BAMD_CL(LG_, BAMD_Q6_K); else if (type == BAMD_Q3_K) BAMD_CL(LG_, BAMD_Q3_K); else if (type == BAMD_Q2_K) BAMD_CL(LG_, BAMD_Q2_K); else return 1; } while (0)
     switch (t.hd >> 6) {
         case 1: BAMD_CL_T(1); break;
         case 2: BAMD_CL_T(2); break;

@@ -25,7 +25,10 @@
 //   ggml_v_silu / ggml_vec_silu_f32  ggml/src/ggml.c:2524-2531, :2595-2617
 //   tinyBLAS<8,..,fp16,float,float>  ggml/src/llamafile/sgemm.cpp:405-431 (KQ at T=1, KQV always)
 //   ggml_vec_dot_f16                 ggml/src/ggml.c:2038-2079 (KQ at T>1)
+//   ggml_vec_dot_q3_K_q8_K (AVX2)    ggml/src/ggml-quants.c:6161-6263
+//   ggml_vec_dot_q2_K_q8_K (AVX2)    ggml/src/ggml-quants.c:5553-5617
 //   dequantize_row_q{4,5,6}_K        ggml/src/ggml-quants.c:2548, :2756, :2970 (embedding get_rows)
+//   dequantize_row_q{2,3}_K          ggml/src/ggml-quants.c:1972, :2320
 //   CUDA counterparts replaced       ggml/src/ggml-cuda/mmvq.cu:50-130, quantize.cu:4-38, norm.cu:101-131,
 //                                    rope.cu:31-69, softmax.cu:14-116, cpy.cu:33-59, unary.cu:25-32
 #pragma once
@@ -447,6 +450,8 @@ struct RowAcc { float acc, accm; };
 struct RecQ4K { uint4 qs, hd; uint32_t mn47; };              // mn47: BAMD_XSCALES = 1 only (bamd_formats.h); dead otherwise
 struct RecQ5K { uint4 qs, hd; uint32_t qh, mn47; };
 struct RecQ6K { uint4 ql; uint2 qh, sc; uint32_t d; };
+struct RecQ3K { uint2 qs; uint32_t hm, sc0, sc1, sc2, d; }; // sc0..2: the file's 12 packed scale bytes of the row
+struct RecQ2K { uint2 qs; uint4 sc; uint32_t dd; };          // sc: scales[16] (low nibble scale, high nibble min); dd = d | dmin << 16
 
 // Pin a loaded register at its point of use: without this, LLVM folds the first ALU op on a ring register into
 // the loop PHI (i.e. executes it right after the load, one iteration early), which forces s_waitcnt vmcnt(0) at
@@ -462,6 +467,8 @@ __device__ __forceinline__ void pin_rec(RecQ4K & R) { pin(R.qs); pin(R.hd); }
 __device__ __forceinline__ void pin_rec(RecQ5K & R) { pin(R.qs); pin(R.hd); pin(R.qh); }
 #endif
 __device__ __forceinline__ void pin_rec(RecQ6K & R) { pin(R.ql); pin(R.qh); pin(R.sc); pin(R.d); }
+__device__ __forceinline__ void pin_rec(RecQ3K & R) { pin(R.qs); pin(R.hm); pin(R.sc0); pin(R.sc1); pin(R.sc2); pin(R.d); }
+__device__ __forceinline__ void pin_rec(RecQ2K & R) { pin(R.qs); pin(R.sc); pin(R.dd); }
 
 // Weight records are fetched with BUFFER loads: the matrix is one 128-bit resource descriptor in scalar registers, the record a scalar
 // byte offset (soffset), the lane's share a constant 32-bit vector offset + an immediate — no vector instruction computes an address
@@ -531,6 +538,19 @@ __device__ __forceinline__ void load_rec(RecQ6K & R, bamd_rsrc rs, int soff, int
     R.qh = bl64(rs, 1024u + l * 8u, soff);
     R.sc = bl64(rs, 1536u + (l >> 3) * 16u + ((l >> 2) & 1u) * 8u, soff);
     R.d  = bl16(rs, 1664u + (l >> 3) * 2u, soff);
+}
+__device__ __forceinline__ void load_rec(RecQ3K & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane;
+    R.qs = bl64(rs, l * 8u, soff);
+    R.hm = bl32(rs, 512u + l * 4u, soff);
+    R.sc0 = bl32(rs, 768u + (l >> 3) * 12u, soff); R.sc1 = bl32(rs, 772u + (l >> 3) * 12u, soff); R.sc2 = bl32(rs, 776u + (l >> 3) * 12u, soff);
+    R.d  = bl16(rs, 864u + (l >> 3) * 2u, soff);
+}
+__device__ __forceinline__ void load_rec(RecQ2K & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane;
+    R.qs = bl64(rs, l * 8u, soff);
+    R.sc = bl128(rs, 512u + (l >> 3) * 16u, soff);
+    R.dd = bl32(rs, 640u + (l >> 3) * 4u, soff);
 }
 // 6-bit scale/min unpack, ggml-quants.c:6928-6933
 __device__ __forceinline__ void unpack_k4(const uint4 & hd, uint32_t & sc03, uint32_t & sc47, uint32_t & mn03, uint32_t & mn47) {
@@ -620,6 +640,77 @@ __device__ __forceinline__ Terms block_terms(const RecQ6K & R, int ci, int lane,
     return T;
 }
 
+// Q3_K / Q2_K (ggml-quants.c:6161-6263, :5553-5617).  Lane e's eight dwords are elements 128 j + 32 k + 4 e .. + 3 (j = 0, 1: the two qs dwords;
+// k = 0..3: the 2-bit field), dot index 4 j + k = activation chunk c; their 16-element sub-block is 8 j + 2 k + (e >> 2): SIMD lanes 0-3 take the even
+// scales, lanes 4-7 the odd ones (get_scale_shuffle_q3k, :3655).  lowbit_sel: the v_perm selector that picks bytes {h, 2 + h} of two scale dwords.
+__device__ __forceinline__ uint32_t lowbit_sel(int e) { return 0x06040200u + (uint32_t) (e >> 2) * 0x01010101u; }
+// the eight signed 6-bit scales (scale - 32 as int8) of lane e out of the 12 packed bytes: s0 = sub-blocks 2 k + h, s1 = 8 + 2 k + h (:6179-6185)
+__device__ __forceinline__ void q3k_scales(uint32_t a0, uint32_t a1, uint32_t a2, int e, uint32_t & s0, uint32_t & s1) {
+    const uint32_t sel = lowbit_sel(e);
+    const uint32_t P = __builtin_amdgcn_perm(a1, a0, sel), H = __builtin_amdgcn_perm(a2, a2, sel);
+    const uint32_t M = (H & 0x0000ffffu) | ((H >> 2) & 0xffff0000u);       // bytes 0, 1: bits 0-1 / 4-5 of their byte; bytes 2, 3: bits 2-3 / 6-7
+    s0 = (P & 0x0f0f0f0fu) | ((M & 0x03030303u) << 4);
+    s1 = ((P >> 4) & 0x0f0f0f0fu) | (M & 0x30303030u);
+    s0 = (s0 + 0x60606060u) ^ 0x80808080u; s1 = (s1 + 0x60606060u) ^ 0x80808080u;     // - 32 per byte, no inter-byte carry
+}
+// (low2 + 4 hbit - 4) as int8: x = low2 | hbit << 2 in [0, 7] -> (x + 0x7c) ^ 0x80 per byte
+#define BAMD_Q3K_Q(w, k, bit) ((((((w) >> (2 * (k))) & 0x03030303u) | (((hm >> (bit)) & 0x01010101u) << 2)) + 0x7c7c7c7cu) ^ 0x80808080u)
+#define BAMD_Q3K_WQ(wq, R) do { const uint32_t hm = (R).hm; \
+        wq[0] = BAMD_Q3K_Q((R).qs.x, 0, 0); wq[1] = BAMD_Q3K_Q((R).qs.x, 1, 1); wq[2] = BAMD_Q3K_Q((R).qs.x, 2, 2); wq[3] = BAMD_Q3K_Q((R).qs.x, 3, 3); \
+        wq[4] = BAMD_Q3K_Q((R).qs.y, 0, 4); wq[5] = BAMD_Q3K_Q((R).qs.y, 1, 5); wq[6] = BAMD_Q3K_Q((R).qs.y, 2, 6); wq[7] = BAMD_Q3K_Q((R).qs.y, 3, 7); } while (0)
+#define BAMD_Q2K_WQ(wq, R) do { \
+        wq[0] = (R).qs.x & 0x03030303u; wq[1] = ((R).qs.x >> 2) & 0x03030303u; wq[2] = ((R).qs.x >> 4) & 0x03030303u; wq[3] = ((R).qs.x >> 6) & 0x03030303u; \
+        wq[4] = (R).qs.y & 0x03030303u; wq[5] = ((R).qs.y >> 2) & 0x03030303u; wq[6] = ((R).qs.y >> 4) & 0x03030303u; wq[7] = ((R).qs.y >> 6) & 0x03030303u; } while (0)
+__device__ __forceinline__ Terms block_terms(const RecQ3K & R, int ci, int lane, const uint32_t * q8, const int * S, const float * yd) {
+    (void) S;
+    const int e = lane & 7;
+    Terms T;
+    T.d = yd[ci] * h2f(R.d);
+    T.dmin = 0.f; T.pm = 0.f;
+    const uint4 a0 = *(const uint4 *) (q8 + ci * 64 + e * 8), a1 = *(const uint4 *) (q8 + ci * 64 + e * 8 + 4);
+    uint32_t s0, s1; q3k_scales(R.sc0, R.sc1, R.sc2, e, s0, s1);
+    uint32_t wq[8]; BAMD_Q3K_WQ(wq, R);
+    const uint32_t aq[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+    T.fs = (float) dotscale8<true>(wq, aq, s0, s1);
+    return T;
+}
+// Q2_K's min term (:5570-5574): SIMD lane e holds mins[2 e] * bsums[2 e] + mins[2 e + 1] * bsums[2 e + 1], the two 16-element halves of chunk e.  The
+// prologue keeps sums of 32 only; the halves come from the q8 image itself: bytes 0-15 of chunk e are dword e of lanes e' = 0..3, bytes 16-31 that of
+// e' = 4..7 (exact integers, any order; |bsum| <= 16 * 128, min <= 15)
+__device__ __forceinline__ int q2k_minsum(int ma, int mb, int ci, int e, const uint32_t * q8) {
+    int off = ci * 64 + e;
+    asm volatile("" : "+v"(off));                    // pinned behind this record's pin_rec: otherwise the eight reads of EVERY record of an unrolled ring are hoisted to its top (172 spilled registers in the gate/up kernel)
+    const uint32_t * q = q8 + off;
+    int b0 = 0, b1 = 0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { b0 = __builtin_amdgcn_sdot4((int) q[u * 8], 0x01010101, b0, false); b1 = __builtin_amdgcn_sdot4((int) q[(u + 4) * 8], 0x01010101, b1, false); }
+    int r = mul24(ma, b0) + mul24(mb, b1);
+    asm volatile("" : "+v"(r));                      // ... and closed here: at most one record's sixteen dwords are live at a time
+    return r;
+}
+__device__ __forceinline__ void q2k_mins(const uint4 & sc, int e, int & ma, int & mb) {
+    const uint32_t lo = (e & 4) ? sc.z : sc.x, hi = (e & 4) ? sc.w : sc.y;
+    const uint32_t w = ((e & 2) ? hi : lo) >> ((e & 1) * 16);
+    ma = (int) ((w >> 4) & 0xfu); mb = (int) ((w >> 12) & 0xfu);
+}
+__device__ __forceinline__ Terms block_terms(const RecQ2K & R, int ci, int lane, const uint32_t * q8, const int * S, const float * yd) {
+    (void) S;
+    const int e = lane & 7;
+    const float ydv = yd[ci];
+    Terms T;
+    T.d = ydv * h2f(R.dd & 0xffffu);
+    T.dmin = (-ydv) * h2f(R.dd >> 16);
+    const uint4 a0 = *(const uint4 *) (q8 + ci * 64 + e * 8), a1 = *(const uint4 *) (q8 + ci * 64 + e * 8 + 4);
+    const uint32_t sel = lowbit_sel(e);
+    const uint32_t s0 = __builtin_amdgcn_perm(R.sc.y, R.sc.x, sel) & 0x0f0f0f0fu, s1 = __builtin_amdgcn_perm(R.sc.w, R.sc.z, sel) & 0x0f0f0f0fu;
+    uint32_t wq[8]; BAMD_Q2K_WQ(wq, R);
+    const uint32_t aq[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+    T.fs = (float) dotscale8<false>(wq, aq, s0, s1);
+    int ma, mb; q2k_mins(R.sc, e, ma, mb);
+    T.pm = (float) q2k_minsum(ma, mb, ci, e, q8);
+    return T;
+}
+
 // ---- block_terms in two halves: what depends on the weight record only (PreTerms, computed while a co-launched workgroup waits for its
 //      activations: bamd_colaunch.hip) and the rest.  Same operations on the same values as block_terms above, in the same order per result.
 template <int TYPE> struct PreTerms;
@@ -699,9 +790,51 @@ template <> struct PreTerms<BAMD_Q6_K> {
     }
 };
 
+template <> struct PreTerms<BAMD_Q3_K> {
+    uint32_t wq[8], s0, s1; float dh;
+    __device__ __forceinline__ void prep(const RecQ3K & R, int lane) {
+        dh = h2f(R.d); q3k_scales(R.sc0, R.sc1, R.sc2, lane & 7, s0, s1);
+        BAMD_Q3K_WQ(wq, R);
+    }
+    __device__ __forceinline__ Terms finish(int ci, int lane, const uint32_t * q8, const int * S, const float * yd) const {
+        (void) S;
+        const int e = lane & 7;
+        Terms T;
+        T.d = yd[ci] * dh; T.dmin = 0.f; T.pm = 0.f;
+        const uint4 a0 = *(const uint4 *) (q8 + ci * 64 + e * 8), a1 = *(const uint4 *) (q8 + ci * 64 + e * 8 + 4);
+        const uint32_t aq[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+        T.fs = (float) dotscale8<true>(wq, aq, s0, s1);
+        return T;
+    }
+};
+template <> struct PreTerms<BAMD_Q2_K> {
+    uint32_t wq[8], s0, s1; int ma, mb; float dh, dminh;
+    __device__ __forceinline__ void prep(const RecQ2K & R, int lane) {
+        const int e = lane & 7;
+        dh = h2f(R.dd & 0xffffu); dminh = h2f(R.dd >> 16);
+        const uint32_t sel = lowbit_sel(e);
+        s0 = __builtin_amdgcn_perm(R.sc.y, R.sc.x, sel) & 0x0f0f0f0fu; s1 = __builtin_amdgcn_perm(R.sc.w, R.sc.z, sel) & 0x0f0f0f0fu;
+        BAMD_Q2K_WQ(wq, R);
+        q2k_mins(R.sc, e, ma, mb);
+    }
+    __device__ __forceinline__ Terms finish(int ci, int lane, const uint32_t * q8, const int * S, const float * yd) const {
+        (void) S;
+        const int e = lane & 7;
+        const float ydv = yd[ci];
+        Terms T;
+        T.d = ydv * dh; T.dmin = (-ydv) * dminh;
+        const uint4 a0 = *(const uint4 *) (q8 + ci * 64 + e * 8), a1 = *(const uint4 *) (q8 + ci * 64 + e * 8 + 4);
+        const uint32_t aq[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+        T.fs = (float) dotscale8<false>(wq, aq, s0, s1);
+        T.pm = (float) q2k_minsum(ma, mb, ci, e, q8);
+        return T;
+    }
+};
+
 // one step of the reference's per-lane f32 chains (the ONLY place their order is defined)
 template <int TYPE>
 __device__ __forceinline__ void chain_step(RowAcc & A, float d, float fs, float dmin, float pm) {
+    if (TYPE == BAMD_Q2_K) A.acc = fmaf(dmin, pm, A.acc);                      // the min term goes into the SAME accumulator, first (:5574, then :5613)
     A.acc = fmaf(d, fs, A.acc);
     if (TYPE == BAMD_Q4_K) A.accm = fmaf(dmin, pm, A.accm);                    // _mm_fmadd_ps(dmin, prod, acc_m)
     if (TYPE == BAMD_Q5_K) { const float t = dmin * pm; A.accm = A.accm + t; } // summs += dmin * hsum  (mul, then add)
@@ -722,7 +855,7 @@ __device__ __forceinline__ float finish_row(const RowAcc & A) {
         return v + m;
     }
     if (TYPE == BAMD_Q5_K) return v + A.accm;
-    return v;
+    return v;                                                                  // Q6_K, Q3_K, Q2_K: one chain
 }
 
 // ggml_v_expf (AVX2), one lane — ggml.c:2490-2522
@@ -800,6 +933,24 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
                 }
                 const float t = d1 * (float) q;
                 y = t - m1;
+            } else if (embd_type == BAMD_Q3_K) {                // dequantize_row_q3_K: dl = d_all * (sc - 32); y = dl * q
+                const float d_all = h2f(*(const unsigned short *) (b + 108));
+                const int half = n >> 7, nn = n & 127, j = nn >> 5, l = nn & 31;
+                const int is = 8 * half + 2 * j + (l >> 4);
+                const uint8_t * sp = b + 96;
+                const int lo4 = is < 8 ? (sp[is] & 0xF) : (sp[is - 8] >> 4), hi2 = (sp[8 + (is & 3)] >> (2 * (is >> 2))) & 3;
+                const int sc = (int) (int8_t) (lo4 | (hi2 << 4)) - 32;
+                const int q = (int) (int8_t) ((b[32 + 32 * half + l] >> (2 * j)) & 3) - (((b[l] >> (4 * half + j)) & 1) ? 0 : 4);
+                const float dl = d_all * (float) sc;
+                y = dl * (float) q;
+            } else if (embd_type == BAMD_Q2_K) {                // dequantize_row_q2_K: dl = d * (sc & 15); ml = dmin * (sc >> 4); y = dl * q - ml
+                const float d = h2f(*(const unsigned short *) (b + 80)), mn = h2f(*(const unsigned short *) (b + 82));
+                const int half = n >> 7, nn = n & 127, j = nn >> 5, l = nn & 31;
+                const uint8_t sc = b[8 * half + 2 * j + (l >> 4)];
+                const float dl = d * (float) (sc & 0xF), ml = mn * (float) (sc >> 4);
+                const int q = (int) (int8_t) ((b[16 + 32 * half + l] >> (2 * j)) & 3);
+                const float t = dl * (float) q;
+                y = t - ml;
             } else {
                 const float d = h2f(*(const unsigned short *) (b + 208));
                 const int half = n >> 7, nn = n & 127, cc = nn >> 5, l = nn & 31;

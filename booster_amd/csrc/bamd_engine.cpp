@@ -192,10 +192,10 @@ static int upload_mat(bamd_model * m, const GgufTensor * t, DevMat & d, bool kee
                       void * stream_dst = nullptr) {
     if (t->ne.size() != 2) return fail("tensor " + t->name + ": expected 2 dims");
     d.type = t->type; d.K = (int) t->ne[0]; d.nrows = (int) t->ne[1]; d.bytes = t->nbytes;
-    if (d.type != BAMD_F32 && d.type != BAMD_F16 && !bamd_is_kquant(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, Q4_K, Q5_K, Q6_K)");
+    if (d.type != BAMD_F32 && d.type != BAMD_F16 && !bamd_is_kquant(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
     if (bamd_is_kquant(d.type) && d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     if (want_stream) {
-        if (!bamd_is_kquant(d.type)) return fail("tensor " + t->name + ": only Q4_K/Q5_K/Q6_K matrices are supported on the matmul path");
+        if (!bamd_is_kquant(d.type)) return fail("tensor " + t->name + ": only Q2_K/Q3_K/Q4_K/Q5_K/Q6_K matrices are supported on the matmul path");
         if (d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     }
     d.nrows_pad = (d.nrows + 7) / 8 * 8;
@@ -496,7 +496,7 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
         a.nseg = qkv_segments(ly, c->q, a.seg);
         a.x = c->x; a.normw = ly.attn_norm; a.eps = m->eps; a.K = m->E; a.tl = tl_next(c);
         if (tm) tm->begin(s, 0, (double) (ly.wq.bytes + ly.wk.bytes + ly.wv.bytes));
-        bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_STORE, m->n_cu, s);
+        if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_STORE, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
         if (tm) tm->end(s);
         // 2. RoPE, KV store, softmax(QK^T) V                               (llama.cpp:8837-8849, :8318-8353)
         bamd_attn_args t; memset(&t, 0, sizeof t);
@@ -529,31 +529,32 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
             if (tm) tm->end(s);
             a.tl = tl_next(c);
             if (tm) tm->begin(s, 0, (double) ly.wo.bytes, 3);
-            bamd_launch_matvec(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s);
+            if (bamd_launch_matvec(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
             if (tm) tm->end(s);
         }
         // 4. h = silu(Wg . a) * (Wu . a),  a = Q8_K(rms_norm(x2) * ffn_norm)  (llama.cpp:8869-8885)
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wg, c->h); seg_of(a.seg[1], ly.wu, c->h); a.nseg = 2; a.x = c->x2; a.normw = ly.ffn_norm; a.eps = m->eps; a.K = m->E; a.tl = tl_next(c);
         if (tm) tm->begin(s, 0, (double) (ly.wg.bytes + ly.wu.bytes), 4);
-        bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_SILU_MUL, m->n_cu, s);
+        if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_SILU_MUL, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
         if (tm) tm->end(s);
         // 5. x = x2 + Wd . Q8_K(h)                                          (llama.cpp:8885, :8902)
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wd, c->x); a.nseg = 1; a.x = c->h; a.K = m->F; a.res = c->x2; a.tl = tl_next(c);
         if (tm) tm->begin(s, 0, (double) ly.wd.bytes, 5);
-        bamd_launch_matvec(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s);
+        if (bamd_launch_matvec(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
         if (tm) tm->end(s);
     }
     return 0;
 }
-static void enqueue_lm_head(bamd_context * c, hipStream_t s, StepTimer * tm) {
+static int enqueue_lm_head(bamd_context * c, hipStream_t s, StepTimer * tm) {
     bamd_model * m = c->m;
     bamd_mv_args a; memset(&a, 0, sizeof a);
     seg_of(a.seg[0], m->output, c->logits); a.nseg = 1; a.x = c->x; a.normw = m->out_norm; a.eps = m->eps; a.K = m->E; a.best_key = &c->st->best_key; a.tl = tl_next(c);
     if (tm) tm->begin(s, 0, (double) m->output.bytes, 6);
-    bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_ARGMAX, m->n_cu, s);
+    if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_ARGMAX, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
     if (tm) tm->end(s);
+    return 0;
 }
 static void enqueue_begin(bamd_context * c, int n_forced, int do_embed, hipStream_t s, bool with_slots = false) {
     bamd_model * m = c->m;
@@ -561,7 +562,7 @@ static void enqueue_begin(bamd_context * c, int n_forced, int do_embed, hipStrea
                            with_slots ? c->slots : nullptr, with_slots ? c->cellpos : nullptr, c->rope, c->rope_cur, m->hd);
 }
 
-static int enqueue_step(bamd_context * c, hipStream_t s, int pos_hi) { const int rc = enqueue_layers(c, 0, s, nullptr, pos_hi); enqueue_lm_head(c, s, nullptr); return rc; }   // a whole single-stage step behind its step_begin launch
+static int enqueue_step(bamd_context * c, hipStream_t s, int pos_hi) { if (enqueue_layers(c, 0, s, nullptr, pos_hi)) return 1; return enqueue_lm_head(c, s, nullptr); }   // a whole single-stage step behind its step_begin launch
 
 // The tag of a granule hand-over (bamd_colaunch.hip) is (host serial : 12, device step : 12, layer : 8); a word must never already hold the tag a
 // consumer is about to wait for.  The serial runs 1 .. 0xffe (0 is what zero-initialised granules carry, 0xfff is reserved) and every time it wraps ALL granule
@@ -802,7 +803,10 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
         items.push_back({ ly.wd.stream, ly.wd.type, ly.wd.nrows_pad, m->F, &ly.aux_d });
     }
     size_t need = 0;
-    for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) { m->aux_why = "a matrix type / shape without a matrix-core kernel"; return; } need += b + 4096; }
+    for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
+        m->aux_why = it.type == BAMD_Q2_K || it.type == BAMD_Q3_K ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                                                                  : "a matrix type / shape without a matrix-core kernel";
+        return; } need += b + 4096; }
     if (items.empty()) return;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); m->aux_why = "hipMemGetInfo failed"; return; }
@@ -977,7 +981,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_decode(bamd_context *
         // one micro-batch: every layer once for all tokens (each weight record unpacked once per 8 tokens), lm_head for the last
         if (ensure_batch_buffers(c)) return 1;
         if (enqueue_prefill_batch(c, n_tokens, n_past, s)) return 1;
-        enqueue_lm_head(c, s, nullptr);                                  // n_outputs = 1: last token only (llama.cpp:14580-14593)
+        if (enqueue_lm_head(c, s, nullptr)) return 1;                    // n_outputs = 1: last token only (llama.cpp:14580-14593)
     } else if (n_tokens == 1) {
         // single token: the captured stage-step graph (state and token are two small host copies, then one graph launch)
         if (bamd_stage_step(c, tokens[0], nullptr, n_past, nullptr, nullptr, 1, 0, s)) return 1;
@@ -987,7 +991,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_decode(bamd_context *
         for (int t = 0; t < n_tokens; ++t) {
             enqueue_begin(c, n_tokens, 1, s);
             if (enqueue_layers(c, prefill_mode, s, nullptr, n_past + n_tokens)) return 1;
-            if (t == n_tokens - 1) enqueue_lm_head(c, s, nullptr);
+            if (t == n_tokens - 1 && enqueue_lm_head(c, s, nullptr)) return 1;
         }
     }
     if (launch_check()) return 1;
@@ -1020,7 +1024,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_prefill(bamd_co
     if (!m->with_output && !hidden_out_dev) return fail("bamd_stage_prefill: hidden_out required");
     if (ensure_batch_buffers(c)) return 1;
     if (enqueue_prefill_batch(c, n_tokens, n_past, s, hidden_in_dev, hidden_out_dev)) return 1;
-    if (m->with_output && want_logits) enqueue_lm_head(c, s, nullptr);
+    if (m->with_output && want_logits && enqueue_lm_head(c, s, nullptr)) return 1;
     return launch_check();
 }
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_batch(int on) { g_prefill_batch = on ? 1 : 0; g_prefill_mfma = on == 2 ? 0 : 1; }
@@ -1226,7 +1230,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_step(bamd_conte
             HIPC(hipMemcpyAsync(c->x, hidden_in_dev, (size_t) m->E * 4, hipMemcpyDeviceToDevice, s));
         }
         if (enqueue_layers(c, prefill_mode, s, nullptr, attn_hi)) return 1;
-        if (m->with_output) { if (want_logits) enqueue_lm_head(c, s, nullptr); }
+        if (m->with_output) { if (want_logits && enqueue_lm_head(c, s, nullptr)) return 1; }
         else HIPC(hipMemcpyAsync(hidden_out_dev, c->x, (size_t) m->E * 4, hipMemcpyDeviceToDevice, s));
         return 0;
     };
@@ -1285,7 +1289,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_profile_step_kinds(ba
     StepTimer tm; tm.on = true;
     tm.begin(s, 2, 0.0); enqueue_begin(c, 1, 1, s); tm.end(s);
     if (enqueue_layers(c, 0, s, &tm, pos)) return 1;
-    enqueue_lm_head(c, s, &tm);
+    if (enqueue_lm_head(c, s, &tm)) return 1;
     HIPC(hipStreamSynchronize(s));
     for (int i = 0; i < 8; ++i) { launches[i] = 0; ms[i] = 0; bytes[i] = 0; }
     const int n_kv = std::min(c->n_ctx, (pos + 1 + 31) / 32 * 32);

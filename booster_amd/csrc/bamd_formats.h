@@ -5,6 +5,8 @@
 //   Q4_K 144 B = {f16 d, f16 dmin, u8 scales[12], u8 qs[128]}
 //   Q5_K 176 B = {f16 d, f16 dmin, u8 scales[12], u8 qh[32], u8 qs[128]}
 //   Q6_K 210 B = {u8 ql[128], u8 qh[64], i8 scales[16], f16 d}
+//   Q2_K  84 B = {u8 scales[16] (low nibble scale, high nibble min), u8 qs[64], f16 d, f16 dmin}      (ggml-common.h:234-261)
+//   Q3_K 110 B = {u8 hmask[32], u8 qs[64], u8 scales[12], f16 d}
 //   Q8_K 292 B = {f32 d, i8 qs[256], i16 bsums[16]}   (activations only; never stored in HBM here)
 //
 // Wave-stream layout (our design; the GGUF file itself is untouched).  A matrix [nrows][K] is cut into
@@ -20,6 +22,14 @@
 //                       [qh   : lane*8  -> 2 dwords m=0,1 = file qh[32m+4e .. +3]      ]  512 B
 //                       [sc   : r*16    -> byte hi*8+c = file scales[2c+hi]             ]  128 B
 //                       [d    : r*2     -> f16 d                                        ]   16 B
+//   Q3_K record  880 B: [qs   : lane*8  -> 2 dwords j=0,1 = file qs[32j+4e .. +3]       ]  512 B
+//                       [hmask: lane*4  -> file hmask[4e .. 4e+3]                        ]  256 B
+//                       [sc   : r*12    -> file scales[12] (packed 6-bit, as in the file)]   96 B
+//                       [d    : r*2     -> f16 d                                        ]   16 B
+//   Q2_K record  672 B: [qs   : lane*8  -> 2 dwords j=0,1 = file qs[32j+4e .. +3]       ]  512 B
+//                       [sc   : r*16    -> file scales[16]                              ]  128 B
+//                       [dd   : r*4     -> f16 d, f16 dmin                              ]   32 B
+//   (Q3_K / Q2_K: 3.4375 / 2.625 bits per weight leave a lane 8 B of qs per super-block, so its widest load is 8 bytes; records are 16-byte multiples)
 //
 // Record bytes = 8 x file block bytes, so HBM traffic per weight is exactly the GGUF's bits per weight, every
 // wave load instruction is one contiguous, 16-byte-per-lane kilobyte, and consecutive records of a row-group
@@ -35,9 +45,9 @@
 #define BAMD_HD
 #endif
 
-enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14 };
+enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_Q2_K = 10, BAMD_Q3_K = 11, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14 };
 
-BAMD_HD static inline int bamd_block_bytes(int t) { return t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : 0; }
+BAMD_HD static inline int bamd_block_bytes(int t) { return t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : t == BAMD_Q3_K ? 110 : t == BAMD_Q2_K ? 84 : 0; }
 #ifndef BAMD_XSCALES
 #define BAMD_XSCALES 0          /* 0: the file's 12 packed scale bytes per row (records of 1152 / 1408 B = 8 x the GGUF block); 1: unpacked scales and
                                    mins, a byte each (1184 / 1440 B) — measured SLOWER on the MI355X in round 2 (gate/up 14.8 vs 13.2 us, decode 649 vs
@@ -46,10 +56,15 @@ BAMD_HD static inline int bamd_block_bytes(int t) { return t == BAMD_Q4_K ? 144 
 #endif
 #define BAMD_RECB_Q4K (BAMD_XSCALES ? 1184 : 1152)
 #define BAMD_RECB_Q5K (BAMD_XSCALES ? 1440 : 1408)
-BAMD_HD static inline int bamd_record_bytes(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? 1680 : 0; }   // wave-stream record: 8 rows x 1 super-block
+#define BAMD_RECB_Q6K 1680
+#define BAMD_RECB_Q3K 880
+#define BAMD_RECB_Q2K 672
+// record bytes as a constant expression of a kernel's TYPE template argument; a type without a record does not compile
+#define BAMD_RECB_OF(T_) ((T_) == BAMD_Q4_K ? BAMD_RECB_Q4K : (T_) == BAMD_Q5_K ? BAMD_RECB_Q5K : (T_) == BAMD_Q6_K ? BAMD_RECB_Q6K : (T_) == BAMD_Q3_K ? BAMD_RECB_Q3K : (T_) == BAMD_Q2_K ? BAMD_RECB_Q2K : -1)
+BAMD_HD static inline int bamd_record_bytes(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? BAMD_RECB_Q6K : t == BAMD_Q3_K ? BAMD_RECB_Q3K : t == BAMD_Q2_K ? BAMD_RECB_Q2K : 0; }   // wave-stream record: 8 rows x 1 super-block
 // bytes of the wave-stream copy of a K-quant matrix [nrows_pad (multiple of 8)][K]
 BAMD_HD static inline size_t bamd_stream_bytes(int t, int64_t k, int64_t nrows_pad) { return (size_t) (nrows_pad / 8) * (size_t) (k / BAMD_QK_K) * (size_t) bamd_record_bytes(t); }
-BAMD_HD static inline int bamd_is_kquant(int t) { return t == BAMD_Q4_K || t == BAMD_Q5_K || t == BAMD_Q6_K; }
+BAMD_HD static inline int bamd_is_kquant(int t) { return t == BAMD_Q4_K || t == BAMD_Q5_K || t == BAMD_Q6_K || t == BAMD_Q3_K || t == BAMD_Q2_K; }
 BAMD_HD static inline size_t bamd_row_bytes(int t, int64_t k) {
     return t == BAMD_F32 ? (size_t) k * 4 : t == BAMD_F16 ? (size_t) k * 2 : (size_t) (k / BAMD_QK_K) * bamd_block_bytes(t);
 }

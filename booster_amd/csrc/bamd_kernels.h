@@ -73,7 +73,7 @@ struct bamd_mm_args {
 int  bamd_timing_enabled(void);   // 1 when the kernels were compiled with -DBAMD_TIMING
 void bamd_launch_repack(const void * raw, void * dst, int type, int nrows, int K, hipStream_t s);
 void bamd_launch_quantize_q8k_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
-void bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
+[[nodiscard]] int bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);          // 1 = a segment's type has no kernel (nothing launched)
 void bamd_launch_step_begin(bamd_step_state * st, const int32_t * forced, int n_forced, int32_t * out_tokens, const void * embd,
                             int embd_type, int E, int V, float * x, int do_embed, hipStream_t s, const int32_t * slots = nullptr, int32_t * cellpos = nullptr,
                             const float * rope = nullptr, float * rope_cur = nullptr, int hd = 0, const bamd_step_state * inbox = nullptr);

@@ -10,7 +10,7 @@ __global__ void repack_kernel(const uint8_t * __restrict__ raw, uint8_t * __rest
     if (idx >= (int64_t) nrows * nb) return;
     const int row = (int) (idx / nb), i = (int) (idx % nb);
     const int rg = row >> 3, r = row & 7;
-    const int bb = type == BAMD_Q4_K ? 144 : type == BAMD_Q5_K ? 176 : 210;
+    const int bb = bamd_block_bytes(type);
     const uint8_t * src = raw + ((int64_t) row * nb + i) * bb;
     uint8_t * rec = dst + ((int64_t) rg * nb + i) * bamd_record_bytes(type);
     if (type == BAMD_Q4_K || type == BAMD_Q5_K) {
@@ -36,7 +36,20 @@ __global__ void repack_kernel(const uint8_t * __restrict__ raw, uint8_t * __rest
 #else
         for (int t = 0; t < 16; ++t) rec[hdr_off + r * 16 + t] = src[t];
 #endif
-    } else {
+    } else if (type == BAMD_Q3_K || type == BAMD_Q2_K) {
+        const uint8_t * qs = src + (type == BAMD_Q3_K ? 32 : 16);
+        for (int e = 0; e < 8; ++e)
+            for (int j = 0; j < 2; ++j)
+                for (int t = 0; t < 4; ++t) rec[(r * 8 + e) * 8 + 4 * j + t] = qs[32 * j + 4 * e + t];
+        if (type == BAMD_Q3_K) {
+            for (int t = 0; t < 32; ++t) rec[512 + r * 32 + t] = src[t];                    // hmask[4e + t'] -> lane (r*8 + e) * 4 + t'
+            for (int t = 0; t < 12; ++t) rec[768 + r * 12 + t] = src[96 + t];
+            rec[864 + r * 2] = src[108]; rec[864 + r * 2 + 1] = src[109];
+        } else {
+            for (int t = 0; t < 16; ++t) rec[512 + r * 16 + t] = src[t];
+            for (int t = 0; t < 4; ++t) rec[640 + r * 4 + t] = src[80 + t];
+        }
+    } else if (type == BAMD_Q6_K) {
         const uint8_t * ql = src, * qh = src + 128, * sc = src + 192;
         for (int e = 0; e < 8; ++e) {
             for (int j = 0; j < 4; ++j)
@@ -114,7 +127,10 @@ __global__ void __launch_bounds__(512) matvec_kernel(bamd_mv_args a) {
             const int nv = a.seg[s].nvalid > 0 ? a.seg[s].nvalid : a.seg[s].nrows;
             if (t == BAMD_Q4_K)      stream_dispatch_depth<BAMD_Q4_K, RecQ4K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
             else if (t == BAMD_Q5_K) stream_dispatch_depth<BAMD_Q5_K, RecQ5K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
-            else                     stream_dispatch_depth<BAMD_Q6_K, RecQ6K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_Q6_K) stream_dispatch_depth<BAMD_Q6_K, RecQ6K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_Q3_K) stream_dispatch_depth<BAMD_Q3_K, RecQ3K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_Q2_K) stream_dispatch_depth<BAMD_Q2_K, RecQ2K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else __builtin_trap();                           // unreachable: bamd_launch_matvec refuses any other type on the host; never a silent read as another format
             pro_done = true;
         }
         off += nrg;
@@ -181,7 +197,10 @@ __global__ void __launch_bounds__(512) matvec_split_kernel(bamd_mv_args a) {
             const int nv = a.seg[s].nvalid > 0 ? a.seg[s].nvalid : a.seg[s].nrows;
             if (t == BAMD_Q4_K)      split_dispatch<BAMD_Q4_K, RecQ4K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
             else if (t == BAMD_Q5_K) split_dispatch<BAMD_Q5_K, RecQ5K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
-            else                     split_dispatch<BAMD_Q6_K, RecQ6K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_Q6_K) split_dispatch<BAMD_Q6_K, RecQ6K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_Q3_K) split_dispatch<BAMD_Q3_K, RecQ3K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_Q2_K) split_dispatch<BAMD_Q2_K, RecQ2K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else __builtin_trap();
             pro_done = true;
         }
         off += nrg;
@@ -301,9 +320,15 @@ static void launch_mv_split(const bamd_mv_args & a, int epi, int grid, hipStream
 // faster split than with one wave per row-group: 6.9 / 4.8 us against 6.2 / 5.1 for its QKV / wo.)
 static bool split_supported(int nb) { const int nbw = nb >> 3; return (nb & 7) == 0 ? (nbw == 1 || nbw == 2 || nbw == 4 || nbw == 7) : (nbw == 2 || nbw == 5 || nbw == 6); }
 
+static void bamd_launch_matvec_checked(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
 static const bool g_mv_generic = [] { const char * e = getenv("BAMD_MV_GENERIC"); return e && e[0] == '1'; }();
 
-void bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
+int bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
+    for (int i = 0; i < a.nseg; ++i) if (!bamd_is_kquant(a.seg[i].type)) return 1;      // never launched: the kernels' own `else` is unreachable
+    bamd_launch_matvec_checked(a, pro, epi, n_cu, s);
+    return 0;
+}
+static void bamd_launch_matvec_checked(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
     int nrg = 0;
     if (epi == BAMD_EPI_SILU_MUL) nrg = a.seg[0].nrows >> 3;
     else for (int i = 0; i < a.nseg; ++i) nrg += a.seg[i].nrows >> 3;

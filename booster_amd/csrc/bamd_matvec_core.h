@@ -8,6 +8,8 @@ template <int TYPE> struct RecOf;
 template <> struct RecOf<BAMD_Q4_K> { typedef RecQ4K type; };
 template <> struct RecOf<BAMD_Q5_K> { typedef RecQ5K type; };
 template <> struct RecOf<BAMD_Q6_K> { typedef RecQ6K type; };
+template <> struct RecOf<BAMD_Q3_K> { typedef RecQ3K type; };
+template <> struct RecOf<BAMD_Q2_K> { typedef RecQ2K type; };
 
 // The fields a launch needs for its FIRST requests travel as leading scalar kernel parameters: with -amdgpu-kernarg-preload-count the
 // hardware places them in SGPRs at wave launch (gfx950 kernarg preload), so the activation and ring requests do not wait for an s_load of
@@ -46,7 +48,7 @@ __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, 
                                                int first, int count, int stride, float * __restrict__ out,
                                                const float * __restrict__ res, const ProArgs & pa, ActPro<PRO == BAMD_PRO_NORM> & ap,
                                                bool issue_here, bool do_pro, unsigned long long & best, int nvalid, float * half_slot = nullptr, int * half_flag = nullptr) {
-    constexpr int RECB = TYPE == BAMD_Q4_K ? BAMD_RECB_Q4K : TYPE == BAMD_Q5_K ? BAMD_RECB_Q5K : 1680;     // bamd_record_bytes
+    constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");     // bamd_record_bytes
     constexpr bool PAIR = EPI == BAMD_EPI_SILU_MUL;
     constexpr int NPARTS = PAIR ? 2 : 1;
     const int lane = threadIdx.x & 63;
@@ -158,7 +160,7 @@ __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, 
 template <int TYPE, typename REC, int NBP, bool HELPER>
 __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ wG, const uint8_t * __restrict__ wU, int rg0, int rg_stride, int j,
                                                   float * __restrict__ out, const ProArgs & pa, ActPro<true> & ap, float4 * park, int * flags, int nvalid) {
-    constexpr int RECB = TYPE == BAMD_Q4_K ? BAMD_RECB_Q4K : TYPE == BAMD_Q5_K ? BAMD_RECB_Q5K : 1680;
+    constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");
     constexpr int NB = 16, Q = NB / 4, CUT = NB - Q, D = 8, NREC = HELPER ? 3 * 2 * Q : 2 * CUT;      // 24 records either way
     static_assert(NREC % D == 0, "whole ring chunks");
     const int lane = threadIdx.x & 63;
@@ -247,7 +249,7 @@ __device__ __forceinline__ void split_stream(const uint8_t * __restrict__ w, int
                                              float * __restrict__ out, const float * __restrict__ res, const ProArgs & pa,
                                              ActPro<PRO == BAMD_PRO_NORM> & ap, ActPro<PRO == BAMD_PRO_NORM> & ap2, bool issue_here, bool do_pro,
                                              float * part0, int & batchctr, int nvalid, PRE pre = PRE()) {
-    constexpr int RECB = TYPE == BAMD_Q4_K ? BAMD_RECB_Q4K : TYPE == BAMD_Q5_K ? BAMD_RECB_Q5K : 1680;     // bamd_record_bytes
+    constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");     // bamd_record_bytes
     constexpr int D = NBW * M;                               // ring depth = one batch (M row-groups) of this wave's records
     const int lane = threadIdx.x & 63, wave = wave_id();
     const int r8 = lane >> 3, l4 = lane & 3;

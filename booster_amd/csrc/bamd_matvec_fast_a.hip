@@ -137,10 +137,11 @@ template <int PRO, int EPI>
 static bool launch_fast_a_types(const bamd_mv_args & a, int t0, int t1, int grid, hipStream_t s) {
     constexpr bool MIX = PRO == BAMD_PRO_NORM && EPI == BAMD_EPI_STORE;      // two differently typed segments: the fused QKV launch only
 #define BAMD_A_CASE(T0_, T1_) if (t0 == T0_ && t1 == T1_) { launch_fast_a_inst<PRO, EPI, T0_, T1_>(a, grid, s); return true; }
-    BAMD_A_CASE(BAMD_Q4_K, 0) BAMD_A_CASE(BAMD_Q5_K, 0) BAMD_A_CASE(BAMD_Q6_K, 0)
-    if (MIX) {
+    BAMD_A_CASE(BAMD_Q4_K, 0) BAMD_A_CASE(BAMD_Q5_K, 0) BAMD_A_CASE(BAMD_Q6_K, 0) BAMD_A_CASE(BAMD_Q3_K, 0) BAMD_A_CASE(BAMD_Q2_K, 0)
+    if constexpr (MIX) {                                     // (constexpr: the pairs are instantiated for the one prologue / epilogue that can launch them)
         BAMD_A_CASE(BAMD_Q4_K, BAMD_Q5_K) BAMD_A_CASE(BAMD_Q4_K, BAMD_Q6_K) BAMD_A_CASE(BAMD_Q5_K, BAMD_Q4_K)
         BAMD_A_CASE(BAMD_Q5_K, BAMD_Q6_K) BAMD_A_CASE(BAMD_Q6_K, BAMD_Q4_K) BAMD_A_CASE(BAMD_Q6_K, BAMD_Q5_K)
+        BAMD_A_CASE(BAMD_Q2_K, BAMD_Q3_K)                    // the Q2_K recipe without GQA (Llama-2-7B: six row-groups per workgroup); other low-bit pairs at mode-A shapes: generic kernel
     }
 #undef BAMD_A_CASE
     return false;
@@ -160,13 +161,13 @@ bool bamd_launch_fast_a(bamd_mv_args a, int pro, int epi, int grid, hipStream_t 
     if (g_gateup7 && pro == BAMD_PRO_NORM && epi == BAMD_EPI_SILU_MUL && nb == 16 && nrg0 == 7 * grid && (a.mode & 15) == 0) {
         const size_t lds = act_lds_bytes(a.K) + BAMD_GU7_PARK_BYTES(16) + 16;
 #define BAMD_G7(T_) if (t0 == T_) { BAMD_LAUNCH((matvec_gateup7_kernel<T_, 2>), dim3(grid), dim3(512), lds, s, BAMD_LEAD_ARGS(a), a); return true; }
-        BAMD_G7(BAMD_Q4_K) BAMD_G7(BAMD_Q5_K) BAMD_G7(BAMD_Q6_K)
+        BAMD_G7(BAMD_Q4_K) BAMD_G7(BAMD_Q5_K) BAMD_G7(BAMD_Q6_K) BAMD_G7(BAMD_Q3_K) BAMD_G7(BAMD_Q2_K)
 #undef BAMD_G7
     }
     if (g_gateup14 && pro == BAMD_PRO_NORM && epi == BAMD_EPI_SILU_MUL && nb == 32 && nrg0 == 14 * grid && (a.mode & 15) == 0) {
         const size_t lds = act_lds_bytes(a.K) + 16 * 4 + 2 * 4 + 8;
 #define BAMD_G14(T_) if (t0 == T_) { BAMD_LAUNCH((matvec_gateup14_kernel<T_, 4>), dim3(grid), dim3(512), lds, s, BAMD_LEAD_ARGS(a), a); return true; }
-        BAMD_G14(BAMD_Q4_K) BAMD_G14(BAMD_Q5_K) BAMD_G14(BAMD_Q6_K)
+        BAMD_G14(BAMD_Q4_K) BAMD_G14(BAMD_Q5_K) BAMD_G14(BAMD_Q6_K) BAMD_G14(BAMD_Q3_K) BAMD_G14(BAMD_Q2_K)
 #undef BAMD_G14
     }
     if (pro == BAMD_PRO_NORM) {

@@ -43,8 +43,8 @@ template <int TA, int TB, int NBW, int MA, bool COMPACT = false>
 __device__ __forceinline__ void split_mixed_body(const bamd_mv_args & a, const ProArgs & pa, ActPro<true> & ap, float * part0, int g_last) {
     typedef typename RecOf<TA>::type RECA;
     typedef typename RecOf<TB>::type RECB_T;
-    constexpr int RA = TA == BAMD_Q4_K ? BAMD_RECB_Q4K : TA == BAMD_Q5_K ? BAMD_RECB_Q5K : 1680;
-    constexpr int RB = TB == BAMD_Q4_K ? BAMD_RECB_Q4K : TB == BAMD_Q5_K ? BAMD_RECB_Q5K : 1680;
+    constexpr int RA = BAMD_RECB_OF(TA);
+    constexpr int RB = BAMD_RECB_OF(TB); static_assert(RA > 0 && RB > 0, "no wave-stream record for this type");
     constexpr bool SAME = TA == TB;                          // the last row-group still belongs to segment 0
     const int nb = pa.K >> 8;
     const int lane = threadIdx.x & 63, wave = wave_id(), r8 = lane >> 3;
@@ -186,6 +186,7 @@ bool bamd_launch_fast_mixed(const bamd_mv_args & a, int pro, int epi, int grid, 
     if (cnt != 3 || nrg0 < 2 * grid || nbw != 2) return false;                  // the Llama-3-8B / Mistral-7B shape: K = 4096, three row-groups per workgroup
 #define BAMD_MX(TA_, TB_) if (t0 == TA_ && t1 == TB_) { launch_mixed_inst<TA_, TB_, 2, 2>(a, grid, s); return true; }
     BAMD_MX(BAMD_Q4_K, BAMD_Q6_K) BAMD_MX(BAMD_Q4_K, BAMD_Q5_K) BAMD_MX(BAMD_Q5_K, BAMD_Q6_K)
+    BAMD_MX(BAMD_Q3_K, BAMD_Q4_K) BAMD_MX(BAMD_Q3_K, BAMD_Q5_K) BAMD_MX(BAMD_Q2_K, BAMD_Q4_K) BAMD_MX(BAMD_Q2_K, BAMD_Q3_K)      // the Q3_K_M and Q2_K recipes' q | k + v
 #undef BAMD_MX
     return false;
 }
@@ -219,7 +220,7 @@ static bool launch_fast_b_types(const bamd_mv_args & a, int t, int nbw, int grid
     }
     if (g_down14 && PRO == BAMD_PRO_PLAIN && (a.K >> 8) == 56 && a.cnt_q >= 1) {                // K = 14336 on fourteen waves, four records each (one row-group per batch: 128 VGPRs)
 #define BAMD_B14(T_) if (t == T_) { launch_fast_b_inst<PRO, EPI, T_, 4, 1, false, 14>(a, grid, s); return true; }
-        BAMD_B14(BAMD_Q4_K) BAMD_B14(BAMD_Q5_K) BAMD_B14(BAMD_Q6_K)
+        BAMD_B14(BAMD_Q4_K) BAMD_B14(BAMD_Q5_K) BAMD_B14(BAMD_Q6_K) BAMD_B14(BAMD_Q3_K) BAMD_B14(BAMD_Q2_K)
 #undef BAMD_B14
     }
     const int mmax = nbw == 1 ? 8 : nbw == 2 ? 4 : nbw == 4 ? 2 : 1;
@@ -233,6 +234,7 @@ static bool launch_fast_b_types(const bamd_mv_args & a, int t, int nbw, int grid
 #define BAMD_B_ONE(T_, NBW_, M_) if (PRO == BAMD_PRO_PLAIN && EPI == BAMD_EPI_ADD && oneb && t == T_ && nbw == NBW_ && m == M_) { launch_fast_b_inst<PRO, EPI, T_, NBW_, M_, true>(a, grid, s); return true; }
 #define BAMD_B_ONES(NBW_, M_) BAMD_B_ONE(BAMD_Q4_K, NBW_, M_) BAMD_B_ONE(BAMD_Q5_K, NBW_, M_) BAMD_B_ONE(BAMD_Q6_K, NBW_, M_)
     BAMD_B_ONES(2, 2) BAMD_B_ONES(2, 4) BAMD_B_ONES(4, 2) BAMD_B_ONES(4, 4) BAMD_B_ONES(1, 8)
+    BAMD_B_ONE(BAMD_Q3_K, 2, 2) BAMD_B_ONE(BAMD_Q2_K, 2, 2)          // wo at K = 4096, two row-groups per workgroup (the Q2_K recipe's wo is Q3_K); every other Q2_K / Q3_K split-K shape: generic kernel
 #undef BAMD_B_ONES
 #undef BAMD_B_ONE
 #define BAMD_B_CASE(T_, NBW_, M_) if (t == T_ && nbw == NBW_ && m == M_) { launch_fast_b_inst<PRO, EPI, T_, NBW_, M_>(a, grid, s); return true; }

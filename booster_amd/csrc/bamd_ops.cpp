@@ -60,7 +60,7 @@ static int op_matvec(int type, const void * wA, const void * wB, int nrows, int 
     a.seg[0].w = strA; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows_pad; a.seg[0].nvalid = nrows; a.nseg = 1;
     if (wB) { a.seg[1] = a.seg[0]; a.seg[1].w = strB; a.nseg = 2; }
     a.x = dx; a.normw = dw; a.eps = eps; a.K = k; a.res = dres; a.best_key = key; a.mode = mode;
-    bamd_launch_matvec(a, norm_w ? BAMD_PRO_NORM : BAMD_PRO_PLAIN, epi, n_cu0(), nullptr);
+    if (bamd_launch_matvec(a, norm_w ? BAMD_PRO_NORM : BAMD_PRO_PLAIN, epi, n_cu0(), nullptr)) return fail("mat-vec: type without a kernel");
     if (finish(y, dy, (size_t) nrows * 4)) return 1;
     if (best_key) HIPC(hipMemcpy(best_key, key, 8, hipMemcpyDeviceToHost));
     return 0;
@@ -93,6 +93,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     bamd_launch_repack(raw, str, type, nrows, k, nullptr);
     bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr);
     if (impl == 2) {                                                // the matrix-core kernel: side table built here, as the engine builds it at model load
+        if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K: the integer-dot kernel only
         void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
         if (!aux) return fail("device alloc failed");
         bamd_launch_prefill_aux(str, type, nrows_pad, k, aux, nullptr);
@@ -305,7 +306,10 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
     const int bb = bamd_block_bytes(type);
     for (size_t b = 0; b < wb / bb; ++b) {                    // sane f16 scales (0x1c00 ~ 0.0039)
         uint8_t * p = hw.data() + b * bb;
-        if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; } else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
+        if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; }
+        else if (type == BAMD_Q3_K) { p[108] = 0x00; p[109] = 0x1c; }
+        else if (type == BAMD_Q2_K) { p[80] = 0; p[81] = 0x1c; p[82] = 0; p[83] = 0x1c; }
+        else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
     }
     std::vector<float> hx((size_t) k); for (int i = 0; i < k; ++i) { sd = sd * 1664525u + 1013904223u; hx[i] = (float) (int) (sd >> 8) / 8388608.0f - 1.0f; }
     std::vector<float> hn((size_t) k, 1.0f);
@@ -326,11 +330,11 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
     if (iters < 1) return fail("iters < 1");
     OwnedStream os; HIPC(hipStreamCreate(&os.s));
     hipStream_t s = os.s;
-    for (int i = 0; i < 3; ++i) bamd_launch_matvec(a, pro, epi, ncu, s);
+    for (int i = 0; i < 3; ++i) if (bamd_launch_matvec(a, pro, epi, ncu, s)) return fail("mat-vec: type without a kernel");
     HIPC(hipGetLastError());
     EventPair ev; HIPC(ev.create());
     HIPC(hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters; ++i) bamd_launch_matvec(a, pro, epi, ncu, s);
+    for (int i = 0; i < iters; ++i) if (bamd_launch_matvec(a, pro, epi, ncu, s)) return fail("mat-vec: type without a kernel");
     HIPC(hipEventRecord(ev.b, s));
     HIPC(hipStreamSynchronize(s));
     float ms = 0.f; HIPC(hipEventElapsedTime(&ms, ev.a, ev.b));

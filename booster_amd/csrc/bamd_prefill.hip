@@ -63,7 +63,7 @@ template <int TYPE, typename REC, int D, int EPI, int TT>
 __device__ __forceinline__ void batch_segment(const uint8_t * __restrict__ wA, const uint8_t * __restrict__ wB, int nb, int first, int count, int stride,
                                               float * __restrict__ out, const float * __restrict__ res, int ldo, int t0, int nt,
                                               const unsigned char * acts, size_t bb, int nvalid) {
-    constexpr int RECB = TYPE == BAMD_Q4_K ? BAMD_RECB_Q4K : TYPE == BAMD_Q5_K ? BAMD_RECB_Q5K : 1680;     // bamd_record_bytes
+    constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");     // bamd_record_bytes
     constexpr bool PAIR = EPI == BAMD_EPI_SILU_MUL;
     constexpr int NPARTS = PAIR ? 2 : 1;
     const int lane = threadIdx.x & 63;
@@ -163,11 +163,17 @@ __global__ void __launch_bounds__(512) matmul_batch_kernel(bamd_mm_args a) {
             if ((nb & 3) == 0) {
                 if (t == BAMD_Q4_K)      batch_segment<BAMD_Q4_K, RecQ4K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
                 else if (t == BAMD_Q5_K) batch_segment<BAMD_Q5_K, RecQ5K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else                     batch_segment<BAMD_Q6_K, RecQ6K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else if (t == BAMD_Q6_K) batch_segment<BAMD_Q6_K, RecQ6K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else if (t == BAMD_Q3_K) batch_segment<BAMD_Q3_K, RecQ3K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else if (t == BAMD_Q2_K) batch_segment<BAMD_Q2_K, RecQ2K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else __builtin_trap();                       // the launcher checks the types: never a silent read as another format
             } else {
                 if (t == BAMD_Q4_K)      batch_segment<BAMD_Q4_K, RecQ4K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
                 else if (t == BAMD_Q5_K) batch_segment<BAMD_Q5_K, RecQ5K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else                     batch_segment<BAMD_Q6_K, RecQ6K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else if (t == BAMD_Q6_K) batch_segment<BAMD_Q6_K, RecQ6K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else if (t == BAMD_Q3_K) batch_segment<BAMD_Q3_K, RecQ3K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else if (t == BAMD_Q2_K) batch_segment<BAMD_Q2_K, RecQ2K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
+                else __builtin_trap();                       // the launcher checks the types: never a silent read as another format
             }
         }
         off += nrg;
@@ -198,6 +204,7 @@ int bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStrea
     const int tt = (size_t) BAMD_TT * BAMD_BLOB_BYTES(a.K >> 8) <= 160 * 1024 ? BAMD_TT : 4;     // tokens per tile: 8 while their activations fit the LDS, else 4
     const size_t lds = (size_t) tt * BAMD_BLOB_BYTES(a.K >> 8);
     if (lds > 160 * 1024) return 1;                           // K > 35840: would need a K-split of the activation tile
+    for (int i = 0; i < a.nseg; ++i) if (!bamd_is_kquant(a.seg[i].type)) return 1;
     const int tiles = (a.T + tt - 1) / tt;
     // row slots: enough workgroups to fill the chip a few times over, at least one row-group per wave
     int gy = (4 * (n_cu > 0 ? n_cu : 256) + tiles - 1) / tiles;

@@ -16,12 +16,15 @@ DEFAULT_ALIGNMENT = 32
 GGML_TYPES = {
     0: (1, 4),        # F32
     1: (1, 2),        # F16
+    10: (256, 84),    # Q2_K
+    11: (256, 110),   # Q3_K
     12: (256, 144),   # Q4_K
     13: (256, 176),   # Q5_K
     14: (256, 210),   # Q6_K
 }
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
-TYPE_NAMES = {0: "F32", 1: "F16", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K"}
+Q2_K, Q3_K = 10, 11
+TYPE_NAMES = {0: "F32", 1: "F16", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K"}
 
 # gguf KV value types
 T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I64, T_F64 = range(13)
@@ -198,6 +201,16 @@ def random_kquant_tensor(ttype, row_len, n_rows, rng, amp=1.0):
     elif ttype == Q6_K:
         d = (sigma / (64.0 * 18.0)) * rng.uniform(0.5, 1.5, size=nblk)
         blk[:, 208:210] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    elif ttype == Q3_K:
+        # w = d*(sc - 32)*q ; sc - 32 in [-32,31] (rms ~18.5), q in [-4,3] (rms ~2.35)
+        d = (sigma / (18.5 * 2.35)) * rng.uniform(0.5, 1.5, size=nblk)
+        blk[:, 108:110] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    elif ttype == Q2_K:
+        # w = d*sc*q - dmin*m ; q in [0,3], sc,m in [0,15]: the Q4_K / Q5_K rule with 7.5 for their mean scale 32
+        d = (sigma / (7.5 * 3.0 * 0.3)) * rng.uniform(0.5, 1.5, size=nblk)
+        dmin = d * 3.0 * 0.5 * rng.uniform(0.8, 1.2, size=nblk)
+        blk[:, 80:82] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+        blk[:, 82:84] = dmin.astype(np.float16).view(np.uint8).reshape(-1, 2)
     else:
         raise ValueError(ttype)
     return blk.reshape(-1)
@@ -219,6 +232,33 @@ def q4_k_m_type_70b(name, il, n_layer=80):
     Q4_K (llama.cpp:15552-15555)."""
     t = q4_k_m_type(name, il, n_layer)
     return Q5_K if (name == "attn_v" and t == Q4_K) else t
+
+
+def q3_k_m_type(name, il, n_layer):
+    """llama.cpp's Q3_K_M recipe for the Llama architecture (llama_tensor_get_type, llama.cpp:15435-15660): attn_v Q5_K in layers 0-1, else Q4_K;
+    attn_output Q4_K; ffn_down Q5_K for il < n_layer / 16, else Q4_K (the use_more_bits cases of the recipe give Q4_K as well); output Q6_K;
+    everything else — token_embd included — Q3_K."""
+    if name == "output":
+        return Q6_K
+    if name == "attn_v":
+        return Q5_K if il < 2 else Q4_K
+    if name == "attn_output":
+        return Q4_K
+    if name == "ffn_down":
+        return Q5_K if il < n_layer // 16 else Q4_K
+    return Q3_K
+
+
+def q2_k_type(name, il, n_layer, n_gqa=4):
+    """llama.cpp's Q2_K recipe for the Llama architecture: attn_v Q4_K where n_gqa >= 4, else Q3_K; attn_output and ffn_down Q3_K; output Q6_K;
+    everything else — token_embd included — Q2_K."""
+    if name == "output":
+        return Q6_K
+    if name == "attn_v":
+        return Q4_K if n_gqa >= 4 else Q3_K
+    if name in ("attn_output", "ffn_down"):
+        return Q3_K
+    return Q2_K
 
 
 def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_ctx_train=8192, seed=7,
@@ -246,7 +286,7 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
         if not reuse_layers:
             return None
         bb = GGML_TYPES[t][1]; nb = cols // 256
-        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0}[t]                # qs / qs / ql
+        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32}[t]      # qs / qs / ql / qs / qs
         n = min(64, rows)
         return ([(k * rows // n) * nb * bb + qoff + (k % 32) for k in range(n)], il + 1)
 

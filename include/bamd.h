@@ -20,7 +20,7 @@ typedef struct bamd_model   bamd_model;
 typedef struct bamd_context bamd_context;
 
 /* ggml tensor type ids, as stored in GGUF (cpp/ggml/include/ggml.h:360-375) */
-enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14 };
+enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q2_K = 10, BAMD_TYPE_Q3_K = 11, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14 };
 
 const char * bamd_last_error(void);
 

@@ -1,0 +1,77 @@
+"""Greedy decode rate of the synthetic Llama-3-8B file under the Q3_K_M and Q2_K recipes beside the Q4_K_M file, and the prompt rate of the Q3_K_M file on the
+integer-dot kernel (GPU box only).  Per file: a 128-token prompt, then generate_greedy of 128 steps, five repetitions — median and range.
+
+    python tools/lowbit_decode.py [--prompt 2048]
+"""
+import importlib.util
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import booster_amd as b  # noqa: E402
+from booster_amd import gguf  # noqa: E402
+
+_spec = importlib.util.spec_from_file_location("gen_lowbit_fixtures", os.path.join(ROOT, "tests", "golden", "gen_lowbit_fixtures.py"))
+gen = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(gen)
+
+
+def q4_k_m_file():
+    p = gen.full.model_path("8b")
+    if not os.path.exists(p + ".done"):
+        gguf.write_synthetic_llama(p, seed=7, reuse_layers=True, **gen.L3_8B)
+        open(p + ".done", "w").write("ok")
+    return p
+
+
+def decode_rate(path, n_prompt=128, n_steps=128, reps=5, n_ctx=512):
+    m = b.Model(path)
+    ctx = b.Context(m, n_ctx)
+    prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
+    rates = []
+    for _ in range(reps + 1):                                   # the first repetition warms up (graph capture, clocks)
+        b.lib().bamd_kv_cache_clear(ctx.h)
+        ctx.decode(prompt, 0)
+        _, ms = ctx.generate_greedy(n_prompt, n_steps)
+        rates.append(n_steps / ms * 1e3)
+    ctx.close(); m.close()
+    return rates[1:]
+
+
+def prompt_rate(path, n_prompt, reps=3):
+    m = b.Model(path)
+    ctx = b.Context(m, 4096)
+    prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
+    rates = []
+    for _ in range(reps + 1):
+        b.lib().bamd_kv_cache_clear(ctx.h)
+        t0 = time.perf_counter()
+        for i in range(0, n_prompt, 512):
+            ctx.decode(prompt[i:i + 512], i)
+        rates.append(n_prompt / (time.perf_counter() - t0))
+    ctx.close(); m.close()
+    return rates[1:]
+
+
+def main():
+    files = [("Q4_K_M", q4_k_m_file()), ("Q3_K_M", gen.ensure_model("8b_q3_k_m")), ("Q2_K", gen.ensure_model("8b_q2_k"))]
+    for name, p in files:
+        r = decode_rate(p)
+        print("decode %-7s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, statistics.median(r), min(r), max(r)), flush=True)
+    # Llama-2-7B widths: no GQA (attn_v Q3_K under Q2_K), n_ff 11008 = 43 super-blocks; its gate/up launch (1376 row-groups) has no seven-pair shape
+    for name, p in (("Q4_K_M", gen.full.ensure_model("l2_7b")), ("Q2_K", gen.ensure_model("l2_7b_q2_k"))):
+        r = decode_rate(p, n_prompt=64, n_ctx=256)
+        print("decode Llama-2-7B %-7s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 64-token prompt)" % (name, os.path.getsize(p) / 1e9, statistics.median(r), min(r), max(r)), flush=True)
+    if "--prompt" in sys.argv:
+        n = int(sys.argv[sys.argv.index("--prompt") + 1])
+        for name, p in files[:2]:
+            r = prompt_rate(p, n)
+            print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
+                  "matrix-core kernels" if name == "Q4_K_M" else "integer-dot kernel: the model holds Q3_K matrices"), flush=True)
+
+
+if __name__ == "__main__":
+    main()

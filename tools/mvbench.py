@@ -1,17 +1,18 @@
 """Micro-benchmark of mat-vec launch shapes, back to back on one matrix (GPU box only).
 
-    python tools/mvbench.py [8b | 70b | modea | ceiling | l2-7b | l32]
+    python tools/mvbench.py [8b | 70b | modea | ceiling | l2-7b | l32 | lowbit]
 
 8b (default): the launch shapes of Llama-3-8B Q4_K_M, both launch modes where both exist, and prologue-only launches; modea: the mode-A
 kernels only (a quick A/B target for kernel edits); ceiling: streaming rate by matrix size, Infinity-Cache-resident (75 MB) up to HBM-bound
-(0.9 GB); l2-7b: Llama-2-7B (n_ff 11008 = 43 super-blocks: uneven split-K); l32: Llama-3.2-3B / 1B (n_embd 3072 / 2048)."""
+(0.9 GB); l2-7b: Llama-2-7B (n_ff 11008 = 43 super-blocks: uneven split-K); l32: Llama-3.2-3B / 1B (n_embd 3072 / 2048); lowbit: qkv, wo, gate/up and
+down at the 8B widths for Q2_K, Q3_K and Q4_K side by side (a Q3_K launch moves 0.76, a Q2_K launch 0.58 of the bytes of its Q4_K twin)."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import booster_amd as b
 
-BB = {12: 144, 13: 176, 14: 210}
+BB = {10: 84, 11: 110, 12: 144, 13: 176, 14: 210}
 # (name, type, rows, K, prologue (1 = RMSNorm), epilogue (0 store, 1 +residual, 2 silu(gate)*up, 3 arg-max), modes)
 SETS = {
     "8b": [("prologue-only K4096", 12, 8, 4096, 0, 0, (1, 2)), ("prologue-only norm K4096", 12, 8, 4096, 1, 0, (1, 2)), ("prologue-only K14336", 12, 8, 14336, 0, 0, (1, 2)),
@@ -30,6 +31,8 @@ SETS = {
     "l32": [("3B qkv", 12, 5120, 3072, 1, 0, (0,)), ("3B wo", 12, 3072, 3072, 0, 1, (0,)), ("3B gate/up", 12, 8192, 3072, 1, 2, (0,)), ("3B down q4k", 12, 3072, 8192, 0, 1, (0,)),
             ("3B down q6k", 14, 3072, 8192, 0, 1, (0,)), ("lm_head 3B", 14, 128256, 3072, 1, 3, (0,)), ("1B qkv", 12, 3072, 2048, 1, 0, (0,)), ("1B wo", 12, 2048, 2048, 0, 1, (0,)),
             ("1B gate/up", 12, 8192, 2048, 1, 2, (0,)), ("1B down q6k", 14, 2048, 8192, 0, 1, (0,))],
+    "lowbit": [("%s %s" % (nm, tn), t, rows, k, pro, epi, (0,)) for nm, rows, k, pro, epi in (("qkv", 6144, 4096, 1, 0), ("wo", 4096, 4096, 0, 1), ("gate/up", 14336, 4096, 1, 2),
+                                                                                                 ("down", 4096, 14336, 0, 1)) for t, tn in ((10, "q2k"), (11, "q3k"), (12, "q4k"))],
 }
 
 
