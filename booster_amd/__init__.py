@@ -69,6 +69,9 @@ def lib():
         L.bamd_op_rope_row.argtypes = [ci, ci, cf, cf, vp, vp]
         L.bamd_op_k_shift.argtypes = [vp, ci, ci, ci, vp, cf, cf, vp, cf, cf, ci]
         L.bamd_op_attention_cells.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
+        L.bamd_op_fused_qkv.argtypes = [ci, vp, vp, vp, ci, vp, vp, cf, ci, vp]
+        L.bamd_op_mul_mat_batch_seg.argtypes = [ci, vp, vp, vp, ci, vp, ci, vp, cf, ci, vp, ci, ci, vp]
+        L.bamd_op_attention_wo.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.bamd_set_aql.argtypes = [ci]; L.bamd_set_aql.restype = None
         L.bamd_aql_runs.argtypes = [vp]
         _lib = L
@@ -351,3 +354,54 @@ def op_attention_batch(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, pos
     out = np.zeros((T, H * hd), np.float32)
     _chk(lib().bamd_op_attention_batch(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope), H, Hkv, hd, n_ctx, pos0, T, impl, ld, _p(out)))
     return out
+
+
+def _segments(segs):
+    """[(type, raw blocks, rows), ...] -> what the segment ops take: (n, types, pointer array, rows, the arrays kept alive)"""
+    keep = [np.ascontiguousarray(w, np.uint8) for _, w, _ in segs]
+    types = np.array([t for t, _, _ in segs], np.int32); rows = np.array([r for _, _, r in segs], np.int32)
+    ptrs = (C.c_void_p * len(segs))(*[w.ctypes.data for w in keep])
+    return len(segs), types, ptrs, rows, keep
+
+
+def op_fused_qkv(segs, k, x, norm_w, eps=1e-5, mode=0):
+    """the fused QKV launch of a decode step over up to three differently typed segments [(type, raw blocks, rows), ...]: the segments' outputs, concatenated"""
+    n, types, ptrs, rows, keep = _segments(segs)
+    x = np.ascontiguousarray(x, np.float32); nw = np.ascontiguousarray(norm_w, np.float32)
+    y = np.zeros(int(rows.sum()), np.float32)
+    _chk(lib().bamd_op_fused_qkv(n, _p(types), ptrs, _p(rows), k, _p(x), _p(nw), eps, mode, _p(y)))
+    return y
+
+
+def op_mul_mat_batch_seg(segs, k, x, ldo, epi=0, residual=None, norm_w=None, eps=0.0, impl=0, fill=0.0):
+    """one batched prompt mat-mul as the engine issues it: x [T][k] against the segments [(type, raw blocks, rows), ...] into [T][ldo] (columns the call does
+    not write keep `fill`).  epi 0 store, 1 add (one segment, residual [T][ldo]), 2 silu(segment 0) * segment 1; impl 0 integer-dot, 2 matrix cores where
+    the type has them"""
+    n, types, ptrs, rows, keep = _segments(segs)
+    x = np.ascontiguousarray(x, np.float32)
+    T = x.shape[0]
+    nw = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32)
+    res = None if residual is None else np.ascontiguousarray(residual, np.float32).reshape(T, ldo)
+    y = np.full((T, ldo), fill, np.float32)
+    _chk(lib().bamd_op_mul_mat_batch_seg(n, _p(types), ptrs, _p(rows), k, _p(x), T, _p(nw), eps, ldo, _p(res), epi, impl, _p(y)))
+    return y
+
+
+def op_attention_wo(q, k, v, k_cache, v_cache_t, rope_row, H, Hkv, hd, n_ctx, pos, wo_type, wo_raw, wo_rows, residual, lds_ld=0, serial=1, step=1, il=0,
+                    gran_init=None, with_cellpos=False):
+    """attention and the wo projection of one decode layer in one launch.  The caches (uint16, reference layouts) are updated in place.  Returns a dict:
+    declined (the launcher has no co-launch for the shape: nothing else is valid), n_cu, x2 [wo_rows], gran [H*hd] uint64 {value bits | tag << 32} as the
+    launch left them, gave_up (the give-up counter)"""
+    q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
+    rope_row = np.ascontiguousarray(rope_row, np.float32)
+    assert k_cache.dtype == np.uint16 and v_cache_t.dtype == np.uint16 and k_cache.flags.c_contiguous and v_cache_t.flags.c_contiguous
+    assert k_cache.size == n_ctx * Hkv * hd and v_cache_t.size == n_ctx * Hkv * hd and q.size == H * hd
+    wo_raw = np.ascontiguousarray(wo_raw, np.uint8); res = np.ascontiguousarray(residual, np.float32)
+    assert res.size == wo_rows
+    g0 = None if gran_init is None else np.ascontiguousarray(gran_init, np.uint64)
+    assert g0 is None or g0.size == H * hd
+    x2 = np.zeros(wo_rows, np.float32); gran = np.zeros(H * hd, np.uint64)
+    gave_up = C.c_uint32(0); declined = C.c_int32(0); n_cu = C.c_int32(0)
+    _chk(lib().bamd_op_attention_wo(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope_row), H, Hkv, hd, n_ctx, pos, lds_ld, wo_type, _p(wo_raw), wo_rows,
+                                    _p(res), serial, step, il, int(bool(with_cellpos)), _p(g0), _p(x2), _p(gran), C.byref(gave_up), C.byref(declined), C.byref(n_cu)))
+    return dict(declined=bool(declined.value), n_cu=int(n_cu.value), x2=x2, gran=gran, gave_up=int(gave_up.value))

@@ -14,7 +14,7 @@
 //                   tag, quantises them, parks its terms.
 // Placement-independent: the grid is one workgroup per CU, so all roles are resident together whatever the dispatch order; every spin is
 // bounded and reports through `err` (the host checks it).  The tag = (host call serial, device step, layer) is unique among consecutive
-// uses of the granules, which are never reset.  Same arithmetic, same order, same bits as the two separate launches (tests).
+// uses of the granules, which are never reset.  Same arithmetic, same order, same bits as the two separate launches (tests/test_gpu_colaunch.py).
 #include "bamd_matvec_core.h"
 #include "bamd_attn_fused.h"
 

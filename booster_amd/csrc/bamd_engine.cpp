@@ -845,12 +845,13 @@ static int ensure_batch_buffers(bamd_context * c) {
     return 0;
 }
 // one batched mat-mul: K-quant segments with a side table on the matrix-core kernels, the rest on the integer-dot kernel (identical bits either way).
-// aux[i]: side table of segment i (null: none)
-static int batch_mm(bamd_context * c, bamd_mm_args a, int epi, int T, hipStream_t s, const void * const * aux) {
-    bamd_model * m = c->m;
+// aux[i]: side table of segment i (null: none); blob16: the f16 activations of the matrix-core kernel.  The ONE place this routing is written down: the
+// prompt path below and the op-level entry point (bamd_op_mul_mat_batch_seg) both come through here
+int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s) {
+    const int T = a.T;
     auto on_mfma = [&](int i) { return g_prefill_mfma && aux[i] && (a.seg[i].type == BAMD_Q4_K || a.seg[i].type == BAMD_Q5_K || a.seg[i].type == BAMD_Q6_K); };
     auto mm_mfma = [&](const bamd_mv_seg & sg, const void * ax, int nv, float * out, const float * res, int e) {
-        return bamd_launch_matmul_mfma2(sg.w, ax, sg.type, nv, sg.nrows, a.K, c->bblob16, T, out, res, e, a.ldo, s);
+        return bamd_launch_matmul_mfma2(sg.w, ax, sg.type, nv, sg.nrows, a.K, blob16, T, out, res, e, a.ldo, s);
     };
     if (epi == BAMD_EPI_SILU_MUL) {
         if (on_mfma(0) && on_mfma(1) && a.seg[1].type == a.seg[0].type) {
@@ -860,7 +861,7 @@ static int batch_mm(bamd_context * c, bamd_mm_args a, int epi, int T, hipStream_
             if (mm_mfma(a.seg[1], aux[1], nv, a.seg[0].out, a.seg[0].out, BAMD_EPI_SILU_MUL)) return 1;
             return 0;
         }
-        return bamd_launch_matmul_batch(a, epi, m->n_cu, s);
+        return bamd_launch_matmul_batch(a, epi, n_cu, s);
     }
     bamd_mm_args rest = a; rest.nseg = 0;
     for (int i = 0; i < a.nseg; ++i) {
@@ -872,10 +873,11 @@ static int batch_mm(bamd_context * c, bamd_mm_args a, int epi, int T, hipStream_
     }
     if (rest.nseg) {
         if (epi == BAMD_EPI_ADD) rest.res = a.res + (rest.seg[0].out - a.seg[0].out);
-        return bamd_launch_matmul_batch(rest, epi, m->n_cu, s);
+        return bamd_launch_matmul_batch(rest, epi, n_cu, s);
     }
     return 0;
 }
+static int batch_mm(bamd_context * c, const bamd_mm_args & a, int epi, hipStream_t s, const void * const * aux) { return bamd_batch_mm(a, epi, c->bblob16, aux, c->m->n_cu, s); }
 // first stage: tokens already in c->forced; later stages: hidden_in [T][E] f32 on this device.  Last stage: leaves the hidden state of
 // the LAST token in c->x (for lm_head); other stages: writes hidden_out [T][E] (possibly on the next device: peer copy).
 static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_t s, const void * hidden_in = nullptr, void * hidden_out = nullptr) {
@@ -894,7 +896,7 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s);
         a.nseg = qkv_segments(ly, c->bqkv, a.seg);
         a.blob = c->bblob; a.K = E; a.T = T; a.ldo = ldq;
-        if (batch_mm(c, a, BAMD_EPI_STORE, T, s, ly.aux_qkv)) return fail("batched mat-mul: unsupported shape");
+        if (batch_mm(c, a, BAMD_EPI_STORE, s, ly.aux_qkv)) return fail("batched mat-mul: unsupported shape");
         // RoPE, KV store, attention with the T>1 semantics                  (llama.cpp:8837-8849, :8318-8353)
         bamd_attn_args t; memset(&t, 0, sizeof t);
         t.st = c->st; t.q = c->bqkv; t.k = c->bqkv + E; t.v = c->bqkv + E + Ekv; t.kc = c->kc[il]; t.vc = c->vc[il]; t.rope = c->rope; t.out = c->batt;
@@ -918,17 +920,17 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s);
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wo, c->bx2); a.nseg = 1; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = E; a.res = c->bx;
-        { const void * ax[3] = { ly.aux_o, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, T, s, ax)) return fail("batched mat-mul: unsupported shape"); }
+        { const void * ax[3] = { ly.aux_o, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }
         // h = silu(Wg . a) * (Wu . a)
         bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s);
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wg, c->bh); seg_of(a.seg[1], ly.wu, c->bh); a.nseg = 2; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = F;
-        { const void * ax[3] = { ly.aux_g, ly.aux_u, nullptr }; if (batch_mm(c, a, BAMD_EPI_SILU_MUL, T, s, ax)) return fail("batched mat-mul: unsupported shape"); }
+        { const void * ax[3] = { ly.aux_g, ly.aux_u, nullptr }; if (batch_mm(c, a, BAMD_EPI_SILU_MUL, s, ax)) return fail("batched mat-mul: unsupported shape"); }
         // x = x2 + Wd . h
         bamd_launch_quantize_batch(c->bh, nullptr, 0.f, F, T, c->bblob, c->bblob16, s);
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wd, c->bx); a.nseg = 1; a.blob = c->bblob; a.K = F; a.T = T; a.ldo = E; a.res = c->bx2;
-        { const void * ax[3] = { ly.aux_d, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, T, s, ax)) return fail("batched mat-mul: unsupported shape"); }
+        { const void * ax[3] = { ly.aux_d, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }
     }
     if (m->with_output) HIPC(hipMemcpyAsync(c->x, c->bx + (size_t) (T - 1) * E, (size_t) E * 4, hipMemcpyDeviceToDevice, s));
     else HIPC(hipMemcpyAsync(hidden_out, c->bx, (size_t) T * E * 4, hipMemcpyDeviceToDevice, s));

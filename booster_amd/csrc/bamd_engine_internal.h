@@ -27,3 +27,7 @@ void rope_row(float * cache, int32_t pos, int n_dims, float freq_base, float fre
               float ext_factor, float attn_factor, int n_ctx_orig, float beta_fast, float beta_slow);
 void k_shift_table(const int32_t * delta, int n_cells, int n_idx, int hd, float freq_base, float freq_scale, const float * freq_factors,
                    float ext_factor, float attn_factor, int n_ctx_orig, std::vector<int32_t> & idx, std::vector<float> & tab);
+// defined in bamd_engine.cpp: one batched prompt mat-mul, each segment routed to the matrix-core kernel (side table aux[i], f16 activations blob16) or to the
+// integer-dot kernel — the prompt path's routing, shared with bamd_op_mul_mat_batch_seg
+struct bamd_mm_args;
+int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s);

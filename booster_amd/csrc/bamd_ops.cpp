@@ -295,6 +295,141 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(co
     return f.down(a, out, (size_t) T * E, k_cache, v_cache_t);
 }
 
+// ---- launches with more than one operand role, with the argument blocks of the engine (enqueue_layers, enqueue_prefill_batch) ----
+
+// up to three K-quant matrices of `k` columns on the device as wave streams, with outputs one behind the other from `out` as qkv_segments / seg_of lay them
+// out: nrows padded to 8 per segment, nvalid the real rows, segment i's output `rows[0] + .. + rows[i - 1]` floats behind `out`
+struct SegFixture {
+    bamd_mv_seg seg[3]; int nseg = 0, total = 0;
+    int build(Tmp & t, int n, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, float * out, bool same_out = false) {
+        if (n < 1 || n > 3 || k <= 0 || k % 256) return fail("bad segment count / row length");
+        for (int i = 0; i < n; ++i) {
+            if (!bamd_is_kquant(types[i]) || rows[i] <= 0 || !w_raw[i]) return fail("bad segment type / rows");
+            const int pad = (rows[i] + 7) / 8 * 8;
+            const size_t wb = bamd_row_bytes(types[i], k) * (size_t) rows[i], wbp = bamd_stream_bytes(types[i], k, pad);
+            void * raw = t.up(w_raw[i], wb), * str = t.up(nullptr, wbp);
+            if (!raw || !str) return fail("device alloc/copy failed");
+            HIPC(hipMemset(str, 0, wbp));
+            bamd_launch_repack(raw, str, types[i], rows[i], k, nullptr);
+            seg[i].w = str; seg[i].out = same_out ? out : out + total; seg[i].type = types[i]; seg[i].nrows = pad; seg[i].nvalid = rows[i];
+            total += rows[i];
+        }
+        nseg = n;
+        return 0;
+    }
+};
+
+// the fused QKV launch of a decode step (enqueue_layers, 1.): RMSNorm prologue + store over up to three differently typed segments
+extern "C" __attribute__((visibility("default"))) int bamd_op_fused_qkv(int nseg, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, const float * x,
+                                                                          const float * norm_w, float eps, int mode, float * y) {
+    if (need_device()) return 1;
+    if (nseg < 1 || nseg > 3 || !norm_w) return fail("bad segment count / no norm weight");
+    int total = 0; for (int i = 0; i < nseg; ++i) { if (rows[i] <= 0) return fail("bad segment rows"); total += rows[i]; }
+    Tmp t;
+    float * dy = (float *) t.up(nullptr, (size_t) total * 4 + 64);           // (+ 64: a ragged last segment is padded to 8 rows in the stream, never in the output)
+    float * dx = (float *) t.up(x, (size_t) k * 4), * dw = (float *) t.up(norm_w, (size_t) k * 4);
+    if (!dy || !dx || !dw) return fail("device alloc/copy failed");
+    SegFixture f; if (f.build(t, nseg, types, w_raw, rows, k, dy)) return 1;
+    bamd_mv_args a; memset(&a, 0, sizeof a);
+    for (int i = 0; i < nseg; ++i) a.seg[i] = f.seg[i];
+    a.nseg = nseg; a.x = dx; a.normw = dw; a.eps = eps; a.K = k; a.mode = mode;
+    if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_STORE, n_cu0(), nullptr)) return fail("mat-vec: type without a kernel");
+    return finish(y, dy, (size_t) total * 4);
+}
+
+// one batched prompt mat-mul as enqueue_prefill_batch issues it: up to three segments into one [T][ldo] matrix (STORE: the q | k | v call; ADD: one segment
+// + residual; SILU_MUL: gate and up into the same columns), routed by bamd_batch_mm.  impl 0: no side tables (integer-dot kernel); impl 2: a side table for
+// every segment whose type has a matrix-core kernel, built as build_prefill_aux builds them — the others stay on the integer-dot kernel
+extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(int nseg, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, const float * x,
+                                                                                  int T, const float * norm_w, float eps, int ldo, const float * residual, int epi, int impl, float * y) {
+    if (need_device()) return 1;
+    if (T <= 0 || T > BAMD_PREFILL_CAP || ldo <= 0 || (impl != 0 && impl != 2)) return fail("bad T / ldo / impl");
+    if (epi != BAMD_EPI_STORE && epi != BAMD_EPI_ADD && epi != BAMD_EPI_SILU_MUL) return fail("bad epilogue");
+    if (nseg < 1 || nseg > 3 || (epi == BAMD_EPI_ADD && (nseg != 1 || !residual)) || (epi == BAMD_EPI_SILU_MUL && (nseg != 2 || rows[0] != rows[1]))) return fail("bad segments for this epilogue");
+    int total = 0; for (int i = 0; i < nseg; ++i) { if (rows[i] <= 0) return fail("bad segment rows"); total += rows[i]; }
+    if ((epi == BAMD_EPI_SILU_MUL ? rows[0] : total) > ldo) return fail("ldo smaller than the rows of a token");
+    Tmp t; const size_t ob = (size_t) T * ldo * 4;
+    float * dy = (float *) t.up(y, ob);                                      // the caller's content stays where the launch writes nothing
+    float * dx = (float *) t.up(x, (size_t) T * k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr;
+    float * dres = residual ? (float *) t.up(residual, ob) : nullptr;
+    void * blob = t.up(nullptr, (size_t) T * bamd_blob_bytes(k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
+    if (!dy || !dx || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
+    SegFixture f; if (f.build(t, nseg, types, w_raw, rows, k, dy, epi == BAMD_EPI_SILU_MUL)) return 1;
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr);
+    const void * aux[3] = { nullptr, nullptr, nullptr };
+    if (impl == 2) for (int i = 0; i < nseg; ++i) {
+        const size_t ab = bamd_prefill_aux_bytes(f.seg[i].type, f.seg[i].nrows, k);
+        if (!ab) continue;                                                   // Q2_K / Q3_K, or a shape without a matrix-core kernel
+        void * ax = t.up(nullptr, ab);
+        if (!ax) return fail("device alloc failed");
+        bamd_launch_prefill_aux(f.seg[i].w, f.seg[i].type, f.seg[i].nrows, k, ax, nullptr);
+        aux[i] = ax;
+    }
+    bamd_mm_args a; memset(&a, 0, sizeof a);
+    for (int i = 0; i < nseg; ++i) a.seg[i] = f.seg[i];
+    a.nseg = nseg; a.blob = (const uint8_t *) blob; a.K = k; a.T = T; a.ldo = ldo; a.res = epi == BAMD_EPI_ADD ? dres : nullptr;
+    if (bamd_batch_mm(a, epi, blob16, aux, n_cu0(), nullptr)) return fail("batched mat-mul: unsupported shape");
+    return finish(y, dy, ob);
+}
+
+// attention and the wo projection of one decode layer in ONE launch (bamd_launch_attn_wo), with the argument blocks of enqueue_layers: the attention block as
+// bamd_op_attention fills it plus lds_ld (0: the engine's min(512, padded n_ctx)) and rope_cur, the wo block with a.x = the attention output vector, a.res = the
+// residual, mode 0, n_cu from the device.  serial / step / il make the tag of this launch; gran_init (null: zeros) is what the H * hd granules hold before it.
+// *declined = 1: the launcher has no co-launch for this shape (nothing ran, no output is written)
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention_wo(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                                                             const float * rope_row_h, int H, int Hkv, int hd, int n_ctx, int pos, int lds_ld, int wo_type,
+                                                                             const void * wo_raw, int wo_rows, const float * residual, int serial, int step, int il,
+                                                                             int with_cellpos, const uint64_t * gran_init, float * x2, uint64_t * gran_out, uint32_t * gave_up,
+                                                                             int32_t * declined, int32_t * n_cu_used) {
+    if (need_device()) return 1;
+    if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || pos < 0 || pos >= n_ctx || n_ctx % 32 || H % Hkv) return fail("bad attention shape");
+    const int K = H * hd;
+    if (!bamd_is_kquant(wo_type) || K % 256 || wo_rows <= 0 || !residual) return fail("bad wo type/shape, or no residual");
+    AttnFixture f(n_ctx, Hkv, hd); const int Ekv = Hkv * hd;
+    bamd_step_state h; memset(&h, 0, sizeof h);
+    h.pos_base = pos; h.pos = pos; h.n_ctx = n_ctx; h.n_kv = std::min(n_ctx, std::max(32, (pos + 1 + 31) / 32 * 32)); h.serial = serial; h.step = step;
+    if (lds_ld == 0) lds_ld = std::min(512, f.n_ctx_pad);                       // enqueue_layers
+    if (lds_ld % 64 || lds_ld < (h.n_kv + 63) / 64 * 64 || lds_ld > f.n_ctx_pad) return fail("lds_ld must be a multiple of 64 between the padded sequence length and the padded n_ctx");
+    std::vector<float> rope((size_t) n_ctx * hd, 0.f);
+    memcpy(rope.data() + (size_t) pos * hd, rope_row_h, (size_t) hd * 4);
+    std::vector<uint64_t> g0((size_t) K, 0ull);
+    if (gran_init) memcpy(g0.data(), gran_init, (size_t) K * 8);
+    std::vector<int32_t> cp((size_t) f.n_ctx_pad, -1);
+    for (int i = 0; i <= pos; ++i) cp[(size_t) i] = i;
+    const uint32_t zero8[8] = { 0 };
+    bamd_attn_args a; memset(&a, 0, sizeof a);
+    a.st = (bamd_step_state *) f.up(&h, sizeof h);
+    a.q = (float *) f.up(q, (size_t) K * 4); a.k = (float *) f.up(k, (size_t) Ekv * 4); a.v = (float *) f.up(v, (size_t) Ekv * 4);
+    f.kv_up(k_cache, v_cache_t);
+    a.rope = (float *) f.up(rope.data(), rope.size() * 4); a.rope_cur = (float *) f.up(rope_row_h, (size_t) hd * 4);
+    f.rows(a, H);
+    unsigned long long * gran = (unsigned long long *) f.up(g0.data(), (size_t) K * 8);
+    uint32_t * err = (uint32_t *) f.up(zero8, sizeof zero8);
+    if (with_cellpos) a.cellpos = (const int32_t *) f.up(cp.data(), cp.size() * 4);
+    const int nrows_pad = (wo_rows + 7) / 8 * 8;
+    const size_t wb = bamd_row_bytes(wo_type, K) * (size_t) wo_rows, wbp = bamd_stream_bytes(wo_type, K, nrows_pad);
+    void * raw = f.up(wo_raw, wb), * str = f.up(nullptr, wbp);
+    float * dres = (float *) f.up(residual, (size_t) wo_rows * 4), * dx2 = (float *) f.up(nullptr, (size_t) nrows_pad * 4);
+    if (!f.ok()) return fail("device alloc/copy failed");
+    HIPC(hipMemset(str, 0, wbp));
+    HIPC(hipMemset(dx2, 0, (size_t) nrows_pad * 4));
+    bamd_launch_repack(raw, str, wo_type, wo_rows, K, nullptr);
+    f.args(a, 0);
+    a.lds_ld = lds_ld;
+    if (bamd_attention_split_is_ik_clean(a, H / Hkv)) a.probs = nullptr;        // enqueue_layers: the probability rows in global memory belong to the softmax | P.V pair only
+    bamd_mv_args w; memset(&w, 0, sizeof w);
+    w.seg[0].w = str; w.seg[0].out = dx2; w.seg[0].type = wo_type; w.seg[0].nrows = nrows_pad; w.seg[0].nvalid = wo_rows; w.nseg = 1;
+    w.x = a.out; w.K = K; w.res = dres;
+    const int n_cu = n_cu0();
+    *n_cu_used = n_cu;
+    *declined = bamd_launch_attn_wo(a, H / Hkv, w, n_cu, gran, il & 255, err, nullptr) != 0;
+    if (*declined) return 0;
+    if (finish(x2, dx2, (size_t) wo_rows * 4) || f.kv_down(k_cache, v_cache_t)) return 1;
+    HIPC(hipMemcpy(gran_out, gran, (size_t) K * 8, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(gave_up, err, 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- micro-benchmark of one mat-vec launch shape (random resident weights; HIP-event timing of `iters` launches) ----
 extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type, int nrows, int k, int pro, int epi, int mode, int iters,
                                                                         float * us_per_launch) {

@@ -236,6 +236,27 @@ int bamd_op_k_shift(uint16_t * k_cache, int n_ctx, int Hkv, int hd, const int32_
 int bamd_op_attention_cells(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t, const float * rope_row,
                             const int32_t * cellpos, int cell, int n_kv, int H, int Hkv, int hd, int n_ctx, int pos, int tiles, float * out,
                             float * probs_h0);
+/* the fused QKV launch of a decode step over up to three differently typed segments (types / w_raw / rows [nseg]: GGUF-layout blocks [rows[i]][k]), argument
+ * block as the engine's: outputs one behind the other, RMSNorm prologue (norm_w required), store epilogue.  y [rows[0] + .. + rows[nseg - 1]].
+ * mode: 0 the launcher's choice, 1 one wave per row-group, 2 split-K, + 16 generic kernels */
+int bamd_op_fused_qkv(int nseg, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, const float * x, const float * norm_w,
+                      float eps, int mode, float * y);
+/* one batched prompt mat-mul as the engine issues it: T activation rows x [T][k] against up to three segments, into y [T][ldo] (in: what the untouched
+ * columns keep; out: the result).  epi 0 (store): segment outputs one behind the other in each row; epi 1 (add): one segment, residual [T][ldo]; epi 2:
+ * y = silu(seg 0 . a) * (seg 1 . a), both of rows[0] rows.  impl 0: integer-dot kernel; impl 2: every segment whose type has a matrix-core kernel runs
+ * there, with a side table built as at model load, the others (Q2_K, Q3_K) stay on the integer-dot kernel — the routing of the engine's prompt path */
+int bamd_op_mul_mat_batch_seg(int nseg, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, const float * x, int T,
+                              const float * norm_w, float eps, int ldo, const float * residual, int epi, int impl, float * y);
+/* attention and the wo projection of one decode layer in ONE launch (the co-launch of a decode step below 448 positions): the inputs of bamd_op_attention
+ * (decode semantics), lds_ld = floats per LDS score row (0 = the engine's min(512, padded n_ctx)), the wo matrix [wo_rows][H * hd] of wo_type and the residual
+ * [wo_rows].  serial, step and il go into the launch's tag (serial << 20 | (step & 0xfff) << 8 | il) as the step state and the layer index; with_cellpos != 0
+ * passes a cell-position table (the launcher must decline); gran_init (NULL = zeros) is what the H * hd 8-byte granules {value bits, tag} hold before the
+ * launch.  Out: x2 [wo_rows], the updated caches, gran_out [H * hd] as the launch left them, *gave_up = the give-up counter, *n_cu_used = the device's CU
+ * count.  *declined = 1: the launcher has no co-launch kernel for the shape; nothing ran and the other outputs are untouched */
+int bamd_op_attention_wo(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t, const float * rope_row, int H, int Hkv,
+                         int hd, int n_ctx, int pos, int lds_ld, int wo_type, const void * wo_raw, int wo_rows, const float * residual, int serial, int step,
+                         int il, int with_cellpos, const uint64_t * gran_init, float * x2, uint64_t * gran_out, uint32_t * gave_up, int32_t * declined,
+                         int32_t * n_cu_used);
 
 #ifdef __cplusplus
 }
