@@ -72,6 +72,8 @@ def lib():
         L.bamd_op_fused_qkv.argtypes = [ci, vp, vp, vp, ci, vp, vp, cf, ci, vp]
         L.bamd_op_mul_mat_batch_seg.argtypes = [ci, vp, vp, vp, ci, vp, ci, vp, cf, ci, vp, ci, ci, vp]
         L.bamd_op_attention_wo.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+        L.bamd_trace_matvec.argtypes = [ci, vp, vp, ci, ci, ci, ci, ci, vp]
+        L.bamd_trace_attn_wo.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         L.bamd_set_aql.argtypes = [ci]; L.bamd_set_aql.restype = None
         L.bamd_aql_runs.argtypes = [vp]
         _lib = L
@@ -405,3 +407,30 @@ def op_attention_wo(q, k, v, k_cache, v_cache_t, rope_row, H, Hkv, hd, n_ctx, po
     _chk(lib().bamd_op_attention_wo(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope_row), H, Hkv, hd, n_ctx, pos, lds_ld, wo_type, _p(wo_raw), wo_rows,
                                     _p(res), serial, step, il, int(bool(with_cellpos)), _p(g0), _p(x2), _p(gran), C.byref(gave_up), C.byref(declined), C.byref(n_cu)))
     return dict(declined=bool(declined.value), n_cu=int(n_cu.value), x2=x2, gran=gran, gave_up=int(gave_up.value))
+
+
+class _LaunchTrace(C.Structure):
+    _fields_ = [("kernel", C.c_char * 1024), ("grid", C.c_uint32 * 3), ("block", C.c_uint32 * 3), ("lds_bytes", C.c_uint32), ("kernarg_bytes", C.c_uint32),
+                ("kernarg_hash", C.c_uint64)]
+
+
+def _trace(rc, t):
+    if rc == 1:
+        return None
+    _chk(rc)
+    return dict(kernel=t.kernel.decode(), grid=list(t.grid), block=list(t.block), lds=int(t.lds_bytes), kernarg_bytes=int(t.kernarg_bytes),
+                kernarg_hash=int(t.kernarg_hash))
+
+
+def trace_matvec(segs, k, pro, epi, mode=0, n_cu=256):
+    """what bamd_launch_matvec would launch for the segments [(type, rows), ...] (host only, no device needed): a dict {kernel (mangled name), grid, block, lds,
+    kernarg_bytes, kernarg_hash}, or None when a segment's type has no kernel"""
+    types = np.array([t for t, _ in segs], np.int32); rows = np.array([r for _, r in segs], np.int32)
+    t = _LaunchTrace()
+    return _trace(lib().bamd_trace_matvec(len(segs), _p(types), _p(rows), k, pro, epi, mode, n_cu, C.byref(t)), t)
+
+
+def trace_attn_wo(H, Hkv, hd, n_ctx, lds_ld, wo_type, wo_rows, k, n_cu=256, il=0, with_cellpos=False):
+    """what bamd_launch_attn_wo would launch (as trace_matvec), or None when it declines the shape"""
+    t = _LaunchTrace()
+    return _trace(lib().bamd_trace_attn_wo(H, Hkv, hd, n_ctx, lds_ld, int(bool(with_cellpos)), wo_type, wo_rows, k, n_cu, il, C.byref(t)), t)

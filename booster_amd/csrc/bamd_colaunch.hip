@@ -78,7 +78,7 @@ __device__ __forceinline__ void wo_role(const bamd_mv_args & a, const ProArgs & 
     TL_STAMP(pa.tl, 2);
     ap.template quantize_batch<NBW>(1.0f, pa.K, i0, pa.q8, pa.S, pa.yd, 1, i0 + NBW);
     const uint32_t * q8 = pa.q8; const int * S = pa.S; const float * yd = pa.yd;
-    const size_t rg_floats = BAMD_TERM_FLOATS(nb);
+    const size_t rg_floats = mv_term_floats(nb);
 #pragma unroll
     for (int m = 0; m < M; ++m) {
         float4 * P = (float4 *) (part0 + (size_t) m * rg_floats);
@@ -114,7 +114,6 @@ __device__ __forceinline__ void wo_role(const bamd_mv_args & a, const ProArgs & 
 template <int TYPE>
 __device__ __forceinline__ void wo_role_batched(const bamd_mv_args & a, const ProArgs & pa, const int j, const int G, const int count, float * part0, const unsigned long long * gran,
                                                 const bamd_step_state * st, const int il, const int ring_delay_in, uint32_t * err) {
-    typedef typename RecOf<TYPE>::type REC;
     constexpr int NBW = 4;
     const int ring_delay = ring_delay_in & 0xff; const bool poll_sleep = (ring_delay_in >> 8) & 1;
     const int nb = pa.K >> 8, lane = threadIdx.x & 63, i0 = wave_id() * NBW;
@@ -142,7 +141,7 @@ __device__ __forceinline__ void wo_role_batched(const bamd_mv_args & a, const Pr
     };
     int batchctr = 0;
     const int nv = a.seg[0].nvalid > 0 ? a.seg[0].nvalid : a.seg[0].nrows;
-    split_stream<TYPE, REC, NBW, 2, 2, BAMD_EPI_ADD, BAMD_PRO_PLAIN, true, false, false>((const uint8_t *) a.seg[0].w, nb, j, count, G, a.seg[0].out, a.res, pa, ap, ap2, false, true,
+    split_stream<TYPE, NBW, 2, 2, BAMD_EPI_ADD, BAMD_PRO_PLAIN, true, false, false>((const uint8_t *) a.seg[0].w, nb, j, count, G, a.seg[0].out, a.res, pa, ap, ap2, false, true,
                                                                                          part0, batchctr, nv, wait_for_attention);
 }
 
@@ -160,7 +159,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     TL_STAMP(wo.tl, 0);
     const int j = (int) blockIdx.x - H, G = (int) gridDim.x - H;
     const ProArgs pa = carve_lds(wo, smem);
-    float * part0 = (float *) (smem + BAMD_ACT_RED_OFF(wo.K >> 8) + 16 * sizeof(double));
+    float * part0 = (float *) (smem + BAMD_ACT_RED_OFF(wo.K >> 8) + 16 * sizeof(double));         // = mv_terms_off, written out: through the function this kernel's registers are allocated differently
     if ((wo.K >> 8) == 32) {                                                                          // 70B width: batched (count = 5 or 6 row-groups)
         const int nrg = wo.seg[0].nrows >> 3;
         wo_role_batched<TYPE>(wo, pa, j, G, nrg / G + (j < nrg % G ? 1 : 0), part0, gran, at.st, il, ring_delay, err);
@@ -170,8 +169,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     TL_STAMP(wo.tl, 7);
 }
 
-static const bool g_colaunch = [] { const char * e = getenv("BAMD_COLAUNCH"); return !(e && e[0] == '0'); }();
-static const int g_ring_delay = [] { const char * e = getenv("BAMD_COLAUNCH_DELAY"); return e ? atoi(e) : 12 + 256; }();   // low byte: x ~0.2 us; + 256: s_sleep between polls (A/B on the MI355X, round 3 end: 707 / 708 / 710 / 713-717 / 712 / 705 / 694 tok/s at 6 / 8 / 10 / 12 / 14 / 16 / 20, all + sleep)      // x ~0.2 us before the wo role requests its weights
+static const bool g_colaunch = env_flag("BAMD_COLAUNCH", true);
+static const bool g_colaunch70 = env_flag("BAMD_COLAUNCH70", false);
+static const int g_ring_delay = env_int("BAMD_COLAUNCH_DELAY", 12 + 256);   // low byte: x ~0.2 us; + 256: s_sleep between polls (A/B on the MI355X, round 3 end: 707 / 708 / 710 / 713-717 / 712 / 705 / 694 tok/s at 6 / 8 / 10 / 12 / 14 / 16 / 20, all + sleep)      // x ~0.2 us before the wo role requests its weights
 
 // 0 = launched; 1 = this shape has no co-launch kernel (the caller issues the two ordinary launches)
 int bamd_launch_attn_wo(const bamd_attn_args & t, int gq, const bamd_mv_args & wo, int n_cu, unsigned long long * gran, int il, uint32_t * err, hipStream_t s) {
@@ -187,22 +187,14 @@ int bamd_launch_attn_wo(const bamd_attn_args & t, int gq, const bamd_mv_args & w
         // the 70B width: MEASURED NEUTRAL (round 4: a 10-layer stage 1.267 ms per token co-launched against 1.260 with the two launches; the whole model 110.9
         // against 115.2 tok/s in one bench.py pairing) — the wo role's 5 - 6 row-groups x 32 records are 190 KB per workgroup, of which only the first
         // batch can be in flight while the attention role works, and the hand-over costs what the boundary did.  BAMD_COLAUNCH70=1 selects it.
-        static const bool on70 = [] { const char * e = getenv("BAMD_COLAUNCH70"); return e && e[0] == '1'; }();
-        if (!on70 || nrg / G < 2) return 1;
+        if (!g_colaunch70 || nrg / G < 2) return 1;
     }
     const int extra = nrg - 2 * G;
-    const size_t lds_wo = act_lds_bytes(wo.K) + 16 + (nb == 32 ? (size_t) 2 * 2 * nb * 256 * 4 : (size_t) 3 * nb * 256 * 4), lds_at = (size_t) ld * 8;
-    const size_t lds = lds_wo > lds_at ? lds_wo : lds_at;
-    const dim3 grid(n_cu), block(512);
-#define BAMD_CL(LG_, T_) BAMD_LAUNCH((attn_wo_kernel<LG_, T_>), grid, block, lds, s, t, gq, wo, gran, il, extra, g_ring_delay, err)
-#define BAMD_CL_T(LG_) do { if (type == BAMD_Q4_K) BAMD_CL(LG_, BAMD_Q4_K); else if (type == BAMD_Q5_K) BAMD_CL(LG_, BAMD_Q5_K); else if (type == BAMD_Q6_K) BAMD_CL(LG_, BAMD_Q6_K); else if (type == BAMD_Q3_K) BAMD_CL(LG_, BAMD_Q3_K); else if (type == BAMD_Q2_K) BAMD_CL(LG_, BAMD_Q2_K); else return 1; } while (0)
-    switch (t.hd >> 6) {
-        case 1: BAMD_CL_T(1); break;
-        case 2: BAMD_CL_T(2); break;
-        case 3: BAMD_CL_T(3); break;
-        default: BAMD_CL_T(4); break;
-    }
-#undef BAMD_CL_T
-#undef BAMD_CL
-    return 0;
+    // term buffers of the wo role: K = 4096 up to three row-groups in one batch (wo_role), K = 8192 two buffers of two (wo_role_batched)
+    const size_t lds = mv_lds_colaunch(nb, nb == 32 ? 2 * 2 : 3, ld);
+    const int lg = t.hd >> 6;                                                                 // attention instance: head size / 64 (1..4, checked above)
+    return with_const(consts<1, 2, 3, 4>(), lg >= 1 && lg <= 3 ? lg : 4, [&](auto LG) -> bool {
+        return with_kquant(type, [&](auto T) -> bool {
+            BAMD_LAUNCH((attn_wo_kernel<decltype(LG)::value, decltype(T)::value>), dim3(n_cu), dim3(512), lds, s, t, gq, wo, gran, il, extra, g_ring_delay, err);
+            return true; }); }) ? 0 : 1;
 }

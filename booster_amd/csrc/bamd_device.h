@@ -1077,12 +1077,7 @@ __device__ __forceinline__ void rope_heads(const float * src, const float * rope
 
 
 // dynamic LDS of a mat-vec workgroup: quantised activations + reduction scratch (host side of carve_lds)
-static inline size_t act_lds_bytes(int K) {
-    const int nb = K >> 8;
-    size_t b = (size_t) nb * (256 + 32 + 4);
-    b = (b + 15) & ~(size_t) 15;
-    return b + 16 * sizeof(double) + 16 * sizeof(unsigned long long);
-}
+constexpr size_t act_lds_bytes(int K) { return BAMD_ACT_RED_OFF(K >> 8) + 16 * sizeof(double) + 16 * sizeof(unsigned long long); }
 
 
 // one token's Q8_K activations in global memory: LDS layout (matmul_batch_kernel) and f16 MFMA layout (matmul_mfma_*), bamd_prefill.hip

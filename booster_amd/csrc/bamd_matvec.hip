@@ -87,15 +87,15 @@ __global__ void __launch_bounds__(512) quantize_q8k_test_kernel(const float * x,
     }
 }
 
-template <int TYPE, typename REC, int EPI, int PRO>
+template <int TYPE, int EPI, int PRO>
 __device__ __forceinline__ void stream_dispatch_depth(const uint8_t * wA, const uint8_t * wB, int nb, int first, int count, int stride,
                                                       float * out, const float * res, const ProArgs & pa, bool do_pro,
                                                       unsigned long long & best, int nvalid) {
     ActPro<PRO == BAMD_PRO_NORM> ap;
-    if ((nb & 7) == 0)      stream_segment<TYPE, REC, 8, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
-    else if ((nb & 3) == 0) stream_segment<TYPE, REC, 4, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
-    else if ((nb & 1) == 0) stream_segment<TYPE, REC, 2, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
-    else                    stream_segment<TYPE, REC, 1, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
+    if ((nb & 7) == 0)      stream_segment<TYPE, 8, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
+    else if ((nb & 3) == 0) stream_segment<TYPE, 4, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
+    else if ((nb & 1) == 0) stream_segment<TYPE, 2, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
+    else                    stream_segment<TYPE, 1, EPI, PRO>(wA, wB, nb, first, count, stride, out, res, pa, ap, do_pro, do_pro, best, nvalid);
 }
 
 template <int PRO, int EPI>
@@ -125,11 +125,11 @@ __global__ void __launch_bounds__(512) matvec_kernel(bamd_mv_args a) {
             float * out = a.seg[s].out;
             const float * res = a.res;
             const int nv = a.seg[s].nvalid > 0 ? a.seg[s].nvalid : a.seg[s].nrows;
-            if (t == BAMD_Q4_K)      stream_dispatch_depth<BAMD_Q4_K, RecQ4K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
-            else if (t == BAMD_Q5_K) stream_dispatch_depth<BAMD_Q5_K, RecQ5K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
-            else if (t == BAMD_Q6_K) stream_dispatch_depth<BAMD_Q6_K, RecQ6K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
-            else if (t == BAMD_Q3_K) stream_dispatch_depth<BAMD_Q3_K, RecQ3K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
-            else if (t == BAMD_Q2_K) stream_dispatch_depth<BAMD_Q2_K, RecQ2K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            if (t == BAMD_Q4_K)      stream_dispatch_depth<BAMD_Q4_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_Q5_K) stream_dispatch_depth<BAMD_Q5_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_Q6_K) stream_dispatch_depth<BAMD_Q6_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_Q3_K) stream_dispatch_depth<BAMD_Q3_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_Q2_K) stream_dispatch_depth<BAMD_Q2_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
             else __builtin_trap();                           // unreachable: bamd_launch_matvec refuses any other type on the host; never a silent read as another format
             pro_done = true;
         }
@@ -152,36 +152,37 @@ __global__ void __launch_bounds__(512) matvec_kernel(bamd_mv_args a) {
     TL_STAMP(a.tl, 7);
 }
 
-template <int TYPE, typename REC, int EPI, int PRO>
+template <int TYPE, int EPI, int PRO>
 __device__ __forceinline__ void split_dispatch(const uint8_t * w, int nb, int first, int count, int stride, float * out, const float * res,
                                                const ProArgs & pa, bool do_pro, float * part0, int & rgctr, int nvalid) {
     const int nbw = nb >> 3;
     ActPro<PRO == BAMD_PRO_NORM> ap, ap2;
-    if (nb & 7) {                                        // uneven K-split (split_supported): NBW = the larger share
-        if (nbw == 5)      split_stream<TYPE, REC, 6, 1, 2, EPI, PRO, false, false, true>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
-        else if (nbw == 6) split_stream<TYPE, REC, 7, 1, 2, EPI, PRO, false, false, true>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
-        else if (nbw == 2) split_stream<TYPE, REC, 3, 2, 2, EPI, PRO, false, false, true>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
+    if (nb & 7) {                                        // uneven K-split: NBW = the larger share
+        if (nbw == 5)      split_stream<TYPE, 6, 1, 2, EPI, PRO, false, false, true>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
+        else if (nbw == 6) split_stream<TYPE, 7, 1, 2, EPI, PRO, false, false, true>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
+        else if (nbw == 2) split_stream<TYPE, 3, 2, 2, EPI, PRO, false, false, true>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
         else __builtin_trap();
         return;
     }
-    // (records per wave per row-group, row-groups per batch, term buffers): the batch is the prefetch depth.  K = 14336 with M = 2
-    // (all of ffn_down's work per workgroup in flight from the first instruction, single-buffered) measured no better for Q4_K and
-    // 14 % worse for Q6_K than M = 1: the kernel is instruction-issue bound, not latency bound.
-    if (nbw == 2)       split_stream<TYPE, REC, 2, 4, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
-    else if (nbw == 7)  split_stream<TYPE, REC, 7, 1, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
-    else if (nbw == 4)  split_stream<TYPE, REC, 4, 2, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
-    else if (nbw == 1)  split_stream<TYPE, REC, 1, 8, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
+    // (records per wave per row-group, row-groups per batch, term buffers) of split_shape, written out: taking them from the table inside this function
+    // changes the kernels' register allocation.  The assertion below keeps the two in step
+    if (nbw == 2)       split_stream<TYPE, 2, 4, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
+    else if (nbw == 7)  split_stream<TYPE, 7, 1, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
+    else if (nbw == 4)  split_stream<TYPE, 4, 2, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
+    else if (nbw == 1)  split_stream<TYPE, 1, 8, 2, EPI, PRO>(w, nb, first, count, stride, out, res, pa, ap, ap2, do_pro, do_pro, part0, rgctr, nvalid);
     else __builtin_trap();                               // the launcher only picks this kernel for the shapes above
 }
+static_assert(split_shape(41) == SplitShape{6, 1, 2, true} && split_shape(49) == SplitShape{7, 1, 2, true} && split_shape(17) == SplitShape{3, 2, 2, true} && split_shape(16) == SplitShape{2, 4, 2, false} &&
+              split_shape(56) == SplitShape{7, 1, 2, false} && split_shape(32) == SplitShape{4, 2, 2, false} && split_shape(8) == SplitShape{1, 8, 2, false}, "split_dispatch's instances are split_shape's entries");
 
-// host must check bamd_split_supported(nb) before choosing this kernel
+// the launcher picks this kernel only where split_shape(K / 256) has an entry
 template <int PRO, int EPI>
 __global__ void __launch_bounds__(512) matvec_split_kernel(bamd_mv_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     TL_STAMP(a.tl, 0);
     const int nb = a.K >> 8;
     const ProArgs pa = carve_lds(a, smem);
-    float * part0 = (float *) (smem + BAMD_ACT_RED_OFF(nb) + 16 * sizeof(double));
+    float * part0 = (float *) (smem + mv_terms_off(nb));
     int rgctr = 0;
     bool pro_done = false;
     int off = 0;
@@ -195,11 +196,11 @@ __global__ void __launch_bounds__(512) matvec_split_kernel(bamd_mv_args a) {
             const int t = a.seg[s].type;
             const uint8_t * w = (const uint8_t *) a.seg[s].w;
             const int nv = a.seg[s].nvalid > 0 ? a.seg[s].nvalid : a.seg[s].nrows;
-            if (t == BAMD_Q4_K)      split_dispatch<BAMD_Q4_K, RecQ4K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
-            else if (t == BAMD_Q5_K) split_dispatch<BAMD_Q5_K, RecQ5K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
-            else if (t == BAMD_Q6_K) split_dispatch<BAMD_Q6_K, RecQ6K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
-            else if (t == BAMD_Q3_K) split_dispatch<BAMD_Q3_K, RecQ3K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
-            else if (t == BAMD_Q2_K) split_dispatch<BAMD_Q2_K, RecQ2K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            if (t == BAMD_Q4_K)      split_dispatch<BAMD_Q4_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_Q5_K) split_dispatch<BAMD_Q5_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_Q6_K) split_dispatch<BAMD_Q6_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_Q3_K) split_dispatch<BAMD_Q3_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_Q2_K) split_dispatch<BAMD_Q2_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
             else __builtin_trap();
             pro_done = true;
         }
@@ -295,67 +296,44 @@ void bamd_launch_quantize_q8k_test(const float * x, const float * nw, float eps,
     BAMD_LAUNCH(quantize_q8k_test_kernel, dim3(1), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, norm, (uint8_t *) out);
 }
 
-template <int PRO>
-static void launch_mv_epi(const bamd_mv_args & a, int epi, int grid, hipStream_t s) {
-    const size_t lds = act_lds_bytes(a.K);
-    switch (epi) {
-        case BAMD_EPI_STORE:    BAMD_LAUNCH((matvec_kernel<PRO, BAMD_EPI_STORE>),    dim3(grid), dim3(512), lds, s, a); break;
-        case BAMD_EPI_ADD:      BAMD_LAUNCH((matvec_kernel<PRO, BAMD_EPI_ADD>),      dim3(grid), dim3(512), lds, s, a); break;
-        case BAMD_EPI_SILU_MUL: BAMD_LAUNCH((matvec_kernel<PRO, BAMD_EPI_SILU_MUL>), dim3(grid), dim3(512), lds, s, a); break;
-        case BAMD_EPI_ARGMAX:   BAMD_LAUNCH((matvec_kernel<PRO, BAMD_EPI_ARGMAX>),   dim3(grid), dim3(512), lds, s, a); break;
-    }
-}
-template <int PRO>
-static void launch_mv_split(const bamd_mv_args & a, int epi, int grid, hipStream_t s) {
-    const int nb = a.K >> 8;
-    const int nbw = nb >> 3;
-    const int M = (nb & 7) ? (nbw == 2 ? 2 : 1) : nbw == 2 ? 4 : nbw == 7 ? 1 : nbw == 4 ? 2 : 8, NBUF = 2;   // must match split_dispatch
-    const size_t lds = act_lds_bytes(a.K) + 16 + (size_t) NBUF * M * nb * 256 * 4;   // 112..128 KiB of term buffers
-    if (epi == BAMD_EPI_ADD) BAMD_LAUNCH((matvec_split_kernel<PRO, BAMD_EPI_ADD>),   dim3(grid), dim3(512), lds, s, a);
-    else                     BAMD_LAUNCH((matvec_split_kernel<PRO, BAMD_EPI_STORE>), dim3(grid), dim3(512), lds, s, a);
+// the generic kernels (type and segment picked at run time inside): split-K with the term buffers of split_shape, or one wave per row-group
+static bool launch_mv_generic(const bamd_mv_args & a, int pro, int epi, bool split, int grid, hipStream_t s) {
+    const SplitShape sh = split_shape(a.K >> 8);
+    const size_t lds = split ? mv_lds_terms(a.K >> 8, sh.nbuf * sh.m) : act_lds_bytes(a.K);          // split: 112..128 KiB of term buffers
+    typedef consts<BAMD_PRO_NORM, BAMD_PRO_PLAIN> pros;
+    if (split) return with_const(pros(), pro, [&](auto P) -> bool { return with_const(consts<BAMD_EPI_ADD, BAMD_EPI_STORE>(), epi, [&](auto E) -> bool {
+        BAMD_LAUNCH((matvec_split_kernel<decltype(P)::value, decltype(E)::value>), dim3(grid), dim3(512), lds, s, a); return true; }); });
+    return with_const(pros(), pro, [&](auto P) -> bool { return with_const(consts<BAMD_EPI_STORE, BAMD_EPI_ADD, BAMD_EPI_SILU_MUL, BAMD_EPI_ARGMAX>(), epi, [&](auto E) -> bool {
+        BAMD_LAUNCH((matvec_kernel<decltype(P)::value, decltype(E)::value>), dim3(grid), dim3(512), lds, s, a); return true; }); });
 }
 
-// K / 256 a multiple of 8 with 1, 2, 4 or 7 records per wave; or uneven shares of 2-3, 5-6, 6-7 records (17..23, 41..47, 49..55 super-blocks:
-// Llama-2-13B's n_embd 5120, Llama-2-7B's n_ff 11008, Llama-2-13B's n_ff 13824).  (9..15 super-blocks — Llama-3.2-3B's n_embd 3072 — measured no
-// faster split than with one wave per row-group: 6.9 / 4.8 us against 6.2 / 5.1 for its QKV / wo.)
-static bool split_supported(int nb) { const int nbw = nb >> 3; return (nb & 7) == 0 ? (nbw == 1 || nbw == 2 || nbw == 4 || nbw == 7) : (nbw == 2 || nbw == 5 || nbw == 6); }
+static const bool g_mv_generic = env_flag("BAMD_MV_GENERIC", false);     // 1: every launch on the generic kernels (A/B comparison, tests of the fallback)
 
-static void bamd_launch_matvec_checked(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
-static const bool g_mv_generic = [] { const char * e = getenv("BAMD_MV_GENERIC"); return e && e[0] == '1'; }();
-
+// ---- SELECTION: which kernel family serves a launch.  The order of preference is here; each family's own preconditions are stated once, in its
+// bamd_launch_fast_* function (false = no instance for this shape: the next family is asked); pinned by tests/test_launch_selection.py ----
 int bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
     for (int i = 0; i < a.nseg; ++i) if (!bamd_is_kquant(a.seg[i].type)) return 1;      // never launched: the kernels' own `else` is unreachable
-    bamd_launch_matvec_checked(a, pro, epi, n_cu, s);
-    return 0;
-}
-static void bamd_launch_matvec_checked(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
     int nrg = 0;
     if (epi == BAMD_EPI_SILU_MUL) nrg = a.seg[0].nrows >> 3;
     else for (int i = 0; i < a.nseg; ++i) nrg += a.seg[i].nrows >> 3;
     const int cus = n_cu > 0 ? n_cu : 256;
+    const int grid = nrg < 1 ? 1 : nrg < cus ? nrg : cus;    // one 8-wave workgroup per CU
     // few row-groups: split K over the 8 waves of a workgroup (mode B); otherwise one wave per row-group (mode A)
-    const bool can_split = (epi == BAMD_EPI_STORE || epi == BAMD_EPI_ADD) && split_supported(a.K >> 8);
+    const bool few = nrg < 8 * cus;
+    const bool can_split = (epi == BAMD_EPI_STORE || epi == BAMD_EPI_ADD) && split_shape(a.K >> 8).m > 0;
     // differently typed segments (wq|wk Q4_K + wv Q6_K): a split-K workgroup would stream them one after the other, each with its
     // own ring fill; with one wave per row-group every wave has a single row-group of a single type
     const bool mixed = a.nseg > 1 && epi == BAMD_EPI_STORE && nrg <= 8 * cus;
-    const int fmode = a.mode & 15;
-    const bool split = fmode == 2 ? can_split : fmode == 1 ? false : (can_split && nrg < 8 * cus && !mixed);
-    int grid = cus;                                          // one 8-wave workgroup per CU
-    if (grid > nrg) grid = nrg;
-    if (grid < 1) grid = 1;
-    const bool generic = g_mv_generic || a.mode >= 16;       // mode bit 4: force the generic kernels (tests)
-    // K = 28672 (the 70B ffn_down): a fast split-K instance only (bamd_matvec_fast_b.hip); the generic split kernel has no table entry for 14 records per wave
-    if (!generic && fmode != 1 && nrg < 8 * cus && bamd_launch_fast_b112_supported(a.K, pro, epi, a.nseg, a.seg[0].type) && bamd_launch_fast_b(a, pro, epi, grid, s)) return;
-    if (!generic && mixed && fmode == 0 && can_split && bamd_launch_fast_mixed(a, pro, epi, grid, s)) return;
-    if (split) {
-        if (!generic && bamd_launch_fast_b(a, pro, epi, grid, s)) return;
-        if (pro == BAMD_PRO_NORM) launch_mv_split<BAMD_PRO_NORM>(a, epi, grid, s);
-        else                      launch_mv_split<BAMD_PRO_PLAIN>(a, epi, grid, s);
-        return;
-    }
-    if (!generic && bamd_launch_fast_a(a, pro, epi, grid, s)) return;
-    if (pro == BAMD_PRO_NORM) launch_mv_epi<BAMD_PRO_NORM>(a, epi, grid, s);
-    else                      launch_mv_epi<BAMD_PRO_PLAIN>(a, epi, grid, s);
+    const int fmode = a.mode & 15;                           // 1: force mode A, 2: force split-K (tests)
+    const bool split = fmode == 2 ? can_split : fmode == 1 ? false : (can_split && few && !mixed);
+    const bool fast = !g_mv_generic && a.mode < 16;          // mode bit 4: force the generic kernels (tests)
+    // 1. K = 28672 (the 70B ffn_down): a fast split-K instance only; the generic split kernel has no shape for 14 records per wave
+    if (fast && fmode != 1 && few && (a.K >> 8) == 112 && bamd_launch_fast_b(a, pro, epi, grid, s)) return 0;
+    // 2. the fused QKV launch with a differently typed attn_v: split-K over both segments in one pass
+    if (fast && mixed && fmode == 0 && can_split && bamd_launch_fast_mixed(a, pro, epi, grid, s)) return 0;
+    // 3. split-K, 4. one wave per row-group: the fast instance of the shape, else the generic kernel
+    if (fast && (split ? bamd_launch_fast_b(a, pro, epi, grid, s) : bamd_launch_fast_a(a, pro, epi, grid, s))) return 0;
+    return launch_mv_generic(a, pro, epi, split, grid, s) ? 0 : 1;
 }
 
 void bamd_launch_step_begin(bamd_step_state * st, const int32_t * forced, int n_forced, int32_t * out_tokens, const void * embd,

@@ -3,6 +3,7 @@
 // split-K loop.  Numerics contract and reference citations: bamd_device.h.
 #pragma once
 #include "bamd_device.h"
+#include "bamd_mv_select.h"
 
 template <int TYPE> struct RecOf;
 template <> struct RecOf<BAMD_Q4_K> { typedef RecQ4K type; };
@@ -43,11 +44,12 @@ __device__ __forceinline__ ProArgs carve_lds(const bamd_mv_args & a, unsigned ch
 // s_waitcnt vmcnt(N) waits.  The ring is filled BEFORE the activation prologue (weights do not depend on it), so
 // the first HBM round trip overlaps the RMSNorm/Q8_K work.  With PAIR each row-group is streamed twice back to
 // back — gate (wA) then up (wB) — and the epilogue fuses silu(gate)*up.
-template <int TYPE, typename REC, int D, int EPI, int PRO, bool SMALLK = false, int NBP = BAMD_ACT_BATCH>
+template <int TYPE, int D, int EPI, int PRO, bool SMALLK = false, int NBP = BAMD_ACT_BATCH>
 __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, const uint8_t * __restrict__ wB, int nb,
                                                int first, int count, int stride, float * __restrict__ out,
                                                const float * __restrict__ res, const ProArgs & pa, ActPro<PRO == BAMD_PRO_NORM> & ap,
                                                bool issue_here, bool do_pro, unsigned long long & best, int nvalid, float * half_slot = nullptr, int * half_flag = nullptr) {
+    typedef typename RecOf<TYPE>::type REC;
     constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");     // bamd_record_bytes
     constexpr bool PAIR = EPI == BAMD_EPI_SILU_MUL;
     constexpr int NPARTS = PAIR ? 2 : 1;
@@ -156,10 +158,10 @@ __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, 
 // and parks them in LDS (the split-K kernels' mechanism); waves 4-6 then replay them IN ORDER behind their own chain steps: every SIMD streams
 // 56 records, and each lane's f32 chain is still the reference's sequential chain over super-blocks 0..nb-1 (ggml-quants.c:6937-6941, :6970).
 // HELPER = wave 7; otherwise wave 4 + j of the workgroup (its pair: row-group rg0).  LDS: park[3 pairs][gate | up][nb / 4][64 lanes] float4, flags[3].
-#define BAMD_GU7_PARK_BYTES(nb) ((size_t) 3 * 2 * ((nb) / 4) * 64 * 16)
-template <int TYPE, typename REC, int NBP, bool HELPER>
+template <int TYPE, int NBP, bool HELPER>
 __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ wG, const uint8_t * __restrict__ wU, int rg0, int rg_stride, int j,
                                                   float * __restrict__ out, const ProArgs & pa, ActPro<true> & ap, float4 * park, int * flags, int nvalid) {
+    typedef typename RecOf<TYPE>::type REC;
     constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");
     constexpr int NB = 16, Q = NB / 4, CUT = NB - Q, D = 8, NREC = HELPER ? 3 * 2 * Q : 2 * CUT;      // 24 records either way
     static_assert(NREC % D == 0, "whole ring chunks");
@@ -230,8 +232,7 @@ __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ w
 // after a workgroup barrier ONE wave replays the reference's sequential f32 chain over all nb blocks in order.
 // Same arithmetic, same order, 8x the parallelism.  Term buffers are double-buffered so the chain of row-group n
 // overlaps the streaming of row-group n+1; the prefetch ring spans row-group boundaries (M row-groups per body).
-// LDS term buffers: 2 (double buffer) x M (row-groups per batch) x nb x 64 lanes x float4 {d, fs, dmin, pm}
-#define BAMD_TERM_FLOATS(nb) ((size_t) (nb) * 256)      /* one float4 {d, fs, dmin, pm} per lane per super-block */
+// LDS term buffers: 2 (double buffer) x M (row-groups per batch) x nb x 64 lanes x float4 {d, fs, dmin, pm} (bamd_mv_select.h: mv_term_floats, mv_lds_terms)
 
 // ONEB (fast kernels): every workgroup has exactly M row-groups — one batch, no refills, no loop: the waits for the ring stay counted
 // (record by record) instead of one full wait at the loop head
@@ -244,11 +245,12 @@ __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ w
 // lane, so that TWO term buffers of a whole row-group fit the LDS beside the activations (2 x 63 KB + 32 KB) and the chain of row-group n overlaps the
 // streaming of row-group n + 1 (with one buffer every batch ends in barrier + 112-step chain + barrier: measured slower than one wave per row-group, round 5)
 struct SplitNoPre { __device__ __forceinline__ void operator()() const { } };
-template <int TYPE, typename REC, int NBW, int M, int NBUF, int EPI, int PRO, bool SMALLK = false, bool ONEB = false, bool UNEVEN = false, typename PRE = SplitNoPre, bool COMPACT = false>
+template <int TYPE, int NBW, int M, int NBUF, int EPI, int PRO, bool SMALLK = false, bool ONEB = false, bool UNEVEN = false, typename PRE = SplitNoPre, bool COMPACT = false>
 __device__ __forceinline__ void split_stream(const uint8_t * __restrict__ w, int nb, int first, int count, int stride,
                                              float * __restrict__ out, const float * __restrict__ res, const ProArgs & pa,
                                              ActPro<PRO == BAMD_PRO_NORM> & ap, ActPro<PRO == BAMD_PRO_NORM> & ap2, bool issue_here, bool do_pro,
                                              float * part0, int & batchctr, int nvalid, PRE pre = PRE()) {
+    typedef typename RecOf<TYPE>::type REC;
     constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");     // bamd_record_bytes
     constexpr int D = NBW * M;                               // ring depth = one batch (M row-groups) of this wave's records
     const int lane = threadIdx.x & 63, wave = wave_id();
@@ -258,7 +260,7 @@ __device__ __forceinline__ void split_stream(const uint8_t * __restrict__ w, int
     const int rg_step = stride * rgb;
     const int n_w = UNEVEN ? (NBW - 1) + (wave < (nb & 7) ? 1 : 0) : NBW;                  // this wave's records per row-group
     const int i0 = UNEVEN ? wave * (NBW - 1) + (wave < (nb & 7) ? wave : (nb & 7)) : wave * NBW;   // its first super-block inside a row
-    const size_t rg_floats = COMPACT ? (size_t) nb * 144 : BAMD_TERM_FLOATS(nb);
+    const size_t rg_floats = mv_term_floats(nb, COMPACT);
     // PLAIN prologue: wave w consumes only the activations of its own K-slice (blocks i0 .. i0+NBW-1), so it quantises exactly
     // those — no workgroup barrier, and a wave starts on its records as soon as ITS blocks are done.  (NORM needs the sum of
     // squares of the whole vector: shared prologue as in mode A.)
@@ -411,4 +413,3 @@ __device__ __forceinline__ void split_stream(const uint8_t * __restrict__ w, int
 bool bamd_launch_fast_a(bamd_mv_args a, int pro, int epi, int grid, hipStream_t s);
 bool bamd_launch_fast_b(bamd_mv_args a, int pro, int epi, int grid, hipStream_t s);
 bool bamd_launch_fast_mixed(const bamd_mv_args & a, int pro, int epi, int grid, hipStream_t s);
-bool bamd_launch_fast_b112_supported(int K, int pro, int epi, int nseg, int type);

@@ -18,13 +18,12 @@ __global__ void __launch_bounds__(64 * NW) matvec_split_fast_kernel(BAMD_LEAD_PA
         ap.template issue<BAMD_NB1(NBW)>(pa.x, pa.nw, pa.K, i0, 1, i0 + NBW);
         if (NBW > BAMD_ACT_BATCH) ap2.template issue<BAMD_NB2(NBW)>(pa.x, pa.nw, pa.K, i0 + BAMD_ACT_BATCH, 1, i0 + NBW);
     } else BAMD_PRO_ISSUE_NB(ap, pa, BAMD_NB1(NBW));         // shared prologue: wave w takes blocks w, w + 8, ...: NBW of them
-    float * part0 = (float *) (smem + BAMD_ACT_RED_OFF(nb) + 16 * sizeof(double));
+    float * part0 = (float *) (smem + mv_terms_off(nb));
     int rgctr = 0;
     const int count = a.cnt_q + ((int) blockIdx.x < a.cnt_r ? 1 : 0);
     const int nv = a.seg[0].nvalid > 0 ? a.seg[0].nvalid : a.seg[0].nrows;
-    typedef typename RecOf<TYPE>::type REC;
-    constexpr int NBUF = COMPACT ? 2 : NBW * M > 8 ? 1 : 2;  // term buffers: 2 x M x K/256 KiB must fit the LDS
-    split_stream<TYPE, REC, NBW, M, NBUF, EPI, PRO, true, ONEB, false, SplitNoPre, COMPACT>((const uint8_t *) a.seg[0].w, nb, (int) blockIdx.x, count, (int) gridDim.x, a.seg[0].out, a.res, pa,
+    constexpr int NBUF = split_fast_nbuf(NBW, M, COMPACT);
+    split_stream<TYPE, NBW, M, NBUF, EPI, PRO, true, ONEB, false, SplitNoPre, COMPACT>((const uint8_t *) a.seg[0].w, nb, (int) blockIdx.x, count, (int) gridDim.x, a.seg[0].out, a.res, pa,
                                                        ap, ap2, false, true, part0, rgctr, nv, SplitNoPre());      // the launcher's grid gives every workgroup >= 1 row-group
     TL_STAMP(a.tl, 7);
 }
@@ -73,7 +72,7 @@ __device__ __forceinline__ void split_mixed_body(const bamd_mv_args & a, const P
     BAMD_PRO_FINISH_NB_MID(ap, pa, last_ring, BAMD_NB1(NBW));
     TL_STAMP(pa.tl, 2);
     const uint32_t * q8 = pa.q8; const int * S = pa.S; const float * yd = pa.yd;
-    const size_t rg_floats = COMPACT ? (size_t) nb * 144 : BAMD_TERM_FLOATS(nb);         // floats per parked row-group (compact: 576 bytes per record)
+    const size_t rg_floats = mv_term_floats(nb, COMPACT);         // floats per parked row-group
     auto park = [&](float * base, int ci, const Terms & T) {
         if (COMPACT) {
             float * rec = base + (size_t) ci * 144;
@@ -151,22 +150,28 @@ __global__ void __launch_bounds__(64 * NW) matvec_split_mixed_kernel(BAMD_LEAD_P
     const ProArgs pa = carve_lds(a, smem);
     ActPro<true> ap;
     BAMD_PRO_ISSUE_NB(ap, pa, BAMD_NB1(NBW));
-    float * part0 = (float *) (smem + BAMD_ACT_RED_OFF(nb) + 16 * sizeof(double));
+    float * part0 = (float *) (smem + mv_terms_off(nb));
     const int g_last = MA * (int) gridDim.x + (int) blockIdx.x;       // index of this workgroup's last row-group in the concatenated segments
     if (g_last < (a.seg[0].nrows >> 3)) split_mixed_body<TA, TA, NBW, MA, COMPACT>(a, pa, ap, part0, g_last);
     else                                split_mixed_body<TA, TB, NBW, MA, COMPACT>(a, pa, ap, part0, g_last);
     TL_STAMP(a.tl, 7);
 }
+// every instance's K is fixed by its shape (NW waves x NBW records), and so is its LDS
 template <int TA, int TB, int NBW, int MA, bool COMPACT = false, int NW = 8>
 static void launch_mixed_inst(const bamd_mv_args & a, int grid, hipStream_t s) {
-    const int nb = a.K >> 8;
-    const size_t lds = act_lds_bytes(a.K) + 16 + (size_t) (MA + 1) * nb * (COMPACT ? 576 : 1024);
+    constexpr size_t lds = mv_lds_terms(NW * NBW, MA + 1, COMPACT);
+    static_assert(lds <= BAMD_LDS_CU_BYTES, "the workgroup does not fit the LDS of a CU");
     BAMD_LAUNCH((matvec_split_mixed_kernel<TA, TB, NBW, MA, COMPACT, NW>), dim3(grid), dim3(64 * NW), lds, s, BAMD_LEAD_ARGS(a), a);
 }
+static const bool g_mixed_split = env_flag("BAMD_MIXED_SPLIT", true);
+static const int g_qkv70_waves = env_int("BAMD_QKV70_WAVES", 0);
+// the (wq | wk, wv) type pairs with an instance: the Q4_K / Q5_K recipes' Q6_K or Q5_K attn_v, and the Q3_K_M and Q2_K recipes' q | k + v
+typedef pairs<cpair<BAMD_Q4_K, BAMD_Q6_K>, cpair<BAMD_Q4_K, BAMD_Q5_K>, cpair<BAMD_Q5_K, BAMD_Q6_K>, cpair<BAMD_Q3_K, BAMD_Q4_K>, cpair<BAMD_Q3_K, BAMD_Q5_K>,
+              cpair<BAMD_Q2_K, BAMD_Q4_K>, cpair<BAMD_Q2_K, BAMD_Q3_K>> mixed_pairs;
+typedef pairs<cpair<BAMD_Q4_K, BAMD_Q6_K>, cpair<BAMD_Q4_K, BAMD_Q5_K>> mixed70_pairs;
 // fused QKV launch with two differently typed segments; false: shape not covered (mode A takes it)
 bool bamd_launch_fast_mixed(const bamd_mv_args & a, int pro, int epi, int grid, hipStream_t s) {
-    static const bool on = [] { const char * e = getenv("BAMD_MIXED_SPLIT"); return !(e && e[0] == '0'); }();
-    if (!on || pro != BAMD_PRO_NORM || epi != BAMD_EPI_STORE || a.nseg != 2) return false;
+    if (!g_mixed_split || pro != BAMD_PRO_NORM || epi != BAMD_EPI_STORE || a.nseg != 2) return false;
     const int nb = a.K >> 8, t0 = a.seg[0].type, t1 = a.seg[1].type;
     const int nrg0 = a.seg[0].nrows >> 3, nrg1 = a.seg[1].nrows >> 3;
     if ((nb & 7) != 0 || nb > 8 * BAMD_ACT_BATCH || t0 == t1 || grid < 1 || (nrg0 + nrg1) % grid) return false;
@@ -176,96 +181,72 @@ bool bamd_launch_fast_mixed(const bamd_mv_args & a, int pro, int epi, int grid, 
         // split-K instance on eight waves (20 records per wave in registers) 1.275, on sixteen waves (10 records, 128 VGPRs) 1.293 — the prologue, the
         // terms of a wave's records and a 32-step chain per workgroup cost more than five of eight waves streaming 32 records each.  BAMD_QKV70_WAVES=8 / 16
         // selects it for the record (tests/test_gpu_fullsize_ref.py::test_config4_70b_stage runs bit-exact through either).
-        static const int nw70 = [] { const char * e = getenv("BAMD_QKV70_WAVES"); return e ? atoi(e) : 0; }();
-        if (nw70 != 8 && nw70 != 16) return false;
-#define BAMD_MX70(TA_, TB_) if (t0 == TA_ && t1 == TB_) { if (nw70 == 16) launch_mixed_inst<TA_, TB_, 2, 4, true, 16>(a, grid, s); else launch_mixed_inst<TA_, TB_, 4, 4, true>(a, grid, s); return true; }
-        BAMD_MX70(BAMD_Q4_K, BAMD_Q6_K) BAMD_MX70(BAMD_Q4_K, BAMD_Q5_K)
-#undef BAMD_MX70
-        return false;
+        if (g_qkv70_waves != 8 && g_qkv70_waves != 16) return false;
+        return with_pair(mixed70_pairs(), t0, t1, [&](auto P) -> bool {
+            if (g_qkv70_waves == 16) launch_mixed_inst<decltype(P)::a, decltype(P)::b, 2, 4, true, 16>(a, grid, s);
+            else                     launch_mixed_inst<decltype(P)::a, decltype(P)::b, 4, 4, true>(a, grid, s);
+            return true; });
     }
     if (cnt != 3 || nrg0 < 2 * grid || nbw != 2) return false;                  // the Llama-3-8B / Mistral-7B shape: K = 4096, three row-groups per workgroup
-#define BAMD_MX(TA_, TB_) if (t0 == TA_ && t1 == TB_) { launch_mixed_inst<TA_, TB_, 2, 2>(a, grid, s); return true; }
-    BAMD_MX(BAMD_Q4_K, BAMD_Q6_K) BAMD_MX(BAMD_Q4_K, BAMD_Q5_K) BAMD_MX(BAMD_Q5_K, BAMD_Q6_K)
-    BAMD_MX(BAMD_Q3_K, BAMD_Q4_K) BAMD_MX(BAMD_Q3_K, BAMD_Q5_K) BAMD_MX(BAMD_Q2_K, BAMD_Q4_K) BAMD_MX(BAMD_Q2_K, BAMD_Q3_K)      // the Q3_K_M and Q2_K recipes' q | k + v
-#undef BAMD_MX
-    return false;
+    return with_pair(mixed_pairs(), t0, t1, [&](auto P) -> bool { launch_mixed_inst<decltype(P)::a, decltype(P)::b, 2, 2>(a, grid, s); return true; });
 }
 
 template <int PRO, int EPI, int T, int NBW, int M, bool ONEB = false, int NW = 8, bool COMPACT = false>
 static void launch_fast_b_inst(const bamd_mv_args & a, int grid, hipStream_t s) {
-    const int nb = a.K >> 8;
-    const size_t lds = act_lds_bytes(a.K) + 16 + (COMPACT ? (size_t) 2 * M * nb * 576 : (size_t) (NBW * M > 8 ? 1 : 2) * M * nb * 256 * 4);
+    constexpr size_t lds = mv_lds_terms(NW * NBW, split_fast_nbuf(NBW, M, COMPACT) * M, COMPACT);
+    static_assert(lds <= BAMD_LDS_CU_BYTES, "the workgroup does not fit the LDS of a CU");
     BAMD_LAUNCH((matvec_split_fast_kernel<T, NBW, M, PRO, EPI, ONEB, NW, COMPACT>), dim3(grid), dim3(64 * NW), lds, s, BAMD_LEAD_ARGS(a), a);
 }
-static const bool g_down14 = [] { const char * e = getenv("BAMD_DOWN14"); return !(e && e[0] == '0'); }();
-static const bool g_down112 = [] { const char * e = getenv("BAMD_DOWN112"); return !(e && e[0] == '0'); }();
-// K = 28672 (112 super-blocks: the Llama-3-70B ffn_down) as split-K over SIXTEEN waves x seven records, one row-group per batch, two COMPACT term buffers.
-// With one wave per row-group (mode A) this launch is bound by its prologue — every workgroup quantises all 112 blocks behind shared barriers: 22 us of the
-// 30 (tools/mvbench.py 70b, `prologue-only K28672`) — and only four waves per CU have a row-group; here a wave quantises the seven blocks of its own K-slice.
-bool bamd_launch_fast_b112_supported(int K, int pro, int epi, int nseg, int type) {
-    return g_down112 && (K >> 8) == 112 && pro == BAMD_PRO_PLAIN && (epi == BAMD_EPI_STORE || epi == BAMD_EPI_ADD) && nseg == 1 &&
-           (type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K);
-}
+static const bool g_down14 = env_flag("BAMD_DOWN14", true);
+static const bool g_down112 = env_flag("BAMD_DOWN112", true);
+static const bool g_wo4 = env_flag("BAMD_WO4", true);
+static const bool g_qkv3 = env_flag("BAMD_QKV3", true);
+// the (records per wave, row-groups per batch) shapes of the eight-wave kernel family; K = 14336 (7, 1) behind a plain prologue only
+typedef pairs<cpair<1, 8>, cpair<1, 4>, cpair<1, 2>, cpair<1, 1>, cpair<2, 4>, cpair<2, 2>, cpair<2, 1>, cpair<4, 2>, cpair<4, 1>> fast_b_shapes;
+// ... of its single-batch instances: exactly M row-groups in every workgroup (residual-add launches: wo, ffn_down)
+typedef pairs<cpair<2, 2>, cpair<2, 4>, cpair<4, 2>, cpair<4, 4>, cpair<1, 8>> fast_b_one_batch_shapes;
 template <int PRO, int EPI>
 static bool launch_fast_b_types(const bamd_mv_args & a, int t, int nbw, int grid, hipStream_t s) {
+    // K = 28672 (112 super-blocks: the Llama-3-70B ffn_down) as split-K over SIXTEEN waves x seven records, one row-group per batch, two COMPACT term buffers.
+    // With one wave per row-group (mode A) this launch is bound by its prologue — every workgroup quantises all 112 blocks behind shared barriers: 22 us of the
+    // 30 (tools/mvbench.py 70b, `prologue-only K28672`) — and only four waves per CU have a row-group; here a wave quantises the seven blocks of its own K-slice.
+    // No other kernel family has this K: bamd_launch_matvec asks for it ahead of its own split / no-split decision
+    if constexpr (PRO == BAMD_PRO_PLAIN) if ((a.K >> 8) == 112)
+        return g_down112 && a.cnt_q >= 1 && with_const(kquants_456(), t, [&](auto T) -> bool { launch_fast_b_inst<PRO, EPI, decltype(T)::value, 7, 1, false, 16, true>(a, grid, s); return true; });
+    if (g_down14 && PRO == BAMD_PRO_PLAIN && (a.K >> 8) == 56 && a.cnt_q >= 1 &&                // K = 14336 on fourteen waves, four records each (one row-group per batch: 128 VGPRs)
+        with_kquant(t, [&](auto T) -> bool { launch_fast_b_inst<PRO, EPI, decltype(T)::value, 4, 1, false, 14>(a, grid, s); return true; })) return true;
     // row-groups per batch: the largest M of the kernel family that every workgroup can fill (cnt_q = the smallest count)
     // (K = 14336 with both row-groups of a workgroup in flight — M = 2, 14 records per wave — measured no faster, again: the wave that
     // issues 130 KB of requests up front sits in the issue stage until most of them have landed, and its prologue starts that much later)
-    if constexpr (PRO == BAMD_PRO_PLAIN) if ((a.K >> 8) == 112) {                               // bamd_launch_fast_b112_supported
-        if (a.cnt_q < 1) return false;
-#define BAMD_B112(T_) if (t == T_) { launch_fast_b_inst<PRO, EPI, T_, 7, 1, false, 16, true>(a, grid, s); return true; }
-        BAMD_B112(BAMD_Q4_K) BAMD_B112(BAMD_Q5_K) BAMD_B112(BAMD_Q6_K)
-#undef BAMD_B112
-        return false;
-    }
-    if (g_down14 && PRO == BAMD_PRO_PLAIN && (a.K >> 8) == 56 && a.cnt_q >= 1) {                // K = 14336 on fourteen waves, four records each (one row-group per batch: 128 VGPRs)
-#define BAMD_B14(T_) if (t == T_) { launch_fast_b_inst<PRO, EPI, T_, 4, 1, false, 14>(a, grid, s); return true; }
-        BAMD_B14(BAMD_Q4_K) BAMD_B14(BAMD_Q5_K) BAMD_B14(BAMD_Q6_K) BAMD_B14(BAMD_Q3_K) BAMD_B14(BAMD_Q2_K)
-#undef BAMD_B14
-    }
     const int mmax = nbw == 1 ? 8 : nbw == 2 ? 4 : nbw == 4 ? 2 : 1;
     int m = 1; while (m * 2 <= mmax && m * 2 <= a.cnt_q) m *= 2;
     // K = 8192 with exactly FOUR row-groups per workgroup behind a plain prologue and a residual add (the 70B wo): all four in one batch — sixteen records per wave
     // requested at entry, one barrier, four chains side by side, one 128-KB term buffer — instead of two batches of two
-    static const bool wo4 = [] { const char * e = getenv("BAMD_WO4"); return !(e && e[0] == '0'); }();
-    if (wo4 && PRO == BAMD_PRO_PLAIN && EPI == BAMD_EPI_ADD && nbw == 4 && a.cnt_q == 4 && a.cnt_r == 0) m = 4;
-    // exactly M row-groups in every workgroup: the single-batch instances (residual-add launches: wo, ffn_down)
-    const bool oneb = a.cnt_r == 0 && a.cnt_q == m;
-#define BAMD_B_ONE(T_, NBW_, M_) if (PRO == BAMD_PRO_PLAIN && EPI == BAMD_EPI_ADD && oneb && t == T_ && nbw == NBW_ && m == M_) { launch_fast_b_inst<PRO, EPI, T_, NBW_, M_, true>(a, grid, s); return true; }
-#define BAMD_B_ONES(NBW_, M_) BAMD_B_ONE(BAMD_Q4_K, NBW_, M_) BAMD_B_ONE(BAMD_Q5_K, NBW_, M_) BAMD_B_ONE(BAMD_Q6_K, NBW_, M_)
-    BAMD_B_ONES(2, 2) BAMD_B_ONES(2, 4) BAMD_B_ONES(4, 2) BAMD_B_ONES(4, 4) BAMD_B_ONES(1, 8)
-    BAMD_B_ONE(BAMD_Q3_K, 2, 2) BAMD_B_ONE(BAMD_Q2_K, 2, 2)          // wo at K = 4096, two row-groups per workgroup (the Q2_K recipe's wo is Q3_K); every other Q2_K / Q3_K split-K shape: generic kernel
-#undef BAMD_B_ONES
-#undef BAMD_B_ONE
-#define BAMD_B_CASE(T_, NBW_, M_) if (t == T_ && nbw == NBW_ && m == M_) { launch_fast_b_inst<PRO, EPI, T_, NBW_, M_>(a, grid, s); return true; }
-#define BAMD_B_TYPES(NBW_, M_) BAMD_B_CASE(BAMD_Q4_K, NBW_, M_) BAMD_B_CASE(BAMD_Q5_K, NBW_, M_) BAMD_B_CASE(BAMD_Q6_K, NBW_, M_)
-    BAMD_B_TYPES(1, 8) BAMD_B_TYPES(1, 4) BAMD_B_TYPES(1, 2) BAMD_B_TYPES(1, 1)
-    BAMD_B_TYPES(2, 4) BAMD_B_TYPES(2, 2) BAMD_B_TYPES(2, 1)
-    BAMD_B_TYPES(4, 2) BAMD_B_TYPES(4, 1)
-    if (PRO == BAMD_PRO_PLAIN) { BAMD_B_TYPES(7, 1) }
-#undef BAMD_B_TYPES
-#undef BAMD_B_CASE
+    if (g_wo4 && PRO == BAMD_PRO_PLAIN && EPI == BAMD_EPI_ADD && nbw == 4 && a.cnt_q == 4 && a.cnt_r == 0) m = 4;
+    if (PRO == BAMD_PRO_PLAIN && EPI == BAMD_EPI_ADD && a.cnt_r == 0 && a.cnt_q == m) {         // single batch
+        if (with_pair(fast_b_one_batch_shapes(), nbw, m, [&](auto S) -> bool {
+                return with_const(kquants_456(), t, [&](auto T) -> bool { launch_fast_b_inst<PRO, EPI, decltype(T)::value, decltype(S)::a, decltype(S)::b, true>(a, grid, s); return true; }); })) return true;
+        // wo at K = 4096, two row-groups per workgroup (the Q2_K recipe's wo is Q3_K); every other Q2_K / Q3_K split-K shape: generic kernel
+        if (nbw == 2 && m == 2 && with_const(consts<BAMD_Q3_K, BAMD_Q2_K>(), t, [&](auto T) -> bool { launch_fast_b_inst<PRO, EPI, decltype(T)::value, 2, 2, true>(a, grid, s); return true; })) return true;
+    }
+    auto batched = [&](auto S) -> bool {
+        return with_const(kquants_456(), t, [&](auto T) -> bool { launch_fast_b_inst<PRO, EPI, decltype(T)::value, decltype(S)::a, decltype(S)::b>(a, grid, s); return true; }); };
+    if (with_pair(fast_b_shapes(), nbw, m, batched)) return true;
+    if (PRO == BAMD_PRO_PLAIN && with_pair(pairs<cpair<7, 1>>(), nbw, m, batched)) return true;
     return false;
 }
-static const bool g_qkv3 = [] { const char * e = getenv("BAMD_QKV3"); return !(e && e[0] == '0'); }();
+// split-K over one segment: K / 256 a multiple of 8, every workgroup at least one row-group (the launcher's grid)
 bool bamd_launch_fast_b(bamd_mv_args a, int pro, int epi, int grid, hipStream_t s) {
     const int nb = a.K >> 8;
     if ((nb & 7) != 0 || a.nseg != 1) return false;
-    const int nrg = a.seg[0].nrows >> 3;
-    a.cnt_q = nrg / grid; a.cnt_r = nrg % grid;
+    mv_set_counts(a, a.seg[0].nrows >> 3, grid);
     const int t = a.seg[0].type, nbw = nb >> 3;
     // exactly THREE row-groups per workgroup at K = 4096 behind an RMSNorm prologue (the fused QKV launch of a layer whose wq | wk | wv are of one type, 8B / Mistral
     // widths): all three in ONE batch — six records per wave requested at entry, one barrier, three chains side by side — on the body of the mixed-type kernel with
     // both types equal, instead of two batches of two and one row-groups
-    if (g_qkv3 && pro == BAMD_PRO_NORM && epi == BAMD_EPI_STORE && nbw == 2 && a.cnt_q == 3 && a.cnt_r == 0 && (a.mode & 15) == 0) {
-#define BAMD_Q3(T_) if (t == T_) { launch_mixed_inst<T_, T_, 2, 2>(a, grid, s); return true; }
-        BAMD_Q3(BAMD_Q4_K) BAMD_Q3(BAMD_Q5_K) BAMD_Q3(BAMD_Q6_K)
-#undef BAMD_Q3
-    }
-    if (pro == BAMD_PRO_NORM) { if (epi == BAMD_EPI_STORE && nb <= 8 * BAMD_ACT_BATCH) return launch_fast_b_types<BAMD_PRO_NORM, BAMD_EPI_STORE>(a, t, nbw, grid, s); return false; }
-    if (epi == BAMD_EPI_STORE) return launch_fast_b_types<BAMD_PRO_PLAIN, BAMD_EPI_STORE>(a, t, nbw, grid, s);
-    if (epi == BAMD_EPI_ADD)   return launch_fast_b_types<BAMD_PRO_PLAIN, BAMD_EPI_ADD>(a, t, nbw, grid, s);
-    return false;
+    if (g_qkv3 && pro == BAMD_PRO_NORM && epi == BAMD_EPI_STORE && nbw == 2 && a.cnt_q == 3 && a.cnt_r == 0 && (a.mode & 15) == 0 &&
+        with_const(kquants_456(), t, [&](auto T) -> bool { launch_mixed_inst<decltype(T)::value, decltype(T)::value, 2, 2>(a, grid, s); return true; })) return true;
+    if (pro == BAMD_PRO_NORM && nb > 8 * BAMD_ACT_BATCH) return false;                       // shared prologue: K <= 8192
+    typedef pairs<cpair<BAMD_PRO_NORM, BAMD_EPI_STORE>, cpair<BAMD_PRO_PLAIN, BAMD_EPI_STORE>, cpair<BAMD_PRO_PLAIN, BAMD_EPI_ADD>> pro_epi;
+    return with_pair(pro_epi(), pro, epi, [&](auto PE) -> bool { return launch_fast_b_types<decltype(PE)::a, decltype(PE)::b>(a, t, nbw, grid, s); });
 }
-
-// BAMD_MV_GENERIC=1: every launch on the generic kernels (A/B comparison, tests of the fallback)

@@ -1,6 +1,7 @@
 // bamd_ops.cpp — op-level entry points (host in / host out) and the mat-vec micro-benchmark of libbooster_amd.so: thin wrappers that run the SAME kernels as the
 // model runtime (bamd_engine.cpp) on device 0.  They are what the tests and tools call; nothing here touches bamd_model / bamd_context.
 #include "../../include/bamd.h"
+#include "bamd_aql.h"
 #include "bamd_engine_internal.h"
 #include "bamd_formats.h"
 #include "bamd_kernels.h"
@@ -428,6 +429,65 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention_wo(const
     HIPC(hipMemcpy(gran_out, gran, (size_t) K * 8, hipMemcpyDeviceToHost));
     HIPC(hipMemcpy(gave_up, err, 4, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---- launch-selection trace: which kernel, grid, LDS and arguments the launchers choose for a shape, from the recording path of BAMD_LAUNCH (host code only) ----
+template <typename T> static T * fake_ptr(int field) { return (T *) (uintptr_t) (0x10000u * (unsigned) (field + 1)); }      // distinct per field, never dereferenced
+static int trace_result(const bamd_aql_recording & rec, bamd_launch_trace * out) {
+    if (rec.launches.size() != 1) return fail("launch trace: " + std::to_string(rec.launches.size()) + " launches recorded, expected one"), 2;
+    const bamd_aql_launch & l = rec.launches[0];
+    const char * name = hipKernelNameRefByPtr(l.host_fn, nullptr);
+    if (!name || strlen(name) >= sizeof out->kernel) return fail("launch trace: kernel name not resolved"), 2;
+    memset(out, 0, sizeof *out);
+    strcpy(out->kernel, name);
+    for (int i = 0; i < 3; ++i) { out->grid[i] = l.grid[i]; out->block[i] = l.block[i]; }
+    out->lds_bytes = l.lds_bytes; out->kernarg_bytes = (uint32_t) l.kernarg.size();
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (uint8_t b : l.kernarg) h = (h ^ b) * 0x100000001b3ull;
+    out->kernarg_hash = h;
+    return 0;
+}
+struct TraceScope {                      // BAMD_LAUNCH records into `rec` while this lives
+    bamd_aql_recording rec; bamd_aql_recording * prev;
+    TraceScope() : prev(bamd_aql_rec) { bamd_aql_rec = &rec; }
+    ~TraceScope() { bamd_aql_rec = prev; }
+};
+extern "C" __attribute__((visibility("default"))) int bamd_trace_matvec(int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu,
+                                                                          bamd_launch_trace * out) {
+    if (nseg < 1 || nseg > 3 || k <= 0 || k % 256 || !out) return fail("launch trace: bad segment count / row length"), 2;
+    if ((pro != BAMD_PRO_PLAIN && pro != BAMD_PRO_NORM) || epi < BAMD_EPI_STORE || epi > BAMD_EPI_ARGMAX) return fail("launch trace: bad prologue / epilogue"), 2;
+    bamd_mv_args a; memset(&a, 0, sizeof a);
+    float * y = fake_ptr<float>(8);
+    int off = 0;
+    for (int i = 0; i < nseg; ++i) {                                          // seg_of / qkv_segments; gate and up write the same output
+        if (rows[i] <= 0) return fail("launch trace: bad segment rows"), 2;
+        a.seg[i].w = fake_ptr<uint8_t>(i); a.seg[i].out = epi == BAMD_EPI_SILU_MUL ? y : y + off; a.seg[i].type = types[i];
+        a.seg[i].nrows = (rows[i] + 7) / 8 * 8; a.seg[i].nvalid = rows[i];
+        off += rows[i];
+    }
+    a.nseg = nseg; a.x = fake_ptr<float>(3); a.K = k; a.mode = mode;
+    if (pro == BAMD_PRO_NORM) { a.normw = fake_ptr<float>(4); a.eps = 1e-5f; }
+    if (epi == BAMD_EPI_ADD) a.res = fake_ptr<float>(5);
+    if (epi == BAMD_EPI_ARGMAX) a.best_key = fake_ptr<unsigned long long>(6);
+    TraceScope ts;
+    if (bamd_launch_matvec(a, pro, epi, n_cu, nullptr)) return 1;
+    return trace_result(ts.rec, out);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_trace_attn_wo(int H, int Hkv, int hd, int n_ctx, int lds_ld, int with_cellpos, int wo_type, int wo_rows, int k,
+                                                                           int n_cu, int il, bamd_launch_trace * out) {
+    if (H <= 0 || Hkv <= 0 || H % Hkv || hd <= 0 || n_ctx <= 0 || wo_rows <= 0 || k <= 0 || k % 256 || !out) return fail("launch trace: bad attention / wo shape"), 2;
+    bamd_attn_args t; memset(&t, 0, sizeof t);                               // enqueue_layers, 2.
+    t.st = fake_ptr<bamd_step_state>(16); t.q = fake_ptr<float>(17); t.k = fake_ptr<float>(18); t.v = fake_ptr<float>(19);
+    t.kc = fake_ptr<unsigned short>(20); t.vc = fake_ptr<unsigned short>(21); t.rope = fake_ptr<float>(22); t.rope_cur = fake_ptr<float>(23);
+    t.scores = fake_ptr<float>(24); t.out = fake_ptr<float>(25);
+    t.hd = hd; t.Hkv = Hkv; t.n_ctx = n_ctx; t.kq_scale = 1.0f / sqrtf((float) hd); t.lds_ld = lds_ld;
+    if (with_cellpos) t.cellpos = fake_ptr<int32_t>(26);
+    bamd_mv_args a; memset(&a, 0, sizeof a);                                 // enqueue_layers, 3.
+    a.seg[0].w = fake_ptr<uint8_t>(0); a.seg[0].out = fake_ptr<float>(8); a.seg[0].type = wo_type; a.seg[0].nrows = (wo_rows + 7) / 8 * 8; a.seg[0].nvalid = wo_rows;
+    a.nseg = 1; a.x = t.out; a.K = k; a.res = fake_ptr<float>(5);
+    TraceScope ts;
+    if (bamd_launch_attn_wo(t, H / Hkv, a, n_cu, fake_ptr<unsigned long long>(27), il, fake_ptr<uint32_t>(28), nullptr)) return 1;
+    return trace_result(ts.rec, out);
 }
 
 // ---- micro-benchmark of one mat-vec launch shape (random resident weights; HIP-event timing of `iters` launches) ----

@@ -258,6 +258,25 @@ int bamd_op_attention_wo(const float * q, const float * k, const float * v, uint
                          int il, int with_cellpos, const uint64_t * gran_init, float * x2, uint64_t * gran_out, uint32_t * gave_up, int32_t * declined,
                          int32_t * n_cu_used);
 
+/* ---- launch-selection trace (host only: needs no device) ----
+ * What the mat-vec launchers would launch for a shape, taken from their own recording path (the one the own-queue replay uses): nothing runs, no pointer is
+ * dereferenced.  The argument blocks are filled as the engine's decode step fills them (rows padded to 8 per segment, nvalid = the real rows), with fixed
+ * made-up addresses, so the hash of the packed kernel arguments pins every field a launcher sets (the row-group counts, the leading arguments, ...).
+ * Return: 0 = one launch, described in *out; 1 = refused (a type without a kernel) / declined (no co-launch for the shape): nothing recorded; 2 = error */
+typedef struct bamd_launch_trace {
+    char kernel[1024];               /* mangled name of the kernel */
+    uint32_t grid[3], block[3];
+    uint32_t lds_bytes;              /* dynamic LDS */
+    uint32_t kernarg_bytes;
+    uint64_t kernarg_hash;           /* FNV-1a 64 of the packed explicit arguments */
+} bamd_launch_trace;
+/* bamd_launch_matvec: nseg (1..3) segments of types[i] / rows[i]; pro 0 plain, 1 RMSNorm; epi 0 store, 1 residual add, 2 silu(gate) * up (two segments, one
+ * output), 3 arg-max; mode as bamd_op_fused_qkv */
+int bamd_trace_matvec(int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu, bamd_launch_trace * out);
+/* bamd_launch_attn_wo: the attention block of a decode layer (n_ctx: padded; with_cellpos != 0: a cell-position table is set) and the wo launch behind it
+ * (one segment [wo_rows][k], residual add, mode 0) */
+int bamd_trace_attn_wo(int H, int Hkv, int hd, int n_ctx, int lds_ld, int with_cellpos, int wo_type, int wo_rows, int k, int n_cu, int il, bamd_launch_trace * out);
+
 #ifdef __cplusplus
 }
 #endif
