@@ -57,6 +57,9 @@ def lib():
         L.bamd_profile_step.argtypes = [vp, ci, vp, vp, vp]; L.bamd_profile_step_kinds.argtypes = [vp, ci, vp, vp, vp]
         L.bamd_timeline_step.argtypes = [vp, ci, ci, vp, ci, C.POINTER(ci)]
         L.bamd_set_prefill_batch.argtypes = [ci]; L.bamd_set_prefill_batch.restype = None
+        L.bamd_set_prefill_lowbit.argtypes = [ci]; L.bamd_set_prefill_lowbit.restype = None
+        L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong
+        L.bamd_model_prefill_aux_bytes.argtypes = [vp]; L.bamd_model_prefill_aux_bytes.restype = i64
         L.bamd_bench_matvec.argtypes = [ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)]
         L.bamd_op_quantize_q8_K.argtypes = [vp, i64, vp, cf, vp]
         L.bamd_op_mul_mat_vec.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, vp, ci]
@@ -94,6 +97,17 @@ def set_prefill_batch(on):
     lib().bamd_set_prefill_batch(int(on))      # 2: batched without the MFMA kernel
 
 
+def set_prefill_lowbit(on):
+    """True: models loaded from now on build side tables for their Q3_K / Q2_K matrices and evaluate prompts on the matrix-core kernels; False (default, also
+    env BAMD_PREFILL_LOWBIT): a model that holds such a matrix evaluates prompts on the integer-dot kernel.  Same bits either way."""
+    lib().bamd_set_prefill_lowbit(int(bool(on)))
+
+
+def prefill_mfma_runs(t):
+    """matrix-core prompt mat-mul launches of weight type t (GGUF type id) since the library was loaded"""
+    return int(lib().bamd_prefill_mfma_runs(int(t)))
+
+
 def set_aql(on):
     """True (default): Context.generate_greedy replays the step as AQL packets with fence scope NONE on the library's own HSA queue (csrc/bamd_aql.h) where it
     can; False: one hipGraph per step on the context's HIP stream.  Same kernels, same bits.  Takes effect at the next generate_greedy call."""
@@ -125,6 +139,10 @@ class Model:
         if lib().bamd_model_tensor_raw(self.h, name.encode(), _p(out), n) != n:
             raise BamdError("bamd_model_tensor_raw: size changed")
         return out
+
+    def prefill_aux_bytes(self):
+        """bytes of the prompt mat-muls' side tables this model built at load; 0: none, its prompts run on the integer-dot kernel"""
+        return int(lib().bamd_model_prefill_aux_bytes(self.h))
 
     def close(self):
         if self.h:

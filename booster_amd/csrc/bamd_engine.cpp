@@ -34,6 +34,7 @@ static int g_prefill_mfma = [] { const char * e = getenv("BAMD_PREFILL_MFMA"); r
 // The matrix-core kernels need a side table per matrix (bamd_prefill2.hip): built at MODEL LOAD, all matrices or none, against an explicit memory budget — after the
 // weights are resident the tables (+ 78 % of the Q4_K / Q5_K bytes, + 63 % of the Q6_K bytes) must leave BAMD_PREFILL_AUX_RESERVE_GB (default 8) GiB of the device free,
 // else the model runs its prompts on the integer-dot kernel (token by token where that has no instance).  BAMD_PREFILL_AUX=0 skips them (decode-only deployments).
+// Q3_K / Q2_K matrices have tables and kernels only with the switch bamd_prefill_lowbit() on (bamd_kernels.h: bamd_prefill_mfma_type, the one list): a model takes its value at load.
 static const int g_prefill_aux = [] { const char * e = getenv("BAMD_PREFILL_AUX"); return (e && e[0] == '0') ? 0 : 1; }();
 // BAMD_STAGE_GRAPH=0: bamd_stage_step enqueues its kernels one by one instead of replaying a captured hipGraph
 static const int g_stage_graph = [] { const char * e = getenv("BAMD_STAGE_GRAPH"); return (e && e[0] == '0') ? 0 : 1; }();
@@ -360,6 +361,7 @@ extern "C" __attribute__((visibility("default"))) void bamd_model_free(bamd_mode
     delete m;
 }
 extern "C" __attribute__((visibility("default"))) int bamd_model_n_vocab(const bamd_model * m) { return m->V; }
+extern "C" __attribute__((visibility("default"))) int64_t bamd_model_prefill_aux_bytes(const bamd_model * m) { return m->aux_ok ? m->aux_bytes : 0; }
 extern "C" __attribute__((visibility("default"))) int bamd_model_n_embd(const bamd_model * m) { return m->E; }
 extern "C" __attribute__((visibility("default"))) int bamd_model_n_layer(const bamd_model * m) { return m->L; }
 extern "C" __attribute__((visibility("default"))) int bamd_model_n_ctx_train(const bamd_model * m) { return m->n_ctx_train; }
@@ -780,7 +782,7 @@ static bool prefill_batch_supported(const bamd_context * c, int pos_hi) {
     if (!(g_prefill_batch && g_attn_fused && (size_t) attn_lds_ld(c, pos_hi) * 8 <= 144 * 1024 && m->hd <= 256 && (m->hd & 63) == 0 && gq >= 1 && gq <= 8)) return false;
     // every mat-mul needs a kernel: the matrix-core kernels take every K-quant at any K when the model has its side tables; the integer-dot kernel
     // takes any K-quant while 4 tokens of Q8_K activations fit the LDS (K <= 35840; tiles of 8 tokens up to K = 17920)
-    auto ok = [&](int type, int K) { return (g_prefill_mfma && m->aux_ok && (type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K)) || 4 * bamd_blob_bytes(K) <= 160 * 1024; };
+    auto ok = [&](int type, int K) { return (g_prefill_mfma && m->aux_ok && bamd_prefill_mfma_type(type)) || 4 * bamd_blob_bytes(K) <= 160 * 1024; };
     for (const DevLayer & ly : m->layers)
         if (!ok(ly.wq.type, m->E) || !ok(ly.wk.type, m->E) || !ok(ly.wv.type, m->E) || !ok(ly.wo.type, m->E) || !ok(ly.wg.type, m->E) || !ok(ly.wu.type, m->E) || !ok(ly.wd.type, m->F)) return false;
     return true;
@@ -804,7 +806,7 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     }
     size_t need = 0;
     for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
-        m->aux_why = it.type == BAMD_Q2_K || it.type == BAMD_Q3_K ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+        m->aux_why = bamd_is_kquant(it.type) && !bamd_prefill_mfma_type(it.type) ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                                                                   : "a matrix type / shape without a matrix-core kernel";
         return; } need += b + 4096; }
     if (items.empty()) return;
@@ -849,7 +851,7 @@ static int ensure_batch_buffers(bamd_context * c) {
 // prompt path below and the op-level entry point (bamd_op_mul_mat_batch_seg) both come through here
 int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s) {
     const int T = a.T;
-    auto on_mfma = [&](int i) { return g_prefill_mfma && aux[i] && (a.seg[i].type == BAMD_Q4_K || a.seg[i].type == BAMD_Q5_K || a.seg[i].type == BAMD_Q6_K); };
+    auto on_mfma = [&](int i) { return g_prefill_mfma && aux[i] && bamd_prefill_mfma_type(a.seg[i].type); };
     auto mm_mfma = [&](const bamd_mv_seg & sg, const void * ax, int nv, float * out, const float * res, int e) {
         return bamd_launch_matmul_mfma2(sg.w, ax, sg.type, nv, sg.nrows, a.K, blob16, T, out, res, e, a.ldo, s);
     };

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/bamd.h"   // bamd_logit_penalty, bamd_shortlist_head
+#include "bamd_formats.h"
 
 enum { BAMD_PRO_PLAIN = 0, BAMD_PRO_NORM = 1 };
 enum { BAMD_EPI_STORE = 0, BAMD_EPI_ADD = 1, BAMD_EPI_SILU_MUL = 2, BAMD_EPI_ARGMAX = 3 };
@@ -94,6 +95,13 @@ void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, in
 // BAMD_EPI_SILU_MUL: out = silu(res) * y (res = the gate projection, may alias out).  The A fragments are built once per 64-row x 64-token workgroup from the
 // wave-stream copy and the matrix's load-time side table (aux: bamd_prefill_aux_bytes bytes, filled by bamd_launch_prefill_aux).  1 = type / shape not supported or no table
 int  bamd_prefill_mfma_supported(void);      // the current device accepts the kernels' LDS size (asked at model load)
+// "this weight type has a matrix-core prompt mat-mul now": the ONE list — side-table sizes, the launcher, the engine's routing and its load-time message all ask here.
+// Q3_K / Q2_K are behind the process-wide switch bamd_prefill_lowbit() (BAMD_PREFILL_LOWBIT=1 / bamd_set_prefill_lowbit; default off): a model builds their
+// tables, or not, with the value it finds at load
+int  bamd_prefill_lowbit(void);
+static inline bool bamd_prefill_mfma_type(int type) {
+    return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit());
+}
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,

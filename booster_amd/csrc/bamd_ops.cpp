@@ -94,7 +94,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     bamd_launch_repack(raw, str, type, nrows, k, nullptr);
     bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr);
     if (impl == 2) {                                                // the matrix-core kernel: side table built here, as the engine builds it at model load
-        if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K: the integer-dot kernel only
+        if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K with the switch off (bamd_prefill_mfma_type): the integer-dot kernel only
         void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
         if (!aux) return fail("device alloc failed");
         bamd_launch_prefill_aux(str, type, nrows_pad, k, aux, nullptr);
@@ -360,7 +360,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(
     const void * aux[3] = { nullptr, nullptr, nullptr };
     if (impl == 2) for (int i = 0; i < nseg; ++i) {
         const size_t ab = bamd_prefill_aux_bytes(f.seg[i].type, f.seg[i].nrows, k);
-        if (!ab) continue;                                                   // Q2_K / Q3_K, or a shape without a matrix-core kernel
+        if (!ab) continue;                                                   // Q2_K / Q3_K with the switch off, or a shape without a matrix-core kernel
         void * ax = t.up(nullptr, ab);
         if (!ax) return fail("device alloc failed");
         bamd_launch_prefill_aux(f.seg[i].w, f.seg[i].type, f.seg[i].nrows, k, ax, nullptr);

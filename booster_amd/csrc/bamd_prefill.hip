@@ -15,10 +15,10 @@
 // ===========================================================================================================
 
 // one workgroup per token: RMSNorm (optional) + Q8_K of row t of x[T][K] -> blob[t]
-// f16 copy of a token's Q8_K row for the MFMA path.  Per super-block BAMD_B16_REC = 608 B (560 used): 8 (e) x 4 (g) groups of 8 halves — group
+// f16 copy of a token's Q8_K row for the MFMA path.  Per super-block BAMD_B16_REC = 608 B: 8 (e) x 4 (g) groups of 8 halves — group
 // (e, g) = the int8 of sub-blocks 2g and 2g+1, chunk e, as exact f16: one 16-byte B operand of v_mfma_f32_16x16x32_f16 per lane —
 // then, per pair l of sub-blocks, the four halves {S_h(2l), S_h(2l+1), S_l(2l), S_l(2l+1)} of the block sums split as S = 2 S_h + S_l
-// (the B operand of the Q4_K min-term MFMA), then the four i16 pairs (S_2l, S_2l+1) (Q5_K), then the block scale d_y (f32, byte 560); after the nb super-blocks, yd[nb] f32 again.
+// (the B operand of the Q4_K min-term MFMA), then the four i16 pairs (S_2l, S_2l+1) (Q5_K), then the block scale d_y (f32, byte 560), then the sixteen sums of sixteen activations as f16 (bytes 576..607: Q2_K's min term); after the nb super-blocks, yd[nb] f32 again.
 template <bool NORM>
 __global__ void __launch_bounds__(512) quantize_batch_kernel(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K,
                                                              uint8_t * __restrict__ blob, uint8_t * __restrict__ blob16) {
@@ -52,6 +52,13 @@ __global__ void __launch_bounds__(512) quantize_batch_kernel(const float * __res
             *(uint2 *) (o + (size_t) ci * BAMD_B16_REC + 512 + l * 8) = mf;
             // (S_2l, S_2l+1) as i16 pairs (Q5_K: v_dot2_i32_i16)
             *(uint32_t *) (o + (size_t) ci * BAMD_B16_REC + 544 + l * 4) = ((uint32_t) sa & 0xffffu) | ((uint32_t) sb << 16);
+        }
+        for (int i = threadIdx.x; i < nb * 16; i += blockDim.x) {          // Q2_K min term: the sums of sixteen activations (Q8_K's bsums), sixteen f16 at bytes 576..607
+            const int ci = i >> 4, sb = i & 15, c = sb >> 1, h = sb & 1;     // sub-block sb = bytes 0..15 (h = 0: chunks e = 0..3) or 16..31 (h = 1) of the 32 of chunk row c
+            int b = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) b = __builtin_amdgcn_sdot4((int) q8[ci * 64 + (4 * h + e) * 8 + c], 0x01010101, b, false);
+            *(unsigned short *) (o + (size_t) ci * BAMD_B16_REC + 576 + sb * 2) = f2h((float) b);                  // |b| <= 2048: exact
         }
         float * oyd = (float *) (o + (size_t) nb * BAMD_B16_REC);
         for (int i = threadIdx.x; i < nb; i += blockDim.x) { oyd[i] = yd[i]; *(float *) (o + (size_t) i * BAMD_B16_REC + 560) = yd[i]; }   // d_y also inside the record (bamd_prefill2.hip: no separate copy)

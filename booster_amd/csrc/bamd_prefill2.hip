@@ -16,7 +16,8 @@
 //     super-block for Q4_K / Q5_K, 72 B for Q6_K: the MI355X has the HBM for it): the builders' per-(row, sub-block pair) scale operands
 //     {s, -1024 s, s'/16, -64 s'} as packed f16 pairs, and the consumers' d, dmin as f32 plus the min-term MFMA operands {2 m_a, 2 m_b, m_a, m_b}, which
 //     travel global -> LDS by DMA with the activation records;
-//   * two layouts: sixteen waves with one 16 x 16 tile each (matmul_mfma3_q4k_kernel: Q4_K / Q5_K), eight waves with 16 x 32 each (matmul_mfma2_q6k_kernel: Q6_K).
+//   * two layouts: sixteen waves with one 16 x 16 tile each (matmul_mfma3_q4k_kernel: Q4_K / Q5_K), eight waves with 16 x 32 each (matmul_mfma2_q6k_kernel: Q6_K;
+//     matmul_mfma2_lowbit_kernel: Q3_K / Q2_K, behind the switch BAMD_PREFILL_LOWBIT / bamd_set_prefill_lowbit, default off).
 // Same bits as the round-2 kernels (removed in round 6), a third fewer vector instructions per MFMA — and the same time: DESIGN 4c has the measurements of what
 // bounds it, profiles/r06_prefill_ceiling.txt the timing-only ceiling builds (-DBAMD_PREFILL_CEILING).
 #include "bamd_device.h"
@@ -284,6 +285,222 @@ __global__ void __launch_bounds__(512) matmul_mfma2_q6k_kernel(bamd_mma2_args a)
     }
 }
 
+// ---- Q3_K / Q2_K: the Q6_K kernel's half steps with ONE fragment and ONE MFMA per (e, token tile) -------------------------------------------
+// Reference: ggml_vec_dot_q3_K_q8_K / ggml_vec_dot_q2_K_q8_K (ggml-quants.c:6161-6263, :5553-5617).  SIMD lane e owns bytes 4e..4e+3 of the eight chunks c,
+// its scale is that of the 16-element sub-block 2c + (e >= 4): e-half h and chunk pairs (2g, 2g+1) per MFMA lane group g, as for Q6_K.  (sc - 32) x q with
+// q = low2 + 4 hbit - 4 (Q3_K, |.| <= 128) and sc x q (Q2_K, <= 45) are exact f16, so one v_mfma_f32_16x16x32_f16 gives the exact isum_e (|isum_e| <= 2^19,
+// every partial sum an integer): no split scale, no chained second MFMA.  Wave-stream lane (r, e) holds two qs dwords j (fields k = 0..3 = chunk 4j + k) and,
+// Q3_K, the hmask dword (bit c of byte u = element 32c + 4e + u): the pieces of MFMA lanes (row, g = 2p + j') come from qs dword p, fields 2j', 2j'+1, and
+// hmask bits 2g, 2g+1.  Fragment ring: the Q6_K kernel's slots with the second fragment of every pair unused (the 2 x X_FR pitch keeps the builders' stores
+// of eight lanes on eight bank quads).
+// Q2_K's min term goes into the same accumulator in front of the dot term (chain_step): prod_e = mins[2e] bsum16[2e] + mins[2e+1] bsum16[2e+1] is one
+// v_dot2_f32_f16 per row and token on packed pairs — the mins of a row as sixteen f16 in the consumer header, the sums of sixteen activations as sixteen f16 at
+// bytes 576..607 of the token record (quantize_batch_kernel); |prod_e| <= 61 440, exact in f32 in any order.
+#define XL_CH2_RT 640                                      /* Q2_K consumer header of a row tile: 16 x d f32 | 16 x dmin f32 | 16 rows x 16 f16 mins */
+#define XL_CH3_RT 64                                       /* Q3_K: 16 x d f32 */
+#define XL_PH_SB 4096                                      /* builder operands of a row block and super-block: [e-half][4 row tiles][64 MFMA lanes][{s, s}, {s', s'}] */
+template <bool Q2>
+__global__ void __launch_bounds__(64) prefill_aux_lowbit_kernel(const uint8_t * __restrict__ w, int nrows_pad, int nb, uint8_t * __restrict__ ph, uint8_t * __restrict__ ch) {
+    constexpr uint32_t RECB = Q2 ? BAMD_RECB_Q2K : BAMD_RECB_Q3K;
+    const int ci = blockIdx.x, rtile = blockIdx.y, lane = threadIdx.x, m = lane & 15, g = lane >> 4;
+    const int row = rtile * 16 + m;
+    const size_t sb = (size_t) (rtile >> 2) * nb + ci;
+    int sc[4] = { 0, 0, 0, 0 }, mn[4] = { 0, 0, 0, 0 }; uint32_t d16 = 0u, dm16 = 0u;       // sub-blocks 4g .. 4g+3 of row m
+    if (row < nrows_pad) {
+        const uint8_t * rec = w + ((size_t) (row >> 3) * nb + ci) * RECB;
+        if (Q2) {
+            const uint8_t * s = rec + 512 + (row & 7) * 16;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { sc[i] = s[4 * g + i] & 15; mn[i] = s[4 * g + i] >> 4; }
+            const uint32_t dd = *(const uint32_t *) (rec + 640 + (row & 7) * 4); d16 = dd & 0xffffu; dm16 = dd >> 16;
+        } else {
+            const uint8_t * s = rec + 768 + (row & 7) * 12;                                          // the file's 12 packed bytes (ggml-quants.c:6179-6185)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int idx = 4 * g + i;
+                const int low4 = idx < 8 ? s[idx] & 15 : s[idx - 8] >> 4, hi2 = (s[8 + (idx & 3)] >> (2 * (idx >> 2))) & 3;
+                sc[i] = (low4 | (hi2 << 4)) - 32;
+            }
+            d16 = *(const unsigned short *) (rec + 864 + (row & 7) * 2);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                                                                    // chunk 2g: sub-block 4g + h, chunk 2g+1: 4g + 2 + h
+        const _Float16 s0 = (_Float16) (float) sc[h], s1 = (_Float16) (float) sc[2 + h];
+        bamd_h2u o0, o1; o0.h = (bamd_h2) { s0, s0 }; o1.h = (bamd_h2) { s1, s1 };
+        *(uint2 *) (ph + sb * XL_PH_SB + (size_t) (((h * 4 + (rtile & 3)) * 64 + lane) * 8)) = (uint2) { o0.u, o1.u };
+    }
+    if (Q2) {
+        uint8_t * c = ch + sb * (4 * XL_CH2_RT) + (rtile & 3) * XL_CH2_RT;
+        if (g == 0) { *(float *) (c + m * 4) = h2f(d16); *(float *) (c + 64 + m * 4) = h2f(dm16); }
+        bamd_h2u a, b; a.h = (bamd_h2) { (_Float16) (float) mn[0], (_Float16) (float) mn[1] }; b.h = (bamd_h2) { (_Float16) (float) mn[2], (_Float16) (float) mn[3] };
+        *(uint2 *) (c + 128 + m * 32 + g * 8) = (uint2) { a.u, b.u };
+    } else if (g == 0) *(float *) (ch + sb * (4 * XL_CH3_RT) + (rtile & 3) * XL_CH3_RT + m * 4) = h2f(d16);
+}
+
+template <int EPI, bool Q2>
+__global__ void __launch_bounds__(512) matmul_mfma2_lowbit_kernel(bamd_mma2_args a) {
+    constexpr uint32_t RECB = Q2 ? BAMD_RECB_Q2K : BAMD_RECB_Q3K;
+    constexpr int CHRT = Q2 ? XL_CH2_RT : XL_CH3_RT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), m = lane & 15, g = lane >> 4;
+    const int rt = wave >> 1, tp = wave & 1;
+    const int nb = a.K >> 8;
+    const int rb = blockIdx.y, t0 = blockIdx.x * 64;
+    const int rtg = rb * 4 + rt;
+    const bool live = rtg * 16 < a.nrows_pad;
+    const size_t b16 = BAMD_BLOB16_BYTES(nb);
+    const uint32_t lds0 = (uint32_t) (size_t) (bamd_lds_vp) smem;
+    XStage<4 * CHRT / 16> stg; stg.plan(tid, wave, lane, t0, a.T, b16, nb);
+    const uint8_t * chb = a.ch + (size_t) rb * nb * (4 * CHRT);
+#define XL_STAGE(ci_, b_) stg.issue(a.blob16 + (size_t) (ci_) * BAMD_B16_REC, chb + (size_t) (ci_) * (4 * CHRT), a.blob16 + (size_t) (ci_) * 4, lds0 + X_BLK0 + (uint32_t) (b_) * X_BLK, wave, lane)
+    // builder (the Q6_K kernel's lane order): wave (rt, q = tp), lane (p = lane >> 5, r = (lane >> 2) & 7, el = lane & 3) takes, per half step, chunk e = 4 H + el of
+    // row 8q + r and builds the pieces of MFMA lanes (8q + r, g = 2p + j), j = 0, 1, of fragment e from qs dword p and the hmask dword of stream lane (r, e)
+    const int bp = lane >> 5, br = (lane >> 2) & 7, bel = lane & 3;
+    const int rgq = 2 * (live ? rtg : rb * 4) + tp;
+    const int rgc = rgq * 8 < a.nrows_pad ? rgq : rgq - 1;            // a last tile of 8 (padded) rows: its first record group twice (rows 8..15 are never stored)
+    const uint8_t * wqs = a.w + (size_t) rgc * nb * RECB + (size_t) ((br * 8 + bel) * 8 + bp * 4);
+    const uint8_t * whm = a.w + (size_t) rgc * nb * RECB + 512 + (size_t) ((br * 8 + bel) * 4);
+    const uint8_t * phb = a.ph + (size_t) rb * nb * XL_PH_SB + (size_t) rt * 512 + (size_t) (((2 * bp) * 16 + 8 * tp + br) * 8);
+    uint32_t qs[2], hm[2]; uint2 sc[2][2];
+    auto load_set = [&](int hs, auto set_tag) {                // operands of half step hs = 2 ci + h
+        constexpr int S = decltype(set_tag)::value;
+        const int ci = hs >> 1, h = hs & 1;
+        qs[S] = *(const uint32_t *) (wqs + (size_t) ci * RECB + h * 32);
+        if (!Q2) hm[S] = *(const uint32_t *) (whm + (size_t) ci * RECB + h * 16) >> (4 * bp);      // bits 2g, 2g+1 of every byte at bits 2j, 2j+1
+        sc[S][0] = *(const uint2 *) (phb + (size_t) hs * (XL_PH_SB / 2)); sc[S][1] = *(const uint2 *) (phb + (size_t) hs * (XL_PH_SB / 2) + 128);
+    };
+    const _Float16 kz = Q2 ? (_Float16) -1024.f : (_Float16) -1028.f;
+    const bamd_h2 kzero = { kz, kz };
+    bamd_h2u v0, v1, v2, v3;
+    auto build_a = [&](uint32_t q, uint32_t hq, int j) {
+        uint32_t uA = (q >> (4 * j)) & 0x03030303u, uB = (q >> (4 * j + 2)) & 0x03030303u;
+        if (!Q2) { uA |= ((hq >> (2 * j)) & 0x01010101u) << 2; uB |= ((hq >> (2 * j + 1)) & 0x01010101u) << 2; }
+        bamd_h2u c;
+        c.u = __builtin_amdgcn_perm(0x64646464u, uA, 0x04010400u); v0.h = c.h + kzero;      // Q3_K: (1024 + low2 + 4 hbit) - 1028 = q; Q2_K: (1024 + q) - 1024, exact
+        c.u = __builtin_amdgcn_perm(0x64646464u, uA, 0x04030402u); v1.h = c.h + kzero;
+        c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04010400u); v2.h = c.h + kzero;
+        c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04030402u); v3.h = c.h + kzero;
+    };
+    auto build_b = [&](const uint2 & s, unsigned char * dst) {
+        bamd_h2u s0, s1, x0, x1, x2, x3; s0.u = s.x; s1.u = s.y;
+        x0.h = v0.h * s0.h; x1.h = v1.h * s0.h; x2.h = v2.h * s1.h; x3.h = v3.h * s1.h;
+        *(uint4 *) dst = (uint4) { x0.u, x1.u, x2.u, x3.u };
+    };
+    unsigned char * afw = smem + X_AF0 + (rt * 4 + bel) * (2 * X_FR) + ((2 * bp) * 16 + 8 * tp + br) * 16;     // [row tile][e' = 0..3][2 x X_FR]: MFMA lane (8 tp + br, 2 bp + j) at + j * 256
+    const unsigned char * afr = smem + X_AF0 + rt * 8 * X_FR + lane * 16;
+    const unsigned char * tok = smem + X_BLK0 + (size_t) ((2 * tp) * 16 + m) * BAMD_B16_REC;       // this lane's token record of tile n = 0; n = 1: 16 records on
+    const unsigned char * bop = tok + g * 16;
+    const unsigned char * chd = smem + X_BLK0 + X_CH_OFF + rt * CHRT + g * 16;                     // d of rows 4g .. 4g+3 (Q2_K: their dmin 64 bytes on)
+    const unsigned char * chm = smem + X_BLK0 + X_CH_OFF + rt * CHRT + 128 + g * 128;              // Q2_K: the mins of rows 4g .. 4g+3, 32 bytes each
+    const unsigned char * ydp = smem + X_BLK0 + X_YD_OFF + ((2 * tp) * 16 + m) * 4;
+    bamd_f4 acc[2][8];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[n][e] = (bamd_f4) { 0.f, 0.f, 0.f, 0.f };
+    }
+    XL_STAGE(0, 0);
+    load_set(0, std::integral_constant<int, 0>());
+    load_set(1, std::integral_constant<int, 1>());
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { build_a(qs[0], Q2 ? 0u : hm[0], j); build_b(sc[0][j], afw + j * 256); }
+    lds_dma_wait();
+    __syncthreads();
+    const int nhs = 2 * nb;
+    // half step hs = 2 ci + H: fragments in ring slot H, activation block ci & 1 = BLK
+    auto step = [&](const int hs, auto h_tag, auto blk_tag) {
+        constexpr int H = decltype(h_tag)::value, BLK = decltype(blk_tag)::value, NXT = H ^ 1;
+        const int ci = hs >> 1;
+        if (H == 0) XL_STAGE(ci + 1 < nb ? ci + 1 : nb - 1, BLK ^ 1);                              // the next super-block's records: a whole step ahead
+        load_set(hs + 2 < nhs ? hs + 2 : nhs - 2 + H, std::integral_constant<int, H>());
+        __builtin_amdgcn_sched_barrier(0);
+        float D[2][4], Dm[2][4];
+        bamd_h2u mn[4][4], bs[2][4];                                                               // Q2_K: {mins[2e], mins[2e+1]} of rows 4g+i, {bsum16[2e], bsum16[2e+1]} of the two tokens, e = 4 H + 0..3
+        {
+            const bamd_f4 dw = *(const bamd_f4 *) (chd + BLK * X_BLK);
+            bamd_f4 dmw = { 0.f, 0.f, 0.f, 0.f };
+            if (Q2) dmw = *(const bamd_f4 *) (chd + BLK * X_BLK + 64);
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                const float ydv = *(const float *) (ydp + BLK * X_BLK + n * 64);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { D[n][i] = ydv * dw[i]; if (Q2) Dm[n][i] = (-ydv) * dmw[i]; }
+                if (Q2) { const uint4 b = *(const uint4 *) (tok + BLK * X_BLK + n * (16 * BAMD_B16_REC) + 576 + 16 * H); bs[n][0].u = b.x; bs[n][1].u = b.y; bs[n][2].u = b.z; bs[n][3].u = b.w; }
+            }
+            if (Q2) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { const uint4 v = *(const uint4 *) (chm + BLK * X_BLK + i * 32 + 16 * H); mn[i][0].u = v.x; mn[i][1].u = v.y; mn[i][2].u = v.z; mn[i][3].u = v.w; }
+            }
+        }
+        bamd_h8 Aq[2], Bq[2][2]; bamd_f4 sp[2];
+#define XL_LDA(e_) (*(const bamd_h8 *) (afr + H * X_AF_BYTES + (e_) * (2 * X_FR)))
+#define XL_LDB(e_, n_) (*(const bamd_h8 *) (bop + BLK * X_BLK + (n_) * (16 * BAMD_B16_REC) + (4 * H + (e_)) * 64))
+        // the chain of (e, n) follows the MFMAs of e + 1 (one iteration behind: no MFMA -> VALU wait states in front of it)
+        auto chain = [&](int e, int n, const bamd_f4 & s) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float av = acc[n][4 * H + e][i];
+                if (Q2) av = fmaf(Dm[n][i], __builtin_amdgcn_fdot2(mn[i][e].h, bs[n][e].h, 0.f, false), av);      // the min term first, into the same accumulator
+                acc[n][4 * H + e][i] = fmaf(D[n][i], s[i], av);
+            }
+        };
+        Aq[0] = XL_LDA(0); Bq[0][0] = XL_LDB(0, 0); Bq[0][1] = XL_LDB(0, 1);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (e + 1 < 4) { Aq[(e + 1) & 1] = XL_LDA(e + 1); Bq[(e + 1) & 1][0] = XL_LDB(e + 1, 0); Bq[(e + 1) & 1][1] = XL_LDB(e + 1, 1); }
+            if ((e & 1) == 0) build_a(qs[NXT], Q2 ? 0u : hm[NXT], e >> 1);
+            const bamd_f4 z = { 0.f, 0.f, 0.f, 0.f };
+            const bamd_f4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[e & 1], Bq[e & 1][0], z, 0, 0, 0);
+            const bamd_f4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[e & 1], Bq[e & 1][1], z, 0, 0, 0);
+            if (e > 0) { chain(e - 1, 0, sp[0]); chain(e - 1, 1, sp[1]); }
+            if (e & 1) build_b(sc[NXT][e >> 1], afw + NXT * X_AF_BYTES + (e >> 1) * 256);
+            sp[0] = s0; sp[1] = s1;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        chain(3, 0, sp[0]); chain(3, 1, sp[1]);
+#undef XL_LDA
+#undef XL_LDB
+        if (H == 1) lds_dma_wait();
+        __syncthreads();
+    };
+    for (int ci = 0; ci < nb; ci += 2) {
+        step(2 * ci, std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
+        step(2 * ci + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
+        if (ci + 1 < nb) {
+            step(2 * ci + 2, std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
+            step(2 * ci + 3, std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
+        }
+    }
+#undef XL_STAGE
+    if (!live) return;
+    // hsum_float_8 over e, then the epilogue as in the sixteen-wave kernel: rows 4g .. 4g+3 of token t are 16 consecutive bytes
+    const int row0 = rtg * 16 + 4 * g;
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int t = t0 + (2 * tp + n) * 16 + m;
+        float val[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) val[i] = ((acc[n][0][i] + acc[n][4][i]) + (acc[n][2][i] + acc[n][6][i])) + ((acc[n][1][i] + acc[n][5][i]) + (acc[n][3][i] + acc[n][7][i]));
+        if (t < a.T && row0 < a.nrows) {
+            const size_t o = (size_t) t * a.ldo + row0;
+            if (row0 + 3 < a.nrows && (a.ldo & 3) == 0) {
+                bamd_f4 y = { val[0], val[1], val[2], val[3] };
+                if (EPI != BAMD_EPI_STORE) {
+                    const bamd_f4 r = *(const bamd_f4 *) (a.res + o);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) y[i] = EPI == BAMD_EPI_ADD ? val[i] + r[i] : v_silu(r[i]) * val[i];
+                }
+                *(bamd_f4 *) (a.out + o) = y;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (row0 + i < a.nrows) a.out[o + i] = EPI == BAMD_EPI_ADD ? val[i] + a.res[o + i] : EPI == BAMD_EPI_SILU_MUL ? v_silu(a.res[o + i]) * val[i] : val[i];
+            }
+        }
+    }
+}
+
 // ==== sixteen waves ===========================================================================================================================
 // The eight-wave kernels above trade vector instructions for LDS traffic and end where the round-2 kernels were (two waves per SIMD: a step is a chain of
 // dependent latencies).  This kernel — the default for Q4_K / Q5_K — puts four waves on every SIMD:
@@ -546,20 +763,32 @@ __global__ void __launch_bounds__(1024) matmul_mfma3_q4k_kernel(bamd_mma2_args a
 static inline int x_row_blocks(int nrows_pad) { return (nrows_pad + 63) / 64; }
 static unsigned long long * g_prefill_dbg = nullptr;      // -DX_TIMING builds: where the kernels of the next launches leave their phase clocks (bamd_prefill_dbg)
 extern "C" __attribute__((visibility("default"))) void bamd_prefill_dbg(void * dev_buf) { g_prefill_dbg = (unsigned long long *) dev_buf; }
+// process-wide switch of the Q3_K / Q2_K kernels (default off: BAMD_PREFILL_LOWBIT=1 or bamd_set_prefill_lowbit) and the launch counters per weight type
+static int g_prefill_lowbit = [] { const char * e = getenv("BAMD_PREFILL_LOWBIT"); return (e && e[0] == '1') ? 1 : 0; }();
+static long long g_mfma_runs[16] = { 0 };
+int bamd_prefill_lowbit(void) { return g_prefill_lowbit; }
+extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_lowbit(int on) { g_prefill_lowbit = on ? 1 : 0; }
+extern "C" __attribute__((visibility("default"))) long long bamd_prefill_mfma_runs(int type) { return type >= 0 && type < 16 ? g_mfma_runs[type] : 0; }
+static inline bool x_lowbit(int type) { return type == BAMD_Q3_K || type == BAMD_Q2_K; }
+// builder / consumer part of a (row block, super-block) in the side table, and the super-blocks of slack behind each part (the sixteen-wave kernel's last
+// two staging calls read past the end of K; the eight-wave kernels clamp)
+static inline size_t x_ph_sb(int type) { return type == BAMD_Q6_K ? 8192 : x_lowbit(type) ? XL_PH_SB : 4096; }
+static inline size_t x_ch_sb(int type) { return type == BAMD_Q6_K ? 4 * X_CH6_RT : type == BAMD_Q3_K ? 4 * XL_CH3_RT : type == BAMD_Q2_K ? 4 * XL_CH2_RT : X3_CHS; }
+static inline size_t x_slack(int type) { return x_lowbit(type) ? 0 : 2; }
+static inline size_t x_ph_bytes(int type, int nrows_pad, int K) { return ((size_t) x_row_blocks(nrows_pad) * (size_t) (K >> 8) + x_slack(type)) * x_ph_sb(type); }
 // bytes of the side table of a K-quant matrix [nrows_pad][K]: builder part first, the consumer part behind it (both 16-byte aligned)
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K) {
-    if ((type != BAMD_Q4_K && type != BAMD_Q5_K && type != BAMD_Q6_K) || (K & 255) || (nrows_pad & 7)) return 0;
-    const size_t nb = (size_t) (K >> 8), rbk = (size_t) x_row_blocks(nrows_pad);
-    // + two super-blocks of slack behind each table: the sixteen-wave kernel's last two staging calls read past the end of K
-    return type == BAMD_Q6_K ? (rbk * nb + 2) * 8192 + (rbk * nb + 2) * 4 * X_CH6_RT : (rbk * nb + 2) * 4096 + (rbk * nb + 2) * X3_CHS;
+    if (!bamd_prefill_mfma_type(type) || (K & 255) || (nrows_pad & 7)) return 0;
+    return x_ph_bytes(type, nrows_pad, K) + ((size_t) x_row_blocks(nrows_pad) * (size_t) (K >> 8) + x_slack(type)) * x_ch_sb(type);
 }
-static inline size_t x_ph_bytes(int type, int nrows_pad, int K) { return ((size_t) x_row_blocks(nrows_pad) * (size_t) (K >> 8) + 2) * (type == BAMD_Q6_K ? 8192 : 4096); }
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s) {
     const int nb = K >> 8, nrt = x_row_blocks(nrows_pad) * 4;
     uint8_t * ph = (uint8_t *) aux, * ch = ph + x_ph_bytes(type, nrows_pad, K);
     const dim3 grid(nb, nrt);
     if (type == BAMD_Q6_K)      hipLaunchKernelGGL(prefill_aux_q6k_kernel, grid, dim3(64), 0, s, (const uint8_t *) w_stream, nrows_pad, nb, ph, ch);
     else if (type == BAMD_Q5_K) hipLaunchKernelGGL((prefill_aux_q4k_kernel<true>), grid, dim3(64), 0, s, (const uint8_t *) w_stream, nrows_pad, nb, ph, ch);
+    else if (type == BAMD_Q3_K) hipLaunchKernelGGL((prefill_aux_lowbit_kernel<false>), grid, dim3(64), 0, s, (const uint8_t *) w_stream, nrows_pad, nb, ph, ch);
+    else if (type == BAMD_Q2_K) hipLaunchKernelGGL((prefill_aux_lowbit_kernel<true>), grid, dim3(64), 0, s, (const uint8_t *) w_stream, nrows_pad, nb, ph, ch);
     else                        hipLaunchKernelGGL((prefill_aux_q4k_kernel<false>), grid, dim3(64), 0, s, (const uint8_t *) w_stream, nrows_pad, nb, ph, ch);
 }
 // 1 when the current device takes the matrix-core kernels' launches (158 784 B of dynamic LDS at 1024 threads): asked once per model load, before any side table is
@@ -569,12 +798,14 @@ int bamd_prefill_mfma_supported(void) {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) { (void) hipGetLastError(); return 0; }
     if ((size_t) lds < (size_t) X3_LDS_BYTES || (size_t) lds < (size_t) X_LDS_BYTES) return 0;
     if (hipFuncSetAttribute((const void *) matmul_mfma3_q4k_kernel<BAMD_EPI_STORE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X3_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void *) matmul_mfma2_q6k_kernel<BAMD_EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess) { (void) hipGetLastError(); return 0; }
+        hipFuncSetAttribute((const void *) matmul_mfma2_q6k_kernel<BAMD_EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void *) matmul_mfma2_lowbit_kernel<BAMD_EPI_STORE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void *) matmul_mfma2_lowbit_kernel<BAMD_EPI_STORE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess) { (void) hipGetLastError(); return 0; }
     return 1;
 }
 int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                              int epi, int ldo, hipStream_t s) {
-    if ((type != BAMD_Q4_K && type != BAMD_Q5_K && type != BAMD_Q6_K) || (nrows_pad & 7) || (K & 255) || !aux) return 1;
+    if (!bamd_prefill_mfma_type(type) || (nrows_pad & 7) || (K & 255) || !aux) return 1;
     if (epi != BAMD_EPI_STORE && epi != BAMD_EPI_ADD && epi != BAMD_EPI_SILU_MUL) return 1;
     if ((epi != BAMD_EPI_STORE) != (res != nullptr)) return 1;
     bamd_mma2_args a; a.w = (const uint8_t *) w_stream; a.ph = (const uint8_t *) aux; a.ch = a.ph + x_ph_bytes(type, nrows_pad, K);
@@ -590,7 +821,10 @@ int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, 
         if (epi == BAMD_EPI_ADD)           hipLaunchKernelGGL((KERNEL<BAMD_EPI_ADD __VA_ARGS__>),      grid3, dim3(1024), X3_LDS_BYTES, s, a); \
         else if (epi == BAMD_EPI_SILU_MUL) hipLaunchKernelGGL((KERNEL<BAMD_EPI_SILU_MUL __VA_ARGS__>), grid3, dim3(1024), X3_LDS_BYTES, s, a); \
         else                               hipLaunchKernelGGL((KERNEL<BAMD_EPI_STORE __VA_ARGS__>),    grid3, dim3(1024), X3_LDS_BYTES, s, a); } while (0)
+    g_mfma_runs[type] += 1;
     if (type == BAMD_Q6_K)      X_LAUNCH(matmul_mfma2_q6k_kernel);
+    else if (type == BAMD_Q3_K) X_LAUNCH(matmul_mfma2_lowbit_kernel, , false);
+    else if (type == BAMD_Q2_K) X_LAUNCH(matmul_mfma2_lowbit_kernel, , true);
     else if (type == BAMD_Q5_K) X3_LAUNCH(matmul_mfma3_q4k_kernel, , true);
     else                        X3_LAUNCH(matmul_mfma3_q4k_kernel, , false);
 #undef X3_LAUNCH

@@ -38,6 +38,7 @@ int          bamd_model_n_embd(const bamd_model * m);                   /* llama
 int          bamd_model_n_layer(const bamd_model * m);                  /* llama_n_layer (whole model) */
 int          bamd_model_n_ctx_train(const bamd_model * m);              /* llama_n_ctx_train */
 int64_t      bamd_model_weight_bytes(const bamd_model * m);             /* bytes of matmul weights resident on this stage */
+int64_t      bamd_model_prefill_aux_bytes(const bamd_model * m);        /* bytes of the prompt mat-muls' side tables built at load; 0 = none (prompts on the integer-dot kernel) */
 /* copy back the GGUF-layout bytes of one resident tensor (testing / oracle cross-checks); returns bytes or <0 */
 int64_t      bamd_model_tensor_raw(const bamd_model * m, const char * name, void * dst, int64_t cap);
 
@@ -176,6 +177,12 @@ int bamd_bridge_stage_layout(void * ctx, int32_t * out, int cap_stages);
  * kernels.  Bit-identical results.  Contexts with n_ctx > 8192 use the token-by-token path regardless (round 1). */
 void bamd_set_prefill_batch(int on);   /* 2 = batched, but the mat-muls on the integer-dot kernel instead of the matrix-core kernels (the path of a model whose
                                         * side tables did not fit: they are built at model load, all matrices or none, BAMD_PREFILL_AUX_RESERVE_GB of the device left free) */
+/* Matrix-core prompt mat-muls for Q3_K / Q2_K weights, process-wide: 0 (default, also env BAMD_PREFILL_LOWBIT) = a model that holds such a matrix builds
+ * no side tables and evaluates its prompts on the integer-dot kernel; 1 = these types have side tables and kernels like Q4_K / Q5_K / Q6_K.  A model takes the
+ * value at load (its tables exist or not); with the switch off again a model that has tables runs its prompts on the integer-dot kernel.  Bit-identical results. */
+void bamd_set_prefill_lowbit(int on);
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 10 Q2_K .. 14 Q6_K) since the library was loaded */
+long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* One eager single-token step at position `pos` with a HIP-event pair around every kernel launch.
