@@ -910,6 +910,24 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
     } else if (embd_type == BAMD_F16) {
         const unsigned short * src = (const unsigned short *) embd + (size_t) tok * E;
         for (int i = threadIdx.x; i < E; i += blockDim.x) ik_st(x + i, h2f(src[i]));
+    } else if (bamd_is_q0(embd_type)) {
+        // dequantize_row_q8_0 / q4_0 / q5_0 (ggml-quants.c:1609, :1515, :1556): y = (q - 8 | 16 | 0) * d, one f32 product of the integer and the widened f16 d
+        const int bb = bamd_block_bytes(embd_type);
+        const uint8_t * row = embd + (size_t) tok * (E >> 5) * bb;
+        for (int i = threadIdx.x; i < E; i += blockDim.x) {
+            const uint8_t * b = row + (size_t) (i >> 5) * bb;
+            const int n = i & 31;
+            const float d = h2f(*(const unsigned short *) b);
+            int q;
+            if (embd_type == BAMD_Q8_0) q = (int) (int8_t) b[2 + n];
+            else if (embd_type == BAMD_Q4_0) { const uint8_t v = b[2 + (n & 15)]; q = (int) (n < 16 ? (v & 0xF) : (v >> 4)) - 8; }
+            else {
+                const uint32_t qh = (uint32_t) b[2] | ((uint32_t) b[3] << 8) | ((uint32_t) b[4] << 16) | ((uint32_t) b[5] << 24);
+                const uint8_t v = b[6 + (n & 15)];
+                q = (int) ((n < 16 ? (v & 0xF) : (v >> 4)) | (((qh >> n) & 1u) << 4)) - 16;
+            }
+            ik_st(x + i, (float) q * d);
+        }
     } else {
         const int nb = E >> 8;
         const int bb = bamd_block_bytes(embd_type);

@@ -193,10 +193,10 @@ static int upload_mat(bamd_model * m, const GgufTensor * t, DevMat & d, bool kee
                       void * stream_dst = nullptr) {
     if (t->ne.size() != 2) return fail("tensor " + t->name + ": expected 2 dims");
     d.type = t->type; d.K = (int) t->ne[0]; d.nrows = (int) t->ne[1]; d.bytes = t->nbytes;
-    if (d.type != BAMD_F32 && d.type != BAMD_F16 && !bamd_is_kquant(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
-    if (bamd_is_kquant(d.type) && d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
+    if (d.type != BAMD_F32 && d.type != BAMD_F16 && !bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
+    if (bamd_has_record(d.type) && d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     if (want_stream) {
-        if (!bamd_is_kquant(d.type)) return fail("tensor " + t->name + ": only Q2_K/Q3_K/Q4_K/Q5_K/Q6_K matrices are supported on the matmul path");
+        if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": only Q4_0/Q5_0/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K matrices are supported on the matmul path");
         if (d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     }
     d.nrows_pad = (d.nrows + 7) / 8 * 8;
@@ -266,7 +266,10 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
     const int gq = m->H / m->Hkv;
     if (gq < 1 || gq > 8) return fail("GQA ratio (heads per KV head) must be 1 .. 8");
     if (m->hd % 64 || m->hd > 256) return fail("head dim must be 64, 128, 192 or 256");
-    if (m->E % 256 || m->F % 256) return fail("n_embd and n_ff must be multiples of 256");
+    if (m->E % 256 || m->F % 256)
+        return fail(m->E % 32 || m->F % 32 ? "n_embd and n_ff must be multiples of 256"
+                                           : "n_embd and n_ff must be multiples of 256 (n_embd " + std::to_string(m->E) + ", n_ff " + std::to_string(m->F) +
+                                             ": a row length that is a multiple of 32 but not of 256 is a valid Q4_0 / Q5_0 / Q8_0 tensor, but a wave-stream record holds 256 weights per row)");
     if (m->E > 32768 || m->F > 131072) return fail("n_embd / n_ff beyond what the kernels' LDS budgets were sized for");
     if (ll < 0 || ll > m->L) ll = m->L;
     if (lf < 0 || lf > ll) return fail("bad layer range");
@@ -316,7 +319,7 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
                 size_t tot = 0;
                 for (int j = 0; j < 3; ++j) {
                     const GgufTensor * t = g.tensor(p + mats[j].n + ".weight");
-                    if (t && t->ne.size() == 2 && bamd_is_kquant(t->type)) tot += bamd_stream_bytes(t->type, t->ne[0], ((int64_t) t->ne[1] + 7) / 8 * 8);
+                    if (t && t->ne.size() == 2 && bamd_has_record(t->type)) tot += bamd_stream_bytes(t->type, t->ne[0], ((int64_t) t->ne[1] + 7) / 8 * 8);
                 }
                 if (dev_alloc(m->allocs, (void **) &qkv_base, tot)) { rc = 1; break; }
             }
@@ -325,7 +328,7 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
                 const GgufTensor * t = g.tensor(p + mm.n + ".weight");
                 if (!t) { rc = fail("missing tensor " + p + mm.n + ".weight"); break; }
                 void * dst = nullptr;
-                if (mi < 3) { dst = qkv_base + qkv_off; if (t->ne.size() == 2 && bamd_is_kquant(t->type)) qkv_off += bamd_stream_bytes(t->type, t->ne[0], ((int64_t) t->ne[1] + 7) / 8 * 8); }
+                if (mi < 3) { dst = qkv_base + qkv_off; if (t->ne.size() == 2 && bamd_has_record(t->type)) qkv_off += bamd_stream_bytes(t->type, t->ne[0], ((int64_t) t->ne[1] + 7) / 8 * 8); }
                 if ((rc = upload_mat(m, t, *mm.d, false, true, staging, s, dst))) break;
                 ++mi;
             }
@@ -334,6 +337,13 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
                 ly.wo.nrows != m->E || ly.wo.K != m->E || ly.wg.nrows != m->F || ly.wg.K != m->E || ly.wu.nrows != m->F || ly.wu.K != m->E ||
                 ly.wd.nrows != m->E || ly.wd.K != m->F) { rc = fail("layer " + std::to_string(il) + ": unexpected tensor shapes"); break; }
             if (ly.wg.type != ly.wu.type) { rc = fail("ffn_gate and ffn_up must share one quantisation type"); break; }
+            // the fused QKV launch quantises its activations ONCE: Q8_K for K-quant segments, Q8_0 for Q4_0 / Q5_0 / Q8_0 ones.  No llama.cpp recipe mixes the two
+            // families inside attn_q | attn_k | attn_v; a file that does is refused here rather than run with the wrong form
+            for (int j = 1; j < 3 && !rc; ++j)
+                if (bamd_is_q0(mats[j].d->type) != bamd_is_q0(mats[0].d->type))
+                    rc = fail(p + mats[0].n + ".weight (type " + std::to_string(mats[0].d->type) + ") and " + p + mats[j].n + ".weight (type " + std::to_string(mats[j].d->type) +
+                              ") need different activation formats (Q8_K / Q8_0) in one fused launch: not supported");
+            if (rc) break;
         }
     } while (0);
     hipStreamSynchronize(s);
@@ -498,7 +508,7 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
         a.nseg = qkv_segments(ly, c->q, a.seg);
         a.x = c->x; a.normw = ly.attn_norm; a.eps = m->eps; a.K = m->E; a.tl = tl_next(c);
         if (tm) tm->begin(s, 0, (double) (ly.wq.bytes + ly.wk.bytes + ly.wv.bytes));
-        if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_STORE, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
+        if (bamd_launch_mv(a, BAMD_PRO_NORM, BAMD_EPI_STORE, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
         if (tm) tm->end(s);
         // 2. RoPE, KV store, softmax(QK^T) V                               (llama.cpp:8837-8849, :8318-8353)
         bamd_attn_args t; memset(&t, 0, sizeof t);
@@ -531,20 +541,20 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
             if (tm) tm->end(s);
             a.tl = tl_next(c);
             if (tm) tm->begin(s, 0, (double) ly.wo.bytes, 3);
-            if (bamd_launch_matvec(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
+            if (bamd_launch_mv(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
             if (tm) tm->end(s);
         }
         // 4. h = silu(Wg . a) * (Wu . a),  a = Q8_K(rms_norm(x2) * ffn_norm)  (llama.cpp:8869-8885)
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wg, c->h); seg_of(a.seg[1], ly.wu, c->h); a.nseg = 2; a.x = c->x2; a.normw = ly.ffn_norm; a.eps = m->eps; a.K = m->E; a.tl = tl_next(c);
         if (tm) tm->begin(s, 0, (double) (ly.wg.bytes + ly.wu.bytes), 4);
-        if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_SILU_MUL, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
+        if (bamd_launch_mv(a, BAMD_PRO_NORM, BAMD_EPI_SILU_MUL, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
         if (tm) tm->end(s);
         // 5. x = x2 + Wd . Q8_K(h)                                          (llama.cpp:8885, :8902)
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wd, c->x); a.nseg = 1; a.x = c->h; a.K = m->F; a.res = c->x2; a.tl = tl_next(c);
         if (tm) tm->begin(s, 0, (double) ly.wd.bytes, 5);
-        if (bamd_launch_matvec(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
+        if (bamd_launch_mv(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
         if (tm) tm->end(s);
     }
     return 0;
@@ -554,7 +564,7 @@ static int enqueue_lm_head(bamd_context * c, hipStream_t s, StepTimer * tm) {
     bamd_mv_args a; memset(&a, 0, sizeof a);
     seg_of(a.seg[0], m->output, c->logits); a.nseg = 1; a.x = c->x; a.normw = m->out_norm; a.eps = m->eps; a.K = m->E; a.best_key = &c->st->best_key; a.tl = tl_next(c);
     if (tm) tm->begin(s, 0, (double) m->output.bytes, 6);
-    if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_ARGMAX, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
+    if (bamd_launch_mv(a, BAMD_PRO_NORM, BAMD_EPI_ARGMAX, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
     if (tm) tm->end(s);
     return 0;
 }
@@ -806,7 +816,8 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     }
     size_t need = 0;
     for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
-        m->aux_why = bamd_is_kquant(it.type) && !bamd_prefill_mfma_type(it.type) ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+        m->aux_why = bamd_is_q0(it.type) ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                   : bamd_is_kquant(it.type) && !bamd_prefill_mfma_type(it.type) ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                                                                   : "a matrix type / shape without a matrix-core kernel";
         return; } need += b + 4096; }
     if (items.empty()) return;
@@ -895,7 +906,8 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         const DevLayer & ly = m->layers[il];
         bamd_mm_args a; memset(&a, 0, sizeof a);
         // q,k,v                                                            (llama.cpp:8810-8835)
-        bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s);
+        // (the activation form of each mat-mul follows its weights: Q8_0 blocks for Q4_0 / Q5_0 / Q8_0, else Q8_K; the load refused a QKV launch that would need both)
+        bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wq.type));
         a.nseg = qkv_segments(ly, c->bqkv, a.seg);
         a.blob = c->bblob; a.K = E; a.T = T; a.ldo = ldq;
         if (batch_mm(c, a, BAMD_EPI_STORE, s, ly.aux_qkv)) return fail("batched mat-mul: unsupported shape");
@@ -919,17 +931,17 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         }
         if (bamd_launch_attention_batch(t, gq, T, s)) return fail("batched attention: unsupported head configuration");
         // x2 = x + Wo . att
-        bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s);
+        bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wo.type));
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wo, c->bx2); a.nseg = 1; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = E; a.res = c->bx;
         { const void * ax[3] = { ly.aux_o, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }
         // h = silu(Wg . a) * (Wu . a)
-        bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s);
+        bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wg.type));
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wg, c->bh); seg_of(a.seg[1], ly.wu, c->bh); a.nseg = 2; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = F;
         { const void * ax[3] = { ly.aux_g, ly.aux_u, nullptr }; if (batch_mm(c, a, BAMD_EPI_SILU_MUL, s, ax)) return fail("batched mat-mul: unsupported shape"); }
         // x = x2 + Wd . h
-        bamd_launch_quantize_batch(c->bh, nullptr, 0.f, F, T, c->bblob, c->bblob16, s);
+        bamd_launch_quantize_batch(c->bh, nullptr, 0.f, F, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wd.type));
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wd, c->bx); a.nseg = 1; a.blob = c->bblob; a.K = F; a.T = T; a.ldo = E; a.res = c->bx2;
         { const void * ax[3] = { ly.aux_d, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }

@@ -8,6 +8,10 @@
 //   Q2_K  84 B = {u8 scales[16] (low nibble scale, high nibble min), u8 qs[64], f16 d, f16 dmin}      (ggml-common.h:234-261)
 //   Q3_K 110 B = {u8 hmask[32], u8 qs[64], u8 scales[12], f16 d}
 //   Q8_K 292 B = {f32 d, i8 qs[256], i16 bsums[16]}   (activations only; never stored in HBM here)
+// and the 32-weight block formats (ggml-common.h:140-190), whose activations are Q8_0 blocks themselves:
+//   Q4_0  18 B = {f16 d, u8 qs[16]}             element i: low nibble of qs[i] (i < 16), high nibble of qs[i - 16]; value = nibble - 8
+//   Q5_0  22 B = {f16 d, u8 qh[4], u8 qs[16]}   nibbles as Q4_0; bit i of qh = bit 4 of element i; value = 5 bits - 16
+//   Q8_0  34 B = {f16 d, i8 qs[32]}
 //
 // Wave-stream layout (our design; the GGUF file itself is untouched).  A matrix [nrows][K] is cut into
 // row-groups of 8 rows; for each row-group the K/256 super-blocks follow one another as RECORDS, and a record
@@ -29,6 +33,13 @@
 //   Q2_K record  672 B: [qs   : lane*8  -> 2 dwords j=0,1 = file qs[32j+4e .. +3]       ]  512 B
 //                       [sc   : r*16    -> file scales[16]                              ]  128 B
 //                       [dd   : r*4     -> f16 d, f16 dmin                              ]   32 B
+//   Q8_0 / Q4_0 / Q5_0: a record is still 8 rows x 256 weights = eight 32-blocks c = 0..7 per row; lane (r, e) covers bytes 4e .. 4e+3 of every block
+//   (SIMD lane e of the reference's 256-bit accumulator, sgemm.cpp:711-759)
+//   Q8_0 record 2176 B: [qs   : h*1024 + lane*16 -> 4 dwords j=0..3 = block c=4h+j, file qs[4e .. 4e+3]   ] 2048 B (h = 0, 1)
+//                       [d    : r*16    -> eight f16 d, block c = 0..7                  ]  128 B
+//   Q4_0 record 1152 B: [qs   : (r*4 + (e&3))*32 -> 8 dwords c=0..7 = file qs[4(e&3) .. +3]: lanes e and e+4 read the SAME 32 bytes, low / high nibbles] 1024 B
+//                       [d    : r*16    -> eight f16 d                                  ]  128 B
+//   Q5_0 record 1408 B: [qs 1024 B as Q4_0][qh: lane*4 -> one dword, bit 8t + c = bit 4e + t of block c's qh   ] 256 B [d 128 B]
 //   (Q3_K / Q2_K: 3.4375 / 2.625 bits per weight leave a lane 8 B of qs per super-block, so its widest load is 8 bytes; records are 16-byte multiples)
 //
 // Record bytes = 8 x file block bytes, so HBM traffic per weight is exactly the GGUF's bits per weight, every
@@ -45,9 +56,13 @@
 #define BAMD_HD
 #endif
 
-enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_Q2_K = 10, BAMD_Q3_K = 11, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14 };
+enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_Q4_0 = 2, BAMD_Q5_0 = 6, BAMD_Q8_0 = 8, BAMD_Q2_K = 10, BAMD_Q3_K = 11, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14 };
 
-BAMD_HD static inline int bamd_block_bytes(int t) { return t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : t == BAMD_Q3_K ? 110 : t == BAMD_Q2_K ? 84 : 0; }
+BAMD_HD static inline int bamd_is_q0(int t) { return t == BAMD_Q8_0 || t == BAMD_Q4_0 || t == BAMD_Q5_0; }       // 32-weight blocks, Q8_0 activations
+BAMD_HD static inline int bamd_block_bytes(int t) {
+    return t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : t == BAMD_Q3_K ? 110 : t == BAMD_Q2_K ? 84 : t == BAMD_Q8_0 ? 34 : t == BAMD_Q4_0 ? 18 : t == BAMD_Q5_0 ? 22 : 0;
+}
+BAMD_HD static inline int bamd_block_weights(int t) { return bamd_is_q0(t) ? 32 : BAMD_QK_K; }
 #ifndef BAMD_XSCALES
 #define BAMD_XSCALES 0          /* 0: the file's 12 packed scale bytes per row (records of 1152 / 1408 B = 8 x the GGUF block); 1: unpacked scales and
                                    mins, a byte each (1184 / 1440 B) — measured SLOWER on the MI355X in round 2 (gate/up 14.8 vs 13.2 us, decode 649 vs
@@ -59,12 +74,16 @@ BAMD_HD static inline int bamd_block_bytes(int t) { return t == BAMD_Q4_K ? 144 
 #define BAMD_RECB_Q6K 1680
 #define BAMD_RECB_Q3K 880
 #define BAMD_RECB_Q2K 672
+#define BAMD_RECB_Q80 2176
+#define BAMD_RECB_Q40 1152
+#define BAMD_RECB_Q50 1408
 // record bytes as a constant expression of a kernel's TYPE template argument; a type without a record does not compile
-#define BAMD_RECB_OF(T_) ((T_) == BAMD_Q4_K ? BAMD_RECB_Q4K : (T_) == BAMD_Q5_K ? BAMD_RECB_Q5K : (T_) == BAMD_Q6_K ? BAMD_RECB_Q6K : (T_) == BAMD_Q3_K ? BAMD_RECB_Q3K : (T_) == BAMD_Q2_K ? BAMD_RECB_Q2K : -1)
-BAMD_HD static inline int bamd_record_bytes(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? BAMD_RECB_Q6K : t == BAMD_Q3_K ? BAMD_RECB_Q3K : t == BAMD_Q2_K ? BAMD_RECB_Q2K : 0; }   // wave-stream record: 8 rows x 1 super-block
-// bytes of the wave-stream copy of a K-quant matrix [nrows_pad (multiple of 8)][K]
+#define BAMD_RECB_OF(T_) ((T_) == BAMD_Q4_K ? BAMD_RECB_Q4K : (T_) == BAMD_Q5_K ? BAMD_RECB_Q5K : (T_) == BAMD_Q6_K ? BAMD_RECB_Q6K : (T_) == BAMD_Q3_K ? BAMD_RECB_Q3K : (T_) == BAMD_Q2_K ? BAMD_RECB_Q2K : (T_) == BAMD_Q8_0 ? BAMD_RECB_Q80 : (T_) == BAMD_Q4_0 ? BAMD_RECB_Q40 : (T_) == BAMD_Q5_0 ? BAMD_RECB_Q50 : -1)
+BAMD_HD static inline int bamd_record_bytes(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? BAMD_RECB_Q6K : t == BAMD_Q3_K ? BAMD_RECB_Q3K : t == BAMD_Q2_K ? BAMD_RECB_Q2K : t == BAMD_Q8_0 ? BAMD_RECB_Q80 : t == BAMD_Q4_0 ? BAMD_RECB_Q40 : t == BAMD_Q5_0 ? BAMD_RECB_Q50 : 0; }   // wave-stream record: 8 rows x 256 weights
+// bytes of the wave-stream copy of a quantised matrix [nrows_pad (multiple of 8)][K]
 BAMD_HD static inline size_t bamd_stream_bytes(int t, int64_t k, int64_t nrows_pad) { return (size_t) (nrows_pad / 8) * (size_t) (k / BAMD_QK_K) * (size_t) bamd_record_bytes(t); }
 BAMD_HD static inline int bamd_is_kquant(int t) { return t == BAMD_Q4_K || t == BAMD_Q5_K || t == BAMD_Q6_K || t == BAMD_Q3_K || t == BAMD_Q2_K; }
 BAMD_HD static inline size_t bamd_row_bytes(int t, int64_t k) {
-    return t == BAMD_F32 ? (size_t) k * 4 : t == BAMD_F16 ? (size_t) k * 2 : (size_t) (k / BAMD_QK_K) * bamd_block_bytes(t);
+    return t == BAMD_F32 ? (size_t) k * 4 : t == BAMD_F16 ? (size_t) k * 2 : (size_t) (k / bamd_block_weights(t)) * bamd_block_bytes(t);
 }
+BAMD_HD static inline int bamd_has_record(int t) { return bamd_is_kquant(t) || bamd_is_q0(t); }     // has a wave-stream record (rows of K % 256 == 0)

@@ -60,6 +60,29 @@ __global__ void repack_kernel(const uint8_t * __restrict__ raw, uint8_t * __rest
         for (int hi = 0; hi < 2; ++hi)
             for (int c = 0; c < 8; ++c) rec[1536 + r * 16 + hi * 8 + c] = sc[2 * c + hi];
         rec[1664 + r * 2] = src[208]; rec[1664 + r * 2 + 1] = src[209];
+    } else if (bamd_is_q0(type)) {
+        // the eight 32-blocks of this row's 256 weights -> one row of the record (layout: bamd_formats.h)
+        const uint8_t * blk = raw + ((int64_t) row * nb + i) * 8 * bb;
+        const int qo = type == BAMD_Q5_0 ? 6 : 2, dq = type == BAMD_Q8_0 ? 2048 : type == BAMD_Q4_0 ? 1024 : 1280;
+        for (int c = 0; c < 8; ++c) {
+            const uint8_t * b = blk + c * bb;
+            rec[dq + r * 16 + 2 * c] = b[0]; rec[dq + r * 16 + 2 * c + 1] = b[1];
+            if (type == BAMD_Q8_0) {
+                for (int e = 0; e < 8; ++e)
+                    for (int t = 0; t < 4; ++t) rec[(c >> 2) * 1024 + (r * 8 + e) * 16 + (c & 3) * 4 + t] = b[2 + 4 * e + t];
+            } else {
+                for (int l = 0; l < 4; ++l)
+                    for (int t = 0; t < 4; ++t) rec[(r * 4 + l) * 32 + c * 4 + t] = b[qo + 4 * l + t];
+            }
+        }
+        if (type == BAMD_Q5_0) {
+            for (int e = 0; e < 8; ++e) {
+                uint32_t w = 0u;                             // bit 8t + c = bit 4e + t of block c's qh
+                for (int c = 0; c < 8; ++c)
+                    for (int t = 0; t < 4; ++t) w |= (uint32_t) ((blk[c * bb + 2 + (e >> 1)] >> ((e & 1) * 4 + t)) & 1) << (8 * t + c);
+                for (int t = 0; t < 4; ++t) rec[1024 + (r * 8 + e) * 4 + t] = (uint8_t) (w >> (8 * t));
+            }
+        }
     }
 }
 

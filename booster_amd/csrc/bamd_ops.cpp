@@ -40,10 +40,21 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_K(cons
     return finish(out_blocks, dout, ob);
 }
 
+extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_0(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks) {
+    if (need_device()) return 1;
+    if (k <= 0 || k % 256) return fail("k must be a positive multiple of 256");
+    Tmp t; const size_t ob = (size_t) (k / 32) * 34;
+    float * dx = (float *) t.up(x, (size_t) k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr; void * dout = t.up(nullptr, ob);
+    if (!dx || !dout || (norm_w && !dw)) return fail("device alloc/copy failed");
+    HIPC(hipMemset(dout, 0, ob));
+    bamd_launch_quantize_q80_test(dx, dw, eps, (int) k, norm_w != nullptr, dout, nullptr);
+    return finish(out_blocks, dout, ob);
+}
+
 static int op_matvec(int type, const void * wA, const void * wB, int nrows, int k, const float * x, const float * norm_w, float eps,
                      const float * residual, float * y, int epi, int mode, unsigned long long * best_key = nullptr) {
     if (need_device()) return 1;
-    if (!bamd_is_kquant(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
+    if (!bamd_has_record(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
     const int nrows_pad = (nrows + 7) / 8 * 8;
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
     void * rawA = t.up(wA, wb), * strA = t.up(nullptr, wbp), * rawB = nullptr, * strB = nullptr;
@@ -61,7 +72,7 @@ static int op_matvec(int type, const void * wA, const void * wB, int nrows, int 
     a.seg[0].w = strA; a.seg[0].out = dy; a.seg[0].type = type; a.seg[0].nrows = nrows_pad; a.seg[0].nvalid = nrows; a.nseg = 1;
     if (wB) { a.seg[1] = a.seg[0]; a.seg[1].w = strB; a.nseg = 2; }
     a.x = dx; a.normw = dw; a.eps = eps; a.K = k; a.res = dres; a.best_key = key; a.mode = mode;
-    if (bamd_launch_matvec(a, norm_w ? BAMD_PRO_NORM : BAMD_PRO_PLAIN, epi, n_cu0(), nullptr)) return fail("mat-vec: type without a kernel");
+    if (bamd_launch_mv(a, norm_w ? BAMD_PRO_NORM : BAMD_PRO_PLAIN, epi, n_cu0(), nullptr)) return fail("mat-vec: type without a kernel");
     if (finish(y, dy, (size_t) nrows * 4)) return 1;
     if (best_key) HIPC(hipMemcpy(best_key, key, 8, hipMemcpyDeviceToHost));
     return 0;
@@ -82,7 +93,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec_argmax
 extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const float * x, int T, const float * norm_w,
                                                                               float eps, const float * residual, float * y, int impl) {
     if (need_device()) return 1;
-    if (!bamd_is_kquant(type) || k <= 0 || k % 256 || nrows <= 0 || T <= 0) return fail("bad type/shape");
+    if (!bamd_has_record(type) || k <= 0 || k % 256 || nrows <= 0 || T <= 0) return fail("bad type/shape");
     const int nrows_pad = (nrows + 7) / 8 * 8;
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
     void * raw = t.up(w_raw, wb), * str = t.up(nullptr, wbp);
@@ -92,7 +103,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     if (!raw || !str || !dx || !dy || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     HIPC(hipMemset(str, 0, wbp));
     bamd_launch_repack(raw, str, type, nrows, k, nullptr);
-    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr);
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_is_q0(type));
     if (impl == 2) {                                                // the matrix-core kernel: side table built here, as the engine builds it at model load
         if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K with the switch off (bamd_prefill_mfma_type): the integer-dot kernel only
         void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
@@ -113,8 +124,8 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_ffn_gate_up(int ty
 }
 extern "C" __attribute__((visibility("default"))) int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y) {
     if (need_device()) return 1;
-    if (type != BAMD_F32 && type != BAMD_F16 && !bamd_is_kquant(type)) return fail("bad type");
-    if (k <= 0 || (bamd_is_kquant(type) && k % 256)) return fail("bad row length");
+    if (type != BAMD_F32 && type != BAMD_F16 && !bamd_has_record(type)) return fail("bad type");
+    if (k <= 0 || (bamd_has_record(type) && k % 256)) return fail("bad row length");
     if (row < 0 || row >= nrows) return fail("row out of range");
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows;
     void * raw = t.up(w_raw, wb); float * dy = (float *) t.up(nullptr, (size_t) k * 4);
@@ -305,7 +316,7 @@ struct SegFixture {
     int build(Tmp & t, int n, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, float * out, bool same_out = false) {
         if (n < 1 || n > 3 || k <= 0 || k % 256) return fail("bad segment count / row length");
         for (int i = 0; i < n; ++i) {
-            if (!bamd_is_kquant(types[i]) || rows[i] <= 0 || !w_raw[i]) return fail("bad segment type / rows");
+            if (!bamd_has_record(types[i]) || rows[i] <= 0 || !w_raw[i]) return fail("bad segment type / rows");
             const int pad = (rows[i] + 7) / 8 * 8;
             const size_t wb = bamd_row_bytes(types[i], k) * (size_t) rows[i], wbp = bamd_stream_bytes(types[i], k, pad);
             void * raw = t.up(w_raw[i], wb), * str = t.up(nullptr, wbp);
@@ -334,7 +345,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_fused_qkv(int nseg
     bamd_mv_args a; memset(&a, 0, sizeof a);
     for (int i = 0; i < nseg; ++i) a.seg[i] = f.seg[i];
     a.nseg = nseg; a.x = dx; a.normw = dw; a.eps = eps; a.K = k; a.mode = mode;
-    if (bamd_launch_matvec(a, BAMD_PRO_NORM, BAMD_EPI_STORE, n_cu0(), nullptr)) return fail("mat-vec: type without a kernel");
+    if (bamd_launch_mv(a, BAMD_PRO_NORM, BAMD_EPI_STORE, n_cu0(), nullptr)) return fail("mat-vec: type without a kernel");
     return finish(y, dy, (size_t) total * 4);
 }
 
@@ -356,7 +367,8 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(
     void * blob = t.up(nullptr, (size_t) T * bamd_blob_bytes(k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
     if (!dy || !dx || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     SegFixture f; if (f.build(t, nseg, types, w_raw, rows, k, dy, epi == BAMD_EPI_SILU_MUL)) return 1;
-    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr);
+    for (int i = 1; i < nseg; ++i) if (bamd_is_q0(f.seg[i].type) != bamd_is_q0(f.seg[0].type)) return fail("batched mat-mul: segments that need both activation forms (Q8_K and Q8_0)");
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_is_q0(f.seg[0].type));
     const void * aux[3] = { nullptr, nullptr, nullptr };
     if (impl == 2) for (int i = 0; i < nseg; ++i) {
         const size_t ab = bamd_prefill_aux_bytes(f.seg[i].type, f.seg[i].nrows, k);
@@ -385,7 +397,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention_wo(const
     if (need_device()) return 1;
     if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || pos < 0 || pos >= n_ctx || n_ctx % 32 || H % Hkv) return fail("bad attention shape");
     const int K = H * hd;
-    if (!bamd_is_kquant(wo_type) || K % 256 || wo_rows <= 0 || !residual) return fail("bad wo type/shape, or no residual");
+    if (!bamd_has_record(wo_type) || K % 256 || wo_rows <= 0 || !residual) return fail("bad wo type/shape, or no residual");
     AttnFixture f(n_ctx, Hkv, hd); const int Ekv = Hkv * hd;
     bamd_step_state h; memset(&h, 0, sizeof h);
     h.pos_base = pos; h.pos = pos; h.n_ctx = n_ctx; h.n_kv = std::min(n_ctx, std::max(32, (pos + 1 + 31) / 32 * 32)); h.serial = serial; h.step = step;
@@ -494,7 +506,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_trace_attn_wo(int H, 
 extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type, int nrows, int k, int pro, int epi, int mode, int iters,
                                                                         float * us_per_launch) {
     if (need_device()) return 1;
-    if (!bamd_is_kquant(type) || k % 256 || nrows % 8) return fail("bad type/shape");
+    if (!bamd_has_record(type) || k % 256 || nrows % 8) return fail("bad type/shape");
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows;
     std::vector<uint8_t> hw(wb);
     uint32_t sd = 12345u; for (size_t i = 0; i < wb; ++i) { sd = sd * 1664525u + 1013904223u; hw[i] = (uint8_t) (sd >> 24); }
@@ -504,6 +516,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
         if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; }
         else if (type == BAMD_Q3_K) { p[108] = 0x00; p[109] = 0x1c; }
         else if (type == BAMD_Q2_K) { p[80] = 0; p[81] = 0x1c; p[82] = 0; p[83] = 0x1c; }
+        else if (bamd_is_q0(type)) { p[0] = 0; p[1] = 0x1c; }
         else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
     }
     std::vector<float> hx((size_t) k); for (int i = 0; i < k; ++i) { sd = sd * 1664525u + 1013904223u; hx[i] = (float) (int) (sd >> 8) / 8388608.0f - 1.0f; }
@@ -525,11 +538,11 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
     if (iters < 1) return fail("iters < 1");
     OwnedStream os; HIPC(hipStreamCreate(&os.s));
     hipStream_t s = os.s;
-    for (int i = 0; i < 3; ++i) if (bamd_launch_matvec(a, pro, epi, ncu, s)) return fail("mat-vec: type without a kernel");
+    for (int i = 0; i < 3; ++i) if (bamd_launch_mv(a, pro, epi, ncu, s)) return fail("mat-vec: type without a kernel");
     HIPC(hipGetLastError());
     EventPair ev; HIPC(ev.create());
     HIPC(hipEventRecord(ev.a, s));
-    for (int i = 0; i < iters; ++i) if (bamd_launch_matvec(a, pro, epi, ncu, s)) return fail("mat-vec: type without a kernel");
+    for (int i = 0; i < iters; ++i) if (bamd_launch_mv(a, pro, epi, ncu, s)) return fail("mat-vec: type without a kernel");
     HIPC(hipEventRecord(ev.b, s));
     HIPC(hipStreamSynchronize(s));
     float ms = 0.f; HIPC(hipEventElapsedTime(&ms, ev.a, ev.b));
