@@ -58,6 +58,7 @@ def lib():
         L.bamd_timeline_step.argtypes = [vp, ci, ci, vp, ci, C.POINTER(ci)]
         L.bamd_set_prefill_batch.argtypes = [ci]; L.bamd_set_prefill_batch.restype = None
         L.bamd_set_prefill_lowbit.argtypes = [ci]; L.bamd_set_prefill_lowbit.restype = None
+        L.bamd_set_prefill_q0.argtypes = [ci]; L.bamd_set_prefill_q0.restype = None
         L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong
         L.bamd_model_prefill_aux_bytes.argtypes = [vp]; L.bamd_model_prefill_aux_bytes.restype = i64
         L.bamd_bench_matvec.argtypes = [ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)]
@@ -102,6 +103,12 @@ def set_prefill_lowbit(on):
     """True: models loaded from now on build side tables for their Q3_K / Q2_K matrices and evaluate prompts on the matrix-core kernels; False (default, also
     env BAMD_PREFILL_LOWBIT): a model that holds such a matrix evaluates prompts on the integer-dot kernel.  Same bits either way."""
     lib().bamd_set_prefill_lowbit(int(bool(on)))
+
+
+def set_prefill_q0(on):
+    """True: models loaded from now on build side tables for their Q8_0 / Q4_0 / Q5_0 layer matrices and evaluate prompts on the matrix-core kernel of these types;
+    False (default, also env BAMD_PREFILL_Q0): such a model evaluates prompts on the integer-dot kernel.  Same bits either way."""
+    lib().bamd_set_prefill_q0(int(bool(on)))
 
 
 def prefill_mfma_runs(t):

@@ -1,13 +1,16 @@
 // bamd_prefill_q0.hip — batched prompt evaluation for Q8_0 / Q4_0 / Q5_0 weights: per-token Q8_0 quantisation into the activation blobs and the integer-dot
 // batched mat-mul (the counterpart of quantize_batch_kernel / matmul_batch_kernel, bamd_prefill.hip).  Per (row, token) the arithmetic is exactly the
 // single-token chain of bamd_q0_device.h: the reference quantises every activation row to Q8_0 and runs the same block chain per output element, for one
-// token and for many (tinyBLAS_Q0_AVX::gemm, sgemm.cpp:711-759: the tile shape never changes the order of an element's chain).  No matrix-core kernel exists
-// for these types (bamd_prefill_mfma_type).
+// token and for many (tinyBLAS_Q0_AVX::gemm, sgemm.cpp:711-759: the tile shape never changes the order of an element's chain).  The matrix-core kernel of
+// these types is bamd_prefill2_q0.hip, behind a switch (bamd_prefill_mfma_type); this file also writes its f16 activation records.
 #include "bamd_q0_device.h"
 
-// one workgroup per token: RMSNorm (optional) + Q8_0 of row t of x[T][K] -> blob[t], the LDS image of the mat-vec prologue (q8 | block scales as f32)
+// one workgroup per token: RMSNorm (optional) + Q8_0 of row t of x[T][K] -> blob[t], the LDS image of the mat-vec prologue (q8 | block scales as f32).
+// blob16 (may be null): the same values for the matrix-core kernel, per 256 values one BAMD_B16_REC record of which 544 bytes are used — the 256 quants as
+// exact f16 in the order its A operand reads them, element 4e + k of block c at half c * 32 + (e & 3) * 8 + (e >> 2) * 4 + k, then the eight block scales as f32
 template <bool NORM>
-__global__ void __launch_bounds__(512) quantize_batch_q0_kernel(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, uint8_t * __restrict__ blob) {
+__global__ void __launch_bounds__(512) quantize_batch_q0_kernel(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, uint8_t * __restrict__ blob,
+                                                                uint8_t * __restrict__ blob16) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nb = K >> 8, t = blockIdx.x;
     uint32_t * q8 = (uint32_t *) smem; float * ys = (float *) (q8 + nb * 64);
@@ -18,6 +21,17 @@ __global__ void __launch_bounds__(512) quantize_batch_q0_kernel(const float * __
     const size_t bb = BAMD_BLOB_BYTES(nb);
     const uint4 * src = (const uint4 *) smem; uint4 * dst = (uint4 *) (blob + (size_t) t * bb);
     for (int i = threadIdx.x; i < (int) (bb / 16); i += blockDim.x) dst[i] = src[i];
+    if (blob16) {
+        uint8_t * o = blob16 + (size_t) t * BAMD_BLOB16_BYTES(nb);
+        for (int i = threadIdx.x; i < nb * 64; i += blockDim.x) {          // q8[ci*64 + e*8 + c] = block c, chunk e, 4 int8 (never -128)
+            const int ci = i >> 6, e = (i >> 3) & 7, c = i & 7;
+            const uint32_t w = q8[i];
+            const unsigned short h0 = f2h((float) (int8_t) (w)), h1 = f2h((float) (int8_t) (w >> 8)), h2 = f2h((float) (int8_t) (w >> 16)), h3 = f2h((float) (int8_t) (w >> 24));
+            uint2 v; v.x = (uint32_t) h0 | ((uint32_t) h1 << 16); v.y = (uint32_t) h2 | ((uint32_t) h3 << 16);
+            *(uint2 *) (o + (size_t) ci * BAMD_B16_REC + c * 64 + (e & 3) * 16 + (e >> 2) * 8) = v;
+        }
+        for (int i = threadIdx.x; i < nb * 8; i += blockDim.x) *(float *) (o + (size_t) (i >> 3) * BAMD_B16_REC + 512 + (i & 7) * 4) = ys[i];
+    }
 }
 
 template <int TYPE, int D, int EPI, int TT>
@@ -134,9 +148,9 @@ __global__ void __launch_bounds__(512) matmul_batch_q0_kernel(bamd_mm_args a) {
 // ===========================================================================================================
 // launchers
 // ===========================================================================================================
-void bamd_launch_quantize_batch_q0(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s) {
-    if (nw) hipLaunchKernelGGL((quantize_batch_q0_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob);
-    else    hipLaunchKernelGGL((quantize_batch_q0_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob);
+void bamd_launch_quantize_batch_q0(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16) {
+    if (nw) hipLaunchKernelGGL((quantize_batch_q0_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
+    else    hipLaunchKernelGGL((quantize_batch_q0_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
 }
 // every segment Q8_0 / Q4_0 / Q5_0; a.blob in the Q8_0 form (bamd_launch_quantize_batch_q0).  1 = shape not supported
 int bamd_launch_matmul_batch_q0(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s) {

@@ -181,7 +181,11 @@ void bamd_set_prefill_batch(int on);   /* 2 = batched, but the mat-muls on the i
  * no side tables and evaluates its prompts on the integer-dot kernel; 1 = these types have side tables and kernels like Q4_K / Q5_K / Q6_K.  A model takes the
  * value at load (its tables exist or not); with the switch off again a model that has tables runs its prompts on the integer-dot kernel.  Bit-identical results. */
 void bamd_set_prefill_lowbit(int on);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 10 Q2_K .. 14 Q6_K) since the library was loaded */
+/* The same switch for Q8_0 / Q4_0 / Q5_0 weights (env BAMD_PREFILL_Q0): 0 (default) = a model that holds such a layer matrix builds no side tables and evaluates
+ * its prompts on the integer-dot kernel; 1 = side tables (the rows' block scales as f32, 32 B per row and 256 weights) and a matrix-core kernel of their own.
+ * Taken at model load, like bamd_set_prefill_lowbit.  Bit-identical results. */
+void bamd_set_prefill_q0(int on);
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 2 Q4_0, 6 Q5_0, 8 Q8_0, 10 Q2_K .. 14 Q6_K) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */

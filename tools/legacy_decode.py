@@ -1,17 +1,21 @@
 """Greedy decode rate and prompt rate of the synthetic Llama-3-8B file under the Q8_0, Q4_0 and Q5_0 recipes beside the Q4_K_M file, in one job on one card.
-GPU box only.  Decode: per file a 128-token prompt, then generate_greedy of 128 steps, five repetitions after a warm-up; prompt: N tokens in micro-batches of
-512, five repetitions after a warm-up (the Q8_0 / Q4_0 / Q5_0 files on the integer-dot kernel: they have no matrix-core kernel) — median and range.
+GPU box only.  Decode: per file a 128-token prompt, then generate_greedy of 128 steps, five repetitions after a warm-up.  Prompt: N tokens in micro-batches of
+512; per Q8_0 / Q4_0 / Q5_0 file one model loaded with the switch off (integer-dot kernel) and one with set_prefill_q0(True) (side tables, matrix-core kernel),
+five repetitions each after a warm-up, ALTERNATING between the two; the Q4_K_M file beside them — median and range, and whether the switched-on median clears
+the switched-off maximum by more than the switched-off spread.
 
-    python tools/legacy_decode.py [--prompt 2048]
+    python tools/legacy_decode.py [--prompt 2048] [--only-prompt]
 """
 import importlib.util
 import os
 import statistics
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import booster_amd as b  # noqa: E402
 from booster_amd import gguf  # noqa: E402
 from lowbit_decode import decode_rate, prompt_rate, q4_k_m_file  # noqa: E402
 
@@ -21,17 +25,50 @@ _spec.loader.exec_module(gen)
 gen.CONFIGS.setdefault("8b_q5_0", (gen.L3_8B, "q5_0", 128, 64, 512))          # a model only: no fixture of it is stored
 
 
+def prompt_pair(path, n_prompt, reps=5):
+    """switched-off and switched-on rates of one file, alternating: ([off], [on], side-table bytes of the switched-on model)"""
+    b.set_prefill_q0(False); m0 = b.Model(path)
+    b.set_prefill_q0(True)
+    try:
+        m1 = b.Model(path)
+    finally:
+        b.set_prefill_q0(False)                                 # a model keeps the tables it built at load
+    assert m0.prefill_aux_bytes() == 0 and m1.prefill_aux_bytes() > 0
+    ctxs = [b.Context(m0, 4096), b.Context(m1, 4096)]
+    prompt = [(7919 * i + 13) % m0.n_vocab for i in range(n_prompt)]
+    rates = ([], [])
+    for rep in range(reps + 1):                                 # the first pair warms up
+        for k, ctx in enumerate(ctxs):
+            b.set_prefill_q0(bool(k))                           # the routing asks the switch as well as the tables
+            b.lib().bamd_kv_cache_clear(ctx.h)
+            t0 = time.perf_counter()
+            for i in range(0, n_prompt, 512):
+                ctx.decode(prompt[i:i + 512], i)
+            if rep:
+                rates[k].append(n_prompt / (time.perf_counter() - t0))
+    b.set_prefill_q0(False)
+    aux = m1.prefill_aux_bytes()
+    for c in ctxs:
+        c.close()
+    m0.close(); m1.close()
+    return rates[0], rates[1], aux
+
+
 def main():
     files = [("Q4_K_M", q4_k_m_file()), ("Q8_0", gen.ensure_model("8b_q8_0")), ("Q4_0", gen.ensure_model("8b_q4_0")), ("Q5_0", gen.ensure_model("8b_q5_0"))]
-    for name, p in files:
+    for name, p in [] if "--only-prompt" in sys.argv else files:
         r = decode_rate(p)
         print("decode %-7s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, statistics.median(r), min(r), max(r)), flush=True)
     if "--prompt" in sys.argv:
         n = int(sys.argv[sys.argv.index("--prompt") + 1])
-        for name, p in files:
-            r, aux = prompt_rate(p, n, reps=5)
-            print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
-                  "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+        r, _ = prompt_rate(files[0][1], n, reps=5)
+        print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; matrix-core kernels)" % (files[0][0], n, statistics.median(r), min(r), max(r)), flush=True)
+        for name, p in files[1:]:
+            off, on, aux = prompt_pair(p, n)
+            bar = max(off) + (max(off) - min(off))
+            print("prompt %-7s %d tokens: switch off median %7.1f tok/s (range %.1f - %.1f; integer-dot kernel) | switch on median %7.1f tok/s (range %.1f - %.1f; matrix-core kernel, "
+                  "side tables %.2f GiB) | x %.2f | bar (off max + off spread) %.1f: %s" % (name, n, statistics.median(off), min(off), max(off), statistics.median(on), min(on), max(on),
+                  aux / 2 ** 30, statistics.median(on) / statistics.median(off), bar, "cleared" if statistics.median(on) > bar else "NOT cleared"), flush=True)
 
 
 if __name__ == "__main__":

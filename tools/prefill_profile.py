@@ -1,6 +1,7 @@
 """Only the batched prefill (MFMA path), a few repetitions — target for rocprofv3 --kernel-trace --stats (GPU box only).
 
     python tools/prefill_profile.py [tokens] [8b_q3_k_m | 8b_q2_k]      a low-bit file: with set_prefill_lowbit(True), its prompts on the matrix-core Q3_K / Q2_K kernels
+    python tools/prefill_profile.py [tokens] [8b_q8_0 | 8b_q4_0 | 8b_q5_0]   a legacy-quant file: with set_prefill_q0(True), its prompts on the Q8_0 / Q4_0 / Q5_0 matrix-core kernel
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,10 +10,14 @@ from booster_amd import gguf
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 if len(sys.argv) > 2:
     import importlib.util
-    spec = importlib.util.spec_from_file_location("gen_lowbit_fixtures", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "gen_lowbit_fixtures.py"))
+    legacy = sys.argv[2] in ("8b_q8_0", "8b_q4_0", "8b_q5_0")
+    name = "gen_legacy_fixtures" if legacy else "gen_lowbit_fixtures"
+    spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", name + ".py"))
     gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
+    if legacy:
+        gen.CONFIGS.setdefault("8b_q5_0", (gen.L3_8B, "q5_0", 128, 64, 512))          # a model only: no fixture of it is stored
     path = gen.ensure_model(sys.argv[2])
-    b.set_prefill_lowbit(True)
+    b.set_prefill_q0(True) if legacy else b.set_prefill_lowbit(True)
 else:
     path = "/dev/shm/bamd_prefill_8b.gguf"
     if not os.path.exists(path):
