@@ -64,6 +64,7 @@ def lib():
         L.bamd_bench_matvec.argtypes = [ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)]
         L.bamd_op_quantize_q8_K.argtypes = [vp, i64, vp, cf, vp]
         L.bamd_op_quantize_q8_0.argtypes = [vp, i64, vp, cf, vp]
+        L.bamd_op_quantize_q8_1.argtypes = [vp, i64, vp, cf, vp]
         L.bamd_op_mul_mat_vec.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, vp, ci]
         L.bamd_op_mul_mat_vec_argmax.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, ci, C.POINTER(C.c_int32)]
         L.bamd_op_ffn_gate_up.argtypes = [ci, vp, vp, ci, ci, vp, vp, cf, vp]
@@ -284,6 +285,15 @@ def op_quantize_q8_0(x, norm_w=None, eps=0.0):
     w = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32)
     out = np.zeros(x.size // 32 * 34, np.uint8)
     _chk(lib().bamd_op_quantize_q8_0(_p(x), x.size, _p(w), eps, _p(out)))
+    return out
+
+
+def op_quantize_q8_1(x, norm_w=None, eps=0.0):
+    """the mat-vec prologue of the Q4_1 / Q5_1 kernels as standard block_q8_1 bytes {f16 d, f16 s, i8 qs[32]}"""
+    x = np.ascontiguousarray(x, np.float32)
+    w = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32)
+    out = np.zeros(x.size // 32 * 36, np.uint8)
+    _chk(lib().bamd_op_quantize_q8_1(_p(x), x.size, _p(w), eps, _p(out)))
     return out
 
 

@@ -928,6 +928,25 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
             }
             ik_st(x + i, (float) q * d);
         }
+    } else if (bamd_is_q1(embd_type)) {
+        // dequantize_row_q4_1 / q5_1 (ggml-quants.c:1535-1551, :1582-1604): y = q * d + m with q unsigned; q * d (an integer below 32 times a widened f16)
+        // is exact in f32, so a fused and a separate multiply-add give the same bits (tests/legacy1_ref.py)
+        const int bb = bamd_block_bytes(embd_type);
+        const uint8_t * row = embd + (size_t) tok * (E >> 5) * bb;
+        for (int i = threadIdx.x; i < E; i += blockDim.x) {
+            const uint8_t * b = row + (size_t) (i >> 5) * bb;
+            const int n = i & 31;
+            const float d = h2f(*(const unsigned short *) b), mn = h2f(*(const unsigned short *) (b + 2));
+            int q;
+            if (embd_type == BAMD_Q4_1) { const uint8_t v = b[4 + (n & 15)]; q = (int) (n < 16 ? (v & 0xF) : (v >> 4)); }
+            else {
+                const uint32_t qh = (uint32_t) b[4] | ((uint32_t) b[5] << 8) | ((uint32_t) b[6] << 16) | ((uint32_t) b[7] << 24);
+                const uint8_t v = b[8 + (n & 15)];
+                q = (int) ((n < 16 ? (v & 0xF) : (v >> 4)) | (((qh >> n) & 1u) << 4));
+            }
+            const float p = (float) q * d;
+            ik_st(x + i, p + mn);
+        }
     } else {
         const int nb = E >> 8;
         const int bb = bamd_block_bytes(embd_type);

@@ -193,10 +193,10 @@ static int upload_mat(bamd_model * m, const GgufTensor * t, DevMat & d, bool kee
                       void * stream_dst = nullptr) {
     if (t->ne.size() != 2) return fail("tensor " + t->name + ": expected 2 dims");
     d.type = t->type; d.K = (int) t->ne[0]; d.nrows = (int) t->ne[1]; d.bytes = t->nbytes;
-    if (d.type != BAMD_F32 && d.type != BAMD_F16 && !bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, Q4_0, Q5_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
+    if (d.type != BAMD_F32 && d.type != BAMD_F16 && !bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
     if (bamd_has_record(d.type) && d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     if (want_stream) {
-        if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": only Q4_0/Q5_0/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K matrices are supported on the matmul path");
+        if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": only Q4_0/Q4_1/Q5_0/Q5_1/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K matrices are supported on the matmul path");
         if (d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     }
     d.nrows_pad = (d.nrows + 7) / 8 * 8;
@@ -269,7 +269,7 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
     if (m->E % 256 || m->F % 256)
         return fail(m->E % 32 || m->F % 32 ? "n_embd and n_ff must be multiples of 256"
                                            : "n_embd and n_ff must be multiples of 256 (n_embd " + std::to_string(m->E) + ", n_ff " + std::to_string(m->F) +
-                                             ": a row length that is a multiple of 32 but not of 256 is a valid Q4_0 / Q5_0 / Q8_0 tensor, but a wave-stream record holds 256 weights per row)");
+                                             ": a row length that is a multiple of 32 but not of 256 is a valid Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 tensor, but a wave-stream record holds 256 weights per row)");
     if (m->E > 32768 || m->F > 131072) return fail("n_embd / n_ff beyond what the kernels' LDS budgets were sized for");
     if (ll < 0 || ll > m->L) ll = m->L;
     if (lf < 0 || lf > ll) return fail("bad layer range");
@@ -337,12 +337,13 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
                 ly.wo.nrows != m->E || ly.wo.K != m->E || ly.wg.nrows != m->F || ly.wg.K != m->E || ly.wu.nrows != m->F || ly.wu.K != m->E ||
                 ly.wd.nrows != m->E || ly.wd.K != m->F) { rc = fail("layer " + std::to_string(il) + ": unexpected tensor shapes"); break; }
             if (ly.wg.type != ly.wu.type) { rc = fail("ffn_gate and ffn_up must share one quantisation type"); break; }
-            // the fused QKV launch quantises its activations ONCE: Q8_K for K-quant segments, Q8_0 for Q4_0 / Q5_0 / Q8_0 ones.  No llama.cpp recipe mixes the two
+            // the fused QKV launch quantises its activations ONCE: Q8_K for K-quant segments, Q8_0 for Q4_0 / Q5_0 / Q8_0 ones, Q8_1 for Q4_1 / Q5_1 ones
+            // (bamd_act_form_of).  No llama.cpp recipe mixes the
             // families inside attn_q | attn_k | attn_v; a file that does is refused here rather than run with the wrong form
             for (int j = 1; j < 3 && !rc; ++j)
-                if (bamd_is_q0(mats[j].d->type) != bamd_is_q0(mats[0].d->type))
+                if (bamd_act_form_of(mats[j].d->type) != bamd_act_form_of(mats[0].d->type))
                     rc = fail(p + mats[0].n + ".weight (type " + std::to_string(mats[0].d->type) + ") and " + p + mats[j].n + ".weight (type " + std::to_string(mats[j].d->type) +
-                              ") need different activation formats (Q8_K / Q8_0) in one fused launch: not supported");
+                              ") need different activation formats (" + (bamd_is_q1(mats[0].d->type) || bamd_is_q1(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1" : "Q8_K / Q8_0") + ") in one fused launch: not supported");
             if (rc) break;
         }
     } while (0);
@@ -816,7 +817,8 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     }
     size_t need = 0;
     for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
-        m->aux_why = bamd_is_q0(it.type) ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+        m->aux_why = bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                   : bamd_is_q0(it.type) ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_kquant(it.type) && !bamd_prefill_mfma_type(it.type) ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                                                                   : "a matrix type / shape without a matrix-core kernel";
         return; } need += b + 4096; }
@@ -906,8 +908,8 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         const DevLayer & ly = m->layers[il];
         bamd_mm_args a; memset(&a, 0, sizeof a);
         // q,k,v                                                            (llama.cpp:8810-8835)
-        // (the activation form of each mat-mul follows its weights: Q8_0 blocks for Q4_0 / Q5_0 / Q8_0, else Q8_K; the load refused a QKV launch that would need both)
-        bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wq.type));
+        // (the activation form of each mat-mul follows its weights: Q8_0 blocks for Q4_0 / Q5_0 / Q8_0, Q8_1 blocks for Q4_1 / Q5_1, else Q8_K; the load refused a QKV launch that would need both)
+        bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wq.type));
         a.nseg = qkv_segments(ly, c->bqkv, a.seg);
         a.blob = c->bblob; a.K = E; a.T = T; a.ldo = ldq;
         if (batch_mm(c, a, BAMD_EPI_STORE, s, ly.aux_qkv)) return fail("batched mat-mul: unsupported shape");
@@ -931,17 +933,17 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         }
         if (bamd_launch_attention_batch(t, gq, T, s)) return fail("batched attention: unsupported head configuration");
         // x2 = x + Wo . att
-        bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wo.type));
+        bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wo.type));
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wo, c->bx2); a.nseg = 1; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = E; a.res = c->bx;
         { const void * ax[3] = { ly.aux_o, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }
         // h = silu(Wg . a) * (Wu . a)
-        bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wg.type));
+        bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wg.type));
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wg, c->bh); seg_of(a.seg[1], ly.wu, c->bh); a.nseg = 2; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = F;
         { const void * ax[3] = { ly.aux_g, ly.aux_u, nullptr }; if (batch_mm(c, a, BAMD_EPI_SILU_MUL, s, ax)) return fail("batched mat-mul: unsupported shape"); }
         // x = x2 + Wd . h
-        bamd_launch_quantize_batch(c->bh, nullptr, 0.f, F, T, c->bblob, c->bblob16, s, bamd_is_q0(ly.wd.type));
+        bamd_launch_quantize_batch(c->bh, nullptr, 0.f, F, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wd.type));
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wd, c->bx); a.nseg = 1; a.blob = c->bblob; a.K = F; a.T = T; a.ldo = E; a.res = c->bx2;
         { const void * ax[3] = { ly.aux_d, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }

@@ -12,6 +12,9 @@
 //   Q4_0  18 B = {f16 d, u8 qs[16]}             element i: low nibble of qs[i] (i < 16), high nibble of qs[i - 16]; value = nibble - 8
 //   Q5_0  22 B = {f16 d, u8 qh[4], u8 qs[16]}   nibbles as Q4_0; bit i of qh = bit 4 of element i; value = 5 bits - 16
 //   Q8_0  34 B = {f16 d, i8 qs[32]}
+// and their "_1" siblings, whose quants are UNSIGNED with a per-block minimum m and whose activations are Q8_1 blocks {f16 d, f16 s = d * sum(qs), i8 qs[32]}:
+//   Q4_1  20 B = {f16 d, f16 m, u8 qs[16]}             nibbles as Q4_0; value = nibble * d + m
+//   Q5_1  24 B = {f16 d, f16 m, u8 qh[4], u8 qs[16]}   nibbles and qh as Q5_0; value = (5 bits) * d + m
 //
 // Wave-stream layout (our design; the GGUF file itself is untouched).  A matrix [nrows][K] is cut into
 // row-groups of 8 rows; for each row-group the K/256 super-blocks follow one another as RECORDS, and a record
@@ -40,6 +43,8 @@
 //   Q4_0 record 1152 B: [qs   : (r*4 + (e&3))*32 -> 8 dwords c=0..7 = file qs[4(e&3) .. +3]: lanes e and e+4 read the SAME 32 bytes, low / high nibbles] 1024 B
 //                       [d    : r*16    -> eight f16 d                                  ]  128 B
 //   Q5_0 record 1408 B: [qs 1024 B as Q4_0][qh: lane*4 -> one dword, bit 8t + c = bit 4e + t of block c's qh   ] 256 B [d 128 B]
+//   Q4_1 record 1280 B: [qs 1024 B as Q4_0][dm: r*32 -> eight f16 d, then eight f16 m, block c = 0..7    ] 256 B
+//   Q5_1 record 1536 B: [qs 1024 B as Q4_0][qh 256 B as Q5_0][dm 256 B as Q4_1]
 //   (Q3_K / Q2_K: 3.4375 / 2.625 bits per weight leave a lane 8 B of qs per super-block, so its widest load is 8 bytes; records are 16-byte multiples)
 //
 // Record bytes = 8 x file block bytes, so HBM traffic per weight is exactly the GGUF's bits per weight, every
@@ -56,13 +61,16 @@
 #define BAMD_HD
 #endif
 
-enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_Q4_0 = 2, BAMD_Q5_0 = 6, BAMD_Q8_0 = 8, BAMD_Q2_K = 10, BAMD_Q3_K = 11, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14 };
+enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_Q4_0 = 2, BAMD_Q4_1 = 3, BAMD_Q5_0 = 6, BAMD_Q5_1 = 7, BAMD_Q8_0 = 8, BAMD_Q2_K = 10, BAMD_Q3_K = 11, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14 };
 
 BAMD_HD static inline int bamd_is_q0(int t) { return t == BAMD_Q8_0 || t == BAMD_Q4_0 || t == BAMD_Q5_0; }       // 32-weight blocks, Q8_0 activations
+BAMD_HD static inline int bamd_is_q1(int t) { return t == BAMD_Q4_1 || t == BAMD_Q5_1; }                               // 32-weight blocks with a minimum, Q8_1 activations
+// the form a launch quantises its activations to for weights of type t; one launch has one form (0 = a type without a mat-vec kernel)
+enum bamd_act_form { BAMD_ACT_NONE = 0, BAMD_ACT_Q8_K = 1, BAMD_ACT_Q8_0 = 2, BAMD_ACT_Q8_1 = 3 };
 BAMD_HD static inline int bamd_block_bytes(int t) {
-    return t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : t == BAMD_Q3_K ? 110 : t == BAMD_Q2_K ? 84 : t == BAMD_Q8_0 ? 34 : t == BAMD_Q4_0 ? 18 : t == BAMD_Q5_0 ? 22 : 0;
+    return t == BAMD_Q4_1 ? 20 : t == BAMD_Q5_1 ? 24 : t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : t == BAMD_Q3_K ? 110 : t == BAMD_Q2_K ? 84 : t == BAMD_Q8_0 ? 34 : t == BAMD_Q4_0 ? 18 : t == BAMD_Q5_0 ? 22 : 0;
 }
-BAMD_HD static inline int bamd_block_weights(int t) { return bamd_is_q0(t) ? 32 : BAMD_QK_K; }
+BAMD_HD static inline int bamd_block_weights(int t) { return bamd_is_q0(t) || bamd_is_q1(t) ? 32 : BAMD_QK_K; }
 #ifndef BAMD_XSCALES
 #define BAMD_XSCALES 0          /* 0: the file's 12 packed scale bytes per row (records of 1152 / 1408 B = 8 x the GGUF block); 1: unpacked scales and
                                    mins, a byte each (1184 / 1440 B) — measured SLOWER on the MI355X in round 2 (gate/up 14.8 vs 13.2 us, decode 649 vs
@@ -77,13 +85,16 @@ BAMD_HD static inline int bamd_block_weights(int t) { return bamd_is_q0(t) ? 32 
 #define BAMD_RECB_Q80 2176
 #define BAMD_RECB_Q40 1152
 #define BAMD_RECB_Q50 1408
+#define BAMD_RECB_Q41 1280
+#define BAMD_RECB_Q51 1536
 // record bytes as a constant expression of a kernel's TYPE template argument; a type without a record does not compile
-#define BAMD_RECB_OF(T_) ((T_) == BAMD_Q4_K ? BAMD_RECB_Q4K : (T_) == BAMD_Q5_K ? BAMD_RECB_Q5K : (T_) == BAMD_Q6_K ? BAMD_RECB_Q6K : (T_) == BAMD_Q3_K ? BAMD_RECB_Q3K : (T_) == BAMD_Q2_K ? BAMD_RECB_Q2K : (T_) == BAMD_Q8_0 ? BAMD_RECB_Q80 : (T_) == BAMD_Q4_0 ? BAMD_RECB_Q40 : (T_) == BAMD_Q5_0 ? BAMD_RECB_Q50 : -1)
-BAMD_HD static inline int bamd_record_bytes(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? BAMD_RECB_Q6K : t == BAMD_Q3_K ? BAMD_RECB_Q3K : t == BAMD_Q2_K ? BAMD_RECB_Q2K : t == BAMD_Q8_0 ? BAMD_RECB_Q80 : t == BAMD_Q4_0 ? BAMD_RECB_Q40 : t == BAMD_Q5_0 ? BAMD_RECB_Q50 : 0; }   // wave-stream record: 8 rows x 256 weights
+#define BAMD_RECB_OF(T_) ((T_) == BAMD_Q4_K ? BAMD_RECB_Q4K : (T_) == BAMD_Q5_K ? BAMD_RECB_Q5K : (T_) == BAMD_Q6_K ? BAMD_RECB_Q6K : (T_) == BAMD_Q3_K ? BAMD_RECB_Q3K : (T_) == BAMD_Q2_K ? BAMD_RECB_Q2K : (T_) == BAMD_Q8_0 ? BAMD_RECB_Q80 : (T_) == BAMD_Q4_0 ? BAMD_RECB_Q40 : (T_) == BAMD_Q5_0 ? BAMD_RECB_Q50 : (T_) == BAMD_Q4_1 ? BAMD_RECB_Q41 : (T_) == BAMD_Q5_1 ? BAMD_RECB_Q51 : -1)
+BAMD_HD static inline int bamd_record_bytes(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? BAMD_RECB_Q6K : t == BAMD_Q3_K ? BAMD_RECB_Q3K : t == BAMD_Q2_K ? BAMD_RECB_Q2K : t == BAMD_Q8_0 ? BAMD_RECB_Q80 : t == BAMD_Q4_0 ? BAMD_RECB_Q40 : t == BAMD_Q5_0 ? BAMD_RECB_Q50 : t == BAMD_Q4_1 ? BAMD_RECB_Q41 : t == BAMD_Q5_1 ? BAMD_RECB_Q51 : 0; }   // wave-stream record: 8 rows x 256 weights
 // bytes of the wave-stream copy of a quantised matrix [nrows_pad (multiple of 8)][K]
 BAMD_HD static inline size_t bamd_stream_bytes(int t, int64_t k, int64_t nrows_pad) { return (size_t) (nrows_pad / 8) * (size_t) (k / BAMD_QK_K) * (size_t) bamd_record_bytes(t); }
 BAMD_HD static inline int bamd_is_kquant(int t) { return t == BAMD_Q4_K || t == BAMD_Q5_K || t == BAMD_Q6_K || t == BAMD_Q3_K || t == BAMD_Q2_K; }
 BAMD_HD static inline size_t bamd_row_bytes(int t, int64_t k) {
     return t == BAMD_F32 ? (size_t) k * 4 : t == BAMD_F16 ? (size_t) k * 2 : (size_t) (k / bamd_block_weights(t)) * bamd_block_bytes(t);
 }
-BAMD_HD static inline int bamd_has_record(int t) { return bamd_is_kquant(t) || bamd_is_q0(t); }     // has a wave-stream record (rows of K % 256 == 0)
+BAMD_HD static inline int bamd_has_record(int t) { return bamd_is_kquant(t) || bamd_is_q0(t) || bamd_is_q1(t); }     // has a wave-stream record (rows of K % 256 == 0)
+BAMD_HD static inline int bamd_act_form_of(int t) { return bamd_is_kquant(t) ? BAMD_ACT_Q8_K : bamd_is_q0(t) ? BAMD_ACT_Q8_0 : bamd_is_q1(t) ? BAMD_ACT_Q8_1 : BAMD_ACT_NONE; }

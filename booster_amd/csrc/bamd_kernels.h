@@ -77,12 +77,16 @@ void bamd_launch_quantize_q8k_test(const float * x, const float * nw, float eps,
 [[nodiscard]] int bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);          // 1 = a segment's type has no kernel (nothing launched)
 // the same for launches whose segments are all Q8_0 / Q4_0 / Q5_0 (bamd_matvec_q0.hip: Q8_0 activations)
 [[nodiscard]] int bamd_launch_matvec_q0(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
-// what the engine and the ops call: the family of the first segment picks the launcher, and each launcher refuses a segment of the other family (a launch
-// quantises its activations once, as Q8_K or as Q8_0).  bamd_launch_matvec itself stays the K-quant launcher that tests/test_launch_selection.py pins, its
+// the same for launches whose segments are all Q4_1 / Q5_1 (bamd_matvec_q1.hip: Q8_1 activations); 2 = split-K (mode 2) was asked for, which these types do not have
+[[nodiscard]] int bamd_launch_matvec_q1(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
+// what the engine and the ops call: the family of the first segment picks the launcher, and each launcher refuses a segment of another family (a launch
+// quantises its activations once, as Q8_K, as Q8_0 or as Q8_1: bamd_act_form_of).  bamd_launch_matvec itself stays the K-quant launcher that tests/test_launch_selection.py pins, its
 // refusal of every other type included
 [[nodiscard]] static inline int bamd_launch_mv(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
-    return a.nseg > 0 && bamd_is_q0(a.seg[0].type) ? bamd_launch_matvec_q0(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
+    return a.nseg > 0 && bamd_is_q0(a.seg[0].type) ? bamd_launch_matvec_q0(a, pro, epi, n_cu, s)
+         : a.nseg > 0 && bamd_is_q1(a.seg[0].type) ? bamd_launch_matvec_q1(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
 }
+void bamd_launch_quantize_q81_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 void bamd_launch_quantize_q80_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 void bamd_launch_step_begin(bamd_step_state * st, const int32_t * forced, int n_forced, int32_t * out_tokens, const void * embd,
                             int embd_type, int E, int V, float * x, int do_embed, hipStream_t s, const int32_t * slots = nullptr, int32_t * cellpos = nullptr,
@@ -99,11 +103,14 @@ void bamd_launch_k_shift(unsigned short * kc, int n_cells, int Hkv, int hd, cons
 size_t bamd_blob_bytes(int K);
 size_t bamd_blob16_bytes(int K);
 // blob: int8 activations for matmul_batch_kernel (may be null); blob16: f16 copy for the MFMA kernel (may be null)
-// q0 != 0: the consuming mat-mul has Q8_0 / Q4_0 / Q5_0 weights — blob takes the Q8_0 form of the same size (bamd_prefill_q0.hip); blob16 is written, in the
+// form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_1 form of the same size (bamd_prefill_q1.hip), blob16
+// is not written; BAMD_ACT_Q8_0: the consuming mat-mul has Q8_0 / Q4_0 / Q5_0 weights — blob takes the Q8_0 form of the same size (bamd_prefill_q0.hip); blob16 is written, in the
 // f16 form of bamd_prefill2_q0.hip and with the same per-token stride, only while the switch bamd_prefill_q0() is on (otherwise nothing reads it)
-void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int q0 = 0);
+void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K);
 void bamd_launch_quantize_batch_q0(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
 int  bamd_launch_matmul_batch_q0(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);           // every segment Q8_0 / Q4_0 / Q5_0, a.blob in the Q8_0 form; 1 = shape not supported
+void bamd_launch_quantize_batch_q1(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s);
+int  bamd_launch_matmul_batch_q1(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);           // every segment Q4_1 / Q5_1, a.blob in the Q8_1 form; 1 = shape not supported
 // K-quant matrices on the matrix cores, exact (bamd_prefill2.hip): y[t][row] = W[row,:] . Q8_K(a_t); epi BAMD_EPI_STORE: out = y; BAMD_EPI_ADD: out = y + res;
 // BAMD_EPI_SILU_MUL: out = silu(res) * y (res = the gate projection, may alias out).  The A fragments are built once per 64-row x 64-token workgroup from the
 // wave-stream copy and the matrix's load-time side table (aux: bamd_prefill_aux_bytes bytes, filled by bamd_launch_prefill_aux).  1 = type / shape not supported or no table
@@ -115,7 +122,7 @@ int  bamd_prefill_mfma_supported(void);      // the current device accepts the k
 int  bamd_prefill_lowbit(void);
 int  bamd_prefill_q0(void);
 static inline bool bamd_prefill_mfma_type(int type) {
-    return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit()) || (bamd_is_q0(type) && bamd_prefill_q0());
+    return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit()) || (bamd_is_q0(type) && bamd_prefill_q0());      // Q4_1 / Q5_1: none
 }
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);

@@ -83,6 +83,25 @@ __global__ void repack_kernel(const uint8_t * __restrict__ raw, uint8_t * __rest
                 for (int t = 0; t < 4; ++t) rec[1024 + (r * 8 + e) * 4 + t] = (uint8_t) (w >> (8 * t));
             }
         }
+    } else if (bamd_is_q1(type)) {
+        // Q4_1 / Q5_1: nibbles and qh exactly as Q4_0 / Q5_0 above; behind them the row's eight f16 d, then its eight f16 m (32 B per row)
+        const uint8_t * blk = raw + ((int64_t) row * nb + i) * 8 * bb;
+        const int qo = type == BAMD_Q5_1 ? 8 : 4, dm = type == BAMD_Q5_1 ? 1280 : 1024;
+        for (int c = 0; c < 8; ++c) {
+            const uint8_t * b = blk + c * bb;
+            rec[dm + r * 32 + 2 * c] = b[0]; rec[dm + r * 32 + 2 * c + 1] = b[1];
+            rec[dm + r * 32 + 16 + 2 * c] = b[2]; rec[dm + r * 32 + 16 + 2 * c + 1] = b[3];
+            for (int l = 0; l < 4; ++l)
+                for (int t = 0; t < 4; ++t) rec[(r * 4 + l) * 32 + c * 4 + t] = b[qo + 4 * l + t];
+        }
+        if (type == BAMD_Q5_1) {
+            for (int e = 0; e < 8; ++e) {
+                uint32_t w = 0u;                             // bit 8t + c = bit 4e + t of block c's qh
+                for (int c = 0; c < 8; ++c)
+                    for (int t = 0; t < 4; ++t) w |= (uint32_t) ((blk[c * bb + 4 + (e >> 1)] >> ((e & 1) * 4 + t)) & 1) << (8 * t + c);
+                for (int t = 0; t < 4; ++t) rec[1024 + (r * 8 + e) * 4 + t] = (uint8_t) (w >> (8 * t));
+            }
+        }
     }
 }
 

@@ -51,10 +51,22 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_0(cons
     return finish(out_blocks, dout, ob);
 }
 
+extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_1(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks) {
+    if (need_device()) return 1;
+    if (k <= 0 || k % 256) return fail("k must be a positive multiple of 256");
+    Tmp t; const size_t ob = (size_t) (k / 32) * 36;
+    float * dx = (float *) t.up(x, (size_t) k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr; void * dout = t.up(nullptr, ob);
+    if (!dx || !dout || (norm_w && !dw)) return fail("device alloc/copy failed");
+    HIPC(hipMemset(dout, 0, ob));
+    bamd_launch_quantize_q81_test(dx, dw, eps, (int) k, norm_w != nullptr, dout, nullptr);
+    return finish(out_blocks, dout, ob);
+}
+
 static int op_matvec(int type, const void * wA, const void * wB, int nrows, int k, const float * x, const float * norm_w, float eps,
                      const float * residual, float * y, int epi, int mode, unsigned long long * best_key = nullptr) {
     if (need_device()) return 1;
     if (!bamd_has_record(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
+    if (bamd_is_q1(type) && (mode & 15) == 2) return fail("mat-vec: Q4_1 / Q5_1 have no split-K kernel (mode 2): one wave per row-group only");
     const int nrows_pad = (nrows + 7) / 8 * 8;
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
     void * rawA = t.up(wA, wb), * strA = t.up(nullptr, wbp), * rawB = nullptr, * strB = nullptr;
@@ -103,7 +115,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     if (!raw || !str || !dx || !dy || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     HIPC(hipMemset(str, 0, wbp));
     bamd_launch_repack(raw, str, type, nrows, k, nullptr);
-    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_is_q0(type));
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(type));
     if (impl == 2) {                                                // the matrix-core kernel: side table built here, as the engine builds it at model load
         if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K with the switch off (bamd_prefill_mfma_type): the integer-dot kernel only
         void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
@@ -367,8 +379,8 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(
     void * blob = t.up(nullptr, (size_t) T * bamd_blob_bytes(k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
     if (!dy || !dx || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     SegFixture f; if (f.build(t, nseg, types, w_raw, rows, k, dy, epi == BAMD_EPI_SILU_MUL)) return 1;
-    for (int i = 1; i < nseg; ++i) if (bamd_is_q0(f.seg[i].type) != bamd_is_q0(f.seg[0].type)) return fail("batched mat-mul: segments that need both activation forms (Q8_K and Q8_0)");
-    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_is_q0(f.seg[0].type));
+    for (int i = 1; i < nseg; ++i) if (bamd_act_form_of(f.seg[i].type) != bamd_act_form_of(f.seg[0].type)) return fail(bamd_is_q1(f.seg[i].type) || bamd_is_q1(f.seg[0].type) ? "batched mat-mul: segments that need different activation forms (Q8_K, Q8_0, Q8_1)" : "batched mat-mul: segments that need both activation forms (Q8_K and Q8_0)");
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(f.seg[0].type));
     const void * aux[3] = { nullptr, nullptr, nullptr };
     if (impl == 2) for (int i = 0; i < nseg; ++i) {
         const size_t ab = bamd_prefill_aux_bytes(f.seg[i].type, f.seg[i].nrows, k);
@@ -517,6 +529,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
         else if (type == BAMD_Q3_K) { p[108] = 0x00; p[109] = 0x1c; }
         else if (type == BAMD_Q2_K) { p[80] = 0; p[81] = 0x1c; p[82] = 0; p[83] = 0x1c; }
         else if (bamd_is_q0(type)) { p[0] = 0; p[1] = 0x1c; }
+        else if (bamd_is_q1(type)) { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
         else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
     }
     std::vector<float> hx((size_t) k); for (int i = 0; i < k; ++i) { sd = sd * 1664525u + 1013904223u; hx[i] = (float) (int) (sd >> 8) / 8388608.0f - 1.0f; }

@@ -20,7 +20,9 @@
 // ===========================================================================================================
 template <bool NORM>
 struct ActProQ0 : ActPro<NORM> {
-    template <int NB = BAMD_ACT_BATCH>
+    // Q1: the Q8_1 form of the "_1" weight types (bamd_q1_device.h) — the same d, id and bytes, and the block's 4-byte slot of the S area holds the block's
+    // pair {f16 d, f16 s} (d low) in place of d widened
+    template <int NB = BAMD_ACT_BATCH, bool Q1 = false>
     __device__ __forceinline__ void quantize_batch_q0(float scale, int K, int i0, uint32_t * q8, float * ys, int bstride = 0, int blimit = 0) {
         const int lane = threadIdx.x & 63;
         const int nwaves = bstride ? bstride : (int) (blockDim.x >> 6), nb = bstride ? blimit : (K >> 8);
@@ -43,14 +45,25 @@ struct ActProQ0 : ActPro<NORM> {
             const uint32_t p01 = __builtin_amdgcn_perm(__float_as_uint(t1), __float_as_uint(t0), 0x0c0c0400u);
             const uint32_t p23 = __builtin_amdgcn_perm(__float_as_uint(t3), __float_as_uint(t2), 0x0c0c0400u);
             const uint32_t packed = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+            // quantize_row_q8_1 (ggml-quants.c:1319): s = f16(d * (float) sum of the block's 32 quants), d the UNROUNDED f32 quotient; the sum is exact (|sum| <= 4064)
+            // The product is rounded to f32 FIRST and to f16 after (two roundings, as the reference's scalar code does): its bits pass through a register of
+            // their own, or the compiler folds the multiply into the conversion (v_fma_mixlo_f16: ONE rounding of the exact product, another f16 for about
+            // one block in a thousand — found by tests/test_gpu_legacy1_ops.py)
+            const int qsum = Q1 ? group8_sum(sdot4(packed, 0x01010101u)) : 0;
+            uint32_t sbits = Q1 ? __float_as_uint(d * (float) qsum) : 0u;
+            if (Q1) pin(sbits);
             const int i = i0 + b * nwaves;
             if (i < nb) {                                // wave-uniform
                 q8[i * 64 + (lane & 7) * 8 + (lane >> 3)] = packed;
-                if ((lane & 7) == 0) ys[i * 8 + (lane >> 3)] = h2f(f2h(d));
+                if ((lane & 7) == 0) {
+                    if (Q1) ((uint32_t *) ys)[i * 8 + (lane >> 3)] = (uint32_t) f2h(d) | ((uint32_t) f2h(__uint_as_float(sbits)) << 16);
+                    else ys[i * 8 + (lane >> 3)] = h2f(f2h(d));
+                }
             }
         }
     }
     // ActPro::finish with the Q8_0 quantiser; the f64 sum of squares and its guard are the same code
+    template <bool Q1 = false>
     __device__ __forceinline__ void finish_q0(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, uint32_t * q8, float * ys, double * red) {
         const int lane = threadIdx.x & 63, wave = wave_id(), nwaves = blockDim.x >> 6, nb = K >> 8;
         const int step = nwaves * BAMD_ACT_BATCH;
@@ -89,10 +102,10 @@ struct ActProQ0 : ActPro<NORM> {
             }
             scale = 1.0f / sqrtf(mean + eps);
         }
-        quantize_batch_q0(scale, K, wave, q8, ys);
+        this->template quantize_batch_q0<BAMD_ACT_BATCH, Q1>(scale, K, wave, q8, ys);
         for (int i0 = wave + step; i0 < nb; i0 += step) {
             ActProQ0<NORM> t; t.issue(x, nw, K, i0);
-            t.quantize_batch_q0(scale, K, i0, q8, ys);
+            t.template quantize_batch_q0<BAMD_ACT_BATCH, Q1>(scale, K, i0, q8, ys);
         }
         __syncthreads();
     }

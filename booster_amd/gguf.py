@@ -17,7 +17,9 @@ GGML_TYPES = {
     0: (1, 4),        # F32
     1: (1, 2),        # F16
     2: (32, 18),      # Q4_0
+    3: (32, 20),      # Q4_1
     6: (32, 22),      # Q5_0
+    7: (32, 24),      # Q5_1
     8: (32, 34),      # Q8_0
     10: (256, 84),    # Q2_K
     11: (256, 110),   # Q3_K
@@ -28,7 +30,8 @@ GGML_TYPES = {
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
 Q2_K, Q3_K = 10, 11
 Q4_0, Q5_0, Q8_0 = 2, 6, 8
-TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 6: "Q5_0", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K"}
+Q4_1, Q5_1 = 3, 7
+TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K"}
 
 # gguf KV value types
 T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I64, T_F64 = range(13)
@@ -193,6 +196,8 @@ def random_kquant_tensor(ttype, row_len, n_rows, rng, amp=1.0):
     zero-mean with standard deviation ~ amp / sqrt(row_len)."""
     if ttype in (Q4_0, Q5_0, Q8_0):
         return random_q0_tensor(ttype, row_len, n_rows, rng, amp)
+    if ttype in (Q4_1, Q5_1):
+        return random_q1_tensor(ttype, row_len, n_rows, rng, amp)
     be, bb = GGML_TYPES[ttype]
     nblk = n_rows * (row_len // be)
     blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
@@ -234,6 +239,21 @@ def random_q0_tensor(ttype, row_len, n_rows, rng, amp=1.0):
     return blk.reshape(-1)
 
 
+def random_q1_tensor(ttype, row_len, n_rows, rng, amp=1.0):
+    """Random raw Q4_1 / Q5_1 blocks for an [n_rows, row_len] matrix: every byte pattern in qs / qh, finite f16 d and m of either sign.  The value of a
+    weight is q * d + m with q unsigned (0..15 / 0..31): m lies around -(the quants' midpoint) * d, so the values are roughly zero-mean with standard
+    deviation ~ amp / sqrt(row_len), the magnitude of the Q4_0 / Q5_0 tensors."""
+    be, bb = GGML_TYPES[ttype]
+    nblk = n_rows * (row_len // be)
+    blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
+    rms, mid = {Q4_1: (4.6, 7.5), Q5_1: (9.2, 15.5)}[ttype]      # of the unsigned quants about their midpoint, drawn uniformly
+    d = (amp / np.sqrt(row_len) / rms) * rng.uniform(0.5, 1.5, size=nblk) * np.where(rng.random(nblk) < 0.25, -1.0, 1.0)
+    m = -d * (mid + rng.uniform(-0.25 * mid, 0.25 * mid, size=nblk))
+    blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    blk[:, 2:4] = m.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    return blk.reshape(-1)
+
+
 def q8_0_type(name, il, n_layer):
     """llama.cpp's Q8_0 recipe (llama_tensor_get_type, llama.cpp:15464-15480, :15618-15624): every matrix Q8_0, output.weight and token_embd included."""
     return Q8_0
@@ -247,6 +267,26 @@ def q4_0_type(name, il, n_layer):
 def q5_0_type(name, il, n_layer):
     """llama.cpp's Q5_0 recipe: as q4_0_type with Q5_0."""
     return Q6_K if name == "output" else Q5_0
+
+
+def q4_1_type(name, il, n_layer):
+    """llama.cpp's Q4_1 recipe: as q4_0_type with Q4_1 (output.weight Q6_K, llama.cpp:15464-15480)."""
+    return Q6_K if name == "output" else Q4_1
+
+
+def q5_1_type(name, il, n_layer):
+    """llama.cpp's Q5_1 recipe (the default ftype of llama_model_quantize_default_params): as q4_0_type with Q5_1."""
+    return Q6_K if name == "output" else Q5_1
+
+
+def q4_0_imatrix_type(name, il, n_layer):
+    """llama.cpp's Q4_0 recipe WITH an importance matrix: as q4_0_type, but ffn_down of the first n_layer / 8 layers is Q4_1 (llama.cpp:15618-15624)."""
+    return Q4_1 if name == "ffn_down" and il < n_layer // 8 else q4_0_type(name, il, n_layer)
+
+
+def q5_0_imatrix_type(name, il, n_layer):
+    """llama.cpp's Q5_0 recipe with an importance matrix: as q5_0_type, but ffn_down of the first n_layer / 8 layers is Q5_1."""
+    return Q5_1 if name == "ffn_down" and il < n_layer // 8 else q5_0_type(name, il, n_layer)
 
 
 def q4_k_m_type(name, il, n_layer):
@@ -296,7 +336,7 @@ def q2_k_type(name, il, n_layer, n_gqa=4):
 
 def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_ctx_train=8192, seed=7,
                           type_fn=None, rope_freqs=False, embd_type=Q4_K, reuse_layers=False, vocab=None, n_split=0, rope_scaling=None, tied=False):
-    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q5_0 / Q8_0) blocks.
+    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0) blocks.
     reuse_layers: generate each (tensor kind, type) once and reuse the bytes in every layer (fast path for the
     multi-GB benchmark model; the arithmetic and the bytes streamed per token are unchanged).
     tied: no output.weight — the reader falls back to token_embd.weight (Llama-3.2; llama.cpp:6070-6076)."""
@@ -319,7 +359,7 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
         if not reuse_layers:
             return None
         be, bb = GGML_TYPES[t]; nb = cols // be
-        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32, Q4_0: 2, Q5_0: 6, Q8_0: 2}[t]      # qs / qs / ql / qs / qs / qs / qs / qs
+        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32, Q4_0: 2, Q5_0: 6, Q8_0: 2, Q4_1: 4, Q5_1: 8}[t]      # qs / qs / ql / qs / qs / qs / qs / qs / qs / qs
         n = min(64, rows)
         return ([(k * rows // n) * nb * bb + qoff + (k % 32) for k in range(n)], il + 1)
 

@@ -207,6 +207,8 @@ int bamd_bench_matvec(int type, int nrows, int k, int pro, int epi, int mode, in
 int bamd_op_quantize_q8_K(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks);
 /* the same for the activation form of Q8_0 / Q4_0 / Q5_0 weights: k / 32 block_q8_0 {f16 d, i8 qs[32]}, 34 bytes each (quantize_row_q8_0) */
 int bamd_op_quantize_q8_0(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks);
+/* and of Q4_1 / Q5_1 weights: k / 32 block_q8_1 {f16 d, f16 s, i8 qs[32]}, 36 bytes each (quantize_row_q8_1) */
+int bamd_op_quantize_q8_1(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks);
 /* y[nrows] = W . Q8_K(act) (+ residual), W = GGUF-layout blocks [nrows][k] of `type`  (ggml_compute_forward_mul_mat, ggml.c:12277) */
 int bamd_op_mul_mat_vec(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w, float eps,
                         const float * residual, float * y, int mode /* 0 auto, 1 wave-per-row-group, 2 split-K */);

@@ -5,6 +5,11 @@ five repetitions each after a warm-up, ALTERNATING between the two; the Q4_K_M f
 the switched-off maximum by more than the switched-off spread.
 
     python tools/legacy_decode.py [--prompt 2048] [--only-prompt]
+
+--legacy1: the Q4_1 and Q5_1 recipes instead (full depth, synthetic files of tests/golden/gen_legacy1_fixtures.py's writer) beside Q4_0 and Q4_K_M; their prompts
+run on the integer-dot kernel only (no matrix-core kernel, no switch), so the prompt lines are single rates.
+
+    python tools/legacy_decode.py --legacy1 [--prompt 2048]
 """
 import importlib.util
 import os
@@ -54,7 +59,27 @@ def prompt_pair(path, n_prompt, reps=5):
     return rates[0], rates[1], aux
 
 
+def main_legacy1():
+    _s = importlib.util.spec_from_file_location("gen_legacy1_fixtures", os.path.join(ROOT, "tests", "golden", "gen_legacy1_fixtures.py"))
+    g1 = importlib.util.module_from_spec(_s)
+    _s.loader.exec_module(g1)
+    g1.CONFIGS["8b_q4_1"] = (g1.L3_8B, "q4_1", 128, 64, 512)                   # models only: no fixture of them is stored
+    g1.CONFIGS["8b_q5_1"] = (g1.L3_8B, "q5_1", 128, 64, 512)
+    files = [("Q4_K_M", q4_k_m_file()), ("Q4_0", gen.ensure_model("8b_q4_0")), ("Q4_1", g1.ensure_model("8b_q4_1")), ("Q5_1", g1.ensure_model("8b_q5_1"))]
+    for name, p in files:
+        r = decode_rate(p)
+        print("decode %-7s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, statistics.median(r), min(r), max(r)), flush=True)
+    if "--prompt" in sys.argv:
+        n = int(sys.argv[sys.argv.index("--prompt") + 1])
+        for name, p in files:
+            r, aux = prompt_rate(p, n, reps=5)
+            print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
+                  "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+
+
 def main():
+    if "--legacy1" in sys.argv:
+        return main_legacy1()
     files = [("Q4_K_M", q4_k_m_file()), ("Q8_0", gen.ensure_model("8b_q8_0")), ("Q4_0", gen.ensure_model("8b_q4_0")), ("Q5_0", gen.ensure_model("8b_q5_0"))]
     for name, p in [] if "--only-prompt" in sys.argv else files:
         r = decode_rate(p)
