@@ -59,6 +59,7 @@ def lib():
         L.bamd_set_prefill_batch.argtypes = [ci]; L.bamd_set_prefill_batch.restype = None
         L.bamd_set_prefill_lowbit.argtypes = [ci]; L.bamd_set_prefill_lowbit.restype = None
         L.bamd_set_prefill_q0.argtypes = [ci]; L.bamd_set_prefill_q0.restype = None
+        L.bamd_set_prefill_q1.argtypes = [ci]; L.bamd_set_prefill_q1.restype = None
         L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong
         L.bamd_model_prefill_aux_bytes.argtypes = [vp]; L.bamd_model_prefill_aux_bytes.restype = i64
         L.bamd_bench_matvec.argtypes = [ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)]
@@ -110,6 +111,13 @@ def set_prefill_q0(on):
     """True: models loaded from now on build side tables for their Q8_0 / Q4_0 / Q5_0 layer matrices and evaluate prompts on the matrix-core kernel of these types;
     False (default, also env BAMD_PREFILL_Q0): such a model evaluates prompts on the integer-dot kernel.  Same bits either way."""
     lib().bamd_set_prefill_q0(int(bool(on)))
+
+
+def set_prefill_q1(on):
+    """True: models loaded from now on build side tables for their Q4_1 / Q5_1 layer matrices and evaluate prompts on the matrix-core kernel of these types;
+    False (default, also env BAMD_PREFILL_Q1): such a model evaluates prompts on the integer-dot kernel.  Independent of set_prefill_q0: a Q4_0 / Q5_0 file made
+    with an importance matrix holds Q4_1 / Q5_1 ffn_down matrices and needs both switches on to get tables.  Same bits either way."""
+    lib().bamd_set_prefill_q1(int(bool(on)))
 
 
 def prefill_mfma_runs(t):

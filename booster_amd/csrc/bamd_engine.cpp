@@ -817,7 +817,10 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     }
     size_t need = 0;
     for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
-        m->aux_why = bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+        // (with every switch off the reasons read as they did before the switches existed; with one of BAMD_PREFILL_Q0 / BAMD_PREFILL_Q1 on, the one that is missing is named)
+        m->aux_why = bamd_is_q1(it.type) && bamd_prefill_q0() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_Q0 covers only its Q4_0 / Q5_0 / Q8_0 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                   : bamd_is_q0(it.type) && bamd_prefill_q1() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_Q1 covers only its Q4_1 / Q5_1 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                   : bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q0(it.type) ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_kquant(it.type) && !bamd_prefill_mfma_type(it.type) ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                                                                   : "a matrix type / shape without a matrix-core kernel";
@@ -855,7 +858,7 @@ static int ensure_batch_buffers(bamd_context * c) {
         dev_alloc(c->allocs, (void **) &c->bqkv, T * (m->E + 2 * Ekv) * 4) || dev_alloc(c->allocs, (void **) &c->batt, T * m->E * 4) ||
         dev_alloc(c->allocs, (void **) &c->bh, T * m->F * 4) ||
         dev_alloc(c->allocs, (void **) &c->bblob, T * bamd_blob_bytes(std::max(m->E, m->F))) ||
-        dev_alloc(c->allocs, (void **) &c->bblob16, T * bamd_blob16_bytes(std::max(m->E, m->F)))) return 1;
+        dev_alloc(c->allocs, (void **) &c->bblob16, T * bamd_blob16_bytes(std::max(m->E, m->F)))) return 1;     // (one stride for every form: the K-quant record's 608 B hold the 544 B of the Q8_0 form and the 576 B of the Q8_1 form)
     c->bcap = (int) T;
     return 0;
 }

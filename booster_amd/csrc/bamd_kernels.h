@@ -103,13 +103,13 @@ void bamd_launch_k_shift(unsigned short * kc, int n_cells, int Hkv, int hd, cons
 size_t bamd_blob_bytes(int K);
 size_t bamd_blob16_bytes(int K);
 // blob: int8 activations for matmul_batch_kernel (may be null); blob16: f16 copy for the MFMA kernel (may be null)
-// form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_1 form of the same size (bamd_prefill_q1.hip), blob16
-// is not written; BAMD_ACT_Q8_0: the consuming mat-mul has Q8_0 / Q4_0 / Q5_0 weights — blob takes the Q8_0 form of the same size (bamd_prefill_q0.hip); blob16 is written, in the
+// form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_1 form of the same size (bamd_prefill_q1.hip); blob16
+// is written, in the f16 form of bamd_prefill2_q1.hip (576 bytes of a record, the same stride), only while the switch bamd_prefill_q1() is on; BAMD_ACT_Q8_0: the consuming mat-mul has Q8_0 / Q4_0 / Q5_0 weights — blob takes the Q8_0 form of the same size (bamd_prefill_q0.hip); blob16 is written, in the
 // f16 form of bamd_prefill2_q0.hip and with the same per-token stride, only while the switch bamd_prefill_q0() is on (otherwise nothing reads it)
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K);
 void bamd_launch_quantize_batch_q0(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
 int  bamd_launch_matmul_batch_q0(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);           // every segment Q8_0 / Q4_0 / Q5_0, a.blob in the Q8_0 form; 1 = shape not supported
-void bamd_launch_quantize_batch_q1(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s);
+void bamd_launch_quantize_batch_q1(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
 int  bamd_launch_matmul_batch_q1(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);           // every segment Q4_1 / Q5_1, a.blob in the Q8_1 form; 1 = shape not supported
 // K-quant matrices on the matrix cores, exact (bamd_prefill2.hip): y[t][row] = W[row,:] . Q8_K(a_t); epi BAMD_EPI_STORE: out = y; BAMD_EPI_ADD: out = y + res;
 // BAMD_EPI_SILU_MUL: out = silu(res) * y (res = the gate projection, may alias out).  The A fragments are built once per 64-row x 64-token workgroup from the
@@ -119,10 +119,15 @@ int  bamd_prefill_mfma_supported(void);      // the current device accepts the k
 // Q3_K / Q2_K are behind the process-wide switch bamd_prefill_lowbit() (BAMD_PREFILL_LOWBIT=1 / bamd_set_prefill_lowbit; default off): a model builds their
 // tables, or not, with the value it finds at load
 // Q8_0 / Q4_0 / Q5_0 (bamd_prefill2_q0.hip) are behind a switch of the same shape, bamd_prefill_q0() (BAMD_PREFILL_Q0=1 / bamd_set_prefill_q0; default off)
+// Q4_1 / Q5_1 (bamd_prefill2_q1.hip) are behind a third switch of that shape, bamd_prefill_q1() (BAMD_PREFILL_Q1=1 / bamd_set_prefill_q1; default off), independent of
+// bamd_prefill_q0().  Side tables are all-or-nothing per model, and llama.cpp writes Q4_0 / Q5_0 files made with an importance matrix with Q4_1 / Q5_1 ffn_down
+// matrices in their first layers: such a file needs BOTH switches on to get tables; with one of them it runs on the integer-dot kernel like with none
 int  bamd_prefill_lowbit(void);
 int  bamd_prefill_q0(void);
+int  bamd_prefill_q1(void);
 static inline bool bamd_prefill_mfma_type(int type) {
-    return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit()) || (bamd_is_q0(type) && bamd_prefill_q0());      // Q4_1 / Q5_1: none
+    return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit()) || (bamd_is_q0(type) && bamd_prefill_q0()) ||
+           (bamd_is_q1(type) && bamd_prefill_q1());
 }
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
@@ -132,6 +137,11 @@ int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type,
 size_t bamd_prefill_aux_bytes_q0(int nrows_pad, int K);
 void bamd_launch_prefill_aux_q0(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma_q0(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
+                                int epi, int ldo, hipStream_t s);
+// the Q4_1 / Q5_1 side of them (bamd_prefill2_q1.hip)
+size_t bamd_prefill_aux_bytes_q1(int nrows_pad, int K);
+void bamd_launch_prefill_aux_q1(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
+int  bamd_launch_matmul_mfma_q1(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                                 int epi, int ldo, hipStream_t s);
 int  bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);      // 1 = shape not supported
 void bamd_launch_embed_batch(const int32_t * tokens, int T, const void * embd, int embd_type, int E, int V, float * x, hipStream_t s);

@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(256) embed_batch_kernel(const int32_t * __rest
 size_t bamd_blob_bytes(int K) { return BAMD_BLOB_BYTES(K >> 8); }
 size_t bamd_blob16_bytes(int K) { return BAMD_BLOB16_BYTES(K >> 8); }
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form) {
-    if (form == BAMD_ACT_Q8_1) { bamd_launch_quantize_batch_q1(x, nw, eps, K, T, blob, s); return; }
+    if (form == BAMD_ACT_Q8_1) { bamd_launch_quantize_batch_q1(x, nw, eps, K, T, blob, s, bamd_prefill_q1() ? blob16 : nullptr); return; }
     if (form == BAMD_ACT_Q8_0) { bamd_launch_quantize_batch_q0(x, nw, eps, K, T, blob, s, bamd_prefill_q0() ? blob16 : nullptr); return; }
     if (nw) hipLaunchKernelGGL((quantize_batch_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
     else    hipLaunchKernelGGL((quantize_batch_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);

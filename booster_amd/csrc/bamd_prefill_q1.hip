@@ -1,13 +1,18 @@
 // bamd_prefill_q1.hip — batched prompt evaluation for Q4_1 / Q5_1 weights: per-token Q8_1 quantisation into the activation blob and the integer-dot batched
 // mat-mul (the counterpart of bamd_prefill_q0.hip, whose loop this is).  Per (row, token) the arithmetic is exactly the single-token pair of chains of
 // bamd_q1_device.h: the reference quantises every activation row to Q8_1 and calls ggml_vec_dot_q4_1_q8_1 / _q5_1_q8_1 per output element, for one token and
-// for many (llamafile_sgemm has no case for these types, sgemm.cpp:961-1007).  These types have no matrix-core kernel.
+// for many (llamafile_sgemm has no case for these types, sgemm.cpp:961-1007).  The matrix-core kernel of these types is bamd_prefill2_q1.hip, behind a switch
+// (bamd_prefill_mfma_type); this file also writes its f16 activation records.
 #include "bamd_q1_device.h"
 
 // one workgroup per token: RMSNorm (optional) + Q8_1 of row t of x[T][K] -> blob[t], the LDS image of the mat-vec prologue (q8 | the blocks' {f16 d, f16 s}
-// pairs), with the stride of the Q8_K / Q8_0 blobs
+// pairs), with the stride of the Q8_K / Q8_0 blobs.
+// blob16 (may be null): the same values for the matrix-core kernel, per 256 values one BAMD_B16_REC record of which 576 bytes are used — the Q8_0 form of
+// quantize_batch_q0_kernel (512 B of quants as exact f16 in the order the A operand reads them, the eight d_x as f32 at byte 512), then the eight s_x as f32 at
+// byte 544.  s_x is the f16 s of the image widened: finish_q0<true> rounded it twice (d to f16, the product to f16), and it is not computed again here
 template <bool NORM>
-__global__ void __launch_bounds__(512) quantize_batch_q1_kernel(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, uint8_t * __restrict__ blob) {
+__global__ void __launch_bounds__(512) quantize_batch_q1_kernel(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, uint8_t * __restrict__ blob,
+                                                                uint8_t * __restrict__ blob16) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int nb = K >> 8, t = blockIdx.x;
     uint32_t * q8 = (uint32_t *) smem; float * ys = (float *) (q8 + nb * 64);
@@ -18,6 +23,21 @@ __global__ void __launch_bounds__(512) quantize_batch_q1_kernel(const float * __
     const size_t bb = BAMD_BLOB_BYTES(nb);
     const uint4 * src = (const uint4 *) smem; uint4 * dst = (uint4 *) (blob + (size_t) t * bb);
     for (int i = threadIdx.x; i < (int) (bb / 16); i += blockDim.x) dst[i] = src[i];
+    if (blob16) {
+        uint8_t * o = blob16 + (size_t) t * BAMD_BLOB16_BYTES(nb);
+        for (int i = threadIdx.x; i < nb * 64; i += blockDim.x) {          // q8[ci*64 + e*8 + c] = block c, chunk e, 4 int8 (never -128)
+            const int ci = i >> 6, e = (i >> 3) & 7, c = i & 7;
+            const uint32_t w = q8[i];
+            const unsigned short h0 = f2h((float) (int8_t) (w)), h1 = f2h((float) (int8_t) (w >> 8)), h2 = f2h((float) (int8_t) (w >> 16)), h3 = f2h((float) (int8_t) (w >> 24));
+            uint2 v; v.x = (uint32_t) h0 | ((uint32_t) h1 << 16); v.y = (uint32_t) h2 | ((uint32_t) h3 << 16);
+            *(uint2 *) (o + (size_t) ci * BAMD_B16_REC + c * 64 + (e & 3) * 16 + (e >> 2) * 8) = v;
+        }
+        const uint32_t * yp = (const uint32_t *) ys;                       // {f16 d, f16 s} of block i
+        for (int i = threadIdx.x; i < nb * 8; i += blockDim.x) {
+            float * rec = (float *) (o + (size_t) (i >> 3) * BAMD_B16_REC + 512);
+            rec[i & 7] = h2f(yp[i] & 0xffffu); rec[8 + (i & 7)] = h2f(yp[i] >> 16);
+        }
+    }
 }
 
 template <int TYPE, int D, int EPI, int TT>
@@ -135,9 +155,9 @@ __global__ void __launch_bounds__(512) matmul_batch_q1_kernel(bamd_mm_args a) {
 // ===========================================================================================================
 // launchers
 // ===========================================================================================================
-void bamd_launch_quantize_batch_q1(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s) {
-    if (nw) hipLaunchKernelGGL((quantize_batch_q1_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob);
-    else    hipLaunchKernelGGL((quantize_batch_q1_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob);
+void bamd_launch_quantize_batch_q1(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16) {
+    if (nw) hipLaunchKernelGGL((quantize_batch_q1_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
+    else    hipLaunchKernelGGL((quantize_batch_q1_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
 }
 // every segment Q4_1 / Q5_1; a.blob in the Q8_1 form (bamd_launch_quantize_batch_q1).  1 = shape not supported
 int bamd_launch_matmul_batch_q1(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s) {

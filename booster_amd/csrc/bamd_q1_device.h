@@ -1,5 +1,5 @@
 // bamd_q1_device.h — device code shared by the kernels of the 32-weight block formats with a minimum, Q4_1 / Q5_1 (bamd_matvec_q1.hip: single-token mat-vec;
-// bamd_prefill_q1.hip: batched prompt mat-mul): the wave-stream records (layout: bamd_formats.h), their block terms and the two chains.  The Q8_1 activation
+// bamd_prefill_q1.hip: batched prompt mat-mul on the integer-dot kernel; the matrix-core one, bamd_prefill2_q1.hip, restates the chains for its own lane layout): the wave-stream records (layout: bamd_formats.h), their block terms and the two chains.  The Q8_1 activation
 // prologue is ActProQ0's with Q1 = true (bamd_q0_device.h): the Q8_0 image, with the block's {f16 d, f16 s} pair in the 4-byte slot that holds d widened there.
 //
 // NUMERICS (contract: bamd_device.h).  Reference functions restated here (cpp/ = the reference tree):

@@ -185,7 +185,11 @@ void bamd_set_prefill_lowbit(int on);
  * its prompts on the integer-dot kernel; 1 = side tables (the rows' block scales as f32, 32 B per row and 256 weights) and a matrix-core kernel of their own.
  * Taken at model load, like bamd_set_prefill_lowbit.  Bit-identical results. */
 void bamd_set_prefill_q0(int on);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 2 Q4_0, 6 Q5_0, 8 Q8_0, 10 Q2_K .. 14 Q6_K) since the library was loaded */
+/* And for Q4_1 / Q5_1 weights (env BAMD_PREFILL_Q1): 0 (default) = as above; 1 = side tables (the rows' block scales and minima as f32, 64 B per row and 256
+ * weights) and a matrix-core kernel of their own.  Independent of bamd_set_prefill_q0.  Side tables are all-or-nothing per model: a Q4_0 / Q5_0 file made with
+ * an importance matrix holds Q4_1 / Q5_1 ffn_down matrices and gets tables only with both switches on.  Taken at model load.  Bit-identical results. */
+void bamd_set_prefill_q1(int on);
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */

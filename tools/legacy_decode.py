@@ -6,10 +6,11 @@ the switched-off maximum by more than the switched-off spread.
 
     python tools/legacy_decode.py [--prompt 2048] [--only-prompt]
 
---legacy1: the Q4_1 and Q5_1 recipes instead (full depth, synthetic files of tests/golden/gen_legacy1_fixtures.py's writer) beside Q4_0 and Q4_K_M; their prompts
-run on the integer-dot kernel only (no matrix-core kernel, no switch), so the prompt lines are single rates.
+--legacy1: the Q4_1 and Q5_1 recipes instead (full depth, synthetic files of tests/golden/gen_legacy1_fixtures.py's writer) beside Q4_0 and Q4_K_M.  Their prompt
+lines alternate set_prefill_q1(False) / (True) like the lines above, and two more lines take the Q4_0 file made with an importance matrix (ffn_down of its first
+four layers is Q4_1): once with both switches on against both off, once with only set_prefill_q0(True) — no side tables, so it must read like switched off.
 
-    python tools/legacy_decode.py --legacy1 [--prompt 2048]
+    python tools/legacy_decode.py --legacy1 [--prompt 2048] [--only-prompt]
 """
 import importlib.util
 import os
@@ -30,33 +31,45 @@ _spec.loader.exec_module(gen)
 gen.CONFIGS.setdefault("8b_q5_0", (gen.L3_8B, "q5_0", 128, 64, 512))          # a model only: no fixture of it is stored
 
 
-def prompt_pair(path, n_prompt, reps=5):
-    """switched-off and switched-on rates of one file, alternating: ([off], [on], side-table bytes of the switched-on model)"""
-    b.set_prefill_q0(False); m0 = b.Model(path)
-    b.set_prefill_q0(True)
+def set_switches(q0, q1):
+    b.set_prefill_q0(bool(q0)); b.set_prefill_q1(bool(q1))
+
+
+def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True):
+    """switched-off and switched-on rates of one file, alternating: ([off], [on], side-table bytes of the switched-on model).  q0 / q1: what "on" sets;
+    tables: whether "on" is enough for this file to get side tables"""
+    set_switches(False, False); m0 = b.Model(path)
+    set_switches(q0, q1)
     try:
         m1 = b.Model(path)
     finally:
-        b.set_prefill_q0(False)                                 # a model keeps the tables it built at load
-    assert m0.prefill_aux_bytes() == 0 and m1.prefill_aux_bytes() > 0
+        set_switches(False, False)                              # a model keeps the tables it built at load
+    assert m0.prefill_aux_bytes() == 0 and (m1.prefill_aux_bytes() > 0) == tables
     ctxs = [b.Context(m0, 4096), b.Context(m1, 4096)]
     prompt = [(7919 * i + 13) % m0.n_vocab for i in range(n_prompt)]
     rates = ([], [])
     for rep in range(reps + 1):                                 # the first pair warms up
         for k, ctx in enumerate(ctxs):
-            b.set_prefill_q0(bool(k))                           # the routing asks the switch as well as the tables
+            set_switches(q0 and k, q1 and k)                    # the routing asks the switches as well as the tables
             b.lib().bamd_kv_cache_clear(ctx.h)
             t0 = time.perf_counter()
             for i in range(0, n_prompt, 512):
                 ctx.decode(prompt[i:i + 512], i)
             if rep:
                 rates[k].append(n_prompt / (time.perf_counter() - t0))
-    b.set_prefill_q0(False)
+    set_switches(False, False)
     aux = m1.prefill_aux_bytes()
     for c in ctxs:
         c.close()
     m0.close(); m1.close()
     return rates[0], rates[1], aux
+
+
+def print_pair(name, n, off, on, aux):
+    bar = max(off) + (max(off) - min(off))
+    print("prompt %-7s %d tokens: switch off median %7.1f tok/s (range %.1f - %.1f; integer-dot kernel) | switch on median %7.1f tok/s (range %.1f - %.1f; %s, "
+          "side tables %.2f GiB) | x %.2f | bar (off max + off spread) %.1f: %s" % (name, n, statistics.median(off), min(off), max(off), statistics.median(on), min(on), max(on),
+          "matrix-core kernel" if aux > 0 else "integer-dot kernel", aux / 2 ** 30, statistics.median(on) / statistics.median(off), bar, "cleared" if statistics.median(on) > bar else "NOT cleared"), flush=True)
 
 
 def main_legacy1():
@@ -65,16 +78,23 @@ def main_legacy1():
     _s.loader.exec_module(g1)
     g1.CONFIGS["8b_q4_1"] = (g1.L3_8B, "q4_1", 128, 64, 512)                   # models only: no fixture of them is stored
     g1.CONFIGS["8b_q5_1"] = (g1.L3_8B, "q5_1", 128, 64, 512)
-    files = [("Q4_K_M", q4_k_m_file()), ("Q4_0", gen.ensure_model("8b_q4_0")), ("Q4_1", g1.ensure_model("8b_q4_1")), ("Q5_1", g1.ensure_model("8b_q5_1"))]
-    for name, p in files:
+    g1.CONFIGS["8b_q4_0_imat"] = (g1.L3_8B, "q4_0_imatrix", 128, 64, 512)
+    only_prompt = "--only-prompt" in sys.argv
+    files = [("Q4_K_M", q4_k_m_file())] + ([] if only_prompt else [("Q4_0", gen.ensure_model("8b_q4_0"))]) + [("Q4_1", g1.ensure_model("8b_q4_1")), ("Q5_1", g1.ensure_model("8b_q5_1"))]
+    for name, p in [] if only_prompt else files:
         r = decode_rate(p)
         print("decode %-7s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, statistics.median(r), min(r), max(r)), flush=True)
     if "--prompt" in sys.argv:
         n = int(sys.argv[sys.argv.index("--prompt") + 1])
-        for name, p in files:
+        for name, p in [f for f in files if f[0] in ("Q4_K_M", "Q4_0")]:
             r, aux = prompt_rate(p, n, reps=5)
             print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
                   "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+        for name, p in [f for f in files if f[0] in ("Q4_1", "Q5_1")]:
+            print_pair(name, n, *prompt_pair(p, n, q0=False, q1=True))
+        p = g1.ensure_model("8b_q4_0_imat")
+        print_pair("Q4_0 imatrix, both switches", n, *prompt_pair(p, n, q0=True, q1=True))
+        print_pair("Q4_0 imatrix, BAMD_PREFILL_Q0 only", n, *prompt_pair(p, n, q0=True, q1=False, tables=False))
 
 
 def main():
@@ -89,11 +109,7 @@ def main():
         r, _ = prompt_rate(files[0][1], n, reps=5)
         print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; matrix-core kernels)" % (files[0][0], n, statistics.median(r), min(r), max(r)), flush=True)
         for name, p in files[1:]:
-            off, on, aux = prompt_pair(p, n)
-            bar = max(off) + (max(off) - min(off))
-            print("prompt %-7s %d tokens: switch off median %7.1f tok/s (range %.1f - %.1f; integer-dot kernel) | switch on median %7.1f tok/s (range %.1f - %.1f; matrix-core kernel, "
-                  "side tables %.2f GiB) | x %.2f | bar (off max + off spread) %.1f: %s" % (name, n, statistics.median(off), min(off), max(off), statistics.median(on), min(on), max(on),
-                  aux / 2 ** 30, statistics.median(on) / statistics.median(off), bar, "cleared" if statistics.median(on) > bar else "NOT cleared"), flush=True)
+            print_pair(name, n, *prompt_pair(p, n))
 
 
 if __name__ == "__main__":

@@ -2,6 +2,8 @@
 
     python tools/prefill_profile.py [tokens] [8b_q3_k_m | 8b_q2_k]      a low-bit file: with set_prefill_lowbit(True), its prompts on the matrix-core Q3_K / Q2_K kernels
     python tools/prefill_profile.py [tokens] [8b_q8_0 | 8b_q4_0 | 8b_q5_0]   a legacy-quant file: with set_prefill_q0(True), its prompts on the Q8_0 / Q4_0 / Q5_0 matrix-core kernel
+    python tools/prefill_profile.py [tokens] [8b_q4_1 | 8b_q5_1 | 8b_q4_0_imat]   with set_prefill_q1(True) (8b_q4_0_imat: both switches), on the Q4_1 / Q5_1 matrix-core kernel
+    a trailing "off" leaves the switches off: the same prompts on the integer-dot kernels
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,13 +13,21 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 if len(sys.argv) > 2:
     import importlib.util
     legacy = sys.argv[2] in ("8b_q8_0", "8b_q4_0", "8b_q5_0")
-    name = "gen_legacy_fixtures" if legacy else "gen_lowbit_fixtures"
+    legacy1 = sys.argv[2] in ("8b_q4_1", "8b_q5_1", "8b_q4_0_imat")
+    name = "gen_legacy_fixtures" if legacy else "gen_legacy1_fixtures" if legacy1 else "gen_lowbit_fixtures"
     spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", name + ".py"))
     gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
     if legacy:
         gen.CONFIGS.setdefault("8b_q5_0", (gen.L3_8B, "q5_0", 128, 64, 512))          # a model only: no fixture of it is stored
+    if legacy1:
+        gen.CONFIGS.setdefault(sys.argv[2], (gen.L3_8B, {"8b_q4_1": "q4_1", "8b_q5_1": "q5_1", "8b_q4_0_imat": "q4_0_imatrix"}[sys.argv[2]], 128, 64, 512))
     path = gen.ensure_model(sys.argv[2])
-    b.set_prefill_q0(True) if legacy else b.set_prefill_lowbit(True)
+    if sys.argv[-1] == "off":
+        pass
+    elif legacy1:
+        b.set_prefill_q1(True); b.set_prefill_q0(sys.argv[2] == "8b_q4_0_imat")
+    else:
+        b.set_prefill_q0(True) if legacy else b.set_prefill_lowbit(True)
 else:
     path = "/dev/shm/bamd_prefill_8b.gguf"
     if not os.path.exists(path):
