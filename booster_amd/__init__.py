@@ -60,6 +60,8 @@ def lib():
         L.bamd_set_prefill_lowbit.argtypes = [ci]; L.bamd_set_prefill_lowbit.restype = None
         L.bamd_set_prefill_q0.argtypes = [ci]; L.bamd_set_prefill_q0.restype = None
         L.bamd_set_prefill_q1.argtypes = [ci]; L.bamd_set_prefill_q1.restype = None
+        L.bamd_set_attn_scratch_mb.argtypes = [ci]; L.bamd_set_attn_scratch_mb.restype = None
+        L.bamd_attention_batch_plan.argtypes = [ci, ci, ci, ci, ci, ci, C.c_size_t, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
         L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong
         L.bamd_model_prefill_aux_bytes.argtypes = [vp]; L.bamd_model_prefill_aux_bytes.restype = i64
         L.bamd_bench_matvec.argtypes = [ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)]
@@ -73,6 +75,7 @@ def lib():
         L.bamd_op_get_row.argtypes = [ci, vp, ci, ci, ci, vp]
         L.bamd_op_attention.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
         L.bamd_op_attention_batch.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
+        L.bamd_op_attention_batch_ex.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, C.c_size_t, vp, C.POINTER(ci)]
         L.bamd_op_rope_row.argtypes = [ci, ci, cf, cf, vp, vp]
         L.bamd_op_k_shift.argtypes = [vp, ci, ci, ci, vp, cf, cf, vp, cf, cf, ci]
         L.bamd_op_attention_cells.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
@@ -118,6 +121,20 @@ def set_prefill_q1(on):
     False (default, also env BAMD_PREFILL_Q1): such a model evaluates prompts on the integer-dot kernel.  Independent of set_prefill_q0: a Q4_0 / Q5_0 file made
     with an importance matrix holds Q4_1 / Q5_1 ffn_down matrices and needs both switches on to get tables.  Same bits either way."""
     lib().bamd_set_prefill_q1(int(bool(on)))
+
+
+def set_attn_scratch_mb(mb):
+    """budget in MiB of a context's batched-attention scratch block (also env BAMD_ATTN_SCRATCH_MB); 0 = the default, H x 512 x 18432 x 4 bytes.  A micro-batch whose
+    score rows exceed it is attended in token slices that reuse the block.  Same bits at every setting."""
+    lib().bamd_set_attn_scratch_mb(int(mb))
+
+
+def attention_batch_plan(Hkv, gq, hd, T, ld, impl=0, budget_bytes=0):
+    """the slice plan of a micro-batch's attention (host only): (tokens per slice, slices, scratch bytes), or None where there is no plan"""
+    tps, ns, sb = C.c_int(0), C.c_int(0), C.c_size_t(0)
+    if lib().bamd_attention_batch_plan(Hkv, gq, hd, T, ld, impl, budget_bytes, C.byref(tps), C.byref(ns), C.byref(sb)) != 0:
+        return None
+    return tps.value, ns.value, sb.value
 
 
 def prefill_mfma_runs(t):
@@ -409,6 +426,20 @@ def op_attention_batch(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, pos
     out = np.zeros((T, H * hd), np.float32)
     _chk(lib().bamd_op_attention_batch(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope), H, Hkv, hd, n_ctx, pos0, T, impl, ld, _p(out)))
     return out
+
+
+def op_attention_batch_ex(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, pos0, impl=0, ld=0, scratch_bytes=0):
+    """op_attention_batch with the scratch budget of the slice plan (0 = the default); returns (out [T][H*hd], attention launches issued)"""
+    q = np.ascontiguousarray(q, np.float32).reshape(-1, H * hd)
+    T = q.shape[0]
+    k = np.ascontiguousarray(k, np.float32).reshape(T, Hkv * hd); v = np.ascontiguousarray(v, np.float32).reshape(T, Hkv * hd)
+    rope = np.ascontiguousarray(rope, np.float32).reshape(n_ctx, hd)
+    assert k_cache.dtype == np.uint16 and v_cache_t.dtype == np.uint16 and k_cache.flags.c_contiguous and v_cache_t.flags.c_contiguous
+    assert k_cache.size == n_ctx * Hkv * hd and v_cache_t.size == n_ctx * Hkv * hd
+    out = np.zeros((T, H * hd), np.float32); ns = C.c_int(0)
+    _chk(lib().bamd_op_attention_batch_ex(_p(q), _p(k), _p(v), _p(k_cache), _p(v_cache_t), _p(rope), H, Hkv, hd, n_ctx, pos0, T, impl, ld, scratch_bytes, _p(out),
+                                          C.byref(ns)))
+    return out, ns.value
 
 
 def _segments(segs):

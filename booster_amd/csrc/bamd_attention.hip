@@ -602,12 +602,48 @@ static void launch_attn_fused(const bamd_attn_args & a, int gq, dim3 grid, size_
     }
 }
 
-// attention of a micro-batch of T tokens (a.batch = 1, a.ld_qkv / a.ld_out set): KV store for all tokens, then (head, token) workgroups
-int bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl) {
-    const int ld = a.lds_ld ? a.lds_ld : a.n_ctx;
-    if (a.hd > 256 || (a.hd & 63) || (ld & 63) || (size_t) ld * 8 > BAMD_ATTN_LDS_MAX || !a.batch) return 1;
-    if (gq < 1 || gq > 8 || impl < 0 || impl > 2) return 1;
-    BAMD_LAUNCH(kv_store_batch_kernel, dim3(a.Hkv, T), dim3(256), 0, s, a);
+// ---- the slice plan of a micro-batch's attention: which kernel, how many tokens per launch, how large a scratch block -----------------------------------------
+// The ONE place this is written down (as bamd_batch_mm is for the mat-mul routing): the launcher below, the engine's allocation and the op-level entry point
+// all ask here.  Host code, no device.
+//   kernel   head_dim 128, gq 1 / 2 / 4 / 8, T >= 2, impl != 1: the matrix-core kernel — LONG (scratch block) beyond BAMD_AM_MAXPOS = 512 positions;
+//            else while two rows of ld floats fit BAMD_ATTN_LDS_MAX: the VALU kernels with their rows in LDS (no scratch); else attn_batch_gs_kernel (scratch block; bamd_attention_gs.hip)
+//   tile     the tokens a workgroup row of the grid covers: 16 / gq (matrix cores) or 1 (VALU); a tile's workgroups (one per KV head) take gq x tile x ld floats
+//            each = Hkv x gq x tile x ld x 4 bytes per tile.  A slice is a whole number of tiles; slices are balanced (ceil(tiles / n) each).
+//   budget   bytes the scratch block may take; 0 = the default: Hkv x gq x 512 x 18432 x 4, the scratch of a 512-token micro-batch at ld 18432 — the most a
+//            context could ask for before the plan existed, so with it every ld <= 18432 is ONE slice of the size bamd_attention_batch_mfma_scratch gives.
+// 1 = no plan: bad shape, impl 2 where the matrix-core kernel declines, or a budget that cannot hold one tile (it does not loop).  Where the rows still fit the
+// LDS and the budget cannot hold a matrix-core tile, impl 0 plans the VALU kernels (scratch 0): what runs when the block cannot be allocated.
+#define BAMD_ATTN_PLAN_T 512
+#define BAMD_ATTN_PLAN_LD 18432
+static bool attn_batch_on_mfma(int gq, int hd, int T, int impl) {
+    return impl != 1 && bamd_attention_batch_mfma_on() && hd == 128 && T >= 2 && (gq == 1 || gq == 2 || gq == 4 || gq == 8);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_attention_batch_plan(int Hkv, int gq, int hd, int T, int ld, int impl, size_t budget_bytes, int * tokens_per_slice,
+                                                                                 int * n_slices, size_t * scratch_bytes) {
+    if (Hkv < 1 || gq < 1 || gq > 8 || hd < 64 || hd > 256 || (hd & 63) || T < 1 || ld < 64 || (ld & 63) || impl < 0 || impl > 2) return 1;
+    const bool lds_ok = (size_t) ld * 8 <= BAMD_ATTN_LDS_MAX, mfma = attn_batch_on_mfma(gq, hd, T, impl);
+    if (impl == 2 && !mfma) return 1;
+    const int tt = mfma ? 16 / gq : 1, ntiles = (T + tt - 1) / tt;
+    const size_t per_tile = mfma ? bamd_attention_batch_mfma_scratch(Hkv, gq, tt, ld) : lds_ok ? 0 : (size_t) Hkv * gq * (size_t) ld * 4;
+    const size_t budget = budget_bytes ? budget_bytes : (size_t) Hkv * gq * BAMD_ATTN_PLAN_T * (size_t) BAMD_ATTN_PLAN_LD * 4;
+    int per_slice = ntiles, ns = 1, tile = tt;
+    size_t need = 0;
+    if (per_tile) {
+        const size_t fit = budget / per_tile;
+        if (fit == 0) { if (!(lds_ok && impl == 0)) return 1; tile = 1; per_slice = T; }   // (the VALU kernels with their rows in LDS: one launch of T tokens, no block)
+        else {
+            if ((size_t) ntiles > fit) { ns = (int) (((size_t) ntiles + fit - 1) / fit); per_slice = (ntiles + ns - 1) / ns; ns = (ntiles + per_slice - 1) / per_slice; }
+            need = (size_t) per_slice * per_tile;
+        }
+    }
+    if (tokens_per_slice) *tokens_per_slice = per_slice * tile;
+    if (n_slices) *n_slices = ns;
+    if (scratch_bytes) *scratch_bytes = need;
+    return 0;
+}
+
+// the launches behind the KV store while the rows fit the LDS and one launch covers the micro-batch
+static int launch_attention_batch_lds(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl, int ld) {
     if (impl != 1 && bamd_launch_attention_batch_mfma(a, gq, T, s) == 0) return 0;   // head_dim 128 (beyond 512 positions with a.batch_scratch): the matrix-core kernel (bamd_attention_mfma.hip)
     if (impl == 2) return 1;
     // as many query heads of a KV head per workgroup as have their score rows fit the LDS (ld floats each: the probabilities replace
@@ -620,6 +656,33 @@ int bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStre
     else if (gqh == 4) BAMD_LAUNCH((attn_batch_kernel<4>), grid, dim3(512), lds_g, s, a, gq);
     else if (gqh == 2) BAMD_LAUNCH((attn_batch_kernel<2>), grid, dim3(512), lds_g, s, a, gq);
     else launch_attn_fused(a, gq, dim3(a.Hkv * gq, T), (size_t) ld * 8, s);
+    return 0;
+}
+// attention of a micro-batch of T tokens (a.batch = 1, a.ld_qkv / a.ld_out set): KV store for all tokens, then (head, token) workgroups — one launch while the
+// rows fit the LDS and the scratch block holds the micro-batch (the launches this function has always made), else token slices by the plan, back to back on the
+// stream, all on the one scratch block: stream order is the only dependency between them, and every token's K / V is in the cache before the first slice
+int bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl, size_t scratch_bytes, int * n_slices) {
+    const int ld = a.lds_ld ? a.lds_ld : a.n_ctx;
+    if (a.hd > 256 || (a.hd & 63) || (ld & 63) || !a.batch) return 1;
+    if (gq < 1 || gq > 8 || impl < 0 || impl > 2 || T < 1) return 1;
+    const bool lds_ok = (size_t) ld * 8 <= BAMD_ATTN_LDS_MAX;
+    bamd_attn_args b = a;
+    int tps = T, ns = 1;
+    if (!lds_ok || (a.batch_scratch && scratch_bytes)) {
+        if (!lds_ok && !(a.batch_scratch && scratch_bytes)) return 1;      // beyond the LDS there is no kernel without a block
+        size_t need = 0;
+        if (bamd_attention_batch_plan(a.Hkv, gq, a.hd, T, ld, impl, scratch_bytes, &tps, &ns, &need)) return 1;   // (nothing launched)
+        if (!need) b.batch_scratch = nullptr;
+    }
+    if (n_slices) *n_slices = ns;
+    BAMD_LAUNCH(kv_store_batch_kernel, dim3(a.Hkv, T), dim3(256), 0, s, a);
+    if (lds_ok && ns == 1) return launch_attention_batch_lds(b, gq, T, s, impl, ld);
+    const bool mfma = attn_batch_on_mfma(gq, a.hd, T, impl);
+    for (int t0 = 0; t0 < T; t0 += tps) {
+        const int Ts = T - t0 < tps ? T - t0 : tps;
+        if (mfma) { if (bamd_launch_attention_batch_mfma(b, gq, T, s, t0, Ts)) return 1; continue; }
+        bamd_launch_attention_batch_gs(b, gq, t0, Ts, s);                  // rows in the scratch block on the VALU (bamd_attention_gs.hip)
+    }
     return 0;
 }
 

@@ -51,7 +51,7 @@ __device__ __forceinline__ float h2f_hi(uint32_t w) { return __half2float(__usho
 // ([16 columns][ld] f32: written by pass 1, exponentiated in place by pass 2) and pass 3 walks them in chunks of BAMD_AM_CHUNK positions staged
 // through LDS; the P.V chains simply continue from chunk to chunk.
 template <int GQ, bool LONG>
-__global__ void __launch_bounds__(64 * BAMD_AM_NW) __attribute__((amdgpu_waves_per_eu(2, 2))) attn_batch_mfma_kernel(bamd_attn_args a, int T, int dbg_exit) {
+__global__ void __launch_bounds__(64 * BAMD_AM_NW) __attribute__((amdgpu_waves_per_eu(2, 2))) attn_batch_mfma_kernel(bamd_attn_args a, int T, int dbg_exit, int tok0) {
     constexpr int hd = 128, L = 16, TT = 16 / GQ, NW = BAMD_AM_NW, NT = 64 * NW, DT = BAMD_AM_DT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned short * q16 = (unsigned short *) smem;                            // [16 columns][128], chain-major (kperm)
@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(64 * BAMD_AM_NW) __attribute__((amdgpu_waves_p
     const bamd_step_state * st = a.st;
     const int Hkv = a.Hkv, Ekv = Hkv * hd, n_ctx = a.n_ctx;
     const int hk = (int) blockIdx.x % Hkv, tile = (int) blockIdx.x / Hkv;      // consecutive workgroups: different KV heads (= different XCDs for Hkv = 8)
-    const int t0 = tile * TT;
+    const int t0 = tok0 + tile * TT;                                         // tok0: first token of this launch's slice of the micro-batch (a multiple of TT); the scratch block is the slice's (blockIdx.x)
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     const int P0 = a.batch_pos0p1 > 0 ? a.batch_pos0p1 - 1 : st->pos;          // (the host knows the micro-batch's first position: no dependent load in front of everything)
     const int tlast = (t0 + TT - 1 < T ? t0 + TT - 1 : T - 1);
@@ -283,9 +283,12 @@ size_t bamd_attention_batch_mfma_scratch(int Hkv, int gq, int T, int ld) {      
     const int tt = 16 / gq;
     return (size_t) Hkv * ((T + tt - 1) / tt) * 16 * (size_t) ld * 4;
 }
-int bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hipStream_t s) {
+int bamd_attention_batch_mfma_on(void) {
     static const bool on = [] { const char * e = getenv("BAMD_ATTN_MFMA"); return !(e && e[0] == '0'); }();
-    if (!on || a.hd != 128 || !a.batch || T < 2) return 1;
+    return on ? 1 : 0;
+}
+int bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hipStream_t s, int t0, int Ts) {
+    if (!bamd_attention_batch_mfma_on() || a.hd != 128 || !a.batch || T < 2) return 1;
     if (gq != 1 && gq != 2 && gq != 4 && gq != 8 && gq != 16) return 1;
     const int npos = a.lds_ld ? a.lds_ld : a.n_ctx;                            // the caller's bound on the padded sequence length of this micro-batch (multiple of 64)
     if ((npos & 63) || npos > a.n_ctx) return 1;
@@ -294,9 +297,11 @@ int bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hi
     static const int dbg = [] { const char * e = getenv("BAMD_AM_EXIT"); return e ? atoi(e) : 0; }();     // timing experiments only: leave the kernel after phase 1 / 2 / 3
     const size_t lds = BAMD_AM_QBYTES + BAMD_AM_VBYTES + BAMD_AM_RBYTES + (size_t) (lng ? BAMD_AM_CHUNK : npos) * 64;
     const int tt = 16 / gq;
-    const dim3 grid(a.Hkv * ((T + tt - 1) / tt)), block(64 * BAMD_AM_NW);
-#define BAMD_AM_GO(GQ_) do { if (lng) hipLaunchKernelGGL((attn_batch_mfma_kernel<GQ_, true>), grid, block, lds, s, a, T, dbg); \
-                             else     hipLaunchKernelGGL((attn_batch_mfma_kernel<GQ_, false>), grid, block, lds, s, a, T, dbg); } while (0)
+    if (Ts <= 0) Ts = T - t0;
+    if (t0 < 0 || t0 % tt || t0 + Ts > T) return 1;
+    const dim3 grid(a.Hkv * ((Ts + tt - 1) / tt)), block(64 * BAMD_AM_NW);
+#define BAMD_AM_GO(GQ_) do { if (lng) hipLaunchKernelGGL((attn_batch_mfma_kernel<GQ_, true>), grid, block, lds, s, a, T, dbg, t0); \
+                             else     hipLaunchKernelGGL((attn_batch_mfma_kernel<GQ_, false>), grid, block, lds, s, a, T, dbg, t0); } while (0)
     switch (gq) {
         case 1: BAMD_AM_GO(1); break;
         case 2: BAMD_AM_GO(2); break;

@@ -38,6 +38,7 @@ static int g_prefill_mfma = [] { const char * e = getenv("BAMD_PREFILL_MFMA"); r
 static const int g_prefill_aux = [] { const char * e = getenv("BAMD_PREFILL_AUX"); return (e && e[0] == '0') ? 0 : 1; }();
 // BAMD_STAGE_GRAPH=0: bamd_stage_step enqueues its kernels one by one instead of replaying a captured hipGraph
 static const int g_stage_graph = [] { const char * e = getenv("BAMD_STAGE_GRAPH"); return (e && e[0] == '0') ? 0 : 1; }();
+static int g_attn_scratch_mb = [] { const char * e = getenv("BAMD_ATTN_SCRATCH_MB"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 0; }();   // budget of a context's batched-attention scratch block in MiB (bamd_set_attn_scratch_mb); 0 = the plan's default
 static const bool g_attn_fused = [] { const char * e = getenv("BAMD_ATTN_FUSED"); return !(e && e[0] == '0'); }();   // default: fused single-launch attention (BAMD_ATTN_FUSED=0: three-kernel path)
 // BAMD_AQL=0: the device-side greedy loop replays one hipGraph per step on the context's HIP stream (rounds 1-5) instead of AQL packets with fence scope
 // NONE on the library's own queue (bamd_aql.h).  Same kernels, same bits; BAMD_AQL_VERBOSE=1 says why when the own queue is not used
@@ -169,7 +170,7 @@ struct bamd_context {
     unsigned long long * tl_base = nullptr; int tl_slot = 0, tl_cap = 0;
     // batched prefill buffers, [bcap] tokens each (allocated at the first multi-token decode)
     int bcap = 0;
-    float * attn_bscr = nullptr; size_t attn_bscr_bytes = 0, attn_bscr_failed = 0;   // score rows of the matrix-core prefill attention beyond BAMD_AM_MAXPOS = 512 positions (grow-only; absent = the VALU kernel runs)
+    float * attn_bscr = nullptr; size_t attn_bscr_bytes = 0, attn_bscr_failed = 0;   // score rows of the batched prefill attention: the matrix-core kernel beyond BAMD_AM_MAXPOS = 512 positions, every kernel beyond the LDS (ensure_attn_scratch: grow-only under the budget; absent = the VALU kernels with their rows in LDS, token by token beyond)
     float * bx = nullptr, * bx2 = nullptr, * bqkv = nullptr, * batt = nullptr, * bh = nullptr; unsigned char * bblob = nullptr, * bblob16 = nullptr;
     std::vector<void *> allocs;
 };
@@ -390,6 +391,13 @@ static int context_init(bamd_context * c, bamd_model * m, int n_ctx) {
     HIPC(hipSetDevice(m->device));
     c->m = m; c->n_ctx = n_ctx;
     if (n_ctx < 32 || n_ctx % 32) return fail("n_ctx must be a positive multiple of 32");
+    // the attention kernels read one layer's K / V^T through 32-bit byte offsets into a 2 GiB - 1 window (ik_rsrc, bamd_device.h): a larger cache would read zeros
+    // past the window, silently.  Checked before anything is allocated
+    if ((size_t) ((n_ctx + 63) / 64 * 64) * (size_t) (m->Hkv * m->hd) * 2 >= (size_t) 0x7fffffff) {
+        char b[256]; snprintf(b, sizeof b, "n_ctx %d x %d KV elements per position x 2 bytes = %.2f GiB per layer cache: one layer's K (or V) cache must stay below 2 GiB (32-bit offsets in the attention kernels); open the context with a smaller n_ctx",
+                              n_ctx, m->Hkv * m->hd, (double) ((size_t) ((n_ctx + 63) / 64 * 64) * (size_t) (m->Hkv * m->hd) * 2) / 1073741824.0);
+        return fail(b);
+    }
     HIPC(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const int nl = (int) m->layers.size(), Ekv = m->Hkv * m->hd;
     c->kc.resize((size_t) nl); c->vc.resize((size_t) nl);
@@ -786,17 +794,39 @@ static int kv_find_slot(bamd_context * c, int pos, int * cell, int * n_kv) {
 }
 
 // ---- batched prefill: a micro-batch of T > 1 tokens through the layers at once (llama_decode with n_tokens > 1) -----------
-// pos_hi: last position of the micro-batch — its score rows (2 x padded length floats per head) must fit the LDS: 18 432 positions
-static bool prefill_batch_supported(const bamd_context * c, int pos_hi) {
+// The scratch block of the batched attention (score rows of the matrix-core kernel beyond 512 positions, of every kernel beyond the LDS: bamd_attention_batch_plan),
+// sized by the plan of this micro-batch under the budget and grown while nothing of this context is in flight on `s` (freed with the context).
+// true = the attention of the micro-batch has its kernels: the block is there, or its score rows still fit the LDS (2 x padded length floats per head: 18 432
+// positions), where the VALU kernels run without one.  false = beyond the LDS without a block: the caller evaluates token by token.
+static size_t attn_scratch_budget() { return (size_t) g_attn_scratch_mb << 20; }      // 0 = the plan's default
+static bool ensure_attn_scratch(bamd_context * c, int T, int n_past, hipStream_t s) {
+    const bamd_model * m = c->m;
+    const int gq = m->H / m->Hkv, ld = attn_lds_ld(c, std::max(n_past, 0) + T - 1);      // (a negative n_past is the caller's error to report)
+    const bool lds_ok = (size_t) ld * 8 <= 144 * 1024;
+    size_t need = 0;
+    if (bamd_attention_batch_plan(m->Hkv, gq, m->hd, T, ld, 0, attn_scratch_budget(), nullptr, nullptr, &need)) return false;
+    if (need > c->attn_bscr_bytes && !(c->attn_bscr_failed && need >= c->attn_bscr_failed)) {   // (replaced only while nothing of this context is in flight: stream order)
+        if (hipStreamSynchronize(s) != hipSuccess) { (void) hipGetLastError(); return false; }
+        if (c->attn_bscr) hipFree(c->attn_bscr);
+        c->attn_bscr = nullptr; c->attn_bscr_bytes = 0;
+        // ~ H * T * ld * 4 bytes up to the budget (0.5 GB at 8 K positions on the 8B shape, 1.2 GB from 18 K on; 2.4 GB on a 70B stage).  If the device cannot spare
+        // it the prompt is not lost: without a block the VALU kernels with their rows in LDS run, and beyond the LDS the micro-batch goes token by token
+        if (hipMalloc((void **) &c->attn_bscr, need) == hipSuccess) c->attn_bscr_bytes = need;
+        else { (void) hipGetLastError(); c->attn_bscr = nullptr; c->attn_bscr_failed = need; }   // not retried for this size or larger (every layer of every micro-batch drained the stream and failed again)
+    }
+    return need <= c->attn_bscr_bytes || lds_ok;
+}
+// a micro-batch of T tokens behind n_past cached positions has batched kernels for every operation (and the scratch block its attention needs: allocated here)
+static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStream_t s) {
     const bamd_model * m = c->m;
     const int gq = m->H / m->Hkv;
-    if (!(g_prefill_batch && g_attn_fused && (size_t) attn_lds_ld(c, pos_hi) * 8 <= 144 * 1024 && m->hd <= 256 && (m->hd & 63) == 0 && gq >= 1 && gq <= 8)) return false;
+    if (!(g_prefill_batch && g_attn_fused && m->hd <= 256 && (m->hd & 63) == 0 && gq >= 1 && gq <= 8)) return false;
     // every mat-mul needs a kernel: the matrix-core kernels take every K-quant at any K when the model has its side tables; the integer-dot kernel
     // takes any K-quant while 4 tokens of Q8_K activations fit the LDS (K <= 35840; tiles of 8 tokens up to K = 17920)
     auto ok = [&](int type, int K) { return (g_prefill_mfma && m->aux_ok && bamd_prefill_mfma_type(type)) || 4 * bamd_blob_bytes(K) <= 160 * 1024; };
     for (const DevLayer & ly : m->layers)
         if (!ok(ly.wq.type, m->E) || !ok(ly.wk.type, m->E) || !ok(ly.wv.type, m->E) || !ok(ly.wo.type, m->E) || !ok(ly.wg.type, m->E) || !ok(ly.wu.type, m->E) || !ok(ly.wd.type, m->F)) return false;
-    return true;
+    return ensure_attn_scratch(c, T, n_past, s);
 }
 // prefill side tables of every layer matrix (bamd_prefill2.hip), built at model load (round 6; round 5 built them lazily inside the first batched evaluation — a
 // multi-gigabyte allocation after the contexts existed, and a partial failure mixed kernel generations: ADVICE r5).  The QKV segments are the ones
@@ -921,20 +951,10 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         t.st = c->st; t.q = c->bqkv; t.k = c->bqkv + E; t.v = c->bqkv + E + Ekv; t.kc = c->kc[il]; t.vc = c->vc[il]; t.rope = c->rope; t.out = c->batt;
         t.hd = m->hd; t.Hkv = m->Hkv; t.n_ctx = c->n_ctx_pad; t.kq_scale = 1.0f / sqrtf((float) m->hd); t.prefill_mode = 1;
         t.batch = 1; t.ld_qkv = ldq; t.ld_out = E; t.lds_ld = attn_lds_ld(c, n_past + T - 1); t.batch_pos0p1 = n_past + 1;
-        {
-            const size_t need = m->hd == 128 ? bamd_attention_batch_mfma_scratch(m->Hkv, gq, T, t.lds_ld) : 0;
-            if (need > c->attn_bscr_bytes && !(c->attn_bscr_failed && need >= c->attn_bscr_failed)) {   // (freed with the context; replaced only while nothing of this context is in flight: stream order)
-                HIPC(hipStreamSynchronize(s));
-                if (c->attn_bscr) hipFree(c->attn_bscr);
-                c->attn_bscr = nullptr; c->attn_bscr_bytes = 0;
-                // ~ H * T * ld * 4 bytes (0.5 GB at 8 K positions on the 8B shape, 2.4 GB at 18 K on a 70B stage).  If the device cannot spare it the
-                // prompt is not lost: without a scratch block the matrix-core launcher declines and attn_batch_kernel (VALU, no scratch) runs
-                if (hipMalloc((void **) &c->attn_bscr, need) == hipSuccess) c->attn_bscr_bytes = need;
-                else { (void) hipGetLastError(); c->attn_bscr = nullptr; c->attn_bscr_failed = need; }   // not retried for this size or larger (every layer of every micro-batch drained the stream and failed again)
-            }
-            t.batch_scratch = need && c->attn_bscr_bytes >= need ? c->attn_bscr : nullptr;
-        }
-        if (bamd_launch_attention_batch(t, gq, T, s)) return fail("batched attention: unsupported head configuration");
+        // the attention of the layer through the slice plan: one launch while the block (ensure_attn_scratch) holds the micro-batch's rows, token slices otherwise
+        t.batch_scratch = c->attn_bscr;
+        const size_t bud = attn_scratch_budget(), blk = bud && bud < c->attn_bscr_bytes ? bud : c->attn_bscr_bytes;   // (a budget lowered after the block grew still bounds the slices)
+        if (bamd_launch_attention_batch(t, gq, T, s, 0, blk)) return fail("batched attention: unsupported head configuration");
         // x2 = x + Wo . att
         bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wo.type));
         memset(&a, 0, sizeof a);
@@ -998,7 +1018,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_decode(bamd_context *
     if (c->cells.active && n_tokens > 1) return fail("after a context shift (bamd_kv_seq_add) tokens are evaluated one per call");
     if (!c->cells.active) c->n_cached = std::max(c->n_cached, n_past + n_tokens);
     if (hipMemcpyAsync(c->forced, tokens, (size_t) n_tokens * 4, hipMemcpyHostToDevice, s) != hipSuccess) return fail("H2D tokens");
-    if (n_tokens > 1 && n_tokens <= BAMD_PREFILL_CAP && prefill_batch_supported(c, n_past + n_tokens - 1)) {
+    if (n_tokens > 1 && n_tokens <= BAMD_PREFILL_CAP && prefill_batch_supported(c, n_tokens, n_past, s)) {
         // one micro-batch: every layer once for all tokens (each weight record unpacked once per 8 tokens), lm_head for the last
         if (ensure_batch_buffers(c)) return 1;
         if (enqueue_prefill_batch(c, n_tokens, n_past, s)) return 1;
@@ -1036,7 +1056,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_prefill(bamd_co
     bamd_model * m = c->m;
     HIPC(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t) hip_stream;
-    if (n_tokens < 2 || n_tokens > BAMD_PREFILL_CAP || !prefill_batch_supported(c, n_past + n_tokens - 1)) return 2;
+    if (n_tokens < 2 || n_tokens > BAMD_PREFILL_CAP || !prefill_batch_supported(c, n_tokens, n_past, s)) return 2;
     if (n_past < 0 || n_past + n_tokens > c->n_ctx) return fail("context overflow");
     if (c->cells.active) return fail("after a context shift (bamd_kv_seq_add) tokens are evaluated one per call");
     c->n_cached = std::max(c->n_cached, n_past + n_tokens);
@@ -1049,6 +1069,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_stage_prefill(bamd_co
     return launch_check();
 }
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_batch(int on) { g_prefill_batch = on ? 1 : 0; g_prefill_mfma = on == 2 ? 0 : 1; }
+extern "C" __attribute__((visibility("default"))) void bamd_set_attn_scratch_mb(int mb) { g_attn_scratch_mb = mb > 0 ? mb : 0; }
 extern "C" __attribute__((visibility("default"))) const float * bamd_get_logits(bamd_context * c) {
     if (!c->logits_host_valid) {                                          // bamd_set_logits_readback(c, 0): copy on demand
         if (hipSetDevice(c->m->device) != hipSuccess) return nullptr;

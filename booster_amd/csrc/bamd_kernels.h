@@ -146,9 +146,17 @@ int  bamd_launch_matmul_mfma_q1(const void * w_stream, const void * aux, int typ
 int  bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);      // 1 = shape not supported
 void bamd_launch_embed_batch(const int32_t * tokens, int T, const void * embd, int embd_type, int E, int V, float * x, hipStream_t s);
 // impl: 0 = the matrix-core kernel where it covers the shape, else the VALU kernels (the engine); 1 = the VALU kernels only; 2 = the matrix-core
-// kernel only (1 when it declines the shape — after the KV store).  Op-level tests select the path; the engine passes the default
-int  bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl = 0);     // 1 = shape not supported
-int  bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hipStream_t s);   // the same on the matrix cores (after the KV store); 1 = shape not covered
+// kernel only (1 when it declines the shape — after the KV store).  Op-level tests select the path; the engine passes the default.
+// scratch_bytes: size of a.batch_scratch (0 with a block: the caller sized it by bamd_attention_batch_mfma_scratch, as before the slice plan existed).  While the
+// score rows fit the LDS (ld * 8 <= BAMD_ATTN_LDS_MAX) and the block holds the whole micro-batch this is one launch; otherwise the attention is issued in token slices
+// that reuse the block (bamd_attention_batch_plan with budget = scratch_bytes), *n_slices (optional) = how many
+int  bamd_launch_attention_batch(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl = 0, size_t scratch_bytes = 0, int * n_slices = nullptr);     // 1 = shape not supported
+// the same on the matrix cores (after the KV store); 1 = shape not covered.  t0 / Ts: the slice [t0, t0 + Ts) of the micro-batch's T tokens this launch covers
+// (t0 a multiple of the kernel's token tile 16 / gq; Ts 0 = all of them); positions, q rows and out rows stay those of the whole micro-batch
+int  bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hipStream_t s, int t0 = 0, int Ts = 0);
 size_t bamd_attention_batch_mfma_scratch(int Hkv, int gq, int T, int ld);                         // bytes of a.batch_scratch it needs for sequences of up to ld positions (0: none)
+void bamd_launch_attention_batch_gs(const bamd_attn_args & a, int gq, int t0, int Ts, hipStream_t s);   // the VALU kernel with its rows in a.batch_scratch (beyond the LDS; gq 1..8 checked by the caller)
+int  bamd_attention_batch_mfma_on(void);                                                           // 0: switched off (BAMD_ATTN_MFMA=0)
+// the slice plan of a micro-batch's attention: bamd_attention_batch_plan (include/bamd.h; defined in bamd_attention.hip, host code only)
 void bamd_launch_sampler_shortlist(float * logits, const bamd_logit_penalty * pen, int n_pen, const uint8_t * halve_class, int halve,
                                    const float * cutoff_of, int V, bamd_shortlist_head * head, int32_t * ids, float * vals, int cap, hipStream_t s);

@@ -284,9 +284,10 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention_cells(co
 
 // batched-prefill attention of T tokens at positions pos0 .. pos0 + T - 1 through the launcher enqueue_prefill_batch calls (KV store, then the matrix-core
 // or VALU kernels), with the same argument block: q / k / v packed as one [T][H*hd + 2*Hkv*hd] matrix, batch_pos0p1, lds_ld, scratch block
-extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
-                                                                                const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld,
-                                                                                float * out) {
+// scratch_bytes: the budget of the scratch block handed to the slice plan (0 = the engine's rule); *n_slices (optional): attention launches issued behind the KV store
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch_ex(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                                                                   const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld,
+                                                                                   size_t scratch_bytes, float * out, int * n_slices) {
     if (need_device()) return 1;
     if (H <= 0 || Hkv <= 0 || hd <= 0 || hd % 64 || hd > 256 || n_ctx <= 0 || n_ctx % 32 || H % Hkv || H / Hkv > 8) return fail("bad attention shape");
     if (T < 1 || T > BAMD_PREFILL_CAP || pos0 < 0 || pos0 + T > n_ctx) return fail("bad micro-batch");
@@ -313,10 +314,19 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(co
     a.q = dqkv; a.k = dqkv + E; a.v = dqkv + E + Ekv;
     f.args(a, 1);
     a.batch = 1; a.ld_qkv = ldq; a.ld_out = E; a.lds_ld = ld; a.batch_pos0p1 = pos0 + 1;
-    const size_t need = hd == 128 && impl != 1 ? bamd_attention_batch_mfma_scratch(Hkv, gq, T, ld) : 0;
+    size_t need = 0;
+    if (bamd_attention_batch_plan(Hkv, gq, hd, T, ld, impl, scratch_bytes, nullptr, nullptr, &need))
+        return fail(impl == 2 && !(hd == 128 && T >= 2 && (gq == 1 || gq == 2 || gq == 4 || gq == 8)) ? "matrix-core kernel: shape not covered" : "batched attention: no slice plan (unsupported shape, or a scratch budget below one token tile)");
     if (need && !(a.batch_scratch = (float *) f.up(nullptr, need))) return fail("device alloc failed (scratch block)");
-    if (bamd_launch_attention_batch(a, gq, T, nullptr, impl)) return fail(impl == 2 ? "matrix-core kernel: shape not covered" : "batched attention: unsupported shape");
+    int ns = 0;
+    if (bamd_launch_attention_batch(a, gq, T, nullptr, impl, need, &ns)) return fail(impl == 2 ? "matrix-core kernel: shape not covered" : "batched attention: unsupported shape");
+    if (n_slices) *n_slices = ns;
     return f.down(a, out, (size_t) T * E, k_cache, v_cache_t);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                                                                                const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld,
+                                                                                float * out) {
+    return bamd_op_attention_batch_ex(q, k, v, k_cache, v_cache_t, rope, H, Hkv, hd, n_ctx, pos0, T, impl, ld, 0, out, nullptr);
 }
 
 // ---- launches with more than one operand role, with the argument blocks of the engine (enqueue_layers, enqueue_prefill_batch) ----

@@ -174,9 +174,23 @@ int bamd_bridge_stage_layout(void * ctx, int32_t * out, int cap_stages);
 
 /* Prompt evaluation mode, process-wide: 1 (default, also env BAMD_PREFILL_BATCH) = bamd_decode with 2..512 tokens runs the batched
  * prefill kernels (every layer once per micro-batch, like llama_decode with n_tokens > 1); 0 = token by token through the decode
- * kernels.  Bit-identical results.  Contexts with n_ctx > 8192 use the token-by-token path regardless (round 1). */
+ * kernels.  Bit-identical results.  Micro-batches run batched at every position of the context: while two score rows of the padded sequence length fit the LDS
+ * (18 432 positions) as they always did, beyond that with their score rows in the context's scratch block (bamd_set_attn_scratch_mb), in token slices that reuse
+ * it.  Only where that block cannot be allocated do the micro-batches beyond 18 432 positions go token by token (bamd_stage_prefill returns 2 there).  After a
+ * context shift tokens are evaluated one per call in either mode. */
 void bamd_set_prefill_batch(int on);   /* 2 = batched, but the mat-muls on the integer-dot kernel instead of the matrix-core kernels (the path of a model whose
                                         * side tables did not fit: they are built at model load, all matrices or none, BAMD_PREFILL_AUX_RESERVE_GB of the device left free) */
+/* Budget of a context's batched-attention scratch block in MiB, process-wide (also env BAMD_ATTN_SCRATCH_MB): the score rows of a prompt micro-batch beyond 512
+ * positions live there (H x tokens x padded length x 4 bytes), and a micro-batch whose rows exceed the budget has its attention issued in token slices that reuse
+ * the block (bamd_attention_batch_plan).  0 (default) = H x 512 x 18432 x 4 bytes (1.2 GB on the 8B shape): what a 512-token micro-batch at 18 432 positions
+ * takes, so up to there a micro-batch is one slice.  A budget too small for one token tile sends micro-batches beyond 18 432 positions token by token.
+ * Bit-identical results at every setting. */
+void bamd_set_attn_scratch_mb(int mb);
+/* The slice plan of a micro-batch's attention, host only (no device): T tokens, score rows of ld floats (a multiple of 64), impl as bamd_op_attention_batch,
+ * budget_bytes for the scratch block (0 = the default above).  Slice i covers tokens [i * tokens_per_slice, min(T, (i + 1) * tokens_per_slice)); tokens_per_slice is
+ * a whole number of the kernel's token tiles (16 / gq on the matrix cores, 1 on the VALU); scratch_bytes (<= budget) is what one slice needs (0: none).
+ * Returns 1 when there is no plan: bad shape, impl 2 where the matrix-core kernel declines, or a budget below one tile. */
+int bamd_attention_batch_plan(int Hkv, int gq, int hd, int T, int ld, int impl, size_t budget_bytes, int * tokens_per_slice, int * n_slices, size_t * scratch_bytes);
 /* Matrix-core prompt mat-muls for Q3_K / Q2_K weights, process-wide: 0 (default, also env BAMD_PREFILL_LOWBIT) = a model that holds such a matrix builds
  * no side tables and evaluates its prompts on the integer-dot kernel; 1 = these types have side tables and kernels like Q4_K / Q5_K / Q6_K.  A model takes the
  * value at load (its tables exist or not); with the switch off again a model that has tables runs its prompts on the integer-dot kernel.  Bit-identical results. */
@@ -241,6 +255,11 @@ int bamd_op_attention(const float * q, const float * k, const float * v, uint16_
  * the micro-batch's last position up to the padded n_ctx. */
 int bamd_op_attention_batch(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
                             const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld, float * out);
+/* the same with the scratch budget of the slice plan (scratch_bytes, 0 = the default) and, in *n_slices (optional), the number of attention launches issued behind
+ * the KV store: a small budget forces several slices at a small shape.  ld may exceed 18 432 here and above: the rows then live in the scratch block. */
+int bamd_op_attention_batch_ex(const float * q, const float * k, const float * v, uint16_t * k_cache, uint16_t * v_cache_t,
+                               const float * rope, int H, int Hkv, int hd, int n_ctx, int pos0, int T, int impl, int ld, size_t scratch_bytes, float * out,
+                               int * n_slices);
 /* RoPE (cos,sin) table row as built on the host for position pos (ggml_rope_cache_init, ggml.c:14017) */
 int bamd_op_rope_row(int pos, int n_dims, float freq_base, float freq_scale, const float * freq_factors, float * row);
 /* the K-shift of one layer (llama_kv_cache_update -> build_k_shift, llama.cpp:15245-15277, :8482-8512) through the engine's own table code and launch:
