@@ -151,6 +151,14 @@ __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, 
 }
 
 
+// Completes a wave's own chain in front of a wait: the accumulators pass through an empty volatile asm, which LLVM neither sinks nor splits.  Without
+// it the values are first USED behind the spin loop and the whole term and chain arithmetic of the wave's records is sunk below it (524 vector
+// instructions of the Q4_K gate/up kernel ran after the flag rose; a sched_barrier does not help: the sinking happens before scheduling).
+template <int TYPE> __device__ __forceinline__ void hold_acc(RowAcc & A) {
+    asm volatile("" : "+v"(A.acc));
+    if (TYPE == BAMD_Q4_K || TYPE == BAMD_Q5_K) asm volatile("" : "+v"(A.accm));
+}
+
 // ---- MODE A, gate/up launch with exactly SEVEN row-group pairs per 8-wave workgroup (n_ff = 7 x 8 x 8 x CUs: Llama-3-8B / Mistral-7B, 14336 rows on
 // 256 CUs).  One pair per wave leaves wave 7 idle: SIMD 3 streams 32 records where SIMDs 0-2 stream 64, and the launch is paced by the younger
 // waves 4-6 (timeline, round 2: waves 0-3 exit at 11.4 us, waves 4-6 at 13.8, wave 7 at 3.4).  Here waves 4-6 stop three quarters into their
@@ -158,6 +166,9 @@ __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, 
 // and parks them in LDS (the split-K kernels' mechanism); waves 4-6 then replay them IN ORDER behind their own chain steps: every SIMD streams
 // 56 records, and each lane's f32 chain is still the reference's sequential chain over super-blocks 0..nb-1 (ggml-quants.c:6937-6941, :6970).
 // HELPER = wave 7; otherwise wave 4 + j of the workgroup (its pair: row-group rg0).  LDS: park[3 pairs][gate | up][nb / 4][64 lanes] float4, flags[3].
+// flags[j] COUNTS the parked records of pair j: the helper raises it to Q behind the gate quarter and to 2 Q behind the up quarter, and the pair's wave
+// replays the gate steps, finish_row and SiLU while the helper is still on the up quarter: behind the helper's last record come Q chain steps, one
+// finish_row, one multiply and the store.  (Measured and dropped: a publish per record, 24 release waits in the helper; s_setprio 1 for the helper.)
 template <int TYPE, int NBP, bool HELPER>
 __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ wG, const uint8_t * __restrict__ wU, int rg0, int rg_stride, int j,
                                                   float * __restrict__ out, const ProArgs & pa, ActPro<true> & ap, float4 * park, int * flags, int nvalid) {
@@ -195,9 +206,9 @@ __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ w
             else if (BAMD_GU7_UP(i)) chain_step<TYPE>(Au, T.d, T.fs, T.dmin, T.pm);
             else chain_step<TYPE>(Ag, T.d, T.fs, T.dmin, T.pm);
             if (i + D < NREC) load_rec(ring[s], BAMD_GU7_UP(i + D) ? rsU : rsG, BAMD_GU7_OFF(i + D), lane);
-            if (HELPER && (i % (2 * Q)) == 2 * Q - 1) {            // the six quarter-rows of one pair are parked: tell its wave
+            if (HELPER && (i % Q) == Q - 1) {                      // one more quarter-row of a pair is parked: tell its wave
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                if (lane == 0) __hip_atomic_store(flags + i / (2 * Q), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (lane == 0) __hip_atomic_store(flags + i / (2 * Q), (i % (2 * Q)) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             if ((s & (BAMD_SCHED_GROUP - 1)) == BAMD_SCHED_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
         }
@@ -205,19 +216,28 @@ __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ w
     }
     TL_STAMP(pa.tl, 4);
     if (!HELPER) {
-        while (__hip_atomic_load(flags + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        hold_acc<TYPE>(Ag); hold_acc<TYPE>(Au);              // this wave's own 2 x CUT chain steps are done before it waits
         const float4 * Pg = park + (j * 2 + 0) * Q * 64 + lane, * Pu = park + (j * 2 + 1) * Q * 64 + lane;
+        auto wait_for = [&](const int need) {                // at least `need` parked records of this pair
+            while (__hip_atomic_load(flags + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need) __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        };
         float4 tg[Q], tu[Q];
+        wait_for(Q);
 #pragma unroll
-        for (int u = 0; u < Q; ++u) { tg[u] = Pg[u * 64]; tu[u] = Pu[u * 64]; }
+        for (int u = 0; u < Q; ++u) tg[u] = Pg[u * 64];
 #pragma unroll
         for (int u = 0; u < Q; ++u) chain_step<TYPE>(Ag, tg[u].x, tg[u].y, tg[u].z, tg[u].w);
+        float gate_act = v_silu(finish_row<TYPE>(Ag));
+        asm volatile("" : "+v"(gate_act));                   // SiLU, too, in front of the second wait
+        wait_for(2 * Q);
+#pragma unroll
+        for (int u = 0; u < Q; ++u) tu[u] = Pu[u * 64];
 #pragma unroll
         for (int u = 0; u < Q; ++u) chain_step<TYPE>(Au, tu[u].x, tu[u].y, tu[u].z, tu[u].w);
-        const float gate_val = finish_row<TYPE>(Ag), up_val = finish_row<TYPE>(Au);
+        const float up_val = finish_row<TYPE>(Au);
         const int row = rg0 * 8 + (lane >> 3);
-        if ((lane & 7) == 0 && row < nvalid) ik_st(out + row, v_silu(gate_val) * up_val);
+        if ((lane & 7) == 0 && row < nvalid) ik_st(out + row, gate_act * up_val);
     }
 #undef BAMD_GU7_UP
 #undef BAMD_GU7_SB
