@@ -264,10 +264,13 @@ struct ActPro {
     // blocks i0, i0 + bstride, ... below blimit (defaults: this wave's share of the whole vector, interleaved over the waves)
     // NB: batch slots in use (compile time) — K = 4096 on eight waves fills two of the four; the others would request the last block again
     // and run the whole quantisation arithmetic on it for nothing
-    template <int NB = BAMD_ACT_BATCH>
+    // NWV: waves per workgroup where the kernel has them as a template parameter (0: read blockDim).  blockDim comes from the hidden kernel arguments: in
+    // the split-K QKV kernels that read was a VECTOR load issued between the ring requests, and the sum of squares waited for it — and, loads returning in
+    // order, for the six ring loads in front of it (profiles/mv_heads.txt)
+    template <int NB = BAMD_ACT_BATCH, int NWV = 0>
     __device__ __forceinline__ void issue(const float * __restrict__ x, const float * __restrict__ nw, int K, int i0, int bstride = 0, int blimit = 0) {
         const int lane = threadIdx.x & 63;
-        if (bstride == 0) { bstride = blockDim.x >> 6; blimit = K >> 8; }
+        if (bstride == 0) { bstride = NWV ? NWV : (int) (blockDim.x >> 6); blimit = K >> 8; }
         // UNCONDITIONAL requests (a block index past the end is clamped to the last block and its values are
         // never used): a conditional load becomes a branch around the request with a full s_waitcnt at the join, which serialised the
         // batches into one memory round trip each — and held back the weight ring that is issued after them
@@ -291,10 +294,10 @@ struct ActPro {
     //     0x400000 offset do not touch that byte), and MIN(127, .) (:3617) never binds for |iscale * x| <= 127(1 + 2^-23);
     //   - the sum of the four signed bytes is one v_dot4 against 0x01010101;
     //   - the four wave-max chains are interleaved step by step (DPP results need wait states); row_bcast leaves the result in lane 63.
-    template <int NB = BAMD_ACT_BATCH>
+    template <int NB = BAMD_ACT_BATCH, int NWV = 0>
     __device__ __forceinline__ void quantize_batch(float scale, int K, int i0, uint32_t * q8, int * S, float * yd, int bstride = 0, int blimit = 0) {
         const int lane = threadIdx.x & 63;
-        const int nwaves = bstride ? bstride : (int) (blockDim.x >> 6), nb = bstride ? blimit : (K >> 8);
+        const int nwaves = bstride ? bstride : NWV ? NWV : (int) (blockDim.x >> 6), nb = bstride ? blimit : (K >> 8);
 #if BAMD_CEILING & 1
         // TIMING-ONLY ceiling build (tools/ceiling.sh; never shipped, results are garbage): the activations arrive "already quantised" — no block maxima,
         // no divisions, no rounding: what a prologue costs that is a plain load + three LDS stores
@@ -383,10 +386,10 @@ struct ActPro {
     // mid: called once behind the first workgroup barrier (NORM) / at the start (plain).  The mode-A kernels request the second half of their
     // weight ring there: a CU's texture path takes ~1.5 us to accept the requests of eight full rings, every wave sits in its issue stage
     // for that long, and the barrier behind the sum of squares waited for the last of them
-    template <bool SMALLK = false, typename MID = NoMid, int NB = BAMD_ACT_BATCH>
+    template <bool SMALLK = false, typename MID = NoMid, int NB = BAMD_ACT_BATCH, int NWV = 0>
     __device__ __forceinline__ void finish(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K,
                                            uint32_t * q8, int * S, float * yd, double * red, MID mid = MID()) {
-        const int lane = threadIdx.x & 63, wave = wave_id(), nwaves = blockDim.x >> 6, nb = K >> 8;
+        const int lane = threadIdx.x & 63, wave = wave_id(), nwaves = NWV ? NWV : (int) (blockDim.x >> 6), nb = K >> 8;
         const int step = nwaves * BAMD_ACT_BATCH;
         float scale = 1.0f;
 #if BAMD_CEILING & 1
@@ -430,7 +433,7 @@ struct ActPro {
             }
             scale = 1.0f / sqrtf(mean + eps);
         } else mid();
-        quantize_batch<NB>(scale, K, wave, q8, S, yd);
+        quantize_batch<NB, NWV>(scale, K, wave, q8, S, yd);
         if (!SMALLK) for (int i0 = wave + step; i0 < nb; i0 += step) {
             ActPro<NORM> t; t.issue(x, nw, K, i0);
             t.quantize_batch(scale, K, i0, q8, S, yd);
@@ -892,9 +895,9 @@ struct ProArgs { const float * x, * nw; float eps; int K; uint32_t * q8; int * S
 #define BAMD_PRO_FINISH(ap, pa) (ap).finish((pa).x, (pa).nw, (pa).eps, (pa).K, (pa).q8, (pa).S, (pa).yd, (pa).red)
 #define BAMD_PRO_FINISH_SMALLK(ap, pa) (ap).template finish<true>((pa).x, (pa).nw, (pa).eps, (pa).K, (pa).q8, (pa).S, (pa).yd, (pa).red)
 #define BAMD_PRO_FINISH_SMALLK_MID(ap, pa, mid) (ap).template finish<true>((pa).x, (pa).nw, (pa).eps, (pa).K, (pa).q8, (pa).S, (pa).yd, (pa).red, mid)
-// the same with NB batch slots (the launcher guarantees K <= 256 * NB * waves)
-#define BAMD_PRO_ISSUE_NB(ap, pa, NB_) do { (ap).tl = (pa).tl; (ap).template issue<NB_>((pa).x, (pa).nw, (pa).K, wave_id()); } while (0)
-#define BAMD_PRO_FINISH_NB_MID(ap, pa, mid, NB_) (ap).template finish<true, decltype(mid), NB_>((pa).x, (pa).nw, (pa).eps, (pa).K, (pa).q8, (pa).S, (pa).yd, (pa).red, mid)
+// the same with NB batch slots (the launcher guarantees K <= 256 * NB * waves) in a kernel of NW_ waves (a template parameter of the kernel; 0: read blockDim)
+#define BAMD_PRO_ISSUE_NB(ap, pa, NB_, NW_) do { (ap).tl = (pa).tl; (ap).template issue<NB_, NW_>((pa).x, (pa).nw, (pa).K, wave_id()); } while (0)
+#define BAMD_PRO_FINISH_NB_MID(ap, pa, mid, NB_, NW_) (ap).template finish<true, decltype(mid), NB_, NW_>((pa).x, (pa).nw, (pa).eps, (pa).K, (pa).q8, (pa).S, (pa).yd, (pa).red, mid)
 
 __device__ __forceinline__ void get_scale_min_k4(int j, const uint8_t * q, int & d, int & m) {
     if (j < 4) { d = q[j] & 63; m = q[j + 4] & 63; }

@@ -82,8 +82,8 @@ __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, 
 #pragma unroll
                 for (int s = D / 2; s < D; ++s) load_rec(ring[s], rsA, offA + s * fill_step, lane);
             };
-            BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP);
-        } else if (SMALLK) { auto nm = []() { }; BAMD_PRO_FINISH_NB_MID(ap, pa, nm, NBP); }
+            BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP, 0);
+        } else if (SMALLK) { auto nm = []() { }; BAMD_PRO_FINISH_NB_MID(ap, pa, nm, NBP, 0); }
         else BAMD_PRO_FINISH(ap, pa);
     } else if (RSPLIT) {
 #pragma unroll
@@ -191,7 +191,7 @@ __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ w
 #pragma unroll
         for (int s = D / 2; s < D; ++s) load_rec(ring[s], BAMD_GU7_UP(s) ? rsU : rsG, BAMD_GU7_OFF(s), lane);
     };
-    BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP);
+    BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP, 0);
     TL_STAMP(pa.tl, 2);
     const uint32_t * q8 = pa.q8; const int * S = pa.S; const float * yd = pa.yd;
     RowAcc Ag = { 0.f, 0.f }, Au = { 0.f, 0.f };
@@ -264,8 +264,13 @@ __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ w
 // COMPACT (K = 28672, the 70B ffn_down: 112 super-blocks): a parked record takes 576 bytes — {fs, pm} per lane, {d, dmin} once per row — instead of a float4 per
 // lane, so that TWO term buffers of a whole row-group fit the LDS beside the activations (2 x 63 KB + 32 KB) and the chain of row-group n overlaps the
 // streaming of row-group n + 1 (with one buffer every batch ends in barrier + 112-step chain + barrier: measured slower than one wave per row-group, round 5)
+// NWV: waves per workgroup as a constant (0: blockDim), for the shared prologue (ActPro).
+// Behind an own-slice (PLAIN) prologue the compiler requests the Q6_K rings of four records and every ring of seven BEHIND the wait for the activations and their
+// Q8_K quantisation, not in the source's order.  Measured and left alone: a scheduling fence behind ring_fill(0, DH) restores the order and the ffn_down launch
+// gets SLOWER (Q6_K, fourteen waves: 11.64 -> 11.92 us; profiles/mv_heads.txt, section 3)
 struct SplitNoPre { __device__ __forceinline__ void operator()() const { } };
-template <int TYPE, int NBW, int M, int NBUF, int EPI, int PRO, bool SMALLK = false, bool ONEB = false, bool UNEVEN = false, typename PRE = SplitNoPre, bool COMPACT = false>
+template <int TYPE, int NBW, int M, int NBUF, int EPI, int PRO, bool SMALLK = false, bool ONEB = false, bool UNEVEN = false, typename PRE = SplitNoPre, bool COMPACT = false,
+          int NWV = 0>
 __device__ __forceinline__ void split_stream(const uint8_t * __restrict__ w, int nb, int first, int count, int stride,
                                              float * __restrict__ out, const float * __restrict__ res, const ProArgs & pa,
                                              ActPro<PRO == BAMD_PRO_NORM> & ap, ActPro<PRO == BAMD_PRO_NORM> & ap2, bool issue_here, bool do_pro,
@@ -327,7 +332,7 @@ __device__ __forceinline__ void split_stream(const uint8_t * __restrict__ w, int
             if (NBW > BAMD_ACT_BATCH) ap2.template quantize_batch<BAMD_NB2(NBW)>(1.0f, pa.K, i0 + BAMD_ACT_BATCH, pa.q8, pa.S, pa.yd, 1, i0 + n_w);
         } else if (SMALLK && !UNEVEN) {                      // shared prologue of a fast kernel: NBW blocks per wave (issued with BAMD_PRO_ISSUE_NB at entry)
             auto second_half = [&]() { if (RSPLIT) ring_fill(DH, D); };
-            BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, BAMD_NB1(NBW));
+            BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, BAMD_NB1(NBW), NWV);
         }
         else if (SMALLK) BAMD_PRO_FINISH_SMALLK(ap, pa);
         else BAMD_PRO_FINISH(ap, pa);

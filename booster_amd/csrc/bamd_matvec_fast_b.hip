@@ -17,13 +17,13 @@ __global__ void __launch_bounds__(64 * NW) matvec_split_fast_kernel(BAMD_LEAD_PA
         const int i0 = wave_id() * NBW;
         ap.template issue<BAMD_NB1(NBW)>(pa.x, pa.nw, pa.K, i0, 1, i0 + NBW);
         if (NBW > BAMD_ACT_BATCH) ap2.template issue<BAMD_NB2(NBW)>(pa.x, pa.nw, pa.K, i0 + BAMD_ACT_BATCH, 1, i0 + NBW);
-    } else BAMD_PRO_ISSUE_NB(ap, pa, BAMD_NB1(NBW));         // shared prologue: wave w takes blocks w, w + 8, ...: NBW of them
+    } else BAMD_PRO_ISSUE_NB(ap, pa, BAMD_NB1(NBW), NW);  // shared prologue: wave w takes blocks w, w + NW, ...: NBW of them
     float * part0 = (float *) (smem + mv_terms_off(nb));
     int rgctr = 0;
     const int count = a.cnt_q + ((int) blockIdx.x < a.cnt_r ? 1 : 0);
     const int nv = a.seg[0].nvalid > 0 ? a.seg[0].nvalid : a.seg[0].nrows;
     constexpr int NBUF = split_fast_nbuf(NBW, M, COMPACT);
-    split_stream<TYPE, NBW, M, NBUF, EPI, PRO, true, ONEB, false, SplitNoPre, COMPACT>((const uint8_t *) a.seg[0].w, nb, (int) blockIdx.x, count, (int) gridDim.x, a.seg[0].out, a.res, pa,
+    split_stream<TYPE, NBW, M, NBUF, EPI, PRO, true, ONEB, false, SplitNoPre, COMPACT, NW>((const uint8_t *) a.seg[0].w, nb, (int) blockIdx.x, count, (int) gridDim.x, a.seg[0].out, a.res, pa,
                                                        ap, ap2, false, true, part0, rgctr, nv, SplitNoPre());      // the launcher's grid gives every workgroup >= 1 row-group
     TL_STAMP(a.tl, 7);
 }
@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(64 * NW) matvec_split_fast_kernel(BAMD_LEAD_PA
 // COMPACT (the 70B widths: five row-groups of 32 super-blocks per workgroup): a parked record takes 576 bytes — {fs, pm} per lane, {d, dmin} per row —
 // instead of a float4 per lane, so that the five term buffers fit the LDS (92 KB); the first MA - 2 rings go out at entry, the others behind the
 // prologue's first barrier
-template <int TA, int TB, int NBW, int MA, bool COMPACT = false>
+template <int TA, int TB, int NBW, int MA, bool COMPACT = false, int NW = 0>
 __device__ __forceinline__ void split_mixed_body(const bamd_mv_args & a, const ProArgs & pa, ActPro<true> & ap, float * part0, int g_last) {
     typedef typename RecOf<TA>::type RECA;
     typedef typename RecOf<TB>::type RECB_T;
@@ -69,7 +69,7 @@ __device__ __forceinline__ void split_mixed_body(const bamd_mv_args & a, const P
 #pragma unroll
         for (int j = 0; j < NBW; ++j) load_rec(ringL[j], rs1, lastoff + (i0 + j) * RB, lane);
     };
-    BAMD_PRO_FINISH_NB_MID(ap, pa, last_ring, BAMD_NB1(NBW));
+    BAMD_PRO_FINISH_NB_MID(ap, pa, last_ring, BAMD_NB1(NBW), NW);
     TL_STAMP(pa.tl, 2);
     const uint32_t * q8 = pa.q8; const int * S = pa.S; const float * yd = pa.yd;
     const size_t rg_floats = mv_term_floats(nb, COMPACT);         // floats per parked row-group
@@ -149,11 +149,11 @@ __global__ void __launch_bounds__(64 * NW) matvec_split_mixed_kernel(BAMD_LEAD_P
     const int nb = a.K >> 8;
     const ProArgs pa = carve_lds(a, smem);
     ActPro<true> ap;
-    BAMD_PRO_ISSUE_NB(ap, pa, BAMD_NB1(NBW));
+    BAMD_PRO_ISSUE_NB(ap, pa, BAMD_NB1(NBW), NW);
     float * part0 = (float *) (smem + mv_terms_off(nb));
     const int g_last = MA * (int) gridDim.x + (int) blockIdx.x;       // index of this workgroup's last row-group in the concatenated segments
-    if (g_last < (a.seg[0].nrows >> 3)) split_mixed_body<TA, TA, NBW, MA, COMPACT>(a, pa, ap, part0, g_last);
-    else                                split_mixed_body<TA, TB, NBW, MA, COMPACT>(a, pa, ap, part0, g_last);
+    if (g_last < (a.seg[0].nrows >> 3)) split_mixed_body<TA, TA, NBW, MA, COMPACT, NW>(a, pa, ap, part0, g_last);
+    else                                split_mixed_body<TA, TB, NBW, MA, COMPACT, NW>(a, pa, ap, part0, g_last);
     TL_STAMP(a.tl, 7);
 }
 // every instance's K is fixed by its shape (NW waves x NBW records), and so is its LDS
