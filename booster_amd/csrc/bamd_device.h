@@ -253,6 +253,41 @@ __device__ __forceinline__ double seq_expsum8(const float * vals, int n) {
                                         barrier + sequential chain replay: what the reference's arithmetic costs per launch (profiles/r05_ceiling.txt) */
 #endif
 #define BAMD_ACT_RED_OFF(nb) ((((size_t) (nb) * (256 + 32 + 4)) + 15) & ~(size_t) 15)
+// ---- stage points of the shared prologue (ActPro::finish / quantize_batch) ---------------------------------------------------------------------
+// The `mid` functor of finish() is either plain (operator()(): called once, at BAMD_ST_BAR) or STAGED (operator()(StageC<ST>): called at every stage
+// point below, in this order, each exactly once on every path).  A staged functor deals memory requests over the prologue's dependent arithmetic
+// (mode A: the second half of the weight ring, bamd_matvec_core.h) and fences its own requests with sched_barrier(0).  Every stage point is in
+// straight-line code: none inside the wave-uniform `i < nb` branches of the pack (a request inside a branch costs a full s_waitcnt at the join), so
+// "before the pack" is BAMD_ST_DIV.
+template <int N> struct StageC { static constexpr int value = N; };
+template <int LO, int HI, typename F> __device__ __forceinline__ void static_for(F && f) {
+    if constexpr (LO < HI) { f(StageC<LO>()); static_for<LO + 1, HI>(f); }
+}
+enum {
+    BAMD_ST_SQ = 0,      // own sum of squares done (the activations have landed); in front of the first barrier
+    BAMD_ST_SQ1,         // ... behind each of the four f64 DPP steps of the wave sum
+    BAMD_ST_SQ2, BAMD_ST_SQ3, BAMD_ST_SQ4,
+    BAMD_ST_BAR,         // behind the first workgroup barrier (plain prologue: at the start).  A plain functor runs here
+    BAMD_ST_RED,         // red[] read and summed
+    BAMD_ST_MEAN,        // mean (and its f64-order guard)
+    BAMD_ST_SCALE,       // 1 / sqrt(mean + eps)
+    BAMD_ST_NORM,        // quantize_batch: norm multiply and the lanes' own maxima
+    BAMD_ST_MAX1,        // ... behind each of the six DPP maximum steps
+    BAMD_ST_MAX2, BAMD_ST_MAX3, BAMD_ST_MAX4, BAMD_ST_MAX5, BAMD_ST_MAX6,
+    BAMD_ST_FIRST,       // first element of largest magnitude selected
+    BAMD_ST_DIV,         // the two divisions; in front of the pack
+    BAMD_ST_END,         // behind the quantisation, in front of the last barrier
+    BAMD_ST_COUNT
+};
+template <typename MID, typename = void> struct MidStaged { static constexpr bool value = false; };
+template <typename MID> struct MidStaged<MID, decltype((*(MID *) nullptr)(StageC<0>()), void())> { static constexpr bool value = true; };
+template <int ST, typename MID> __device__ __forceinline__ void mid_at(MID & mid, int) {
+    if constexpr (MidStaged<MID>::value) mid(StageC<ST>());
+    else if constexpr (ST == BAMD_ST_BAR) mid();
+}
+template <int LO, int HI, typename MID> __device__ __forceinline__ void mid_span(MID & mid) {     // stage points LO .. HI - 1 with nothing between them
+    static_for<LO, HI>([&](auto st) { mid_at<decltype(st)::value>(mid, 0); });
+}
 template <bool NORM>
 struct ActPro {
     float4 v[BAMD_ACT_BATCH], w[BAMD_ACT_BATCH];
@@ -294,13 +329,16 @@ struct ActPro {
     //     0x400000 offset do not touch that byte), and MIN(127, .) (:3617) never binds for |iscale * x| <= 127(1 + 2^-23);
     //   - the sum of the four signed bytes is one v_dot4 against 0x01010101;
     //   - the four wave-max chains are interleaved step by step (DPP results need wait states); row_bcast leaves the result in lane 63.
-    template <int NB = BAMD_ACT_BATCH, int NWV = 0>
-    __device__ __forceinline__ void quantize_batch(float scale, int K, int i0, uint32_t * q8, int * S, float * yd, int bstride = 0, int blimit = 0) {
+    struct NoMid { __device__ __forceinline__ void operator()() const { } };
+    // mid: see the stage points above (BAMD_ST_NORM .. BAMD_ST_DIV are here); finish() passes its own on by reference
+    template <int NB = BAMD_ACT_BATCH, int NWV = 0, typename MID = NoMid>
+    __device__ __forceinline__ void quantize_batch(float scale, int K, int i0, uint32_t * q8, int * S, float * yd, int bstride = 0, int blimit = 0, MID mid = MID()) {
         const int lane = threadIdx.x & 63;
         const int nwaves = bstride ? bstride : NWV ? NWV : (int) (blockDim.x >> 6), nb = bstride ? blimit : (K >> 8);
 #if BAMD_CEILING & 1
         // TIMING-ONLY ceiling build (tools/ceiling.sh; never shipped, results are garbage): the activations arrive "already quantised" — no block maxima,
         // no divisions, no rounding: what a prologue costs that is a plain load + three LDS stores
+        mid_span<BAMD_ST_NORM, BAMD_ST_DIV + 1>(mid);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const int i = i0 + b * nwaves;
@@ -323,19 +361,26 @@ struct ActPro {
             const float a = fmaxf(fmaxf(fmaxf(fabsf(v[b].x), fabsf(v[b].y)), fabsf(v[b].z)), fabsf(v[b].w));
             amaxb[b] = __float_as_uint(a);               // non-negative floats order like their bit patterns
         }
+        mid_at<BAMD_ST_NORM>(mid, 0);
         uint32_t t[NB], wmax[NB];
 #pragma unroll
         for (int b = 0; b < NB; ++b) t[b] = umax_(amaxb[b], (uint32_t) dpp_z<DPP_XOR1>((int) amaxb[b]));
+        mid_at<BAMD_ST_MAX1>(mid, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) t[b] = umax_(t[b], (uint32_t) dpp_z<DPP_XOR2>((int) t[b]));
+        mid_at<BAMD_ST_MAX2>(mid, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) t[b] = umax_(t[b], (uint32_t) dpp_z<DPP_HALF_MIRROR>((int) t[b]));
+        mid_at<BAMD_ST_MAX3>(mid, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) t[b] = umax_(t[b], (uint32_t) dpp_z<DPP_MIRROR>((int) t[b]));
+        mid_at<BAMD_ST_MAX4>(mid, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) t[b] = umax_(t[b], (uint32_t) __builtin_amdgcn_update_dpp(0, (int) t[b], 0x142, 0xa, 0xf, false));   // row_bcast:15
+        mid_at<BAMD_ST_MAX5>(mid, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) t[b] = umax_(t[b], (uint32_t) __builtin_amdgcn_update_dpp(0, (int) t[b], 0x143, 0xc, 0xf, false));   // row_bcast:31
+        mid_at<BAMD_ST_MAX6>(mid, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) wmax[b] = (uint32_t) __builtin_amdgcn_readlane((int) t[b], 63);
         // the scale comes from the FIRST element of largest magnitude (strict > scan of the reference): lowest lane, lowest element
@@ -356,8 +401,10 @@ struct ActPro {
             const int mxb = __builtin_amdgcn_readlane(__float_as_int(mine[b]), first);
             mxv = lane == b ? mxb : mxv;
         }
+        mid_at<BAMD_ST_FIRST>(mid, 0);
         const float isc = -127.f / __int_as_float(mxv);  // lane b: block b (other lanes: -127)
         const float dd = 1.0f / isc;
+        mid_at<BAMD_ST_DIV>(mid, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const int i = i0 + b * nwaves;
@@ -382,10 +429,13 @@ struct ActPro {
     // SMALLK: the caller guarantees K <= 256 * BAMD_ACT_BATCH * (waves per workgroup), so the first batch is the whole share of this
     // wave and the loops over further batches (whose in-loop requests force a full s_waitcnt at their exit — which would also wait for
     // the weight ring issued before this call) are compiled out
-    struct NoMid { __device__ __forceinline__ void operator()() const { } };
-    // mid: called once behind the first workgroup barrier (NORM) / at the start (plain).  The mode-A kernels request the second half of their
-    // weight ring there: a CU's texture path takes ~1.5 us to accept the requests of eight full rings, every wave sits in its issue stage
-    // for that long, and the barrier behind the sum of squares waited for the last of them
+    // mid: plain — called once behind the first workgroup barrier (NORM) / at the start (plain prologue); staged — called at every stage point
+    // (BAMD_ST_*, above).  The mode-A kernels request the second half of their weight ring through it.  A CU's texture path takes ~1.5 us to
+    // accept the requests of eight full rings and every wave sits in its issue stage for that long: in front of the prologue the barrier behind the
+    // sum of squares waited for the last of them, and as one burst behind that barrier (the plain form, BAMD_RING_DRIP = 0) half of it stands in
+    // front of the mean, the scale and the quantisation.  The staged form deals the requests over the dependent chains behind the barrier (f64 mean,
+    // sqrt and division, DPP maxima, two more divisions), a few at each stage point, where the texture path's queue drains between two of
+    // a wave's requests (profiles/prologue_ring.txt).  NWV: the waves as a constant make the red[] sum eight straight-line LDS reads
     template <bool SMALLK = false, typename MID = NoMid, int NB = BAMD_ACT_BATCH, int NWV = 0>
     __device__ __forceinline__ void finish(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K,
                                            uint32_t * q8, int * S, float * yd, double * red, MID mid = MID()) {
@@ -393,7 +443,7 @@ struct ActPro {
         const int step = nwaves * BAMD_ACT_BATCH;
         float scale = 1.0f;
 #if BAMD_CEILING & 1
-        if (NORM) { mid(); } else
+        if (NORM) { if constexpr (MidStaged<MID>::value) mid_span<BAMD_ST_SQ, BAMD_ST_SCALE + 1>(mid); else mid(); } else
 #endif
         if (NORM) {
             // sum of squares in double (ggml.c:11874-11877), fixed tree order; f32_rounding_safe() below decides whether the order can matter
@@ -409,13 +459,21 @@ struct ActPro {
                     if (t.okmask >> b & 1) { s += (double) (t.v[b].x * t.v[b].x); s += (double) (t.v[b].y * t.v[b].y); s += (double) (t.v[b].z * t.v[b].z); s += (double) (t.v[b].w * t.v[b].w); }
                 }
             }
-            s = wave_sum_f64(s);
+            if constexpr (MidStaged<MID>::value) {       // wave_sum_f64(), with the stage points between its steps
+                mid_at<BAMD_ST_SQ>(mid, 0);
+                s += dpp_d<DPP_XOR1>(s);        mid_at<BAMD_ST_SQ1>(mid, 0);
+                s += dpp_d<DPP_XOR2>(s);        mid_at<BAMD_ST_SQ2>(mid, 0);
+                s += dpp_d<DPP_HALF_MIRROR>(s); mid_at<BAMD_ST_SQ3>(mid, 0);
+                s += dpp_d<DPP_MIRROR>(s);      mid_at<BAMD_ST_SQ4>(mid, 0);
+                s = ((readlane_d(s, 15) + readlane_d(s, 31)) + readlane_d(s, 47)) + readlane_d(s, 63);
+            } else s = wave_sum_f64(s);
             if (lane == 0) red[wave] = s;
             TL_STAMP(tl, 5);
             __syncthreads();
-            mid();
+            if constexpr (MidStaged<MID>::value) mid_at<BAMD_ST_BAR>(mid, 0); else mid();
             double tot = 0.0;
             for (int w2 = 0; w2 < nwaves; ++w2) tot += red[w2];
+            mid_at<BAMD_ST_RED>(mid, 0);
             // sum / n in double (ggml.c:11879).  For n a power of two (4096, 8192) the quotient is an exact scaling, so the product with the
             // exact reciprocal is the same double — without the ~30 dependent f64 instructions of an IEEE division
             double md = (K & (K - 1)) == 0 ? tot * (1.0 / (double) K) : tot / (double) K;
@@ -431,9 +489,14 @@ struct ActPro {
                 md = red[0] / (double) K;
                 mean = (float) md;
             }
+            mid_at<BAMD_ST_MEAN>(mid, 0);
             scale = 1.0f / sqrtf(mean + eps);
-        } else mid();
-        quantize_batch<NB, NWV>(scale, K, wave, q8, S, yd);
+            mid_at<BAMD_ST_SCALE>(mid, 0);
+        } else if constexpr (MidStaged<MID>::value) mid_span<BAMD_ST_SQ, BAMD_ST_SCALE + 1>(mid);
+        else mid();
+        if constexpr (MidStaged<MID>::value) quantize_batch<NB, NWV, MID &>(scale, K, wave, q8, S, yd, 0, 0, mid);
+        else quantize_batch<NB, NWV>(scale, K, wave, q8, S, yd);          // a plain functor is done (BAMD_ST_BAR)
+        mid_at<BAMD_ST_END>(mid, 0);
         if (!SMALLK) for (int i0 = wave + step; i0 < nb; i0 += step) {
             ActPro<NORM> t; t.issue(x, nw, K, i0);
             t.quantize_batch(scale, K, i0, q8, S, yd);
@@ -554,6 +617,57 @@ __device__ __forceinline__ void load_rec(RecQ2K & R, bamd_rsrc rs, int soff, int
     R.qs = bl64(rs, l * 8u, soff);
     R.sc = bl128(rs, 512u + (l >> 3) * 16u, soff);
     R.dd = bl32(rs, 640u + (l >> 3) * 4u, soff);
+}
+// load_rec request by request: a record takes RecLoads<REC>::value requests and load_rec_part<P> is request P of them, in load_rec's order (the staged
+// ring fill of the mode-A prologues deals single requests over ActPro's stage points).  Keep the two in step
+template <typename REC> struct RecLoads;
+template <> struct RecLoads<RecQ4K> { static constexpr int value = BAMD_XSCALES ? 3 : 2; };
+template <> struct RecLoads<RecQ5K> { static constexpr int value = BAMD_XSCALES ? 4 : 3; };
+template <> struct RecLoads<RecQ6K> { static constexpr int value = 4; };
+template <> struct RecLoads<RecQ3K> { static constexpr int value = 6; };
+template <> struct RecLoads<RecQ2K> { static constexpr int value = 3; };
+template <int P> __device__ __forceinline__ void load_rec_part(RecQ4K & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane;
+    if (P == 0) R.qs = bl128(rs, l * 16u, soff);
+    if (P == 1) R.hd = bl128(rs, 1024u + (l >> 3) * 16u, soff);
+#if BAMD_XSCALES
+    if (P == 2) R.mn47 = bl32(rs, 1152u + (l >> 3) * 4u, soff);
+#else
+    if (P == 1) R.mn47 = 0u;
+#endif
+}
+template <int P> __device__ __forceinline__ void load_rec_part(RecQ5K & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane;
+    if (P == 0) R.qs = bl128(rs, l * 16u, soff);
+    if (P == 1) R.qh = bl32(rs, 1024u + l * 4u, soff);
+    if (P == 2) R.hd = bl128(rs, 1280u + (l >> 3) * 16u, soff);
+#if BAMD_XSCALES
+    if (P == 3) R.mn47 = bl32(rs, 1408u + (l >> 3) * 4u, soff);
+#else
+    if (P == 2) R.mn47 = 0u;
+#endif
+}
+template <int P> __device__ __forceinline__ void load_rec_part(RecQ6K & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane;
+    if (P == 0) R.ql = bl128(rs, l * 16u, soff);
+    if (P == 1) R.qh = bl64(rs, 1024u + l * 8u, soff);
+    if (P == 2) R.sc = bl64(rs, 1536u + (l >> 3) * 16u + ((l >> 2) & 1u) * 8u, soff);
+    if (P == 3) R.d  = bl16(rs, 1664u + (l >> 3) * 2u, soff);
+}
+template <int P> __device__ __forceinline__ void load_rec_part(RecQ3K & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane;
+    if (P == 0) R.qs = bl64(rs, l * 8u, soff);
+    if (P == 1) R.hm = bl32(rs, 512u + l * 4u, soff);
+    if (P == 2) R.sc0 = bl32(rs, 768u + (l >> 3) * 12u, soff);
+    if (P == 3) R.sc1 = bl32(rs, 772u + (l >> 3) * 12u, soff);
+    if (P == 4) R.sc2 = bl32(rs, 776u + (l >> 3) * 12u, soff);
+    if (P == 5) R.d  = bl16(rs, 864u + (l >> 3) * 2u, soff);
+}
+template <int P> __device__ __forceinline__ void load_rec_part(RecQ2K & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane;
+    if (P == 0) R.qs = bl64(rs, l * 8u, soff);
+    if (P == 1) R.sc = bl128(rs, 512u + (l >> 3) * 16u, soff);
+    if (P == 2) R.dd = bl32(rs, 640u + (l >> 3) * 4u, soff);
 }
 // 6-bit scale/min unpack, ggml-quants.c:6928-6933
 __device__ __forceinline__ void unpack_k4(const uint4 & hd, uint32_t & sc03, uint32_t & sc47, uint32_t & mn03, uint32_t & mn47) {

@@ -33,6 +33,42 @@ __device__ __forceinline__ ProArgs carve_lds(const bamd_mv_args & a, unsigned ch
 }
 
 
+// ---- the staged second half of a mode-A ring (ActPro's stage points, bamd_device.h) -------------------------------------------------------------
+// BAMD_RING_DRIP: where the fast mode-A kernels request slots D/2 .. D-1 of their ring inside the RMSNorm prologue (BAMD_RING_SPLIT)
+//   0  one burst behind the first barrier (the plain functor)
+//   1  dealt over the stage points behind the first barrier, up to the two divisions of the quantisation
+//   2  as 1, starting among the f64 DPP steps of the sum of squares, in front of the first barrier
+//   3  all of them behind the quantisation, in front of the last barrier
+// The requests n = 0 .. NL - 1 of the half ring go out in slot order (slot D/2 is consumed first), request by request of a record (load_rec_part):
+// ceil(NL / stages) of them at each stage point from the first one on, every one exactly once on every path through the prologue.  The order of the
+// requests, and so the counted waits of the streaming loop, are those of the burst.  Measured: profiles/prologue_ring.txt.
+#ifndef BAMD_RING_DRIP
+#define BAMD_RING_DRIP 1
+#endif
+// BAMD_RING_DRIP_B: the same for the split-K kernels whose ring is split (BAMD_RING_SPLIT_B: rings of at least BAMD_RING_SPLIT_MIN records — the 70B widths
+// and the Q6_K seven-record rings, not the 8B QKV / ffn_down launches).  0 until those configurations are measured with it (profiles/prologue_ring.txt)
+#ifndef BAMD_RING_DRIP_B
+#define BAMD_RING_DRIP_B 0
+#endif
+// waves per workgroup of the fast mode-A kernels, for their shared prologue: every launcher of them uses 512 threads (0: read blockDim)
+#ifndef BAMD_PRO_NWV_A
+#define BAMD_PRO_NWV_A 8
+#endif
+// one(StageC<n>) issues request n; the requests of a stage point are fenced so that hipcc does not cluster them again
+template <int MODE, int ST, int NL, typename ONE> __device__ __forceinline__ void drip_stage(ONE && one) {
+    constexpr int FIRST = MODE == 2 ? BAMD_ST_SQ1 : MODE == 3 ? BAMD_ST_END : BAMD_ST_BAR, LAST = MODE == 3 ? BAMD_ST_END : BAMD_ST_DIV;
+    constexpr int NS = LAST - FIRST + 1, PER = (NL + NS - 1) / NS, k = ST - FIRST;
+    static_assert(NS >= 1 && PER * NS >= NL, "every request has a stage point");
+    if constexpr (k >= 0 && k < NS) {
+        constexpr int lo = k * PER < NL ? k * PER : NL, hi = (k + 1) * PER < NL ? (k + 1) * PER : NL;
+        if constexpr (lo < hi) {
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<lo, hi>(one);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
 // device-internal epilogues of stream_segment (matvec_gateup14_kernel): HALF a gate/up pair per wave — the gate row's value goes to the partner wave
 // through LDS (`res` = the slot of 8 floats, `out` reinterpreted: see the kernel), the up row's wave waits for it and stores silu(gate) * up
 #define BAMD_EPI_HALF_GATE 16
@@ -78,12 +114,22 @@ __device__ __forceinline__ void stream_segment(const uint8_t * __restrict__ wA, 
     TL_STAMP(pa.tl, 1);
     if (do_pro) {
         if (RSPLIT) {
+#if BAMD_RING_DRIP
+            constexpr int LPR = RecLoads<REC>::value;
+            auto second_half = [&](auto st) {
+                drip_stage<BAMD_RING_DRIP, decltype(st)::value, (D - D / 2) * LPR>([&](auto n) {
+                    constexpr int s = D / 2 + decltype(n)::value / LPR;
+                    load_rec_part<decltype(n)::value % LPR>(ring[s], rsA, offA + s * fill_step, lane);
+                });
+            };
+#else
             auto second_half = [&]() {
 #pragma unroll
                 for (int s = D / 2; s < D; ++s) load_rec(ring[s], rsA, offA + s * fill_step, lane);
             };
-            BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP, 0);
-        } else if (SMALLK) { auto nm = []() { }; BAMD_PRO_FINISH_NB_MID(ap, pa, nm, NBP, 0); }
+#endif
+            BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP, BAMD_PRO_NWV_A);
+        } else if (SMALLK) { auto nm = []() { }; BAMD_PRO_FINISH_NB_MID(ap, pa, nm, NBP, BAMD_PRO_NWV_A); }
         else BAMD_PRO_FINISH(ap, pa);
     } else if (RSPLIT) {
 #pragma unroll
@@ -187,11 +233,21 @@ __device__ __forceinline__ void stream_pair_short(const uint8_t * __restrict__ w
 #pragma unroll
     for (int s = 0; s < D / 2; ++s) load_rec(ring[s], BAMD_GU7_UP(s) ? rsU : rsG, BAMD_GU7_OFF(s), lane);
     TL_STAMP(pa.tl, 1);
+#if BAMD_RING_DRIP
+    constexpr int LPR = RecLoads<REC>::value;
+    auto second_half = [&](auto st) {
+        drip_stage<BAMD_RING_DRIP, decltype(st)::value, (D - D / 2) * LPR>([&](auto n) {
+            constexpr int s = D / 2 + decltype(n)::value / LPR;
+            load_rec_part<decltype(n)::value % LPR>(ring[s], BAMD_GU7_UP(s) ? rsU : rsG, BAMD_GU7_OFF(s), lane);
+        });
+    };
+#else
     auto second_half = [&]() {
 #pragma unroll
         for (int s = D / 2; s < D; ++s) load_rec(ring[s], BAMD_GU7_UP(s) ? rsU : rsG, BAMD_GU7_OFF(s), lane);
     };
-    BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP, 0);
+#endif
+    BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, NBP, BAMD_PRO_NWV_A);
     TL_STAMP(pa.tl, 2);
     const uint32_t * q8 = pa.q8; const int * S = pa.S; const float * yd = pa.yd;
     RowAcc Ag = { 0.f, 0.f }, Au = { 0.f, 0.f };
@@ -331,7 +387,17 @@ __device__ __forceinline__ void split_stream(const uint8_t * __restrict__ w, int
             if (RSPLIT) ring_fill(DH, D);
             if (NBW > BAMD_ACT_BATCH) ap2.template quantize_batch<BAMD_NB2(NBW)>(1.0f, pa.K, i0 + BAMD_ACT_BATCH, pa.q8, pa.S, pa.yd, 1, i0 + n_w);
         } else if (SMALLK && !UNEVEN) {                      // shared prologue of a fast kernel: NBW blocks per wave (issued with BAMD_PRO_ISSUE_NB at entry)
+#if BAMD_RING_DRIP_B
+            constexpr int LPR = RecLoads<REC>::value;
+            auto second_half = [&](auto st) {            // slot sl = (m, j), as in ring_fill
+                if constexpr (RSPLIT) drip_stage<BAMD_RING_DRIP_B, decltype(st)::value, (D - DH) * LPR>([&](auto n) {
+                    constexpr int sl = DH + decltype(n)::value / LPR;
+                    load_rec_part<decltype(n)::value % LPR>(ring[sl], rs, bbase + (sl / NBW) * rg_step + (sl % NBW) * RECB, lane);
+                });
+            };
+#else
             auto second_half = [&]() { if (RSPLIT) ring_fill(DH, D); };
+#endif
             BAMD_PRO_FINISH_NB_MID(ap, pa, second_half, BAMD_NB1(NBW), NWV);
         }
         else if (SMALLK) BAMD_PRO_FINISH_SMALLK(ap, pa);

@@ -22,7 +22,7 @@ __global__ void __launch_bounds__(512) matvec_fast_kernel(BAMD_LEAD_PARAMS, bamd
     const int nb = a.K >> 8;
     const ProArgs pa = carve_lds(a, smem);
     ActPro<PRO == BAMD_PRO_NORM> ap;
-    BAMD_PRO_ISSUE_NB(ap, pa, NBP, 0);                          // activation requests: the first memory instructions of the kernel
+    BAMD_PRO_ISSUE_NB(ap, pa, NBP, BAMD_PRO_NWV_A);                          // activation requests: the first memory instructions of the kernel
     const int wave = wave_id(), nwaves = blockDim.x >> 6;
     const int slot = blockIdx.x + gridDim.x * wave;          // consecutive row-groups land on different CUs
     const int stride = gridDim.x * nwaves;
@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(512) matvec_gateup7_kernel(BAMD_LEAD_PARAMS, b
     const int nb = a.K >> 8;
     const ProArgs pa = carve_lds(a, smem);
     ActPro<true> ap;
-    BAMD_PRO_ISSUE_NB(ap, pa, NBP, 0);
+    BAMD_PRO_ISSUE_NB(ap, pa, NBP, BAMD_PRO_NWV_A);
     const int wave = wave_id(), grid = (int) gridDim.x, b = (int) blockIdx.x;
     float4 * park = (float4 *) (smem + mv_park_off(nb));
     int * flags = (int *) (smem + mv_park_off(nb) + mv_gu7_park_bytes(16));
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(512) matvec_gateup14_kernel(BAMD_LEAD_PARAMS, 
     const int nb = a.K >> 8;
     const ProArgs pa = carve_lds(a, smem);
     ActPro<true> ap;
-    BAMD_PRO_ISSUE_NB(ap, pa, NBP, 0);
+    BAMD_PRO_ISSUE_NB(ap, pa, NBP, BAMD_PRO_NWV_A);
     const int wave = wave_id(), grid = (int) gridDim.x, b = (int) blockIdx.x;
     float * slots = (float *) (smem + mv_park_off(nb));     // [2 half pairs][8 rows]
     int * flags = (int *) (slots + 16);
