@@ -86,6 +86,8 @@ def lib():
         L.bamd_trace_attn_wo.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         L.bamd_set_aql.argtypes = [ci]; L.bamd_set_aql.restype = None
         L.bamd_aql_runs.argtypes = [vp]
+        L.bamd_set_aql_stall_ms.argtypes = [ci]; L.bamd_set_aql_stall_ms.restype = None
+        L.bamd_aql_stats.argtypes = [ci, C.POINTER(C.c_uint64)]; L.bamd_aql_stats.restype = None
         _lib = L
     return _lib
 
@@ -146,6 +148,20 @@ def set_aql(on):
     """True (default): Context.generate_greedy replays the step as AQL packets with fence scope NONE on the library's own HSA queue (csrc/bamd_aql.h) where it
     can; False: one hipGraph per step on the context's HIP stream.  Same kernels, same bits.  Takes effect at the next generate_greedy call."""
     lib().bamd_set_aql(int(bool(on)))
+
+
+def set_aql_stall_ms(ms):
+    """the own queue's stall limit in ms: a run fails once the queue's read index has not moved for that long, however long the run itself takes.  ms <= 0 restores
+    the default, 60 000.  Takes effect at the next run.  A test hook."""
+    lib().bamd_set_aql_stall_ms(int(ms))
+
+
+def aql_stats(device=0):
+    """counters of the device's own queue since the library was loaded: packets written, room_waits (replays that found the ring full at least once before they
+    were written), wrap_doorbells (extra doorbells at the ring's last slot inside a replay) and the ring size; all 0 where the own queue is off or unavailable"""
+    out = (C.c_uint64 * 4)()
+    lib().bamd_aql_stats(int(device), out)
+    return {"packets": int(out[0]), "room_waits": int(out[1]), "wrap_doorbells": int(out[2]), "ring": int(out[3])}
 
 
 def device_count():

@@ -6,6 +6,7 @@
 #include <hsa/hsa_ext_amd.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -27,15 +28,20 @@ std::string hsa_err(const char * what, hsa_status_t st) { const char * m = ""; h
 struct Kernel { uint64_t object = 0; uint32_t kernarg_size = 0, group_size = 0, private_size = 0; };
 
 struct Device {
-    bool tried = false, ok = false; std::string why;
+    bool tried = false; std::atomic<bool> ok{false}, gave_up{false}; std::string why;   // why is written before ok / gave_up change, read after them
     hsa_agent_t agent{}; hsa_queue_t * q = nullptr; hsa_signal_t done{};
     std::vector<hsa_executable_t> exes;
     std::map<std::string, Kernel> kernels;          // by code-object symbol name (mangled kernel name + ".kd"), filled on demand
     uint64_t widx = 0;                              // packets written so far (this library is the queue's only producer)
+    uint64_t widx0 = 0;                             // the queue's write index when it was created: packets = widx - widx0
+    uint64_t room_waits = 0, wrap_doorbells = 0;    // bamd_aql_stats, under mu
+    uint64_t tick_hz = 1000000000ull;               // unit of hsa_signal_wait's timeout (HSA_SYSTEM_INFO_TIMESTAMP_FREQUENCY)
     std::mutex mu;                                  // one replay at a time per device
 };
 Device g_dev[16];
 std::mutex g_mu;
+const int STALL_MS_DEFAULT = 60000;
+std::atomic<int> g_stall_ms{STALL_MS_DEFAULT};      // bamd_aql_set_stall_ms: the longest time a run goes on without the queue's read index moving
 
 struct AgentPick { std::vector<hsa_agent_t> gpus; };
 hsa_status_t agent_cb(hsa_agent_t ag, void * data) {
@@ -94,7 +100,8 @@ Device * device_get(int device) {
         d.exes.push_back(ex);
     }
     if (d.exes.empty()) { d.why = "no embedded code objects"; return &d; }
-    d.widx = hsa_queue_load_write_index_relaxed(d.q);
+    d.widx = d.widx0 = hsa_queue_load_write_index_relaxed(d.q);
+    if (hsa_system_get_info(HSA_SYSTEM_INFO_TIMESTAMP_FREQUENCY, &d.tick_hz) != HSA_STATUS_SUCCESS || !d.tick_hz) d.tick_hz = 1000000000ull;
     d.ok = true;
     return &d;
 }
@@ -136,6 +143,7 @@ struct bamd_aql_graph {
     int device = 0;
     std::vector<hsa_kernel_dispatch_packet_t> packets;   // headers filled at submission
     void * kernarg_dev = nullptr;                        // device memory (kernel arguments in host memory cost 24 us per launch: profiles/r03_aql_probe.txt, `hostargs`)
+    bool abandoned = false;                              // a run of this graph gave up with packets the queue may still read: kernarg_dev is never freed
 };
 
 int bamd_aql_available(int device, const char ** why) {
@@ -191,8 +199,20 @@ int bamd_aql_graph_launches(const bamd_aql_graph * g) { return g ? (int) g->pack
 
 void bamd_aql_free(bamd_aql_graph * g) {
     if (!g) return;
-    if (g->kernarg_dev) { hipSetDevice(g->device); hipFree(g->kernarg_dev); }
+    if (g->kernarg_dev && !g->abandoned) { hipSetDevice(g->device); hipFree(g->kernarg_dev); }   // abandoned: leaked on purpose (bamd_aql_run, give_up)
     delete g;
+}
+
+int bamd_aql_gave_up(int device) { return device >= 0 && device < 16 && g_dev[device].gave_up.load(std::memory_order_acquire) ? 1 : 0; }
+
+void bamd_aql_set_stall_ms(int ms) { g_stall_ms.store(ms > 0 ? ms : STALL_MS_DEFAULT, std::memory_order_relaxed); }
+
+void bamd_aql_get_stats(int device, uint64_t out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0;
+    Device * d = device_get(device);
+    if (!d || (!d->ok && !d->gave_up)) return;           // switched off or unavailable: all zero (a queue that gave up keeps its counts)
+    std::lock_guard<std::mutex> lk(d->mu);
+    out[0] = d->widx - d->widx0; out[1] = d->room_waits; out[2] = d->wrap_doorbells; out[3] = d->q->size;
 }
 
 // fence scopes of the packets between the first and the last of a run: 0 = none (default), 1 = agent (what a HIP stream issues: BAMD_AQL_SCOPE=agent, the A/B)
@@ -205,6 +225,7 @@ int bamd_aql_run(bamd_aql_graph * g, int replays, double * seconds, const char *
     if (!g || replays < 1) { if (why) *why = "nothing to run"; return 1; }
     Device & d = g_dev[g->device];
     std::lock_guard<std::mutex> lk(d.mu);
+    if (!d.ok) { if (why) *why = d.why.c_str(); return 1; }           // (a queue that gave up: the engine asks bamd_aql_gave_up first and replays its hipGraphs)
     hsa_queue_t * q = d.q;
     const uint32_t mask = q->size - 1;
     const size_t P = g->packets.size();
@@ -216,12 +237,47 @@ int bamd_aql_run(bamd_aql_graph * g, int replays, double * seconds, const char *
                            (acq << HSA_PACKET_HEADER_SCACQUIRE_FENCE_SCOPE) | (rel << HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE));
     };
     hsa_signal_store_relaxed(d.done, 1);
-    const auto t0 = std::chrono::steady_clock::now();
-    const auto deadline = t0 + std::chrono::seconds(60);
+    typedef std::chrono::steady_clock clock;
+    const auto t0 = clock::now();
+    // the stall rule: a run may take as long as it likes, but the queue's read index has to move at least once per `stall`
+    const auto stall = std::chrono::milliseconds(g_stall_ms.load(std::memory_order_relaxed));
+    uint64_t seen = hsa_queue_load_read_index_scacquire(q);
+    auto moved_at = t0;                                                // when `seen` last grew (as far as this thread looked)
+    auto stalled = [&](uint64_t rd) {                                  // true: a whole `stall` has passed since the read index last moved
+        const auto now = clock::now();
+        if (rd > seen) { seen = rd; moved_at = now; return false; }
+        return now - moved_at > stall;
+    };
+    // giving up never leaves with packets in flight unnoticed: the queue gets one more `stall` to read everything written (and to signal, when the last packet is
+    // in the ring).  A queue that does not is dead from here on: bamd_aql_available says no, bamd_aql_gave_up says yes, the contexts replay their hipGraphs.  Unless
+    // the run's last packet is known to have completed, this graph's argument block is never freed (bamd_aql_free): the GPU may still read it
+    auto give_up = [&](const char * what, bool last_written) {
+        const auto until = clock::now() + stall;
+        bool drained = false, signalled = false;
+        do {
+            drained = hsa_queue_load_read_index_scacquire(q) >= d.widx;
+            signalled = last_written && hsa_signal_load_scacquire(d.done) < 1;
+        } while (!(drained && (signalled || !last_written)) && clock::now() < until);
+        std::string text = what;
+        if (!signalled) { g->abandoned = true; text += "; the kernel-argument block of the run is leaked, the GPU may still read it"; }
+        if (!drained) {
+            d.why = text + "; the own queue of this device is not used again";
+            d.gave_up.store(true, std::memory_order_release); d.ok = false;
+            text = d.why;
+        } else text += "; the queue has read every packet since";
+        if (seconds) *seconds = std::chrono::duration<double>(clock::now() - t0).count();
+        if (why) *why = why_(text);
+        return 1;
+    };
     for (int r = 0; r < replays; ++r) {
         // room for one replay: the ring holds q->size packets, the packet processor has consumed everything below the read index
-        while (d.widx + P - hsa_queue_load_read_index_scacquire(q) > q->size) {
-            if (std::chrono::steady_clock::now() > deadline) { if (why) *why = "the queue stopped consuming packets"; return 1; }
+        uint64_t rd = hsa_queue_load_read_index_scacquire(q);
+        if (d.widx + P - rd > q->size) {
+            d.room_waits += 1;
+            do {
+                if (stalled(rd)) return give_up("the queue stopped consuming packets", false);
+                rd = hsa_queue_load_read_index_scacquire(q);
+            } while (d.widx + P - rd > q->size);
         }
         hsa_kernel_dispatch_packet_t * ring = (hsa_kernel_dispatch_packet_t *) q->base_address;
         for (size_t i = 0; i < P; ++i) {
@@ -239,14 +295,19 @@ int bamd_aql_run(bamd_aql_graph * g, int replays, double * seconds, const char *
             if (((d.widx + i) & mask) == mask && i + 1 < P) {
                 hsa_queue_store_write_index_screlease(q, d.widx + i + 1);
                 hsa_signal_store_screlease(q->doorbell_signal, (hsa_signal_value_t) (d.widx + i));
+                d.wrap_doorbells += 1;
             }
         }
         d.widx += P;
         hsa_queue_store_write_index_screlease(q, d.widx);
         hsa_signal_store_screlease(q->doorbell_signal, (hsa_signal_value_t) (d.widx - 1));
     }
-    const hsa_signal_value_t v = hsa_signal_wait_scacquire(d.done, HSA_SIGNAL_CONDITION_LT, 1, 60ull * 1000 * 1000 * 1000, HSA_WAIT_STATE_ACTIVE);
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (v >= 1) { if (why) *why = "timed out waiting for the completion signal of the own queue"; return 1; }
+    // the completion signal, in slices of `stall` (hsa_signal_wait counts in ticks of the system timestamp and may return early): given up only when the signal
+    // is still up after a slice in which the read index did not move
+    const uint64_t slice = (uint64_t) ((double) stall.count() * 1e-3 * (double) d.tick_hz) + 1;
+    while (hsa_signal_wait_scacquire(d.done, HSA_SIGNAL_CONDITION_LT, 1, slice, HSA_WAIT_STATE_ACTIVE) >= 1) {
+        if (stalled(hsa_queue_load_read_index_scacquire(q))) return give_up("timed out waiting for the completion signal of the own queue", true);
+    }
+    if (seconds) *seconds = std::chrono::duration<double>(clock::now() - t0).count();
     return 0;
 }

@@ -56,7 +56,17 @@ int bamd_aql_available(int device, const char ** why);
 // turns a finished recording into packets for `device`: kernel objects resolved, kernel arguments (explicit + the hidden block of code object v5) in
 // kernarg memory.  nullptr + *why on failure (an unknown kernel, an allocation)
 bamd_aql_graph * bamd_aql_build(int device, const bamd_aql_recording & rec, const char ** why);
-// `replays` back-to-back replays of the graph; returns when the last packet has completed (or 1 after `timeout_s`); *seconds = submit -> completion on the host clock
+// `replays` back-to-back replays of the graph; returns 0 when the last packet has completed; *seconds = submit -> completion on the host clock.  There is no limit
+// on the run, only on a stall: 1 + *why once the queue's read index has not moved for the stall limit (bamd_aql_set_stall_ms), while waiting for room in the ring
+// or for the completion signal.  Before that return the queue gets one more limit to read what was written; if it does not, the device's own queue is dead
+// (bamd_aql_available 0, bamd_aql_gave_up 1 from then on), and unless the run's last packet completed the graph's argument block is leaked, not freed
 int bamd_aql_run(bamd_aql_graph * g, int replays, double * seconds, const char ** why);
 int bamd_aql_graph_launches(const bamd_aql_graph * g);
 void bamd_aql_free(bamd_aql_graph * g);
+// 1 once a run on `device` gave up on a queue that stayed stuck: graphs built before then must not be run again (one atomic load, no lock)
+int bamd_aql_gave_up(int device);
+// the stall limit of the runs that start from now on, in ms; <= 0: the default, 60 000
+void bamd_aql_set_stall_ms(int ms);
+// out[0] packets written so far, out[1] replays that found the ring full at least once before they were written, out[2] extra doorbells rung at the ring's last
+// slot inside a replay, out[3] the ring's size in packets; all 0 where the own queue is switched off or unavailable
+void bamd_aql_get_stats(int device, uint64_t out[4]);

@@ -44,6 +44,8 @@ static const bool g_attn_fused = [] { const char * e = getenv("BAMD_ATTN_FUSED")
 // NONE on the library's own queue (bamd_aql.h).  Same kernels, same bits; BAMD_AQL_VERBOSE=1 says why when the own queue is not used
 static int g_aql = [] { const char * e = getenv("BAMD_AQL"); return (e && e[0] == '0') ? 0 : 1; }();
 extern "C" __attribute__((visibility("default"))) void bamd_set_aql(int on) { g_aql = on ? 1 : 0; }
+extern "C" __attribute__((visibility("default"))) void bamd_set_aql_stall_ms(int ms) { bamd_aql_set_stall_ms(ms); }
+extern "C" __attribute__((visibility("default"))) void bamd_aql_stats(int device, uint64_t out[4]) { bamd_aql_get_stats(device, out); }
 
 extern "C" __attribute__((visibility("default"))) const char * bamd_last_error(void) { return g_err.c_str(); }
 
@@ -611,7 +613,7 @@ static int set_state(bamd_context * c, int pos_base, hipStream_t s, bool keep_ke
 // May a step with this attention path run as AQL packets on the library's own queue (bamd_aql.h)?  Only the launch sequences whose kernels keep the inter-kernel rules of bamd_device.h: the single-launch
 // attention path, and the scores | softmax + P.V path of long sequences when its kernels are the clean ones; anything else (shifted cells, score rows beyond the LDS) replays a hipGraph
 static bool aql_allowed(const bamd_context * c, AttnPath path) {
-    if (!g_aql || c->aql_failed || path == ATTN_CELLS) return false;
+    if (!g_aql || c->aql_failed || path == ATTN_CELLS || bamd_aql_gave_up(c->m->device)) return false;     // (gave up: a run found the device's queue stuck, bamd_aql_run)
     if (path == ATTN_SINGLE) return true;
     const bamd_model * m = c->m;
     bamd_attn_args t; memset(&t, 0, sizeof t); t.hd = m->hd; t.Hkv = m->Hkv; t.n_ctx = c->n_ctx_pad;

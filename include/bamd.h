@@ -82,6 +82,12 @@ int bamd_kv_seq_div(bamd_context * c, int p0, int p1, int d);
 int bamd_generate_greedy(bamd_context * c, int n_past, int n_steps, int32_t * out_tokens, float * elapsed_ms);
 void bamd_set_aql(int on);                 /* process-wide: 1 (default, also env BAMD_AQL) = own AQL queue where possible; 0 = hipGraph replays */
 int bamd_aql_runs(const bamd_context * c); /* bamd_generate_greedy calls + single-token bamd_decode steps of this context that ran on the own queue so far */
+/* The own queue has no deadline for a run, only a stall limit: a run fails once the queue's read index has not moved for `ms` (default 60 000; ms <= 0
+ * restores it; takes effect at the next run).  A queue that stays stuck for one more limit is not used again: every context replays its hipGraphs from then on. */
+void bamd_set_aql_stall_ms(int ms);
+/* Counters of `device`'s own queue (tests: which path a run took): out[0] packets written so far, out[1] replays that found the ring full at least once before
+ * they were written, out[2] extra doorbells rung at the ring's last slot inside a replay, out[3] ring size in packets.  All 0 with BAMD_AQL=0 / no own queue. */
+void bamd_aql_stats(int device, uint64_t out[4]);
 
 /* ---- layer-split stage interface (one process per GPU; hidden state moves between stages) ---- */
 /* Run this stage's layers on one token.  The token id comes from `token`, or — when token_dev is non-NULL — from that
