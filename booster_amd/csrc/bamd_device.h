@@ -224,6 +224,8 @@ __device__ __forceinline__ double wave_sum_f64(double s) {                  // f
 __device__ __forceinline__ bool f32_rounding_safe(double v, int ulps) {
 #ifdef BAMD_NO_F64_GUARD                                                     /* experiment builds: shows that the constructed worst cases of tests/test_f64_order.py need the guard */
     return true;
+#elif defined(BAMD_F64_GUARD_ALWAYS)                                         /* its mirror: every reduction takes the sequential fallback (profiles/f64_guard_paths.txt) */
+    return false;
 #endif
     if (v == 0.0) return true;                                              // the same in any order (non-negative terms)
     const uint32_t hi = (uint32_t) __double2hiint(v), lo = (uint32_t) __double2loint(v);

@@ -135,3 +135,67 @@ def test_gpu_attention_equals_the_reference_on_the_constructed_row(skat, bamd, p
     else:
         got = bamd.op_attention(q, k, v, kc, vc, rope, H, Hkv, hd, n_ctx, pos, prefill_mode=prefill)
     assert_bits(got, want, "attention out on the constructed row")
+
+
+# ---- constructed inputs for any length (tests/golden/f64_order_kats.npz, f64_softmax_kats.npz; tests/golden/gen_f64_guard_kats.py): the SEQUENTIAL value
+#      sits within 8 units of an f32 rounding boundary, so every order of the same n terms (within 2 n units of it) lies inside the guard's band 2 n + 8:
+#      the sequential fallback runs whatever a kernel's tree is.  tests/test_gpu_f64_guard.py drives every fallback site with them ----
+ORDER_NAMES = ["K256", "K768", "K3072", "K4096", "K4096b", "K8192"]
+SOFTMAX_NAMES = ["v64_p64_hd64", "v96_p96_hd64", "v576_p576_hd64", "v4128_p4128_hd64", "v8224_p8224_hd64", "v64_p64_hd128", "v96_p96_hd128",
+                 "v80_p96_hd128", "v576_p576_hd128", "v64_p64_hd256", "v96_p96_hd64_holes", "v448_p448_hd128"]
+
+
+@pytest.fixture(scope="module")
+def okats():
+    return np.load(os.path.join(GOLDEN, "f64_order_kats.npz"))
+
+
+@pytest.fixture(scope="module")
+def skats():
+    return np.load(os.path.join(GOLDEN, "f64_softmax_kats.npz"))
+
+
+def test_fixtures_hold_every_length(okats, skats):
+    assert {n[2:] for n in okats.files if n.startswith("x_")} == set(ORDER_NAMES)
+    assert {n[2:] for n in skats.files if n.startswith("s_")} == set(SOFTMAX_NAMES)
+    assert np.array_equal(okats["x_K4096"], np.load(os.path.join(GOLDEN, "f64_order_kat.npz"))["x"])       # the existing vector meets the margin: reused
+
+
+@pytest.mark.parametrize("name", ORDER_NAMES)
+def test_rmsnorm_vector_sits_on_a_boundary_in_every_order(okats, po, name):
+    import f64_order_search as fs
+    x = okats["x_" + name]
+    K = int(name[1:].rstrip("b"))
+    assert x.size == K and x.dtype == np.float32
+    o = fs.sum_orders(fs.terms(x))
+    m_seq = fs.mean64(o["seq"], K)
+    assert np.float32(m_seq).view(np.uint32) == okats["mean_" + name].view(np.uint32)
+    assert int(fs.dist_units(m_seq)) <= fs.NEAR_UNITS == 8
+    assert len(o) >= 3 and all(fs.guard_fires(s, K) for s in o.values())          # the sequential order and three others of the same terms
+    assert list(okats["differs_" + name]) == sorted(n for n, s in o.items() if np.float32(fs.mean64(s, K)).view(np.uint32) != okats["mean_" + name].view(np.uint32))   # the recorded orders that round elsewhere
+    if K == fs.K:
+        assert fs.guarded_mean32(fs.terms(x))[1]                                  # ... and ActPro::finish's own tree at eight waves
+    # the oracle's RMSNorm is the sequential mean
+    scale = np.float32(1.0) / np.sqrt(np.float32(okats["mean_" + name] + okats["eps"]), dtype=np.float32)
+    assert np.array_equal(po.rms_norm(x, float(okats["eps"])).view(np.uint32), (x * scale).astype(np.float32).view(np.uint32))
+
+
+@pytest.mark.parametrize("name", SOFTMAX_NAMES)
+def test_softmax_row_sits_on_a_boundary_in_every_order(skats, po, name):
+    import f64_softmax_search as ss
+    s, scale = skats["s_" + name], skats["scale_" + name]
+    valid, padded, hd = (int(f[1:].lstrip("d")) for f in name.split("_")[:3])
+    assert s.size == padded and scale == np.float32(1.0) / np.sqrt(np.float32(hd)) and s[0] == 0.0
+    live = np.isfinite(s)
+    assert np.all(s[~live] == -np.inf) and not live[valid:].any() and (live[:valid].all() or name.endswith("_holes")) and live[valid - 1]
+    assert np.array_equal(s[live].astype(np.float16).astype(np.float32), s[live]) and np.all(s[live][1:] < 0)     # k_i . e_0 in an f16 cache gives them exactly
+    e = ss.row_exps(po, s, scale)
+    den = ss.row_denominators(e)
+    inv_seq = np.float32(1.0 / den["seq"])
+    assert inv_seq.view(np.uint32) == skats["inv_" + name].view(np.uint32)
+    assert int(ss.dist(np.array([1.0 / den["seq"]]))[0]) <= ss.NEAR_UNITS == 8
+    assert len(den) >= 3 and all(ss.guard_fires(t, padded) for t in den.values())
+    assert list(skats["differs_" + name]) == sorted(n for n, t in den.items() if np.float32(1.0 / t).view(np.uint32) != inv_seq.view(np.uint32))
+    # the oracle follows the reference: masked entries as a -inf mask on finite scores, as the attention builds them
+    p = po.soft_max(np.where(live, s, 0).astype(np.float32), np.where(live, 0, -np.inf).astype(np.float32), scale)
+    assert np.array_equal(p.view(np.uint32), (e * inv_seq).astype(np.float32).view(np.uint32))

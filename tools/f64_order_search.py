@@ -8,6 +8,11 @@ n = 4096 and
       the f32 mean, then a tiny last element walks it across one double-ulp at a time; where the two orders cross the boundary
       at different steps the two means differ by one f32 ulp.
     python tools/f64_order_search.py [n_random] [out.npz]
+    python tools/f64_order_search.py --near K [seed] [out.npz]
+  (c) for ANY length K (construct_near): a vector whose SEQUENTIAL f64 mean sits within NEAR_UNITS = 8 units of an f32 rounding boundary
+      (units of f32_rounding_safe: the low 29 mantissa bits D, boundary D = 2^28).  Any other order of the same K terms is within 2 K units of
+      the sequential one, i.e. inside the band 2 K + 8 in which the guard refuses the tree: the fallback runs whatever a kernel's tree is.
+      tests/golden/gen_f64_guard_kats.py stores such vectors (tests/golden/f64_order_kats.npz) for tests/test_gpu_f64_guard.py.
 """
 import sys
 
@@ -119,7 +124,85 @@ def construct(rng, tries=200):
     return None
 
 
+# ---- any length: a vector whose sequential mean is within NEAR_UNITS of a rounding boundary ---------------------------------------------------
+NEAR_UNITS = 8
+
+
+def dist_units(v):
+    """|D - 2^28| of doubles (array): the distance from an f32 rounding boundary in the units of f32_rounding_safe"""
+    lo = np.asarray(v, np.float64).view(np.uint64) & np.uint64(0x1fffffff)
+    return np.abs(lo.astype(np.int64) - (1 << 28))
+
+
+def mean64(s, K):
+    """sum / n in double (ggml.c:11879); for a power of two the kernels multiply by the exact reciprocal: the same double"""
+    return np.float64(s) / np.float64(K)
+
+
+def sum_orders(t):
+    """the same terms in the reference's order and in three others: dict name -> double"""
+    t = np.asarray(t, np.float64)
+    pair = t.copy()
+    while pair.size > 1:                                                 # pairwise tree (odd lengths: the last term rides along)
+        if pair.size & 1:
+            pair = np.concatenate([pair[:-1:2] + pair[1::2], pair[-1:]])
+        else:
+            pair = pair[0::2] + pair[1::2]
+    lanes = np.zeros(64, np.float64)                                     # 64 strided partial sums, then added in order
+    for i in range(0, t.size, 64):
+        c = t[i:i + 64]
+        lanes[:c.size] = lanes[:c.size] + c
+    return dict(seq=sum_seq(t), rev=sum_seq(t[::-1]), pairwise=float(pair[0]), lanes64=sum_seq(lanes))
+
+
+def guard_fires(s, K):
+    return not rounding_safe(float(mean64(s, K)), 2 * K + 8)
+
+
+def construct_near(K, rng, x0=None):
+    """x [K] f32 with dist_units(sequential mean) <= NEAR_UNITS.  K - 2 elements are random (the activation-like distribution of random_trials) or
+    taken from x0; the last two are searched: the sequential sum is (prefix + t_a) + t_b with the prefix computed once, t_a a coarse term (a typical
+    element: its candidates move D over its whole range) and t_b a fine one (below 2^-29 of the sum: steps of a unit or less)."""
+    x = (rng.standard_normal(K) * np.exp(rng.standard_normal(K) * 2.0)).astype(np.float32) if x0 is None else np.array(x0, np.float32)
+    prefix = sum_seq(terms(x[:K - 2]))
+    rms = np.sqrt(prefix)
+    best = None                                                          # (score, x): 2 = some order rounds to another f32, 1 = the orders' sums differ, 0 = all equal (an exact sum)
+    for attempt in range(64):
+        a = (rng.standard_normal(2048) * rms / np.sqrt(K)).astype(np.float32)
+        b = (rms * 2.0 ** -(14.5 + 1.5 * rng.random(32768))).astype(np.float32)
+        ta, tb = terms(a), terms(b)
+        for lo in range(0, a.size, 128):
+            m = ((prefix + ta[lo:lo + 128, None]) + tb[None, :]) / np.float64(K)
+            for k in np.flatnonzero(dist_units(m).ravel() <= NEAR_UNITS)[:8]:
+                y = x.copy()
+                y[K - 2], y[K - 1] = a[lo + k // b.size], b[k % b.size]
+                o = sum_orders(terms(y))
+                assert int(dist_units(mean64(o["seq"], K))) <= NEAR_UNITS
+                score = 2 if len({int(np.float32(mean64(v, K)).view(np.uint32)) for v in o.values()}) > 1 else 1 if len(set(o.values())) > 1 else 0
+                if best is None or score > best[0]:
+                    best = (score, y)
+                if score == 2:
+                    return y
+        if best is not None:
+            return best[1]
+    return None
+
+
+def main_near(argv):
+    K = int(argv[0]); seed = int(argv[1]) if len(argv) > 1 else 0
+    x = construct_near(K, np.random.default_rng(seed))
+    assert x is not None, "nothing found"
+    o = sum_orders(terms(x))
+    for name, s in o.items():
+        print("%-9s mean %r (bits %08x), %d units from the boundary, guard fires: %s" % (name, float(np.float32(mean64(s, K))), np.float32(mean64(s, K)).view(np.uint32), int(dist_units(mean64(s, K))), guard_fires(s, K)))
+    if len(argv) > 2:
+        np.savez_compressed(argv[2], x=x, mean_seq=np.float32(mean64(o["seq"], K)))
+        print("wrote", argv[2])
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[1] == "--near":
+        return main_near(sys.argv[2:])
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     rng = np.random.default_rng(17)
     d = random_trials(n, rng)
