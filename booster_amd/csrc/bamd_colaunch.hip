@@ -17,7 +17,7 @@
 // uses of the granules, which are never reset.  Same arithmetic, same order, same bits as the two separate launches (tests/test_gpu_colaunch.py).
 #include "bamd_matvec_core.h"
 #include "bamd_attn_fused.h"
-#include "bamd_q1_device.h"
+#include "bamd_b32_device.h"
 
 // two granules of another workgroup's write-through output: L1 bypassed (sc1), as the producer stored them; each 8-byte half is one store
 __device__ __forceinline__ uint4 ld_coh128(bamd_rsrc r, uint32_t byte_off) {
@@ -170,125 +170,25 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     TL_STAMP(wo.tl, 7);
 }
 
-// ---- the same for a Q8_0 / Q4_0 / Q5_0 wo at K = 4096 (bamd_q0_device.h), in a kernel of its own: the K-quant instances above keep their code and registers.
-// wo_role with the Q8_0 activation form and the parked terms of matvec_q0_split_kernel (bamd_matvec_q0.hip): f[c][lane] and the scale products s[r][c],
-// BAMD_Q0_TERM_FLOATS per record, one term buffer per row-group of the workgroup; one wave per row-group then runs its K / 32-step chain in block order.
-constexpr size_t colaunch_q0_lds(int nb, int ld) {
-    const size_t t = mv_terms_off(nb) + (size_t) 3 * nb * BAMD_Q0_TERM_FLOATS * 4;
+// ---- the same for a wo of the 32-weight block formats at K = 4096 (bamd_b32_device.h), in a kernel of its own: the K-quant instances above keep their code and
+// registers.  wo_role with the Q8_0 / Q8_1 activation form and the parked terms of matvec_q0_split_kernel (bamd_matvec_b32.h): f[c][lane] and the scale products
+// s[r][c], for Q4_1 / Q5_1 also the row's eight m * s products ms[r][c] (8 x 8 floats behind the scale products) — b32_term_floats: 576 or 640 floats per record,
+// one term buffer per row-group of the workgroup; one wave per row-group then runs its K / 32-step chain in block order (and adds the m * s products in block
+// order into the row's scalar accumulator).
+constexpr size_t colaunch_b32_lds(bool has_min, int nb, int ld) {
+    const size_t t = mv_terms_off(nb) + (size_t) 3 * nb * b32_term_floats(has_min) * 4;
     return t > mv_lds_colaunch(nb, 3, ld) ? t : mv_lds_colaunch(nb, 3, ld);
 }
-template <int TYPE, int M>
-__device__ __forceinline__ void wo_role_q0(const bamd_mv_args & a, const ProArgs & pa, const int j, const int G, float * part0, const unsigned long long * gran,
-                                           const bamd_step_state * st, const int il, const int ring_delay_in, uint32_t * err) {
-    constexpr int NBW = 2, RECB = BAMD_RECB_OF(TYPE);
-    const int ring_delay = ring_delay_in & 0xff; const bool poll_sleep = (ring_delay_in >> 8) & 1;
-    const int nb = pa.K >> 8;
-    const int lane = threadIdx.x & 63, wave = wave_id(), r8 = lane >> 3;
-    const int i0 = wave * NBW;
-    const bamd_rsrc rs = weight_rsrc(a.seg[0].w);
-    const int rgb = nb * RECB;
-    for (int d = 0; d < ring_delay; ++d) __builtin_amdgcn_s_sleep(8);   // the attention role's first requests go first
-    RecQ0<TYPE> ring[M * NBW];
-#pragma unroll
-    for (int m = 0; m < M; ++m)
-#pragma unroll
-        for (int jj = 0; jj < NBW; ++jj) load_rec(ring[m * NBW + jj], rs, (j + m * G) * rgb + (i0 + jj) * RECB, lane);
-    const int nv = a.seg[0].nvalid > 0 ? a.seg[0].nvalid : a.seg[0].nrows;
-    const int crow = (j + (wave < M ? wave : 0) * G) * 8 + r8;          // the row whose chain this wave replays
-    float resv = 0.f;
-    if (crow < nv) resv = ik_ld(a.res + crow);
-    // this wave's slice of the attention output, re-read until every granule carries this launch's tag (wo_role); then Q8_0 into LDS, no workgroup barrier
-    ActProQ0<false> ap; ap.okmask = (1 << NBW) - 1;
-    {
-        const uint32_t tag = ((uint32_t) ik_ld_if<BAMD_IK_ST != 0>(&st->serial) << 20) | (((uint32_t) ik_ld_if<BAMD_IK_ST != 0>(&st->step) & 0xfffu) << 8) | (uint32_t) il;
-        const bamd_rsrc gr = weight_rsrc(gran);
-        unsigned spins = 0;
-        for (;;) {
-            asm volatile("" ::: "memory");
-            bool ok = true;
-#pragma unroll
-            for (int b = 0; b < NBW; ++b) {
-                const uint32_t off = (uint32_t) ((i0 + b) * 256 + lane * 4) * 8u;
-                const uint4 g0 = ld_coh128(gr, off), g1 = ld_coh128(gr, off + 16u);
-                ap.v[b] = make_float4(__uint_as_float(g0.x), __uint_as_float(g0.z), __uint_as_float(g1.x), __uint_as_float(g1.z));
-                ok = ok && g0.y == tag && g0.w == tag && g1.y == tag && g1.w == tag;
-            }
-            if (__all(ok)) break;
-            if (poll_sleep) __builtin_amdgcn_s_sleep(1);
-            if (++spins > BAMD_COLAUNCH_SPINS) { if (lane == 0) atomicAdd(err, 1u); break; }
-        }
-    }
-    float * ys = (float *) pa.S;
-    ap.template quantize_batch_q0<NBW>(1.0f, pa.K, i0, pa.q8, ys, 1, i0 + NBW);
-    const size_t rg_floats = (size_t) nb * BAMD_Q0_TERM_FLOATS;
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-#pragma unroll
-        for (int jj = 0; jj < NBW; ++jj) {
-            pin_rec(ring[m * NBW + jj]);
-            float sc[8], fd[8];
-            q0_terms(ring[m * NBW + jj], i0 + jj, lane, pa.q8, ys, sc, fd);
-            float * P = part0 + (size_t) m * rg_floats + (size_t) (i0 + jj) * BAMD_Q0_TERM_FLOATS;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) P[c * 64 + lane] = fd[c];
-            if ((lane & 7) == 0) {
-                *(float4 *) (P + 512 + r8 * 8) = make_float4(sc[0], sc[1], sc[2], sc[3]);
-                *(float4 *) (P + 512 + r8 * 8 + 4) = make_float4(sc[4], sc[5], sc[6], sc[7]);
-            }
-        }
-    }
-    __syncthreads();
-    if (wave < M) {
-        const float * B = part0 + (size_t) wave * rg_floats;
-        float acc = 0.f;
-        for (int ib = 0; ib < nb; ++ib) {
-            const float * P = B + (size_t) ib * BAMD_Q0_TERM_FLOATS;
-            const float4 s0 = *(const float4 *) (P + 512 + r8 * 8), s1 = *(const float4 *) (P + 512 + r8 * 8 + 4);
-            const float sc[8] = { s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w };
-            float fd[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) fd[c] = P[c * 64 + lane];
-            q0_chain8(acc, sc, fd);
-        }
-        const float val = q0_finish_row(acc);
-        if ((lane & 7) == 0 && crow < nv) ik_st(a.seg[0].out + crow, val + resv);
-    }
-}
-
-template <int LG, int TYPE>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) attn_wo_q0_kernel(bamd_attn_args at, int gq, bamd_mv_args wo, unsigned long long * gran, int il, int extra,
-                                                                                                       int ring_delay, uint32_t * err) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int H = at.Hkv * gq;
-    if ((int) blockIdx.x < H) {
-        const bamd_step_state * st = at.st;
-        const uint32_t tag = ((uint32_t) ik_ld_if<BAMD_IK_ST != 0>(&st->serial) << 20) | (((uint32_t) ik_ld_if<BAMD_IK_ST != 0>(&st->step) & 0xfffu) << 8) | (uint32_t) il;
-        attn_fused_body<LG, true>(at, gq, (int) blockIdx.x, 0, smem, (uint32_t *) gran, tag);
-        return;
-    }
-    const int j = (int) blockIdx.x - H, G = (int) gridDim.x - H;
-    const ProArgs pa = carve_lds(wo, smem);
-    float * part0 = (float *) (smem + mv_terms_off(wo.K >> 8));
-    if (j < extra) wo_role_q0<TYPE, 3>(wo, pa, j, G, part0, gran, at.st, il, ring_delay, err);      // the first `extra` workgroups take a third row-group
-    else           wo_role_q0<TYPE, 2>(wo, pa, j, G, part0, gran, at.st, il, ring_delay, err);
-}
-
-// ---- and for a Q4_1 / Q5_1 wo at K = 4096 (bamd_q1_device.h): wo_role_q0 with the Q8_1 activation form and a parked record that also carries the row's eight
-// m * s products, ms[r][c] (8 x 8 floats behind the scale products): BAMD_Q1_TERM_FLOATS = 640 floats = 2560 bytes per record.  The replaying wave adds them in
-// block order into the row's scalar accumulator.
-#define BAMD_Q1_TERM_FLOATS 640
-constexpr size_t colaunch_q1_lds(int nb, int ld) {
-    const size_t t = mv_terms_off(nb) + (size_t) 3 * nb * BAMD_Q1_TERM_FLOATS * 4;
-    return t > mv_lds_colaunch(nb, 3, ld) ? t : mv_lds_colaunch(nb, 3, ld);
-}
-static_assert(BAMD_Q1_TERM_FLOATS * 4 == 2560, "a parked Q4_1 / Q5_1 record: 8 x 64 dots + 8 x 8 scale products + 8 x 8 m * s products");
+static_assert(b32_term_floats(true) * 4 == 2560, "a parked Q4_1 / Q5_1 record: 8 x 64 dots + 8 x 8 scale products + 8 x 8 m * s products");
 // three row-groups x 16 records x 2560 B behind the activation image fit a CU's LDS, and so do the attention role's rows (the launch takes the larger of the two)
-static_assert(mv_terms_off(16) + (size_t) 3 * 16 * BAMD_Q1_TERM_FLOATS * 4 <= (size_t) BAMD_LDS_CU_BYTES && (size_t) BAMD_ATTN_LDS_MAX <= (size_t) BAMD_LDS_CU_BYTES
-              && colaunch_q1_lds(16, BAMD_ATTN_LDS_MAX / 8) <= (size_t) BAMD_LDS_CU_BYTES, "the Q4_1 / Q5_1 wo role does not fit the LDS of a CU");
+static_assert(mv_terms_off(16) + (size_t) 3 * 16 * b32_term_floats(true) * 4 <= (size_t) BAMD_LDS_CU_BYTES && (size_t) BAMD_ATTN_LDS_MAX <= (size_t) BAMD_LDS_CU_BYTES
+              && colaunch_b32_lds(true, 16, BAMD_ATTN_LDS_MAX / 8) <= (size_t) BAMD_LDS_CU_BYTES, "the Q4_1 / Q5_1 wo role does not fit the LDS of a CU");
 template <int TYPE, int M>
-__device__ __forceinline__ void wo_role_q1(const bamd_mv_args & a, const ProArgs & pa, const int j, const int G, float * part0, const unsigned long long * gran,
-                                           const bamd_step_state * st, const int il, const int ring_delay_in, uint32_t * err) {
+__device__ __forceinline__ void wo_role_b32(const bamd_mv_args & a, const ProArgs & pa, const int j, const int G, float * part0, const unsigned long long * gran,
+                                            const bamd_step_state * st, const int il, const int ring_delay_in, uint32_t * err) {
     constexpr int NBW = 2, RECB = BAMD_RECB_OF(TYPE);
+    constexpr bool MIN = b32_has_min(TYPE);
+    constexpr int TERM_FLOATS = b32_term_floats(MIN);
     const int ring_delay = ring_delay_in & 0xff; const bool poll_sleep = (ring_delay_in >> 8) & 1;
     const int nb = pa.K >> 8;
     const int lane = threadIdx.x & 63, wave = wave_id(), r8 = lane >> 3;
@@ -296,7 +196,7 @@ __device__ __forceinline__ void wo_role_q1(const bamd_mv_args & a, const ProArgs
     const bamd_rsrc rs = weight_rsrc(a.seg[0].w);
     const int rgb = nb * RECB;
     for (int d = 0; d < ring_delay; ++d) __builtin_amdgcn_s_sleep(8);   // the attention role's first requests go first
-    RecQ1<TYPE> ring[M * NBW];
+    RecB32<TYPE> ring[M * NBW];
 #pragma unroll
     for (int m = 0; m < M; ++m)
 #pragma unroll
@@ -305,7 +205,7 @@ __device__ __forceinline__ void wo_role_q1(const bamd_mv_args & a, const ProArgs
     const int crow = (j + (wave < M ? wave : 0) * G) * 8 + r8;          // the row whose chain this wave replays
     float resv = 0.f;
     if (crow < nv) resv = ik_ld(a.res + crow);
-    // this wave's slice of the attention output, re-read until every granule carries this launch's tag (wo_role); then Q8_1 into LDS, no workgroup barrier
+    // this wave's slice of the attention output, re-read until every granule carries this launch's tag (wo_role); then Q8_0 / Q8_1 into LDS, no workgroup barrier
     ActProQ0<false> ap; ap.okmask = (1 << NBW) - 1;
     {
         const uint32_t tag = ((uint32_t) ik_ld_if<BAMD_IK_ST != 0>(&st->serial) << 20) | (((uint32_t) ik_ld_if<BAMD_IK_ST != 0>(&st->step) & 0xfffu) << 8) | (uint32_t) il;
@@ -327,23 +227,25 @@ __device__ __forceinline__ void wo_role_q1(const bamd_mv_args & a, const ProArgs
         }
     }
     float * ys = (float *) pa.S;
-    ap.template quantize_batch_q0<NBW, true>(1.0f, pa.K, i0, pa.q8, ys, 1, i0 + NBW);
-    const size_t rg_floats = (size_t) nb * BAMD_Q1_TERM_FLOATS;
+    ap.template quantize_batch_q0<NBW, MIN>(1.0f, pa.K, i0, pa.q8, ys, 1, i0 + NBW);
+    const size_t rg_floats = (size_t) nb * TERM_FLOATS;
 #pragma unroll
     for (int m = 0; m < M; ++m) {
 #pragma unroll
         for (int jj = 0; jj < NBW; ++jj) {
             pin_rec(ring[m * NBW + jj]);
             float sc[8], fd[8], ms[8];
-            q1_terms(ring[m * NBW + jj], i0 + jj, lane, pa.q8, ys, sc, fd, ms);
-            float * P = part0 + (size_t) m * rg_floats + (size_t) (i0 + jj) * BAMD_Q1_TERM_FLOATS;
+            b32_terms(ring[m * NBW + jj], i0 + jj, lane, pa.q8, ys, sc, fd, ms);
+            float * P = part0 + (size_t) m * rg_floats + (size_t) (i0 + jj) * TERM_FLOATS;
 #pragma unroll
             for (int c = 0; c < 8; ++c) P[c * 64 + lane] = fd[c];
             if ((lane & 7) == 0) {
                 *(float4 *) (P + 512 + r8 * 8) = make_float4(sc[0], sc[1], sc[2], sc[3]);
                 *(float4 *) (P + 512 + r8 * 8 + 4) = make_float4(sc[4], sc[5], sc[6], sc[7]);
-                *(float4 *) (P + 576 + r8 * 8) = make_float4(ms[0], ms[1], ms[2], ms[3]);
-                *(float4 *) (P + 576 + r8 * 8 + 4) = make_float4(ms[4], ms[5], ms[6], ms[7]);
+                if constexpr (MIN) {
+                    *(float4 *) (P + 576 + r8 * 8) = make_float4(ms[0], ms[1], ms[2], ms[3]);
+                    *(float4 *) (P + 576 + r8 * 8 + 4) = make_float4(ms[4], ms[5], ms[6], ms[7]);
+                }
             }
         }
     }
@@ -352,25 +254,27 @@ __device__ __forceinline__ void wo_role_q1(const bamd_mv_args & a, const ProArgs
         const float * B = part0 + (size_t) wave * rg_floats;
         float acc = 0.f, summs = 0.f;
         for (int ib = 0; ib < nb; ++ib) {
-            const float * P = B + (size_t) ib * BAMD_Q1_TERM_FLOATS;
+            const float * P = B + (size_t) ib * TERM_FLOATS;
             const float4 s0 = *(const float4 *) (P + 512 + r8 * 8), s1 = *(const float4 *) (P + 512 + r8 * 8 + 4);
             const float sc[8] = { s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w };
-            const float4 m0 = *(const float4 *) (P + 576 + r8 * 8), m1 = *(const float4 *) (P + 576 + r8 * 8 + 4);
-            const float ms[8] = { m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w };
-            float fd[8];
+            float fd[8], ms[8];
+            if constexpr (MIN) {
+                const float4 m0 = *(const float4 *) (P + 576 + r8 * 8), m1 = *(const float4 *) (P + 576 + r8 * 8 + 4);
+                ms[0] = m0.x; ms[1] = m0.y; ms[2] = m0.z; ms[3] = m0.w; ms[4] = m1.x; ms[5] = m1.y; ms[6] = m1.z; ms[7] = m1.w;
+            }
 #pragma unroll
             for (int c = 0; c < 8; ++c) fd[c] = P[c * 64 + lane];
-            q0_chain8(acc, sc, fd);
-            q1_summs8(summs, ms);                                           // the row's scalar chain, in block order beside the 128-step lane chain
+            b32_chain8(acc, sc, fd);
+            if (MIN) b32_summs8(summs, ms);                                 // the row's scalar chain, in block order beside the 128-step lane chain
         }
-        const float val = q1_finish_row(acc, summs);
+        const float val = b32_finish_row<MIN>(acc, summs);
         if ((lane & 7) == 0 && crow < nv) ik_st(a.seg[0].out + crow, val + resv);
     }
 }
 
 template <int LG, int TYPE>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) attn_wo_q1_kernel(bamd_attn_args at, int gq, bamd_mv_args wo, unsigned long long * gran, int il, int extra,
-                                                                                                       int ring_delay, uint32_t * err) {
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) attn_wo_b32_kernel(bamd_attn_args at, int gq, bamd_mv_args wo, unsigned long long * gran, int il, int extra,
+                                                                                                        int ring_delay, uint32_t * err) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int H = at.Hkv * gq;
     if ((int) blockIdx.x < H) {
@@ -382,8 +286,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int j = (int) blockIdx.x - H, G = (int) gridDim.x - H;
     const ProArgs pa = carve_lds(wo, smem);
     float * part0 = (float *) (smem + mv_terms_off(wo.K >> 8));
-    if (j < extra) wo_role_q1<TYPE, 3>(wo, pa, j, G, part0, gran, at.st, il, ring_delay, err);      // the first `extra` workgroups take a third row-group
-    else           wo_role_q1<TYPE, 2>(wo, pa, j, G, part0, gran, at.st, il, ring_delay, err);
+    if (j < extra) wo_role_b32<TYPE, 3>(wo, pa, j, G, part0, gran, at.st, il, ring_delay, err);     // the first `extra` workgroups take a third row-group
+    else           wo_role_b32<TYPE, 2>(wo, pa, j, G, part0, gran, at.st, il, ring_delay, err);
 }
 
 static const bool g_colaunch = env_flag("BAMD_COLAUNCH", true);
@@ -410,18 +314,11 @@ int bamd_launch_attn_wo(const bamd_attn_args & t, int gq, const bamd_mv_args & w
     // term buffers of the wo role: K = 4096 up to three row-groups in one batch (wo_role), K = 8192 two buffers of two (wo_role_batched)
     const size_t lds = mv_lds_colaunch(nb, nb == 32 ? 2 * 2 : 3, ld);
     const int lg = t.hd >> 6;                                                                 // attention instance: head size / 64 (1..4, checked above)
-    if (bamd_is_q0(type)) {                                                                   // Q8_0 / Q4_0 / Q5_0 wo: K = 4096 only
+    if (bamd_is_q0(type) || bamd_is_q1(type)) {                                               // a wo of the 32-weight block formats: K = 4096 only
         if (nb != 16) return 1;
         return with_const(consts<1, 2, 3, 4>(), lg >= 1 && lg <= 3 ? lg : 4, [&](auto LG) -> bool {
-            return with_const(consts<BAMD_Q8_0, BAMD_Q4_0, BAMD_Q5_0>(), type, [&](auto T) -> bool {
-                BAMD_LAUNCH((attn_wo_q0_kernel<decltype(LG)::value, decltype(T)::value>), dim3(n_cu), dim3(512), colaunch_q0_lds(nb, ld), s, t, gq, wo, gran, il, extra, g_ring_delay, err);
-                return true; }); }) ? 0 : 1;
-    }
-    if (bamd_is_q1(type)) {                                                                   // Q4_1 / Q5_1 wo: K = 4096 only
-        if (nb != 16) return 1;
-        return with_const(consts<1, 2, 3, 4>(), lg >= 1 && lg <= 3 ? lg : 4, [&](auto LG) -> bool {
-            return with_const(consts<BAMD_Q4_1, BAMD_Q5_1>(), type, [&](auto T) -> bool {
-                BAMD_LAUNCH((attn_wo_q1_kernel<decltype(LG)::value, decltype(T)::value>), dim3(n_cu), dim3(512), colaunch_q1_lds(nb, ld), s, t, gq, wo, gran, il, extra, g_ring_delay, err);
+            return with_const(consts<BAMD_Q8_0, BAMD_Q4_0, BAMD_Q5_0, BAMD_Q4_1, BAMD_Q5_1>(), type, [&](auto T) -> bool {
+                BAMD_LAUNCH((attn_wo_b32_kernel<decltype(LG)::value, decltype(T)::value>), dim3(n_cu), dim3(512), colaunch_b32_lds(b32_has_min(decltype(T)::value), nb, ld), s, t, gq, wo, gran, il, extra, g_ring_delay, err);
                 return true; }); }) ? 0 : 1;
     }
     return with_const(consts<1, 2, 3, 4>(), lg >= 1 && lg <= 3 ? lg : 4, [&](auto LG) -> bool {

@@ -75,16 +75,15 @@ int  bamd_timing_enabled(void);   // 1 when the kernels were compiled with -DBAM
 void bamd_launch_repack(const void * raw, void * dst, int type, int nrows, int K, hipStream_t s);
 void bamd_launch_quantize_q8k_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 [[nodiscard]] int bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);          // 1 = a segment's type has no kernel (nothing launched)
-// the same for launches whose segments are all Q8_0 / Q4_0 / Q5_0 (bamd_matvec_q0.hip: Q8_0 activations)
-[[nodiscard]] int bamd_launch_matvec_q0(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
-// the same for launches whose segments are all Q4_1 / Q5_1 (bamd_matvec_q1.hip: Q8_1 activations); 2 = split-K (mode 2) was asked for, which these types do not have
-[[nodiscard]] int bamd_launch_matvec_q1(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
+// the same for launches whose segments are all of ONE family of the 32-weight block formats (bamd_matvec_b32.h): Q8_0 / Q4_0 / Q5_0 (Q8_0 activations) or
+// Q4_1 / Q5_1 (Q8_1 activations); the family of segment 0 decides, 1 = a segment of the other family; 2 = split-K (mode 2) was asked for Q4_1 / Q5_1, which do not have it
+[[nodiscard]] int bamd_launch_matvec_b32(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
+[[nodiscard]] int bamd_launch_matvec_b32_q1(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);      // its Q4_1 / Q5_1 half (a code object per family: bamd_matvec_b32.h)
 // what the engine and the ops call: the family of the first segment picks the launcher, and each launcher refuses a segment of another family (a launch
 // quantises its activations once, as Q8_K, as Q8_0 or as Q8_1: bamd_act_form_of).  bamd_launch_matvec itself stays the K-quant launcher that tests/test_launch_selection.py pins, its
 // refusal of every other type included
 [[nodiscard]] static inline int bamd_launch_mv(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
-    return a.nseg > 0 && bamd_is_q0(a.seg[0].type) ? bamd_launch_matvec_q0(a, pro, epi, n_cu, s)
-         : a.nseg > 0 && bamd_is_q1(a.seg[0].type) ? bamd_launch_matvec_q1(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
+    return a.nseg > 0 && (bamd_is_q0(a.seg[0].type) || bamd_is_q1(a.seg[0].type)) ? bamd_launch_matvec_b32(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
 }
 void bamd_launch_quantize_q81_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 void bamd_launch_quantize_q80_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
@@ -103,14 +102,12 @@ void bamd_launch_k_shift(unsigned short * kc, int n_cells, int Hkv, int hd, cons
 size_t bamd_blob_bytes(int K);
 size_t bamd_blob16_bytes(int K);
 // blob: int8 activations for matmul_batch_kernel (may be null); blob16: f16 copy for the MFMA kernel (may be null)
-// form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_1 form of the same size (bamd_prefill_q1.hip); blob16
-// is written, in the f16 form of bamd_prefill2_q1.hip (576 bytes of a record, the same stride), only while the switch bamd_prefill_q1() is on; BAMD_ACT_Q8_0: the consuming mat-mul has Q8_0 / Q4_0 / Q5_0 weights — blob takes the Q8_0 form of the same size (bamd_prefill_q0.hip); blob16 is written, in the
-// f16 form of bamd_prefill2_q0.hip and with the same per-token stride, only while the switch bamd_prefill_q0() is on (otherwise nothing reads it)
+// form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_0 for Q8_0 / Q4_0 / Q5_0 weights, BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_0 / Q8_1 form
+// of the same size (bamd_prefill_b32.hip); blob16 is written, in the f16 form of bamd_prefill2_b32.hip (544 / 576 bytes of a record, the same per-token stride), only
+// while the family's switch bamd_prefill_q0() / bamd_prefill_q1() is on (otherwise nothing reads it)
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K);
-void bamd_launch_quantize_batch_q0(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
-int  bamd_launch_matmul_batch_q0(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);           // every segment Q8_0 / Q4_0 / Q5_0, a.blob in the Q8_0 form; 1 = shape not supported
-void bamd_launch_quantize_batch_q1(const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
-int  bamd_launch_matmul_batch_q1(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);           // every segment Q4_1 / Q5_1, a.blob in the Q8_1 form; 1 = shape not supported
+void bamd_launch_quantize_batch_b32(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
+int  bamd_launch_matmul_batch_b32(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);          // every segment of the family of segment 0 (Q8_0 / Q4_0 / Q5_0, or Q4_1 / Q5_1), a.blob in its form; 1 = shape not supported
 // K-quant matrices on the matrix cores, exact (bamd_prefill2.hip): y[t][row] = W[row,:] . Q8_K(a_t); epi BAMD_EPI_STORE: out = y; BAMD_EPI_ADD: out = y + res;
 // BAMD_EPI_SILU_MUL: out = silu(res) * y (res = the gate projection, may alias out).  The A fragments are built once per 64-row x 64-token workgroup from the
 // wave-stream copy and the matrix's load-time side table (aux: bamd_prefill_aux_bytes bytes, filled by bamd_launch_prefill_aux).  1 = type / shape not supported or no table
@@ -118,8 +115,8 @@ int  bamd_prefill_mfma_supported(void);      // the current device accepts the k
 // "this weight type has a matrix-core prompt mat-mul now": the ONE list — side-table sizes, the launcher, the engine's routing and its load-time message all ask here.
 // Q3_K / Q2_K are behind the process-wide switch bamd_prefill_lowbit() (BAMD_PREFILL_LOWBIT=1 / bamd_set_prefill_lowbit; default off): a model builds their
 // tables, or not, with the value it finds at load
-// Q8_0 / Q4_0 / Q5_0 (bamd_prefill2_q0.hip) are behind a switch of the same shape, bamd_prefill_q0() (BAMD_PREFILL_Q0=1 / bamd_set_prefill_q0; default off)
-// Q4_1 / Q5_1 (bamd_prefill2_q1.hip) are behind a third switch of that shape, bamd_prefill_q1() (BAMD_PREFILL_Q1=1 / bamd_set_prefill_q1; default off), independent of
+// Q8_0 / Q4_0 / Q5_0 (bamd_prefill2_b32.hip) are behind a switch of the same shape, bamd_prefill_q0() (BAMD_PREFILL_Q0=1 / bamd_set_prefill_q0; default off)
+// Q4_1 / Q5_1 (the same kernel) are behind a third switch of that shape, bamd_prefill_q1() (BAMD_PREFILL_Q1=1 / bamd_set_prefill_q1; default off), independent of
 // bamd_prefill_q0().  Side tables are all-or-nothing per model, and llama.cpp writes Q4_0 / Q5_0 files made with an importance matrix with Q4_1 / Q5_1 ffn_down
 // matrices in their first layers: such a file needs BOTH switches on to get tables; with one of them it runs on the integer-dot kernel like with none
 int  bamd_prefill_lowbit(void);
@@ -133,16 +130,11 @@ size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                               int epi, int ldo, hipStream_t s);
-// the Q8_0 / Q4_0 / Q5_0 side of the three entry points above (bamd_prefill2_q0.hip); callers go through those
-size_t bamd_prefill_aux_bytes_q0(int nrows_pad, int K);
-void bamd_launch_prefill_aux_q0(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
-int  bamd_launch_matmul_mfma_q0(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
-                                int epi, int ldo, hipStream_t s);
-// the Q4_1 / Q5_1 side of them (bamd_prefill2_q1.hip)
-size_t bamd_prefill_aux_bytes_q1(int nrows_pad, int K);
-void bamd_launch_prefill_aux_q1(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
-int  bamd_launch_matmul_mfma_q1(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
-                                int epi, int ldo, hipStream_t s);
+// the side of the three entry points above for the 32-weight block formats, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 (bamd_prefill2_b32.hip); callers go through those
+size_t bamd_prefill_aux_bytes_b32(int type, int nrows_pad, int K);
+void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
+int  bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
+                                 int epi, int ldo, hipStream_t s);
 int  bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);      // 1 = shape not supported
 void bamd_launch_embed_batch(const int32_t * tokens, int T, const void * embd, int embd_type, int E, int V, float * x, hipStream_t s);
 // impl: 0 = the matrix-core kernel where it covers the shape, else the VALU kernels (the engine); 1 = the VALU kernels only; 2 = the matrix-core

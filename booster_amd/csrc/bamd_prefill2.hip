@@ -18,7 +18,7 @@
 //     travel global -> LDS by DMA with the activation records;
 //   * two layouts: sixteen waves with one 16 x 16 tile each (matmul_mfma3_q4k_kernel: Q4_K / Q5_K), eight waves with 16 x 32 each (matmul_mfma2_q6k_kernel: Q6_K;
 //     matmul_mfma2_lowbit_kernel: Q3_K / Q2_K, behind the switch BAMD_PREFILL_LOWBIT / bamd_set_prefill_lowbit, default off).
-//     (Q8_0 / Q4_0 / Q5_0: a kernel of another shape, bamd_prefill2_q0.hip, reached through the launchers at the end of this file.)
+//     (Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1: a kernel of another shape, bamd_prefill2_b32.hip, reached through the launchers at the end of this file.)
 // Same bits as the round-2 kernels (removed in round 6), a third fewer vector instructions per MFMA — and the same time: DESIGN 4c has the measurements of what
 // bounds it, profiles/r06_prefill_ceiling.txt the timing-only ceiling builds (-DBAMD_PREFILL_CEILING).
 #include "bamd_device.h"
@@ -766,9 +766,9 @@ static unsigned long long * g_prefill_dbg = nullptr;      // -DX_TIMING builds: 
 extern "C" __attribute__((visibility("default"))) void bamd_prefill_dbg(void * dev_buf) { g_prefill_dbg = (unsigned long long *) dev_buf; }
 // process-wide switch of the Q3_K / Q2_K kernels (default off: BAMD_PREFILL_LOWBIT=1 or bamd_set_prefill_lowbit) and the launch counters per weight type
 static int g_prefill_lowbit = [] { const char * e = getenv("BAMD_PREFILL_LOWBIT"); return (e && e[0] == '1') ? 1 : 0; }();
-// the same switch for the Q8_0 / Q4_0 / Q5_0 kernel of bamd_prefill2_q0.hip (default off: BAMD_PREFILL_Q0=1 or bamd_set_prefill_q0)
+// the same switch for the Q8_0 / Q4_0 / Q5_0 instances of the kernel of bamd_prefill2_b32.hip (default off: BAMD_PREFILL_Q0=1 or bamd_set_prefill_q0)
 static int g_prefill_q0 = [] { const char * e = getenv("BAMD_PREFILL_Q0"); return (e && e[0] == '1') ? 1 : 0; }();
-// and for the Q4_1 / Q5_1 kernel of bamd_prefill2_q1.hip (default off: BAMD_PREFILL_Q1=1 or bamd_set_prefill_q1); independent of the one above
+// and for its Q4_1 / Q5_1 instances (default off: BAMD_PREFILL_Q1=1 or bamd_set_prefill_q1); independent of the one above
 static int g_prefill_q1 = [] { const char * e = getenv("BAMD_PREFILL_Q1"); return (e && e[0] == '1') ? 1 : 0; }();
 static long long g_mfma_runs[16] = { 0 };
 int bamd_prefill_lowbit(void) { return g_prefill_lowbit; }
@@ -788,13 +788,11 @@ static inline size_t x_ph_bytes(int type, int nrows_pad, int K) { return ((size_
 // bytes of the side table of a K-quant matrix [nrows_pad][K]: builder part first, the consumer part behind it (both 16-byte aligned)
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K) {
     if (!bamd_prefill_mfma_type(type) || (K & 255) || (nrows_pad & 7)) return 0;
-    if (bamd_is_q0(type)) return bamd_prefill_aux_bytes_q0(nrows_pad, K);
-    if (bamd_is_q1(type)) return bamd_prefill_aux_bytes_q1(nrows_pad, K);
+    if (bamd_is_q0(type) || bamd_is_q1(type)) return bamd_prefill_aux_bytes_b32(type, nrows_pad, K);
     return x_ph_bytes(type, nrows_pad, K) + ((size_t) x_row_blocks(nrows_pad) * (size_t) (K >> 8) + x_slack(type)) * x_ch_sb(type);
 }
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s) {
-    if (bamd_is_q0(type)) { bamd_launch_prefill_aux_q0(w_stream, type, nrows_pad, K, aux, s); return; }
-    if (bamd_is_q1(type)) { bamd_launch_prefill_aux_q1(w_stream, type, nrows_pad, K, aux, s); return; }
+    if (bamd_is_q0(type) || bamd_is_q1(type)) { bamd_launch_prefill_aux_b32(w_stream, type, nrows_pad, K, aux, s); return; }
     const int nb = K >> 8, nrt = x_row_blocks(nrows_pad) * 4;
     uint8_t * ph = (uint8_t *) aux, * ch = ph + x_ph_bytes(type, nrows_pad, K);
     const dim3 grid(nb, nrt);
@@ -821,13 +819,8 @@ int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, 
     if (!bamd_prefill_mfma_type(type) || (nrows_pad & 7) || (K & 255) || !aux) return 1;
     if (epi != BAMD_EPI_STORE && epi != BAMD_EPI_ADD && epi != BAMD_EPI_SILU_MUL) return 1;
     if ((epi != BAMD_EPI_STORE) != (res != nullptr)) return 1;
-    if (bamd_is_q0(type)) {                                    // static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
-        if (bamd_launch_matmul_mfma_q0(w_stream, aux, type, nrows, nrows_pad, K, blob16, T, out, res, epi, ldo, s)) return 1;
-        g_mfma_runs[type] += 1;
-        return 0;
-    }
-    if (bamd_is_q1(type)) {                                    // the same: bamd_prefill2_q1.hip
-        if (bamd_launch_matmul_mfma_q1(w_stream, aux, type, nrows, nrows_pad, K, blob16, T, out, res, epi, ldo, s)) return 1;
+    if (bamd_is_q0(type) || bamd_is_q1(type)) {                // bamd_prefill2_b32.hip; static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
+        if (bamd_launch_matmul_mfma_b32(w_stream, aux, type, nrows, nrows_pad, K, blob16, T, out, res, epi, ldo, s)) return 1;
         g_mfma_runs[type] += 1;
         return 0;
     }

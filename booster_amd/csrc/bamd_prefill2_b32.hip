@@ -1,14 +1,20 @@
-// bamd_prefill2_q0.hip — the exact matrix-core prompt mat-mul for Q8_0 / Q4_0 / Q5_0 weights x Q8_0 activations, behind the switch BAMD_PREFILL_Q0 /
-// bamd_set_prefill_q0 (default off; the list of types is bamd_prefill_mfma_type, bamd_kernels.h).
+// bamd_prefill2_b32.hip — the exact matrix-core prompt mat-mul for the 32-weight block formats: Q8_0 / Q4_0 / Q5_0 weights x Q8_0 activations behind the switch
+// BAMD_PREFILL_Q0 / bamd_set_prefill_q0, Q4_1 / Q5_1 weights x Q8_1 activations behind BAMD_PREFILL_Q1 / bamd_set_prefill_q1 (both default off; the list of types
+// is bamd_prefill_mfma_type, bamd_kernels.h).  One kernel template for the five types; MIN = b32_has_min(TYPE) marks what the types with a minimum add.
 //
-// Arithmetic: the contract of bamd_q0_device.h.  One output = eight f32 chains e = 0..7 over the 32-weight blocks l in order,
+// Arithmetic: the contract of bamd_b32_device.h.  One output = eight f32 chains e = 0..7 over the 32-weight blocks l in order,
 //     acc_e = fma(f32(d_w) * f32(d_x), (float) dot4_e, acc_e),         dot4_e = the signed dot of bytes 4e .. 4e+3 of weight block and activation block,
-// closed by q0_finish_row's tree.  A chain link sums FOUR products, so the K = 32 instructions of bamd_prefill2.hip would add across links; what fits are the
+// closed by b32_finish_row's tree.  A chain link sums FOUR products, so the K = 32 instructions of bamd_prefill2.hip would add across links; what fits are the
 // K = 4 multi-block forms.  This kernel uses v_mfma_f32_16x16x4_4b_f16: one instruction = the links (l, e = 4 eh + 0..3) of a 16 x 16 tile.  With f16 operands
 // (|w| <= 128, |x| <= 127) every product and every four-term sum is an integer below 2^24, exact in f32 in any order; the scale product of two widened f16 is
 // exact as well.  The links themselves stay on the VALU: one f32 multiply per (row, token, block) and one fma per (row, token, block, e), in block order.
 // (The two-block 32 x 32 form has the same rate — tools/mfma_k4_probe.hip — but a wave must then hold 128 accumulators and two 32-register results next to
 // them: the first version of this kernel did, and spilled.  Four blocks of 16 x 16 put all eight e of a 16-row x 32-token wave tile in 64 registers.)
+// MIN: a second accumulator per output,
+//     summs = summs + f32(m_w) * f32(s_x)                               one scalar chain per (row, token).  The product of two widened f16 is exact in f32,
+//                                                                       so a multiply and an add give the bits of one fma; the K/32 steps stay in block order
+// and the result is the tree over acc_e, plus summs.  The weights of the 8-lane chain are UNSIGNED and without an offset there (Q4_1: the nibble 0..15, Q5_1:
+// nibble | bit << 4, 0..31): the B operand is (0x6400 | u) - 1024 = u, exact in f16; |w| <= 31, |x| <= 127: every four-term sum is an integer far below 2^24.
 //
 // Layout.  The activations are the A operand, the weights the B operand: D[i = token][j = row], so a lane owns ONE weight row (j = lane & 15) and four tokens
 // per token tile (register v: block v >> 2, token 4 (lane >> 4) + (v & 3)); its row's eight d_w of a record are two 16-byte loads of the side table, the tokens'
@@ -19,11 +25,20 @@
 //     a token's 512 bytes sit 528 bytes apart (132 dwords = 4 mod 64: the 16-byte reads of sixteen lanes fall on sixteen bank quads);
 //   * the weights never go through LDS: MFMA lane (row j, block g) needs, for chunk e = 4 eh + g, exactly the dwords that wave-stream lane (r = j & 7, e) of
 //     its record group holds, so each lane loads its own 16-byte pieces half a record ahead and unpacks them with the 0x6400 | byte v_perm idiom of
-//     build_a (bamd_prefill2.hip): (1024 + u) - (1024 + offset), exact in f16, u = byte ^ 0x80 (Q8_0), nibble (Q4_0), nibble | bit 4 (Q5_0);
+//     build_a (bamd_prefill2.hip): (1024 + u) - (1024 + offset), exact in f16, u = byte ^ 0x80 (Q8_0), nibble (Q4_0, Q4_1), nibble | bit 4 (Q5_0, Q5_1);
 //   * the chain of one MFMA's 16 results follows the NEXT MFMA's issue (no MFMA -> VALU wait states in front of it).
 // Side table ("prefill aux"): the eight f16 d of every row and record widened to f32, [record group][record][row][block] — 32 B per row and 256 weights.
-#include "bamd_q0_device.h"
+// What MIN adds:
+//   * the lane (row j, tokens 16 n + 4 g + 0..3) carries eight summs accumulators next to its 64 chain accumulators.  Per block it takes ONE step of each, written
+//     as two-wide vector fmas (v_pk_fma_f32, an IEEE fma per half) whose only operand that changes is the accumulator itself: the order of a summs chain is its
+//     data dependence, block c + 1 after block c, and there is no scalar f32 add for the SLP vectoriser to gather into a tree;
+//   * side table: the row's eight f16 d AND eight f16 m of every record widened to f32, [record group][record][row r][d 0..7 | m 0..7] — 64 B per row and 256
+//     weights, four 16-byte loads per lane and record;
+//   * f16 activation records (quantize_batch_b32_kernel, bamd_prefill_b32.hip): the Q8_0 form's 512 B of quants and eight f32 d_x at byte 512, then the eight s_x
+//     widened to f32 at byte 544 (576 of the BAMD_B16_REC bytes used); d_x and s_x of a stage sit side by side in LDS, [block c][token].
+#include "bamd_b32_device.h"
 #include "bamd_mfma_common.h"
+#include "bamd_mv_select.h"
 
 typedef float bamd_f16v __attribute__((ext_vector_type(16)));
 typedef float bamd_f2 __attribute__((ext_vector_type(2)));
@@ -33,49 +48,53 @@ union bamd_h2qu { uint32_t u; bamd_h2q h; };
 #define Y_TOK 32                                           /* tokens of a workgroup */
 #define Y_ROWS 64                                          /* rows of a workgroup: four waves x 16 */
 #define Y_QSTR 528                                         /* LDS bytes between the quants of consecutive tokens */
-#define Y_XS_OFF (Y_TOK * Y_QSTR)                          /* d_x of the stage: [block c][token] f32 */
-#define Y_STAGE (Y_XS_OFF + 8 * Y_TOK * 4)                 /* 17 920 B */
+#define Y_XD_OFF (Y_TOK * Y_QSTR)                          /* d_x of the stage: [block c][token] f32 */
+#define Y_XS_OFF (Y_XD_OFF + 8 * Y_TOK * 4)                /* MIN: s_x of the stage, the same shape */
+constexpr int y_stage(bool has_min) { return has_min ? Y_XS_OFF + 8 * Y_TOK * 4 : Y_XS_OFF; }      // 17 920 B, MIN 18 944 B
 // a BAMD_B16_REC record in this form uses 544 bytes: element 4e + k of block c as f16 at half c * 32 + (e & 3) * 8 + (e >> 2) * 4 + k (the A operands of both
-// e-halves of an MFMA lane are 16 consecutive bytes), then the eight d_x as f32 at byte 512
+// e-halves of an MFMA lane are 16 consecutive bytes), then the eight d_x as f32 at byte 512; MIN: 576 bytes, the eight s_x as f32 at byte 544
+static_assert(BAMD_B16_REC >= 512 + 32 + 32, "the f16 activation record holds the quants, eight d_x and eight s_x");
 
-struct bamd_mmaq0_args {
+struct bamd_mma_b32_args {
     const uint8_t * w;               // wave-stream records (bamd_formats.h)
-    const float * sc;                // side table: [record group][record][row r][block c] f32
+    const float * sc;                // side table: [record group][record][row r][block c] f32; MIN: [..][row r][d of block 0..7 | m of block 0..7]
     float * out; const float * res;  // [T][ldo]
-    const uint8_t * blob16;          // f16 activation records (quantize_batch_q0_kernel)
+    const uint8_t * blob16;          // f16 activation records (quantize_batch_b32_kernel)
     int K, T, nrows, nrows_pad, ldo;
 };
 
-// grid (records, record groups), 64 threads = (row r, block c)
+// grid (records, record groups), 64 threads = (row r, block c); MIN: 128 threads = (row r, d of block 0..7 | m of block 0..7): the record's d / dm table is in
+// this order already
 template <int TYPE>
-__global__ void __launch_bounds__(64) prefill_aux_q0_kernel(const uint8_t * __restrict__ w, int nb, float * __restrict__ sc) {
-    constexpr int RECB = BAMD_RECB_OF(TYPE), SDO = TYPE == BAMD_Q8_0 ? 2048 : TYPE == BAMD_Q4_0 ? 1024 : 1280;
+__global__ void __launch_bounds__(b32_has_min(TYPE) ? 128 : 64) prefill_aux_b32_kernel(const uint8_t * __restrict__ w, int nb, float * __restrict__ sc) {
+    constexpr int RECB = BAMD_RECB_OF(TYPE), SDO = TYPE == BAMD_Q8_0 ? 2048 : b32_has_qh(TYPE) ? 1280 : 1024, NT = b32_has_min(TYPE) ? 128 : 64;
     const size_t rec = (size_t) blockIdx.y * nb + blockIdx.x;
-    const int r = threadIdx.x >> 3, c = threadIdx.x & 7;
-    sc[rec * 64 + r * 8 + c] = h2f(*(const unsigned short *) (w + rec * RECB + SDO + r * 16 + c * 2));
+    sc[rec * NT + threadIdx.x] = h2f(*(const unsigned short *) (w + rec * RECB + SDO + threadIdx.x * 2));
 }
 
 // the lane's pieces of HALF a record (blocks c = 4h .. 4h+3) for its two chunks e = g and g + 4
-template <int TYPE> struct HalfQ0 { uint4 q[TYPE == BAMD_Q8_0 ? 2 : 1]; uint32_t qh[2]; };
-template <int TYPE> __device__ __forceinline__ void load_half(HalfQ0<TYPE> & H, const uint8_t * rec, int h, int r, int g) {
+template <int TYPE> struct HalfB32 { uint4 q[TYPE == BAMD_Q8_0 ? 2 : 1]; uint32_t qh[2]; };
+template <int TYPE> __device__ __forceinline__ void load_half(HalfB32<TYPE> & H, const uint8_t * rec, int h, int r, int g) {
     if (TYPE == BAMD_Q8_0) {
         H.q[0] = *(const uint4 *) (rec + h * 1024 + (r * 8 + g) * 16); H.q[1] = *(const uint4 *) (rec + h * 1024 + (r * 8 + g + 4) * 16);
     } else {
         H.q[0] = *(const uint4 *) (rec + (r * 4 + g) * 32 + h * 16);             // chunks g and g + 4 share the bytes: low / high nibbles
-        if (TYPE == BAMD_Q5_0) { H.qh[0] = *(const uint32_t *) (rec + 1024 + (r * 8 + g) * 4); H.qh[1] = *(const uint32_t *) (rec + 1024 + (r * 8 + g + 4) * 4); }
+        if (b32_has_qh(TYPE)) { H.qh[0] = *(const uint32_t *) (rec + 1024 + (r * 8 + g) * 4); H.qh[1] = *(const uint32_t *) (rec + 1024 + (r * 8 + g + 4) * 4); }
     }
 }
-// the four weights of block 4h + cl, chunk 4 eh + g, as unsigned bytes u = weight + offset (128 / 8 / 16)
-template <int TYPE> __device__ __forceinline__ uint32_t half_bytes(const HalfQ0<TYPE> & H, int h, int cl, int eh) {
-    if (TYPE == BAMD_Q8_0) return BAMD_Q0_COMP(H.q[eh], cl) ^ 0x80808080u;
-    const uint32_t nib = (BAMD_Q0_COMP(H.q[0], cl) >> (eh * 4)) & 0x0f0f0f0fu;
-    if (TYPE == BAMD_Q4_0) return nib;
+// the four weights of block 4h + cl, chunk 4 eh + g, as unsigned bytes u = weight + offset (128 / 8 / 16; MIN: b32_weights' bytes, no offset)
+template <int TYPE> __device__ __forceinline__ uint32_t half_bytes(const HalfB32<TYPE> & H, int h, int cl, int eh) {
+    if (TYPE == BAMD_Q8_0) return BAMD_B32_COMP(H.q[eh], cl) ^ 0x80808080u;
+    const uint32_t nib = (BAMD_B32_COMP(H.q[0], cl) >> (eh * 4)) & 0x0f0f0f0fu;
+    if (!b32_has_qh(TYPE)) return nib;
     return nib | (((H.qh[eh] >> (4 * h + cl)) & 0x01010101u) << 4);
 }
 
 template <int TYPE, int EPI>
-__global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) {
+__global__ void __launch_bounds__(256) matmul_mfma_b32_kernel(bamd_mma_b32_args a) {
     constexpr int RECB = BAMD_RECB_OF(TYPE);
+    constexpr bool MIN = b32_has_min(TYPE);
+    constexpr int Y_STAGE = y_stage(MIN), NSC = MIN ? 16 : 8;  // NSC: side-table floats of a row and record
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * Y_STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4, r = j & 7;
     const int nb = a.K >> 8;
@@ -83,9 +102,9 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
     const int nrg = a.nrows_pad >> 3;
     const int rg = (row0 >> 3) + (j >> 3) < nrg ? (row0 >> 3) + (j >> 3) : nrg - 1;      // rows behind the matrix: the last record group again, never stored
     const uint8_t * wrec = a.w + (size_t) rg * nb * RECB;
-    const float * wsc = a.sc + ((size_t) rg * nb * 8 + r) * 8;
+    const float * wsc = a.sc + ((size_t) rg * nb * 8 + r) * NSC;
     const size_t b16 = BAMD_BLOB16_BYTES(nb);
-    // staging plan: four 16-byte pieces of quants and one block scale per thread and record (tokens behind T: the last token again)
+    // staging plan: four 16-byte pieces of quants and one block scale (MIN: one {d_x, s_x} pair) per thread and record (tokens behind T: the last token again)
     const uint8_t * sq[4]; uint32_t dq[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -97,28 +116,32 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
     {
         const int tok = tid >> 3, c = tid & 7;
         const int tg = t0 + tok < a.T ? t0 + tok : a.T - 1;
-        sx = a.blob16 + (size_t) tg * b16 + 512 + c * 4; dx = (uint32_t) (Y_XS_OFF + (c * Y_TOK + tok) * 4);
+        sx = a.blob16 + (size_t) tg * b16 + 512 + c * 4; dx = (uint32_t) (Y_XD_OFF + (c * Y_TOK + tok) * 4);
     }
-    uint4 stq0, stq1, stq2, stq3; float stx;                   // (named: as an array behind the lambdas' references the four stayed in scratch memory)
+    uint4 stq0, stq1, stq2, stq3; float stxd, stxs;            // (named: as an array behind the lambdas' references the four stayed in scratch memory)
     auto stage_load = [&](int ci) {
         const size_t o = (size_t) ci * BAMD_B16_REC;
         stq0 = *(const uint4 *) (sq[0] + o); stq1 = *(const uint4 *) (sq[1] + o); stq2 = *(const uint4 *) (sq[2] + o); stq3 = *(const uint4 *) (sq[3] + o);
-        stx = *(const float *) (sx + o);
+        stxd = *(const float *) (sx + o);
+        if (MIN) stxs = *(const float *) (sx + o + 32);
     };
     auto stage_store = [&](int buf) {
         unsigned char * d = smem + buf * Y_STAGE;
         *(uint4 *) (d + dq[0]) = stq0; *(uint4 *) (d + dq[1]) = stq1; *(uint4 *) (d + dq[2]) = stq2; *(uint4 *) (d + dq[3]) = stq3;
-        *(float *) (d + dx) = stx;
+        *(float *) (d + dx) = stxd;
+        if (MIN) *(float *) (d + dx + (Y_XS_OFF - Y_XD_OFF)) = stxs;
     };
     // [token tile n][e][pair]: tokens 16 n + 4 g + 0..3 of row j.  The chains are WRITTEN as float2 operations (v_pk_fma_f32, an IEEE fma per half): left as scalar
-    // fmaf, the eight links an accumulator takes per record become one tree for the SLP vectoriser, which emits it behind the last MFMA of the loop body
-    bamd_f2 acc[2][8][2];
+    // fmaf, the eight links an accumulator takes per record become one tree for the SLP vectoriser, which emits it behind the last MFMA of the loop body.
+    // summs (MIN): [token tile n][pair]
+    bamd_f2 acc[2][8][2], summs[2][2];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) { acc[n][e][0] = (bamd_f2) { 0.f, 0.f }; acc[n][e][1] = (bamd_f2) { 0.f, 0.f }; }
+        summs[n][0] = (bamd_f2) { 0.f, 0.f }; summs[n][1] = (bamd_f2) { 0.f, 0.f };
     }
-    const _Float16 kz = TYPE == BAMD_Q8_0 ? (_Float16) -1152.f : TYPE == BAMD_Q4_0 ? (_Float16) -1032.f : (_Float16) -1040.f;
+    const _Float16 kz = MIN ? (_Float16) -1024.f : TYPE == BAMD_Q8_0 ? (_Float16) -1152.f : TYPE == BAMD_Q4_0 ? (_Float16) -1032.f : (_Float16) -1040.f;
     const bamd_h2q kzero = { kz, kz };
     auto chain = [&](int n, int eh, const bamd_f16v & s, const bamd_f4 & S) {           // the links (l, 4 eh + 0..3) of the lane's four tokens of tile n
         const bamd_f2 Slo = { S[0], S[1] }, Shi = { S[2], S[3] };
@@ -128,21 +151,22 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
         Y_LINK(0); Y_LINK(1); Y_LINK(2); Y_LINK(3);
 #undef Y_LINK
     };
-    // half step: blocks c = 4h .. 4h+3 of a record whose activations are in `stage`
-    auto half_step = [&](const HalfQ0<TYPE> & H, int h, const float (&dw)[8], const unsigned char * stage) {
+    // half step: blocks c = 4h .. 4h+3 of a record whose activations are in `stage`; dm: the row's d (0..7) and, MIN, m (8..15) of the record
+    auto half_step = [&](const HalfB32<TYPE> & H, int h, const float (&dm)[NSC], const unsigned char * stage) {
         const unsigned char * aq = stage + j * Y_QSTR + g * 16;
-        const unsigned char * xs = stage + Y_XS_OFF + g * 16;
+        const unsigned char * xd = stage + Y_XD_OFF + g * 16;
         bamd_f16v prev; bamd_f4 Sprev;
 #pragma unroll
         for (int cl = 0; cl < 4; ++cl) {
             const int c = 4 * h + cl;
-            bamd_f4 S[2];
+            bamd_f4 S[2], sxv[2];
             union { uint2 u; bamd_h4 h; } A[2][2], B[2];
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
-                const bamd_f4 x = *(const bamd_f4 *) (xs + (c * Y_TOK + 16 * n) * 4);
+                const bamd_f4 x = *(const bamd_f4 *) (xd + (c * Y_TOK + 16 * n) * 4);
+                if (MIN) sxv[n] = *(const bamd_f4 *) (xd + (Y_XS_OFF - Y_XD_OFF) + (c * Y_TOK + 16 * n) * 4);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) S[n][i] = dw[c] * x[i];
+                for (int i = 0; i < 4; ++i) S[n][i] = dm[c] * x[i];
                 const uint4 av = *(const uint4 *) (aq + n * (16 * Y_QSTR) + c * 64);
                 A[n][0].u = (uint2) { av.x, av.y }; A[n][1].u = (uint2) { av.z, av.w };
             }
@@ -154,6 +178,7 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
                 hi.u = __builtin_amdgcn_perm(0x64646464u, u, 0x04030402u); hi.h = hi.h + kzero;
                 B[eh].u = (uint2) { lo.u, hi.u };
             }
+            const bamd_f2 mw = { dm[MIN ? 8 + c : c], dm[MIN ? 8 + c : c] };            // MIN: m_w of block c
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                      // (eh, n) = (k >> 1, k & 1)
                 const int eh = k >> 1, n = k & 1;
@@ -164,6 +189,10 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
                 __builtin_amdgcn_sched_barrier(0);             // the MFMA first, the previous one's chain behind it
                 if (k > 0) chain((k - 1) & 1, (k - 1) >> 1, prev, S[(k - 1) & 1]);
                 else if (cl > 0) chain(1, 1, prev, Sprev);
+                if (MIN && k < 2) {                            // step c of the four summs pairs of token tile k: summs += m_w[c] * s_x[c][token]
+                    summs[k][0] = __builtin_elementwise_fma(mw, (bamd_f2) { sxv[k][0], sxv[k][1] }, summs[k][0]);
+                    summs[k][1] = __builtin_elementwise_fma(mw, (bamd_f2) { sxv[k][2], sxv[k][3] }, summs[k][1]);
+                }
                 prev = s;
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -171,16 +200,19 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
         }
         chain(1, 1, prev, Sprev);
     };
-    HalfQ0<TYPE> H0, H1;
-    float dw[8], dwn[8];
-    auto load_dw = [&](float (&d)[8], int ci) {
-        const bamd_f4 lo = *(const bamd_f4 *) (wsc + (size_t) ci * 64), hi = *(const bamd_f4 *) (wsc + (size_t) ci * 64 + 4);
+    HalfB32<TYPE> H0, H1;
+    float dm[NSC], dmn[NSC];
+    auto load_dm = [&](float (&d)[NSC], int ci) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { d[i] = lo[i]; d[4 + i] = hi[i]; }
+        for (int q = 0; q < NSC / 4; ++q) {
+            const bamd_f4 v = *(const bamd_f4 *) (wsc + (size_t) ci * (8 * NSC) + 4 * q);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) d[4 * q + i] = v[i];
+        }
     };
     stage_load(0);
     load_half(H0, wrec, 0, r, g);
-    load_dw(dw, 0);
+    load_dm(dm, 0);
     stage_store(0);
     __syncthreads();
     for (int ci = 0; ci < nb; ++ci) {
@@ -189,14 +221,14 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
         stage_load(cn);                                        // (no branch inside the loop: the compiler would sink the chains behind it, away from their MFMAs; the last
                                                                //  record is staged once more into the buffer nobody reads again)
         load_half(H1, wrec + (size_t) ci * RECB, 1, r, g);
-        load_dw(dwn, cn);
+        load_dm(dmn, cn);
         __builtin_amdgcn_sched_barrier(0);
-        half_step(H0, 0, dw, stage);
+        half_step(H0, 0, dm, stage);
         load_half(H0, wrec + (size_t) cn * RECB, 0, r, g);
         __builtin_amdgcn_sched_barrier(0);
-        half_step(H1, 1, dw, stage);
+        half_step(H1, 1, dm, stage);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) dw[i] = dwn[i];
+        for (int i = 0; i < NSC; ++i) dm[i] = dmn[i];
         stage_store((ci + 1) & 1);                             // the buffer read in step ci - 1: every wave is past that step's barrier
         __syncthreads();
     }
@@ -208,8 +240,9 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
         for (int i = 0; i < 4; ++i) {
             const int t = t0 + 16 * n + 4 * g + i;
 #define Y_ACC(e_) acc[n][e_][i >> 1][i & 1]
-            const float val = ((Y_ACC(0) + Y_ACC(4)) + (Y_ACC(2) + Y_ACC(6))) + ((Y_ACC(1) + Y_ACC(5)) + (Y_ACC(3) + Y_ACC(7)));      // q0_finish_row's tree
+            const float tree = ((Y_ACC(0) + Y_ACC(4)) + (Y_ACC(2) + Y_ACC(6))) + ((Y_ACC(1) + Y_ACC(5)) + (Y_ACC(3) + Y_ACC(7)));      // b32_finish_row's tree
 #undef Y_ACC
+            const float val = MIN ? tree + summs[n][i >> 1][i & 1] : tree;                                                             // b32_finish_row<MIN>
             if (t < a.T) {
                 const size_t o = (size_t) t * a.ldo + row;
                 a.out[o] = EPI == BAMD_EPI_ADD ? val + a.res[o] : EPI == BAMD_EPI_SILU_MUL ? v_silu(a.res[o]) * val : val;
@@ -219,27 +252,26 @@ __global__ void __launch_bounds__(256) matmul_mfma_q0_kernel(bamd_mmaq0_args a) 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------
-size_t bamd_prefill_aux_bytes_q0(int nrows_pad, int K) { return (size_t) (nrows_pad >> 3) * (size_t) (K >> 8) * 256; }
-void bamd_launch_prefill_aux_q0(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s) {
+typedef consts<BAMD_Q8_0, BAMD_Q4_0, BAMD_Q5_0, BAMD_Q4_1, BAMD_Q5_1> b32_types;
+size_t bamd_prefill_aux_bytes_b32(int type, int nrows_pad, int K) { return (size_t) (nrows_pad >> 3) * (size_t) (K >> 8) * (bamd_is_q1(type) ? 512 : 256); }
+void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s) {
     const dim3 grid(K >> 8, nrows_pad >> 3);
-    if (type == BAMD_Q8_0)      hipLaunchKernelGGL((prefill_aux_q0_kernel<BAMD_Q8_0>), grid, dim3(64), 0, s, (const uint8_t *) w_stream, K >> 8, (float *) aux);
-    else if (type == BAMD_Q4_0) hipLaunchKernelGGL((prefill_aux_q0_kernel<BAMD_Q4_0>), grid, dim3(64), 0, s, (const uint8_t *) w_stream, K >> 8, (float *) aux);
-    else                        hipLaunchKernelGGL((prefill_aux_q0_kernel<BAMD_Q5_0>), grid, dim3(64), 0, s, (const uint8_t *) w_stream, K >> 8, (float *) aux);
+    with_const(b32_types(), type, [&](auto T) -> bool {
+        hipLaunchKernelGGL((prefill_aux_b32_kernel<decltype(T)::value>), grid, dim3(b32_has_min(decltype(T)::value) ? 128 : 64), 0, s, (const uint8_t *) w_stream, K >> 8, (float *) aux);
+        return true; });
 }
-// the launch interface of bamd_launch_matmul_mfma2, which checks the arguments and routes the three types here
-int bamd_launch_matmul_mfma_q0(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
-                               int epi, int ldo, hipStream_t s) {
-    if (!bamd_is_q0(type) || T < 1 || nrows_pad < 8) return 1;
-    bamd_mmaq0_args a; a.w = (const uint8_t *) w_stream; a.sc = (const float *) aux; a.out = out; a.res = res; a.blob16 = (const uint8_t *) blob16;
+// the launch interface of bamd_launch_matmul_mfma2, which checks the arguments and routes the five types here
+int bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
+                                int epi, int ldo, hipStream_t s) {
+    if (!(bamd_is_q0(type) || bamd_is_q1(type)) || T < 1 || nrows_pad < 8) return 1;
+    bamd_mma_b32_args a; a.w = (const uint8_t *) w_stream; a.sc = (const float *) aux; a.out = out; a.res = res; a.blob16 = (const uint8_t *) blob16;
     a.K = K; a.T = T; a.nrows = nrows; a.nrows_pad = nrows_pad; a.ldo = ldo;
     const dim3 grid((T + Y_TOK - 1) / Y_TOK, (nrows_pad + Y_ROWS - 1) / Y_ROWS);
-#define Y_LAUNCH(TYPE_) do { \
-        if (epi == BAMD_EPI_ADD)           hipLaunchKernelGGL((matmul_mfma_q0_kernel<TYPE_, BAMD_EPI_ADD>),      grid, dim3(256), 0, s, a); \
-        else if (epi == BAMD_EPI_SILU_MUL) hipLaunchKernelGGL((matmul_mfma_q0_kernel<TYPE_, BAMD_EPI_SILU_MUL>), grid, dim3(256), 0, s, a); \
-        else                               hipLaunchKernelGGL((matmul_mfma_q0_kernel<TYPE_, BAMD_EPI_STORE>),    grid, dim3(256), 0, s, a); } while (0)
-    if (type == BAMD_Q8_0)      Y_LAUNCH(BAMD_Q8_0);
-    else if (type == BAMD_Q4_0) Y_LAUNCH(BAMD_Q4_0);
-    else                        Y_LAUNCH(BAMD_Q5_0);
-#undef Y_LAUNCH
+    with_const(b32_types(), type, [&](auto TY) -> bool {
+        constexpr int TYPE_ = decltype(TY)::value;
+        if (epi == BAMD_EPI_ADD)           hipLaunchKernelGGL((matmul_mfma_b32_kernel<TYPE_, BAMD_EPI_ADD>),      grid, dim3(256), 0, s, a);
+        else if (epi == BAMD_EPI_SILU_MUL) hipLaunchKernelGGL((matmul_mfma_b32_kernel<TYPE_, BAMD_EPI_SILU_MUL>), grid, dim3(256), 0, s, a);
+        else                               hipLaunchKernelGGL((matmul_mfma_b32_kernel<TYPE_, BAMD_EPI_STORE>),    grid, dim3(256), 0, s, a);
+        return true; });
     return 0;
 }

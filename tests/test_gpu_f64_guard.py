@@ -11,7 +11,7 @@ A shape the launcher declines or routes elsewhere FAILS.  Mat-vec cases call the
 
   site                          cases
   ActPro::finish           bamd_device.h              test_fused_qkv_fast, test_generic_kernels, test_gate_up, test_lm_head_k8192, test_quantize_batch
-  ActProQ0::finish_q0      bamd_q0_device.h           test_q8_0_family, test_q8_1_family
+  ActProQ0::finish_q0      bamd_b32_device.h          test_q8_0_family, test_q8_1_family
   attn_softmax_kernel      bamd_attention.hip         test_softmax_kernel (cached 96 / 4128, uncached 8224), test_softmax_kernel_cells (holes)
   attn_spv_kernel<NH>      bamd_attention.hip         test_spv (NH 1, 2, 4)
   attn_batch_kernel<GQH>   bamd_attention.hip         test_batch_valu
@@ -226,7 +226,7 @@ def _legacy_family(bamd, po, okats, ref, t, random_tensor, quantize_op, quantize
     rows = 13                                                  # two row-groups = two workgroups of one busy wave each: seven waves of each have no rows and still owe it the barriers
     W = random_tensor(t, K, rows, rng)
     want = ref.mul_mat(t, W, rows, K, act)
-    for mode in modes:                                         # 1: matvec_q0 / q1_kernel; 2: matvec_q0_split_kernel (these types have no trace: the mode argument chooses)
+    for mode in modes:                                         # 1: matvec_b32_kernel; 2: matvec_q0_split_kernel (these types have no trace: the mode argument chooses)
         three_calls(lambda: bamd.op_mul_mat_vec(t, W, rows, K, x1, norm_w=w, eps=eps, mode=mode), want, "type %d mat-vec with RMSNorm, mode %d" % (t, mode))
     X = np.stack([quiet_vector(rng, K), x1, quiet_vector(rng, K)])
     want = np.stack([ref.mul_mat(t, W, rows, K, normed(po, X[i], w, eps)) for i in range(3)])
@@ -234,12 +234,12 @@ def _legacy_family(bamd, po, okats, ref, t, random_tensor, quantize_op, quantize
 
 
 def test_q8_0_family(bamd, po, okats):
-    """ActProQ0::finish_q0 (a textual copy of the fallback): the quantiser op, matvec_q0_kernel, matvec_q0_split_kernel, quantize_batch_q0_kernel at T = 3"""
+    """ActProQ0::finish_q0 (a textual copy of the fallback): the quantiser op, matvec_b32_kernel<false>, matvec_q0_split_kernel, quantize_batch_b32_kernel<.., false> at T = 3"""
     _legacy_family(bamd, po, okats, lg, lg.Q8_0, random_q0_tensor, bamd.op_quantize_q8_0, lg.quantize_row_q8_0, (1, 2))
 
 
 def test_q8_1_family(bamd, po, okats):
-    """the same with Q8_1 activations: the quantiser op, matvec_q1_kernel, quantize_batch_q1_kernel at T = 3 (these types have no split-K kernel)"""
+    """the same with Q8_1 activations: the quantiser op, matvec_b32_kernel<true>, quantize_batch_b32_kernel<.., true> at T = 3 (these types have no split-K kernel)"""
     _legacy_family(bamd, po, okats, l1, l1.Q4_1, random_q1_tensor, bamd.op_quantize_q8_1, l1.quantize_row_q8_1, (1,))
 
 
@@ -431,7 +431,7 @@ def test_batch_mfma(bamd, po, skats, gq, fire, name, n_ctx, ld, long):
     batch(bamd, po, R, impl=2, ld=ld, scratch=long)
 
 
-@pytest.mark.parametrize("t,kernel", [(12, "attn_wo_kernel"), (lg.Q8_0, "attn_wo_q0_kernel"), (l1.Q4_1, "attn_wo_q1_kernel")])
+@pytest.mark.parametrize("t,kernel", [(12, "attn_wo_kernel"), (lg.Q8_0, "attn_wo_b32_kernel"), (l1.Q4_1, "attn_wo_b32_kernel")])
 def test_colaunch(bamd, po, skats, t, kernel):
     """attention || wo in one launch (attn_fused_body with COLAUNCH = true: what every decode step below 448 positions runs): H 32, Hkv 8, head_dim 128,
     n_ctx 128, position 95, wo 4096 x 4096; head 13 (the second of KV head 3) fires.  x2, the granules, both caches, and the give-up counter"""
@@ -439,7 +439,8 @@ def test_colaunch(bamd, po, skats, t, kernel):
     R = Rows(skats, "v96_p96_hd128", H, Hkv, 1, 0, (13,), n_ctx, hk=3)
     R.assert_guard(po)
     tr = booster_amd.trace_attn_wo(H, Hkv, hd, n_ctx, 128, t, rows, K, n_cu=device_cus(bamd))
-    assert tr is not None and kernel + "ILi2E" in tr["kernel"], "the launcher declines or routes the shape elsewhere: %r" % (tr,)
+    sym = kernel + "ILi2E" if t == 12 else "attn_wo_b32_kernelILi2ELi%dE" % t          # head size / 64 = 2; the block-format kernel also by its weight type
+    assert kernel in sym and tr is not None and sym in tr["kernel"], "the launcher declines or routes the shape elsewhere: %r" % (tr,)
     rng = np.random.default_rng([3, t])
     W = random_kquant_tensor(t, K, rows, rng) if t == 12 else random_q0_tensor(t, K, rows, rng) if t == lg.Q8_0 else random_q1_tensor(t, K, rows, rng)
     res = rng.standard_normal(rows).astype(np.float32)

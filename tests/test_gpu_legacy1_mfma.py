@@ -1,4 +1,4 @@
-"""GPU: the matrix-core prompt mat-mul for Q4_1 / Q5_1 weights (booster_amd/csrc/bamd_prefill2_q1.hip, behind set_prefill_q1 / BAMD_PREFILL_Q1=1; default off).
+"""GPU: the matrix-core prompt mat-mul for Q4_1 / Q5_1 weights (booster_amd/csrc/bamd_prefill2_b32.hip, behind set_prefill_q1 / BAMD_PREFILL_Q1=1; default off).
 Every expectation is the genuine reference's stored output (tests/golden/legacy1_kats.npz, tests/golden/legacy1_*.bgld) or the numpy restatement that
 tests/test_legacy1_ref.py holds to those (tests/legacy1_ref.py); bit equality throughout.  The switches are set through their setters and restored afterwards; the
 launch counters (prefill_mfma_runs) tell the matrix-core kernel from the integer-dot kernel, which gives the same bits.

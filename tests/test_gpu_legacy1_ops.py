@@ -17,7 +17,7 @@ TYPES = list(l1.TYPES)
 EPS = 1e-5
 MODES = (0, 1)                     # the launcher's choice and one wave per row-group; split-K (mode 2) does not exist for these types
 # the batched kernel takes token tiles of 8 while 8 activation images fit the LDS: 8 * blob bytes(K) <= 160 KB with blob bytes = 292 * K / 256 rounded up to 16
-# (bamd_launch_matmul_batch_q1), i.e. up to K = 17920 (70 records); K = 18176 is the first row length that takes tiles of 4
+# (bamd_launch_matmul_batch_b32), i.e. up to K = 17920 (70 records); K = 18176 is the first row length that takes tiles of 4
 K_TILE4 = 18176
 assert 8 * ((292 * (K_TILE4 // 256 - 1) + 15) // 16 * 16) <= 160 * 1024 < 8 * ((292 * (K_TILE4 // 256) + 15) // 16 * 16)
 

@@ -1,4 +1,4 @@
-"""GPU: the matrix-core prompt mat-mul for Q8_0 / Q4_0 / Q5_0 weights (booster_amd/csrc/bamd_prefill2_q0.hip, behind set_prefill_q0 / BAMD_PREFILL_Q0=1; default
+"""GPU: the matrix-core prompt mat-mul for Q8_0 / Q4_0 / Q5_0 weights (booster_amd/csrc/bamd_prefill2_b32.hip, behind set_prefill_q0 / BAMD_PREFILL_Q0=1; default
 off).  Every expectation is the genuine reference's stored output (tests/golden/legacy_kats.npz, tests/golden/legacy_*.bgld) or the numpy restatement that
 tests/test_legacy_ref.py holds to those (tests/legacy_ref.py); bit equality throughout.  The switch is set through the setter and restored afterwards; the launch
 counters (prefill_mfma_runs) tell the matrix-core kernel from the integer-dot kernel, which gives the same bits.

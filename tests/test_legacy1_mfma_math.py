@@ -1,4 +1,4 @@
-"""CPU: the arithmetic of the matrix-core prompt mat-mul for Q4_1 / Q5_1 weights (booster_amd/csrc/bamd_prefill2_q1.hip), checked before a GPU is involved.
+"""CPU: the arithmetic of the matrix-core prompt mat-mul for Q4_1 / Q5_1 weights (booster_amd/csrc/bamd_prefill2_b32.hip), checked before a GPU is involved.
 As tests/test_legacy_mfma_math.py for the Q8_0 family: per 32-weight block l and SIMD lane e of the reference the kernel multiplies the f16 images of four
 UNSIGNED weights (no offset: (0x6400 | u) - 1024 = u) and four int8 activations on the matrix cores and sums the four f32 products in whatever order the
 instruction takes; the scale product, the eight chains in block order and the tree follow on the vector ALUs, and next to them ONE more chain per output,

@@ -1,4 +1,4 @@
-"""CPU: the arithmetic of the matrix-core prompt mat-mul for Q8_0 / Q4_0 / Q5_0 weights (booster_amd/csrc/bamd_prefill2_q0.hip), checked before a GPU is
+"""CPU: the arithmetic of the matrix-core prompt mat-mul for Q8_0 / Q4_0 / Q5_0 weights (booster_amd/csrc/bamd_prefill2_b32.hip), checked before a GPU is
 involved.  Per 32-weight block l and SIMD lane e of the reference the kernel multiplies the f16 images of four weights and four int8 activations on the matrix
 cores and sums the four f32 products in whatever order the instruction takes; the scale product f32(d_w) * f32(d_x), the chain acc_e = fma(scale, dot4_e, acc_e)
 in block order and the hsum tree follow on the vector ALUs.  That is the reference's dot product only if every operand is an exact float16, every four-term sum
