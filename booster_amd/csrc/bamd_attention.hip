@@ -1,5 +1,5 @@
 // bamd_attention.hip — attention kernels: fused single-launch (decode of short sequences), three-launch long-sequence path, batched
-// prefill attention with all query heads of a KV head per workgroup, batched KV store.  Helpers and layout: bamd_device.h.
+// prefill attention with all query heads of a KV head per workgroup (body: bamd_attn_batch.h), batched KV store.  Helpers and layout: bamd_device.h.
 #include "bamd_device.h"
 
 // ---- long contexts: three launches (scores | softmax | P.V), positions / rows spread over many workgroups ------------------
@@ -169,6 +169,8 @@ __global__ void __launch_bounds__(1024) attn_softmax_kernel(bamd_attn_args a) {
     if (lane == 0) redd[wave] = sum;
     __syncthreads();
     double tot = 0.0; for (int w = 0; w < nw; ++w) tot += redd[w];
+    // guarded_softmax_rs (bamd_device.h) written out: with the write-back of the register-cached values in front of its first barrier the helper's form
+    // takes two more VGPRs here
     double rs = 1.0 / tot;
     float fs = (float) rs;
     if (!f32_rounding_safe(rs, BAMD_F64_GUARD_ULPS(n_kv / 8))) {          // workgroup-uniform, rare: the reference's sequential order (bamd_device.h)
@@ -349,15 +351,7 @@ __global__ void __launch_bounds__(1024) attn_spv_kernel(bamd_attn_args a, int gq
         double tot = 0.0;
 #pragma unroll
         for (int w = 0; w < 16; ++w) tot += redd[g][w];
-        double rs = 1.0 / tot;
-        if (!f32_rounding_safe(rs, BAMD_F64_GUARD_ULPS(n_kv / 8))) {          // workgroup-uniform, rare: the reference's sequential order (bamd_device.h)
-            __syncthreads();                                     // (the exponentials of the other threads; redd read by all)
-            if (tid == 0) redd[g][0] = seq_expsum8_vt(spv_p + g * n_ctx, n_kv);
-            __syncthreads();
-            rs = 1.0 / redd[g][0];
-            __syncthreads();
-        }
-        const float fs = (float) rs;
+        const float fs = (float) guarded_softmax_rs(tot, n_kv, &redd[g][0], [=] { return seq_expsum8_vt(spv_p + g * n_ctx, n_kv); }, [](int) { __syncthreads(); });
         float * pr = a.probs + (size_t) (h0 + g) * n_ctx;
         for (int B = B0; B <= last; B += 64) {
             if (BAMD_SPV_VALID(B)) {
@@ -418,137 +412,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 }
 
 // ---- batched prefill attention: one workgroup per (KV head, token) computes ALL GQH query heads that share the KV head -------
-// Same arithmetic per (token, head) as attn_fused_kernel in its T > 1 mode (q rounded to f16, ggml_vec_dot_f16 order for the scores,
-// softmax with the reference's 8-wide partial sums, tinyBLAS chains for P.V), but every K row and V^T chunk is loaded once for the
-// GQH heads, and the token's own K/V are already in the cache (kv_store_batch_kernel).  Dynamic LDS: GQH x ld floats.
+// attn_batch_body (bamd_attn_batch.h) with its rows in dynamic LDS: GQH x ld floats.  gq: query heads per KV head; GQH divides gq (the launcher's ladder
+// halves GQH until the rows fit), so the heads of a workgroup share one KV head.
+#include "bamd_attn_batch.h"
 template <int GQH>
 __global__ void __launch_bounds__(512) attn_batch_kernel(bamd_attn_args a, int gq) {
-    __shared__ __attribute__((aligned(16))) unsigned short q16t[GQH][256];
-    __shared__ float redf[GQH][8];
-    __shared__ double redd[GQH][8];
     extern __shared__ __attribute__((aligned(16))) unsigned char attn_dyn[];
-    const int ld = a.lds_ld ? a.lds_ld : a.n_ctx;                            // LDS row length: bounds the padded sequence length of the micro-batch
-    float * sc = (float *) attn_dyn;                                         // [GQH][ld] scores, then exp values, then — IN PLACE — the
-    float * pt = sc;                                                         // probabilities in V^T position order (vperm stays inside a 64-block)
-    const bamd_step_state * st = a.st;
-    const int tokb = blockIdx.y;
-    const int pos = st->pos + tokb;
-    int n_kv = (pos + 1 + 31) / 32 * 32; n_kv = n_kv < st->n_ctx ? n_kv : st->n_ctx;
-    const int hd = a.hd, Hkv = a.Hkv, Ekv = Hkv * hd, n_ctx = a.n_ctx, L = hd >> 3;
-    const int h0 = blockIdx.x * GQH, hk = h0 / gq;           // GQH divides gq: the heads of a workgroup share one KV head
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), e = lane & 7;
-    const int r_pos = wave * 8 + (lane >> 3);
-    const float * q = a.q + (size_t) tokb * a.ld_qkv + (size_t) h0 * hd;
-    const float * rope = a.rope + (size_t) pos * hd;
-    // RoPE of the GQH query heads -> f16, chain-major (rope_heads arithmetic; only the f16 copy is needed at T > 1)
-    for (int i = tid; i < GQH * (hd / 2); i += blockDim.x) {
-        const int hh = i / (hd / 2), p = i - hh * (hd / 2);
-        const float c = rope[2 * p], sn = rope[2 * p + 1];
-        const float x0 = q[hh * hd + 2 * p], x1 = q[hh * hd + 2 * p + 1];
-        const float t0 = x0 * c, t1 = x1 * sn, t2 = x0 * sn, t3 = x1 * c;
-        q16t[hh][kperm(2 * p, L)] = f2h(t0 - t1); q16t[hh][kperm(2 * p + 1, L)] = f2h(t2 + t3);
-    }
-    __syncthreads();
-    // ---- scores: K row i once, GQH chains ----
-    for (int t0 = 0; t0 < n_kv; t0 += 64) {
-        const int i = t0 + r_pos;
-        const bool valid = i < n_kv && i <= pos;
-        // unconditional requests (a masked position reads row `pos`, which this micro-batch stored), every chain runs, the mask is a select:
-        // a conditional load is a branch with a full wait at its join
-        const unsigned short * krow = a.kc + (size_t) (valid ? i : pos) * Ekv + hk * hd + e * 8;
-        uint4 kl[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) kl[g] = g * 8 < L ? *(const uint4 *) (krow + g * BAMD_KGRP) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (int hh = 0; hh < GQH; ++hh) {
-            float v = hsum8_vecdot(kq_chain<true>(kl, L, nullptr, &q16t[hh][0] + e * 8));
-            v = valid ? v : -INFINITY;                             // masked (KQ_mask, llama.cpp:14152-14200)
-            if (e == 0 && i < n_kv) sc[(size_t) hh * ld + i] = v;
-        }
-    }
-    __syncthreads();
-    // ---- softmax per head (ggml.c:13682-13778 + :2619-2671) ----
-    const float scale = a.kq_scale;
-#pragma unroll
-    for (int hh = 0; hh < GQH; ++hh) {
-        const float * s_ = sc + (size_t) hh * ld;
-        float mx = -INFINITY;
-        for (int i = tid; i < n_kv; i += blockDim.x) { const float w = s_[i] * scale; mx = w > mx ? w : mx; }
-        uint32_t u = __float_as_uint(mx); u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        u = wave_max_u32(u);
-        if (lane == 0) redf[hh][wave] = __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int hh = 0; hh < GQH; ++hh) {
-        float * s_ = sc + (size_t) hh * ld;
-        float mx = redf[hh][0];
-        for (int w = 1; w < 8; ++w) mx = redf[hh][w] > mx ? redf[hh][w] : mx;
-        double sum = 0.0;
-        for (int i = tid; i < n_kv; i += blockDim.x) {             // n_kv % 32 == 0: 8-lane groups are all-active or all-idle
-            const float w = s_[i] * scale;
-            const float val = v_expf(w - mx);
-            s_[i] = val;
-            const float c = hsum8_tinyblas(val);
-            if (e == 0) sum += (double) c;
-        }
-        sum = wave_sum_f64(sum);
-        if (lane == 0) redd[hh][wave] = sum;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int hh = 0; hh < GQH; ++hh) {
-        const float * s_ = sc + (size_t) hh * ld; float * p_ = pt + (size_t) hh * ld;
-        double tot = 0.0;
-        for (int w = 0; w < 8; ++w) tot += redd[hh][w];
-        double rs = 1.0 / tot;
-        float fs = (float) rs;
-        if (!f32_rounding_safe(rs, BAMD_F64_GUARD_ULPS(n_kv / 8))) {      // workgroup-uniform, rare: the reference's sequential order (bamd_device.h)
-            __syncthreads();
-            if (tid == 0) redd[hh][0] = seq_expsum8(s_, n_kv);
-            __syncthreads();
-            rs = 1.0 / redd[hh][0]; fs = (float) rs;
-        }
-        // one wave per 64-block: all 64 values are read before the permuted ones are written, so the block is permuted in place;
-        // the idle half of a half-filled last block becomes zeros (exact no-ops in the chains)
-        for (int i = tid; i < ((n_kv + 63) & ~63); i += blockDim.x) { const float val = i < n_kv ? s_[i] * fs : 0.f; p_[vperm(i)] = val; }
-    }
-    __syncthreads();
-    // ---- P.V: V^T chunk once, GQH chains; lane (d, e) carries Cv[e] of output d, up to 4 rows d per lane ----
-    float acc[GQH][4];
-#pragma unroll
-    for (int hh = 0; hh < GQH; ++hh) { acc[hh][0] = 0.f; acc[hh][1] = 0.f; acc[hh][2] = 0.f; acc[hh][3] = 0.f; }
-    for (int b0 = 0; b0 < n_kv; b0 += 64) {
-#pragma unroll
-        for (int dd = 0; dd < 4; ++dd) {
-            if (r_pos + 64 * dd < hd) {
-                const uint4 vv = *(const uint4 *) (a.vc + (size_t) (hk * hd + r_pos + 64 * dd) * n_ctx + b0 + e * 8);
-                const uint32_t w[4] = { vv.x, vv.y, vv.z, vv.w };
-                float vf[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) vf[u] = h2f((w[u >> 1] >> (16 * (u & 1))) & 0xffffu);
-#pragma unroll
-                for (int hh = 0; hh < GQH; ++hh) {
-                    const float * p_ = pt + (size_t) hh * ld + b0 + e * 8;
-                    const float4 pa = *(const float4 *) p_, pb = *(const float4 *) (p_ + 4);
-                    const float pv[8] = { pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w };
-                    float c = acc[hh][dd];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) c = fmaf(vf[u], pv[u], c);
-                    acc[hh][dd] = c;
-                }
-            }
-        }
-    }
-    float * out = a.out + (size_t) tokb * a.ld_out + (size_t) h0 * hd;
-#pragma unroll
-    for (int hh = 0; hh < GQH; ++hh) {
-#pragma unroll
-        for (int dd = 0; dd < 4; ++dd) {
-            const int d = r_pos + 64 * dd;
-            if (d < hd) { const float v = hsum8_tinyblas(acc[hh][dd]); if (e == 0) out[(size_t) hh * hd + d] = v; }
-        }
-    }
+    const int h0 = blockIdx.x * GQH;
+    attn_batch_body<GQH>(a, h0 / gq, h0, (int) blockIdx.y, AttnRowsLDS{(float *) attn_dyn});
 }
 
 // batched prefill: RoPE(K) + KV store of every token of the micro-batch, before any of them attends (grid (Hkv, T))

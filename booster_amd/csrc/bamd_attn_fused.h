@@ -147,14 +147,7 @@ __device__ __forceinline__ void attn_fused_body(bamd_attn_args a, int gq, const 
     env.sync();
     double tot = 0.0;
     for (int w = 0; w < 8; ++w) tot += redd[w];
-    double rs = 1.0 / tot;
-    float fs = (float) rs;
-    if (!f32_rounding_safe(rs, BAMD_F64_GUARD_ULPS(n_kv / 8))) {          // workgroup-uniform, rare: the reference's sequential order (bamd_device.h)
-        env.sync();
-        if (tid == 0) redd[0] = seq_expsum8(sc, n_kv);
-        env.sync();
-        rs = 1.0 / redd[0]; fs = (float) rs;
-    }
+    const float fs = (float) guarded_softmax_rs(tot, n_kv, &redd[0], [=] { return seq_expsum8(sc, n_kv); }, [&](int k) { if (k < 2) env.sync(); });
     for (int i = tid; i < n_kv; i += env.nthr) pt[vperm(i)] = sc[i] * fs;
     // half-filled last block (n_kv % 64 == 32): p = 0 for the missing positions, so the chain steps there are exact no-ops
     for (int i = n_kv + tid; i < ((n_kv + 63) & ~63); i += env.nthr) pt[vperm(i)] = 0.f;

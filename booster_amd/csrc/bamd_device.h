@@ -244,6 +244,24 @@ __device__ __forceinline__ double seq_expsum8(const float * vals, int n) {
     }
     return s;
 }
+// 1 / sum of a workgroup-wide softmax: tot = the tree sum over the waves' partials (the same double in every thread) of the n / 8 8-wide terms of n exp values.
+// Where the guard cannot rule the order out (workgroup-uniform, rare) ONE lane redoes the sum in the reference's sequential order — seq(): seq_expsum8 over
+// the site's exp values — and hands it over in *slot (LDS).  bar(k) is the site's barrier at k = 0: in front of the sequential sum (the other threads' exp
+// values; *slot read by all), 1: behind it, 2: behind the re-read of *slot.  A plain site synchronises at 0 and 1 (GuardSync).
+// The callables capture by value where they can: a site keeps the code object it had with the sequence written out (tools/codeobj_diff.py).
+struct GuardSync { __device__ __forceinline__ void operator()(int k) const { if (k < 2) __syncthreads(); } };
+template <typename SEQ, typename BAR = GuardSync>
+__device__ __forceinline__ double guarded_softmax_rs(double tot, int n, double * slot, SEQ seq, BAR bar = BAR()) {
+    double rs = 1.0 / tot;
+    if (!f32_rounding_safe(rs, BAMD_F64_GUARD_ULPS(n / 8))) {
+        bar(0);
+        if (threadIdx.x == 0) *slot = seq();
+        bar(1);
+        rs = 1.0 / *slot;
+        bar(2);
+    }
+    return rs;
+}
 
 // One wave quantises BATCH super-blocks at a time (independent dependency chains interleave); lane l holds the 4
 // consecutive elements 4l..4l+3 of a block.  quantize_row_q8_K_ref semantics (ggml-quants.c:3593-3630): the scale comes

@@ -53,6 +53,16 @@ def test_first_ld_beyond_the_lds_valu(bamd, po, gq, hd):
     run(bamd, po, gq, 1, hd, FIRST["n_ctx"], FIRST["pos0"], FIRST["T"], [(1, ld, 0) for ld in LDS])
 
 
+# ---- attn_batch_body's two instantiations on identical inputs ----
+@pytest.mark.parametrize("gq,hd", [(2, 64), (4, 64), (8, 64), (8, 256)])
+def test_lds_rows_equal_scratch_rows(bamd, po, gq, hd):
+    """one micro-batch through impl 1 with its rows in LDS (ld 4608: attn_batch_kernel<gq>, no ladder step — 8 x 4608 x 4 B = 144 KiB) and in the scratch block
+    (ld 18496: attn_batch_gs_kernel<gq>): each == the oracle (run()) and the two == each other.  Positions 77 .. 87 in n_kv = 96: a masked tail and a half-filled
+    last 64-block"""
+    (a, _), (b, _) = run(bamd, po, gq, 1, hd, FIRST["n_ctx"], FIRST["pos0"], FIRST["T"], [(1, 4608, 0), (1, 18496, 0)])
+    assert_bits(a, b, "rows in LDS (ld 4608) vs rows in the scratch block (ld 18496)")
+
+
 # ---- really long sequences ----
 @pytest.mark.parametrize("H,Hkv,hd,n_ctx,pos0,T,impls", [
     (8, 2, 128, 18592, 18530, 37, (0, 1, 2)),              # n_ctx = 32 mod 64, last cell filled, T ragged against the token tile of 4

@@ -14,9 +14,9 @@ A shape the launcher declines or routes elsewhere FAILS.  Mat-vec cases call the
   ActProQ0::finish_q0      bamd_b32_device.h          test_q8_0_family, test_q8_1_family
   attn_softmax_kernel      bamd_attention.hip         test_softmax_kernel (cached 96 / 4128, uncached 8224), test_softmax_kernel_cells (holes)
   attn_spv_kernel<NH>      bamd_attention.hip         test_spv (NH 1, 2, 4)
-  attn_batch_kernel<GQH>   bamd_attention.hip         test_batch_valu
+  attn_batch_kernel<GQH>   bamd_attn_batch.h          test_batch_valu (attn_batch_body, rows in LDS)
   attn_fused_body          bamd_attn_fused.h          test_fused (single launch), test_colaunch (attention || wo, COLAUNCH = true)
-  attn_batch_gs_kernel     bamd_attention_gs.hip      test_batch_scratch_rows
+  attn_batch_gs_kernel     bamd_attn_batch.h          test_batch_scratch_rows (the same attn_batch_body, rows in the scratch block)
   attn_batch_mfma_kernel<GQ, false>                   test_batch_mfma, padded length <= 512: rows in LDS (64 and 448 positions)
   attn_batch_mfma_kernel<GQ, true>                    test_batch_mfma, padded length > 512: rows in the scratch block (576 positions; 64 and 576 under ld 18496)
 
