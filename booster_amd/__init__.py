@@ -68,6 +68,7 @@ def lib():
         L.bamd_op_quantize_q8_K.argtypes = [vp, i64, vp, cf, vp]
         L.bamd_op_quantize_q8_0.argtypes = [vp, i64, vp, cf, vp]
         L.bamd_op_quantize_q8_1.argtypes = [vp, i64, vp, cf, vp]
+        L.bamd_op_act_bf16.argtypes = [vp, i64, vp, cf, vp]
         L.bamd_op_mul_mat_vec.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, vp, ci]
         L.bamd_op_mul_mat_vec_argmax.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, ci, C.POINTER(C.c_int32)]
         L.bamd_op_ffn_gate_up.argtypes = [ci, vp, vp, ci, ci, vp, vp, cf, vp]
@@ -335,6 +336,16 @@ def op_quantize_q8_1(x, norm_w=None, eps=0.0):
     w = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32)
     out = np.zeros(x.size // 32 * 36, np.uint8)
     _chk(lib().bamd_op_quantize_q8_1(_p(x), x.size, _p(w), eps, _p(out)))
+    return out
+
+
+def op_act_bf16(x, norm_w=None, eps=0.0):
+    """the mat-vec prologue of the BF16 kernels: the (normed) vector as bf16 bits (uint16), ggml_fp32_to_bf16_row.  F32 / F16 weights take the f32 vector as it
+    is; the mat-vec / mat-mul ops accept the types 0 (F32), 1 (F16) and 30 (BF16) with w_raw = the row-major bytes of the matrix"""
+    x = np.ascontiguousarray(x, np.float32)
+    w = None if norm_w is None else np.ascontiguousarray(norm_w, np.float32)
+    out = np.zeros(x.size, np.uint16)
+    _chk(lib().bamd_op_act_bf16(_p(x), x.size, _p(w), eps, _p(out)))
     return out
 
 

@@ -300,6 +300,7 @@ int bamd_launch_attn_wo(const bamd_attn_args & t, int gq, const bamd_mv_args & w
     const int H = t.Hkv * gq, ld = t.lds_ld ? t.lds_ld : t.n_ctx;
     if (t.batch || t.cellpos || t.hd > 256 || (t.hd & 63) || gq < 1 || gq > 8 || (ld & 63) || (size_t) ld * 8 > BAMD_ATTN_LDS_MAX || il < 0 || il > 255) return 1;
     const int nb = wo.K >> 8, type = wo.seg[0].type;
+    if (bamd_is_flt(type)) return 1;                                                          // an F32 / F16 / BF16 wo: the two launches
     if (wo.nseg != 1 || (nb != 16 && nb != 32) || (wo.mode & 31) != 0 || !wo.res) return 1;  // K = 4096: two records per wave and row-group; K = 8192: four, in batches
     const int G = n_cu - H, nrg = wo.seg[0].nrows >> 3;
     if (G < 8) return 1;

@@ -1047,6 +1047,9 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
     } else if (embd_type == BAMD_F16) {
         const unsigned short * src = (const unsigned short *) embd + (size_t) tok * E;
         for (int i = threadIdx.x; i < E; i += blockDim.x) ik_st(x + i, h2f(src[i]));
+    } else if (embd_type == BAMD_BF16) {                                   // ggml_bf16_to_fp32_row: bits << 16
+        const unsigned short * src = (const unsigned short *) embd + (size_t) tok * E;
+        for (int i = threadIdx.x; i < E; i += blockDim.x) ik_st(x + i, __uint_as_float((uint32_t) src[i] << 16));
     } else if (bamd_is_q0(embd_type)) {
         // dequantize_row_q8_0 / q4_0 / q5_0 (ggml-quants.c:1609, :1515, :1556): y = (q - 8 | 16 | 0) * d, one f32 product of the integer and the widened f16 d
         const int bb = bamd_block_bytes(embd_type);

@@ -196,11 +196,13 @@ static int upload_mat(bamd_model * m, const GgufTensor * t, DevMat & d, bool kee
                       void * stream_dst = nullptr) {
     if (t->ne.size() != 2) return fail("tensor " + t->name + ": expected 2 dims");
     d.type = t->type; d.K = (int) t->ne[0]; d.nrows = (int) t->ne[1]; d.bytes = t->nbytes;
-    if (d.type != BAMD_F32 && d.type != BAMD_F16 && !bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
+    if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
     if (bamd_has_record(d.type) && d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     if (want_stream) {
-        if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": only Q4_0/Q4_1/Q5_0/Q5_1/Q8_0/Q2_K/Q3_K/Q4_K/Q5_K/Q6_K matrices are supported on the matmul path");
         if (d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
+        // an unquantised matrix keeps its whole activation vector in the LDS of a CU (bamd_matvec_flt.hip): refused here, not at the first launch
+        if (bamd_is_flt(d.type) && d.K > bamd_flt_max_k(d.type))
+            return fail("tensor " + t->name + ": row length " + std::to_string(d.K) + " is beyond what the F32 / F16 / BF16 mat-vec kernels hold in LDS (" + std::to_string(bamd_flt_max_k(d.type)) + " for this type)");
     }
     d.nrows_pad = (d.nrows + 7) / 8 * 8;
     if (d.nrows_pad != d.nrows && stream_dst) return fail("tensor " + t->name + ": fused QKV needs row counts that are multiples of 8");
@@ -346,7 +348,7 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
             for (int j = 1; j < 3 && !rc; ++j)
                 if (bamd_act_form_of(mats[j].d->type) != bamd_act_form_of(mats[0].d->type))
                     rc = fail(p + mats[0].n + ".weight (type " + std::to_string(mats[0].d->type) + ") and " + p + mats[j].n + ".weight (type " + std::to_string(mats[j].d->type) +
-                              ") need different activation formats (" + (bamd_is_q1(mats[0].d->type) || bamd_is_q1(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1" : "Q8_K / Q8_0") + ") in one fused launch: not supported");
+                              ") need different activation formats (" + (bamd_is_flt(mats[0].d->type) || bamd_is_flt(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1 / F32 / BF16" : bamd_is_q1(mats[0].d->type) || bamd_is_q1(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1" : "Q8_K / Q8_0") + ") in one fused launch: not supported");
             if (rc) break;
         }
     } while (0);
@@ -825,7 +827,8 @@ static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStre
     if (!(g_prefill_batch && g_attn_fused && m->hd <= 256 && (m->hd & 63) == 0 && gq >= 1 && gq <= 8)) return false;
     // every mat-mul needs a kernel: the matrix-core kernels take every K-quant at any K when the model has its side tables; the integer-dot kernel
     // takes any K-quant while 4 tokens of Q8_K activations fit the LDS (K <= 35840; tiles of 8 tokens up to K = 17920)
-    auto ok = [&](int type, int K) { return (g_prefill_mfma && m->aux_ok && bamd_prefill_mfma_type(type)) || 4 * bamd_blob_bytes(K) <= 160 * 1024; };
+    // (the unquantised family: its VALU kernel takes any K the load accepted)
+    auto ok = [&](int type, int K) { return bamd_is_flt(type) || (g_prefill_mfma && m->aux_ok && bamd_prefill_mfma_type(type)) || 4 * bamd_blob_bytes(K) <= 160 * 1024; };
     for (const DevLayer & ly : m->layers)
         if (!ok(ly.wq.type, m->E) || !ok(ly.wk.type, m->E) || !ok(ly.wv.type, m->E) || !ok(ly.wo.type, m->E) || !ok(ly.wg.type, m->E) || !ok(ly.wu.type, m->E) || !ok(ly.wd.type, m->F)) return false;
     return ensure_attn_scratch(c, T, n_past, s);
@@ -850,7 +853,8 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     size_t need = 0;
     for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
         // (with every switch off the reasons read as they did before the switches existed; with one of BAMD_PREFILL_Q0 / BAMD_PREFILL_Q1 on, the one that is missing is named)
-        m->aux_why = bamd_is_q1(it.type) && bamd_prefill_q0() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_Q0 covers only its Q4_0 / Q5_0 / Q8_0 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+        m->aux_why = bamd_is_flt(it.type) ? "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels"
+                   : bamd_is_q1(it.type) && bamd_prefill_q0() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_Q0 covers only its Q4_0 / Q5_0 / Q8_0 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q0(it.type) && bamd_prefill_q1() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_Q1 covers only its Q4_1 / Q5_1 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q0(it.type) ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
@@ -886,10 +890,13 @@ static int ensure_batch_buffers(bamd_context * c) {
     if (c->bcap) return 0;
     bamd_model * m = c->m;
     const size_t T = BAMD_PREFILL_CAP, Ekv = (size_t) m->Hkv * m->hd;
+    size_t flt_bytes = 0;
+    for (const DevLayer & ly : m->layers)
+        for (const DevMat * d : { &ly.wq, &ly.wk, &ly.wv, &ly.wo, &ly.wg, &ly.wu, &ly.wd }) flt_bytes = std::max(flt_bytes, bamd_flt_act_bytes(bamd_act_form_of(d->type), d->K));
     if (dev_alloc(c->allocs, (void **) &c->bx, T * m->E * 4) || dev_alloc(c->allocs, (void **) &c->bx2, T * m->E * 4) ||
         dev_alloc(c->allocs, (void **) &c->bqkv, T * (m->E + 2 * Ekv) * 4) || dev_alloc(c->allocs, (void **) &c->batt, T * m->E * 4) ||
         dev_alloc(c->allocs, (void **) &c->bh, T * m->F * 4) ||
-        dev_alloc(c->allocs, (void **) &c->bblob, T * bamd_blob_bytes(std::max(m->E, m->F))) ||
+        dev_alloc(c->allocs, (void **) &c->bblob, T * std::max(bamd_blob_bytes(std::max(m->E, m->F)), flt_bytes)) ||      // (an unquantised matrix takes its activations as f32 / bf16 rows)
         dev_alloc(c->allocs, (void **) &c->bblob16, T * bamd_blob16_bytes(std::max(m->E, m->F)))) return 1;     // (one stride for every form: the K-quant record's 608 B hold the 544 B of the Q8_0 form and the 576 B of the Q8_1 form)
     c->bcap = (int) T;
     return 0;

@@ -117,7 +117,7 @@ bool GgufFile::open_one(const std::string & path, std::string & err) {
     for (size_t i = 0; i < tensors.size(); ++i) {
         auto & t = tensors[i];
         unsigned __int128 rows = 1; for (size_t d = 1; d < t.ne.size(); ++d) rows *= (unsigned __int128) t.ne[d];
-        const bool known = t.type == BAMD_F32 || t.type == BAMD_F16 || bamd_has_record(t.type);
+        const bool known = bamd_has_record(t.type);      // F32, F16 and BF16 included
         const unsigned __int128 nbytes = known ? (unsigned __int128) bamd_row_bytes(t.type, t.ne.empty() ? 0 : t.ne[0]) * rows : 0;
         if (data_off > size_ || t.offset > size_ - data_off || nbytes > (unsigned __int128) (size_ - data_off - t.offset)) { err = "tensor " + t.name + " out of file bounds"; return false; }
         t.nbytes = (size_t) nbytes;

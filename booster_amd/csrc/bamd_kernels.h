@@ -82,7 +82,16 @@ void bamd_launch_quantize_q8k_test(const float * x, const float * nw, float eps,
 // what the engine and the ops call: the family of the first segment picks the launcher, and each launcher refuses a segment of another family (a launch
 // quantises its activations once, as Q8_K, as Q8_0 or as Q8_1: bamd_act_form_of).  bamd_launch_matvec itself stays the K-quant launcher that tests/test_launch_selection.py pins, its
 // refusal of every other type included
+// the unquantised family, F32 / F16 (f32 activations) and BF16 (bf16 activations): bamd_matvec_flt.hip; 1 = a segment of another activation form, or a K the LDS does not hold
+[[nodiscard]] int bamd_launch_matvec_flt(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
+void bamd_launch_repack_flt(const void * raw, void * dst, int type, int nrows, int K, hipStream_t s);                  // behind bamd_launch_repack
+void bamd_launch_act_bf16_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
+// batched prompt path of that family (bamd_prefill_flt.hip; behind bamd_launch_quantize_batch / bamd_launch_matmul_batch): a token's activations are
+// bamd_flt_act_bytes(form, K) bytes, in the order the chains read them
+void bamd_launch_act_batch_flt(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s);
+int  bamd_launch_matmul_batch_flt(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);
 [[nodiscard]] static inline int bamd_launch_mv(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
+    if (a.nseg > 0 && bamd_is_flt(a.seg[0].type)) return bamd_launch_matvec_flt(a, pro, epi, n_cu, s);
     return a.nseg > 0 && (bamd_is_q0(a.seg[0].type) || bamd_is_q1(a.seg[0].type)) ? bamd_launch_matvec_b32(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
 }
 void bamd_launch_quantize_q81_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
@@ -101,6 +110,8 @@ int  bamd_launch_attn_wo(const bamd_attn_args & t, int gq, const bamd_mv_args & 
 void bamd_launch_k_shift(unsigned short * kc, int n_cells, int Hkv, int hd, const int32_t * tab_of_cell, const float * tab, hipStream_t s);
 size_t bamd_blob_bytes(int K);
 size_t bamd_blob16_bytes(int K);
+// bytes of one token's activations in `form` (any bamd_act_form): what a caller of bamd_launch_quantize_batch allocates per token
+static inline size_t bamd_act_blob_bytes(int form, int K) { const size_t f = bamd_flt_act_bytes(form, K); return f ? f : bamd_blob_bytes(K); }
 // blob: int8 activations for matmul_batch_kernel (may be null); blob16: f16 copy for the MFMA kernel (may be null)
 // form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_0 for Q8_0 / Q4_0 / Q5_0 weights, BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_0 / Q8_1 form
 // of the same size (bamd_prefill_b32.hip); blob16 is written, in the f16 form of bamd_prefill2_b32.hip (544 / 576 bytes of a record, the same per-token stride), only

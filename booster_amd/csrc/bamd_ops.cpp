@@ -62,11 +62,24 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_quantize_q8_1(cons
     return finish(out_blocks, dout, ob);
 }
 
+// the activation form of BF16 weights, in the order of the vector: k values of ggml_fp32_to_bf16_row (the sibling of bamd_op_quantize_q8_0)
+extern "C" __attribute__((visibility("default"))) int bamd_op_act_bf16(const float * x, int64_t k, const float * norm_w, float eps, uint16_t * out_u16) {
+    if (need_device()) return 1;
+    if (k <= 0 || k % 256 || k > bamd_flt_max_k(BAMD_BF16)) return fail("k must be a positive multiple of 256 (at most 65536)");
+    Tmp t; const size_t ob = (size_t) k * 2;
+    float * dx = (float *) t.up(x, (size_t) k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr; void * dout = t.up(nullptr, ob);
+    if (!dx || !dout || (norm_w && !dw)) return fail("device alloc/copy failed");
+    HIPC(hipMemset(dout, 0, ob));
+    bamd_launch_act_bf16_test(dx, dw, eps, (int) k, norm_w != nullptr, dout, nullptr);
+    return finish(out_u16, dout, ob);
+}
+
 static int op_matvec(int type, const void * wA, const void * wB, int nrows, int k, const float * x, const float * norm_w, float eps,
                      const float * residual, float * y, int epi, int mode, unsigned long long * best_key = nullptr) {
     if (need_device()) return 1;
     if (!bamd_has_record(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
     if (bamd_is_q1(type) && (mode & 15) == 2) return fail("mat-vec: Q4_1 / Q5_1 have no split-K kernel (mode 2): one wave per row-group only");
+    if (bamd_is_flt(type) && k > bamd_flt_max_k(type)) return fail("mat-vec: row length beyond what the F32 / F16 / BF16 kernels hold in LDS");
     const int nrows_pad = (nrows + 7) / 8 * 8;
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
     void * rawA = t.up(wA, wb), * strA = t.up(nullptr, wbp), * rawB = nullptr, * strB = nullptr;
@@ -111,11 +124,12 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     void * raw = t.up(w_raw, wb), * str = t.up(nullptr, wbp);
     float * dx = (float *) t.up(x, (size_t) T * k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr;
     float * dres = residual ? (float *) t.up(residual, (size_t) T * nrows * 4) : nullptr; float * dy = (float *) t.up(nullptr, (size_t) T * nrows * 4);
-    void * blob = t.up(nullptr, (size_t) T * bamd_blob_bytes(k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
+    void * blob = t.up(nullptr, (size_t) T * bamd_act_blob_bytes(bamd_act_form_of(type), k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
     if (!raw || !str || !dx || !dy || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     HIPC(hipMemset(str, 0, wbp));
     bamd_launch_repack(raw, str, type, nrows, k, nullptr);
     bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(type));
+    if (bamd_is_flt(type) && impl != 0) return fail(impl == 2 ? "MFMA path: unsupported type/shape (F32 / F16 / BF16 have no matrix-core kernel)" : "batched mat-mul: impl must be 0 for F32 / F16 / BF16");
     if (impl == 2) {                                                // the matrix-core kernel: side table built here, as the engine builds it at model load
         if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K with the switch off (bamd_prefill_mfma_type): the integer-dot kernel only
         void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
@@ -137,7 +151,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_ffn_gate_up(int ty
 extern "C" __attribute__((visibility("default"))) int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y) {
     if (need_device()) return 1;
     if (type != BAMD_F32 && type != BAMD_F16 && !bamd_has_record(type)) return fail("bad type");
-    if (k <= 0 || (bamd_has_record(type) && k % 256)) return fail("bad row length");
+    if (k <= 0 || (bamd_has_record(type) && type != BAMD_F32 && type != BAMD_F16 && k % 256)) return fail("bad row length");
     if (row < 0 || row >= nrows) return fail("row out of range");
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows;
     void * raw = t.up(w_raw, wb); float * dy = (float *) t.up(nullptr, (size_t) k * 4);
@@ -386,12 +400,13 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(
     float * dy = (float *) t.up(y, ob);                                      // the caller's content stays where the launch writes nothing
     float * dx = (float *) t.up(x, (size_t) T * k * 4); float * dw = norm_w ? (float *) t.up(norm_w, (size_t) k * 4) : nullptr;
     float * dres = residual ? (float *) t.up(residual, ob) : nullptr;
-    void * blob = t.up(nullptr, (size_t) T * bamd_blob_bytes(k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
+    void * blob = t.up(nullptr, (size_t) T * bamd_act_blob_bytes(bamd_act_form_of(types[0]), k)), * blob16 = t.up(nullptr, (size_t) T * bamd_blob16_bytes(k));
     if (!dy || !dx || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     SegFixture f; if (f.build(t, nseg, types, w_raw, rows, k, dy, epi == BAMD_EPI_SILU_MUL)) return 1;
-    for (int i = 1; i < nseg; ++i) if (bamd_act_form_of(f.seg[i].type) != bamd_act_form_of(f.seg[0].type)) return fail(bamd_is_q1(f.seg[i].type) || bamd_is_q1(f.seg[0].type) ? "batched mat-mul: segments that need different activation forms (Q8_K, Q8_0, Q8_1)" : "batched mat-mul: segments that need both activation forms (Q8_K and Q8_0)");
+    for (int i = 1; i < nseg; ++i) if (bamd_act_form_of(f.seg[i].type) != bamd_act_form_of(f.seg[0].type)) return fail(bamd_is_flt(f.seg[i].type) || bamd_is_flt(f.seg[0].type) ? "batched mat-mul: segments that need different activation forms (Q8_K, Q8_0, Q8_1, F32, BF16)" : bamd_is_q1(f.seg[i].type) || bamd_is_q1(f.seg[0].type) ? "batched mat-mul: segments that need different activation forms (Q8_K, Q8_0, Q8_1)" : "batched mat-mul: segments that need both activation forms (Q8_K and Q8_0)");
     bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(f.seg[0].type));
     const void * aux[3] = { nullptr, nullptr, nullptr };
+    if (impl == 2 && bamd_is_flt(f.seg[0].type)) return fail("MFMA path: unsupported type/shape (F32 / F16 / BF16 have no matrix-core kernel)");
     if (impl == 2) for (int i = 0; i < nseg; ++i) {
         const size_t ab = bamd_prefill_aux_bytes(f.seg[i].type, f.seg[i].nrows, k);
         if (!ab) continue;                                                   // Q2_K / Q3_K with the switch off, or a shape without a matrix-core kernel
@@ -533,6 +548,13 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
     std::vector<uint8_t> hw(wb);
     uint32_t sd = 12345u; for (size_t i = 0; i < wb; ++i) { sd = sd * 1664525u + 1013904223u; hw[i] = (uint8_t) (sd >> 24); }
     const int bb = bamd_block_bytes(type);
+    if (bamd_is_flt(type)) {                                  // finite values around 0.004 of either sign
+        for (size_t i = 0; i < wb / (type == BAMD_F32 ? 4 : 2); ++i) {
+            if (type == BAMD_F32) { hw[4 * i + 3] = (uint8_t) (0x3b | (hw[4 * i + 3] & 0x80)); hw[4 * i + 2] |= 0x80; }
+            else if (type == BAMD_F16) hw[2 * i + 1] = (uint8_t) (0x1c | (hw[2 * i + 1] & 0x83));
+            else { hw[2 * i + 1] = (uint8_t) (0x3b | (hw[2 * i + 1] & 0x80)); hw[2 * i] |= 0x80; }
+        }
+    } else
     for (size_t b = 0; b < wb / bb; ++b) {                    // sane f16 scales (0x1c00 ~ 0.0039)
         uint8_t * p = hw.data() + b * bb;
         if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; }

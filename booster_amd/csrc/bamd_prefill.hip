@@ -202,12 +202,14 @@ __global__ void __launch_bounds__(256) embed_batch_kernel(const int32_t * __rest
 size_t bamd_blob_bytes(int K) { return BAMD_BLOB_BYTES(K >> 8); }
 size_t bamd_blob16_bytes(int K) { return BAMD_BLOB16_BYTES(K >> 8); }
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form) {
+    if (form == BAMD_ACT_F32 || form == BAMD_ACT_BF16) { bamd_launch_act_batch_flt(form, x, nw, eps, K, T, blob, s); return; }
     if (form == BAMD_ACT_Q8_1) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_q1() ? blob16 : nullptr); return; }
     if (form == BAMD_ACT_Q8_0) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_q0() ? blob16 : nullptr); return; }
     if (nw) hipLaunchKernelGGL((quantize_batch_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
     else    hipLaunchKernelGGL((quantize_batch_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
 }
 int bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s) {
+    if (a.nseg > 0 && bamd_is_flt(a.seg[0].type)) return bamd_launch_matmul_batch_flt(a, epi, n_cu, s);      // f32 / bf16 activations (bamd_prefill_flt.hip)
     if (a.nseg > 0 && (bamd_is_q0(a.seg[0].type) || bamd_is_q1(a.seg[0].type))) return bamd_launch_matmul_batch_b32(a, epi, n_cu, s);      // Q8_0 / Q8_1 activations: kernels of their own; a launch that mixes the forms has none
     int nrg = 0;
     if (epi == BAMD_EPI_SILU_MUL) nrg = a.seg[0].nrows >> 3; else for (int i = 0; i < a.nseg; ++i) nrg += a.seg[i].nrows >> 3;

@@ -26,12 +26,14 @@ GGML_TYPES = {
     12: (256, 144),   # Q4_K
     13: (256, 176),   # Q5_K
     14: (256, 210),   # Q6_K
+    30: (1, 2),       # BF16
 }
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
 Q2_K, Q3_K = 10, 11
 Q4_0, Q5_0, Q8_0 = 2, 6, 8
 Q4_1, Q5_1 = 3, 7
-TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K"}
+BF16 = 30
+TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 30: "BF16"}
 
 # gguf KV value types
 T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I64, T_F64 = range(13)
@@ -194,6 +196,8 @@ class GGUFWriter:
 def random_kquant_tensor(ttype, row_len, n_rows, rng, amp=1.0):
     """Random raw blocks of type `ttype` for an [n_rows, row_len] matrix whose dequantised values are roughly
     zero-mean with standard deviation ~ amp / sqrt(row_len)."""
+    if ttype in (F32, F16, BF16):
+        return random_float_tensor(ttype, row_len, n_rows, rng, amp)
     if ttype in (Q4_0, Q5_0, Q8_0):
         return random_q0_tensor(ttype, row_len, n_rows, rng, amp)
     if ttype in (Q4_1, Q5_1):
@@ -252,6 +256,41 @@ def random_q1_tensor(ttype, row_len, n_rows, rng, amp=1.0):
     blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
     blk[:, 2:4] = m.astype(np.float16).view(np.uint8).reshape(-1, 2)
     return blk.reshape(-1)
+
+
+def f32_to_bf16(x):
+    """ggml_compute_fp32_to_bf16 (ggml-impl.h:88-101) on an array: uint16 bits, round to nearest even, NaN quieted"""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    r = ((u.astype(np.uint64) + 0x7fff + ((u >> 16) & 1)) >> 16).astype(np.uint32)
+    return np.where((u & 0x7fffffff) > 0x7f800000, (u >> 16) | 64, r).astype(np.uint16)
+
+
+def random_float_tensor(ttype, row_len, n_rows, rng, amp=1.0):
+    """Raw bytes of a seeded unquantised [n_rows, row_len] matrix of type F32 / F16 / BF16: normal values with standard deviation amp / sqrt(row_len), the
+    magnitude of the quantised synthetic tensors (logits stay finite and distinct), rounded to the type."""
+    v = (rng.standard_normal((n_rows, row_len)) * (amp / np.sqrt(row_len))).astype(np.float32)
+    if ttype == F32:
+        return v.view(np.uint8).reshape(-1)
+    if ttype == F16:
+        return v.astype(np.float16).view(np.uint8).reshape(-1)
+    if ttype == BF16:
+        return f32_to_bf16(v).view(np.uint8).reshape(-1)
+    raise ValueError(ttype)
+
+
+def f16_type(name, il, n_layer):
+    """convert_hf_to_gguf --outtype f16: every matrix F16, token_embd and output.weight included (norms stay F32)."""
+    return F16
+
+
+def bf16_type(name, il, n_layer):
+    """convert_hf_to_gguf --outtype bf16: every matrix BF16."""
+    return BF16
+
+
+def f32_type(name, il, n_layer):
+    """convert_hf_to_gguf --outtype f32: every matrix F32."""
+    return F32
 
 
 def q8_0_type(name, il, n_layer):
@@ -336,7 +375,8 @@ def q2_k_type(name, il, n_layer, n_gqa=4):
 
 def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_ctx_train=8192, seed=7,
                           type_fn=None, rope_freqs=False, embd_type=Q4_K, reuse_layers=False, vocab=None, n_split=0, rope_scaling=None, tied=False):
-    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0) blocks.
+    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0) blocks, or unquantised F32 / F16 / BF16 matrices
+    (embd_type may be one of those too).
     reuse_layers: generate each (tensor kind, type) once and reuse the bytes in every layer (fast path for the
     multi-GB benchmark model; the arithmetic and the bytes streamed per token are unchanged).
     tied: no output.weight — the reader falls back to token_embd.weight (Llama-3.2; llama.cpp:6070-6076)."""
@@ -358,6 +398,9 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
         full-size fixtures (every logit digest of the reference's run) catch it; generation stays O(1) per layer."""
         if not reuse_layers:
             return None
+        if t in (F32, F16, BF16):                             # the low mantissa byte of 64 weights (il + 1 < 64 leaves the exponent alone)
+            bb = GGML_TYPES[t][1]; n = min(64, rows)
+            return ([(k * rows // n) * cols * bb + (k % 32) * bb for k in range(n)], il + 1)
         be, bb = GGML_TYPES[t]; nb = cols // be
         qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32, Q4_0: 2, Q5_0: 6, Q8_0: 2, Q4_1: 4, Q5_1: 8}[t]      # qs / qs / ql / qs / qs / qs / qs / qs / qs / qs
         n = min(64, rows)

@@ -20,7 +20,7 @@ typedef struct bamd_model   bamd_model;
 typedef struct bamd_context bamd_context;
 
 /* ggml tensor type ids, as stored in GGUF (cpp/ggml/include/ggml.h:360-375) */
-enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q2_K = 10, BAMD_TYPE_Q3_K = 11, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14 };
+enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q2_K = 10, BAMD_TYPE_Q3_K = 11, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14, BAMD_TYPE_BF16 = 30 };
 
 const char * bamd_last_error(void);
 
@@ -233,6 +233,9 @@ int bamd_op_quantize_q8_K(const float * x, int64_t k, const float * norm_w, floa
 int bamd_op_quantize_q8_0(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks);
 /* and of Q4_1 / Q5_1 weights: k / 32 block_q8_1 {f16 d, f16 s, i8 qs[32]}, 36 bytes each (quantize_row_q8_1) */
 int bamd_op_quantize_q8_1(const float * x, int64_t k, const float * norm_w, float eps, void * out_blocks);
+/* and of BF16 weights: k bf16 values, ggml_fp32_to_bf16_row of the (normed) vector.  F32 and F16 weights take the f32 vector as it is: the ops below accept the
+   types 0 (F32), 1 (F16) and 30 (BF16) with w_raw row-major as in the GGUF file */
+int bamd_op_act_bf16(const float * x, int64_t k, const float * norm_w, float eps, uint16_t * out_u16);
 /* y[nrows] = W . Q8_K(act) (+ residual), W = GGUF-layout blocks [nrows][k] of `type`  (ggml_compute_forward_mul_mat, ggml.c:12277) */
 int bamd_op_mul_mat_vec(int type, const void * w_raw, int nrows, int k, const float * x, const float * norm_w, float eps,
                         const float * residual, float * y, int mode /* 0 auto, 1 wave-per-row-group, 2 split-K */);

@@ -1,0 +1,68 @@
+"""Greedy decode rate and prompt rate of the synthetic Llama-3-8B file as an unquantised GGUF — F16, BF16 and F32 — beside the Q8_0 file, in one job on one card.
+GPU box only.  Decode: per file a 128-token prompt, then generate_greedy of 128 steps, five repetitions after a warm-up.  Prompt: N tokens in micro-batches of
+512, five repetitions after a warm-up (the float family's VALU kernel; Q8_0 on the integer-dot kernel).  Beside every decode median: the bytes streamed per
+token (every matrix once) and the share of the 8 TB/s token roofline the rate amounts to.
+
+The F16 and BF16 files have the full shape (V 128256).  The F32 file has V 32000: an F32 lm_head of 128256 x 4096 is 2.1 GB, beyond the 2 GiB cap of a stream
+copy, and is refused at load.  Each float file is 16 - 30 GB: it is written, measured and removed again before the next one (--keep: left in place).
+
+    python tools/float_decode.py [--prompt 2048] [--types f16,bf16,f32] [--keep]
+"""
+import importlib.util
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import booster_amd as b  # noqa: E402
+from booster_amd import gguf  # noqa: E402
+from lowbit_decode import decode_rate, prompt_rate  # noqa: E402
+
+_spec = importlib.util.spec_from_file_location("gen_legacy_fixtures", os.path.join(ROOT, "tests", "golden", "gen_legacy_fixtures.py"))
+legacy = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(legacy)
+
+L3_8B = dict(E=4096, H=32, Hkv=8, L=32, F=14336, V=128256, theta=500000.0)
+SHAPES = {"f16": (L3_8B, gguf.f16_type, gguf.F16), "bf16": (L3_8B, gguf.bf16_type, gguf.BF16), "f32": (dict(L3_8B, V=32000), gguf.f32_type, gguf.F32)}
+HBM_BYTES_PER_S = 8.0e12
+
+
+def float_file(name, d="/dev/shm"):
+    kw, rf, embd = SHAPES[name]
+    p = os.path.join(d, "bamd_float_8b_%s.gguf" % name)
+    if not os.path.exists(p + ".done"):
+        gguf.write_synthetic_llama(p, seed=7, reuse_layers=True, type_fn=lambda n, il: rf(n, il, kw["L"]), embd_type=embd, **kw)
+        open(p + ".done", "w").write("ok")
+    return p
+
+
+def measure(name, p, n_prompt):
+    wb = sum(int(t["data"].size) for n, t in gguf.GGUFReader(p).tensors.items() if len(t["shape"]) == 2 and n != "token_embd.weight")      # what Model.weight_bytes counts
+    r = decode_rate(p)
+    med = statistics.median(r)
+    print("decode %-5s %6.2f GB file, %6.2f GB of matrices per token: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt) = %4.1f %% of the 8 TB/s token roofline (%.1f tok/s)"
+          % (name, os.path.getsize(p) / 1e9, wb / 1e9, med, min(r), max(r), 100.0 * med * wb / HBM_BYTES_PER_S, HBM_BYTES_PER_S / wb), flush=True)
+    if n_prompt:
+        r, aux = prompt_rate(p, n_prompt, reps=5)
+        print("prompt %-5s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n_prompt, statistics.median(r), min(r), max(r),
+              "VALU kernel" if name != "Q8_0" else "integer-dot kernel"), flush=True)
+
+
+def main():
+    n_prompt = int(sys.argv[sys.argv.index("--prompt") + 1]) if "--prompt" in sys.argv else 0
+    types = sys.argv[sys.argv.index("--types") + 1].split(",") if "--types" in sys.argv else ["f16", "bf16", "f32"]
+    measure("Q8_0", legacy.ensure_model("8b_q8_0"), n_prompt)
+    for name in types:
+        had = os.path.exists(os.path.join("/dev/shm", "bamd_float_8b_%s.gguf.done" % name))
+        p = float_file(name)
+        try:
+            measure(name.upper(), p, n_prompt)
+        finally:
+            if not had and "--keep" not in sys.argv:
+                os.remove(p); os.remove(p + ".done")
+
+
+if __name__ == "__main__":
+    main()
