@@ -122,6 +122,7 @@ int  bamd_launch_matmul_batch_b32(const bamd_mm_args & a, int epi, int n_cu, hip
 // K-quant matrices on the matrix cores, exact (bamd_prefill2.hip): y[t][row] = W[row,:] . Q8_K(a_t); epi BAMD_EPI_STORE: out = y; BAMD_EPI_ADD: out = y + res;
 // BAMD_EPI_SILU_MUL: out = silu(res) * y (res = the gate projection, may alias out).  The A fragments are built once per 64-row x 64-token workgroup from the
 // wave-stream copy and the matrix's load-time side table (aux: bamd_prefill_aux_bytes bytes, filled by bamd_launch_prefill_aux).  1 = type / shape not supported or no table
+// (Q4_K / Q5_K: the sixteen-wave matmul_mfma3_q4k_kernel; Q6_K / Q3_K / Q2_K: the eight-wave matmul_mfma2_kernel, one body with a policy struct per format)
 int  bamd_prefill_mfma_supported(void);      // the current device accepts the kernels' LDS size (asked at model load)
 // "this weight type has a matrix-core prompt mat-mul now": the ONE list — side-table sizes, the launcher, the engine's routing and its load-time message all ask here.
 // Q3_K / Q2_K are behind the process-wide switch bamd_prefill_lowbit() (BAMD_PREFILL_LOWBIT=1 / bamd_set_prefill_lowbit; default off): a model builds their

@@ -16,13 +16,15 @@
 //     super-block for Q4_K / Q5_K, 72 B for Q6_K: the MI355X has the HBM for it): the builders' per-(row, sub-block pair) scale operands
 //     {s, -1024 s, s'/16, -64 s'} as packed f16 pairs, and the consumers' d, dmin as f32 plus the min-term MFMA operands {2 m_a, 2 m_b, m_a, m_b}, which
 //     travel global -> LDS by DMA with the activation records;
-//   * two layouts: sixteen waves with one 16 x 16 tile each (matmul_mfma3_q4k_kernel: Q4_K / Q5_K), eight waves with 16 x 32 each (matmul_mfma2_q6k_kernel: Q6_K;
-//     matmul_mfma2_lowbit_kernel: Q3_K / Q2_K, behind the switch BAMD_PREFILL_LOWBIT / bamd_set_prefill_lowbit, default off).
+//   * two layouts: sixteen waves with one 16 x 16 tile each (matmul_mfma3_q4k_kernel: Q4_K / Q5_K), eight waves with 16 x 32 each (matmul_mfma2_kernel: ONE body,
+//     a policy struct per format — X2Q6K: Q6_K; X2LowBit<Q2>: Q3_K / Q2_K, behind the switch BAMD_PREFILL_LOWBIT / bamd_set_prefill_lowbit, default off).
+//     Both layouts close with the same hsum tree (x_hsum8) and the same row-of-four store, which each kernel writes out itself (note at the eight-wave policies).
 //     (Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1: a kernel of another shape, bamd_prefill2_b32.hip, reached through the launchers at the end of this file.)
 // Same bits as the round-2 kernels (removed in round 6), a third fewer vector instructions per MFMA — and the same time: DESIGN 4c has the measurements of what
 // bounds it, profiles/r06_prefill_ceiling.txt the timing-only ceiling builds (-DBAMD_PREFILL_CEILING).
 #include "bamd_device.h"
 #include "bamd_mfma_common.h"
+#include "bamd_mv_select.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -114,11 +116,15 @@ __global__ void __launch_bounds__(64) prefill_aux_q6k_kernel(const uint8_t * __r
 // wave-instruction k = 64 consecutive chunks; round r: instruction 8 r + wave.  Rounds 0..3 (and round 4 for waves 0..5) are records; round
 // 4 of waves 6, 7 and the tail instructions are headers (NCH = 160 for Q4_K / Q5_K: a half instruction on wave 0; 16 for Q6_K: lanes 0..15 of
 // wave 6); the 64 block scales d_y go as one 4-byte instruction on wave 1.
+// byte offset into blob16 of record chunk idx of a token tile (token idx / 38 of the tile at t0, its chunk idx % 38); tokens past T read the last one
+__device__ inline uint32_t x_rec_off(int idx, int t0, int T, size_t b16) {
+    const int tok = idx / BAMD_B16_Q, q = idx - tok * BAMD_B16_Q; const int tg = t0 + tok < T ? t0 + tok : T - 1; return (uint32_t) ((size_t) tg * b16 + (size_t) q * 16);
+}
 template <int NCH>
 struct XStage {
     uint32_t off[5]; uint32_t offx; bool x_on;
     __device__ __forceinline__ void plan(int tid, int wave, int lane, int t0, int T, size_t b16, int nb) {
-        auto rec_off = [&](int idx) { const int tok = idx / BAMD_B16_Q, q = idx - tok * BAMD_B16_Q; const int tg = t0 + tok < T ? t0 + tok : T - 1; return (uint32_t) ((size_t) tg * b16 + (size_t) q * 16); };
+        auto rec_off = [&](int idx) { return x_rec_off(idx, t0, T, b16); };
 #pragma unroll
         for (int r = 0; r < 4; ++r) off[r] = rec_off(r * 512 + tid);
         off[4] = wave < 6 ? rec_off(2048 + tid) : (uint32_t) (tid - 384) * 16u;
@@ -137,55 +143,57 @@ struct XStage {
     }
 };
 
+// ---- the reference's hsum_float_8 tree over the eight per-e accumulators of an output (component i of a 16 x 16 tile's lane), for both layouts
+__device__ __forceinline__ float x_hsum8(const bamd_f4 (&acc)[8], int i) {
+    return ((acc[0][i] + acc[4][i]) + (acc[2][i] + acc[6][i])) + ((acc[1][i] + acc[5][i]) + (acc[3][i] + acc[7][i]));
+}
+
 // ---- Q4_K / Q5_K: the sixteen-wave kernel further down (matmul_mfma3_q4k_kernel).  MFMA lane l = (m = l & 15, g = l >> 4): A row m, B token m, k-slots (g, i) =
 //      (sub-block 2g + (i >> 2), u = i & 3); C/D rows 4g + i, token m.  (An eight-wave layout of the same arithmetic — 16 x 32 per wave, 96 accumulators, two waves
 //      per SIMD — lived here in round 5: 27.4 vs 25.4 ms per 512-token micro-batch; removed in round 6, profiles/r06_prefill_ceiling.txt.)
 
-// ---- Q6_K: a step is HALF a super-block (four e: 16 MFMAs per wave, two per e and token tile) -----------------------------------------------
+// ==== eight waves: ONE kernel body (matmul_mfma2_kernel, behind the policies) and a policy struct F per format ===============================================
+// What the body asks of F: the sizes RECB (record), CHRT (consumer header of a row tile), PH_SB (builder operands of a row block and super-block: two half steps x
+// 4 row tiles x 64 MFMA lanes), NFRAG (fragments = MFMAs per (e, token tile)), LATE_CHAIN (the chain FMAs of e behind the MFMAs of e + 1 instead of behind its own),
+// Hdr (the consumer header values of a half step and the min term: X2Hdr, behind the policies), lane_ptrs (the builder lane's two pointers into its record group),
+// and the registers of two weight sets with load_set<S>(hs, the two pointers, the lane's builder operands, bp), build_a(S, j), build_b(S, j, dst).
+// Three things in this cut are there because the Q3_K / Q2_K and the sixteen-wave instances then compile to the code objects they had as separate kernels
+// (profiles/prefill2_unify.txt): the lane's pointers are three locals of the body, not members of F (as members of one struct the prologue's address arithmetic
+// is scheduled differently); D is a local of the step that Hdr fills; and the row-of-four store stands in each kernel, not in a shared function (inlined from
+// one, the loop's phi nodes and with them the register assignment change).
+template <bool MINS> struct X2Hdr;
+
+// ---- Q6_K: 16 MFMAs per wave and half step, two per e and token tile -------------------------------------------------------------------------
 // scale x (q - 32) reaches 4096: the scale is split sc = sa + sl (prefill_aux_q6k_kernel), both fragments come from one f16 image v = (1024 + q) - 1056
 // of the quants as v x sa and v x sl (exact), and the two MFMAs of an (e, token tile) are CHAINED through the accumulator: S = A_l.B + (A_a.B + 0)
 // is the exact integer isum (|isum| < 2^24, every partial sum an integer below that bound) — the fmaf(16, S_1, S_2) of bamd_prefill.hip is gone.
 // Scales are per 16 elements: for SIMD lane e the sub-block c uses scales[2c + (e >= 4)] (ggml-quants.c:8145-8216), i.e. the builder operands of a
 // half step are those of e-half h.  Fragment ring: two half steps x 4 row tiles x 4 e x 2 fragments x 1 KiB = 2 x 32 KiB; the activation stage
 // (whole super-blocks) is refilled every second half step.
-template <int EPI>
-__global__ void __launch_bounds__(512) matmul_mfma2_q6k_kernel(bamd_mma2_args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), m = lane & 15, g = lane >> 4;
-    const int rt = wave >> 1, tp = wave & 1;
-    const int nb = a.K >> 8;
-    const int rb = blockIdx.y, t0 = blockIdx.x * 64;
-    const int rtg = rb * 4 + rt;
-    const bool live = rtg * 16 < a.nrows_pad;
-    const size_t b16 = BAMD_BLOB16_BYTES(nb);
-    const uint32_t lds0 = (uint32_t) (size_t) (bamd_lds_vp) smem;
-    XStage<16> stg; stg.plan(tid, wave, lane, t0, a.T, b16, nb);
-    const uint8_t * chb = a.ch + (size_t) rb * nb * (4 * X_CH6_RT);
-#define X_STAGE(ci_, b_) stg.issue(a.blob16 + (size_t) (ci_) * BAMD_B16_REC, chb + (size_t) (ci_) * (4 * X_CH6_RT), a.blob16 + (size_t) (ci_) * 4, lds0 + X_BLK0 + (uint32_t) (b_) * X_BLK, wave, lane)
-    // builder (as in the Q4_K kernel: the stream's own rows, one record group per wave): wave (rt, q = tp), lane (p = lane >> 5, r = (lane >> 2) & 7, el = lane & 3)
-    // takes, per half step, chunk e = 4 H + el of row 8q + r and builds the pieces of MFMA lanes (8q + r, g = 2p + j), j = 0, 1: the ql dwords 2p, 2p + 1
-    // (sub-blocks 2g / 2g+1 sit in the low (j = 0) or high (j = 1) nibbles) and the qh dword p of stream lane (r, e).  Eight consecutive lanes = two rows x
-    // four fragments: their 16-byte stores fall on eight different bank quads (fragment pairs 2 x X_FR bytes apart).
-    const int bp = lane >> 5, br = (lane >> 2) & 7, bel = lane & 3;
-    const int rgq = 2 * (live ? rtg : rb * 4) + tp;
-    const int rgc = rgq * 8 < a.nrows_pad ? rgq : rgq - 1;
-    const uint8_t * wql = a.w + (size_t) rgc * nb * 1680 + (size_t) ((br * 8 + bel) * 16 + bp * 8);
-    const uint8_t * wqh = a.w + (size_t) rgc * nb * 1680 + 1024 + (size_t) ((br * 8 + bel) * 8 + bp * 4);
-    const uint8_t * phb = a.ph + (size_t) rb * nb * 8192 + (size_t) rt * 1024 + (size_t) ((2 * bp) * 256 + (8 * tp + br) * 16);
+struct X2Q6K {
+    static constexpr uint32_t RECB = BAMD_RECB_Q6K;
+    static constexpr int CHRT = X_CH6_RT, PH_SB = 8192, NFRAG = 2;
+    static constexpr bool LATE_CHAIN = false;
+    typedef X2Hdr<false> Hdr;
+    // where a builder lane (p, r, el) finds its weight sets: per half step the ql dwords 2p, 2p + 1 (sub-blocks 2g / 2g+1 sit in the low (j = 0) or high (j = 1) nibbles)
+    // and the qh dword p of stream lane (r, e); rec0: byte offset of the record group's first record in the stream w, ph: the lane's builder operands of half step 0
+    static __device__ __forceinline__ void lane_ptrs(const uint8_t * w, size_t rec0, int bp, int br, int bel, const uint8_t * & wql, const uint8_t * & wqh) {
+        wql = w + rec0 + (size_t) ((br * 8 + bel) * 16 + bp * 8);
+        wqh = w + rec0 + 1024 + (size_t) ((br * 8 + bel) * 8 + bp * 4);
+    }
     uint2 ql[2]; uint32_t qh[2]; uint4 sc[2][2];
-    auto load_set = [&](int hs, auto set_tag) {                // operands of half step hs = 2 ci + h
-        constexpr int S = decltype(set_tag)::value;
-        const int ci = hs >> 1, h = hs & 1;
-        ql[S] = *(const uint2 *) (wql + (size_t) ci * 1680 + h * 64);
-        qh[S] = *(const uint32_t *) (wqh + (size_t) ci * 1680 + h * 32);
-        sc[S][0] = *(const uint4 *) (phb + (size_t) hs * 4096); sc[S][1] = *(const uint4 *) (phb + (size_t) hs * 4096 + 256);
-    };
-    const bamd_h2 k1056 = { (_Float16) -1056.f, (_Float16) -1056.f };
     bamd_h2u v0, v1, v2, v3;
-    auto build_a = [&](const uint2 & q, uint32_t hq, int j) {
+    template <int S> __device__ __forceinline__ void load_set(int hs, const uint8_t * wql, const uint8_t * wqh, const uint8_t * phb, int) {     // operands of half step hs = 2 ci + h
+        const int ci = hs >> 1, h = hs & 1;
+        ql[S] = *(const uint2 *) (wql + (size_t) ci * RECB + h * 64);
+        qh[S] = *(const uint32_t *) (wqh + (size_t) ci * RECB + h * 32);
+        sc[S][0] = *(const uint4 *) (phb + (size_t) hs * (PH_SB / 2)); sc[S][1] = *(const uint4 *) (phb + (size_t) hs * (PH_SB / 2) + 256);
+    }
+    __device__ __forceinline__ void build_a(int S, int j) {
         // the two high bits of a quant sit at bits sh, sh + 1 (sub-block 2g) / sh + 2, sh + 3 (2g + 1) of their byte of hq (sh = 4 j) and belong at bits 4, 5:
         // a ROTATION of the dword (what wraps around lands outside the mask 0x30 of every byte), then one and-or
-        const uint32_t sh = 4u * (uint32_t) j;
+        const bamd_h2 k1056 = { (_Float16) -1056.f, (_Float16) -1056.f };
+        const uint2 q = ql[S]; const uint32_t hq = qh[S], sh = 4u * (uint32_t) j;
         const uint32_t uA = (__builtin_amdgcn_alignbit(hq, hq, (28u + sh) & 31u) & 0x30303030u) | ((q.x >> sh) & 0x0f0f0f0fu);
         const uint32_t uB = (__builtin_amdgcn_alignbit(hq, hq, (30u + sh) & 31u) & 0x30303030u) | ((q.y >> sh) & 0x0f0f0f0fu);
         bamd_h2u c;
@@ -193,108 +201,26 @@ __global__ void __launch_bounds__(512) matmul_mfma2_q6k_kernel(bamd_mma2_args a)
         c.u = __builtin_amdgcn_perm(0x64646464u, uA, 0x04030402u); v1.h = c.h + k1056;
         c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04010400u); v2.h = c.h + k1056;
         c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04030402u); v3.h = c.h + k1056;
-    };
-    auto build_b = [&](const uint4 & s, unsigned char * dst) {  // dst: the A_a fragment; A_l X_FR bytes behind it
+    }
+    __device__ __forceinline__ void build_b(int S, int j, unsigned char * dst) const {  // dst: the A_a fragment; A_l X_FR bytes behind it
+        const uint4 s = sc[S][j];
         bamd_h2u sa0, sl0, sa1, sl1, x0, x1, x2, x3; sa0.u = s.x; sl0.u = s.y; sa1.u = s.z; sl1.u = s.w;
         x0.h = v0.h * sa0.h; x1.h = v1.h * sa0.h; x2.h = v2.h * sa1.h; x3.h = v3.h * sa1.h;
         *(uint4 *) dst = (uint4) { x0.u, x1.u, x2.u, x3.u };
         x0.h = v0.h * sl0.h; x1.h = v1.h * sl0.h; x2.h = v2.h * sl1.h; x3.h = v3.h * sl1.h;
         *(uint4 *) (dst + X_FR) = (uint4) { x0.u, x1.u, x2.u, x3.u };
-    };
-    unsigned char * afw = smem + X_AF0 + (rt * 4 + bel) * (2 * X_FR) + ((2 * bp) * 16 + 8 * tp + br) * 16;     // [row tile][e' = 0..3][a | l][X_FR]: MFMA lane (8 tp + br, 2 bp + j) at + j * 256
-    const unsigned char * afr = smem + X_AF0 + rt * 8 * X_FR + lane * 16;
-    const unsigned char * bop = smem + X_BLK0 + (size_t) ((2 * tp) * 16 + m) * BAMD_B16_REC + g * 16;
-    const unsigned char * chd = smem + X_BLK0 + X_CH_OFF + rt * X_CH6_RT + g * 16;                 // d of rows 4g .. 4g+3
-    const unsigned char * ydp = smem + X_BLK0 + X_YD_OFF + ((2 * tp) * 16 + m) * 4;
-    bamd_f4 acc[2][8];
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[n][e] = (bamd_f4) { 0.f, 0.f, 0.f, 0.f };
     }
-    X_STAGE(0, 0);
-    load_set(0, std::integral_constant<int, 0>());
-    load_set(1, std::integral_constant<int, 1>());
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { build_a(ql[0], qh[0], j); build_b(sc[0][j], afw + j * 256); }
-    lds_dma_wait();
-    __syncthreads();
-    const int nhs = 2 * nb;
-    // half step hs = 2 ci + H: fragments in ring slot H, activation block ci & 1 = BLK
-    auto step = [&](const int hs, auto h_tag, auto blk_tag) {
-        constexpr int H = decltype(h_tag)::value, BLK = decltype(blk_tag)::value, NXT = H ^ 1;
-        const int ci = hs >> 1;
-        if (H == 0) X_STAGE(ci + 1 < nb ? ci + 1 : nb - 1, BLK ^ 1);                               // the next super-block's records: a whole step ahead
-        load_set(hs + 2 < nhs ? hs + 2 : nhs - 2 + H, std::integral_constant<int, H>());
-        __builtin_amdgcn_sched_barrier(0);
-        float D[2][4];
-        {
-            const bamd_f4 dw = *(const bamd_f4 *) (chd + BLK * X_BLK);
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const float ydv = *(const float *) (ydp + BLK * X_BLK + n * 64);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) D[n][i] = ydv * dw[i];
-            }
-        }
-        bamd_h8 Aa[2], Al[2], Bq[2][2];
-#define X_LDA(e_, p_) (*(const bamd_h8 *) (afr + H * X_AF_BYTES + (e_) * (2 * X_FR) + (p_) * X_FR))
-#define X_LDB(e_, n_) (*(const bamd_h8 *) (bop + BLK * X_BLK + (n_) * (16 * BAMD_B16_REC) + (4 * H + (e_)) * 64))
-        Aa[0] = X_LDA(0, 0); Al[0] = X_LDA(0, 1); Bq[0][0] = X_LDB(0, 0); Bq[0][1] = X_LDB(0, 1);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (e + 1 < 4) { Aa[(e + 1) & 1] = X_LDA(e + 1, 0); Al[(e + 1) & 1] = X_LDA(e + 1, 1); Bq[(e + 1) & 1][0] = X_LDB(e + 1, 0); Bq[(e + 1) & 1][1] = X_LDB(e + 1, 1); }
-            if ((e & 1) == 0) build_a(ql[NXT], qh[NXT], e >> 1);
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const bamd_f4 z = { 0.f, 0.f, 0.f, 0.f };
-                const bamd_f4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aa[e & 1], Bq[e & 1][n], z, 0, 0, 0);
-                const bamd_f4 s2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[e & 1], Bq[e & 1][n], s1, 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[n][4 * H + e][i] = fmaf(D[n][i], s2[i], acc[n][4 * H + e][i]);
-            }
-            if (e & 1) build_b(sc[NXT][e >> 1], afw + NXT * X_AF_BYTES + (e >> 1) * 256);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#undef X_LDA
-#undef X_LDB
-        if (H == 1) lds_dma_wait();
-        __syncthreads();
-    };
-    for (int ci = 0; ci < nb; ci += 2) {
-        step(2 * ci, std::integral_constant<int, 0>(), std::integral_constant<int, 0>());
-        step(2 * ci + 1, std::integral_constant<int, 1>(), std::integral_constant<int, 0>());
-        if (ci + 1 < nb) {
-            step(2 * ci + 2, std::integral_constant<int, 0>(), std::integral_constant<int, 1>());
-            step(2 * ci + 3, std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
-        }
-    }
-#undef X_STAGE
-    if (!live) return;
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const int t = t0 + (2 * tp + n) * 16 + m;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float val = ((acc[n][0][i] + acc[n][4][i]) + (acc[n][2][i] + acc[n][6][i])) + ((acc[n][1][i] + acc[n][5][i]) + (acc[n][3][i] + acc[n][7][i]));
-            const int row = rtg * 16 + 4 * g + i;
-            if (t < a.T && row < a.nrows) {
-                const size_t o = (size_t) t * a.ldo + row;
-                a.out[o] = EPI == BAMD_EPI_ADD ? val + a.res[o] : EPI == BAMD_EPI_SILU_MUL ? v_silu(a.res[o]) * val : val;
-            }
-        }
-    }
-}
+};
 
-// ---- Q3_K / Q2_K: the Q6_K kernel's half steps with ONE fragment and ONE MFMA per (e, token tile) -------------------------------------------
+// ---- Q3_K / Q2_K: ONE fragment and ONE MFMA per (e, token tile) ---------------------------------------------------------------------------------
 // Reference: ggml_vec_dot_q3_K_q8_K / ggml_vec_dot_q2_K_q8_K (ggml-quants.c:6161-6263, :5553-5617).  SIMD lane e owns bytes 4e..4e+3 of the eight chunks c,
 // its scale is that of the 16-element sub-block 2c + (e >= 4): e-half h and chunk pairs (2g, 2g+1) per MFMA lane group g, as for Q6_K.  (sc - 32) x q with
 // q = low2 + 4 hbit - 4 (Q3_K, |.| <= 128) and sc x q (Q2_K, <= 45) are exact f16, so one v_mfma_f32_16x16x32_f16 gives the exact isum_e (|isum_e| <= 2^19,
 // every partial sum an integer): no split scale, no chained second MFMA.  Wave-stream lane (r, e) holds two qs dwords j (fields k = 0..3 = chunk 4j + k) and,
 // Q3_K, the hmask dword (bit c of byte u = element 32c + 4e + u): the pieces of MFMA lanes (row, g = 2p + j') come from qs dword p, fields 2j', 2j'+1, and
-// hmask bits 2g, 2g+1.  Fragment ring: the Q6_K kernel's slots with the second fragment of every pair unused (the 2 x X_FR pitch keeps the builders' stores
+// hmask bits 2g, 2g+1.  Fragment ring: the second fragment slot of every pair unused (the 2 x X_FR pitch keeps the builders' stores
 // of eight lanes on eight bank quads).
-// Q2_K's min term goes into the same accumulator in front of the dot term (chain_step): prod_e = mins[2e] bsum16[2e] + mins[2e+1] bsum16[2e+1] is one
+// Q2_K's min term goes into the same accumulator in front of the dot term (chain_step; X2Hdr::chain): prod_e = mins[2e] bsum16[2e] + mins[2e+1] bsum16[2e+1] is one
 // v_dot2_f32_f16 per row and token on packed pairs — the mins of a row as sixteen f16 in the consumer header, the sums of sixteen activations as sixteen f16 at
 // bytes 576..607 of the token record (quantize_batch_kernel); |prod_e| <= 61 440, exact in f32 in any order.
 #define XL_CH2_RT 640                                      /* Q2_K consumer header of a row tile: 16 x d f32 | 16 x dmin f32 | 16 rows x 16 f16 mins */
@@ -339,10 +265,84 @@ __global__ void __launch_bounds__(64) prefill_aux_lowbit_kernel(const uint8_t * 
     } else if (g == 0) *(float *) (ch + sb * (4 * XL_CH3_RT) + (rtile & 3) * XL_CH3_RT + m * 4) = h2f(d16);
 }
 
-template <int EPI, bool Q2>
-__global__ void __launch_bounds__(512) matmul_mfma2_lowbit_kernel(bamd_mma2_args a) {
-    constexpr uint32_t RECB = Q2 ? BAMD_RECB_Q2K : BAMD_RECB_Q3K;
-    constexpr int CHRT = Q2 ? XL_CH2_RT : XL_CH3_RT;
+template <bool Q2>
+struct X2LowBit {
+    static constexpr uint32_t RECB = Q2 ? BAMD_RECB_Q2K : BAMD_RECB_Q3K;
+    static constexpr int CHRT = Q2 ? XL_CH2_RT : XL_CH3_RT, PH_SB = XL_PH_SB, NFRAG = 1;
+    static constexpr bool LATE_CHAIN = true;                   // one iteration behind: no MFMA -> VALU wait states in front of the chain
+    typedef X2Hdr<Q2> Hdr;
+    // where a builder lane (p, r, el) finds its weight sets: per half step qs dword p and the hmask dword of stream lane (r, e)
+    static __device__ __forceinline__ void lane_ptrs(const uint8_t * w, size_t rec0, int bp, int br, int bel, const uint8_t * & wqs, const uint8_t * & whm) {
+        wqs = w + rec0 + (size_t) ((br * 8 + bel) * 8 + bp * 4);
+        whm = w + rec0 + 512 + (size_t) ((br * 8 + bel) * 4);
+    }
+    uint32_t hm[2], qs[2]; uint2 sc[2][2];                     // (hm in front of qs: the order of the ring loop's phi nodes, and with it the register assignment, follows the members)
+    bamd_h2u v0, v1, v2, v3;
+    template <int S> __device__ __forceinline__ void load_set(int hs, const uint8_t * wqs, const uint8_t * whm, const uint8_t * phb, int bp) {  // operands of half step hs = 2 ci + h
+        const int ci = hs >> 1, h = hs & 1;
+        qs[S] = *(const uint32_t *) (wqs + (size_t) ci * RECB + h * 32);
+        if (!Q2) hm[S] = *(const uint32_t *) (whm + (size_t) ci * RECB + h * 16) >> (4 * bp);      // bits 2g, 2g+1 of every byte at bits 2j, 2j+1
+        sc[S][0] = *(const uint2 *) (phb + (size_t) hs * (PH_SB / 2)); sc[S][1] = *(const uint2 *) (phb + (size_t) hs * (PH_SB / 2) + 128);
+    }
+    __device__ __forceinline__ void build_a(int S, int j) {
+        const _Float16 kz = Q2 ? (_Float16) -1024.f : (_Float16) -1028.f;
+        const bamd_h2 kzero = { kz, kz };
+        const uint32_t q = qs[S], hq = Q2 ? 0u : hm[S];
+        uint32_t uA = (q >> (4 * j)) & 0x03030303u, uB = (q >> (4 * j + 2)) & 0x03030303u;
+        if (!Q2) { uA |= ((hq >> (2 * j)) & 0x01010101u) << 2; uB |= ((hq >> (2 * j + 1)) & 0x01010101u) << 2; }
+        bamd_h2u c;
+        c.u = __builtin_amdgcn_perm(0x64646464u, uA, 0x04010400u); v0.h = c.h + kzero;      // Q3_K: (1024 + low2 + 4 hbit) - 1028 = q; Q2_K: (1024 + q) - 1024, exact
+        c.u = __builtin_amdgcn_perm(0x64646464u, uA, 0x04030402u); v1.h = c.h + kzero;
+        c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04010400u); v2.h = c.h + kzero;
+        c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04030402u); v3.h = c.h + kzero;
+    }
+    __device__ __forceinline__ void build_b(int S, int j, unsigned char * dst) const {
+        const uint2 s = sc[S][j];
+        bamd_h2u s0, s1, x0, x1, x2, x3; s0.u = s.x; s1.u = s.y;
+        x0.h = v0.h * s0.h; x1.h = v1.h * s0.h; x2.h = v2.h * s1.h; x3.h = v3.h * s1.h;
+        *(uint4 *) dst = (uint4) { x0.u, x1.u, x2.u, x3.u };
+    }
+};
+// the consumer side's header values of a half step: D = d_y d of the lane's rows 4g + i and two tokens n; MINS (Q2_K): Dm = -d_y dmin, {mins[2e], mins[2e+1]} of the
+// rows and {bsum16[2e], bsum16[2e+1]} of the tokens, e = 4 H + 0..3.  chain() is one link of acc_e: the min term first, into the same accumulator
+template <bool MINS>
+struct X2Hdr {
+    const unsigned char * tok, * chd, * chm, * ydp;
+    float Dm[2][4]; bamd_h2u mn[4][4], bs[2][4];
+    // tok_: the lane's token record of tile n = 0 (token tl of the block) in LDS block 0 (blk), rto: byte offset of the row tile's consumer header (16 x d | 16 x dmin | 16 rows x 16 mins)
+    __device__ __forceinline__ void init(const unsigned char * tok_, const unsigned char * blk, int rto, int tl, int g) {
+        tok = tok_;
+        chd = blk + X_CH_OFF + rto + g * 16;                   // d of rows 4g .. 4g+3 (MINS: their dmin 64 bytes on)
+        chm = blk + X_CH_OFF + rto + 128 + g * 128;            // MINS: the mins of rows 4g .. 4g+3, 32 bytes each
+        ydp = blk + X_YD_OFF + tl * 4;
+    }
+    __device__ __forceinline__ void read(int BLK, int H, float (&D)[2][4]) {
+        const bamd_f4 dw = *(const bamd_f4 *) (chd + BLK * X_BLK);
+        bamd_f4 dmw = { 0.f, 0.f, 0.f, 0.f };
+        if (MINS) dmw = *(const bamd_f4 *) (chd + BLK * X_BLK + 64);
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const float ydv = *(const float *) (ydp + BLK * X_BLK + n * 64);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { D[n][i] = ydv * dw[i]; if (MINS) Dm[n][i] = (-ydv) * dmw[i]; }
+            if (MINS) { const uint4 b = *(const uint4 *) (tok + BLK * X_BLK + n * (16 * BAMD_B16_REC) + 576 + 16 * H); bs[n][0].u = b.x; bs[n][1].u = b.y; bs[n][2].u = b.z; bs[n][3].u = b.w; }
+        }
+        if (MINS) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const uint4 v = *(const uint4 *) (chm + BLK * X_BLK + i * 32 + 16 * H); mn[i][0].u = v.x; mn[i][1].u = v.y; mn[i][2].u = v.z; mn[i][3].u = v.w; }
+        }
+    }
+    __device__ __forceinline__ float mins(float av, int n, int e, int i) const {
+        if (MINS) av = fmaf(Dm[n][i], __builtin_amdgcn_fdot2(mn[i][e].h, bs[n][e].h, 0.f, false), av);
+        return av;
+    }
+};
+
+// ---- the eight-wave body: a workgroup of 64 rows x 64 tokens, wave (rt, tp) = row tile rt x token tiles 2 tp, 2 tp + 1.  A step is HALF a super-block (four e);
+//      the fragment ring holds two half steps x 4 row tiles x 4 e x 2 fragment slots (the second one unused where NFRAG = 1), the activation stage (whole
+//      super-blocks) is refilled every second half step
+template <int EPI, class F>
+__global__ void __launch_bounds__(512) matmul_mfma2_kernel(bamd_mma2_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), m = lane & 15, g = lane >> 4;
     const int rt = wave >> 1, tp = wave & 1;
@@ -352,60 +352,35 @@ __global__ void __launch_bounds__(512) matmul_mfma2_lowbit_kernel(bamd_mma2_args
     const bool live = rtg * 16 < a.nrows_pad;
     const size_t b16 = BAMD_BLOB16_BYTES(nb);
     const uint32_t lds0 = (uint32_t) (size_t) (bamd_lds_vp) smem;
-    XStage<4 * CHRT / 16> stg; stg.plan(tid, wave, lane, t0, a.T, b16, nb);
-    const uint8_t * chb = a.ch + (size_t) rb * nb * (4 * CHRT);
-#define XL_STAGE(ci_, b_) stg.issue(a.blob16 + (size_t) (ci_) * BAMD_B16_REC, chb + (size_t) (ci_) * (4 * CHRT), a.blob16 + (size_t) (ci_) * 4, lds0 + X_BLK0 + (uint32_t) (b_) * X_BLK, wave, lane)
-    // builder (the Q6_K kernel's lane order): wave (rt, q = tp), lane (p = lane >> 5, r = (lane >> 2) & 7, el = lane & 3) takes, per half step, chunk e = 4 H + el of
-    // row 8q + r and builds the pieces of MFMA lanes (8q + r, g = 2p + j), j = 0, 1, of fragment e from qs dword p and the hmask dword of stream lane (r, e)
+    XStage<4 * F::CHRT / 16> stg; stg.plan(tid, wave, lane, t0, a.T, b16, nb);
+    const uint8_t * chb = a.ch + (size_t) rb * nb * (4 * F::CHRT);
+    auto stage = [&](int ci, int b) { stg.issue(a.blob16 + (size_t) ci * BAMD_B16_REC, chb + (size_t) ci * (4 * F::CHRT), a.blob16 + (size_t) ci * 4, lds0 + X_BLK0 + (uint32_t) b * X_BLK, wave, lane); };
+    // builder (the stream's own rows, one record group per wave): wave (rt, q = tp), lane (p = lane >> 5, r = (lane >> 2) & 7, el = lane & 3) takes, per half step, chunk
+    // e = 4 H + el of row 8q + r and builds the pieces of MFMA lanes (8q + r, g = 2p + j), j = 0, 1, of fragment e.  Eight consecutive lanes = two rows x four
+    // fragments: their 16-byte stores fall on eight different bank quads (fragment pairs 2 x X_FR bytes apart).
     const int bp = lane >> 5, br = (lane >> 2) & 7, bel = lane & 3;
     const int rgq = 2 * (live ? rtg : rb * 4) + tp;
     const int rgc = rgq * 8 < a.nrows_pad ? rgq : rgq - 1;            // a last tile of 8 (padded) rows: its first record group twice (rows 8..15 are never stored)
-    const uint8_t * wqs = a.w + (size_t) rgc * nb * RECB + (size_t) ((br * 8 + bel) * 8 + bp * 4);
-    const uint8_t * whm = a.w + (size_t) rgc * nb * RECB + 512 + (size_t) ((br * 8 + bel) * 4);
-    const uint8_t * phb = a.ph + (size_t) rb * nb * XL_PH_SB + (size_t) rt * 512 + (size_t) (((2 * bp) * 16 + 8 * tp + br) * 8);
-    uint32_t qs[2], hm[2]; uint2 sc[2][2];
-    auto load_set = [&](int hs, auto set_tag) {                // operands of half step hs = 2 ci + h
-        constexpr int S = decltype(set_tag)::value;
-        const int ci = hs >> 1, h = hs & 1;
-        qs[S] = *(const uint32_t *) (wqs + (size_t) ci * RECB + h * 32);
-        if (!Q2) hm[S] = *(const uint32_t *) (whm + (size_t) ci * RECB + h * 16) >> (4 * bp);      // bits 2g, 2g+1 of every byte at bits 2j, 2j+1
-        sc[S][0] = *(const uint2 *) (phb + (size_t) hs * (XL_PH_SB / 2)); sc[S][1] = *(const uint2 *) (phb + (size_t) hs * (XL_PH_SB / 2) + 128);
-    };
-    const _Float16 kz = Q2 ? (_Float16) -1024.f : (_Float16) -1028.f;
-    const bamd_h2 kzero = { kz, kz };
-    bamd_h2u v0, v1, v2, v3;
-    auto build_a = [&](uint32_t q, uint32_t hq, int j) {
-        uint32_t uA = (q >> (4 * j)) & 0x03030303u, uB = (q >> (4 * j + 2)) & 0x03030303u;
-        if (!Q2) { uA |= ((hq >> (2 * j)) & 0x01010101u) << 2; uB |= ((hq >> (2 * j + 1)) & 0x01010101u) << 2; }
-        bamd_h2u c;
-        c.u = __builtin_amdgcn_perm(0x64646464u, uA, 0x04010400u); v0.h = c.h + kzero;      // Q3_K: (1024 + low2 + 4 hbit) - 1028 = q; Q2_K: (1024 + q) - 1024, exact
-        c.u = __builtin_amdgcn_perm(0x64646464u, uA, 0x04030402u); v1.h = c.h + kzero;
-        c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04010400u); v2.h = c.h + kzero;
-        c.u = __builtin_amdgcn_perm(0x64646464u, uB, 0x04030402u); v3.h = c.h + kzero;
-    };
-    auto build_b = [&](const uint2 & s, unsigned char * dst) {
-        bamd_h2u s0, s1, x0, x1, x2, x3; s0.u = s.x; s1.u = s.y;
-        x0.h = v0.h * s0.h; x1.h = v1.h * s0.h; x2.h = v2.h * s1.h; x3.h = v3.h * s1.h;
-        *(uint4 *) dst = (uint4) { x0.u, x1.u, x2.u, x3.u };
-    };
+    const uint8_t * w0, * w1; F::lane_ptrs(a.w, (size_t) rgc * nb * F::RECB, bp, br, bel, w0, w1);
+    // builder operands: [row block][super-block][e-half][4 row tiles (PH_SB / 8 bytes each)][64 MFMA lanes (PH_SB / 512 bytes each)]
+    const uint8_t * phb = a.ph + (size_t) rb * nb * F::PH_SB + (size_t) rt * (F::PH_SB / 8) + (size_t) (((2 * bp) * 16 + 8 * tp + br) * (F::PH_SB / 512));
+    F f;
     unsigned char * afw = smem + X_AF0 + (rt * 4 + bel) * (2 * X_FR) + ((2 * bp) * 16 + 8 * tp + br) * 16;     // [row tile][e' = 0..3][2 x X_FR]: MFMA lane (8 tp + br, 2 bp + j) at + j * 256
     const unsigned char * afr = smem + X_AF0 + rt * 8 * X_FR + lane * 16;
     const unsigned char * tok = smem + X_BLK0 + (size_t) ((2 * tp) * 16 + m) * BAMD_B16_REC;       // this lane's token record of tile n = 0; n = 1: 16 records on
     const unsigned char * bop = tok + g * 16;
-    const unsigned char * chd = smem + X_BLK0 + X_CH_OFF + rt * CHRT + g * 16;                     // d of rows 4g .. 4g+3 (Q2_K: their dmin 64 bytes on)
-    const unsigned char * chm = smem + X_BLK0 + X_CH_OFF + rt * CHRT + 128 + g * 128;              // Q2_K: the mins of rows 4g .. 4g+3, 32 bytes each
-    const unsigned char * ydp = smem + X_BLK0 + X_YD_OFF + ((2 * tp) * 16 + m) * 4;
+    typename F::Hdr hdr; hdr.init(tok, smem + X_BLK0, rt * F::CHRT, (2 * tp) * 16 + m, g);
     bamd_f4 acc[2][8];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[n][e] = (bamd_f4) { 0.f, 0.f, 0.f, 0.f };
     }
-    XL_STAGE(0, 0);
-    load_set(0, std::integral_constant<int, 0>());
-    load_set(1, std::integral_constant<int, 1>());
+    stage(0, 0);
+    f.template load_set<0>(0, w0, w1, phb, bp);
+    f.template load_set<1>(1, w0, w1, phb, bp);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { build_a(qs[0], Q2 ? 0u : hm[0], j); build_b(sc[0][j], afw + j * 256); }
+    for (int j = 0; j < 2; ++j) { f.build_a(0, j); f.build_b(0, j, afw + j * 256); }
     lds_dma_wait();
     __syncthreads();
     const int nhs = 2 * nb;
@@ -413,55 +388,41 @@ __global__ void __launch_bounds__(512) matmul_mfma2_lowbit_kernel(bamd_mma2_args
     auto step = [&](const int hs, auto h_tag, auto blk_tag) {
         constexpr int H = decltype(h_tag)::value, BLK = decltype(blk_tag)::value, NXT = H ^ 1;
         const int ci = hs >> 1;
-        if (H == 0) XL_STAGE(ci + 1 < nb ? ci + 1 : nb - 1, BLK ^ 1);                              // the next super-block's records: a whole step ahead
-        load_set(hs + 2 < nhs ? hs + 2 : nhs - 2 + H, std::integral_constant<int, H>());
+        if (H == 0) stage(ci + 1 < nb ? ci + 1 : nb - 1, BLK ^ 1);                                 // the next super-block's records: a whole step ahead
+        f.template load_set<H>(hs + 2 < nhs ? hs + 2 : nhs - 2 + H, w0, w1, phb, bp);
         __builtin_amdgcn_sched_barrier(0);
-        float D[2][4], Dm[2][4];
-        bamd_h2u mn[4][4], bs[2][4];                                                               // Q2_K: {mins[2e], mins[2e+1]} of rows 4g+i, {bsum16[2e], bsum16[2e+1]} of the two tokens, e = 4 H + 0..3
-        {
-            const bamd_f4 dw = *(const bamd_f4 *) (chd + BLK * X_BLK);
-            bamd_f4 dmw = { 0.f, 0.f, 0.f, 0.f };
-            if (Q2) dmw = *(const bamd_f4 *) (chd + BLK * X_BLK + 64);
+        float D[2][4];
+        hdr.read(BLK, H, D);
+        bamd_h8 Aq[2][F::NFRAG], Bq[2][2]; bamd_f4 sp[2];
+        auto load_ops = [&](int e) {                           // A fragments and B operands of e, double-buffered
 #pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const float ydv = *(const float *) (ydp + BLK * X_BLK + n * 64);
+            for (int p = 0; p < F::NFRAG; ++p) Aq[e & 1][p] = *(const bamd_h8 *) (afr + H * X_AF_BYTES + e * (2 * X_FR) + p * X_FR);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { D[n][i] = ydv * dw[i]; if (Q2) Dm[n][i] = (-ydv) * dmw[i]; }
-                if (Q2) { const uint4 b = *(const uint4 *) (tok + BLK * X_BLK + n * (16 * BAMD_B16_REC) + 576 + 16 * H); bs[n][0].u = b.x; bs[n][1].u = b.y; bs[n][2].u = b.z; bs[n][3].u = b.w; }
-            }
-            if (Q2) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { const uint4 v = *(const uint4 *) (chm + BLK * X_BLK + i * 32 + 16 * H); mn[i][0].u = v.x; mn[i][1].u = v.y; mn[i][2].u = v.z; mn[i][3].u = v.w; }
-            }
-        }
-        bamd_h8 Aq[2], Bq[2][2]; bamd_f4 sp[2];
-#define XL_LDA(e_) (*(const bamd_h8 *) (afr + H * X_AF_BYTES + (e_) * (2 * X_FR)))
-#define XL_LDB(e_, n_) (*(const bamd_h8 *) (bop + BLK * X_BLK + (n_) * (16 * BAMD_B16_REC) + (4 * H + (e_)) * 64))
-        // the chain of (e, n) follows the MFMAs of e + 1 (one iteration behind: no MFMA -> VALU wait states in front of it)
+            for (int n = 0; n < 2; ++n) Bq[e & 1][n] = *(const bamd_h8 *) (bop + BLK * X_BLK + n * (16 * BAMD_B16_REC) + (4 * H + e) * 64);
+        };
         auto chain = [&](int e, int n, const bamd_f4 & s) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float av = acc[n][4 * H + e][i];
-                if (Q2) av = fmaf(Dm[n][i], __builtin_amdgcn_fdot2(mn[i][e].h, bs[n][e].h, 0.f, false), av);      // the min term first, into the same accumulator
-                acc[n][4 * H + e][i] = fmaf(D[n][i], s[i], av);
-            }
+            for (int i = 0; i < 4; ++i) acc[n][4 * H + e][i] = fmaf(D[n][i], s[i], hdr.mins(acc[n][4 * H + e][i], n, e, i));
         };
-        Aq[0] = XL_LDA(0); Bq[0][0] = XL_LDB(0, 0); Bq[0][1] = XL_LDB(0, 1);
+        load_ops(0);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            if (e + 1 < 4) { Aq[(e + 1) & 1] = XL_LDA(e + 1); Bq[(e + 1) & 1][0] = XL_LDB(e + 1, 0); Bq[(e + 1) & 1][1] = XL_LDB(e + 1, 1); }
-            if ((e & 1) == 0) build_a(qs[NXT], Q2 ? 0u : hm[NXT], e >> 1);
-            const bamd_f4 z = { 0.f, 0.f, 0.f, 0.f };
-            const bamd_f4 s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[e & 1], Bq[e & 1][0], z, 0, 0, 0);
-            const bamd_f4 s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[e & 1], Bq[e & 1][1], z, 0, 0, 0);
-            if (e > 0) { chain(e - 1, 0, sp[0]); chain(e - 1, 1, sp[1]); }
-            if (e & 1) build_b(sc[NXT][e >> 1], afw + NXT * X_AF_BYTES + (e >> 1) * 256);
-            sp[0] = s0; sp[1] = s1;
+            if (e + 1 < 4) load_ops(e + 1);
+            if ((e & 1) == 0) f.build_a(NXT, e >> 1);
+            bamd_f4 s[2];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {                      // NFRAG MFMAs chained through the accumulator: the exact integer isum_e of the tile
+                s[n] = (bamd_f4) { 0.f, 0.f, 0.f, 0.f };
+#pragma unroll
+                for (int p = 0; p < F::NFRAG; ++p) s[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Aq[e & 1][p], Bq[e & 1][n], s[n], 0, 0, 0);
+                if (!F::LATE_CHAIN) chain(e, n, s[n]);
+            }
+            if (F::LATE_CHAIN && e > 0) { chain(e - 1, 0, sp[0]); chain(e - 1, 1, sp[1]); }
+            if (e & 1) f.build_b(NXT, e >> 1, afw + NXT * X_AF_BYTES + (e >> 1) * 256);
+            sp[0] = s[0]; sp[1] = s[1];
             __builtin_amdgcn_sched_barrier(0);
         }
-        chain(3, 0, sp[0]); chain(3, 1, sp[1]);
-#undef XL_LDA
-#undef XL_LDB
+        if (F::LATE_CHAIN) { chain(3, 0, sp[0]); chain(3, 1, sp[1]); }
         if (H == 1) lds_dma_wait();
         __syncthreads();
     };
@@ -473,16 +434,16 @@ __global__ void __launch_bounds__(512) matmul_mfma2_lowbit_kernel(bamd_mma2_args
             step(2 * ci + 3, std::integral_constant<int, 1>(), std::integral_constant<int, 1>());
         }
     }
-#undef XL_STAGE
     if (!live) return;
-    // hsum_float_8 over e, then the epilogue as in the sixteen-wave kernel: rows 4g .. 4g+3 of token t are 16 consecutive bytes
+    // hsum_float_8 over e, then rows 4g .. 4g+3 of token t — 16 consecutive bytes — as one 16-byte access where all four exist and the token rows are 16-byte aligned,
+    // else one by one
     const int row0 = rtg * 16 + 4 * g;
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const int t = t0 + (2 * tp + n) * 16 + m;
         float val[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) val[i] = ((acc[n][0][i] + acc[n][4][i]) + (acc[n][2][i] + acc[n][6][i])) + ((acc[n][1][i] + acc[n][5][i]) + (acc[n][3][i] + acc[n][7][i]));
+        for (int i = 0; i < 4; ++i) val[i] = x_hsum8(acc[n], i);
         if (t < a.T && row0 < a.nrows) {
             const size_t o = (size_t) t * a.ldo + row0;
             if (row0 + 3 < a.nrows && (a.ldo & 3) == 0) {
@@ -549,7 +510,7 @@ __global__ void __launch_bounds__(1024) matmul_mfma3_q4k_kernel(bamd_mma2_args a
     const uint32_t lds0 = (uint32_t) (size_t) (bamd_lds_vp) smem;
     // ---- stage plan.  A block = 45 KiB-instructions: k = 0..37 records (chunk 64 k + lane of 64 tokens x 38), 38..40 consumer headers, 41..44 builder
     //      operands.  Wave w issues k = w, 16 + w and k2 = 32 + w (w <= 12; waves 13..15 repeat the operand copies 41..43: same bytes, same place).
-    auto rec_off = [&](int idx) { const int tok = idx / BAMD_B16_Q, q = idx - tok * BAMD_B16_Q; const int tg = t0 + tok < a.T ? t0 + tok : a.T - 1; return (uint32_t) ((size_t) tg * b16 + (size_t) q * 16); };
+    auto rec_off = [&](int idx) { return x_rec_off(idx, t0, a.T, b16); };
     const int k2 = wave <= 12 ? 32 + wave : 28 + wave;
     const bool rec2 = k2 <= 37, hdr2 = k2 >= 38 && k2 <= 40;
     uint32_t so0 = rec_off(tid), so1 = rec_off(1024 + tid);          // advance by one super-block per step (sources stay fixed scalar pointers)
@@ -732,12 +693,12 @@ __global__ void __launch_bounds__(1024) matmul_mfma3_q4k_kernel(bamd_mma2_args a
     }
 #endif
     if (!live) return;
-    // hsum_float_8 over e and the acc_m folds, in the reference's order (finish_row), then the epilogue: rows 4g .. 4g+3 of token t are 16 consecutive bytes
+    // hsum_float_8 over e and the acc_m folds, in the reference's order (finish_row), then the row-of-four store of the eight-wave body
     const int t = t0 + tt * 16 + m;
     float val[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const float v = ((acc[0][i] + acc[4][i]) + (acc[2][i] + acc[6][i])) + ((acc[1][i] + acc[5][i]) + (acc[3][i] + acc[7][i]));
+        const float v = x_hsum8(acc, i);
         const float mm = Q5 ? accm[0][i] : (accm[0][i] + accm[2][i]) + (accm[1][i] + accm[3][i]);
         val[i] = v + mm;
     }
@@ -809,9 +770,9 @@ int bamd_prefill_mfma_supported(void) {
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) { (void) hipGetLastError(); return 0; }
     if ((size_t) lds < (size_t) X3_LDS_BYTES || (size_t) lds < (size_t) X_LDS_BYTES) return 0;
     if (hipFuncSetAttribute((const void *) matmul_mfma3_q4k_kernel<BAMD_EPI_STORE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X3_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void *) matmul_mfma2_q6k_kernel<BAMD_EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void *) matmul_mfma2_lowbit_kernel<BAMD_EPI_STORE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess ||
-        hipFuncSetAttribute((const void *) matmul_mfma2_lowbit_kernel<BAMD_EPI_STORE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess) { (void) hipGetLastError(); return 0; }
+        hipFuncSetAttribute((const void *) matmul_mfma2_kernel<BAMD_EPI_STORE, X2Q6K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void *) matmul_mfma2_kernel<BAMD_EPI_STORE, X2LowBit<false>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess ||
+        hipFuncSetAttribute((const void *) matmul_mfma2_kernel<BAMD_EPI_STORE, X2LowBit<true>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) X_LDS_BYTES) != hipSuccess) { (void) hipGetLastError(); return 0; }
     return 1;
 }
 int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
@@ -828,22 +789,16 @@ int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, 
     a.out = out; a.res = res; a.blob16 = (const uint8_t *) blob16; a.K = K; a.T = T; a.nrows = nrows; a.nrows_pad = nrows_pad; a.ldo = ldo;
     a.dbg = g_prefill_dbg;
     const dim3 grid((T + 63) / 64, x_row_blocks(nrows_pad));
-#define X_LAUNCH(KERNEL, ...) do { \
-        if (epi == BAMD_EPI_ADD)           hipLaunchKernelGGL((KERNEL<BAMD_EPI_ADD __VA_ARGS__>),      grid, dim3(512), X_LDS_BYTES, s, a); \
-        else if (epi == BAMD_EPI_SILU_MUL) hipLaunchKernelGGL((KERNEL<BAMD_EPI_SILU_MUL __VA_ARGS__>), grid, dim3(512), X_LDS_BYTES, s, a); \
-        else                               hipLaunchKernelGGL((KERNEL<BAMD_EPI_STORE __VA_ARGS__>),    grid, dim3(512), X_LDS_BYTES, s, a); } while (0)
     const dim3 grid3(grid.x, BAMD_PREFILL_CEILING == 2 ? (grid.y + 1) / 2 : grid.y);     // (ceiling build 2: every workgroup issues the MFMAs of two; timing only)
-#define X3_LAUNCH(KERNEL, ...) do { \
-        if (epi == BAMD_EPI_ADD)           hipLaunchKernelGGL((KERNEL<BAMD_EPI_ADD __VA_ARGS__>),      grid3, dim3(1024), X3_LDS_BYTES, s, a); \
-        else if (epi == BAMD_EPI_SILU_MUL) hipLaunchKernelGGL((KERNEL<BAMD_EPI_SILU_MUL __VA_ARGS__>), grid3, dim3(1024), X3_LDS_BYTES, s, a); \
-        else                               hipLaunchKernelGGL((KERNEL<BAMD_EPI_STORE __VA_ARGS__>),    grid3, dim3(1024), X3_LDS_BYTES, s, a); } while (0)
     g_mfma_runs[type] += 1;
-    if (type == BAMD_Q6_K)      X_LAUNCH(matmul_mfma2_q6k_kernel);
-    else if (type == BAMD_Q3_K) X_LAUNCH(matmul_mfma2_lowbit_kernel, , false);
-    else if (type == BAMD_Q2_K) X_LAUNCH(matmul_mfma2_lowbit_kernel, , true);
-    else if (type == BAMD_Q5_K) X3_LAUNCH(matmul_mfma3_q4k_kernel, , true);
-    else                        X3_LAUNCH(matmul_mfma3_q4k_kernel, , false);
-#undef X3_LAUNCH
-#undef X_LAUNCH
+    with_const(consts<BAMD_EPI_ADD, BAMD_EPI_SILU_MUL, BAMD_EPI_STORE>(), epi, [&](auto E) -> bool {
+        constexpr int EPI = decltype(E)::value;
+        auto launch = [&](auto kernel, dim3 g, int threads, size_t lds) { hipLaunchKernelGGL(kernel, g, dim3(threads), lds, s, a); };
+        if (type == BAMD_Q6_K)      launch(matmul_mfma2_kernel<EPI, X2Q6K>, grid, 512, X_LDS_BYTES);
+        else if (type == BAMD_Q3_K) launch(matmul_mfma2_kernel<EPI, X2LowBit<false>>, grid, 512, X_LDS_BYTES);
+        else if (type == BAMD_Q2_K) launch(matmul_mfma2_kernel<EPI, X2LowBit<true>>, grid, 512, X_LDS_BYTES);
+        else if (type == BAMD_Q5_K) launch(matmul_mfma3_q4k_kernel<EPI, true>, grid3, 1024, X3_LDS_BYTES);
+        else                        launch(matmul_mfma3_q4k_kernel<EPI, false>, grid3, 1024, X3_LDS_BYTES);
+        return true; });
     return 0;
 }

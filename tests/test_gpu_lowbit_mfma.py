@@ -1,4 +1,4 @@
-"""GPU: the matrix-core prompt mat-muls for Q3_K / Q2_K weights (matmul_mfma2_lowbit_kernel, behind set_prefill_lowbit / BAMD_PREFILL_LOWBIT=1; default off).
+"""GPU: the matrix-core prompt mat-muls for Q3_K / Q2_K weights (matmul_mfma2_kernel with the X2LowBit policies, behind set_prefill_lowbit / BAMD_PREFILL_LOWBIT=1; default off).
 Every expectation is the genuine reference's stored output (tests/golden/lowbit_kats.npz, tests/golden/lowbit_*.bgld) or the numpy restatement that
 tests/test_lowbit_ref.py holds to those (tests/lowbit_ref.py); bit equality throughout.  The switch is set through the setter and restored afterwards; the
 launch counters (prefill_mfma_runs) tell the matrix-core kernel from the integer-dot kernel, which gives the same bits."""

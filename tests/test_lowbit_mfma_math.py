@@ -1,4 +1,4 @@
-"""CPU: the arithmetic of the matrix-core prompt mat-muls for Q3_K / Q2_K weights (booster_amd/csrc/bamd_prefill2.hip, matmul_mfma2_lowbit_kernel), checked
+"""CPU: the arithmetic of the matrix-core prompt mat-muls for Q3_K / Q2_K weights (booster_amd/csrc/bamd_prefill2.hip, matmul_mfma2_kernel with the X2LowBit policies), checked
 before a GPU is involved.  Per SIMD lane e of the reference and super-block the kernel forms an f16 fragment scale x quant, multiplies it with the f16 image of
 the 32 int8 activations of lane e and sums the products in f32 in whatever order the matrix core takes; then come the reference's f32 chains.  That is only
 the reference's dot product if every operand is an exact float16 and the f32 sum is exact in any order; both are asserted here, and the whole formulation is
