@@ -60,6 +60,7 @@ def lib():
         L.bamd_set_prefill_lowbit.argtypes = [ci]; L.bamd_set_prefill_lowbit.restype = None
         L.bamd_set_prefill_q0.argtypes = [ci]; L.bamd_set_prefill_q0.restype = None
         L.bamd_set_prefill_q1.argtypes = [ci]; L.bamd_set_prefill_q1.restype = None
+        L.bamd_set_prefill_flt.argtypes = [ci]; L.bamd_set_prefill_flt.restype = None
         L.bamd_set_attn_scratch_mb.argtypes = [ci]; L.bamd_set_attn_scratch_mb.restype = None
         L.bamd_attention_batch_plan.argtypes = [ci, ci, ci, ci, ci, ci, C.c_size_t, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
         L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong
@@ -124,6 +125,13 @@ def set_prefill_q1(on):
     False (default, also env BAMD_PREFILL_Q1): such a model evaluates prompts on the integer-dot kernel.  Independent of set_prefill_q0: a Q4_0 / Q5_0 file made
     with an importance matrix holds Q4_1 / Q5_1 ffn_down matrices and needs both switches on to get tables.  Same bits either way."""
     lib().bamd_set_prefill_q1(int(bool(on)))
+
+
+def set_prefill_flt(on):
+    """True: F32 / F16 matrices evaluate prompts on the f32 matrix-core kernel; False (default, also env BAMD_PREFILL_FLT): on the VALU kernel.  Read at each
+    launch, not at model load (the kernel needs no side tables), so it also applies to models loaded before.  BF16 matrices stay on the VALU kernel.  Same bits
+    either way."""
+    lib().bamd_set_prefill_flt(int(bool(on)))
 
 
 def set_attn_scratch_mb(mb):

@@ -117,7 +117,7 @@ struct bamd_model {
     int n_cu = 256;
     std::unique_ptr<GgufFile> file;  // stays mapped (bamd_model_tensor_raw)
     std::vector<void *> allocs;
-    bool aux_ok = false; int64_t aux_bytes = 0; std::string aux_why;      // prefill side tables: all matrices or none (build_prefill_aux)
+    bool aux_ok = false, aux_none_needed = false; int64_t aux_bytes = 0; std::string aux_why;      // prefill side tables: all matrices or none (build_prefill_aux)
 };
 
 // ---- one cached replay of "the fixed launch sequence of one step", rebuilt when, and only when, the key of the step at hand differs from the one it was built for.
@@ -356,7 +356,7 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
     hipFree(staging);
     if (!rc) {
         build_prefill_aux(m, s);
-        if (!m->aux_ok && getenv("BAMD_PREFILL_VERBOSE")) fprintf(stderr, "bamd: prompts run without the matrix-core kernels: %s\n", m->aux_why.c_str());
+        if (!m->aux_ok && !m->aux_none_needed && getenv("BAMD_PREFILL_VERBOSE")) fprintf(stderr, "bamd: prompts run without the matrix-core kernels: %s\n", m->aux_why.c_str());
     }
     hipStreamDestroy(s);
     return rc;
@@ -850,10 +850,16 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
         items.push_back({ ly.wu.stream, ly.wu.type, ly.wu.nrows_pad, m->E, &ly.aux_u });
         items.push_back({ ly.wd.stream, ly.wd.type, ly.wd.nrows_pad, m->F, &ly.aux_d });
     }
+    // F32 / F16 matrices with BAMD_PREFILL_FLT on: their matrix-core kernel has no side table (bamd_batch_mm reads the switch at each launch), so they ask for
+    // nothing here; a model of such matrices only has nothing to build and nothing to report
+    const size_t n_all = items.size();
+    if (bamd_prefill_flt()) items.erase(std::remove_if(items.begin(), items.end(), [](const Item & it) { return it.type == BAMD_F32 || it.type == BAMD_F16; }), items.end());
+    if (n_all && items.empty()) { m->aux_none_needed = true; return; }
     size_t need = 0;
     for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
         // (with every switch off the reasons read as they did before the switches existed; with one of BAMD_PREFILL_Q0 / BAMD_PREFILL_Q1 on, the one that is missing is named)
-        m->aux_why = bamd_is_flt(it.type) ? "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels"
+        m->aux_why = bamd_is_flt(it.type) && bamd_prefill_flt() ? "the model holds a BF16 matrix: these have no matrix-core kernel (BAMD_PREFILL_FLT covers F32 / F16 only), and side tables are all-or-nothing per model, so every prompt mat-mul of the other types runs on the VALU kernels"
+                   : bamd_is_flt(it.type) ? "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels"
                    : bamd_is_q1(it.type) && bamd_prefill_q0() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_Q0 covers only its Q4_0 / Q5_0 / Q8_0 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q0(it.type) && bamd_prefill_q1() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_Q1 covers only its Q4_1 / Q5_1 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
@@ -906,8 +912,11 @@ static int ensure_batch_buffers(bamd_context * c) {
 // prompt path below and the op-level entry point (bamd_op_mul_mat_batch_seg) both come through here
 int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s) {
     const int T = a.T;
-    auto on_mfma = [&](int i) { return g_prefill_mfma && aux[i] && bamd_prefill_mfma_type(a.seg[i].type); };
+    // (F32 / F16 with bamd_prefill_flt(): no side table — the switch is read here, at each launch; their kernel takes the f32 rows of a.blob.  BF16 never)
+    auto flt_mfma = [&](int i) { return g_prefill_mfma && bamd_prefill_flt() && (a.seg[i].type == BAMD_F32 || a.seg[i].type == BAMD_F16); };
+    auto on_mfma = [&](int i) { return flt_mfma(i) || (g_prefill_mfma && aux[i] && bamd_prefill_mfma_type(a.seg[i].type)); };
     auto mm_mfma = [&](const bamd_mv_seg & sg, const void * ax, int nv, float * out, const float * res, int e) {
+        if (sg.type == BAMD_F32 || sg.type == BAMD_F16) return bamd_launch_matmul_mfma_flt(sg.w, sg.type, nv, sg.nrows, a.K, a.blob, T, out, res, e, a.ldo, s);
         return bamd_launch_matmul_mfma2(sg.w, ax, sg.type, nv, sg.nrows, a.K, blob16, T, out, res, e, a.ldo, s);
     };
     if (epi == BAMD_EPI_SILU_MUL) {

@@ -147,6 +147,14 @@ size_t bamd_prefill_aux_bytes_b32(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                                  int epi, int ldo, hipStream_t s);
+// F32 / F16 matrices on the matrix cores, exact (bamd_prefill2_flt.hip), behind a switch of their own, bamd_prefill_flt() (BAMD_PREFILL_FLT=1 / bamd_set_prefill_flt; default
+// off).  Unlike the switches above it is read at each launch, not at model load: the kernel reads the resident weight stream and the f32 activation rows of
+// bamd_launch_act_batch_flt (blob) as they are, there is no side table to build.  BF16 has no such kernel.  Epilogues as bamd_launch_matmul_mfma2; 1 = type / shape
+// not supported.  bamd_prefill_mfma_count: one more launch of `type` for bamd_prefill_mfma_runs (the counters live in bamd_prefill2.hip)
+int  bamd_prefill_flt(void);
+int  bamd_launch_matmul_mfma_flt(const void * w_stream, int type, int nrows, int nrows_pad, int K, const void * blob, int T, float * out, const float * res, int epi, int ldo,
+                                 hipStream_t s);
+void bamd_prefill_mfma_count(int type);
 int  bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);      // 1 = shape not supported
 void bamd_launch_embed_batch(const int32_t * tokens, int T, const void * embd, int embd_type, int E, int V, float * x, hipStream_t s);
 // impl: 0 = the matrix-core kernel where it covers the shape, else the VALU kernels (the engine); 1 = the VALU kernels only; 2 = the matrix-core

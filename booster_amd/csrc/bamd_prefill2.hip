@@ -739,6 +739,7 @@ extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_lowbit(i
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_q0(int on) { g_prefill_q0 = on ? 1 : 0; }
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_q1(int on) { g_prefill_q1 = on ? 1 : 0; }
 extern "C" __attribute__((visibility("default"))) long long bamd_prefill_mfma_runs(int type) { return type >= 0 && type < 16 ? g_mfma_runs[type] : 0; }
+void bamd_prefill_mfma_count(int type) { if (type >= 0 && type < 16) g_mfma_runs[type] += 1; }      // the F32 / F16 launcher's (bamd_prefill2_flt.hip)
 static inline bool x_lowbit(int type) { return type == BAMD_Q3_K || type == BAMD_Q2_K; }
 // builder / consumer part of a (row block, super-block) in the side table, and the super-blocks of slack behind each part (the sixteen-wave kernel's last
 // two staging calls read past the end of K; the eight-wave kernels clamp)

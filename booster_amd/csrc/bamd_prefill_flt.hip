@@ -1,6 +1,6 @@
 // bamd_prefill_flt.hip — batched prompt path of the unquantised weight family (F32 / F16 / BF16): the activation pass for T rows and a VALU mat-mul for 1..512
 // tokens.  Every output runs the chain of the mat-vec (bamd_flt_device.h) — the reference's per-element chain does not depend on the number of tokens either
-// (tinyBLAS tiles differ only in which outputs share a loop) — so a batched prompt gives the bits of token by token.  A matrix-core kernel is a follow-up.
+// (tinyBLAS tiles differ only in which outputs share a loop) — so a batched prompt gives the bits of token by token.  F32 / F16: bamd_prefill2_flt.hip runs the same chains on the matrix cores (BAMD_PREFILL_FLT).
 #include "bamd_flt_device.h"
 #include "bamd_kernels.h"
 

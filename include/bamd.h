@@ -209,7 +209,12 @@ void bamd_set_prefill_q0(int on);
  * weights) and a matrix-core kernel of their own.  Independent of bamd_set_prefill_q0.  Side tables are all-or-nothing per model: a Q4_0 / Q5_0 file made with
  * an importance matrix holds Q4_1 / Q5_1 ffn_down matrices and gets tables only with both switches on.  Taken at model load.  Bit-identical results. */
 void bamd_set_prefill_q1(int on);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K) since the library was loaded */
+/* Matrix-core prompt mat-muls for F32 / F16 weights (env BAMD_PREFILL_FLT): 0 (default) = such matrices evaluate prompts on the VALU kernel; 1 = on
+ * v_mfma_f32_16x16x4_f32, the same fma chains.  UNLIKE the three switches above this one is read at each launch, not at model load: the kernel reads the resident
+ * weights and the f32 activation rows as they are, there is no side table (bamd_model_prefill_aux_bytes stays 0 for such a model), so it takes effect for models and
+ * contexts that exist already.  BF16 weights stay on the VALU kernel either way (their chain is a multiply and an add, not an fma).  Bit-identical results. */
+void bamd_set_prefill_flt(int on);
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
