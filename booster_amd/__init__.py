@@ -15,6 +15,7 @@ _lib = None
 
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
 Q2_K, Q3_K = 10, 11
+IQ4_NL = 20
 
 
 class BamdError(RuntimeError):
@@ -85,6 +86,7 @@ def lib():
         L.bamd_op_mul_mat_batch_seg.argtypes = [ci, vp, vp, vp, ci, vp, ci, vp, cf, ci, vp, ci, ci, vp]
         L.bamd_op_attention_wo.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.bamd_trace_matvec.argtypes = [ci, vp, vp, ci, ci, ci, ci, ci, vp]
+        L.bamd_trace_mv.argtypes = [ci, vp, vp, ci, ci, ci, ci, ci, vp]
         L.bamd_trace_attn_wo.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
         L.bamd_set_aql.argtypes = [ci]; L.bamd_set_aql.restype = None
         L.bamd_aql_runs.argtypes = [vp]
@@ -277,7 +279,7 @@ class Context:
     def timeline_step(self, pos, replays=3):
         """phase stamps of one decode step (BAMD_LIB=.../libbooster_amd_timing.so): u64 [launches][512 workgroups][24], 100 MHz;
         per workgroup: 8 phases of wave 0, 8 phases of wave 7, the exit stamp of each of the 8 waves"""
-        cap = 5 * self.model.n_layer + 1
+        cap = 6 * self.model.n_layer + 1        # (five launches per layer, six where the QKV needs two activation forms: the IQ4_NL recipe)
         out = np.zeros((cap, 512, 24), np.uint64)
         n = C.c_int(0)
         _chk(lib().bamd_timeline_step(self.h, pos, replays, _p(out), cap, C.byref(n)))
@@ -547,6 +549,13 @@ def trace_matvec(segs, k, pro, epi, mode=0, n_cu=256):
     types = np.array([t for t, _ in segs], np.int32); rows = np.array([r for _, r in segs], np.int32)
     t = _LaunchTrace()
     return _trace(lib().bamd_trace_matvec(len(segs), _p(types), _p(rows), k, pro, epi, mode, n_cu, C.byref(t)), t)
+
+
+def trace_mv(segs, k, pro, epi, mode=0, n_cu=256):
+    """as trace_matvec, through the dispatch the engine uses (bamd_launch_mv): every family of weight types, not the K-quants alone"""
+    types = np.array([t for t, _ in segs], np.int32); rows = np.array([r for _, r in segs], np.int32)
+    t = _LaunchTrace()
+    return _trace(lib().bamd_trace_mv(len(segs), _p(types), _p(rows), k, pro, epi, mode, n_cu, C.byref(t)), t)
 
 
 def trace_attn_wo(H, Hkv, hd, n_ctx, lds_ld, wo_type, wo_rows, k, n_cu=256, il=0, with_cellpos=False):

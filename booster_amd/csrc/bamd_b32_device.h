@@ -2,6 +2,7 @@
 // prompt mat-mul on the integer-dot kernel; the matrix-core one, bamd_prefill2_b32.hip, restates the chains for its own lane layout): the Q8_0 / Q8_1 activation
 // prologue, the wave-stream records (layout: bamd_formats.h), their block terms and the chains.  Two families, told apart by b32_has_min(TYPE):
 //   without a minimum  Q8_0 / Q4_0 / Q5_0   weights {d, q}, Q8_0 activations {d, q}
+//                      IQ4_NL               the Q4_0 record; a nibble indexes a table of 16 int8; TWO accumulators (b32_two_acc(TYPE)), see below
 //   with a minimum     Q4_1 / Q5_1          weights {d, m, q}, Q8_1 activations {d, s, q}
 //
 // NUMERICS (contract: bamd_device.h).  Reference functions restated here (cpp/ = the reference tree):
@@ -11,6 +12,7 @@
 //   ggml_vec_dot_q5_0_q8_0 (AVX2)    ggml/src/ggml-quants.c:4644-4666     (the same chain; _q4_0_q8_0 :3900-3923 and _q8_0_q8_0 :5227- have its shape too)
 //   ggml_vec_dot_q4_1_q8_1 (AVX2)    ggml/src/ggml-quants.c:4344-4377     (llamafile_sgemm has no case for these types: one token and many go through vec_dot)
 //   ggml_vec_dot_q5_1_q8_1 (AVX2)    ggml/src/ggml-quants.c:5009-5034
+//   ggml_vec_dot_iq4_nl_q8_0 (AVX2)  ggml/src/ggml-quants.c:11596-11670, AVX2 branch :11643-11670 (llamafile_sgemm has no case for the type either, sgemm.cpp:865-985)
 // Without a minimum, one output = ONE 8-lane f32 accumulator: for the 32-blocks l = 0 .. K/32 - 1 in order, lane e: acc_e = fma(f32(f16 d_w) * f32(f16 d_x), (float) dot4_e,
 // acc_e), with dot4_e the exact signed dot of bytes 4e .. 4e+3 of the weight block and the activation block (sign_epi8 / maddubs: |pair sum| <= 2 * 128 * 127, never
 // saturates; activations never hold -128), then hsum (finish_row's tree).  Wave lane r*8 + e is SIMD lane e of row r.
@@ -21,11 +23,17 @@
 //   from its outputs and does not matter: the product of two widened f16 values is exact in f32, so both forms give the same bits (tests/legacy1_ref.py;
 //   the stored reference outputs, tests/golden/legacy1_kats.npz, are reproduced by either).  Here: a product, then a sum (-ffp-contract=off).
 // Result: hsum(acc) + summs.  Every lane of a row carries the row's summs chain redundantly (K/32 dependent steps whose order must not change: nothing crosses lanes).
+// IQ4_NL, one output = TWO 8-lane accumulators of the first shape (:11649-11668): the loop takes two blocks per iteration, accum1_e = fma(f32(d_x) * f32(d_w),
+// (float) p_e, accum1_e) over the EVEN blocks l in order and accum2_e likewise over the ODD ones, p_e the exact dot of kvalues_iq4nl[nibble] (:3548) with the
+// activation bytes 4e .. 4e+3 (mul_add_epi8 / madd: |pair sum| <= 2 * 127 * 127, never saturates); then accum1 + accum2 lane by lane and hsum_float_8 (:11670).
+// K is a multiple of 256: the block count is even and the reference's scalar tail never runs.  A record is eight consecutive blocks, so a block's parity is the
+// parity of its index c in the record.
 #pragma once
 #include <type_traits>
 #include "bamd_device.h"
 constexpr bool b32_has_min(int type) { return type == BAMD_Q4_1 || type == BAMD_Q5_1; }
 constexpr bool b32_has_qh(int type) { return type == BAMD_Q5_0 || type == BAMD_Q5_1; }
+constexpr bool b32_two_acc(int type) { return type == BAMD_IQ4_NL; }
 // floats of a parked record of the split-K kernels: f[c][lane] (8 x 64 floats) + the scale products s[r][c] (8 x 8); with a minimum also the row's m * s products ms[r][c] (8 x 8)
 constexpr int b32_term_floats(bool has_min) { return has_min ? 640 : 576; }
 
@@ -164,11 +172,17 @@ template <int TYPE> __device__ __forceinline__ void load_rec(RecB32<TYPE> & R, b
 #define BAMD_B32_COMP(v, k) ((k) == 0 ? (v).x : (k) == 1 ? (v).y : (k) == 2 ? (v).z : (v).w)
 // the four weights of block c for lane e as int8.  Without a minimum: Q8_0 as stored (-128 included); Q4_0 nibble - 8 = (n + 0x78) ^ 0x80 per byte (sgemm.cpp:773-775,
 // low nibbles = elements 0-15, high = 16-31); Q5_0 (nibble | bit 4) - 16 = (x + 0x70) ^ 0x80 (ggml-quants.c:4655-4658: a clear qh bit ORs 0xF0 into the nibble).  No
-// inter-byte carry.  With a minimum: unsigned and without an offset (ggml-quants.c:4364, :5021-5024)
+// inter-byte carry.  With a minimum: unsigned and without an offset (ggml-quants.c:4364, :5021-5024).  IQ4_NL: kvalues_iq4nl[nibble] (_mm_shuffle_epi8, :11656-11659) as
+// byte permutes of the table in registers: its halves 0-7 and 8-15 selected by the nibble's low three bits, then of each byte pair the half its bit 3 names
 template <int TYPE> __device__ __forceinline__ uint32_t b32_weights(const RecB32<TYPE> & R, int c, int e) {
     const uint32_t raw = c < 4 ? BAMD_B32_COMP(R.q0, c) : BAMD_B32_COMP(R.q1, c - 4);
     if (TYPE == BAMD_Q8_0) return raw;
     const uint32_t nib = (raw >> ((e >> 2) * 4)) & 0x0f0f0f0fu;
+    if (TYPE == BAMD_IQ4_NL) {                                           // {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}, four to a dword
+        const uint32_t sel = nib & 0x07070707u;
+        const uint32_t lo = __builtin_amdgcn_perm(0xf6eaddcfu, 0xbfad9881u, sel), hi = __builtin_amdgcn_perm(0x71594535u, 0x26190d01u, sel);
+        return __builtin_amdgcn_perm(hi, lo, ((nib >> 1) & 0x04040404u) | 0x03020100u);
+    }
     const uint32_t u = b32_has_qh(TYPE) ? nib | (((R.qh >> c) & 0x01010101u) << 4) : nib;
     if (b32_has_min(TYPE)) return u;
     return (u + (b32_has_qh(TYPE) ? 0x70707070u : 0x78787878u)) ^ 0x80808080u;
@@ -205,6 +219,12 @@ template <int TYPE> __device__ __forceinline__ void b32_terms(const RecB32<TYPE>
 __device__ __forceinline__ void b32_chain8(float & acc, const float (&s)[8], const float (&f)[8]) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) acc = fmaf(s[c], f[c], acc);
+}
+// the two-accumulator shape (b32_two_acc: IQ4_NL, ggml-quants.c:11651-11668): the even blocks of the record into acc1, the odd ones into acc2, each in block order
+// (the ONLY place this order is defined); the row ends with b32_finish_row(acc1 + acc2) (:11670)
+__device__ __forceinline__ void b32_chain8(float & acc1, float & acc2, const float (&s)[8], const float (&f)[8]) {
+#pragma unroll
+    for (int c = 0; c < 8; c += 2) { acc1 = fmaf(s[c], f[c], acc1); acc2 = fmaf(s[c + 1], f[c + 1], acc2); }
 }
 // eight steps of the row's scalar chain, in block order (the ONLY place its order is defined): ms[c] is an exact product, the sum rounds
 __device__ __forceinline__ void b32_summs8(float & summs, const float (&ms)[8]) {

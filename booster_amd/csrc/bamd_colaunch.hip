@@ -252,7 +252,7 @@ __device__ __forceinline__ void wo_role_b32(const bamd_mv_args & a, const ProArg
     __syncthreads();
     if (wave < M) {
         const float * B = part0 + (size_t) wave * rg_floats;
-        float acc = 0.f, summs = 0.f;
+        float acc = 0.f, acc2 = 0.f, summs = 0.f;                           // (acc2: the odd blocks' accumulator of a type with two, b32_two_acc)
         for (int ib = 0; ib < nb; ++ib) {
             const float * P = B + (size_t) ib * TERM_FLOATS;
             const float4 s0 = *(const float4 *) (P + 512 + r8 * 8), s1 = *(const float4 *) (P + 512 + r8 * 8 + 4);
@@ -264,10 +264,11 @@ __device__ __forceinline__ void wo_role_b32(const bamd_mv_args & a, const ProArg
             }
 #pragma unroll
             for (int c = 0; c < 8; ++c) fd[c] = P[c * 64 + lane];
-            b32_chain8(acc, sc, fd);
+            if constexpr (b32_two_acc(TYPE)) b32_chain8(acc, acc2, sc, fd);
+            else b32_chain8(acc, sc, fd);
             if (MIN) b32_summs8(summs, ms);                                 // the row's scalar chain, in block order beside the 128-step lane chain
         }
-        const float val = b32_finish_row<MIN>(acc, summs);
+        const float val = b32_finish_row<MIN>(b32_two_acc(TYPE) ? acc + acc2 : acc, summs);
         if ((lane & 7) == 0 && crow < nv) ik_st(a.seg[0].out + crow, val + resv);
     }
 }
@@ -315,10 +316,10 @@ int bamd_launch_attn_wo(const bamd_attn_args & t, int gq, const bamd_mv_args & w
     // term buffers of the wo role: K = 4096 up to three row-groups in one batch (wo_role), K = 8192 two buffers of two (wo_role_batched)
     const size_t lds = mv_lds_colaunch(nb, nb == 32 ? 2 * 2 : 3, ld);
     const int lg = t.hd >> 6;                                                                 // attention instance: head size / 64 (1..4, checked above)
-    if (bamd_is_q0(type) || bamd_is_q1(type)) {                                               // a wo of the 32-weight block formats: K = 4096 only
+    if (bamd_takes_q8_0(type) || bamd_is_q1(type)) {                                          // a wo of the 32-weight block formats: K = 4096 only
         if (nb != 16) return 1;
         return with_const(consts<1, 2, 3, 4>(), lg >= 1 && lg <= 3 ? lg : 4, [&](auto LG) -> bool {
-            return with_const(consts<BAMD_Q8_0, BAMD_Q4_0, BAMD_Q5_0, BAMD_Q4_1, BAMD_Q5_1>(), type, [&](auto T) -> bool {
+            return with_const(consts<BAMD_Q8_0, BAMD_Q4_0, BAMD_Q5_0, BAMD_Q4_1, BAMD_Q5_1, BAMD_IQ4_NL>(), type, [&](auto T) -> bool {
                 BAMD_LAUNCH((attn_wo_b32_kernel<decltype(LG)::value, decltype(T)::value>), dim3(n_cu), dim3(512), colaunch_b32_lds(b32_has_min(decltype(T)::value), nb, ld), s, t, gq, wo, gran, il, extra, g_ring_delay, err);
                 return true; }); }) ? 0 : 1;
     }

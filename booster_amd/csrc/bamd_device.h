@@ -1068,6 +1068,18 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
             }
             ik_st(x + i, (float) q * d);
         }
+    } else if (embd_type == BAMD_IQ4_NL) {
+        // dequantize_row_iq4_nl (ggml-quants.c:3550-3566): y = d * kvalues_iq4nl[nibble], one f32 product; the table (:3548) as two 64-bit constants, a byte per entry
+        const uint8_t * row = embd + (size_t) tok * (E >> 5) * 18;
+        for (int i = threadIdx.x; i < E; i += blockDim.x) {
+            const uint8_t * b = row + (size_t) (i >> 5) * 18;
+            const int n = i & 31;
+            const float d = h2f(*(const unsigned short *) b);
+            const uint8_t v = b[2 + (n & 15)];
+            const int nib = n < 16 ? (v & 0xF) : (v >> 4);
+            const int q = (int) (int8_t) ((nib < 8 ? 0xf6eaddcfbfad9881ull : 0x7159453526190d01ull) >> ((nib & 7) * 8));
+            ik_st(x + i, d * (float) q);
+        }
     } else if (bamd_is_q1(embd_type)) {
         // dequantize_row_q4_1 / q5_1 (ggml-quants.c:1535-1551, :1582-1604): y = q * d + m with q unsigned; q * d (an integer below 32 times a widened f16)
         // is exact in f32, so a fused and a separate multiply-add give the same bits (tests/legacy1_ref.py)

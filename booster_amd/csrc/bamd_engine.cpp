@@ -196,7 +196,7 @@ static int upload_mat(bamd_model * m, const GgufTensor * t, DevMat & d, bool kee
                       void * stream_dst = nullptr) {
     if (t->ne.size() != 2) return fail("tensor " + t->name + ": expected 2 dims");
     d.type = t->type; d.K = (int) t->ne[0]; d.nrows = (int) t->ne[1]; d.bytes = t->nbytes;
-    if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K)");
+    if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL)");
     if (bamd_has_record(d.type) && d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     if (want_stream) {
         if (d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
@@ -230,6 +230,10 @@ static int upload_f32(bamd_model * m, const GgufTensor * t, float ** p, int n, h
 }
 
 static void build_prefill_aux(bamd_model * m, hipStream_t s);
+// The ONE attn_q | attn_k | attn_v whose matrices need two activation forms and that loads: the pair llama.cpp's IQ4_NL recipe writes.  llama_tensor_get_type
+// (src/llama.cpp:15544-15546) makes attn_v Q5_K wherever n_gqa >= 4 (Llama-3, Mistral, the 8B shape) while attn_q and attn_k stay IQ4_NL: Q8_0 activations
+// for the first two, Q8_K for the third.  The engine runs such a layer's QKV as one launch per form (qkv_groups); every other mix stays refused at load
+static bool qkv_recipe_mix(int tq, int tk, int tv) { return tq == BAMD_IQ4_NL && tk == BAMD_IQ4_NL && bamd_is_kquant(tv); }
 static int model_load_impl(bamd_model * m, const char * path, int device, int lf, int ll, int with_embd, int with_output) {
     // the file is read and its header validated before any device is touched: a bad file is reported as such on any machine
     m->file.reset(new GgufFile());
@@ -274,7 +278,7 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
     if (m->E % 256 || m->F % 256)
         return fail(m->E % 32 || m->F % 32 ? "n_embd and n_ff must be multiples of 256"
                                            : "n_embd and n_ff must be multiples of 256 (n_embd " + std::to_string(m->E) + ", n_ff " + std::to_string(m->F) +
-                                             ": a row length that is a multiple of 32 but not of 256 is a valid Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 tensor, but a wave-stream record holds 256 weights per row)");
+                                             ": a row length that is a multiple of 32 but not of 256 is a valid Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 tensor (or IQ4_NL one), but a wave-stream record holds 256 weights per row)");
     if (m->E > 32768 || m->F > 131072) return fail("n_embd / n_ff beyond what the kernels' LDS budgets were sized for");
     if (ll < 0 || ll > m->L) ll = m->L;
     if (lf < 0 || lf > ll) return fail("bad layer range");
@@ -344,9 +348,11 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
             if (ly.wg.type != ly.wu.type) { rc = fail("ffn_gate and ffn_up must share one quantisation type"); break; }
             // the fused QKV launch quantises its activations ONCE: Q8_K for K-quant segments, Q8_0 for Q4_0 / Q5_0 / Q8_0 ones, Q8_1 for Q4_1 / Q5_1 ones
             // (bamd_act_form_of).  No llama.cpp recipe mixes the
-            // families inside attn_q | attn_k | attn_v; a file that does is refused here rather than run with the wrong form
-            for (int j = 1; j < 3 && !rc; ++j)
-                if (bamd_act_form_of(mats[j].d->type) != bamd_act_form_of(mats[0].d->type))
+            // families inside attn_q | attn_k | attn_v; a file that does is refused here rather than run with the wrong form.  The one exception is the pair
+            // qkv_recipe_mix names, which the decode step and the batched prompt path run as one launch per form (qkv_groups).  IQ4_NL beside Q8_0 / Q4_0 / Q5_0
+            // (one form, but no recipe writes it either) is refused in the same words: what loads is what a recipe writes
+            for (int j = 1; j < 3 && !rc && !qkv_recipe_mix(ly.wq.type, ly.wk.type, ly.wv.type); ++j)
+                if (bamd_act_form_of(mats[j].d->type) != bamd_act_form_of(mats[0].d->type) || (mats[j].d->type == BAMD_IQ4_NL) != (mats[0].d->type == BAMD_IQ4_NL))
                     rc = fail(p + mats[0].n + ".weight (type " + std::to_string(mats[0].d->type) + ") and " + p + mats[j].n + ".weight (type " + std::to_string(mats[j].d->type) +
                               ") need different activation formats (" + (bamd_is_flt(mats[0].d->type) || bamd_is_flt(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1 / F32 / BF16" : bamd_is_q1(mats[0].d->type) || bamd_is_q1(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1" : "Q8_K / Q8_0") + ") in one fused launch: not supported");
             if (rc) break;
@@ -500,6 +506,17 @@ static int qkv_segments(const DevLayer & ly, float * out, bamd_mv_seg sg[3], int
     return n;
 }
 
+// A launch quantises its activations once, so consecutive QKV segments of one activation form (bamd_act_form_of) are ONE launch: group g is the segments
+// [first[g], first[g + 1]).  One group for every model but the one qkv_recipe_mix lets through the load; each launch normalises and quantises x for itself (the
+// same deterministic sum, the same bits) and writes its own slice of q | k | v.  The decode step and the batched prompt path both group here
+static int qkv_groups(const bamd_mv_seg * sg, int nseg, int first[4]) {
+    int n = 0;
+    for (int i = 0; i < nseg; ++i) if (!i || bamd_act_form_of(sg[i].type) != bamd_act_form_of(sg[i - 1].type)) first[n++] = i;
+    first[n] = nseg;
+    return n;
+}
+static int qkv_launches(const DevLayer & ly) { bamd_mv_seg sg[3]; int first[4]; return qkv_groups(sg, qkv_segments(ly, nullptr, sg), first); }
+
 // enqueue the layers of this stage for the token whose hidden state is in c->x; leaves the result in c->x
 // pos_hi: the highest position this enqueue (or every replay of the graph being captured) will see.  The single-launch attention
 // kernel (one workgroup per query head, serial over the sequence) wins below ~450 positions (measured crossover, 8B shape: 1.73 vs
@@ -517,12 +534,18 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
     for (size_t il = 0; il < m->layers.size(); ++il) {
         const DevLayer & ly = m->layers[il];
         bamd_mv_args a; memset(&a, 0, sizeof a);
-        // 1. q,k,v = W{q,k,v} . Q8_K(rms_norm(x) * attn_norm)          (llama.cpp:8810-8835)
-        a.nseg = qkv_segments(ly, c->q, a.seg);
-        a.x = c->x; a.normw = ly.attn_norm; a.eps = m->eps; a.K = m->E; a.tl = tl_next(c);
-        if (tm) tm->begin(s, 0, (double) (ly.wq.bytes + ly.wk.bytes + ly.wv.bytes));
-        if (bamd_launch_mv(a, BAMD_PRO_NORM, BAMD_EPI_STORE, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
-        if (tm) tm->end(s);
+        // 1. q,k,v = W{q,k,v} . Q8_K(rms_norm(x) * attn_norm)          (llama.cpp:8810-8835), one launch per activation form (qkv_groups)
+        bamd_mv_seg qs[3]; int gf[4];
+        const int ng = qkv_groups(qs, qkv_segments(ly, c->q, qs), gf);
+        for (int g = 0; g < ng; ++g) {
+            memset(&a, 0, sizeof a);
+            double bytes = 0.0;
+            for (int i = gf[g]; i < gf[g + 1]; ++i) { a.seg[a.nseg++] = qs[i]; bytes += (double) (bamd_row_bytes(qs[i].type, m->E) * (size_t) qs[i].nvalid); }
+            a.x = c->x; a.normw = ly.attn_norm; a.eps = m->eps; a.K = m->E; a.tl = tl_next(c);
+            if (tm) tm->begin(s, 0, bytes);
+            if (bamd_launch_mv(a, BAMD_PRO_NORM, BAMD_EPI_STORE, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
+            if (tm) tm->end(s);
+        }
         // 2. RoPE, KV store, softmax(QK^T) V                               (llama.cpp:8837-8849, :8318-8353)
         bamd_attn_args t; memset(&t, 0, sizeof t);
         t.st = c->st; t.q = c->q; t.k = c->k; t.v = c->v; t.kc = c->kc[il]; t.vc = c->vc[il]; t.rope = c->rope; t.rope_cur = c->rope_cur; t.scores = c->scores; t.probs = c->probs; t.out = c->att;
@@ -860,6 +883,7 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
         // (with every switch off the reasons read as they did before the switches existed; with one of BAMD_PREFILL_Q0 / BAMD_PREFILL_Q1 on, the one that is missing is named)
         m->aux_why = bamd_is_flt(it.type) && bamd_prefill_flt() ? "the model holds a BF16 matrix: these have no matrix-core kernel (BAMD_PREFILL_FLT covers F32 / F16 only), and side tables are all-or-nothing per model, so every prompt mat-mul of the other types runs on the VALU kernels"
                    : bamd_is_flt(it.type) ? "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels"
+                   : it.type == BAMD_IQ4_NL ? "the model holds an IQ4_NL matrix: these have no matrix-core kernel (BAMD_PREFILL_Q0 covers Q4_0 / Q5_0 / Q8_0 only), and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q1(it.type) && bamd_prefill_q0() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_Q0 covers only its Q4_0 / Q5_0 / Q8_0 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q0(it.type) && bamd_prefill_q1() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_Q1 covers only its Q4_1 / Q5_1 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
@@ -960,10 +984,16 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         bamd_mm_args a; memset(&a, 0, sizeof a);
         // q,k,v                                                            (llama.cpp:8810-8835)
         // (the activation form of each mat-mul follows its weights: Q8_0 blocks for Q4_0 / Q5_0 / Q8_0, Q8_1 blocks for Q4_1 / Q5_1, else Q8_K; the load refused a QKV launch that would need both)
-        bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wq.type));
-        a.nseg = qkv_segments(ly, c->bqkv, a.seg);
-        a.blob = c->bblob; a.K = E; a.T = T; a.ldo = ldq;
-        if (batch_mm(c, a, BAMD_EPI_STORE, s, ly.aux_qkv)) return fail("batched mat-mul: unsupported shape");
+        // (one quantisation and one mat-mul per activation form: qkv_groups)
+        bamd_mv_seg qs[3]; int gf[4];
+        const int ng = qkv_groups(qs, qkv_segments(ly, c->bqkv, qs), gf);
+        for (int g = 0; g < ng; ++g) {
+            bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(qs[gf[g]].type));
+            memset(&a, 0, sizeof a);
+            for (int i = gf[g]; i < gf[g + 1]; ++i) a.seg[a.nseg++] = qs[i];
+            a.blob = c->bblob; a.K = E; a.T = T; a.ldo = ldq;
+            if (batch_mm(c, a, BAMD_EPI_STORE, s, ly.aux_qkv + gf[g])) return fail("batched mat-mul: unsupported shape");
+        }
         // RoPE, KV store, attention with the T>1 semantics                  (llama.cpp:8837-8849, :8318-8353)
         bamd_attn_args t; memset(&t, 0, sizeof t);
         t.st = c->st; t.q = c->bqkv; t.k = c->bqkv + E; t.v = c->bqkv + E + Ekv; t.kc = c->kc[il]; t.vc = c->vc[il]; t.rope = c->rope; t.out = c->batt;
@@ -1385,15 +1415,16 @@ extern "C" __attribute__((visibility("default"))) int bamd_profile_step(bamd_con
 
 // Phase stamps of one decode step at position `pos` (BAMD_TIMING builds only): the step is captured into a hipGraph whose launches
 // carry their stamp blocks, replayed `replays` times back to back (each replay overwrites the stamps: the last one is read), and the
-// blocks are copied to `out` ([n_launches][BAMD_TL_SLOT_WORDS] u64, launch order: per layer qkv, attention, wo, gate/up, down; then
-// lm_head).  100 MHz device wall clock.  *n_launches receives the number of stamped launches.
+// blocks are copied to `out` ([n_launches][BAMD_TL_SLOT_WORDS] u64, launch order: per layer qkv (one launch per activation form: two in a layer whose
+// QKV mixes them, qkv_recipe_mix), attention, wo, gate/up, down; then lm_head).  100 MHz device wall clock.  *n_launches receives the number of stamped launches.
 extern "C" __attribute__((visibility("default"))) int bamd_timeline_step(bamd_context * c, int pos, int replays, unsigned long long * out, int cap_launches, int * n_launches) {
     bamd_model * m = c->m;
     if (!bamd_timing_enabled()) return fail("bamd_timeline_step: library built without -DBAMD_TIMING (use booster_amd/lib/libbooster_amd_timing.so)");
     if (!m->with_embd || !m->with_output) return fail("timeline needs a full single-stage model");
     HIPC(hipSetDevice(m->device));
     hipStream_t s = c->stream;
-    const int cap = (int) m->layers.size() * 5 + 1;
+    int cap = 1;
+    for (const DevLayer & ly : m->layers) cap += 4 + qkv_launches(ly);
     if (cap > cap_launches) return fail("bamd_timeline_step: output buffer too small");
     const size_t bytes = (size_t) cap * BAMD_TL_SLOT_WORDS * 8;
     OwnedDevMem mem;

@@ -76,9 +76,12 @@ void bamd_launch_repack(const void * raw, void * dst, int type, int nrows, int K
 void bamd_launch_quantize_q8k_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 [[nodiscard]] int bamd_launch_matvec(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);          // 1 = a segment's type has no kernel (nothing launched)
 // the same for launches whose segments are all of ONE family of the 32-weight block formats (bamd_matvec_b32.h): Q8_0 / Q4_0 / Q5_0 (Q8_0 activations) or
-// Q4_1 / Q5_1 (Q8_1 activations); the family of segment 0 decides, 1 = a segment of the other family; 2 = split-K (mode 2) was asked for Q4_1 / Q5_1, which do not have it
+// Q4_1 / Q5_1 (Q8_1 activations); the family of segment 0 decides, 1 = a segment of the other family; 2 = split-K (mode 2) was asked for Q4_1 / Q5_1, which do not have it.
+// IQ4_NL counts to the first family (Q8_0 activations): a launch with such a segment takes a kernel of its own, 2 = split-K was asked for in such a launch
 [[nodiscard]] int bamd_launch_matvec_b32(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
 [[nodiscard]] int bamd_launch_matvec_b32_q1(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);      // its Q4_1 / Q5_1 half (a code object per family: bamd_matvec_b32.h)
+// and the launches of the first family with at least one IQ4_NL segment (a third code object, bamd_matvec_b32_nl.hip); 2 = split-K (mode 2) was asked for: IQ4_NL has none
+[[nodiscard]] int bamd_launch_matvec_b32_nl(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s);
 // what the engine and the ops call: the family of the first segment picks the launcher, and each launcher refuses a segment of another family (a launch
 // quantises its activations once, as Q8_K, as Q8_0 or as Q8_1: bamd_act_form_of).  bamd_launch_matvec itself stays the K-quant launcher that tests/test_launch_selection.py pins, its
 // refusal of every other type included
@@ -92,7 +95,7 @@ void bamd_launch_act_batch_flt(int form, const float * x, const float * nw, floa
 int  bamd_launch_matmul_batch_flt(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);
 [[nodiscard]] static inline int bamd_launch_mv(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
     if (a.nseg > 0 && bamd_is_flt(a.seg[0].type)) return bamd_launch_matvec_flt(a, pro, epi, n_cu, s);
-    return a.nseg > 0 && (bamd_is_q0(a.seg[0].type) || bamd_is_q1(a.seg[0].type)) ? bamd_launch_matvec_b32(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
+    return a.nseg > 0 && (bamd_takes_q8_0(a.seg[0].type) || bamd_is_q1(a.seg[0].type)) ? bamd_launch_matvec_b32(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
 }
 void bamd_launch_quantize_q81_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 void bamd_launch_quantize_q80_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
@@ -118,6 +121,7 @@ static inline size_t bamd_act_blob_bytes(int form, int K) { const size_t f = bam
 // while the family's switch bamd_prefill_q0() / bamd_prefill_q1() is on (otherwise nothing reads it)
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K);
 void bamd_launch_quantize_batch_b32(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
+int  bamd_launch_matmul_batch_b32_nl(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);       // its launches with an IQ4_NL segment (bamd_prefill_b32_nl.hip); callers go through the next
 int  bamd_launch_matmul_batch_b32(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);          // every segment of the family of segment 0 (Q8_0 / Q4_0 / Q5_0, or Q4_1 / Q5_1), a.blob in its form; 1 = shape not supported
 // K-quant matrices on the matrix cores, exact (bamd_prefill2.hip): y[t][row] = W[row,:] . Q8_K(a_t); epi BAMD_EPI_STORE: out = y; BAMD_EPI_ADD: out = y + res;
 // BAMD_EPI_SILU_MUL: out = silu(res) * y (res = the gate projection, may alias out).  The A fragments are built once per 64-row x 64-token workgroup from the
@@ -136,7 +140,7 @@ int  bamd_prefill_q0(void);
 int  bamd_prefill_q1(void);
 static inline bool bamd_prefill_mfma_type(int type) {
     return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit()) || (bamd_is_q0(type) && bamd_prefill_q0()) ||
-           (bamd_is_q1(type) && bamd_prefill_q1());
+           (bamd_is_q1(type) && bamd_prefill_q1());      // IQ4_NL: none (bamd_is_q0 does not hold it)
 }
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);

@@ -10,7 +10,7 @@ __global__ void repack_kernel(const uint8_t * __restrict__ raw, uint8_t * __rest
     if (idx >= (int64_t) nrows * nb) return;
     const int row = (int) (idx / nb), i = (int) (idx % nb);
     const int rg = row >> 3, r = row & 7;
-    const int bb = bamd_block_bytes(type);
+    const int bb = bamd_block_bytes_repack(type);
     const uint8_t * src = raw + ((int64_t) row * nb + i) * bb;
     uint8_t * rec = dst + ((int64_t) rg * nb + i) * bamd_record_bytes_quant(type);      // (F32 / F16 / BF16: repack_flt_kernel, bamd_matvec_flt.hip)
     if (type == BAMD_Q4_K || type == BAMD_Q5_K) {
@@ -330,6 +330,7 @@ int bamd_timing_enabled(void) {
 }
 void bamd_launch_repack(const void * raw, void * dst, int type, int nrows, int K, hipStream_t s) {
     if (bamd_is_flt(type)) { bamd_launch_repack_flt(raw, dst, type, nrows, K, s); return; }      // kernel of its own (bamd_matvec_flt.hip)
+    if (type == BAMD_IQ4_NL) type = BAMD_Q4_0;                                                   // the same file block, the same record (bamd_formats.h)
     const int nb = K >> 8;
     const int64_t n = (int64_t) nrows * nb;
     BAMD_LAUNCH(repack_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, (const uint8_t *) raw, (uint8_t *) dst, type, nrows, nb);

@@ -3,9 +3,11 @@
 // measured slower than one wave per row-group for the whole Q8_0 family (profiles/legacy_matvec.txt), so the types with a minimum never got one, and a request
 // for it (mode 2) is refused by the caller in words.  The K-quant kernels (bamd_matvec.hip, bamd_matvec_fast_*.hip) are not touched by these types: a launch
 // whose segments are all of one of the two families comes here (bamd_launch_mv, bamd_kernels.h), every other launch goes where it went before.
-// ONE source, TWO translation units: bamd_matvec_b32_q0.hip instantiates the kernels of the family without a minimum, bamd_matvec_b32_q1.hip those of the other,
-// so each family keeps a code object of its own, as before the sources were one.  In one code object every instance was instruction for instruction what it had
-// been and the Q4_1 qkv launch (6144 x 4096, RMSNorm) still measured 9.55 -> 10.29 us (profiles/b32_unify.txt).
+// IQ4_NL (Q8_0 activations, the Q4_0 record, two accumulators per lane) has mode A only; a request for split-K is refused in words like the one for Q4_1 / Q5_1.
+// ONE source, THREE translation units: bamd_matvec_b32_q0.hip instantiates the kernels of the family without a minimum, bamd_matvec_b32_q1.hip those of the other,
+// so each family keeps a code object of its own, as before the sources were one; bamd_matvec_b32_nl.hip holds a third kernel whose type list is Q8_0 / Q4_0 / Q5_0
+// AND IQ4_NL, for the launches with at least one IQ4_NL segment (every other launch goes where it went before, its kernels instruction for instruction what they
+// were).  Why a code object each: with both families in one, every instance was instruction for instruction what it had been and the Q4_1 qkv launch (6144 x 4096, RMSNorm) still measured 9.55 -> 10.29 us (profiles/b32_unify.txt).
 //
 // Numerics, records and the chains: bamd_b32_device.h.
 #pragma once
@@ -52,7 +54,7 @@ __device__ __forceinline__ void b32_stream(const uint8_t * __restrict__ wA, cons
             const int after_off = (PAIR && part == 0) ? rowoff : rowoff + rg_step;
             float resv = 0.f;
             if (EPI == BAMD_EPI_ADD && row < nvalid) resv = ik_ld(res + row);
-            float acc = 0.f, summs = 0.f;
+            float acc = 0.f, acc2 = 0.f, summs = 0.f;        // (acc2: the odd blocks' accumulator of a type with two, b32_two_acc)
             for (int c = 0; c < chunks; ++c) {
                 const bool inrow = c + 1 < chunks;
                 const bool tail = !inrow && last;            // behind the wave's last chunk: the zero-record descriptor (returns 0, fetches nothing)
@@ -69,13 +71,14 @@ __device__ __forceinline__ void b32_stream(const uint8_t * __restrict__ wA, cons
                         b32_summs8(summs, ms);
                     } else {
                         b32_terms(ring[s], c * D + s, lane, L.q8, L.ys, sc, fd);
-                        b32_chain8(acc, sc, fd);
+                        if constexpr (b32_two_acc(TYPE)) b32_chain8(acc, acc2, sc, fd);
+                        else b32_chain8(acc, sc, fd);
                     }
                     load_rec(ring[s], nrs, nxt + s * RECB, lane);
                     if ((s & (BAMD_SCHED_GROUP - 1)) == BAMD_SCHED_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            const float val = b32_finish_row<MIN>(acc, summs);
+            const float val = b32_finish_row<MIN>(b32_two_acc(TYPE) ? acc + acc2 : acc, summs);
             if (PAIR) {
                 if (part == 0) gate_val = val;
                 else if ((lane & 7) == 0 && row < nvalid) ik_st(out + row, v_silu(gate_val) * val);
@@ -96,9 +99,18 @@ __device__ __forceinline__ void b32_stream_depth(const uint8_t * wA, const uint8
     else                    b32_stream<TYPE, 1, EPI, NORM>(wA, wB, nb, first, count, stride, out, res, a, L, do_pro, best, nvalid);
 }
 
-// MIN: the family of the launch.  The weight type is a run-time property of a segment; the family selects the type list
+// FAM: the type list of a launch (the weight type is a run-time property of a segment): without a minimum, with one, or the first with IQ4_NL beside it
+enum { B32_FAM_Q0 = 0, B32_FAM_Q1 = 1, B32_FAM_NL = 2 };
+// The translation unit names its mode A kernel and says whether the type list without a minimum holds IQ4_NL (bamd_matvec_b32_nl.hip: matvec_b32_nl_kernel, 1).
+// A macro, not a body shared by two kernels: inlined from a function of its own, the same statements compile to other instructions (the workgroup size is then
+// read the long way), and the kernels of the two earlier translation units are to stay what they are
+#ifndef BAMD_B32_MV_KERNEL
+#define BAMD_B32_MV_KERNEL matvec_b32_kernel
+#define BAMD_B32_MV_NL 0
+#endif
+// MIN: the family of the launch
 template <bool MIN, int PRO, int EPI>
-__global__ void __launch_bounds__(512) matvec_b32_kernel(bamd_mv_args a) {
+__global__ void __launch_bounds__(512) BAMD_B32_MV_KERNEL(bamd_mv_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool NORM = PRO == BAMD_PRO_NORM;
     const int nb = a.K >> 8;
@@ -130,6 +142,7 @@ __global__ void __launch_bounds__(512) matvec_b32_kernel(bamd_mv_args a) {
                 if (t == BAMD_Q8_0)      BAMD_B32_SEG(BAMD_Q8_0);
                 else if (t == BAMD_Q4_0) BAMD_B32_SEG(BAMD_Q4_0);
                 else if (t == BAMD_Q5_0) BAMD_B32_SEG(BAMD_Q5_0);
+                else if constexpr (BAMD_B32_MV_NL != 0) { if (t == BAMD_IQ4_NL) BAMD_B32_SEG(BAMD_IQ4_NL); else __builtin_trap(); }
                 else __builtin_trap();
             }
 #undef BAMD_B32_SEG
@@ -284,24 +297,26 @@ __global__ void __launch_bounds__(512) quantize_q8_test_kernel(const float * x, 
 }
 
 // ===========================================================================================================
-// launchers, instantiated once per family by the two .hip files
+// launchers, instantiated once per type list by the three .hip files
 // ===========================================================================================================
 template <bool Q1> void launch_quantize_q8_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s) {
     BAMD_LAUNCH(quantize_q8_test_kernel<Q1>, dim3(1), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, norm, (uint8_t *) out);
 }
 
-// every segment of the family MIN (1 = a segment of the other family, or of neither).  Mode A for every shape; split-K only on request (mode 2) and only
-// without a minimum: why, and what was measured, is in DESIGN.md section 3.  2 = split-K was asked for (mode 2) for Q4_1 / Q5_1, which have none
-template <bool MIN> int launch_matvec_b32(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
-    for (int i = 0; i < a.nseg; ++i) if (!(MIN ? bamd_is_q1(a.seg[i].type) : bamd_is_q0(a.seg[i].type))) return 1;
-    if (MIN && (a.mode & 15) == 2) return 2;
+// every segment of the type list FAM (1 = a segment of another list, or of none).  Mode A for every shape; split-K only on request (mode 2) and only
+// for Q8_0 / Q4_0 / Q5_0: why, and what was measured, is in DESIGN.md section 3.  2 = split-K was asked for (mode 2) for Q4_1 / Q5_1 or in a launch with IQ4_NL, which have none
+template <int FAM> int launch_matvec_b32(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
+    static_assert((FAM == B32_FAM_NL) == (BAMD_B32_MV_NL != 0), "the IQ4_NL type list is launched from the translation unit whose kernel has it");
+    constexpr bool MIN = FAM == B32_FAM_Q1;
+    for (int i = 0; i < a.nseg; ++i) if (!(MIN ? bamd_is_q1(a.seg[i].type) : FAM == B32_FAM_NL ? bamd_takes_q8_0(a.seg[i].type) : bamd_is_q0(a.seg[i].type))) return 1;
+    if (FAM != B32_FAM_Q0 && (a.mode & 15) == 2) return 2;
     int nrg = 0;
     if (epi == BAMD_EPI_SILU_MUL) nrg = a.seg[0].nrows >> 3;
     else for (int i = 0; i < a.nseg; ++i) nrg += a.seg[i].nrows >> 3;
     const int cus = n_cu > 0 ? n_cu : 256;
     const int grid = nrg < 1 ? 1 : nrg < cus ? nrg : cus;
     typedef consts<BAMD_PRO_NORM, BAMD_PRO_PLAIN> pros;
-    if constexpr (!MIN) {
+    if constexpr (FAM == B32_FAM_Q0) {
         const int nb = a.K >> 8;
         const bool can_split = (epi == BAMD_EPI_STORE || epi == BAMD_EPI_ADD) && q0_can_split(nb);
         const bool split = (a.mode & 15) == 2 && can_split;      // mode 2: split-K where the shape has it
@@ -309,5 +324,5 @@ template <bool MIN> int launch_matvec_b32(const bamd_mv_args & a, int pro, int e
             BAMD_LAUNCH((matvec_q0_split_kernel<decltype(P)::value, decltype(E)::value>), dim3(grid), dim3(512), q0_split_lds(nb), s, a); return true; }); }) ? 0 : 1;
     }
     return with_const(pros(), pro, [&](auto P) -> bool { return with_const(consts<BAMD_EPI_STORE, BAMD_EPI_ADD, BAMD_EPI_SILU_MUL, BAMD_EPI_ARGMAX>(), epi, [&](auto E) -> bool {
-        BAMD_LAUNCH((matvec_b32_kernel<MIN, decltype(P)::value, decltype(E)::value>), dim3(grid), dim3(512), act_lds_bytes(a.K), s, a); return true; }); }) ? 0 : 1;
+        BAMD_LAUNCH((BAMD_B32_MV_KERNEL<MIN, decltype(P)::value, decltype(E)::value>), dim3(grid), dim3(512), act_lds_bytes(a.K), s, a); return true; }); }) ? 0 : 1;
 }

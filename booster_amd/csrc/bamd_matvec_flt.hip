@@ -13,7 +13,7 @@
 
 // ---- repack: GGUF row-major -> records.  One thread per 16-byte request of a record ----
 __global__ void __launch_bounds__(256) repack_flt_kernel(const uint8_t * __restrict__ raw, uint8_t * __restrict__ dst, int type, int nrows, int K) {
-    const int recb = bamd_record_bytes(type), per = recb >> 4, nb = K >> 8;
+    const int recb = bamd_record_bytes_repack(type), per = recb >> 4, nb = K >> 8;
     const int64_t idx = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t total = (int64_t) ((nrows + 7) >> 3) * nb * per;
     if (idx >= total) return;

@@ -79,6 +79,7 @@ static int op_matvec(int type, const void * wA, const void * wB, int nrows, int 
     if (need_device()) return 1;
     if (!bamd_has_record(type) || k <= 0 || k % 256 || nrows <= 0) return fail("bad type/shape");
     if (bamd_is_q1(type) && (mode & 15) == 2) return fail("mat-vec: Q4_1 / Q5_1 have no split-K kernel (mode 2): one wave per row-group only");
+    if (type == BAMD_IQ4_NL && (mode & 15) == 2) return fail("mat-vec: IQ4_NL has no split-K kernel (mode 2): one wave per row-group only");
     if (bamd_is_flt(type) && k > bamd_flt_max_k(type)) return fail("mat-vec: row length beyond what the F32 / F16 / BF16 kernels hold in LDS");
     const int nrows_pad = (nrows + 7) / 8 * 8;
     Tmp t; const size_t wb = bamd_row_bytes(type, k) * (size_t) nrows, wbp = bamd_stream_bytes(type, k, nrows_pad);
@@ -508,8 +509,8 @@ struct TraceScope {                      // BAMD_LAUNCH records into `rec` while
     TraceScope() : prev(bamd_aql_rec) { bamd_aql_rec = &rec; }
     ~TraceScope() { bamd_aql_rec = prev; }
 };
-extern "C" __attribute__((visibility("default"))) int bamd_trace_matvec(int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu,
-                                                                          bamd_launch_trace * out) {
+// any: through bamd_launch_mv, what the engine and the ops call (every family of types); else bamd_launch_matvec itself, the K-quant launcher
+static int trace_mv(bool any, int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu, bamd_launch_trace * out) {
     if (nseg < 1 || nseg > 3 || k <= 0 || k % 256 || !out) return fail("launch trace: bad segment count / row length"), 2;
     if ((pro != BAMD_PRO_PLAIN && pro != BAMD_PRO_NORM) || epi < BAMD_EPI_STORE || epi > BAMD_EPI_ARGMAX) return fail("launch trace: bad prologue / epilogue"), 2;
     bamd_mv_args a; memset(&a, 0, sizeof a);
@@ -526,8 +527,16 @@ extern "C" __attribute__((visibility("default"))) int bamd_trace_matvec(int nseg
     if (epi == BAMD_EPI_ADD) a.res = fake_ptr<float>(5);
     if (epi == BAMD_EPI_ARGMAX) a.best_key = fake_ptr<unsigned long long>(6);
     TraceScope ts;
-    if (bamd_launch_matvec(a, pro, epi, n_cu, nullptr)) return 1;
+    if (any ? bamd_launch_mv(a, pro, epi, n_cu, nullptr) : bamd_launch_matvec(a, pro, epi, n_cu, nullptr)) return 1;
     return trace_result(ts.rec, out);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_trace_matvec(int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu,
+                                                                          bamd_launch_trace * out) {
+    return trace_mv(false, nseg, types, rows, k, pro, epi, mode, n_cu, out);
+}
+extern "C" __attribute__((visibility("default"))) int bamd_trace_mv(int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu,
+                                                                      bamd_launch_trace * out) {
+    return trace_mv(true, nseg, types, rows, k, pro, epi, mode, n_cu, out);
 }
 extern "C" __attribute__((visibility("default"))) int bamd_trace_attn_wo(int H, int Hkv, int hd, int n_ctx, int lds_ld, int with_cellpos, int wo_type, int wo_rows, int k,
                                                                            int n_cu, int il, bamd_launch_trace * out) {
@@ -567,7 +576,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
         if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; }
         else if (type == BAMD_Q3_K) { p[108] = 0x00; p[109] = 0x1c; }
         else if (type == BAMD_Q2_K) { p[80] = 0; p[81] = 0x1c; p[82] = 0; p[83] = 0x1c; }
-        else if (bamd_is_q0(type)) { p[0] = 0; p[1] = 0x1c; }
+        else if (bamd_takes_q8_0(type)) { p[0] = 0; p[1] = 0x1c; }
         else if (bamd_is_q1(type)) { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
         else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
     }

@@ -26,14 +26,17 @@ GGML_TYPES = {
     12: (256, 144),   # Q4_K
     13: (256, 176),   # Q5_K
     14: (256, 210),   # Q6_K
+    20: (32, 18),     # IQ4_NL
     30: (1, 2),       # BF16
 }
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
 Q2_K, Q3_K = 10, 11
 Q4_0, Q5_0, Q8_0 = 2, 6, 8
 Q4_1, Q5_1 = 3, 7
+IQ4_NL = 20
 BF16 = 30
-TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 30: "BF16"}
+FTYPE_MOSTLY_IQ4_NL = 25      # general.file_type of a file written under iq4_nl_type (LLAMA_FTYPE_MOSTLY_IQ4_NL)
+TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 20: "IQ4_NL", 30: "BF16"}
 
 # gguf KV value types
 T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I64, T_F64 = range(13)
@@ -202,6 +205,8 @@ def random_kquant_tensor(ttype, row_len, n_rows, rng, amp=1.0):
         return random_q0_tensor(ttype, row_len, n_rows, rng, amp)
     if ttype in (Q4_1, Q5_1):
         return random_q1_tensor(ttype, row_len, n_rows, rng, amp)
+    if ttype == IQ4_NL:
+        return random_iq4_nl_tensor(row_len, n_rows, rng, amp)
     be, bb = GGML_TYPES[ttype]
     nblk = n_rows * (row_len // be)
     blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
@@ -238,6 +243,18 @@ def random_q0_tensor(ttype, row_len, n_rows, rng, amp=1.0):
     nblk = n_rows * (row_len // be)
     blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
     rms = {Q4_0: 4.6, Q5_0: 9.2, Q8_0: 74.0}[ttype]               # of nibble - 8, 5 bits - 16, int8, drawn uniformly
+    d = (amp / np.sqrt(row_len) / rms) * rng.uniform(0.5, 1.5, size=nblk)
+    blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    return blk.reshape(-1)
+
+
+def random_iq4_nl_tensor(row_len, n_rows, rng, amp=1.0):
+    """Random raw IQ4_NL blocks for an [n_rows, row_len] matrix: every nibble pattern in qs, finite positive f16 scales sized so that the dequantised values
+    (d * kvalues_iq4nl[nibble]) have standard deviation ~ amp / sqrt(row_len)."""
+    be, bb = GGML_TYPES[IQ4_NL]
+    nblk = n_rows * (row_len // be)
+    blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
+    rms = 67.4                                                   # of the sixteen table values -127 .. 113, drawn uniformly
     d = (amp / np.sqrt(row_len) / rms) * rng.uniform(0.5, 1.5, size=nblk)
     blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
     return blk.reshape(-1)
@@ -328,6 +345,20 @@ def q5_0_imatrix_type(name, il, n_layer):
     return Q5_1 if name == "ffn_down" and il < n_layer // 8 else q5_0_type(name, il, n_layer)
 
 
+def iq4_nl_type(name, il, n_layer, n_gqa=4, imatrix=False):
+    """llama.cpp's IQ4_NL recipe for the Llama architecture (llama_tensor_get_type): attn_v Q5_K where n_gqa >= 4 (llama.cpp:15544-15546), else IQ4_NL;
+    ffn_down Q5_K in the layers il < n_layer / 8 unless the file was made with an importance matrix (:15611-15613); output.weight Q6_K; everything
+    else — attn_q, attn_k, attn_output, ffn_gate, ffn_up, token_embd — IQ4_NL.  (A tied embedding is written as the output matrix: Q6_K, embd_type of
+    write_synthetic_llama.)"""
+    if name == "output":
+        return Q6_K
+    if name == "attn_v":
+        return Q5_K if n_gqa >= 4 else IQ4_NL
+    if name == "ffn_down":
+        return Q5_K if il < n_layer // 8 and not imatrix else IQ4_NL
+    return IQ4_NL
+
+
 def q4_k_m_type(name, il, n_layer):
     """Tensor type under llama.cpp's Q4_K_M recipe for the tensors we use (reference: llama.cpp:15442-15444,
     :15547-15555, :15603-15610, use_more_bits :15466-15480; SURVEY §8 header)."""
@@ -374,12 +405,13 @@ def q2_k_type(name, il, n_layer, n_gqa=4):
 
 
 def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_ctx_train=8192, seed=7,
-                          type_fn=None, rope_freqs=False, embd_type=Q4_K, reuse_layers=False, vocab=None, n_split=0, rope_scaling=None, tied=False):
-    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0) blocks, or unquantised F32 / F16 / BF16 matrices
+                          type_fn=None, rope_freqs=False, embd_type=Q4_K, reuse_layers=False, vocab=None, n_split=0, rope_scaling=None, tied=False, file_type=None):
+    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / IQ4_NL) blocks, or unquantised F32 / F16 / BF16 matrices
     (embd_type may be one of those too).
     reuse_layers: generate each (tensor kind, type) once and reuse the bytes in every layer (fast path for the
     multi-GB benchmark model; the arithmetic and the bytes streamed per token are unchanged).
-    tied: no output.weight — the reader falls back to token_embd.weight (Llama-3.2; llama.cpp:6070-6076)."""
+    tied: no output.weight — the reader falls back to token_embd.weight (Llama-3.2; llama.cpp:6070-6076).
+    file_type: general.file_type (the LLAMA_FTYPE of the recipe, e.g. FTYPE_MOSTLY_IQ4_NL); None writes no such key, as before."""
     rng = np.random.default_rng(seed)
     _cache = {}
 
@@ -402,7 +434,7 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
             bb = GGML_TYPES[t][1]; n = min(64, rows)
             return ([(k * rows // n) * cols * bb + (k % 32) * bb for k in range(n)], il + 1)
         be, bb = GGML_TYPES[t]; nb = cols // be
-        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32, Q4_0: 2, Q5_0: 6, Q8_0: 2, Q4_1: 4, Q5_1: 8}[t]      # qs / qs / ql / qs / qs / qs / qs / qs / qs / qs
+        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32, Q4_0: 2, Q5_0: 6, Q8_0: 2, Q4_1: 4, Q5_1: 8, IQ4_NL: 2}[t]      # qs / qs / ql / qs / qs / qs / qs / qs / qs / qs / qs
         n = min(64, rows)
         return ([(k * rows // n) * nb * bb + qoff + (k % 32) for k in range(n)], il + 1)
 
@@ -411,6 +443,8 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
     w = GGUFWriter()
     w.add_str("general.architecture", "llama")
     w.add_str("general.name", "booster-amd-synthetic")
+    if file_type is not None:
+        w.add_u32("general.file_type", int(file_type))
     w.add_u32("llama.context_length", n_ctx_train)
     w.add_u32("llama.embedding_length", E)
     w.add_u32("llama.block_count", L)

@@ -20,7 +20,7 @@ typedef struct bamd_model   bamd_model;
 typedef struct bamd_context bamd_context;
 
 /* ggml tensor type ids, as stored in GGUF (cpp/ggml/include/ggml.h:360-375) */
-enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q2_K = 10, BAMD_TYPE_Q3_K = 11, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14, BAMD_TYPE_BF16 = 30 };
+enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q2_K = 10, BAMD_TYPE_Q3_K = 11, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14, BAMD_TYPE_IQ4_NL = 20, BAMD_TYPE_BF16 = 30 };
 
 const char * bamd_last_error(void);
 
@@ -214,7 +214,7 @@ void bamd_set_prefill_q1(int on);
  * weights and the f32 activation rows as they are, there is no side table (bamd_model_prefill_aux_bytes stays 0 for such a model), so it takes effect for models and
  * contexts that exist already.  BF16 weights stay on the VALU kernel either way (their chain is a multiply and an add, not an fma).  Bit-identical results. */
 void bamd_set_prefill_flt(int on);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K) since the library was loaded */
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K; 20 IQ4_NL has no such kernel: always 0) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
@@ -325,6 +325,8 @@ typedef struct bamd_launch_trace {
 /* bamd_launch_matvec: nseg (1..3) segments of types[i] / rows[i]; pro 0 plain, 1 RMSNorm; epi 0 store, 1 residual add, 2 silu(gate) * up (two segments, one
  * output), 3 arg-max; mode as bamd_op_fused_qkv */
 int bamd_trace_matvec(int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu, bamd_launch_trace * out);
+/* the same through the dispatch the engine uses, which serves every family of weight types (the one above is the K-quant launcher alone) */
+int bamd_trace_mv(int nseg, const int32_t * types, const int32_t * rows, int k, int pro, int epi, int mode, int n_cu, bamd_launch_trace * out);
 /* bamd_launch_attn_wo: the attention block of a decode layer (n_ctx: padded; with_cellpos != 0: a cell-position table is set) and the wo launch behind it
  * (one segment [wo_rows][k], residual add, mode 0) */
 int bamd_trace_attn_wo(int H, int Hkv, int hd, int n_ctx, int lds_ld, int with_cellpos, int wo_type, int wo_rows, int k, int n_cu, int il, bamd_launch_trace * out);

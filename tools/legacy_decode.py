@@ -11,6 +11,13 @@ lines alternate set_prefill_q1(False) / (True) like the lines above, and two mor
 four layers is Q4_1): once with both switches on against both off, once with only set_prefill_q0(True) — no side tables, so it must read like switched off.
 
     python tools/legacy_decode.py --legacy1 [--prompt 2048] [--only-prompt]
+
+--iq4nl: the IQ4_NL recipe (full depth, synthetic files of tests/golden/gen_iq4nl_fixtures.py's writer) beside Q4_0 and Q4_K_M: the 8B shape as the recipe
+writes it (n_gqa 4: Q5_K attn_v, so the QKV of a layer is two launches, six launches per layer) and a uniform-QKV variant of the same shape (attn_v IQ4_NL like
+attn_q / attn_k: one QKV launch) — the difference between the two is what the second QKV launch costs per token.  The prompt rate is the integer-dot kernel's:
+the type has no matrix-core kernel.
+
+    python tools/legacy_decode.py --iq4nl [--prompt 2048]
 """
 import importlib.util
 import os
@@ -97,9 +104,39 @@ def main_legacy1():
         print_pair("Q4_0 imatrix, BAMD_PREFILL_Q0 only", n, *prompt_pair(p, n, q0=True, q1=False, tables=False))
 
 
+def main_iq4nl():
+    _s = importlib.util.spec_from_file_location("gen_iq4nl_fixtures", os.path.join(ROOT, "tests", "golden", "gen_iq4nl_fixtures.py"))
+    gn = importlib.util.module_from_spec(_s)
+    _s.loader.exec_module(gn)
+    gn.CONFIGS["8b_iq4nl"] = (gen.L3_8B, dict(imatrix=False), False, 128, 64, 512)                  # models only: no fixture of them is stored
+    uniform = os.path.join("/dev/shm", "bamd_fx_iq4nl_8b_iq4nl_uniform.gguf")                      # the recipe at n_gqa 1 on the same shape: attn_v IQ4_NL
+    if not os.path.exists(uniform + ".done"):
+        L = gen.L3_8B["L"]
+        fn = lambda name, il: gguf.iq4_nl_type(name, il, L, n_gqa=1)
+        gguf.write_synthetic_llama(uniform, seed=7, reuse_layers=True, type_fn=fn, embd_type=gguf.IQ4_NL, file_type=gguf.FTYPE_MOSTLY_IQ4_NL, **gen.L3_8B)
+        open(uniform + ".done", "w").write("ok")
+    files = [("Q4_K_M", q4_k_m_file()), ("Q4_0", gen.ensure_model("8b_q4_0")), ("IQ4_NL", gn.ensure_model("8b_iq4nl")), ("IQ4_NL uniform QKV", uniform)]
+    med = {}
+    for name, p in files:
+        r = decode_rate(p)
+        med[name] = statistics.median(r)
+        print("decode %-18s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, med[name], min(r), max(r)), flush=True)
+    two, one = 1e6 / med["IQ4_NL"], 1e6 / med["IQ4_NL uniform QKV"]
+    print("second QKV launch: %.1f us per token at six launches per layer against %.1f us at five = %.2f us per layer (32 layers; the Q5_K attn_v is also %.1f %% more bytes than an IQ4_NL one)"
+          % (two, one, (two - one) / 32, 100.0 * (176 / 256 - 18 / 32) / (18 / 32)), flush=True)
+    if "--prompt" in sys.argv:
+        n = int(sys.argv[sys.argv.index("--prompt") + 1])
+        for name, p in files:
+            r, aux = prompt_rate(p, n, reps=5)
+            print("prompt %-18s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
+                  "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+
+
 def main():
     if "--legacy1" in sys.argv:
         return main_legacy1()
+    if "--iq4nl" in sys.argv:
+        return main_iq4nl()
     files = [("Q4_K_M", q4_k_m_file()), ("Q8_0", gen.ensure_model("8b_q8_0")), ("Q4_0", gen.ensure_model("8b_q4_0")), ("Q5_0", gen.ensure_model("8b_q5_0"))]
     for name, p in [] if "--only-prompt" in sys.argv else files:
         r = decode_rate(p)
