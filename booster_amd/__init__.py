@@ -61,6 +61,7 @@ def lib():
         L.bamd_set_prefill_lowbit.argtypes = [ci]; L.bamd_set_prefill_lowbit.restype = None
         L.bamd_set_prefill_q0.argtypes = [ci]; L.bamd_set_prefill_q0.restype = None
         L.bamd_set_prefill_q1.argtypes = [ci]; L.bamd_set_prefill_q1.restype = None
+        L.bamd_set_prefill_nl.argtypes = [ci]; L.bamd_set_prefill_nl.restype = None
         L.bamd_set_prefill_flt.argtypes = [ci]; L.bamd_set_prefill_flt.restype = None
         L.bamd_set_attn_scratch_mb.argtypes = [ci]; L.bamd_set_attn_scratch_mb.restype = None
         L.bamd_attention_batch_plan.argtypes = [ci, ci, ci, ci, ci, ci, C.c_size_t, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
@@ -127,6 +128,13 @@ def set_prefill_q1(on):
     False (default, also env BAMD_PREFILL_Q1): such a model evaluates prompts on the integer-dot kernel.  Independent of set_prefill_q0: a Q4_0 / Q5_0 file made
     with an importance matrix holds Q4_1 / Q5_1 ffn_down matrices and needs both switches on to get tables.  Same bits either way."""
     lib().bamd_set_prefill_q1(int(bool(on)))
+
+
+def set_prefill_nl(on):
+    """True: models loaded from now on build side tables for their IQ4_NL layer matrices and evaluate prompts on the matrix-core kernel of the type; False
+    (default, also env BAMD_PREFILL_NL): such a model evaluates prompts on the integer-dot kernel.  Independent of the other switches: a model that also holds
+    a Q8_0 / Q4_0 / Q5_0 or Q4_1 / Q5_1 layer matrix needs that family's switch as well to get tables.  Same bits either way."""
+    lib().bamd_set_prefill_nl(int(bool(on)))
 
 
 def set_prefill_flt(on):

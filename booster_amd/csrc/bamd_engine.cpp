@@ -880,12 +880,14 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     if (n_all && items.empty()) { m->aux_none_needed = true; return; }
     size_t need = 0;
     for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
-        // (with every switch off the reasons read as they did before the switches existed; with one of BAMD_PREFILL_Q0 / BAMD_PREFILL_Q1 on, the one that is missing is named)
+        // (with every switch off the reasons read as they did before the switches existed; with one of BAMD_PREFILL_Q0 / BAMD_PREFILL_Q1 / BAMD_PREFILL_NL on, the one that is missing is named)
         m->aux_why = bamd_is_flt(it.type) && bamd_prefill_flt() ? "the model holds a BF16 matrix: these have no matrix-core kernel (BAMD_PREFILL_FLT covers F32 / F16 only), and side tables are all-or-nothing per model, so every prompt mat-mul of the other types runs on the VALU kernels"
                    : bamd_is_flt(it.type) ? "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels"
-                   : it.type == BAMD_IQ4_NL ? "the model holds an IQ4_NL matrix: these have no matrix-core kernel (BAMD_PREFILL_Q0 covers Q4_0 / Q5_0 / Q8_0 only), and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                   : it.type == BAMD_IQ4_NL ? "the model holds an IQ4_NL matrix: these have no matrix-core kernel (BAMD_PREFILL_Q0 covers Q4_0 / Q5_0 / Q8_0 only), and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840); BAMD_PREFILL_NL, the switch of the IQ4_NL matrix-core kernel, is off"
                    : bamd_is_q1(it.type) && bamd_prefill_q0() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_Q0 covers only its Q4_0 / Q5_0 / Q8_0 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q0(it.type) && bamd_prefill_q1() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_Q1 covers only its Q4_1 / Q5_1 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                   : bamd_is_q1(it.type) && bamd_prefill_nl() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_NL covers only its IQ4_NL matrices): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
+                   : bamd_is_q0(it.type) && bamd_prefill_nl() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_NL covers only its IQ4_NL matrices): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_q0(it.type) ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
                    : bamd_is_kquant(it.type) && !bamd_prefill_mfma_type(it.type) ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"

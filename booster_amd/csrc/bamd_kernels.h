@@ -118,7 +118,8 @@ static inline size_t bamd_act_blob_bytes(int form, int K) { const size_t f = bam
 // blob: int8 activations for matmul_batch_kernel (may be null); blob16: f16 copy for the MFMA kernel (may be null)
 // form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_0 for Q8_0 / Q4_0 / Q5_0 weights, BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_0 / Q8_1 form
 // of the same size (bamd_prefill_b32.hip); blob16 is written, in the f16 form of bamd_prefill2_b32.hip (544 / 576 bytes of a record, the same per-token stride), only
-// while the family's switch bamd_prefill_q0() / bamd_prefill_q1() is on (otherwise nothing reads it)
+// while the family's switch bamd_prefill_q0() / bamd_prefill_q1() is on (otherwise nothing reads it); the Q8_0 form also while bamd_prefill_nl() is on (IQ4_NL weights
+// take the same records)
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K);
 void bamd_launch_quantize_batch_b32(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
 int  bamd_launch_matmul_batch_b32_nl(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);       // its launches with an IQ4_NL segment (bamd_prefill_b32_nl.hip); callers go through the next
@@ -137,20 +138,27 @@ int  bamd_prefill_mfma_supported(void);      // the current device accepts the k
 // matrices in their first layers: such a file needs BOTH switches on to get tables; with one of them it runs on the integer-dot kernel like with none
 int  bamd_prefill_lowbit(void);
 int  bamd_prefill_q0(void);
+// IQ4_NL (bamd_prefill2_b32_nl.hip: the Q4_0 record and side table, a kernel of its own with two accumulator sets) is behind a fourth switch of that shape,
+// bamd_prefill_nl() (BAMD_PREFILL_NL=1 / bamd_set_prefill_nl; default off), independent of the others.  bamd_is_q0 does not hold the type (split-K asks it): where
+// the question is "a 32-weight block type with a side table of that family", ask bamd_is_q0 || bamd_is_q1 || IQ4_NL
 int  bamd_prefill_q1(void);
+int  bamd_prefill_nl(void);
 static inline bool bamd_prefill_mfma_type(int type) {
     return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit()) || (bamd_is_q0(type) && bamd_prefill_q0()) ||
-           (bamd_is_q1(type) && bamd_prefill_q1());      // IQ4_NL: none (bamd_is_q0 does not hold it)
+           (bamd_is_q1(type) && bamd_prefill_q1()) || (type == BAMD_IQ4_NL && bamd_prefill_nl());
 }
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                               int epi, int ldo, hipStream_t s);
-// the side of the three entry points above for the 32-weight block formats, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 (bamd_prefill2_b32.hip); callers go through those
+// the side of the three entry points above for the 32-weight block formats, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 (bamd_prefill2_b32.hip) and IQ4_NL (the Q4_0 table; its
+// kernel: bamd_prefill2_b32_nl.hip, reached through bamd_launch_matmul_mfma_b32); callers go through those
 size_t bamd_prefill_aux_bytes_b32(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                                  int epi, int ldo, hipStream_t s);
+int  bamd_launch_matmul_mfma_b32_nl(const void * w_stream, const void * aux, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res, int epi,
+                                    int ldo, hipStream_t s);
 // F32 / F16 matrices on the matrix cores, exact (bamd_prefill2_flt.hip), behind a switch of their own, bamd_prefill_flt() (BAMD_PREFILL_FLT=1 / bamd_set_prefill_flt; default
 // off).  Unlike the switches above it is read at each launch, not at model load: the kernel reads the resident weight stream and the f32 activation rows of
 // bamd_launch_act_batch_flt (blob) as they are, there is no side table to build.  BF16 has no such kernel.  Epilogues as bamd_launch_matmul_mfma2; 1 = type / shape

@@ -204,7 +204,7 @@ size_t bamd_blob16_bytes(int K) { return BAMD_BLOB16_BYTES(K >> 8); }
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form) {
     if (form == BAMD_ACT_F32 || form == BAMD_ACT_BF16) { bamd_launch_act_batch_flt(form, x, nw, eps, K, T, blob, s); return; }
     if (form == BAMD_ACT_Q8_1) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_q1() ? blob16 : nullptr); return; }
-    if (form == BAMD_ACT_Q8_0) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_q0() ? blob16 : nullptr); return; }
+    if (form == BAMD_ACT_Q8_0) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_q0() || bamd_prefill_nl() ? blob16 : nullptr); return; }
     if (nw) hipLaunchKernelGGL((quantize_batch_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
     else    hipLaunchKernelGGL((quantize_batch_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
 }

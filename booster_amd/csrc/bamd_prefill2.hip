@@ -731,15 +731,19 @@ static int g_prefill_lowbit = [] { const char * e = getenv("BAMD_PREFILL_LOWBIT"
 static int g_prefill_q0 = [] { const char * e = getenv("BAMD_PREFILL_Q0"); return (e && e[0] == '1') ? 1 : 0; }();
 // and for its Q4_1 / Q5_1 instances (default off: BAMD_PREFILL_Q1=1 or bamd_set_prefill_q1); independent of the one above
 static int g_prefill_q1 = [] { const char * e = getenv("BAMD_PREFILL_Q1"); return (e && e[0] == '1') ? 1 : 0; }();
-static long long g_mfma_runs[16] = { 0 };
+// and for the IQ4_NL kernel of bamd_prefill2_b32_nl.hip (default off: BAMD_PREFILL_NL=1 or bamd_set_prefill_nl); independent of the others
+static int g_prefill_nl = [] { const char * e = getenv("BAMD_PREFILL_NL"); return (e && e[0] == '1') ? 1 : 0; }();
+static long long g_mfma_runs[32] = { 0 };                  // by bamd_type (IQ4_NL = 20, BF16 = 30)
 int bamd_prefill_lowbit(void) { return g_prefill_lowbit; }
 int bamd_prefill_q0(void) { return g_prefill_q0; }
 int bamd_prefill_q1(void) { return g_prefill_q1; }
+int bamd_prefill_nl(void) { return g_prefill_nl; }
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_lowbit(int on) { g_prefill_lowbit = on ? 1 : 0; }
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_q0(int on) { g_prefill_q0 = on ? 1 : 0; }
 extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_q1(int on) { g_prefill_q1 = on ? 1 : 0; }
-extern "C" __attribute__((visibility("default"))) long long bamd_prefill_mfma_runs(int type) { return type >= 0 && type < 16 ? g_mfma_runs[type] : 0; }
-void bamd_prefill_mfma_count(int type) { if (type >= 0 && type < 16) g_mfma_runs[type] += 1; }      // the F32 / F16 launcher's (bamd_prefill2_flt.hip)
+extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_nl(int on) { g_prefill_nl = on ? 1 : 0; }
+extern "C" __attribute__((visibility("default"))) long long bamd_prefill_mfma_runs(int type) { return type >= 0 && type < 32 ? g_mfma_runs[type] : 0; }
+void bamd_prefill_mfma_count(int type) { if (type >= 0 && type < 32) g_mfma_runs[type] += 1; }      // the F32 / F16 launcher's (bamd_prefill2_flt.hip)
 static inline bool x_lowbit(int type) { return type == BAMD_Q3_K || type == BAMD_Q2_K; }
 // builder / consumer part of a (row block, super-block) in the side table, and the super-blocks of slack behind each part (the sixteen-wave kernel's last
 // two staging calls read past the end of K; the eight-wave kernels clamp)
@@ -750,11 +754,11 @@ static inline size_t x_ph_bytes(int type, int nrows_pad, int K) { return ((size_
 // bytes of the side table of a K-quant matrix [nrows_pad][K]: builder part first, the consumer part behind it (both 16-byte aligned)
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K) {
     if (!bamd_prefill_mfma_type(type) || (K & 255) || (nrows_pad & 7)) return 0;
-    if (bamd_is_q0(type) || bamd_is_q1(type)) return bamd_prefill_aux_bytes_b32(type, nrows_pad, K);
+    if (bamd_is_q0(type) || bamd_is_q1(type) || type == BAMD_IQ4_NL) return bamd_prefill_aux_bytes_b32(type, nrows_pad, K);
     return x_ph_bytes(type, nrows_pad, K) + ((size_t) x_row_blocks(nrows_pad) * (size_t) (K >> 8) + x_slack(type)) * x_ch_sb(type);
 }
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s) {
-    if (bamd_is_q0(type) || bamd_is_q1(type)) { bamd_launch_prefill_aux_b32(w_stream, type, nrows_pad, K, aux, s); return; }
+    if (bamd_is_q0(type) || bamd_is_q1(type) || type == BAMD_IQ4_NL) { bamd_launch_prefill_aux_b32(w_stream, type, nrows_pad, K, aux, s); return; }
     const int nb = K >> 8, nrt = x_row_blocks(nrows_pad) * 4;
     uint8_t * ph = (uint8_t *) aux, * ch = ph + x_ph_bytes(type, nrows_pad, K);
     const dim3 grid(nb, nrt);
@@ -781,7 +785,7 @@ int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, 
     if (!bamd_prefill_mfma_type(type) || (nrows_pad & 7) || (K & 255) || !aux) return 1;
     if (epi != BAMD_EPI_STORE && epi != BAMD_EPI_ADD && epi != BAMD_EPI_SILU_MUL) return 1;
     if ((epi != BAMD_EPI_STORE) != (res != nullptr)) return 1;
-    if (bamd_is_q0(type) || bamd_is_q1(type)) {                // bamd_prefill2_b32.hip; static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
+    if (bamd_is_q0(type) || bamd_is_q1(type) || type == BAMD_IQ4_NL) {                // bamd_prefill2_b32.hip / _nl.hip; static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
         if (bamd_launch_matmul_mfma_b32(w_stream, aux, type, nrows, nrows_pad, K, blob16, T, out, res, epi, ldo, s)) return 1;
         g_mfma_runs[type] += 1;
         return 0;

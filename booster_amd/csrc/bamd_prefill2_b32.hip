@@ -1,6 +1,8 @@
 // bamd_prefill2_b32.hip — the exact matrix-core prompt mat-mul for the 32-weight block formats: Q8_0 / Q4_0 / Q5_0 weights x Q8_0 activations behind the switch
 // BAMD_PREFILL_Q0 / bamd_set_prefill_q0, Q4_1 / Q5_1 weights x Q8_1 activations behind BAMD_PREFILL_Q1 / bamd_set_prefill_q1 (both default off; the list of types
 // is bamd_prefill_mfma_type, bamd_kernels.h).  One kernel template for the five types; MIN = b32_has_min(TYPE) marks what the types with a minimum add.
+// (IQ4_NL, the sixth type of the family, has a sibling kernel in bamd_prefill2_b32_nl.hip — two accumulator sets per output, another tile — behind BAMD_PREFILL_NL;
+// this file's launchers route the type there and write its side table with the Q4_0 instance of prefill_aux_b32_kernel.)
 //
 // Arithmetic: the contract of bamd_b32_device.h.  One output = eight f32 chains e = 0..7 over the 32-weight blocks l in order,
 //     acc_e = fma(f32(d_w) * f32(d_x), (float) dot4_e, acc_e),         dot4_e = the signed dot of bytes 4e .. 4e+3 of weight block and activation block,
@@ -256,13 +258,16 @@ typedef consts<BAMD_Q8_0, BAMD_Q4_0, BAMD_Q5_0, BAMD_Q4_1, BAMD_Q5_1> b32_types;
 size_t bamd_prefill_aux_bytes_b32(int type, int nrows_pad, int K) { return (size_t) (nrows_pad >> 3) * (size_t) (K >> 8) * (bamd_is_q1(type) ? 512 : 256); }
 void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s) {
     const dim3 grid(K >> 8, nrows_pad >> 3);
+    if (type == BAMD_IQ4_NL) type = BAMD_Q4_0;                 // the record is the Q4_0 record: the same table at the same offsets
     with_const(b32_types(), type, [&](auto T) -> bool {
         hipLaunchKernelGGL((prefill_aux_b32_kernel<decltype(T)::value>), grid, dim3(b32_has_min(decltype(T)::value) ? 128 : 64), 0, s, (const uint8_t *) w_stream, K >> 8, (float *) aux);
         return true; });
 }
-// the launch interface of bamd_launch_matmul_mfma2, which checks the arguments and routes the five types here
+// the launch interface of bamd_launch_matmul_mfma2, which checks the arguments and routes the five types and IQ4_NL here; IQ4_NL has a kernel of its own
+// (bamd_prefill2_b32_nl.hip: two accumulator sets, another tile)
 int bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                                 int epi, int ldo, hipStream_t s) {
+    if (type == BAMD_IQ4_NL) return bamd_launch_matmul_mfma_b32_nl(w_stream, aux, nrows, nrows_pad, K, blob16, T, out, res, epi, ldo, s);
     if (!(bamd_is_q0(type) || bamd_is_q1(type)) || T < 1 || nrows_pad < 8) return 1;
     bamd_mma_b32_args a; a.w = (const uint8_t *) w_stream; a.sc = (const float *) aux; a.out = out; a.res = res; a.blob16 = (const uint8_t *) blob16;
     a.K = K; a.T = T; a.nrows = nrows; a.nrows_pad = nrows_pad; a.ldo = ldo;

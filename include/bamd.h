@@ -209,12 +209,18 @@ void bamd_set_prefill_q0(int on);
  * weights) and a matrix-core kernel of their own.  Independent of bamd_set_prefill_q0.  Side tables are all-or-nothing per model: a Q4_0 / Q5_0 file made with
  * an importance matrix holds Q4_1 / Q5_1 ffn_down matrices and gets tables only with both switches on.  Taken at model load.  Bit-identical results. */
 void bamd_set_prefill_q1(int on);
+/* And for IQ4_NL weights (env BAMD_PREFILL_NL): 0 (default) = a model that holds such a layer matrix builds no side tables and evaluates its prompts on the
+ * integer-dot kernel; 1 = side tables (the Q4_0 ones: the rows' block scales as f32, 32 B per row and 256 weights) and a matrix-core kernel of their own, with the
+ * two accumulator sets of the type's chain.  Independent of the switches above: a model that also holds a Q8_0 / Q4_0 / Q5_0 or Q4_1 / Q5_1 layer matrix needs that
+ * family's switch too (side tables are all-or-nothing per model); llama.cpp's IQ4_NL files hold IQ4_NL and K-quant matrices and need this one alone.  Taken at
+ * model load.  Bit-identical results. */
+void bamd_set_prefill_nl(int on);
 /* Matrix-core prompt mat-muls for F32 / F16 weights (env BAMD_PREFILL_FLT): 0 (default) = such matrices evaluate prompts on the VALU kernel; 1 = on
- * v_mfma_f32_16x16x4_f32, the same fma chains.  UNLIKE the three switches above this one is read at each launch, not at model load: the kernel reads the resident
+ * v_mfma_f32_16x16x4_f32, the same fma chains.  UNLIKE the four switches above this one is read at each launch, not at model load: the kernel reads the resident
  * weights and the f32 activation rows as they are, there is no side table (bamd_model_prefill_aux_bytes stays 0 for such a model), so it takes effect for models and
  * contexts that exist already.  BF16 weights stay on the VALU kernel either way (their chain is a multiply and an add, not an fma).  Bit-identical results. */
 void bamd_set_prefill_flt(int on);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K; 20 IQ4_NL has no such kernel: always 0) since the library was loaded */
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */

@@ -14,10 +14,11 @@ four layers is Q4_1): once with both switches on against both off, once with onl
 
 --iq4nl: the IQ4_NL recipe (full depth, synthetic files of tests/golden/gen_iq4nl_fixtures.py's writer) beside Q4_0 and Q4_K_M: the 8B shape as the recipe
 writes it (n_gqa 4: Q5_K attn_v, so the QKV of a layer is two launches, six launches per layer) and a uniform-QKV variant of the same shape (attn_v IQ4_NL like
-attn_q / attn_k: one QKV launch) — the difference between the two is what the second QKV launch costs per token.  The prompt rate is the integer-dot kernel's:
-the type has no matrix-core kernel.
+attn_q / attn_k: one QKV launch) — the difference between the two is what the second QKV launch costs per token.  The prompt lines of the two IQ4_NL files
+alternate set_prefill_nl(False) / (True) like the lines above (integer-dot kernel against the matrix-core kernel of bamd_prefill2_b32_nl.hip), beside the Q4_0
+file under set_prefill_q0 as the nearest twin and the Q4_K_M file.
 
-    python tools/legacy_decode.py --iq4nl [--prompt 2048]
+    python tools/legacy_decode.py --iq4nl [--prompt 2048] [--only-prompt]
 """
 import importlib.util
 import os
@@ -38,15 +39,15 @@ _spec.loader.exec_module(gen)
 gen.CONFIGS.setdefault("8b_q5_0", (gen.L3_8B, "q5_0", 128, 64, 512))          # a model only: no fixture of it is stored
 
 
-def set_switches(q0, q1):
-    b.set_prefill_q0(bool(q0)); b.set_prefill_q1(bool(q1))
+def set_switches(q0, q1, nl=False):
+    b.set_prefill_q0(bool(q0)); b.set_prefill_q1(bool(q1)); b.set_prefill_nl(bool(nl))
 
 
-def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True):
-    """switched-off and switched-on rates of one file, alternating: ([off], [on], side-table bytes of the switched-on model).  q0 / q1: what "on" sets;
+def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True, nl=False):
+    """switched-off and switched-on rates of one file, alternating: ([off], [on], side-table bytes of the switched-on model).  q0 / q1 / nl: what "on" sets;
     tables: whether "on" is enough for this file to get side tables"""
     set_switches(False, False); m0 = b.Model(path)
-    set_switches(q0, q1)
+    set_switches(q0, q1, nl)
     try:
         m1 = b.Model(path)
     finally:
@@ -57,7 +58,7 @@ def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True):
     rates = ([], [])
     for rep in range(reps + 1):                                 # the first pair warms up
         for k, ctx in enumerate(ctxs):
-            set_switches(q0 and k, q1 and k)                    # the routing asks the switches as well as the tables
+            set_switches(q0 and k, q1 and k, nl and k)                 # the routing asks the switches as well as the tables
             b.lib().bamd_kv_cache_clear(ctx.h)
             t0 = time.perf_counter()
             for i in range(0, n_prompt, 512):
@@ -74,7 +75,7 @@ def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True):
 
 def print_pair(name, n, off, on, aux):
     bar = max(off) + (max(off) - min(off))
-    print("prompt %-7s %d tokens: switch off median %7.1f tok/s (range %.1f - %.1f; integer-dot kernel) | switch on median %7.1f tok/s (range %.1f - %.1f; %s, "
+    print("prompt %-18s %d tokens: switch off median %7.1f tok/s (range %.1f - %.1f; integer-dot kernel) | switch on median %7.1f tok/s (range %.1f - %.1f; %s, "
           "side tables %.2f GiB) | x %.2f | bar (off max + off spread) %.1f: %s" % (name, n, statistics.median(off), min(off), max(off), statistics.median(on), min(on), max(on),
           "matrix-core kernel" if aux > 0 else "integer-dot kernel", aux / 2 ** 30, statistics.median(on) / statistics.median(off), bar, "cleared" if statistics.median(on) > bar else "NOT cleared"), flush=True)
 
@@ -117,19 +118,22 @@ def main_iq4nl():
         open(uniform + ".done", "w").write("ok")
     files = [("Q4_K_M", q4_k_m_file()), ("Q4_0", gen.ensure_model("8b_q4_0")), ("IQ4_NL", gn.ensure_model("8b_iq4nl")), ("IQ4_NL uniform QKV", uniform)]
     med = {}
-    for name, p in files:
+    for name, p in [] if "--only-prompt" in sys.argv else files:
         r = decode_rate(p)
         med[name] = statistics.median(r)
         print("decode %-18s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, med[name], min(r), max(r)), flush=True)
-    two, one = 1e6 / med["IQ4_NL"], 1e6 / med["IQ4_NL uniform QKV"]
-    print("second QKV launch: %.1f us per token at six launches per layer against %.1f us at five = %.2f us per layer (32 layers; the Q5_K attn_v is also %.1f %% more bytes than an IQ4_NL one)"
-          % (two, one, (two - one) / 32, 100.0 * (176 / 256 - 18 / 32) / (18 / 32)), flush=True)
+    if med:
+        two, one = 1e6 / med["IQ4_NL"], 1e6 / med["IQ4_NL uniform QKV"]
+        print("second QKV launch: %.1f us per token at six launches per layer against %.1f us at five = %.2f us per layer (32 layers; the Q5_K attn_v is also %.1f %% more bytes than an IQ4_NL one)"
+              % (two, one, (two - one) / 32, 100.0 * (176 / 256 - 18 / 32) / (18 / 32)), flush=True)
     if "--prompt" in sys.argv:
         n = int(sys.argv[sys.argv.index("--prompt") + 1])
-        for name, p in files:
-            r, aux = prompt_rate(p, n, reps=5)
-            print("prompt %-18s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
-                  "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+        r, aux = prompt_rate(files[0][1], n, reps=5)
+        print("prompt %-18s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (files[0][0], n, statistics.median(r), min(r), max(r),
+              "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+        print_pair("Q4_0", n, *prompt_pair(files[1][1], n))                    # the nearest twin: the same record, one accumulator set, BAMD_PREFILL_Q0
+        for name, p in files[2:]:
+            print_pair(name, n, *prompt_pair(p, n, q0=False, nl=True))
 
 
 def main():
