@@ -58,11 +58,8 @@ def lib():
         L.bamd_profile_step.argtypes = [vp, ci, vp, vp, vp]; L.bamd_profile_step_kinds.argtypes = [vp, ci, vp, vp, vp]
         L.bamd_timeline_step.argtypes = [vp, ci, ci, vp, ci, C.POINTER(ci)]
         L.bamd_set_prefill_batch.argtypes = [ci]; L.bamd_set_prefill_batch.restype = None
-        L.bamd_set_prefill_lowbit.argtypes = [ci]; L.bamd_set_prefill_lowbit.restype = None
-        L.bamd_set_prefill_q0.argtypes = [ci]; L.bamd_set_prefill_q0.restype = None
-        L.bamd_set_prefill_q1.argtypes = [ci]; L.bamd_set_prefill_q1.restype = None
-        L.bamd_set_prefill_nl.argtypes = [ci]; L.bamd_set_prefill_nl.restype = None
-        L.bamd_set_prefill_flt.argtypes = [ci]; L.bamd_set_prefill_flt.restype = None
+        for n in ("lowbit", "q0", "q1", "nl", "flt"):                    # the switches of csrc/bamd_prefill_family.h
+            getattr(L, "bamd_set_prefill_" + n).argtypes = [ci]; getattr(L, "bamd_set_prefill_" + n).restype = None
         L.bamd_set_attn_scratch_mb.argtypes = [ci]; L.bamd_set_attn_scratch_mb.restype = None
         L.bamd_attention_batch_plan.argtypes = [ci, ci, ci, ci, ci, ci, C.c_size_t, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
         L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong

@@ -10,6 +10,7 @@
 #include "bamd_formats.h"
 #include "bamd_gguf.h"
 #include "bamd_kernels.h"
+#include "bamd_prefill_family.h"
 #include "bamd_aql.h"
 #include "bamd_engine_internal.h"
 
@@ -34,7 +35,7 @@ static int g_prefill_mfma = [] { const char * e = getenv("BAMD_PREFILL_MFMA"); r
 // The matrix-core kernels need a side table per matrix (bamd_prefill2.hip): built at MODEL LOAD, all matrices or none, against an explicit memory budget — after the
 // weights are resident the tables (+ 78 % of the Q4_K / Q5_K bytes, + 63 % of the Q6_K bytes) must leave BAMD_PREFILL_AUX_RESERVE_GB (default 8) GiB of the device free,
 // else the model runs its prompts on the integer-dot kernel (token by token where that has no instance).  BAMD_PREFILL_AUX=0 skips them (decode-only deployments).
-// Q3_K / Q2_K matrices have tables and kernels only with the switch bamd_prefill_lowbit() on (bamd_kernels.h: bamd_prefill_mfma_type, the one list): a model takes its value at load.
+// Which types have tables and kernels, and the switches of those that are off by default: bamd_prefill_family.h (bamd_prefill_mfma_type); a model takes their values at load.
 static const int g_prefill_aux = [] { const char * e = getenv("BAMD_PREFILL_AUX"); return (e && e[0] == '0') ? 0 : 1; }();
 // BAMD_STAGE_GRAPH=0: bamd_stage_step enqueues its kernels one by one instead of replaying a captured hipGraph
 static const int g_stage_graph = [] { const char * e = getenv("BAMD_STAGE_GRAPH"); return (e && e[0] == '0') ? 0 : 1; }();
@@ -876,23 +877,14 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     // F32 / F16 matrices with BAMD_PREFILL_FLT on: their matrix-core kernel has no side table (bamd_batch_mm reads the switch at each launch), so they ask for
     // nothing here; a model of such matrices only has nothing to build and nothing to report
     const size_t n_all = items.size();
-    if (bamd_prefill_flt()) items.erase(std::remove_if(items.begin(), items.end(), [](const Item & it) { return it.type == BAMD_F32 || it.type == BAMD_F16; }), items.end());
+    items.erase(std::remove_if(items.begin(), items.end(), [](const Item & it) { return bamd_prefill_mfma_type_notable(it.type); }), items.end());
     if (n_all && items.empty()) { m->aux_none_needed = true; return; }
     size_t need = 0;
-    for (const Item & it : items) { const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K); if (!b) {
-        // (with every switch off the reasons read as they did before the switches existed; with one of BAMD_PREFILL_Q0 / BAMD_PREFILL_Q1 / BAMD_PREFILL_NL on, the one that is missing is named)
-        m->aux_why = bamd_is_flt(it.type) && bamd_prefill_flt() ? "the model holds a BF16 matrix: these have no matrix-core kernel (BAMD_PREFILL_FLT covers F32 / F16 only), and side tables are all-or-nothing per model, so every prompt mat-mul of the other types runs on the VALU kernels"
-                   : bamd_is_flt(it.type) ? "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels"
-                   : it.type == BAMD_IQ4_NL ? "the model holds an IQ4_NL matrix: these have no matrix-core kernel (BAMD_PREFILL_Q0 covers Q4_0 / Q5_0 / Q8_0 only), and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840); BAMD_PREFILL_NL, the switch of the IQ4_NL matrix-core kernel, is off"
-                   : bamd_is_q1(it.type) && bamd_prefill_q0() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_Q0 covers only its Q4_0 / Q5_0 / Q8_0 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
-                   : bamd_is_q0(it.type) && bamd_prefill_q1() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_Q1 covers only its Q4_1 / Q5_1 matrices; a Q4_0 / Q5_0 file made with an importance matrix needs both switches): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
-                   : bamd_is_q1(it.type) && bamd_prefill_nl() ? "the model holds a Q4_1 / Q5_1 matrix and BAMD_PREFILL_Q1 is off (BAMD_PREFILL_NL covers only its IQ4_NL matrices): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
-                   : bamd_is_q0(it.type) && bamd_prefill_nl() ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix and BAMD_PREFILL_Q0 is off (BAMD_PREFILL_NL covers only its IQ4_NL matrices): side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
-                   : bamd_is_q1(it.type) ? "the model holds a Q4_1 / Q5_1 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
-                   : bamd_is_q0(it.type) ? "the model holds a Q4_0 / Q5_0 / Q8_0 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
-                   : bamd_is_kquant(it.type) && !bamd_prefill_mfma_type(it.type) ? "the model holds a Q2_K / Q3_K matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
-                                                                  : "a matrix type / shape without a matrix-core kernel";
-        return; } need += b + 4096; }
+    for (const Item & it : items) {
+        const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K);
+        if (!b) { m->aux_why = bamd_prefill_reason(it.type); return; }      // (the sentences: bamd_prefill_family.cpp)
+        need += b + 4096;
+    }
     if (items.empty()) return;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); m->aux_why = "hipMemGetInfo failed"; return; }
@@ -938,9 +930,8 @@ static int ensure_batch_buffers(bamd_context * c) {
 // prompt path below and the op-level entry point (bamd_op_mul_mat_batch_seg) both come through here
 int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s) {
     const int T = a.T;
-    // (F32 / F16 with bamd_prefill_flt(): no side table — the switch is read here, at each launch; their kernel takes the f32 rows of a.blob.  BF16 never)
-    auto flt_mfma = [&](int i) { return g_prefill_mfma && bamd_prefill_flt() && (a.seg[i].type == BAMD_F32 || a.seg[i].type == BAMD_F16); };
-    auto on_mfma = [&](int i) { return flt_mfma(i) || (g_prefill_mfma && aux[i] && bamd_prefill_mfma_type(a.seg[i].type)); };
+    // (F32 / F16 with BAMD_PREFILL_FLT on: no side table — the switch is read here, at each launch; their kernel takes the f32 rows of a.blob.  BF16 never)
+    auto on_mfma = [&](int i) { return g_prefill_mfma && (bamd_prefill_mfma_type_notable(a.seg[i].type) || (aux[i] && bamd_prefill_mfma_type(a.seg[i].type))); };
     auto mm_mfma = [&](const bamd_mv_seg & sg, const void * ax, int nv, float * out, const float * res, int e) {
         if (sg.type == BAMD_F32 || sg.type == BAMD_F16) return bamd_launch_matmul_mfma_flt(sg.w, sg.type, nv, sg.nrows, a.K, a.blob, T, out, res, e, a.ldo, s);
         return bamd_launch_matmul_mfma2(sg.w, ax, sg.type, nv, sg.nrows, a.K, blob16, T, out, res, e, a.ldo, s);

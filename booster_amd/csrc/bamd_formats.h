@@ -76,6 +76,7 @@ BAMD_HD static inline int bamd_is_q0(int t) { return t == BAMD_Q8_0 || t == BAMD
 // no IQ4_NL instance and keep asking bamd_is_q0)
 BAMD_HD static inline int bamd_takes_q8_0(int t) { return bamd_is_q0(t) || t == BAMD_IQ4_NL; }
 BAMD_HD static inline int bamd_is_q1(int t) { return t == BAMD_Q4_1 || t == BAMD_Q5_1; }                               // 32-weight blocks with a minimum, Q8_1 activations
+BAMD_HD static inline int bamd_is_b32(int t) { return bamd_takes_q8_0(t) || bamd_is_q1(t); }                         // any 32-weight block type: Q8_0 / Q4_0 / Q5_0, IQ4_NL, Q4_1 / Q5_1
 BAMD_HD static inline int bamd_is_flt(int t) { return t == BAMD_F32 || t == BAMD_F16 || t == BAMD_BF16; }               // unquantised weights: f32 activations (F32 / F16) or bf16 ones (BF16)
 // the form a launch quantises its activations to for weights of type t; one launch has one form (0 = a type without a mat-vec kernel)
 enum bamd_act_form { BAMD_ACT_NONE = 0, BAMD_ACT_Q8_K = 1, BAMD_ACT_Q8_0 = 2, BAMD_ACT_Q8_1 = 3, BAMD_ACT_F32 = 4, BAMD_ACT_BF16 = 5 };

@@ -1,4 +1,4 @@
-// bamd_kernels.h — host-visible launch interface of the kernel files (bamd_matvec.hip, bamd_attention.hip, bamd_prefill.hip)
+// bamd_kernels.h — host-visible launch interface of the kernel files (bamd_matvec*.hip, bamd_attention*.hip, bamd_colaunch.hip, bamd_prefill*.hip, bamd_sampler.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -95,7 +95,7 @@ void bamd_launch_act_batch_flt(int form, const float * x, const float * nw, floa
 int  bamd_launch_matmul_batch_flt(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);
 [[nodiscard]] static inline int bamd_launch_mv(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
     if (a.nseg > 0 && bamd_is_flt(a.seg[0].type)) return bamd_launch_matvec_flt(a, pro, epi, n_cu, s);
-    return a.nseg > 0 && (bamd_takes_q8_0(a.seg[0].type) || bamd_is_q1(a.seg[0].type)) ? bamd_launch_matvec_b32(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
+    return a.nseg > 0 && bamd_is_b32(a.seg[0].type) ? bamd_launch_matvec_b32(a, pro, epi, n_cu, s) : bamd_launch_matvec(a, pro, epi, n_cu, s);
 }
 void bamd_launch_quantize_q81_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 void bamd_launch_quantize_q80_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
@@ -118,8 +118,7 @@ static inline size_t bamd_act_blob_bytes(int form, int K) { const size_t f = bam
 // blob: int8 activations for matmul_batch_kernel (may be null); blob16: f16 copy for the MFMA kernel (may be null)
 // form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_0 for Q8_0 / Q4_0 / Q5_0 weights, BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_0 / Q8_1 form
 // of the same size (bamd_prefill_b32.hip); blob16 is written, in the f16 form of bamd_prefill2_b32.hip (544 / 576 bytes of a record, the same per-token stride), only
-// while the family's switch bamd_prefill_q0() / bamd_prefill_q1() is on (otherwise nothing reads it); the Q8_0 form also while bamd_prefill_nl() is on (IQ4_NL weights
-// take the same records)
+// while a family that reads this form is on (bamd_prefill_reads_act16, bamd_prefill_family.h; otherwise nothing reads it)
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K);
 void bamd_launch_quantize_batch_b32(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
 int  bamd_launch_matmul_batch_b32_nl(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);       // its launches with an IQ4_NL segment (bamd_prefill_b32_nl.hip); callers go through the next
@@ -129,24 +128,7 @@ int  bamd_launch_matmul_batch_b32(const bamd_mm_args & a, int epi, int n_cu, hip
 // wave-stream copy and the matrix's load-time side table (aux: bamd_prefill_aux_bytes bytes, filled by bamd_launch_prefill_aux).  1 = type / shape not supported or no table
 // (Q4_K / Q5_K: the sixteen-wave matmul_mfma3_q4k_kernel; Q6_K / Q3_K / Q2_K: the eight-wave matmul_mfma2_kernel, one body with a policy struct per format)
 int  bamd_prefill_mfma_supported(void);      // the current device accepts the kernels' LDS size (asked at model load)
-// "this weight type has a matrix-core prompt mat-mul now": the ONE list — side-table sizes, the launcher, the engine's routing and its load-time message all ask here.
-// Q3_K / Q2_K are behind the process-wide switch bamd_prefill_lowbit() (BAMD_PREFILL_LOWBIT=1 / bamd_set_prefill_lowbit; default off): a model builds their
-// tables, or not, with the value it finds at load
-// Q8_0 / Q4_0 / Q5_0 (bamd_prefill2_b32.hip) are behind a switch of the same shape, bamd_prefill_q0() (BAMD_PREFILL_Q0=1 / bamd_set_prefill_q0; default off)
-// Q4_1 / Q5_1 (the same kernel) are behind a third switch of that shape, bamd_prefill_q1() (BAMD_PREFILL_Q1=1 / bamd_set_prefill_q1; default off), independent of
-// bamd_prefill_q0().  Side tables are all-or-nothing per model, and llama.cpp writes Q4_0 / Q5_0 files made with an importance matrix with Q4_1 / Q5_1 ffn_down
-// matrices in their first layers: such a file needs BOTH switches on to get tables; with one of them it runs on the integer-dot kernel like with none
-int  bamd_prefill_lowbit(void);
-int  bamd_prefill_q0(void);
-// IQ4_NL (bamd_prefill2_b32_nl.hip: the Q4_0 record and side table, a kernel of its own with two accumulator sets) is behind a fourth switch of that shape,
-// bamd_prefill_nl() (BAMD_PREFILL_NL=1 / bamd_set_prefill_nl; default off), independent of the others.  bamd_is_q0 does not hold the type (split-K asks it): where
-// the question is "a 32-weight block type with a side table of that family", ask bamd_is_q0 || bamd_is_q1 || IQ4_NL
-int  bamd_prefill_q1(void);
-int  bamd_prefill_nl(void);
-static inline bool bamd_prefill_mfma_type(int type) {
-    return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((type == BAMD_Q3_K || type == BAMD_Q2_K) && bamd_prefill_lowbit()) || (bamd_is_q0(type) && bamd_prefill_q0()) ||
-           (bamd_is_q1(type) && bamd_prefill_q1()) || (type == BAMD_IQ4_NL && bamd_prefill_nl());
-}
+// which weight types have such a kernel now, and the switches they are behind (bamd_prefill_mfma_type and its kin): bamd_prefill_family.h
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
@@ -159,11 +141,9 @@ int  bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int ty
                                  int epi, int ldo, hipStream_t s);
 int  bamd_launch_matmul_mfma_b32_nl(const void * w_stream, const void * aux, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res, int epi,
                                     int ldo, hipStream_t s);
-// F32 / F16 matrices on the matrix cores, exact (bamd_prefill2_flt.hip), behind a switch of their own, bamd_prefill_flt() (BAMD_PREFILL_FLT=1 / bamd_set_prefill_flt; default
-// off).  Unlike the switches above it is read at each launch, not at model load: the kernel reads the resident weight stream and the f32 activation rows of
+// F32 / F16 matrices on the matrix cores, exact (bamd_prefill2_flt.hip): the kernel reads the resident weight stream and the f32 activation rows of
 // bamd_launch_act_batch_flt (blob) as they are, there is no side table to build.  BF16 has no such kernel.  Epilogues as bamd_launch_matmul_mfma2; 1 = type / shape
-// not supported.  bamd_prefill_mfma_count: one more launch of `type` for bamd_prefill_mfma_runs (the counters live in bamd_prefill2.hip)
-int  bamd_prefill_flt(void);
+// not supported.  bamd_prefill_mfma_count: one more launch of `type` for bamd_prefill_mfma_runs (every matrix-core launcher; the counters live in bamd_prefill2.hip)
 int  bamd_launch_matmul_mfma_flt(const void * w_stream, int type, int nrows, int nrows_pad, int K, const void * blob, int T, float * out, const float * res, int epi, int ldo,
                                  hipStream_t s);
 void bamd_prefill_mfma_count(int type);

@@ -5,6 +5,7 @@
 #include "bamd_engine_internal.h"
 #include "bamd_formats.h"
 #include "bamd_kernels.h"
+#include "bamd_prefill_family.h"
 
 #include <math.h>
 #include <string.h>
@@ -116,7 +117,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec_argmax
     return 0;
 }
 // batched mat-mul of T activation rows against one matrix through the prefill kernels: impl 0 = integer-dot kernel, 2 = matrix-core kernel (1 and 3 were the generations removed in round 6)
-// (F32 / F16 / BF16: impl 0 = the VALU kernel; impl 2 = the f32 matrix-core kernel, for F32 / F16 only and only while bamd_prefill_flt() is on)
+// (F32 / F16 / BF16: impl 0 = the VALU kernel; impl 2 = the f32 matrix-core kernel, for F32 / F16 only and only while BAMD_PREFILL_FLT is on)
 extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const float * x, int T, const float * norm_w,
                                                                               float eps, const float * residual, float * y, int impl) {
     if (need_device()) return 1;
@@ -131,7 +132,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     HIPC(hipMemset(str, 0, wbp));
     bamd_launch_repack(raw, str, type, nrows, k, nullptr);
     bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(type));
-    const bool flt_mfma = impl == 2 && (type == BAMD_F32 || type == BAMD_F16) && bamd_prefill_flt();      // F32 / F16 with BAMD_PREFILL_FLT on: bamd_prefill2_flt.hip, no side table
+    const bool flt_mfma = impl == 2 && bamd_prefill_mfma_type_notable(type);      // F32 / F16 with BAMD_PREFILL_FLT on: bamd_prefill2_flt.hip, no side table
     if (bamd_is_flt(type) && impl != 0 && !flt_mfma) return fail(impl == 2 ? "MFMA path: unsupported type/shape (F32 / F16 / BF16 have no matrix-core kernel)" : "batched mat-mul: impl must be 0 for F32 / F16 / BF16");
     if (flt_mfma) {
         if (bamd_launch_matmul_mfma_flt(str, type, nrows, nrows_pad, k, blob, T, dy, dres, dres ? BAMD_EPI_ADD : BAMD_EPI_STORE, nrows, nullptr)) return fail("MFMA path: unsupported type/shape");
@@ -393,7 +394,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_fused_qkv(int nseg
 // one batched prompt mat-mul as enqueue_prefill_batch issues it: up to three segments into one [T][ldo] matrix (STORE: the q | k | v call; ADD: one segment
 // + residual; SILU_MUL: gate and up into the same columns), routed by bamd_batch_mm.  impl 0: no side tables (integer-dot kernel); impl 2: a side table for
 // every segment whose type has a matrix-core kernel, built as build_prefill_aux builds them — the others stay on the integer-dot kernel.  F32 / F16 segments need
-// no table: while bamd_prefill_flt() is on, bamd_batch_mm sends them to their matrix-core kernel (at impl 0 as well, as the engine would); while it is off, and for
+// no table: while BAMD_PREFILL_FLT is on, bamd_batch_mm sends them to their matrix-core kernel (at impl 0 as well, as the engine would); while it is off, and for
 // BF16 always, impl 2 is refused for the unquantised family
 extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(int nseg, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, const float * x,
                                                                                   int T, const float * norm_w, float eps, int ldo, const float * residual, int epi, int impl, float * y) {
@@ -414,7 +415,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(
     bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(f.seg[0].type));
     const void * aux[3] = { nullptr, nullptr, nullptr };
     // (F32 / F16 with BAMD_PREFILL_FLT on have a matrix-core kernel without a side table: bamd_batch_mm routes them by the switch alone)
-    if (impl == 2 && (f.seg[0].type == BAMD_BF16 || (bamd_is_flt(f.seg[0].type) && !bamd_prefill_flt()))) return fail("MFMA path: unsupported type/shape (F32 / F16 / BF16 have no matrix-core kernel)");
+    if (impl == 2 && bamd_is_flt(f.seg[0].type) && !bamd_prefill_mfma_type_notable(f.seg[0].type)) return fail("MFMA path: unsupported type/shape (F32 / F16 / BF16 have no matrix-core kernel)");
     if (impl == 2) for (int i = 0; i < nseg; ++i) {
         const size_t ab = bamd_prefill_aux_bytes(f.seg[i].type, f.seg[i].nrows, k);
         if (!ab) continue;                                                   // Q2_K / Q3_K with the switch off, or a shape without a matrix-core kernel

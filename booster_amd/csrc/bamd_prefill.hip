@@ -2,6 +2,7 @@
 // the integer-dot batched mat-mul (any K-quant), batched embedding, silu*up.  Helpers: bamd_device.h.
 #include "bamd_device.h"
 #include "bamd_mfma_common.h"
+#include "bamd_prefill_family.h"
 #include <type_traits>
 
 // ===========================================================================================================
@@ -203,14 +204,13 @@ size_t bamd_blob_bytes(int K) { return BAMD_BLOB_BYTES(K >> 8); }
 size_t bamd_blob16_bytes(int K) { return BAMD_BLOB16_BYTES(K >> 8); }
 void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form) {
     if (form == BAMD_ACT_F32 || form == BAMD_ACT_BF16) { bamd_launch_act_batch_flt(form, x, nw, eps, K, T, blob, s); return; }
-    if (form == BAMD_ACT_Q8_1) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_q1() ? blob16 : nullptr); return; }
-    if (form == BAMD_ACT_Q8_0) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_q0() || bamd_prefill_nl() ? blob16 : nullptr); return; }
+    if (form == BAMD_ACT_Q8_1 || form == BAMD_ACT_Q8_0) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_reads_act16(form) ? blob16 : nullptr); return; }
     if (nw) hipLaunchKernelGGL((quantize_batch_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
     else    hipLaunchKernelGGL((quantize_batch_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
 }
 int bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s) {
     if (a.nseg > 0 && bamd_is_flt(a.seg[0].type)) return bamd_launch_matmul_batch_flt(a, epi, n_cu, s);      // f32 / bf16 activations (bamd_prefill_flt.hip)
-    if (a.nseg > 0 && (bamd_takes_q8_0(a.seg[0].type) || bamd_is_q1(a.seg[0].type))) return bamd_launch_matmul_batch_b32(a, epi, n_cu, s);      // Q8_0 / Q8_1 activations: kernels of their own; a launch that mixes the forms has none
+    if (a.nseg > 0 && bamd_is_b32(a.seg[0].type)) return bamd_launch_matmul_batch_b32(a, epi, n_cu, s);      // Q8_0 / Q8_1 activations: kernels of their own; a launch that mixes the forms has none
     int nrg = 0;
     if (epi == BAMD_EPI_SILU_MUL) nrg = a.seg[0].nrows >> 3; else for (int i = 0; i < a.nseg; ++i) nrg += a.seg[i].nrows >> 3;
     const int tt = (size_t) BAMD_TT * BAMD_BLOB_BYTES(a.K >> 8) <= 160 * 1024 ? BAMD_TT : 4;     // tokens per tile: 8 while their activations fit the LDS, else 4

@@ -17,7 +17,7 @@
 //     {s, -1024 s, s'/16, -64 s'} as packed f16 pairs, and the consumers' d, dmin as f32 plus the min-term MFMA operands {2 m_a, 2 m_b, m_a, m_b}, which
 //     travel global -> LDS by DMA with the activation records;
 //   * two layouts: sixteen waves with one 16 x 16 tile each (matmul_mfma3_q4k_kernel: Q4_K / Q5_K), eight waves with 16 x 32 each (matmul_mfma2_kernel: ONE body,
-//     a policy struct per format — X2Q6K: Q6_K; X2LowBit<Q2>: Q3_K / Q2_K, behind the switch BAMD_PREFILL_LOWBIT / bamd_set_prefill_lowbit, default off).
+//     a policy struct per format — X2Q6K: Q6_K; X2LowBit<Q2>: Q3_K / Q2_K, behind the switch BAMD_PREFILL_LOWBIT / bamd_set_prefill_lowbit, default off: bamd_prefill_family.h).
 //     Both layouts close with the same hsum tree (x_hsum8) and the same row-of-four store, which each kernel writes out itself (note at the eight-wave policies).
 //     (Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1: a kernel of another shape, bamd_prefill2_b32.hip, reached through the launchers at the end of this file.)
 // Same bits as the round-2 kernels (removed in round 6), a third fewer vector instructions per MFMA — and the same time: DESIGN 4c has the measurements of what
@@ -25,6 +25,7 @@
 #include "bamd_device.h"
 #include "bamd_mfma_common.h"
 #include "bamd_mv_select.h"
+#include "bamd_prefill_family.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -725,25 +726,10 @@ __global__ void __launch_bounds__(1024) matmul_mfma3_q4k_kernel(bamd_mma2_args a
 static inline int x_row_blocks(int nrows_pad) { return (nrows_pad + 63) / 64; }
 static unsigned long long * g_prefill_dbg = nullptr;      // -DX_TIMING builds: where the kernels of the next launches leave their phase clocks (bamd_prefill_dbg)
 extern "C" __attribute__((visibility("default"))) void bamd_prefill_dbg(void * dev_buf) { g_prefill_dbg = (unsigned long long *) dev_buf; }
-// process-wide switch of the Q3_K / Q2_K kernels (default off: BAMD_PREFILL_LOWBIT=1 or bamd_set_prefill_lowbit) and the launch counters per weight type
-static int g_prefill_lowbit = [] { const char * e = getenv("BAMD_PREFILL_LOWBIT"); return (e && e[0] == '1') ? 1 : 0; }();
-// the same switch for the Q8_0 / Q4_0 / Q5_0 instances of the kernel of bamd_prefill2_b32.hip (default off: BAMD_PREFILL_Q0=1 or bamd_set_prefill_q0)
-static int g_prefill_q0 = [] { const char * e = getenv("BAMD_PREFILL_Q0"); return (e && e[0] == '1') ? 1 : 0; }();
-// and for its Q4_1 / Q5_1 instances (default off: BAMD_PREFILL_Q1=1 or bamd_set_prefill_q1); independent of the one above
-static int g_prefill_q1 = [] { const char * e = getenv("BAMD_PREFILL_Q1"); return (e && e[0] == '1') ? 1 : 0; }();
-// and for the IQ4_NL kernel of bamd_prefill2_b32_nl.hip (default off: BAMD_PREFILL_NL=1 or bamd_set_prefill_nl); independent of the others
-static int g_prefill_nl = [] { const char * e = getenv("BAMD_PREFILL_NL"); return (e && e[0] == '1') ? 1 : 0; }();
+// the launch counters per weight type (the switches the kernels are behind: bamd_prefill_family.h)
 static long long g_mfma_runs[32] = { 0 };                  // by bamd_type (IQ4_NL = 20, BF16 = 30)
-int bamd_prefill_lowbit(void) { return g_prefill_lowbit; }
-int bamd_prefill_q0(void) { return g_prefill_q0; }
-int bamd_prefill_q1(void) { return g_prefill_q1; }
-int bamd_prefill_nl(void) { return g_prefill_nl; }
-extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_lowbit(int on) { g_prefill_lowbit = on ? 1 : 0; }
-extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_q0(int on) { g_prefill_q0 = on ? 1 : 0; }
-extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_q1(int on) { g_prefill_q1 = on ? 1 : 0; }
-extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_nl(int on) { g_prefill_nl = on ? 1 : 0; }
 extern "C" __attribute__((visibility("default"))) long long bamd_prefill_mfma_runs(int type) { return type >= 0 && type < 32 ? g_mfma_runs[type] : 0; }
-void bamd_prefill_mfma_count(int type) { if (type >= 0 && type < 32) g_mfma_runs[type] += 1; }      // the F32 / F16 launcher's (bamd_prefill2_flt.hip)
+void bamd_prefill_mfma_count(int type) { if (type >= 0 && type < 32) g_mfma_runs[type] += 1; }
 static inline bool x_lowbit(int type) { return type == BAMD_Q3_K || type == BAMD_Q2_K; }
 // builder / consumer part of a (row block, super-block) in the side table, and the super-blocks of slack behind each part (the sixteen-wave kernel's last
 // two staging calls read past the end of K; the eight-wave kernels clamp)
@@ -754,11 +740,11 @@ static inline size_t x_ph_bytes(int type, int nrows_pad, int K) { return ((size_
 // bytes of the side table of a K-quant matrix [nrows_pad][K]: builder part first, the consumer part behind it (both 16-byte aligned)
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K) {
     if (!bamd_prefill_mfma_type(type) || (K & 255) || (nrows_pad & 7)) return 0;
-    if (bamd_is_q0(type) || bamd_is_q1(type) || type == BAMD_IQ4_NL) return bamd_prefill_aux_bytes_b32(type, nrows_pad, K);
+    if (bamd_is_b32(type)) return bamd_prefill_aux_bytes_b32(type, nrows_pad, K);
     return x_ph_bytes(type, nrows_pad, K) + ((size_t) x_row_blocks(nrows_pad) * (size_t) (K >> 8) + x_slack(type)) * x_ch_sb(type);
 }
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s) {
-    if (bamd_is_q0(type) || bamd_is_q1(type) || type == BAMD_IQ4_NL) { bamd_launch_prefill_aux_b32(w_stream, type, nrows_pad, K, aux, s); return; }
+    if (bamd_is_b32(type)) { bamd_launch_prefill_aux_b32(w_stream, type, nrows_pad, K, aux, s); return; }
     const int nb = K >> 8, nrt = x_row_blocks(nrows_pad) * 4;
     uint8_t * ph = (uint8_t *) aux, * ch = ph + x_ph_bytes(type, nrows_pad, K);
     const dim3 grid(nb, nrt);
@@ -785,9 +771,9 @@ int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, 
     if (!bamd_prefill_mfma_type(type) || (nrows_pad & 7) || (K & 255) || !aux) return 1;
     if (epi != BAMD_EPI_STORE && epi != BAMD_EPI_ADD && epi != BAMD_EPI_SILU_MUL) return 1;
     if ((epi != BAMD_EPI_STORE) != (res != nullptr)) return 1;
-    if (bamd_is_q0(type) || bamd_is_q1(type) || type == BAMD_IQ4_NL) {                // bamd_prefill2_b32.hip / _nl.hip; static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
+    if (bamd_is_b32(type)) {                // bamd_prefill2_b32.hip / _nl.hip; static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
         if (bamd_launch_matmul_mfma_b32(w_stream, aux, type, nrows, nrows_pad, K, blob16, T, out, res, epi, ldo, s)) return 1;
-        g_mfma_runs[type] += 1;
+        bamd_prefill_mfma_count(type);
         return 0;
     }
     bamd_mma2_args a; a.w = (const uint8_t *) w_stream; a.ph = (const uint8_t *) aux; a.ch = a.ph + x_ph_bytes(type, nrows_pad, K);
@@ -795,7 +781,7 @@ int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, 
     a.dbg = g_prefill_dbg;
     const dim3 grid((T + 63) / 64, x_row_blocks(nrows_pad));
     const dim3 grid3(grid.x, BAMD_PREFILL_CEILING == 2 ? (grid.y + 1) / 2 : grid.y);     // (ceiling build 2: every workgroup issues the MFMAs of two; timing only)
-    g_mfma_runs[type] += 1;
+    bamd_prefill_mfma_count(type);
     with_const(consts<BAMD_EPI_ADD, BAMD_EPI_SILU_MUL, BAMD_EPI_STORE>(), epi, [&](auto E) -> bool {
         constexpr int EPI = decltype(E)::value;
         auto launch = [&](auto kernel, dim3 g, int threads, size_t lds) { hipLaunchKernelGGL(kernel, g, dim3(threads), lds, s, a); };

@@ -1,6 +1,6 @@
 // bamd_prefill2_b32.hip — the exact matrix-core prompt mat-mul for the 32-weight block formats: Q8_0 / Q4_0 / Q5_0 weights x Q8_0 activations behind the switch
 // BAMD_PREFILL_Q0 / bamd_set_prefill_q0, Q4_1 / Q5_1 weights x Q8_1 activations behind BAMD_PREFILL_Q1 / bamd_set_prefill_q1 (both default off; the list of types
-// is bamd_prefill_mfma_type, bamd_kernels.h).  One kernel template for the five types; MIN = b32_has_min(TYPE) marks what the types with a minimum add.
+// is bamd_prefill_mfma_type, bamd_prefill_family.h).  One kernel template for the five types; MIN = b32_has_min(TYPE) marks what the types with a minimum add.
 // (IQ4_NL, the sixth type of the family, has a sibling kernel in bamd_prefill2_b32_nl.hip — two accumulator sets per output, another tile — behind BAMD_PREFILL_NL;
 // this file's launchers route the type there and write its side table with the Q4_0 instance of prefill_aux_b32_kernel.)
 //

@@ -1,5 +1,5 @@
 // bamd_prefill2_b32_nl.hip — the exact matrix-core prompt mat-mul for IQ4_NL weights x Q8_0 activations, behind the switch BAMD_PREFILL_NL / bamd_set_prefill_nl
-// (default off; the list of types is bamd_prefill_mfma_type, bamd_kernels.h).  A sibling of matmul_mfma_b32_kernel (bamd_prefill2_b32.hip) in a translation unit of
+// (default off; the list of types is bamd_prefill_mfma_type, bamd_prefill_family.h).  A sibling of matmul_mfma_b32_kernel (bamd_prefill2_b32.hip) in a translation unit of
 // its own, so that kernel's five instances stay instruction for instruction what they are; read that file's header first: the instruction
 // (v_mfma_f32_16x16x4_4b_f16), the lane maps, the f16 operand images, the weights from the wave stream straight into registers, the activations through the
 // double-buffered LDS stage, the links on the VALU as v_pk_fma_f32 and one MFMA's chain behind the next MFMA's issue are the same here.

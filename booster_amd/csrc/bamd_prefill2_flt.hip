@@ -1,5 +1,5 @@
 // bamd_prefill2_flt.hip — the exact matrix-core prompt mat-mul for F32 / F16 weights x f32 activations, behind the switch BAMD_PREFILL_FLT=1 /
-// bamd_set_prefill_flt (default off).  BF16 weights stay on the VALU kernel of bamd_prefill_flt.hip: their chain is add(mul(w, x), c) with two roundings, which
+// bamd_set_prefill_flt (default off; the families and their switches: bamd_prefill_family.h).  BF16 weights stay on the VALU kernel of bamd_prefill_flt.hip: their chain is add(mul(w, x), c) with two roundings, which
 // an fma chain does not restate below 2^-126.
 //
 // Arithmetic: the contract of bamd_flt_device.h.  One output = ONE 8-lane accumulator, lane j: acc_j = fmaf(w[8i + j], x[8i + j], acc_j) for i = 0 .. K/8 - 1,
@@ -142,12 +142,7 @@ __global__ void __launch_bounds__(256) matmul_mfma_flt_kernel(bamd_mma_flt_args 
 #undef F_STAGE_STORE
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------------
-// process-wide switch (default off: BAMD_PREFILL_FLT=1 or bamd_set_prefill_flt).  The kernel reads the resident weight stream and the activation rows as they
-// are — no side table — so the switch is read at each launch, not at model load
-static int g_prefill_flt = [] { const char * e = getenv("BAMD_PREFILL_FLT"); return (e && e[0] == '1') ? 1 : 0; }();
-int bamd_prefill_flt(void) { return g_prefill_flt; }
-extern "C" __attribute__((visibility("default"))) void bamd_set_prefill_flt(int on) { g_prefill_flt = on ? 1 : 0; }
-
+// (the callers ask the family's switch at each launch: bamd_prefill_mfma_type_notable, bamd_prefill_family.h)
 template <int WT, int EPI> static int launch_flt(const bamd_mma_flt_args & a, dim3 grid, hipStream_t s) {
     // (once per device and instance: the attribute belongs to the current device, and the stages of a layer-split model launch on several)
     static bool set[64] = { false };
