@@ -1,7 +1,7 @@
 """GPU: the SEQUENTIAL fallback of every double-precision sum, per kernel.  f32_rounding_safe (bamd_device.h) sends a reduction down the reference's
 order when the tree order could show in the f32 result — about 1e-5 of natural reductions, so seeded tests never take it.  The fallback is hand-written
-at nine sites, each with its own barriers and its own storage of the exponentials.  Every case here feeds one site a CONSTRUCTED input
-(tests/golden/f64_order_kats.npz, f64_softmax_kats.npz; tools/f64_order_search.py, tools/f64_softmax_search.py) whose sequential value sits within 8 units
+at ten sites, each with its own barriers and its own storage of the exponentials.  Every case here feeds one site a CONSTRUCTED input
+(tests/golden/f64_order_kats.npz, f64_teeth_kats.npz, f64_softmax_kats.npz; tools/f64_order_search.py, tools/f64_softmax_search.py) whose sequential value sits within 8 units
 of an f32 rounding boundary: any tree of the same terms lies inside the guard's band, so the fallback runs whatever the kernel's tree is.  Each case
   - asserts on the CPU that the guard fires on its input (and, where the case says so, that the neighbouring rows do NOT fire: their sequential value is
     further from a boundary than the band plus the largest reordering error);
@@ -11,14 +11,24 @@ A shape the launcher declines or routes elsewhere FAILS.  Mat-vec cases call the
 
   site                          cases
   ActPro::finish           bamd_device.h              test_fused_qkv_fast, test_generic_kernels, test_gate_up, test_lm_head_k8192, test_quantize_batch
-  ActProQ0::finish_q0      bamd_b32_device.h          test_q8_0_family, test_q8_1_family
-  attn_softmax_kernel      bamd_attention.hip         test_softmax_kernel (cached 96 / 4128, uncached 8224), test_softmax_kernel_cells (holes)
+  ActProQ0::finish_q0      bamd_b32_device.h          test_q8_0_family, test_q8_1_family, test_legacy_family_teeth; test_teeth: matvec_b32_nl_kernel and
+                                                      matvec_b32_kernel with the STORE / SILU_MUL / ARGMAX epilogues, launches whose first segment has no row-group
+                                                      for a workgroup (also matvec_q0_split_kernel), quantize_batch_b32_kernel's f32 and f16 (blob16) records
+  flt_act                  bamd_flt_device.h          test_teeth: matvec_flt_kernel<BF, PRO_NORM, EPI> (STORE / SILU_MUL / ARGMAX x two activation forms, an F32 segment
+                                                      beside an F16 one), act_bf16_test_kernel, act_batch_flt_kernel<true, BF> in front of the VALU and of the
+                                                      matrix-core prompt kernel
+  attn_softmax_kernel     bamd_attention.hip         test_softmax_kernel (cached 96 / 4128, uncached 8224), test_softmax_kernel_cells (holes)
   attn_spv_kernel<NH>      bamd_attention.hip         test_spv (NH 1, 2, 4)
   attn_batch_kernel<GQH>   bamd_attn_batch.h          test_batch_valu (attn_batch_body, rows in LDS)
   attn_fused_body          bamd_attn_fused.h          test_fused (single launch), test_colaunch (attention || wo, COLAUNCH = true)
   attn_batch_gs_kernel     bamd_attn_batch.h          test_batch_scratch_rows (the same attn_batch_body, rows in the scratch block)
   attn_batch_mfma_kernel<GQ, false>                   test_batch_mfma, padded length <= 512: rows in LDS (64 and 448 positions)
   attn_batch_mfma_kernel<GQ, true>                    test_batch_mfma, padded length > 512: rows in the scratch block (576 positions; 64 and 576 under ld 18496)
+
+Which RMSNorm cases can see a wrong VALUE (and not only a hang or a fault of the fallback): those whose vector rounds to another f32 mean and scale under the
+site's own tree.  Of f64_order_kats.npz that holds for K3072 and K4096 (both trees of tools/f64_order_search.py SITE_TREES); at K8192 the mean differs and the scale
+does not; at K256, K768 and K4096b no restated order differs.  The vectors of f64_teeth_kats.npz are chosen for it per (site, length), and tests/test_f64_teeth.py
+shows on the CPU that the expected output of every case on them is another one under the tree's mean: test_teeth, test_quantize_batch_teeth, test_legacy_family_teeth.
 
 Which attention kernel a shape lands on: the batched launches ask bamd_attention_batch_plan, whose scratch bytes are non-zero exactly when the rows live
 in the scratch block (matrix cores: ld > 512 = LONG; VALU: ld > 18432 = attn_batch_gs_kernel), and the case fails where that differs from what it names.
@@ -28,6 +38,7 @@ ratio and for cell positions), which the cases state and cannot assert.
 
 Softmax rows reach a kernel as dot products: q = c e_0 for the heads of one KV head (c = 1: the constructed row; c = 1/2: a quiet one), K rows = score x e_0
 (f16-exact), identity RoPE.  Positions behind the constructed token hold further random scores, so every token of a micro-batch has a row of its own."""
+import contextlib
 import os
 import sys
 
@@ -35,6 +46,7 @@ import numpy as np
 import pytest
 
 import booster_amd
+import f64_teeth_cases as tc
 import legacy1_ref as l1
 import legacy_ref as lg
 from booster_amd.gguf import random_kquant_tensor, random_q0_tensor, random_q1_tensor
@@ -241,6 +253,65 @@ def test_q8_0_family(bamd, po, okats):
 def test_q8_1_family(bamd, po, okats):
     """the same with Q8_1 activations: the quantiser op, matvec_b32_kernel<true>, quantize_batch_b32_kernel<.., true> at T = 3 (these types have no split-K kernel)"""
     _legacy_family(bamd, po, okats, l1, l1.Q4_1, random_q1_tensor, bamd.op_quantize_q8_1, l1.quantize_row_q8_1, (1,))
+
+
+# ---- vectors WITH TEETH (tests/golden/f64_teeth_kats.npz; the cases and both of their expectations: tests/f64_teeth_cases.py) --------------------------
+# On K4096b, K256 and K768 above every restated order rounds to the sequential f32: those cases see a hang or a fault of the fallback, not a wrong value.
+# On the vectors below the site's own tree rounds to ANOTHER f32 mean and scale, and tests/test_f64_teeth.py proves per case (CPU) that the expected output
+# under that mean differs: a kernel that skips the fallback, or sums it wrongly, fails here by value (profiles/f64_guard_paths.txt: a build with
+# -DBAMD_NO_F64_GUARD fails every one of them).
+@pytest.fixture(scope="module")
+def tkats():
+    return tc.load()
+
+
+def run_teeth(bamd, po, tkats, cid):
+    """one case of tests/f64_teeth_cases.py: the guard fires on its vector (teeth_vector, CPU), the launcher names the kernel the case names (trace_mv with the
+    device's CU count; a matrix-core prompt case: the type's launch counter moves), and three calls give the expectation of the SEQUENTIAL mean bit for bit —
+    which is not the expectation of the tree's mean"""
+    c = tc.built(po, tkats, cid)
+    assert not np.array_equal(c.want_seq.view(np.uint8), c.want_tree.view(np.uint8))
+    if c.trace:
+        segs, epi, mode, kernel = c.trace
+        tr = booster_amd.trace_mv(segs, c.K, PRO_NORM, epi, mode, n_cu=device_cus(bamd))
+        assert tr is not None and kernel in tr["kernel"], "the launcher declines or routes the shape elsewhere: %r, wanted %s" % (tr, kernel)
+    with tc.switched(bamd, c.switch) if c.switch else contextlib.nullcontext():
+        for i in range(3):
+            before = bamd.prefill_mfma_runs(c.mfma) if c.mfma is not None else 0
+            got = c.run(bamd, c.x, c.w, c.eps)
+            what = "%s, call %d" % (cid, i)
+            if c.mfma is not None:
+                assert bamd.prefill_mfma_runs(c.mfma) == before + 1, what + ": not on the matrix-core kernel"
+            if c.argmax:
+                from test_gpu_prologue_ring import argmax_keys
+                got, row = got
+                assert row == int(np.argmax(c.want_seq)) and argmax_keys(got)[row] == argmax_keys(c.want_seq).max(), what + ": row %d" % row
+            if c.want_seq.dtype == np.float32:
+                assert_bits(got, c.want_seq, what)
+            else:
+                assert got.dtype == c.want_seq.dtype and np.array_equal(got, c.want_seq), "%s: %d elements differ" % (what, int((got != c.want_seq).sum()))
+
+
+@pytest.mark.parametrize("cid", [c for c in tc.CASES if c not in tc.FAMILY_IDS and not c.startswith("quantize_batch")])
+def test_teeth(bamd, po, tkats, cid):
+    """flt_act in its three kernels (matvec_flt_kernel with every epilogue and both activation forms, act_bf16_test_kernel, act_batch_flt_kernel in front of the VALU
+    and the matrix-core prompt kernel) and the instantiations of finish_q0 that had no firing vector: the IQ4_NL code objects, the SiLU and arg-max epilogues
+    of matvec_b32_kernel (the arg-max's two barriers behind the idle waves' prologue), launches whose first segment has no row-group for a workgroup, and the
+    f16 records of quantize_batch_b32_kernel behind the matrix-core prompt kernels"""
+    run_teeth(bamd, po, tkats, cid)
+
+
+@pytest.mark.parametrize("impl", [0, 2])
+def test_quantize_batch_teeth(bamd, po, tkats, impl):
+    """test_quantize_batch on the vector of ActPro::finish's own tree at K = 4096"""
+    run_teeth(bamd, po, tkats, "quantize_batch-q4_k-impl%d" % impl)
+
+
+@pytest.mark.parametrize("cid", tc.FAMILY["q8_0"] + tc.FAMILY["q8_1"])
+def test_legacy_family_teeth(bamd, po, tkats, cid):
+    """the steps of test_q8_0_family / test_q8_1_family (the quantiser op, the mat-vec modes, the integer-dot batch; 13 rows) on the vector of finish_q0's own
+    tree at K = 4096"""
+    run_teeth(bamd, po, tkats, cid)
 
 
 # =====================================================================================================================================================

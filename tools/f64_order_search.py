@@ -13,6 +13,9 @@ n = 4096 and
       (units of f32_rounding_safe: the low 29 mantissa bits D, boundary D = 2^28).  Any other order of the same K terms is within 2 K units of
       the sequential one, i.e. inside the band 2 K + 8 in which the guard refuses the tree: the fallback runs whatever a kernel's tree is.
       tests/golden/gen_f64_guard_kats.py stores such vectors (tests/golden/f64_order_kats.npz) for tests/test_gpu_f64_guard.py.
+  (d) the tree of every RMSNorm site for any length (SITE_TREES: sum_tree_blocks = ActPro::finish = ActProQ0::finish_q0, sum_tree_flt = flt_act):
+      tests/golden/gen_f64_teeth_kats.py keeps only vectors of (c) on which the site's OWN tree rounds to another f32 mean and another f32 scale than
+      the sequential order (tests/golden/f64_teeth_kats.npz): on those a kernel that skipped its fallback gives other output bits.
 """
 import sys
 
@@ -48,6 +51,62 @@ def sum_tree(t):
         s = s + s[(i & ~15) | (15 - (i & 15))]
         tot = tot + (((s[15] + s[31]) + s[47]) + s[63])
     return float(tot)
+
+
+def wave_sum_f64(s):
+    """wave_sum_f64 (bamd_device.h) over [64] lane values: s += xor 1, s += xor 2, s += the mirror inside groups of 8 lanes, s += the mirror inside rows
+    of 16 lanes (every lane of a row then holds the row's sum), then ((lane 15 + lane 31) + lane 47) + lane 63"""
+    i = np.arange(64)
+    s = s + s[i ^ 1]
+    s = s + s[i ^ 2]
+    s = s + s[(i & ~7) | (7 - (i & 7))]
+    s = s + s[(i & ~15) | (15 - (i & 15))]
+    return float(((s[15] + s[31]) + s[47]) + s[63])
+
+
+def sum_tree_blocks(t, nwaves=8):
+    """ActPro<true>::finish (bamd_device.h) and ActProQ0<true>::finish_q0 (bamd_b32_device.h) for any K that is a multiple of 256: the two hold the same
+    statements.  issue(x, nw, K, wave) loads the blocks wave, wave + nwaves, .. (BAMD_ACT_BATCH = 4 of them), the loop behind it the batches that start
+    at wave + 4 nwaves, wave + 8 nwaves, ..: wave w owns the 256-blocks i = w (mod nwaves) in increasing order, lane l adds the elements 4l .. 4l+3 of
+    each in order; wave_sum_f64; the wave sums are added in order starting from 0 (a wave without a block contributes 0).  sum_tree is this at K = 4096"""
+    b = np.asarray(t, np.float64).reshape(-1, 64, 4)                # [block][lane][element]
+    tot = 0.0
+    for w in range(nwaves):
+        lane = np.zeros(64, np.float64)
+        for blk in range(w, b.shape[0], nwaves):
+            for c in range(4):
+                lane = lane + b[blk, :, c]
+        tot = tot + wave_sum_f64(lane)
+    return float(tot)
+
+
+def sum_tree_flt(t, nthreads=512):
+    """flt_act<true, ..> (bamd_flt_device.h) for any K that is a multiple of 256, 512 threads: thread k4 % 512 adds the float4s k4 = thread, thread + 512,
+    .. (elements 4 k4 .. 4 k4 + 3 in order); wave_sum_f64 over the 64 threads of a wave; the eight wave sums are added in order starting from 0.  Threads
+    >= K / 4 contribute 0"""
+    t = np.asarray(t, np.float64)
+    n4 = t.size // 4
+    rounds = -(-n4 // nthreads)
+    b = np.zeros((rounds * nthreads, 4), np.float64)
+    b[:n4] = t.reshape(n4, 4)
+    b = b.reshape(rounds, nthreads, 4)                             # [round][thread][element]
+    part = np.zeros(nthreads, np.float64)
+    for r in range(rounds):
+        for c in range(4):
+            part = part + b[r, :, c]
+    tot = 0.0
+    for w in range(nthreads // 64):
+        tot = tot + wave_sum_f64(part[w * 64:(w + 1) * 64])
+    return float(tot)
+
+
+# the restated tree of every RMSNorm site (tests/test_gpu_f64_guard.py's table): ActPro::finish and finish_q0 are one function
+SITE_TREES = dict(flt=sum_tree_flt, q0=sum_tree_blocks, actpro=sum_tree_blocks)
+
+
+def scale32(mean, eps):
+    """1 / sqrtf(mean + eps) in f32, as the kernels and the oracle's rms_norm compute it (ggml.c:11881)"""
+    return np.float32(1.0) / np.sqrt(np.float32(np.float32(mean) + np.float32(eps)), dtype=np.float32)
 
 
 def mean32(s):
