@@ -114,7 +114,8 @@ def test_gpu_attention_equals_the_reference_on_the_constructed_row(skat, bamd, p
     identity RoPE, head dimension 64 (scale 1/8): the kernel's scores ARE the constructed row, its guard must take the sequential order.
     (A build with -DBAMD_NO_F64_GUARD fails this test on the single-launch kernel — 44 of 64 outputs one ulp off — and the RMSNorm test above;
     the softmax + P.V kernel's own tree happens to agree with the sequential order on this row, its fallback runs all the same.)"""
-    from test_gpu_ops import oracle_attention, assert_bits
+    from bitcheck import assert_bits
+    from test_gpu_ops import oracle_attention
     H = Hkv = 1; hd = 64; n_ctx = 64; pos = 63
     s = skat["scores"]
     rng = np.random.default_rng(99)

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import booster_amd
+from bitcheck import assert_bits
 from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -24,12 +25,6 @@ import f64_softmax_search as ss  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 THETA = 500000.0
-
-
-def assert_bits(a, b, what=""):
-    a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
-    bad = np.flatnonzero(a.view(np.uint32) != b.view(np.uint32))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 def assert_cache(got, want, what):

@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 import booster_amd
-from test_gpu_attention_batch import assert_bits, assert_cache, make_inputs, rope_table
+from bitcheck import assert_bits
+from test_gpu_attention_batch import assert_cache, make_inputs, rope_table
 
 pytestmark = pytest.mark.gpu
 

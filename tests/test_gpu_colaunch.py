@@ -15,6 +15,7 @@ import pytest
 import edge_inputs as ei
 import lowbit_ref as lr
 from booster_amd import gguf
+from bitcheck import bits
 from booster_amd.gguf import random_kquant_tensor
 from test_gpu_ops import oracle_attention
 
@@ -30,10 +31,6 @@ NAN_BITS = 0x7fc00000
 # activation kinds of tests/edge_inputs.py fed through v.  The V cache is f16: `tiny_max` and `overflow_iscale` blocks (maxima of 1e-30 and 1e-37) would
 # round to zeros on the way, and the magnitudes of `huge` and `single` do not fit, so those four edges of the quantiser cannot be reached through this launch
 EDGE_AKINDS = ("random", "zero", "constant", "near_constant", "ties", "opposite_max")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def tag_of(serial, step, il):
@@ -110,8 +107,8 @@ def attention_inputs(rng, H, Hkv, hd, n_ctx):
     return q, k, v, kc, vc
 
 
-def run_case(bamd, po, t, H, Hkv, hd, n_ctx, pos, rows, lds_ld=0, serial=1, step=1, il=0, gran_kind=None, seed=0, v=None, W=None, what=""):
-    """one co-launch against the oracle; rows: a row count or one of ROW_KINDS"""
+def run_case(bamd, po, t, H, Hkv, hd, n_ctx, pos, rows, lds_ld=0, serial=1, step=1, il=0, gran_kind=None, seed=0, v=None, W=None, what="", ref=ref_mul_mat):
+    """one co-launch against the oracle; rows: a row count or one of ROW_KINDS; ref(po, t, W, rows, x): the reference mat-mul of the wo rows"""
     what = "%s type %d H %d Hkv %d hd %d n_ctx %d lds_ld %d pos %d rows %s tag (%#x, %#x, %d) granules %s" % (what, t, H, Hkv, hd, n_ctx, lds_ld, pos, rows, serial, step, il, gran_kind)
     if os.environ.get("BAMD_COLAUNCH") == "0":
         pytest.skip("the co-launch is switched off by the environment (BAMD_COLAUNCH=0)")
@@ -129,7 +126,7 @@ def run_case(bamd, po, t, H, Hkv, hd, n_ctx, pos, rows, lds_ld=0, serial=1, step
     rope = po.rope_cache(pos, hd, 500000.0)
     kc2, vc2 = kc.copy(), vc.copy()
     att, _ = oracle_attention(po, q, k, v, kc2, vc2, rope, H, Hkv, hd, n_ctx, pos, False)
-    want = ref_mul_mat(po, t, W, rows, att) + res
+    want = ref(po, t, W, rows, att) + res
     assert np.isfinite(att).all() and np.isfinite(want).all(), what + ": the expectation is not finite"
     g0 = initial_granules(gran_kind, H * hd, serial, step, il, rng)
     r = bamd.op_attention_wo(q, k, v, kc, vc, rope, H, Hkv, hd, n_ctx, pos, t, W, rows, res, lds_ld=lds_ld, serial=serial, step=step, il=il, gran_init=g0)

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import edge_inputs as E
+from bitcheck import assert_bits
 from booster_amd.gguf import random_kquant_tensor
 
 pytestmark = pytest.mark.gpu
@@ -23,16 +24,6 @@ EPS = 1e-5
 NT = 8
 FLT_MIN = 2.0 ** -126
 LOG2E = 1.4426950408889634
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 def oracle_act(po, x, norm_w):

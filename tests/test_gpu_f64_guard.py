@@ -49,6 +49,7 @@ import booster_amd
 import f64_teeth_cases as tc
 import legacy1_ref as l1
 import legacy_ref as lg
+from bitcheck import assert_bits
 from booster_amd.gguf import random_kquant_tensor, random_q0_tensor, random_q1_tensor
 from conftest import GOLDEN, ROOT
 from test_gpu_colaunch import device_cus, tag_of
@@ -64,17 +65,6 @@ GENERIC = 16                                                  # mode + 16: the g
 LD_SCRATCH = 18496                                           # the first ld beyond the VALU kernels' LDS bound (18432): attn_batch_gs_kernel.  (The matrix-core kernel moves its rows to the scratch block beyond 512 already)
 AM_MAXPOS = 512                                              # BAMD_AM_MAXPOS: the matrix-core kernel keeps its score rows in LDS up to this padded length
 N_CTX_SCRATCH = 18560
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert a.shape == b.shape and np.isfinite(b).all(), what + ": shape, or an expectation that is not finite"
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 def assert_cache(got, want, what):

@@ -6,35 +6,20 @@ restored afterwards; the launch counters (prefill_mfma_runs) tell the matrix-cor
 Tile edges of the kernel: a workgroup is 64 rows x 64 tokens, a wave 32 rows x 32 tokens (2 x 2 MFMA tiles of 16 x 16), a record group 8 rows, a stage 128 of K
 (two per record).  So the row counts below are 8, 24 (inside one wave), 32 (exactly a wave), 40 (a wave and a partial one), 64 (exactly a workgroup) and 72 (a
 partial second workgroup); the token counts 1, 16, 17, 32, 33, 64, 65 are both sides of the MFMA tile, of the wave and of the workgroup."""
-import contextlib
-
 import numpy as np
 import pytest
 
 import float_ref as fr
+from bitcheck import ADD, EPS, FILL, SILU_MUL, STORE, assert_bits, normed, silu_mul
 from booster_amd.gguf import random_float_tensor
+from mfma_harness import layer_types, prefill_switches, prompt_step, runs, two_stages_on_the_matrix_cores
+from refmodel import FLOAT, load_fixture, model_for
 from test_float_ref import stored  # noqa: F401  (fixture)
-from test_gpu_float_ops import EPS, assert_bits, normed, silu_mul
-from test_gpu_float_ref import check_step, gen, load_fixture, model_for
 
 pytestmark = pytest.mark.gpu
 F32, F16, BF16 = fr.F32, fr.F16, fr.BF16
 TYPES = [F32, F16]
-STORE, ADD, SILU_MUL = 0, 1, 2
-FILL = np.float32(-7.25)
-
-
-@contextlib.contextmanager
-def flt_switch(bamd, on=True):
-    bamd.set_prefill_flt(on)
-    try:
-        yield
-    finally:
-        bamd.set_prefill_flt(False)                 # the default
-
-
-def runs(bamd):
-    return {t: bamd.prefill_mfma_runs(t) for t in TYPES + [14]}
+COUNTED = TYPES + [14]
 
 
 def ref_batch(t, W, rows, K, A):
@@ -47,15 +32,15 @@ def test_switch_is_off_by_default_and_refuses(bamd, t):
     W = random_float_tensor(t, 256, fr.ROWS, np.random.default_rng(1))
     Wb = random_float_tensor(BF16, 256, fr.ROWS, np.random.default_rng(2))
     X = np.random.default_rng(3).standard_normal((2, 256)).astype(np.float32)
-    before = runs(bamd)
+    before = runs(bamd, COUNTED)
     with pytest.raises(bamd.BamdError, match="F32 / F16 / BF16 have no matrix-core kernel"):
         bamd.op_mul_mat_batch(t, W, fr.ROWS, 256, X, impl=2)
     with pytest.raises(bamd.BamdError, match="F32 / F16 / BF16 have no matrix-core kernel"):
         bamd.op_mul_mat_batch_seg([(t, W, fr.ROWS)], 256, X, fr.ROWS, epi=STORE, impl=2)
-    assert runs(bamd) == before
-    with flt_switch(bamd):
+    assert runs(bamd, COUNTED) == before
+    with prefill_switches(bamd, flt=True):
         got = bamd.op_mul_mat_batch(t, W, fr.ROWS, 256, X, impl=2)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
         for args in ((BF16, Wb, fr.ROWS, 256, X),):
             with pytest.raises(bamd.BamdError, match="F32 / F16 / BF16 have no matrix-core kernel"):
                 bamd.op_mul_mat_batch(*args, impl=2)
@@ -63,7 +48,7 @@ def test_switch_is_off_by_default_and_refuses(bamd, t):
                 bamd.op_mul_mat_batch_seg([(BF16, Wb, fr.ROWS)], 256, X, fr.ROWS, epi=STORE, impl=2)
         with pytest.raises(bamd.BamdError, match="impl must be 0"):
             bamd.op_mul_mat_batch(t, W, fr.ROWS, 256, X, impl=1)
-        assert runs(bamd) == after
+        assert runs(bamd, COUNTED) == after
     assert after[t] == before[t] + 1 and all(after[u] == before[u] for u in after if u != t)
     assert_bits(got, ref_batch(t, W, fr.ROWS, 256, X), "type %d" % t)
     with pytest.raises(bamd.BamdError, match="F32 / F16 / BF16 have no matrix-core kernel"):      # restored
@@ -77,7 +62,7 @@ def test_mul_mat_batch_kats(bamd, stored, t, T):
     """every stored case — K = 256, 512, 1024, 4096 and the edge matrix x edge vectors (subnormal f16 weights, f32 subnormal activations, products and partial
     sums below 2^-126, cancellation to a subnormal) — on the matrix-core kernel; the token rows cycle through the case's vectors"""
     rng = np.random.default_rng(T + t)
-    with flt_switch(bamd):
+    with prefill_switches(bamd, flt=True):
         for key, raw, xs, digest in fr.all_cases(t):
             assert str(stored[key + "_inputs_sha256"]) == digest
             dots = stored[key + "_sgemm1"]
@@ -135,7 +120,7 @@ def shape_ref(po, t, K, norm):
 @pytest.mark.parametrize("T", [1, 16, 17, 32, 33, 64, 65])      # both sides of the 16-token tile, of the wave's 32 tokens and of the workgroup's 64
 def test_mul_mat_batch_shapes(bamd, po, t, K, rows, T):
     rb = K * fr.ESIZE[t]
-    with flt_switch(bamd):
+    with prefill_switches(bamd, flt=True):
         for norm in (False, True):
             c, want = shape_ref(po, t, K, norm)
             for with_res in (False, True):
@@ -150,7 +135,7 @@ def test_mul_mat_batch_row_tile_edges(bamd, po, t, rows):
     K, T = 512, 33
     rb = K * fr.ESIZE[t]
     c, want = shape_ref(po, t, K, False)
-    with flt_switch(bamd):
+    with prefill_switches(bamd, flt=True):
         before = bamd.prefill_mfma_runs(t)
         assert_bits(bamd.op_mul_mat_batch(t, c["W"][:rows * rb], rows, K, c["X"][:T], impl=2), want[:T, :rows], "type %d rows %d" % (t, rows))
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -165,7 +150,7 @@ def test_mul_mat_batch_long_chain(bamd, po, t):
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
     res = rng.standard_normal((T, rows)).astype(np.float32)
-    with flt_switch(bamd):
+    with prefill_switches(bamd, flt=True):
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, impl=2), ref_batch(t, W, rows, K, X), "K 14336 plain")
         A = np.stack([normed(po, x, w) for x in X])
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, residual=res, impl=2), ref_batch(t, W, rows, K, A) + res, "K 14336 norm + residual")
@@ -179,7 +164,7 @@ def test_matrix_core_kernel_equals_valu_kernel(bamd, t):
     W = random_float_tensor(t, K, rows, rng, amp=4.0)
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
-    with flt_switch(bamd):
+    with prefill_switches(bamd, flt=True):
         before = bamd.prefill_mfma_runs(t)
         a = bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, impl=2)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -201,10 +186,10 @@ def test_seg_f16_beside_f32_into_one_matrix(bamd, po):
     A = np.stack([normed(po, x, w) for x in X])
     ldo = sum(rows) + 9
     want = np.concatenate([ref_batch(t, W, r, K, A) for t, W, r in zip(types, Ws, rows)], axis=1)
-    with flt_switch(bamd):
-        before = runs(bamd)
+    with prefill_switches(bamd, flt=True):
+        before = runs(bamd, COUNTED)
         got = bamd.op_mul_mat_batch_seg([(t, W, r) for t, W, r in zip(types, Ws, rows)], K, X, ldo, epi=STORE, norm_w=w, eps=EPS, impl=2, fill=FILL)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert after[F16] == before[F16] + 2 and after[F32] == before[F32] + 1 and after[14] == before[14]
     assert_bits(got[:, :sum(rows)], want, "q | k | v")
     assert (got[:, sum(rows):] == FILL).all(), "wrote behind the rows"
@@ -222,7 +207,7 @@ def test_seg_silu_mul_pair(bamd, po, t, T):
     A = np.stack([normed(po, x, w) for x in X])
     g, u = ref_batch(t, Wg, rows, K, A), ref_batch(t, Wu, rows, K, A)
     want = silu_mul(po, g.reshape(-1), u.reshape(-1)).reshape(T, rows)
-    with flt_switch(bamd):
+    with prefill_switches(bamd, flt=True):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, Wg, rows), (t, Wu, rows)], K, X, rows + 64, epi=SILU_MUL, norm_w=w, eps=EPS, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 2
@@ -240,7 +225,7 @@ def test_seg_add_with_wide_rows(bamd, po, t, ldo):
     W = random_float_tensor(t, K, rows, rng, amp=4.0)
     res = rng.standard_normal((T, ldo)).astype(np.float32)
     want = ref_batch(t, W, rows, K, X) + res[:, :rows]
-    with flt_switch(bamd):
+    with prefill_switches(bamd, flt=True):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, W, rows)], K, X, ldo, epi=ADD, residual=res, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -249,43 +234,16 @@ def test_seg_add_with_wide_rows(bamd, po, t, ldo):
 
 
 # ---- whole models against the genuine reference's llama_decode ---------------------------------------------------------------------------------------------
-def layer_types(path):
-    from booster_amd.gguf import GGUFReader
-    r = GGUFReader(path)
-    return {int(ti["type"]) for name, ti in r.tensors.items() if name.startswith("blk.") and name.endswith(".weight") and len(ti["shape"]) == 2}
-
-
-def prompt_step(bamd, cfg, capfd):
-    """(logits, counters before, counters after, load-time stderr, side-table bytes) of the prompt step of a fixture's model"""
-    fx = load_fixture(cfg)
-    _, _, n_prompt, _, n_ctx = gen.CONFIGS[cfg]
-    path = model_for(cfg, fx)
-    capfd.readouterr()
-    m = bamd.Model(path)
-    err = capfd.readouterr().err
-    try:
-        aux = m.prefill_aux_bytes()
-        ctx = bamd.Context(m, n_ctx)
-        before = runs(bamd)
-        prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
-        logits = ctx.decode(prompt, 0)
-        after = runs(bamd)
-        ctx.close()
-    finally:
-        m.close()
-    return fx, path, logits, before, after, err, aux
-
-
 @pytest.mark.parametrize("cfg", ["tiny_f16", "tiny_f32", "8bw_f16", "8bw_f32"])
 def test_whole_model_prompt_on_the_matrix_cores(bamd, cfg, monkeypatch, capfd):
     """the prompt step only, with the switch on: the reference's logits, launches of the file's layer types counted, no side table"""
+    fx = load_fixture(FLOAT, cfg)
+    path = model_for(FLOAT, cfg, fx)
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    with flt_switch(bamd):
-        fx, path, logits, before, after, err, aux = prompt_step(bamd, cfg, capfd)
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(flt=True), fam=FLOAT, cfg=cfg, fx=fx)
     assert "prompts run without the matrix-core kernels" not in err, err
     assert aux == 0
-    check_step(fx, 0, logits, cfg + " prompt on the matrix cores")
-    low = layer_types(path) & set(TYPES)
+    low = layer_types(path, TYPES)
     assert low, "the fixture holds no F32 / F16 layer matrix"
     for t in low:
         assert after[t] > before[t], "no matrix-core launch of type %d" % t
@@ -293,28 +251,15 @@ def test_whole_model_prompt_on_the_matrix_cores(bamd, cfg, monkeypatch, capfd):
 
 def test_whole_bf16_model_stays_on_the_valu_kernel(bamd, monkeypatch, capfd):
     """tiny_bf16 with the switch on: the same logits, no launch counted for F32 / F16, and the load-time note still names the missing kernel"""
+    fx = load_fixture(FLOAT, "tiny_bf16")
+    path = model_for(FLOAT, "tiny_bf16", fx)
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    with flt_switch(bamd):
-        fx, path, logits, before, after, err, aux = prompt_step(bamd, "tiny_bf16", capfd)
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(flt=True), fam=FLOAT, cfg="tiny_bf16", fx=fx)
     assert aux == 0
     assert "no matrix-core kernel" in err, err
-    check_step(fx, 0, logits, "tiny_bf16 prompt")
     assert after == before
 
 
-def test_prompt_through_two_stages_on_the_matrix_cores(bamd, monkeypatch):
+def test_prompt_through_two_stages_on_the_matrix_cores(bamd):
     """tiny_f16 through two layer-split stages (bamd_stage_prefill): the stage path takes the same routing"""
-    import test_gpu_fullsize_ref as tf
-    cfg = "tiny_f16"
-    kw, _, n_prompt, n_decode, n_ctx = gen.CONFIGS[cfg]
-
-    class _Gen:
-        CONFIGS = {cfg: (kw, n_prompt, n_decode, n_ctx)}
-    monkeypatch.setattr(tf, "load_fixture", load_fixture)
-    monkeypatch.setattr(tf, "model_for", model_for)
-    monkeypatch.setattr(tf, "gen", _Gen)
-    with flt_switch(bamd):
-        before = runs(bamd)
-        tf.run_config_through_stages(bamd, cfg, [(0, 2), (2, kw["L"])], 0)
-        after = runs(bamd)
-    assert after[F16] > before[F16], "no matrix-core launch of type %d" % F16
+    two_stages_on_the_matrix_cores(bamd, FLOAT, "tiny_f16", COUNTED, (F16,), dict(flt=True))

@@ -16,28 +16,17 @@ import numpy as np
 import pytest
 
 import lowbit_ref as lr
+from bitcheck import EPS, assert_bits
 from booster_amd.gguf import random_kquant_tensor
 
 pytestmark = pytest.mark.gpu
 TYPES = [10, 11, 12, 13, 14]                                 # Q2_K, Q3_K, Q4_K, Q5_K, Q6_K
 K, ROWS, RAGGED = 4096, 14336, 14331
 SHORT0 = 4 * 256 * 8                                         # first row of a pair that waves 4-6 stream (256 workgroups x 8 rows per wave slot)
-EPS = 1e-5
 NT = 8
 LOG2E = 1.4426950408889634
 BLOCK_BYTES = {10: 84, 11: 110, 12: 144, 13: 176, 14: 210}
 D_OFFSETS = {10: (80, 82), 11: (108,), 12: (0, 2), 13: (0, 2), 14: (208,)}   # f16 d (and dmin) of a super-block
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert a.shape == b.shape and np.isfinite(b).all(), what + ": shape, or an expectation that is not finite"
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 def ref_mv(po, t, W, rows, a):

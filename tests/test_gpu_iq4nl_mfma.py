@@ -6,43 +6,21 @@ the same bits.
 
 Tile edges of the kernel: a workgroup is 64 rows x 16 tokens, a wave 16 rows x ONE token tile of 16 (wave and workgroup token tile coincide), a record group 8
 rows."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import iq4nl_ref as nl
 import legacy_ref as lg
+from bitcheck import ADD, EPS, FILL, SILU_MUL, STORE, assert_bits, normed, silu_mul
 from booster_amd.gguf import random_iq4_nl_tensor, random_q0_tensor
-from test_gpu_iq4nl_ops import EPS, assert_bits, normed, silu_mul
-from test_gpu_iq4nl_ref import check_step, gen, load_fixture, model_for
+from mfma_harness import layer_types, no_tables_with_the_switches_off, prefill_switches, prompt_step, runs, two_stages_on_the_matrix_cores
+from refmodel import IQ4NL, load_fixture, model_for
 from test_iq4nl_ref import stored, stored_case  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
 NL = nl.IQ4_NL
 Q4_0, Q8_0, Q5_K, Q6_K = lg.Q4_0, lg.Q8_0, 13, 14
 COUNTED = [NL, Q4_0, lg.Q5_0, Q8_0, Q5_K, Q6_K]
-STORE, ADD, SILU_MUL = 0, 1, 2
-FILL = np.float32(-7.25)
-# what the library read from the environment when it was loaded: the suite is also run under BAMD_PREFILL_NL=1 / BAMD_PREFILL_Q0=1, and the tests behind this file
-# must still find those settings
-ENV_NL, ENV_Q0 = (os.environ.get(n, "")[:1] == "1" for n in ("BAMD_PREFILL_NL", "BAMD_PREFILL_Q0"))
-
-
-@contextlib.contextmanager
-def switches(bamd, on=True, q0=False):
-    bamd.set_prefill_nl(on)
-    bamd.set_prefill_q0(q0)
-    try:
-        yield
-    finally:
-        bamd.set_prefill_nl(ENV_NL)                 # the process's defaults
-        bamd.set_prefill_q0(ENV_Q0)
-
-
-def runs(bamd):
-    return {t: bamd.prefill_mfma_runs(t) for t in COUNTED}
 
 
 def ref_batch(W, rows, K, A):
@@ -53,16 +31,16 @@ def test_switch_is_off_by_default_and_refuses(bamd):
     """off: impl 2 declines the type as before and counts nothing — also with the Q8_0 family's switch on; on: it runs and counts.  (The first refusal is asked
     for before any setter call: under BAMD_PREFILL_NL=1 in the environment this test fails, by design.)"""
     blocks, xs, _ = nl.rand_case(256)
-    before = runs(bamd)
+    before = runs(bamd, COUNTED)
     with pytest.raises(bamd.BamdError, match="MFMA path: unsupported type/shape"):
         bamd.op_mul_mat_batch(NL, blocks, nl.ROWS, 256, np.stack(xs), impl=2)
-    with switches(bamd, on=False, q0=True):
+    with prefill_switches(bamd, nl=False, q0=True):
         with pytest.raises(bamd.BamdError, match="MFMA path: unsupported type/shape"):
             bamd.op_mul_mat_batch(NL, blocks, nl.ROWS, 256, np.stack(xs), impl=2)
-    assert runs(bamd) == before
-    with switches(bamd):
+    assert runs(bamd, COUNTED) == before
+    with prefill_switches(bamd, nl=True, q0=False):
         bamd.op_mul_mat_batch(NL, blocks, nl.ROWS, 256, np.stack(xs), impl=2)
-    after = runs(bamd)
+    after = runs(bamd, COUNTED)
     assert after[NL] == before[NL] + 1 and all(after[u] == before[u] for u in after if u != NL)
 
 
@@ -72,7 +50,7 @@ def test_mul_mat_batch_kats(bamd, stored, T):
     """every stored case — K = 256, 512, 4096, 11008 and the edge matrix (d negative, zero, subnormal, large; all nibbles 0 / 15) — on the matrix-core kernel.
     K = 4096 is the case a one-accumulator chain fails (tests/test_iq4nl_ref.py, tests/test_iq4nl_mfma_math.py)"""
     rng = np.random.default_rng(T + NL)
-    with switches(bamd):
+    with prefill_switches(bamd, nl=True, q0=False):
         for key, blocks, xs, digest, _ in nl.all_cases():
             dots, _, _ = stored_case(stored, key, digest)
             K = xs[0].size
@@ -118,7 +96,7 @@ def shape_ref(po, K, norm):
 @pytest.mark.parametrize("T", [1, 15, 16, 17, 32, 33, 65])      # both sides of the 16-token tile (wave = workgroup), two and four full tiles, a fifth with one token
 def test_mul_mat_batch_shapes(bamd, po, K, rows, T):
     rb = K // 32 * nl.BB
-    with switches(bamd):
+    with prefill_switches(bamd, nl=True, q0=False):
         for norm in (False, True):
             c, want = shape_ref(po, K, norm)
             for with_res in (False, True):
@@ -132,7 +110,7 @@ def test_mul_mat_batch_row_tile_edges(bamd, po, rows):
     K, T = 512, 33
     rb = K // 32 * nl.BB
     c, want = shape_ref(po, K, False)
-    with switches(bamd):
+    with prefill_switches(bamd, nl=True, q0=False):
         assert_bits(bamd.op_mul_mat_batch(NL, c["W"][:rows * rb], rows, K, c["X"][:T], impl=2), want[:T, :rows], "rows %d" % rows)
 
 
@@ -144,7 +122,7 @@ def test_mul_mat_batch_43_records(bamd, po):
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
     res = rng.standard_normal((T, rows)).astype(np.float32)
-    with switches(bamd):
+    with prefill_switches(bamd, nl=True, q0=False):
         assert_bits(bamd.op_mul_mat_batch(NL, W, rows, K, X, impl=2), ref_batch(W, rows, K, X), "K 11008 plain")
         A = np.stack([normed(po, x, w) for x in X])
         assert_bits(bamd.op_mul_mat_batch(NL, W, rows, K, X, norm_w=w, eps=EPS, residual=res, impl=2), ref_batch(W, rows, K, A) + res, "K 11008 norm + residual")
@@ -156,7 +134,7 @@ def test_matrix_core_kernel_equals_integer_dot_kernel(bamd):
     W = random_iq4_nl_tensor(K, rows, rng)
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
-    with switches(bamd):
+    with prefill_switches(bamd, nl=True, q0=False):
         before = bamd.prefill_mfma_runs(NL)
         a = bamd.op_mul_mat_batch(NL, W, rows, K, X, norm_w=w, eps=EPS, impl=2)
         assert bamd.prefill_mfma_runs(NL) == before + 1
@@ -178,10 +156,10 @@ def test_seg_two_iq4_nl_into_one_matrix(bamd, po, pad):
     A = np.stack([normed(po, x, w) for x in X])
     ldo = sum(rows) + pad
     want = np.concatenate([ref_batch(W, r, K, A) for W, r in zip(Ws, rows)], axis=1)
-    with switches(bamd):
-        before = runs(bamd)
+    with prefill_switches(bamd, nl=True, q0=False):
+        before = runs(bamd, COUNTED)
         got = bamd.op_mul_mat_batch_seg([(NL, W, r) for W, r in zip(Ws, rows)], K, X, ldo, epi=STORE, norm_w=w, eps=EPS, impl=2, fill=FILL)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert after[NL] == before[NL] + 2 and all(after[u] == before[u] for u in after if u != NL)
     assert_bits(got[:, :sum(rows)], want, "q | k")
     assert (got[:, sum(rows):] == FILL).all(), "wrote behind the rows"
@@ -195,10 +173,10 @@ def test_seg_iq4_nl_beside_q8_0_with_only_this_switch(bamd, po):
     Ws = [random_iq4_nl_tensor(K, rows[0], rng), random_iq4_nl_tensor(K, rows[1], rng), random_q0_tensor(Q8_0, K, rows[2], rng)]
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     want = np.concatenate([ref_batch(Ws[0], rows[0], K, X), ref_batch(Ws[1], rows[1], K, X), np.stack([lg.mul_mat(Q8_0, Ws[2], rows[2], K, x) for x in X])], axis=1)
-    with switches(bamd):
-        before = runs(bamd)
+    with prefill_switches(bamd, nl=True, q0=False):
+        before = runs(bamd, COUNTED)
         got = bamd.op_mul_mat_batch_seg([(NL, Ws[0], rows[0]), (NL, Ws[1], rows[1]), (Q8_0, Ws[2], rows[2])], K, X, sum(rows) + 4, epi=STORE, impl=2, fill=FILL)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert after[NL] == before[NL] + 2 and all(after[u] == before[u] for u in after if u != NL)
     assert_bits(got[:, :sum(rows)], want, "q | k | v")
     assert (got[:, sum(rows):] == FILL).all(), "wrote behind the rows"
@@ -215,7 +193,7 @@ def test_seg_silu_mul_pair(bamd, po, T):
     A = np.stack([normed(po, x, w) for x in X])
     g, u = ref_batch(Wg, rows, K, A), ref_batch(Wu, rows, K, A)
     want = silu_mul(po, g.reshape(-1), u.reshape(-1)).reshape(T, rows)
-    with switches(bamd):
+    with prefill_switches(bamd, nl=True, q0=False):
         before = bamd.prefill_mfma_runs(NL)
         got = bamd.op_mul_mat_batch_seg([(NL, Wg, rows), (NL, Wu, rows)], K, X, rows + 64, epi=SILU_MUL, norm_w=w, eps=EPS, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(NL) == before + 2
@@ -232,7 +210,7 @@ def test_seg_add_with_wide_rows(bamd, po, ldo):
     W = random_iq4_nl_tensor(K, rows, rng)
     res = rng.standard_normal((T, ldo)).astype(np.float32)
     want = ref_batch(W, rows, K, X) + res[:, :rows]
-    with switches(bamd):
+    with prefill_switches(bamd, nl=True, q0=False):
         before = bamd.prefill_mfma_runs(NL)
         got = bamd.op_mul_mat_batch_seg([(NL, W, rows)], K, X, ldo, epi=ADD, residual=res, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(NL) == before + 1
@@ -241,78 +219,28 @@ def test_seg_add_with_wide_rows(bamd, po, ldo):
 
 
 # ---- whole models against the genuine reference's llama_decode ---------------------------------------------------------------------------------------------
-def layer_types(path):
-    from booster_amd.gguf import GGUFReader
-    r = GGUFReader(path)
-    return {int(ti["type"]) for name, ti in r.tensors.items() if name.startswith("blk.") and name.endswith(".weight") and int(ti["type"]) in COUNTED}
-
-
-def prompt_step(bamd, path, capfd, on, q0=False, cfg=None, fx=None, n_prompt=None, n_ctx=None):
-    """loads the file under the switches; returns (load-time stderr, side-table bytes, counters before, counters after) of its prompt step, whose logits it checks
-    against the fixture where there is one"""
-    if cfg is not None:
-        n_prompt, _, n_ctx = gen.CONFIGS[cfg][3:]
-    capfd.readouterr()
-    with switches(bamd, on=on, q0=q0):
-        m = bamd.Model(path)
-        err = capfd.readouterr().err
-        try:
-            aux = m.prefill_aux_bytes()
-            ctx = bamd.Context(m, n_ctx)
-            before = runs(bamd)
-            prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
-            logits = ctx.decode(prompt, 0)
-            after = runs(bamd)
-            if fx is not None:
-                check_step(fx, 0, logits, "%s prompt, NL switch %d" % (cfg, on))
-            else:
-                assert np.isfinite(logits).all()
-            ctx.close()
-        finally:
-            m.close()
-    return err, aux, before, after
-
-
 @pytest.mark.parametrize("cfg", ["tiny_iq4nl", "tiny_iq4nl_mha", "tiny_iq4nl_imatrix_tied", "8bw_iq4nl"])
 def test_whole_model_prompt_on_the_matrix_cores(bamd, cfg, monkeypatch, capfd):
     """the prompt step only: tables built (IQ4_NL plus K-quant matrices need this switch alone), no load-time complaint, the counters of the file's layer types
     move — on tiny_iq4nl the Q5_K one too: each launch group of the two-form QKV reaches its own matrix-core kernel — and the logits are the reference's"""
-    fx = load_fixture(cfg)
-    path = model_for(cfg, fx)
-    low = layer_types(path)
+    fx = load_fixture(IQ4NL, cfg)
+    path = model_for(IQ4NL, cfg, fx)
+    low = layer_types(path, COUNTED)
     assert NL in low and low <= {NL, Q5_K, Q6_K}
     if cfg == "tiny_iq4nl":
         assert Q5_K in low
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    err, aux, before, after = prompt_step(bamd, path, capfd, on=True, cfg=cfg, fx=fx)
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(nl=True, q0=False), fam=IQ4NL, cfg=cfg, fx=fx)
     assert "prompts run without the matrix-core kernels" not in err, err
     assert aux > 0
     for t in low:
         assert after[t] > before[t], "no matrix-core launch of type %d" % t
-    with switches(bamd, on=False):                    # the switch off again: a fresh model of the same file builds no tables
-        m = bamd.Model(path)
-        try:
-            assert m.prefill_aux_bytes() == 0
-        finally:
-            m.close()
+    no_tables_with_the_switches_off(bamd, path, "nl", "q0")
 
 
-def test_prompt_through_two_stages_on_the_matrix_cores(bamd, monkeypatch):
+def test_prompt_through_two_stages_on_the_matrix_cores(bamd):
     """tiny_iq4nl through two layer-split stages (bamd_stage_prefill): the stage path takes the same routing"""
-    import test_gpu_fullsize_ref as tf
-    cfg = "tiny_iq4nl"
-    kw, _, _, n_prompt, n_decode, n_ctx = gen.CONFIGS[cfg]
-
-    class _Gen:
-        CONFIGS = {cfg: (kw, n_prompt, n_decode, n_ctx)}
-    monkeypatch.setattr(tf, "load_fixture", load_fixture)
-    monkeypatch.setattr(tf, "model_for", model_for)
-    monkeypatch.setattr(tf, "gen", _Gen)
-    with switches(bamd):
-        before = runs(bamd)
-        tf.run_config_through_stages(bamd, cfg, [(0, 2), (2, kw["L"])], 0)
-        after = runs(bamd)
-    assert after[NL] > before[NL] and after[Q5_K] > before[Q5_K], "%r -> %r" % (before, after)
+    two_stages_on_the_matrix_cores(bamd, IQ4NL, "tiny_iq4nl", COUNTED, (NL, Q5_K), dict(nl=True, q0=False))
 
 
 def test_a_q4_0_matrix_beside_iq4_nl_needs_its_own_switch(bamd, tmp_path, monkeypatch, capfd):
@@ -323,10 +251,10 @@ def test_a_q4_0_matrix_beside_iq4_nl_needs_its_own_switch(bamd, tmp_path, monkey
     fn = lambda n, il: gguf.Q4_0 if n == "ffn_down" else gguf.Q6_K if n == "output" else gguf.IQ4_NL
     gguf.write_synthetic_llama(path, E=512, H=8, Hkv=8, L=2, F=768, V=64, type_fn=fn, embd_type=gguf.IQ4_NL, seed=5)
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    err, aux, before, after = prompt_step(bamd, path, capfd, on=True, n_prompt=19, n_ctx=64)
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(nl=True, q0=False), n_prompt=19, n_ctx=64)
     assert aux == 0
     assert "prompts run without the matrix-core kernels" in err and "BAMD_PREFILL_Q0 is off" in err and "all-or-nothing per model" in err and "integer-dot kernel" in err, err
     assert after == before, "a launch on the matrix cores without side tables"
-    err, aux, before, after = prompt_step(bamd, path, capfd, on=True, q0=True, n_prompt=19, n_ctx=64)
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(nl=True, q0=True), n_prompt=19, n_ctx=64)
     assert "prompts run without the matrix-core kernels" not in err, err
     assert aux > 0 and after[NL] > before[NL] and after[Q4_0] > before[Q4_0]

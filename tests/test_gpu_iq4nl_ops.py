@@ -8,34 +8,13 @@ import pytest
 
 import iq4nl_ref as nl
 import legacy_ref as lg
+from bitcheck import assert_bits, EPS, normed, silu_mul
 from booster_amd.gguf import random_iq4_nl_tensor, random_q0_tensor
 from test_iq4nl_ref import stored_case, stored  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
 T = nl.IQ4_NL
-EPS = 1e-5
 MODES = (0, 1)                     # the launcher's choice and one wave per row-group: the same kernel (mode 2, split-K, is refused: below)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert np.isfinite(b).all(), what + ": the expectation is not finite"
-    assert a.shape == b.shape, what
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
-
-
-def normed(po, x, w):
-    return (po.rms_norm(x, EPS) * w).astype(np.float32)
-
-
-def silu_mul(po, g, u):
-    L = po.lib()
-    return np.array([L.bo_v_silu(float(v)) for v in g], np.float32) * u
 
 
 def ref_mul_mat(t, W, rows, K, x):
@@ -232,9 +211,9 @@ def test_mul_mat_batch(bamd, po, K, nt):
 
 # ---- attention and wo in one launch ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("H,Hkv,hd,pos,rows", [(32, 8, 128, 37, "4096"), (32, 8, 128, 446, "ragged"), (64, 8, 64, 0, "extra_max"), (16, 2, 256, 255, "extra0")])
-def test_attention_wo(bamd, po, monkeypatch, H, Hkv, hd, pos, rows):
+def test_attention_wo(bamd, po, H, Hkv, hd, pos, rows):
     """the wo role of the co-launched attention + wo kernel with an IQ4_NL wo at K = 4096, through tests/test_gpu_colaunch.py's run_case (attention role,
     granules, caches, x2) at its head layouts, positions and row kinds; the expectation of the wo rows comes from the restatement"""
     import test_gpu_colaunch as tc
-    monkeypatch.setattr(tc, "ref_mul_mat", lambda po_, t_, W, rows_, x: nl.mul_mat(W, rows_, tc.K, x))
-    tc.run_case(bamd, po, T, H, Hkv, hd, 512, pos, rows, lds_ld=512, serial=3, step=pos + 1, il=T, gran_kind="ff" if pos else None)
+    tc.run_case(bamd, po, T, H, Hkv, hd, 512, pos, rows, lds_ld=512, serial=3, step=pos + 1, il=T, gran_kind="ff" if pos else None,
+                ref=lambda po_, t_, W, rows_, x: nl.mul_mat(W, rows_, tc.K, x))

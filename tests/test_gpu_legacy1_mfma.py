@@ -4,19 +4,16 @@ tests/test_legacy1_ref.py holds to those (tests/legacy1_ref.py); bit equality th
 launch counters (prefill_mfma_runs) tell the matrix-core kernel from the integer-dot kernel, which gives the same bits.
 
 Tile edges of the kernel: a workgroup is 64 rows x 32 tokens, a wave 16 rows x two token tiles of 16, a record group 8 rows."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import legacy1_ref as l1
 import legacy_ref as lg
-import test_gpu_legacy_ref as tlr
+from bitcheck import ADD, EPS, FILL, SILU_MUL, STORE, assert_bits, normed, silu_mul
 from booster_amd.gguf import random_q0_tensor, random_q1_tensor
 from legacy1_ref import all_cases
-from test_gpu_legacy1_ops import EPS, assert_bits, normed, silu_mul
-from test_gpu_legacy1_ref import check_step, gen, load_fixture
+from mfma_harness import layer_types, no_tables_with_the_switches_off, prefill_switches, prompt_step, runs, two_stages_on_the_matrix_cores
+from refmodel import LEGACY1, load_fixture, model_for
 from test_legacy1_ref import stored, stored_case  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
@@ -24,36 +21,6 @@ Q4_1, Q5_1 = l1.Q4_1, l1.Q5_1
 Q4_0, Q5_0, Q8_0 = lg.Q4_0, lg.Q5_0, lg.Q8_0
 TYPES = [Q4_1, Q5_1]
 COUNTED = TYPES + [Q4_0, Q5_0, Q8_0, 14]
-STORE, ADD, SILU_MUL = 0, 1, 2
-FILL = np.float32(-7.25)
-# what the library read from the environment when it was loaded: the suite is also run under BAMD_PREFILL_Q1=1 / BAMD_PREFILL_Q0=1, and the tests behind this file
-# must still find those settings
-ENV_Q1, ENV_Q0 = (os.environ.get(n, "")[:1] == "1" for n in ("BAMD_PREFILL_Q1", "BAMD_PREFILL_Q0"))
-
-
-@pytest.fixture(autouse=True)
-def _these_fixtures(monkeypatch):
-    """tests/test_gpu_legacy_ref.py's model_for with the generator and the fixtures of the Q4_1 / Q5_1 files (as tests/test_gpu_legacy1_ref.py does)"""
-    monkeypatch.setattr(tlr, "gen", gen)
-    monkeypatch.setattr(tlr, "load_fixture", load_fixture)
-
-
-model_for = tlr.model_for
-
-
-@contextlib.contextmanager
-def switches(bamd, q1=True, q0=False):
-    bamd.set_prefill_q1(q1)
-    bamd.set_prefill_q0(q0)
-    try:
-        yield
-    finally:
-        bamd.set_prefill_q1(ENV_Q1)                 # the process's defaults
-        bamd.set_prefill_q0(ENV_Q0)
-
-
-def runs(bamd):
-    return {t: bamd.prefill_mfma_runs(t) for t in COUNTED}
 
 
 def ref_batch(t, W, rows, K, A):
@@ -65,16 +32,16 @@ def test_switch_is_off_by_default_and_refuses(bamd, t):
     """off: impl 2 declines the types as before and counts nothing — also with the OTHER family's switch on; on: it runs and counts.  (The first refusal is asked
     for before any setter call: under BAMD_PREFILL_Q1=1 in the environment this test fails, by design.)"""
     blocks, xs, _ = l1.rand_case(t, 256)
-    before = runs(bamd)
+    before = runs(bamd, COUNTED)
     with pytest.raises(bamd.BamdError, match="MFMA path: unsupported type/shape"):
         bamd.op_mul_mat_batch(t, blocks, l1.ROWS, 256, np.stack(xs), impl=2)
-    with switches(bamd, q1=False, q0=True):
+    with prefill_switches(bamd, q1=False, q0=True):
         with pytest.raises(bamd.BamdError, match="MFMA path: unsupported type/shape"):
             bamd.op_mul_mat_batch(t, blocks, l1.ROWS, 256, np.stack(xs), impl=2)
-    assert runs(bamd) == before
-    with switches(bamd):
+    assert runs(bamd, COUNTED) == before
+    with prefill_switches(bamd, q1=True, q0=False):
         bamd.op_mul_mat_batch(t, blocks, l1.ROWS, 256, np.stack(xs), impl=2)
-    after = runs(bamd)
+    after = runs(bamd, COUNTED)
     assert after[t] == before[t] + 1 and all(after[u] == before[u] for u in after if u != t)
 
 
@@ -85,7 +52,7 @@ def test_mul_mat_batch_kats(bamd, stored, t, T):
     """every stored case — K = 256, 512, 4096, 11008 and the edge matrix (d negative, zero, subnormal, large; m zero, negative, large; quants at both ends; Q5_1: qh
     all zeros and all ones) — on the matrix-core kernel"""
     rng = np.random.default_rng(T + t)
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         for key, blocks, xs, digest, _ in all_cases(t):
             dots, _, _ = stored_case(stored, key, digest)
             K = xs[0].size
@@ -132,7 +99,7 @@ def shape_ref(po, t, K, norm):
 @pytest.mark.parametrize("T", [1, 16, 17, 32, 33, 64, 65])      # both sides of the 16-token tile and of the 32-token workgroup
 def test_mul_mat_batch_shapes(bamd, po, t, K, rows, T):
     rb = K // 32 * l1.BB[t]
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         for norm in (False, True):
             c, want = shape_ref(po, t, K, norm)
             for with_res in (False, True):
@@ -147,7 +114,7 @@ def test_mul_mat_batch_row_tile_edges(bamd, po, t, rows):
     K, T = 512, 33
     rb = K // 32 * l1.BB[t]
     c, want = shape_ref(po, t, K, False)
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         assert_bits(bamd.op_mul_mat_batch(t, c["W"][:rows * rb], rows, K, c["X"][:T], impl=2), want[:T, :rows], "type %d rows %d" % (t, rows))
 
 
@@ -160,7 +127,7 @@ def test_mul_mat_batch_43_records(bamd, po, t):
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
     res = rng.standard_normal((T, rows)).astype(np.float32)
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, impl=2), ref_batch(t, W, rows, K, X), "K 11008 plain")
         A = np.stack([normed(po, x, w) for x in X])
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, residual=res, impl=2), ref_batch(t, W, rows, K, A) + res, "K 11008 norm + residual")
@@ -183,7 +150,7 @@ def test_s_x_of_the_f16_records_is_rounded_twice(bamd, t):
     q8[:, 2:4] = (d32.astype(np.float64) * qsum).astype(np.float16).view(np.uint8).reshape(-1, 2)
     once = l1.vec_dot_rows(t, W, q8.reshape(-1))
     assert (once.view(np.uint32) != want[1].view(np.uint32)).any(), "a once-rounded s gives the same bits: the case checks nothing"
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch(t, W, rows, K, X, impl=2)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -197,7 +164,7 @@ def test_matrix_core_kernel_equals_integer_dot_kernel(bamd, t):
     W = random_q1_tensor(t, K, rows, rng)
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         before = bamd.prefill_mfma_runs(t)
         a = bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, impl=2)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -219,10 +186,10 @@ def test_seg_q4_1_beside_q5_1_into_one_matrix(bamd, po):
     A = np.stack([normed(po, x, w) for x in X])
     ldo = sum(rows) + 9
     want = np.concatenate([ref_batch(t, W, r, K, A) for t, W, r in zip(types, Ws, rows)], axis=1)
-    with switches(bamd):
-        before = runs(bamd)
+    with prefill_switches(bamd, q1=True, q0=False):
+        before = runs(bamd, COUNTED)
         got = bamd.op_mul_mat_batch_seg([(t, W, r) for t, W, r in zip(types, Ws, rows)], K, X, ldo, epi=STORE, norm_w=w, eps=EPS, impl=2, fill=FILL)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert after[Q4_1] == before[Q4_1] + 2 and after[Q5_1] == before[Q5_1] + 1 and all(after[u] == before[u] for u in after if u not in TYPES)
     assert_bits(got[:, :sum(rows)], want, "q | k | v")
     assert (got[:, sum(rows):] == FILL).all(), "wrote behind the rows"
@@ -240,7 +207,7 @@ def test_seg_silu_mul_pair(bamd, po, t, T):
     A = np.stack([normed(po, x, w) for x in X])
     g, u = ref_batch(t, Wg, rows, K, A), ref_batch(t, Wu, rows, K, A)
     want = silu_mul(po, g.reshape(-1), u.reshape(-1)).reshape(T, rows)
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, Wg, rows), (t, Wu, rows)], K, X, rows + 64, epi=SILU_MUL, norm_w=w, eps=EPS, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 2
@@ -258,7 +225,7 @@ def test_seg_add_with_wide_rows(bamd, po, t, ldo):
     W = random_q1_tensor(t, K, rows, rng)
     res = rng.standard_normal((T, ldo)).astype(np.float32)
     want = ref_batch(t, W, rows, K, X) + res[:, :rows]
-    with switches(bamd):
+    with prefill_switches(bamd, q1=True, q0=False):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, W, rows)], K, X, ldo, epi=ADD, residual=res, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -272,11 +239,11 @@ def test_seg_q4_0_beside_q4_1_is_still_refused(bamd):
     rng = np.random.default_rng(828)
     segs = [(Q4_0, random_q0_tensor(Q4_0, K, rows[0], rng), rows[0]), (Q4_0, random_q0_tensor(Q4_0, K, rows[1], rng), rows[1]), (Q4_1, random_q1_tensor(Q4_1, K, rows[2], rng), rows[2])]
     X = rng.standard_normal((T, K)).astype(np.float32)
-    with switches(bamd, q1=True, q0=True):
-        before = runs(bamd)
+    with prefill_switches(bamd, q1=True, q0=True):
+        before = runs(bamd, COUNTED)
         with pytest.raises(bamd.BamdError, match="different activation forms"):
             bamd.op_mul_mat_batch_seg(segs, K, X, sum(rows), epi=STORE, impl=2)
-        assert runs(bamd) == before
+        assert runs(bamd, COUNTED) == before
 
 
 def test_q4_0_gate_up_beside_a_q4_1_down_matrix(bamd, po):
@@ -293,12 +260,12 @@ def test_q4_0_gate_up_beside_a_q4_1_down_matrix(bamd, po):
     h = silu_mul(po, g.reshape(-1), u.reshape(-1)).reshape(T, F).astype(np.float32)
     res = rng.standard_normal((T, E)).astype(np.float32)
     want = ref_batch(Q4_1, Wd, E, F, h) + res
-    with switches(bamd, q1=True, q0=True):
-        before = runs(bamd)
+    with prefill_switches(bamd, q1=True, q0=True):
+        before = runs(bamd, COUNTED)
         got_h = bamd.op_mul_mat_batch_seg([(Q4_0, Wg, F), (Q4_0, Wu, F)], E, X, F, epi=SILU_MUL, norm_w=w, eps=EPS, impl=2)
-        mid = runs(bamd)
+        mid = runs(bamd, COUNTED)
         got = bamd.op_mul_mat_batch_seg([(Q4_1, Wd, E)], F, got_h, E, epi=ADD, residual=res, impl=2)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert mid[Q4_0] == before[Q4_0] + 2 and mid[Q4_1] == before[Q4_1]
     assert after[Q4_1] == mid[Q4_1] + 1 and after[Q4_0] == mid[Q4_0]
     assert_bits(got_h, h, "silu(gate) * up, Q4_0")
@@ -306,97 +273,49 @@ def test_q4_0_gate_up_beside_a_q4_1_down_matrix(bamd, po):
 
 
 # ---- whole models against the genuine reference's llama_decode ---------------------------------------------------------------------------------------------
-def layer_types(path):
-    from booster_amd.gguf import GGUFReader
-    r = GGUFReader(path)
-    return {int(ti["type"]) for name, ti in r.tensors.items() if name.startswith("blk.") and name.endswith(".weight") and int(ti["type"]) in COUNTED[:5]}
-
-
-def prompt_step(bamd, cfg, fx, path, capfd, q1, q0):
-    """loads the file under the switches; returns (load-time stderr, side-table bytes, counters before, counters after) of its prompt step, whose logits it checks"""
-    _, _, n_prompt, _, n_ctx = gen.CONFIGS[cfg]
-    capfd.readouterr()
-    with switches(bamd, q1=q1, q0=q0):
-        m = bamd.Model(path)
-        err = capfd.readouterr().err
-        try:
-            aux = m.prefill_aux_bytes()
-            ctx = bamd.Context(m, n_ctx)
-            before = runs(bamd)
-            prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
-            logits = ctx.decode(prompt, 0)
-            after = runs(bamd)
-            check_step(fx, 0, logits, "%s prompt, Q1 switch %d, Q0 switch %d" % (cfg, q1, q0))
-            ctx.close()
-        finally:
-            m.close()
-    return err, aux, before, after
-
-
-def no_tables_with_the_switches_off(bamd, path):
-    with switches(bamd, q1=False, q0=False):          # the switches off again: a fresh model of the same file builds no tables
-        m = bamd.Model(path)
-        try:
-            assert m.prefill_aux_bytes() == 0
-        finally:
-            m.close()
-
-
 @pytest.mark.parametrize("cfg", ["tiny_q4_1", "tiny_q5_1", "8bw_q4_1", "8bw_q5_1"])
 def test_whole_model_prompt_on_the_matrix_cores(bamd, cfg, monkeypatch, capfd):
     """the prompt step only: tables built, no load-time complaint, the counters of the file's layer types move, logits bit-identical"""
-    fx = load_fixture(cfg)
-    path = model_for(cfg, fx)
-    low = layer_types(path)
+    fx = load_fixture(LEGACY1, cfg)
+    path = model_for(LEGACY1, cfg, fx)
+    low = layer_types(path, COUNTED[:5])
     assert low and low <= set(TYPES)
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    err, aux, before, after = prompt_step(bamd, cfg, fx, path, capfd, q1=True, q0=False)
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(q1=True, q0=False), fam=LEGACY1, cfg=cfg, fx=fx)
     assert "prompts run without the matrix-core kernels" not in err, err
     assert aux > 0
     for t in low:
         assert after[t] > before[t], "no matrix-core launch of type %d" % t
-    no_tables_with_the_switches_off(bamd, path)
+    no_tables_with_the_switches_off(bamd, path, "q1", "q0")
 
 
 @pytest.mark.parametrize("cfg,t0,t1", [("tiny_q4_0_imat", Q4_0, Q4_1), ("tiny_q5_0_imat", Q5_0, Q5_1)])
 def test_imatrix_file_needs_both_switches(bamd, cfg, t0, t1, monkeypatch, capfd):
     """a Q4_0 / Q5_0 file made with an importance matrix (ffn_down of layer 0 is Q4_1 / Q5_1).  Both switches on: tables, both families' counters move.  Only the
     Q0 switch: no tables, the reason names the missing switch, nothing on the matrix cores.  Same logits — the reference's — either way"""
-    fx = load_fixture(cfg)
-    path = model_for(cfg, fx)
-    assert layer_types(path) == {t0, t1}
+    fx = load_fixture(LEGACY1, cfg)
+    path = model_for(LEGACY1, cfg, fx)
+    assert layer_types(path, COUNTED[:5]) == {t0, t1}
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    err, aux, before, after = prompt_step(bamd, cfg, fx, path, capfd, q1=True, q0=True)
+    step = lambda q1, q0: prompt_step(bamd, path, capfd, COUNTED, dict(q1=q1, q0=q0), fam=LEGACY1, cfg=cfg, fx=fx)
+    err, aux, before, after = step(q1=True, q0=True)
     assert "prompts run without the matrix-core kernels" not in err, err
     assert aux > 0
     assert after[t0] > before[t0] and after[t1] > before[t1], "both families on the matrix cores: %r -> %r" % (before, after)
-    err, aux, before, after = prompt_step(bamd, cfg, fx, path, capfd, q1=False, q0=True)
+    err, aux, before, after = step(q1=False, q0=True)
     assert aux == 0
     assert "prompts run without the matrix-core kernels" in err and "BAMD_PREFILL_Q1 is off" in err and "all-or-nothing per model" in err and "integer-dot kernel" in err, err
     assert after == before, "a launch on the matrix cores without side tables"
-    err, aux, before, after = prompt_step(bamd, cfg, fx, path, capfd, q1=True, q0=False)
+    err, aux, before, after = step(q1=True, q0=False)
     assert aux == 0
     assert "prompts run without the matrix-core kernels" in err and "BAMD_PREFILL_Q0 is off" in err, err
     assert after == before
-    no_tables_with_the_switches_off(bamd, path)
+    no_tables_with_the_switches_off(bamd, path, "q1", "q0")
 
 
-def test_prompt_through_two_stages_on_the_matrix_cores(bamd, monkeypatch):
+def test_prompt_through_two_stages_on_the_matrix_cores(bamd):
     """tiny_q5_1 through two layer-split stages (bamd_stage_prefill): the stage path takes the same routing"""
-    import test_gpu_fullsize_ref as tf
     cfg = "tiny_q5_1"
-    kw, _, n_prompt, n_decode, n_ctx = gen.CONFIGS[cfg]
-
-    class _Gen:
-        CONFIGS = {cfg: (kw, n_prompt, n_decode, n_ctx)}
-    monkeypatch.setattr(tf, "load_fixture", load_fixture)
-    monkeypatch.setattr(tf, "model_for", model_for)
-    monkeypatch.setattr(tf, "gen", _Gen)
-    low = layer_types(model_for(cfg, load_fixture(cfg)))
+    low = layer_types(model_for(LEGACY1, cfg, load_fixture(LEGACY1, cfg)), COUNTED[:5])
     assert low
-    with switches(bamd):
-        before = runs(bamd)
-        tf.run_config_through_stages(bamd, cfg, [(0, 2), (2, kw["L"])], 0)
-        after = runs(bamd)
-    for t in low:
-        assert after[t] > before[t], "no matrix-core launch of type %d" % t
+    two_stages_on_the_matrix_cores(bamd, LEGACY1, cfg, COUNTED, low, dict(q1=True, q0=False))

@@ -8,38 +8,18 @@ import numpy as np
 import pytest
 
 import legacy1_ref as l1
+from bitcheck import assert_bits, EPS, normed, silu_mul
 from booster_amd.gguf import random_kquant_tensor, random_q0_tensor, random_q1_tensor
 from legacy1_ref import all_cases
 from test_legacy1_ref import stored_case, stored  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
 TYPES = list(l1.TYPES)
-EPS = 1e-5
 MODES = (0, 1)                     # the launcher's choice and one wave per row-group; split-K (mode 2) does not exist for these types
 # the batched kernel takes token tiles of 8 while 8 activation images fit the LDS: 8 * blob bytes(K) <= 160 KB with blob bytes = 292 * K / 256 rounded up to 16
 # (bamd_launch_matmul_batch_b32), i.e. up to K = 17920 (70 records); K = 18176 is the first row length that takes tiles of 4
 K_TILE4 = 18176
 assert 8 * ((292 * (K_TILE4 // 256 - 1) + 15) // 16 * 16) <= 160 * 1024 < 8 * ((292 * (K_TILE4 // 256) + 15) // 16 * 16)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert np.isfinite(b).all(), what + ": the expectation is not finite"
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
-
-
-def normed(po, x, w):
-    return (po.rms_norm(x, EPS) * w).astype(np.float32)
-
-
-def silu_mul(po, g, u):
-    L = po.lib()
-    return np.array([L.bo_v_silu(float(v)) for v in g], np.float32) * u
 
 
 @functools.lru_cache(maxsize=None)
@@ -287,16 +267,16 @@ def test_matrix_core_path_refuses_the_type(bamd, t):
 # ---- attention and wo in one launch ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("t", TYPES)
 @pytest.mark.parametrize("H,Hkv,hd,pos,rows", [(32, 8, 128, 37, "4096"), (32, 8, 128, 446, "ragged"), (64, 8, 64, 0, "extra_max"), (64, 8, 64, 70, "extra0")])
-def test_attention_wo(bamd, po, monkeypatch, t, H, Hkv, hd, pos, rows):
+def test_attention_wo(bamd, po, t, H, Hkv, hd, pos, rows):
     """the wo role of the co-launched attention + wo kernel with a Q4_1 / Q5_1 wo at K = 4096, heads of 64 and 128, through tests/test_gpu_colaunch.py's
     run_case (attention role, granules, caches, x2 against the oracle; the give-up counter is 0); the expectation of the wo rows comes from the restatement.
     Then the same output from two launches: the attention output the granules carry through the ordinary mat-vec with the residual"""
     import test_gpu_colaunch as tc
-    monkeypatch.setattr(tc, "ref_mul_mat", lambda po_, t_, W, rows_, x: l1.mul_mat(t_, W, rows_, tc.K, x))
     n = tc.wo_rows(rows, tc.device_cus(bamd), H)
     rng = np.random.default_rng([t, H, pos])
     W = random_q1_tensor(t, tc.K, n, rng)
-    r = tc.run_case(bamd, po, t, H, Hkv, hd, 512, pos, rows, lds_ld=512, serial=3, step=pos + 1, il=t, gran_kind="ff" if pos else None, W=W)
+    r = tc.run_case(bamd, po, t, H, Hkv, hd, 512, pos, rows, lds_ld=512, serial=3, step=pos + 1, il=t, gran_kind="ff" if pos else None, W=W,
+                    ref=lambda po_, t_, W_, rows_, x: l1.mul_mat(t_, W_, rows_, tc.K, x))
     assert r["gave_up"] == 0 and not r["declined"]
     att = (r["gran"] & np.uint64(0xffffffff)).astype(np.uint32).view(np.float32)
     res = np.random.default_rng([0, t, H, Hkv, hd, pos, n])          # run_case's generator: replay its draws up to the residual

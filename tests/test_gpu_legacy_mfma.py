@@ -4,36 +4,21 @@ tests/test_legacy_ref.py holds to those (tests/legacy_ref.py); bit equality thro
 counters (prefill_mfma_runs) tell the matrix-core kernel from the integer-dot kernel, which gives the same bits.
 
 Tile edges of the kernel: a workgroup is 64 rows x 32 tokens, a wave 16 rows x two token tiles of 16, a record group 8 rows."""
-import contextlib
-
 import numpy as np
 import pytest
 
 import legacy_ref as lg
+from bitcheck import ADD, EPS, FILL, SILU_MUL, STORE, assert_bits, normed, silu_mul
 from booster_amd.gguf import random_q0_tensor
 from legacy_ref import all_cases
-from test_gpu_legacy_ops import EPS, assert_bits, normed, silu_mul
-from test_gpu_legacy_ref import check_step, gen, load_fixture, model_for
+from mfma_harness import layer_types, no_tables_with_the_switches_off, prefill_switches, prompt_step, runs, two_stages_on_the_matrix_cores
+from refmodel import LEGACY, load_fixture, model_for
 from test_legacy_ref import stored, stored_case  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
 Q4_0, Q5_0, Q8_0 = lg.Q4_0, lg.Q5_0, lg.Q8_0
 TYPES = [Q8_0, Q4_0, Q5_0]
-STORE, ADD, SILU_MUL = 0, 1, 2
-FILL = np.float32(-7.25)
-
-
-@contextlib.contextmanager
-def q0_switch(bamd, on=True):
-    bamd.set_prefill_q0(on)
-    try:
-        yield
-    finally:
-        bamd.set_prefill_q0(False)                  # the default
-
-
-def runs(bamd):
-    return {t: bamd.prefill_mfma_runs(t) for t in TYPES + [14]}
+COUNTED = TYPES + [14]
 
 
 def ref_batch(t, W, rows, K, A):
@@ -44,13 +29,13 @@ def ref_batch(t, W, rows, K, A):
 def test_switch_is_off_by_default_and_refuses(bamd, t):
     """off: impl 2 declines the types as before and counts nothing; on: it runs and counts"""
     blocks, xs, _ = lg.rand_case(t, 256)
-    before = runs(bamd)
+    before = runs(bamd, COUNTED)
     with pytest.raises(bamd.BamdError, match="MFMA path: unsupported type/shape"):
         bamd.op_mul_mat_batch(t, blocks, lg.ROWS, 256, np.stack(xs), impl=2)
-    assert runs(bamd) == before
-    with q0_switch(bamd):
+    assert runs(bamd, COUNTED) == before
+    with prefill_switches(bamd, q0=True):
         bamd.op_mul_mat_batch(t, blocks, lg.ROWS, 256, np.stack(xs), impl=2)
-    after = runs(bamd)
+    after = runs(bamd, COUNTED)
     assert after[t] == before[t] + 1 and all(after[u] == before[u] for u in after if u != t)
 
 
@@ -60,7 +45,7 @@ def test_switch_is_off_by_default_and_refuses(bamd, t):
 def test_mul_mat_batch_kats(bamd, stored, t, T):
     """every stored case — K = 256, 512, 4096, 11008 and the edge matrix (weight byte -128, all-zero blocks, subnormal and zero f16 d) — on the matrix-core kernel"""
     rng = np.random.default_rng(T + t)
-    with q0_switch(bamd):
+    with prefill_switches(bamd, q0=True):
         for key, blocks, xs, digest, _ in all_cases(t):
             dots, _, _ = stored_case(stored, key, digest)
             K = xs[0].size
@@ -107,7 +92,7 @@ def shape_ref(po, t, K, norm):
 @pytest.mark.parametrize("T", [1, 16, 17, 32, 33, 64, 65])      # both sides of the 16-token tile and of the 32-token workgroup
 def test_mul_mat_batch_shapes(bamd, po, t, K, rows, T):
     rb = K // 32 * lg.BB[t]
-    with q0_switch(bamd):
+    with prefill_switches(bamd, q0=True):
         for norm in (False, True):
             c, want = shape_ref(po, t, K, norm)
             for with_res in (False, True):
@@ -122,7 +107,7 @@ def test_mul_mat_batch_row_tile_edges(bamd, po, t, rows):
     K, T = 512, 33
     rb = K // 32 * lg.BB[t]
     c, want = shape_ref(po, t, K, False)
-    with q0_switch(bamd):
+    with prefill_switches(bamd, q0=True):
         assert_bits(bamd.op_mul_mat_batch(t, c["W"][:rows * rb], rows, K, c["X"][:T], impl=2), want[:T, :rows], "type %d rows %d" % (t, rows))
 
 
@@ -135,7 +120,7 @@ def test_mul_mat_batch_43_records(bamd, po, t):
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
     res = rng.standard_normal((T, rows)).astype(np.float32)
-    with q0_switch(bamd):
+    with prefill_switches(bamd, q0=True):
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, impl=2), ref_batch(t, W, rows, K, X), "K 11008 plain")
         A = np.stack([normed(po, x, w) for x in X])
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, residual=res, impl=2), ref_batch(t, W, rows, K, A) + res, "K 11008 norm + residual")
@@ -148,7 +133,7 @@ def test_matrix_core_kernel_equals_integer_dot_kernel(bamd, t):
     W = random_q0_tensor(t, K, rows, rng)
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
-    with q0_switch(bamd):
+    with prefill_switches(bamd, q0=True):
         before = bamd.prefill_mfma_runs(t)
         a = bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, impl=2)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -170,10 +155,10 @@ def test_seg_q4_0_beside_q8_0_into_one_matrix(bamd, po):
     A = np.stack([normed(po, x, w) for x in X])
     ldo = sum(rows) + 9
     want = np.concatenate([ref_batch(t, W, r, K, A) for t, W, r in zip(types, Ws, rows)], axis=1)
-    with q0_switch(bamd):
-        before = runs(bamd)
+    with prefill_switches(bamd, q0=True):
+        before = runs(bamd, COUNTED)
         got = bamd.op_mul_mat_batch_seg([(t, W, r) for t, W, r in zip(types, Ws, rows)], K, X, ldo, epi=STORE, norm_w=w, eps=EPS, impl=2, fill=FILL)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert after[Q4_0] == before[Q4_0] + 1 and after[Q8_0] == before[Q8_0] + 2 and after[Q5_0] == before[Q5_0]
     assert_bits(got[:, :sum(rows)], want, "q | k | v")
     assert (got[:, sum(rows):] == FILL).all(), "wrote behind the rows"
@@ -191,7 +176,7 @@ def test_seg_silu_mul_pair(bamd, po, t, T):
     A = np.stack([normed(po, x, w) for x in X])
     g, u = ref_batch(t, Wg, rows, K, A), ref_batch(t, Wu, rows, K, A)
     want = silu_mul(po, g.reshape(-1), u.reshape(-1)).reshape(T, rows)
-    with q0_switch(bamd):
+    with prefill_switches(bamd, q0=True):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, Wg, rows), (t, Wu, rows)], K, X, rows + 64, epi=SILU_MUL, norm_w=w, eps=EPS, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 2
@@ -209,7 +194,7 @@ def test_seg_add_with_wide_rows(bamd, po, t, ldo):
     W = random_q0_tensor(t, K, rows, rng)
     res = rng.standard_normal((T, ldo)).astype(np.float32)
     want = ref_batch(t, W, rows, K, X) + res[:, :rows]
-    with q0_switch(bamd):
+    with prefill_switches(bamd, q0=True):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, W, rows)], K, X, ldo, epi=ADD, residual=res, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -218,62 +203,25 @@ def test_seg_add_with_wide_rows(bamd, po, t, ldo):
 
 
 # ---- whole models against the genuine reference's llama_decode ---------------------------------------------------------------------------------------------
-def layer_types(path):
-    from booster_amd.gguf import GGUFReader
-    r = GGUFReader(path)
-    low = {int(ti["type"]) for name, ti in r.tensors.items() if name.startswith("blk.") and name.endswith(".weight") and int(ti["type"]) in TYPES}
-    assert low, "the fixture holds no Q8_0 / Q4_0 / Q5_0 layer matrix"
-    return low
-
-
 @pytest.mark.parametrize("cfg", ["tiny_q8_0", "tiny_q4_0", "tiny_q5_0", "8bw_q5_0", "l2w_q5_0", "8b_q4_0"])
 def test_whole_model_prompt_on_the_matrix_cores(bamd, cfg, monkeypatch, capfd):
     """the prompt step only (8b_q4_0: the one full-size case, a 128-token prompt = four token tiles of 32)"""
-    fx = load_fixture(cfg)
-    _, _, n_prompt, _, n_ctx = gen.CONFIGS[cfg]
-    path = model_for(cfg, fx)
-    low = layer_types(path)
+    fx = load_fixture(LEGACY, cfg)
+    path = model_for(LEGACY, cfg, fx)
+    low = layer_types(path, TYPES)
+    assert low, "the fixture holds no Q8_0 / Q4_0 / Q5_0 layer matrix"
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    capfd.readouterr()
-    with q0_switch(bamd):
-        m = bamd.Model(path)
-        err = capfd.readouterr().err
-        try:
-            assert "prompts run without the matrix-core kernels" not in err, err
-            assert m.prefill_aux_bytes() > 0
-            ctx = bamd.Context(m, n_ctx)
-            before = runs(bamd)
-            prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
-            logits = ctx.decode(prompt, 0)
-            after = runs(bamd)
-            check_step(fx, 0, logits, cfg + " prompt on the matrix cores")
-            for t in low:
-                assert after[t] > before[t], "no matrix-core launch of type %d" % t
-            ctx.close()
-        finally:
-            m.close()
-    m = bamd.Model(path)                              # the switch off again: a fresh model of the same file builds no tables
-    try:
-        assert m.prefill_aux_bytes() == 0
-    finally:
-        m.close()
-
-
-def test_prompt_through_two_stages_on_the_matrix_cores(bamd, monkeypatch):
-    """tiny_q5_0 through two layer-split stages (bamd_stage_prefill): the stage path takes the same routing"""
-    import test_gpu_fullsize_ref as tf
-    cfg = "tiny_q5_0"
-    kw, _, n_prompt, n_decode, n_ctx = gen.CONFIGS[cfg]
-
-    class _Gen:
-        CONFIGS = {cfg: (kw, n_prompt, n_decode, n_ctx)}
-    monkeypatch.setattr(tf, "load_fixture", load_fixture)
-    monkeypatch.setattr(tf, "model_for", model_for)
-    monkeypatch.setattr(tf, "gen", _Gen)
-    low = layer_types(model_for(cfg, load_fixture(cfg)))
-    with q0_switch(bamd):
-        before = runs(bamd)
-        tf.run_config_through_stages(bamd, cfg, [(0, 2), (2, kw["L"])], 0)
-        after = runs(bamd)
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(q0=True), fam=LEGACY, cfg=cfg, fx=fx)
+    assert "prompts run without the matrix-core kernels" not in err, err
+    assert aux > 0
     for t in low:
         assert after[t] > before[t], "no matrix-core launch of type %d" % t
+    no_tables_with_the_switches_off(bamd, path, "q0")
+
+
+def test_prompt_through_two_stages_on_the_matrix_cores(bamd):
+    """tiny_q5_0 through two layer-split stages (bamd_stage_prefill): the stage path takes the same routing"""
+    cfg = "tiny_q5_0"
+    low = layer_types(model_for(LEGACY, cfg, load_fixture(LEGACY, cfg)), TYPES)
+    assert low, "the fixture holds no Q8_0 / Q4_0 / Q5_0 layer matrix"
+    two_stages_on_the_matrix_cores(bamd, LEGACY, cfg, COUNTED, low, dict(q0=True))

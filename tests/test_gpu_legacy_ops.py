@@ -8,34 +8,14 @@ import numpy as np
 import pytest
 
 import legacy_ref as lg
+from bitcheck import assert_bits, EPS, normed, silu_mul
 from booster_amd.gguf import random_q0_tensor
 from legacy_ref import all_cases
 from test_legacy_ref import stored_case, stored  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
 TYPES = list(lg.TYPES)
-EPS = 1e-5
 MODES = (0, 1, 2)                  # the launcher's choice, one wave per row-group, split-K (no fast-family instances exist for these types)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert np.isfinite(b).all(), what + ": the expectation is not finite"
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
-
-
-def normed(po, x, w):
-    return (po.rms_norm(x, EPS) * w).astype(np.float32)
-
-
-def silu_mul(po, g, u):
-    L = po.lib()
-    return np.array([L.bo_v_silu(float(v)) for v in g], np.float32) * u
 
 
 @functools.lru_cache(maxsize=None)
@@ -260,9 +240,9 @@ def test_matrix_core_path_refuses_the_type(bamd, t):
 # ---- attention and wo in one launch ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("t", [lg.Q8_0, lg.Q4_0, lg.Q5_0])
 @pytest.mark.parametrize("H,Hkv,hd,pos,rows", [(32, 8, 128, 37, "4096"), (32, 8, 128, 446, "ragged"), (64, 8, 64, 0, "extra_max"), (16, 2, 256, 255, "extra0")])
-def test_attention_wo(bamd, po, monkeypatch, t, H, Hkv, hd, pos, rows):
+def test_attention_wo(bamd, po, t, H, Hkv, hd, pos, rows):
     """the wo role of the co-launched attention + wo kernel with a Q8_0 / Q4_0 / Q5_0 wo, through tests/test_gpu_colaunch.py's run_case (attention role, granules,
     caches, x2) at its head layouts, positions and row kinds; the expectation of the wo rows comes from the restatement"""
     import test_gpu_colaunch as tc
-    monkeypatch.setattr(tc, "ref_mul_mat", lambda po_, t_, W, rows_, x: lg.mul_mat(t_, W, rows_, tc.K, x))
-    tc.run_case(bamd, po, t, H, Hkv, hd, 512, pos, rows, lds_ld=512, serial=3, step=pos + 1, il=t, gran_kind="ff" if pos else None)
+    tc.run_case(bamd, po, t, H, Hkv, hd, 512, pos, rows, lds_ld=512, serial=3, step=pos + 1, il=t, gran_kind="ff" if pos else None,
+                ref=lambda po_, t_, W, rows_, x: lg.mul_mat(t_, W, rows_, tc.K, x))

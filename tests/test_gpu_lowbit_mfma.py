@@ -2,46 +2,33 @@
 Every expectation is the genuine reference's stored output (tests/golden/lowbit_kats.npz, tests/golden/lowbit_*.bgld) or the numpy restatement that
 tests/test_lowbit_ref.py holds to those (tests/lowbit_ref.py); bit equality throughout.  The switch is set through the setter and restored afterwards; the
 launch counters (prefill_mfma_runs) tell the matrix-core kernel from the integer-dot kernel, which gives the same bits."""
-import contextlib
-
 import numpy as np
 import pytest
 
 import lowbit_ref as lr
+from bitcheck import ADD, EPS, FILL, SILU_MUL, assert_bits, normed, silu_mul
 from booster_amd.gguf import random_kquant_tensor
 from lowbit_ref import all_cases
-from test_gpu_lowbit_ops import EPS, assert_bits, normed
-from test_gpu_lowbit_ref import check_step, gen, load_fixture, model_for
-from test_gpu_segments import ADD, FILL, Q2, Q3, Q6, SILU_MUL, batch_inputs, qkv_batch_case, ref_mul_mat, silu_mul
+from mfma_harness import layer_types, no_tables_with_the_switches_off, prefill_switches, prompt_step, runs
+from refmodel import LOWBIT, load_fixture, model_for
+from test_gpu_segments import Q2, Q3, Q6, batch_inputs, qkv_batch_case, ref_mul_mat
 from test_lowbit_ref import stored, stored_case  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
 TYPES = [Q2, Q3]
-
-
-@contextlib.contextmanager
-def lowbit(bamd, on=True):
-    bamd.set_prefill_lowbit(on)
-    try:
-        yield
-    finally:
-        bamd.set_prefill_lowbit(False)              # the default
-
-
-def runs(bamd):
-    return {t: bamd.prefill_mfma_runs(t) for t in (Q2, Q3, Q6)}
+COUNTED = [Q2, Q3, Q6]
 
 
 def test_switch_is_off_by_default_and_refuses(bamd):
     """off: impl 2 declines the types as before and counts nothing; on: it runs and counts"""
     blocks, xs, _ = lr.rand_case(Q3, 256)
-    before = runs(bamd)
+    before = runs(bamd, COUNTED)
     with pytest.raises(bamd.BamdError, match="MFMA path: unsupported type/shape"):
         bamd.op_mul_mat_batch(Q3, blocks, lr.ROWS, 256, np.stack(xs), impl=2)
-    assert runs(bamd) == before
-    with lowbit(bamd):
+    assert runs(bamd, COUNTED) == before
+    with prefill_switches(bamd, lowbit=True):
         bamd.op_mul_mat_batch(Q3, blocks, lr.ROWS, 256, np.stack(xs), impl=2)
-    assert runs(bamd)[Q3] == before[Q3] + 1
+    assert runs(bamd, COUNTED)[Q3] == before[Q3] + 1
 
 
 # ---- the reference's own outputs ---------------------------------------------------------------------------------------------------------------
@@ -50,7 +37,7 @@ def test_switch_is_off_by_default_and_refuses(bamd):
 def test_mul_mat_batch_kats(bamd, stored, t, T):
     """the stored cases of test_gpu_lowbit_ops.test_mul_mat_batch_kats — K = 256, 1024, 14336, 11008 and the edge matrices — on the matrix-core kernel"""
     rng = np.random.default_rng(T + t)
-    with lowbit(bamd):
+    with prefill_switches(bamd, lowbit=True):
         for key, blocks, xs, digest, _ in all_cases(t):
             dots, _, _ = stored_case(stored, key, digest)
             K = xs[0].size
@@ -98,7 +85,7 @@ def shape_ref(po, t, K, norm):
 @pytest.mark.parametrize("T", [1, 16, 17, 64, 65])    # the 16- and 64-token tile edges
 def test_mul_mat_batch_shapes(bamd, po, t, K, rows, T):
     rb = K // 256 * lr.BB[t]
-    with lowbit(bamd):
+    with prefill_switches(bamd, lowbit=True):
         for norm in (False, True):
             c, want = shape_ref(po, t, K, norm)
             for with_res in (False, True):
@@ -116,7 +103,7 @@ def test_mul_mat_batch_43_super_blocks(bamd, po, t):
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
     res = rng.standard_normal((T, rows)).astype(np.float32)
-    with lowbit(bamd):
+    with prefill_switches(bamd, lowbit=True):
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, impl=2), ref_mul_mat(po, t, W, rows, K, X), "K 11008 plain")
         A = np.stack([normed(po, x, w) for x in X])
         assert_bits(bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, residual=res, impl=2), ref_mul_mat(po, t, W, rows, K, A) + res, "K 11008 norm + residual")
@@ -129,7 +116,7 @@ def test_matrix_core_kernel_equals_integer_dot_kernel(bamd, t):
     W = random_kquant_tensor(t, K, rows, rng)
     X = (rng.standard_normal((T, K)) * 3).astype(np.float32)
     w = (1 + 0.1 * rng.standard_normal(K)).astype(np.float32)
-    with lowbit(bamd):
+    with prefill_switches(bamd, lowbit=True):
         before = bamd.prefill_mfma_runs(t)
         a = bamd.op_mul_mat_batch(t, W, rows, K, X, norm_w=w, eps=EPS, impl=2)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -141,18 +128,18 @@ def test_matrix_core_kernel_equals_integer_dot_kernel(bamd, t):
 
 # ---- routing, as the engine issues the launches -------------------------------------------------------------------------------------------------------
 def test_seg_q3_k_beside_q6_k(bamd, po):
-    with lowbit(bamd):
-        before = runs(bamd)
+    with prefill_switches(bamd, lowbit=True):
+        before = runs(bamd, COUNTED)
         qkv_batch_case(bamd, po, Q3, Q6, 17, (2,), "batched QKV, Q3_K | Q6_K on the matrix cores", r0=256, r1=1024)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert after[Q3] == before[Q3] + 1 and after[Q6] == before[Q6] + 1 and after[Q2] == before[Q2]
 
 
 def test_seg_q2_k_beside_q3_k_into_one_matrix(bamd, po):
-    with lowbit(bamd):
-        before = runs(bamd)
+    with prefill_switches(bamd, lowbit=True):
+        before = runs(bamd, COUNTED)
         qkv_batch_case(bamd, po, Q2, Q3, 5, (2,), "batched QKV, Q2_K | Q3_K on the matrix cores", r0=256, r1=1024)
-        after = runs(bamd)
+        after = runs(bamd, COUNTED)
     assert after[Q2] == before[Q2] + 1 and after[Q3] == before[Q3] + 1
 
 
@@ -165,7 +152,7 @@ def test_seg_silu_mul_pair(bamd, po, t, T):
     Wg, Wu = random_kquant_tensor(t, K, rows, rng, amp=4.0), random_kquant_tensor(t, K, rows, rng, amp=4.0)
     A = np.stack([normed(po, x, w) for x in X])
     want = silu_mul(po, ref_mul_mat(po, t, Wg, rows, K, A), ref_mul_mat(po, t, Wu, rows, K, A))
-    with lowbit(bamd):
+    with prefill_switches(bamd, lowbit=True):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, Wg, rows), (t, Wu, rows)], K, X, rows + 64, epi=SILU_MUL, norm_w=w, eps=EPS, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 2
@@ -182,7 +169,7 @@ def test_seg_add_with_wide_rows(bamd, po, t, ldo):
     W = random_kquant_tensor(t, K, rows, rng)
     res = rng.standard_normal((T, ldo)).astype(np.float32)
     want = ref_mul_mat(po, t, W, rows, K, X) + res[:, :rows]
-    with lowbit(bamd):
+    with prefill_switches(bamd, lowbit=True):
         before = bamd.prefill_mfma_runs(t)
         got = bamd.op_mul_mat_batch_seg([(t, W, rows)], K, X, ldo, epi=ADD, residual=res, impl=2, fill=FILL)
         assert bamd.prefill_mfma_runs(t) == before + 1
@@ -193,34 +180,14 @@ def test_seg_add_with_wide_rows(bamd, po, t, ldo):
 # ---- whole models against the genuine reference's llama_decode ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cfg", ["tiny_q3_k_m", "tiny_q2_k", "8bw_q2_k_mix"])
 def test_whole_model_prompt_on_the_matrix_cores(bamd, cfg, monkeypatch, capfd):
-    from booster_amd.gguf import GGUFReader
-    fx = load_fixture(cfg)
-    _, _, n_prompt, _, n_ctx = gen.CONFIGS[cfg]
-    path = model_for(cfg, fx)
-    r = GGUFReader(path)
-    low = {int(ti["type"]) for name, ti in r.tensors.items() if name.startswith("blk.") and name.endswith(".weight") and int(ti["type"]) in (Q2, Q3)}
+    fx = load_fixture(LOWBIT, cfg)
+    path = model_for(LOWBIT, cfg, fx)
+    low = layer_types(path, TYPES)
     assert low, "the fixture holds no low-bit layer matrix"
     monkeypatch.setenv("BAMD_PREFILL_VERBOSE", "1")
-    capfd.readouterr()
-    with lowbit(bamd):
-        m = bamd.Model(path)
-        err = capfd.readouterr().err
-        try:
-            assert "prompts run without the matrix-core kernels" not in err, err
-            assert m.prefill_aux_bytes() > 0
-            ctx = bamd.Context(m, n_ctx)
-            before = runs(bamd)
-            prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
-            lg = ctx.decode(prompt, 0)
-            after = runs(bamd)
-            check_step(fx, 0, lg, cfg + " prompt on the matrix cores")
-            for t in low:
-                assert after[t] > before[t], "no matrix-core launch of type %d" % t
-            ctx.close()
-        finally:
-            m.close()
-    m = bamd.Model(path)                              # the switch off again: a fresh model of the same file builds no tables
-    try:
-        assert m.prefill_aux_bytes() == 0
-    finally:
-        m.close()
+    err, aux, before, after = prompt_step(bamd, path, capfd, COUNTED, dict(lowbit=True), fam=LOWBIT, cfg=cfg, fx=fx)
+    assert "prompts run without the matrix-core kernels" not in err, err
+    assert aux > 0
+    for t in low:
+        assert after[t] > before[t], "no matrix-core launch of type %d" % t
+    no_tables_with_the_switches_off(bamd, path, "lowbit")

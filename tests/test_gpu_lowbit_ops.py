@@ -5,33 +5,13 @@ import numpy as np
 import pytest
 
 import lowbit_ref as lr
+from bitcheck import assert_bits, bits, EPS, normed, silu_mul
 from booster_amd.gguf import random_kquant_tensor
 from lowbit_ref import all_cases
 from test_lowbit_ref import stored_case, stored  # noqa: F401  (stored: fixture)
 
 pytestmark = pytest.mark.gpu
 TYPES = [lr.Q2_K, lr.Q3_K]
-EPS = 1e-5
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert np.isfinite(b).all(), what + ": the expectation is not finite"
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
-
-
-def normed(po, x, w):
-    return (po.rms_norm(x, EPS) * w).astype(np.float32)
-
-
-def silu_mul(po, g, u):
-    L = po.lib()
-    return np.array([L.bo_v_silu(float(v)) for v in g], np.float32) * u
 
 
 # ---- the reference's own outputs ---------------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ import pytest
 
 import lowbit_ref as lr
 import booster_amd
+from bitcheck import assert_bits
 from booster_amd.gguf import random_kquant_tensor
 
 pytestmark = pytest.mark.gpu
@@ -28,17 +29,6 @@ NT = 8
 BLOCK_BYTES = {10: 84, 11: 110, 12: 144, 13: 176, 14: 210}
 PRO_PLAIN, PRO_NORM, EPI_STORE, EPI_ADD = 0, 1, 0, 1
 ZERO_BLOCK, NEG_BLOCK = 3, 6                                 # of the second activation vector
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert a.shape == b.shape and np.isfinite(b).all(), what + ": shape, or an expectation that is not finite"
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 def ref_mv(po, t, W, rows, k, a):

@@ -4,21 +4,12 @@ reference's AVX2 operation order), so every comparison is on the raw bits."""
 import numpy as np
 import pytest
 
+from bitcheck import assert_bits
 from booster_amd.gguf import random_kquant_tensor
 
 pytestmark = pytest.mark.gpu
 TYPES = [12, 13, 14]
 BB = {12: 144, 13: 176, 14: 210}
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 @pytest.mark.parametrize("K", [256, 768, 4096, 14336])

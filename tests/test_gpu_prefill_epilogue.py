@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from booster_amd.gguf import random_kquant_tensor
-from test_gpu_segments import ADD, EPS, FILL, Q4, Q5, Q6, SILU_MUL, assert_bits, batch_inputs, normed, ref_mul_mat, row_bytes, silu_mul
+from bitcheck import ADD, EPS, FILL, SILU_MUL, assert_bits, normed, silu_mul
+from test_gpu_segments import Q4, Q5, Q6, batch_inputs, ref_mul_mat, row_bytes
 
 pytestmark = pytest.mark.gpu
 SHAPE_ROWS, SHAPE_T = 72, 65

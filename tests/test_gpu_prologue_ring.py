@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_gpu_gateup_tail import EPS, NT, ROWS, SHORT0, assert_bits, bits, case
+from bitcheck import EPS, assert_bits, bits
+from test_gpu_gateup_tail import NT, ROWS, SHORT0, case
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 pytestmark = pytest.mark.gpu

@@ -12,24 +12,12 @@ import pytest
 
 import edge_inputs as ei
 import lowbit_ref as lr
+from bitcheck import ADD, assert_bits, EPS, FILL, normed, SILU_MUL, silu_mul, STORE
 from booster_amd.gguf import GGML_TYPES, random_kquant_tensor
 
 pytestmark = pytest.mark.gpu
 Q2, Q3, Q4, Q5, Q6 = 10, 11, 12, 13, 14
-EPS = 1e-5
 PAIRS = [(Q4, Q6), (Q4, Q5), (Q5, Q6), (Q3, Q4), (Q3, Q5), (Q2, Q4), (Q2, Q3)]      # the type pairs matvec_split_mixed_kernel has instances for
-STORE, ADD, SILU_MUL = 0, 1, 2
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def assert_bits(a, b, what=""):
-    a = np.asarray(a, np.float32); b = np.asarray(b, np.float32)
-    assert np.isfinite(b).all(), what + ": the expectation is not finite"
-    bad = np.flatnonzero(bits(a) != bits(b))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 def row_bytes(t, K):
@@ -43,14 +31,6 @@ def ref_mul_mat(po, t, W, rows, K, x):
         return lr.mul_mat(po, t, W, rows, K, x) if x.ndim == 1 else np.stack([lr.mul_mat(po, t, W, rows, K, xi) for xi in x])
     y = po.mul_mat_q(t, W, rows, K, x, nthreads=8)
     return y[0] if x.ndim == 1 else y
-
-
-def normed(po, x, w):
-    return (po.rms_norm(x, EPS) * w).astype(np.float32)
-
-
-def silu_mul(po, g, u):
-    return po.silu(np.ascontiguousarray(g, np.float32).reshape(-1)).reshape(np.shape(g)) * u
 
 
 # ---- the fused QKV launch --------------------------------------------------------------------------------------------------------------------------
@@ -146,7 +126,6 @@ def test_fused_qkv_mixed_edge_values(bamd, po, t0, t1):
 
 # ---- batched prompt mat-muls as the engine issues them ---------------------------------------------------------------------------------------------------
 TS = [1, 7, 64, 65, 129]
-FILL = np.float32(-7.25)                             # what the op leaves in the columns a call does not write
 
 
 def batch_inputs(K, T, seed):

@@ -13,13 +13,9 @@ import math
 import numpy as np
 import pytest
 
+from bitcheck import assert_bits
+
 pytestmark = pytest.mark.gpu
-
-
-def assert_bits(a, b, what=""):
-    a = np.ascontiguousarray(a, np.float32); b = np.ascontiguousarray(b, np.float32)
-    bad = np.flatnonzero(a.view(np.uint32) != b.view(np.uint32))
-    assert bad.size == 0, "%s: %d/%d elements differ, first at %d: %r vs %r" % (what, bad.size, a.size, bad[0], a.flat[bad[0]], b.flat[bad[0]])
 
 
 def assert_f16(got, want, what):

@@ -10,14 +10,16 @@ import pytest
 
 from booster_amd import gguf
 from goldenio import load_bgld
-from test_gpu_fullsize_ref import GOLDEN, check_step, gen, load_fixture, model_for
+from refmodel import FULLSIZE, check_step, load_fixture, model_for, prompt_of
+
+gen = FULLSIZE.gen
 
 
 def _oracle_ctx(po, cfg):
-    fx = load_fixture(cfg)
-    g = load_bgld(os.path.join(GOLDEN, "fullsize_%s.bgld" % cfg))
-    _, n_prompt, n_decode, n_ctx = gen.CONFIGS[cfg]
-    om = po.OracleModel(gguf.GGUFReader(model_for(cfg, fx)))
+    fx = load_fixture(FULLSIZE, cfg)
+    g = load_bgld(FULLSIZE.fixture_path(cfg))
+    _, n_prompt, n_decode, n_ctx = FULLSIZE.shape(cfg)
+    om = po.OracleModel(gguf.GGUFReader(model_for(FULLSIZE, cfg, fx)))
     return fx, g, om, po.OracleContext(om, n_ctx, nthreads=min(8, os.cpu_count() or 1)), n_prompt, n_decode, n_ctx
 
 
@@ -32,7 +34,7 @@ def test_oracle_context_shift_replays_reference(po, cfg):
     n_past of every step and the steps of the shifts as the reference recorded them"""
     fx, g, om, oc, n_prompt, n_decode, n_ctx = _oracle_ctx(po, cfg)
     n_keep = gen.N_KEEP[cfg]
-    prompt = [(7919 * i + 13) % om.V for i in range(n_prompt)]
+    prompt = prompt_of(n_prompt, om.V)
     check_step(fx, 0, oc.decode(prompt, 0), "oracle %s prompt" % cfg)
     n_past, shifts = n_prompt, []
     for s in range(n_decode):
@@ -51,7 +53,7 @@ def test_oracle_self_extend_replays_reference(po, cfg):
     """the script of test_self_extend_matches_reference on the oracle (cpp/bridge.cpp:509-522): every step against the reference's record"""
     fx, g, om, oc, n_prompt, n_decode, n_ctx = _oracle_ctx(po, cfg)
     ga_n, ga_w = (-gen.N_KEEP[cfg]) // 100, (-gen.N_KEEP[cfg]) % 100
-    prompt = [(7919 * i + 13) % om.V for i in range(n_prompt)]
+    prompt = prompt_of(n_prompt, om.V)
     check_step(fx, 0, oc.decode(prompt, 0), "oracle %s prompt" % cfg)
     n_past, ga_i, events = n_prompt, 0, []
     for s in range(n_decode):
