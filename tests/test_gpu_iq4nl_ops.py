@@ -65,7 +65,9 @@ def test_mul_mat_vec_shapes(bamd, po, K):
 
 
 def test_mul_mat_vec_many_row_groups(bamd):
-    """more row-groups than waves in the grid (2049 x 8 rows > 256 workgroups x 8 waves): a wave streams several row-groups, the last one ragged"""
+    """more row-groups than waves in the grid (2049 row-groups on 256 workgroups x 8 waves = 2048 wave slots): exactly one wave streams a second row-group,
+    the ragged last one (K = 512: ring depth 2 with one chunk, residual epilogue).  The other ring depths, a third walk and the gate/up and arg-max
+    epilogues of that walk: tests/test_gpu_sweep_families.py::test_tall_matrix_more_row_groups_than_wave_slots"""
     K, rows = 512, 16389                                              # 2049 row-groups, 5 valid rows in the last
     rng = np.random.default_rng(77 + T)
     W = random_iq4_nl_tensor(K, rows, rng)

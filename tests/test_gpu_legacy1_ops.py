@@ -119,7 +119,9 @@ def test_mul_mat_vec_shapes(bamd, po, t, K):
 
 @pytest.mark.parametrize("t", TYPES)
 def test_mul_mat_vec_many_row_groups(bamd, po, t):
-    """more row-groups than waves in the grid: 20488 rows = 2561 row-groups over at most 256 workgroups x 8 waves, so a wave streams a second row-group"""
+    """more row-groups than waves in the grid: 20488 rows = 2561 row-groups over 256 workgroups x 8 waves = 2048 wave slots, so 513 waves stream a second
+    row-group (K = 512: ring depth 2 with one chunk, residual epilogue).  The other ring depths, a third walk, a ragged last row-group and the gate/up and
+    arg-max epilogues of that walk: tests/test_gpu_sweep_families.py::test_tall_matrix_more_row_groups_than_wave_slots"""
     K, rows = 512, 20488
     rng = np.random.default_rng(77 + t)
     W = random_q1_tensor(t, K, rows, rng)

@@ -87,7 +87,9 @@ def test_mul_mat_vec_shapes(bamd, po, t, K):
 
 @pytest.mark.parametrize("t", TYPES)
 def test_mul_mat_vec_many_row_groups(bamd, po, t):
-    """more row-groups than workgroups: several row-groups per workgroup (split-K: both term buffers, the chain moving from wave to wave) and per wave (mode A)"""
+    """more row-groups than workgroups: in split-K a workgroup takes several row-groups, so both term buffers are used and the chain wave rotates.  In mode A the
+    513 row-groups land on 256 workgroups x 8 waves = 2048 wave slots, so no wave takes a second row-group here: that walk (the next-row-group prefetch, the
+    `last` flag of the final refill) is tests/test_gpu_sweep_families.py::test_tall_matrix_more_row_groups_than_wave_slots"""
     K, rows = 4096, 4104                                              # 513 row-groups
     rng = np.random.default_rng(77 + t)
     W = random_q0_tensor(t, K, rows, rng)
