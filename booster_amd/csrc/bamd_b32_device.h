@@ -1,5 +1,5 @@
 // bamd_b32_device.h — device code shared by the kernels of the 32-weight block formats (bamd_matvec_b32.h: single-token mat-vec; bamd_prefill_b32.hip: batched
-// prompt mat-mul on the integer-dot kernel; the matrix-core ones, bamd_prefill2_b32.hip and bamd_prefill2_b32_nl.hip, restate the chains for their own lane layout): the Q8_0 / Q8_1 activation
+// prompt mat-mul on the integer-dot kernel; the matrix-core one, bamd_prefill2_b32.hip, restates the chains for its own lane layout): the Q8_0 / Q8_1 activation
 // prologue, the wave-stream records (layout: bamd_formats.h), their block terms and the chains.  Two families, told apart by b32_has_min(TYPE):
 //   without a minimum  Q8_0 / Q4_0 / Q5_0   weights {d, q}, Q8_0 activations {d, q}
 //                      IQ4_NL               the Q4_0 record; a nibble indexes a table of 16 int8; TWO accumulators (b32_two_acc(TYPE)), see below
@@ -174,7 +174,7 @@ template <int TYPE> __device__ __forceinline__ void load_rec(RecB32<TYPE> & R, b
 // low nibbles = elements 0-15, high = 16-31); Q5_0 (nibble | bit 4) - 16 = (x + 0x70) ^ 0x80 (ggml-quants.c:4655-4658: a clear qh bit ORs 0xF0 into the nibble).  No
 // inter-byte carry.  With a minimum: unsigned and without an offset (ggml-quants.c:4364, :5021-5024).  IQ4_NL: kvalues_iq4nl[nibble] (_mm_shuffle_epi8, :11656-11659) as
 // byte permutes of the table in registers: its halves 0-7 and 8-15 selected by the nibble's low three bits, then of each byte pair the half its bit 3 names
-// kvalues_iq4nl[nibble] for the four nibbles of a dword (one per byte), as int8: the ONLY place the table stands (the matrix-core kernel, bamd_prefill2_b32_nl.hip, calls it too)
+// kvalues_iq4nl[nibble] for the four nibbles of a dword (one per byte), as int8: the ONLY place the table stands (the matrix-core kernel, bamd_prefill2_b32.hip, calls it too)
 __device__ __forceinline__ uint32_t b32_iq4nl_values(uint32_t nib) {     // {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}, four to a dword
     const uint32_t sel = nib & 0x07070707u;
     const uint32_t lo = __builtin_amdgcn_perm(0xf6eaddcfu, 0xbfad9881u, sel), hi = __builtin_amdgcn_perm(0x71594535u, 0x26190d01u, sel);

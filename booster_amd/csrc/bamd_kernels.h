@@ -133,14 +133,12 @@ size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                               int epi, int ldo, hipStream_t s);
-// the side of the three entry points above for the 32-weight block formats, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 (bamd_prefill2_b32.hip) and IQ4_NL (the Q4_0 table; its
-// kernel: bamd_prefill2_b32_nl.hip, reached through bamd_launch_matmul_mfma_b32); callers go through those
+// the side of the three entry points above for the 32-weight block formats, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 and IQ4_NL (the Q4_0 table), one kernel template
+// (bamd_prefill2_b32.hip); callers go through those
 size_t bamd_prefill_aux_bytes_b32(int type, int nrows_pad, int K);
 void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                                  int epi, int ldo, hipStream_t s);
-int  bamd_launch_matmul_mfma_b32_nl(const void * w_stream, const void * aux, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res, int epi,
-                                    int ldo, hipStream_t s);
 // F32 / F16 matrices on the matrix cores, exact (bamd_prefill2_flt.hip): the kernel reads the resident weight stream and the f32 activation rows of
 // bamd_launch_act_batch_flt (blob) as they are, there is no side table to build.  BF16 has no such kernel.  Epilogues as bamd_launch_matmul_mfma2; 1 = type / shape
 // not supported.  bamd_prefill_mfma_count: one more launch of `type` for bamd_prefill_mfma_runs (every matrix-core launcher; the counters live in bamd_prefill2.hip)

@@ -771,7 +771,7 @@ int bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, 
     if (!bamd_prefill_mfma_type(type) || (nrows_pad & 7) || (K & 255) || !aux) return 1;
     if (epi != BAMD_EPI_STORE && epi != BAMD_EPI_ADD && epi != BAMD_EPI_SILU_MUL) return 1;
     if ((epi != BAMD_EPI_STORE) != (res != nullptr)) return 1;
-    if (bamd_is_b32(type)) {                // bamd_prefill2_b32.hip / _nl.hip; static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
+    if (bamd_is_b32(type)) {                // bamd_prefill2_b32.hip; static LDS below the default limit: nothing for bamd_prefill_mfma_supported to ask
         if (bamd_launch_matmul_mfma_b32(w_stream, aux, type, nrows, nrows_pad, K, blob16, T, out, res, epi, ldo, s)) return 1;
         bamd_prefill_mfma_count(type);
         return 0;

@@ -4,7 +4,7 @@
 // runs the same block chain per output element, for one token and for many (without a minimum tinyBLAS_Q0_AVX::gemm, sgemm.cpp:711-759: the tile shape never
 // changes the order of an element's chain; with a minimum ggml_vec_dot_q4_1_q8_1 / _q5_1_q8_1 per output element: llamafile_sgemm has no case for these types,
 // sgemm.cpp:961-1007; IQ4_NL, Q8_0 activations: ggml_vec_dot_iq4_nl_q8_0 per output element, two chains per (row, token), in a kernel of its own whose type list
-// also holds Q8_0 / Q4_0 / Q5_0: the two earlier kernels stay what they were).  The matrix-core kernels of these types are bamd_prefill2_b32.hip and, for IQ4_NL, bamd_prefill2_b32_nl.hip, behind three switches (bamd_prefill_family.h); this file also writes its
+// also holds Q8_0 / Q4_0 / Q5_0: the two earlier kernels stay what they were).  The matrix-core kernel of these types and of IQ4_NL is bamd_prefill2_b32.hip, behind three switches (bamd_prefill_family.h); this file also writes its
 // f16 activation records.
 #include "bamd_prefill_b32.h"
 

@@ -6,7 +6,7 @@
 //   K       Q4_K / Q5_K (sixteen-wave kernel) and Q6_K (eight-wave kernel), bamd_prefill2.hip: always on
 //   LOWBIT  Q3_K / Q2_K: the eight-wave kernel of bamd_prefill2.hip with a policy struct of their own
 //   Q0, Q1  Q8_0 / Q4_0 / Q5_0 and Q4_1 / Q5_1: one kernel template, bamd_prefill2_b32.hip
-//   NL      IQ4_NL: the Q4_0 record and side table, a kernel of its own with two accumulator sets (bamd_prefill2_b32_nl.hip)
+//   NL      IQ4_NL: the Q4_0 record and side table; the same template with two accumulator sets and a 16-token tile
 //   FLT     F32 / F16 (bamd_prefill2_flt.hip); BF16 has no matrix-core kernel
 // Families WITH A SIDE TABLE are asked three times: when a model builds its tables at load (all or nothing per model: one matrix without a table and every prompt
 // mat-mul stays on the integer-dot kernel — llama.cpp writes Q4_0 / Q5_0 files made with an importance matrix with Q4_1 / Q5_1 ffn_down matrices in their first

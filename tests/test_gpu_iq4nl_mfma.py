@@ -1,4 +1,4 @@
-"""GPU: the matrix-core prompt mat-mul for IQ4_NL weights (booster_amd/csrc/bamd_prefill2_b32_nl.hip, behind set_prefill_nl / BAMD_PREFILL_NL=1; default off).
+"""GPU: the matrix-core prompt mat-mul for IQ4_NL weights (matmul_mfma_b32_kernel<IQ4_NL, EPI>, booster_amd/csrc/bamd_prefill2_b32.hip, behind set_prefill_nl / BAMD_PREFILL_NL=1; default off).
 Every expectation is the genuine reference's stored output (tests/golden/iq4nl_kats.npz, tests/golden/*iq4nl*.bgld) or the numpy restatement that
 tests/test_iq4nl_ref.py holds to those (tests/iq4nl_ref.py); bit equality throughout, every expectation finite.  The switches are set through their setters and
 restored afterwards to what the environment set; the launch counters (prefill_mfma_runs) tell the matrix-core kernel from the integer-dot kernel, which gives

@@ -1,4 +1,4 @@
-"""CPU: the arithmetic of the matrix-core prompt mat-mul for IQ4_NL weights (booster_amd/csrc/bamd_prefill2_b32_nl.hip), checked before a GPU is involved.
+"""CPU: the arithmetic of the matrix-core prompt mat-mul for IQ4_NL weights (matmul_mfma_b32_kernel<IQ4_NL, EPI>, booster_amd/csrc/bamd_prefill2_b32.hip), checked before a GPU is involved.
 As tests/test_legacy1_mfma_math.py for the Q4_1 family: per 32-weight block l and SIMD lane e of the reference the kernel multiplies the f16 images of four table
 values ((0x6400 | (value + 128)) - 1152 = value) and four int8 activations on the matrix cores and sums the four f32 products in whatever order the instruction
 takes; the scale product, TWO sets of eight chains (the even blocks into one, the odd blocks into the other, each in block order), their lane-wise sum and the

@@ -15,7 +15,7 @@ four layers is Q4_1): once with both switches on against both off, once with onl
 --iq4nl: the IQ4_NL recipe (full depth, synthetic files of tests/golden/gen_iq4nl_fixtures.py's writer) beside Q4_0 and Q4_K_M: the 8B shape as the recipe
 writes it (n_gqa 4: Q5_K attn_v, so the QKV of a layer is two launches, six launches per layer) and a uniform-QKV variant of the same shape (attn_v IQ4_NL like
 attn_q / attn_k: one QKV launch) — the difference between the two is what the second QKV launch costs per token.  The prompt lines of the two IQ4_NL files
-alternate set_prefill_nl(False) / (True) like the lines above (integer-dot kernel against the matrix-core kernel of bamd_prefill2_b32_nl.hip), beside the Q4_0
+alternate set_prefill_nl(False) / (True) like the lines above (integer-dot kernel against the matrix-core kernel, bamd_prefill2_b32.hip), beside the Q4_0
 file under set_prefill_q0 as the nearest twin and the Q4_K_M file.
 
     python tools/legacy_decode.py --iq4nl [--prompt 2048] [--only-prompt]
