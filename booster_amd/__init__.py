@@ -22,6 +22,24 @@ class BamdError(RuntimeError):
     pass
 
 
+class LogitPenalty(C.Structure):
+    """bamd_logit_penalty (include/bamd.h): one distinct penalised token of the sampler prefilter"""
+    _fields_ = [("id", C.c_int32), ("count", C.c_int32), ("kind", C.c_int32), ("f", C.c_float), ("d", C.c_double), ("pre", C.c_double)]
+
+
+class ShortlistHead(C.Structure):
+    """bamd_shortlist_head (include/bamd.h)"""
+    _fields_ = [("top_key", C.c_ulonglong), ("count", C.c_int32), ("ntop", C.c_int32), ("nan", C.c_int32), ("top_id", C.c_int32),
+                ("top_logit", C.c_float), ("cutoff", C.c_float)]
+
+
+PENALTY_DTYPE = np.dtype(LogitPenalty)         # numpy view of a penalty list: fields id, count, kind, f, d, pre
+SHORTLIST_CAP = 1024                           # BAMD_SHORTLIST_CAP
+PENALTY_CAP = 512                              # BAMD_PENALTY_CAP
+SHORTLIST_SENTINEL_ID = -1                     # what Context.logits_shortlist leaves in the ids / vals the library did not write
+SHORTLIST_SENTINEL_BITS = 0x7FC5A5A5
+
+
 def lib():
     """The HIP library.  No fallback: a missing .so is an error (run `python -m booster_amd.build`)."""
     global _lib
@@ -90,6 +108,11 @@ def lib():
         L.bamd_aql_runs.argtypes = [vp]
         L.bamd_set_aql_stall_ms.argtypes = [ci]; L.bamd_set_aql_stall_ms.restype = None
         L.bamd_aql_stats.argtypes = [ci, C.POINTER(C.c_uint64)]; L.bamd_aql_stats.restype = None
+        L.bamd_context_stream.restype = vp; L.bamd_context_stream.argtypes = [vp]
+        L.bamd_set_logits_readback.argtypes = [vp, ci]; L.bamd_set_logits_readback.restype = None
+        L.bamd_set_logits_test.argtypes = [vp, vp]
+        L.bamd_sampler_tables.argtypes = [vp, vp, vp, ci]
+        L.bamd_logits_shortlist.argtypes = [vp, vp, ci, ci, C.POINTER(ShortlistHead), vp, vp, vp]
         _lib = L
     return _lib
 
@@ -249,7 +272,42 @@ class Context:
         return int(lib().bamd_aql_runs(self.h))
 
     def last_logits(self):
-        return np.ctypeslib.as_array(lib().bamd_get_logits(self.h), shape=(self.model.n_vocab,)).copy()
+        ptr = lib().bamd_get_logits(self.h)
+        if not ptr:
+            raise BamdError("bamd_get_logits failed: " + lib().bamd_last_error().decode())
+        return np.ctypeslib.as_array(ptr, shape=(self.model.n_vocab,)).copy()
+
+    def set_logits_readback(self, on):
+        """False: decode leaves the logits on the device and last_logits copies them on demand (bamd_set_logits_readback)"""
+        lib().bamd_set_logits_readback(self.h, int(bool(on)))
+
+    def set_logits(self, logits):
+        """test hook: overwrite the device logits (n_vocab floats, bamd_set_logits_test)"""
+        lg = np.ascontiguousarray(logits, np.float32)
+        if lg.shape != (self.model.n_vocab,):
+            raise BamdError("set_logits: needs n_vocab floats")
+        _chk(lib().bamd_set_logits_test(self.h, _p(lg)))
+
+    def sampler_tables(self, halve_class, cutoff_of):
+        """the per-vocabulary tables of the sampler prefilter (bamd_sampler_tables): halve_class [n_vocab] uint8, cutoff_of [n_vocab] f32"""
+        cls = np.ascontiguousarray(halve_class, np.uint8); cut = np.ascontiguousarray(cutoff_of, np.float32)
+        if cls.shape != cut.shape or cls.ndim != 1:
+            raise BamdError("sampler_tables: needs two vectors of one length")
+        _chk(lib().bamd_sampler_tables(self.h, _p(cls), _p(cut), cls.size))
+
+    def logits_shortlist(self, pen, halve):
+        """the sampler prefilter on the context's stream (bamd_logits_shortlist): pen = penalty entries (PENALTY_DTYPE array, or tuples (id, count, kind, f, d,
+        pre)), applied to the device logits in place.  Returns (head, ids, vals): head = dict of count, ntop, nan, top_id, top_logit, cutoff (the floats as
+        np.float32); ids / vals have SHORTLIST_CAP entries, the first min(count, SHORTLIST_CAP) written by the library, in no particular order, the others left
+        at SHORTLIST_SENTINEL_ID / SHORTLIST_SENTINEL_BITS."""
+        p = np.ascontiguousarray(pen, PENALTY_DTYPE).reshape(-1)
+        head = ShortlistHead()
+        ids = np.full(SHORTLIST_CAP, SHORTLIST_SENTINEL_ID, np.int32)
+        vals = np.full(SHORTLIST_CAP, SHORTLIST_SENTINEL_BITS, np.uint32).view(np.float32)
+        _chk(lib().bamd_logits_shortlist(self.h, _p(p) if p.size else None, p.size, int(bool(halve)), C.byref(head), _p(ids), _p(vals),
+                                         lib().bamd_context_stream(self.h)))
+        return (dict(count=int(head.count), ntop=int(head.ntop), nan=int(head.nan), top_id=int(head.top_id), top_logit=np.float32(head.top_logit),
+                     cutoff=np.float32(head.cutoff)), ids, vals)
 
     def kv_seq_rm(self, p0, p1):
         """llama_kv_cache_seq_rm(ctx, 0, p0, p1)"""
