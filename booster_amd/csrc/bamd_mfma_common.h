@@ -1,4 +1,4 @@
-// bamd_mfma_common.h — vector types and the global -> LDS copy helpers shared by the matrix-core prefill kernels (bamd_prefill.hip, bamd_prefill2.hip)
+// bamd_mfma_common.h — vector types and the global -> LDS copy helpers shared by the matrix-core prefill kernels
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,16 +1,14 @@
-// bamd_prefill.hip — batched prefill: per-token Q8_K quantisation into global blobs, the exact MFMA mat-mul kernels (Q4_K, Q6_K),
-// the integer-dot batched mat-mul (any K-quant), batched embedding, silu*up.  Helpers: bamd_device.h.
-#include "bamd_device.h"
-#include "bamd_mfma_common.h"
+// bamd_prefill.hip — batched prefill: per-token Q8_K quantisation into global blobs (and their f16 copy for the matrix-core kernels of bamd_prefill2.hip), the
+// integer-dot batched mat-mul of the K-quants (row policy and type list here, the body in bamd_prefill_valu.h), batched embedding.  Helpers: bamd_device.h.
+#include "bamd_prefill_valu.h"
 #include "bamd_prefill_family.h"
-#include <type_traits>
 
 // ===========================================================================================================
 // Batched prefill (T > 1 tokens per call; reference: llama_decode with a micro-batch, ggml_compute_forward_mul_mat with
-// ne11 = T, ggml.c:12277-12492).  Per (row, token) the arithmetic is EXACTLY the single-token chain above — the reference
+// ne11 = T, ggml.c:12277-12492).  Per (row, token) the arithmetic is EXACTLY the single-token chain of the mat-vec kernels (bamd_device.h) — the reference
 // quantises each activation row to Q8_K and runs the same vec_dot per (row, column).  Two implementations, bit-identical:
-//   matmul_mfma_q4k_kernel / matmul_mfma_q6k_kernel (default): the integer sums of a super-block on the matrix cores, exactly — f16
-//     A = scale x quant, f16 B = the int8 activations, one 32-deep MFMA per SIMD lane e of the reference — and the f32 chains on the VALU;
+//   the matrix-core kernels of bamd_prefill2.hip (default, for a model whose side tables were built): the integer sums of a super-block on
+//     the matrix cores, exactly, and the f32 chains on the VALU;
 //   matmul_batch_kernel (BAMD_PREFILL_MFMA=0; the second implementation the first is tested against): block_terms / chain_step /
 //     finish_row of the decode path, the weights of a record unpacked once for BAMD_TT tokens whose Q8_K activations sit in LDS.
 // ===========================================================================================================
@@ -38,10 +36,7 @@ __global__ void __launch_bounds__(512) quantize_batch_kernel(const float * __res
         uint8_t * o = blob16 + (size_t) t * BAMD_BLOB16_BYTES(nb);
         for (int i = threadIdx.x; i < nb * 64; i += blockDim.x) {          // q8[ci*64 + e*8 + c] = sub-block c, chunk e, 4 int8
             const int ci = i >> 6, e = (i >> 3) & 7, c = i & 7;
-            const uint32_t w = q8[i];
-            const unsigned short h0 = f2h((float) (int8_t) (w)), h1 = f2h((float) (int8_t) (w >> 8)), h2 = f2h((float) (int8_t) (w >> 16)), h3 = f2h((float) (int8_t) (w >> 24));
-            uint2 v; v.x = (uint32_t) h0 | ((uint32_t) h1 << 16); v.y = (uint32_t) h2 | ((uint32_t) h3 << 16);
-            *(uint2 *) (o + (size_t) ci * BAMD_B16_REC + (size_t) (e * 4 + (c >> 1)) * 16 + (c & 1) * 8) = v;
+            *(uint2 *) (o + (size_t) ci * BAMD_B16_REC + (size_t) (e * 4 + (c >> 1)) * 16 + (c & 1) * 8) = i8x4_halves(q8[i]);
         }
         for (int i = threadIdx.x; i < nb * 4; i += blockDim.x) {
             const int ci = i >> 2, l = i & 3;
@@ -67,125 +62,43 @@ __global__ void __launch_bounds__(512) quantize_batch_kernel(const float * __res
 }
 
 
-template <int TYPE, typename REC, int D, int EPI, int TT>
-__device__ __forceinline__ void batch_segment(const uint8_t * __restrict__ wA, const uint8_t * __restrict__ wB, int nb, int first, int count, int stride,
-                                              float * __restrict__ out, const float * __restrict__ res, int ldo, int t0, int nt,
-                                              const unsigned char * acts, size_t bb, int nvalid) {
-    constexpr int RECB = BAMD_RECB_OF(TYPE); static_assert(RECB > 0, "no wave-stream record for this type");     // bamd_record_bytes
-    constexpr bool PAIR = EPI == BAMD_EPI_SILU_MUL;
-    constexpr int NPARTS = PAIR ? 2 : 1;
-    const int lane = threadIdx.x & 63;
-    const bamd_rsrc rsA = weight_rsrc(wA), rsB = PAIR ? weight_rsrc(wB) : rsA;
-    const int rgb = nb * RECB, rg_step = stride * rgb;
-    const int chunks = nb / D;
-    REC ring[D];
-#pragma unroll
-    for (int s = 0; s < D; ++s) load_rec(ring[s], rsA, first * rgb + s * RECB, lane);
-    for (int r = 0; r < count; ++r) {
-        const int rg = first + r * stride;
-        const int row = rg * 8 + (lane >> 3);
-        const int rowoff = rg * rgb;
-        float gate_val[TT];
-#pragma unroll
-        for (int part = 0; part < NPARTS; ++part) {
-            const bool last = !(PAIR && part == 0) && r + 1 >= count;
-            const bool after_b = (PAIR && part == 0) || (last && part == 1);
-            const int after_off = (PAIR && part == 0) ? rowoff : (last ? rowoff + (nb - 1) * RECB : rowoff + rg_step);
-            RowAcc A[TT];
-#pragma unroll
-            for (int u = 0; u < TT; ++u) { A[u].acc = 0.f; A[u].accm = 0.f; }
-            for (int c = 0; c < chunks; ++c) {
-                const bool inrow = c + 1 < chunks;
-                const bamd_rsrc nrs = (inrow ? part == 1 : after_b) ? rsB : rsA;
-                const int nxt = inrow ? rowoff + (c + 1) * (D * RECB) : after_off;
-                const int step = (inrow || !last) ? RECB : 0;
-#pragma unroll
-                for (int s = 0; s < D; ++s) {
-                    pin_rec(ring[s]);
-#pragma unroll
-                    for (int u = 0; u < TT; ++u) {               // tokens beyond nt read stale-but-valid LDS and are never stored
-                        const unsigned char * au = acts + (size_t) u * bb;
-                        const uint32_t * q8 = (const uint32_t *) au; const int * S = (const int *) (q8 + nb * 64); const float * yd = (const float *) (S + nb * 8);
-                        const Terms T = block_terms(ring[s], c * D + s, lane, q8, S, yd);
-                        chain_step<TYPE>(A[u], T.d, T.fs, T.dmin, T.pm);
-                    }
-                    load_rec(ring[s], nrs, nxt + s * step, lane);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < TT; ++u) {
-                const float val = finish_row<TYPE>(A[u]);
-                if (PAIR && part == 0) { gate_val[u] = val; continue; }
-                if ((lane & 7) == 0 && row < nvalid && u < nt) {
-                    const size_t o = (size_t) (t0 + u) * ldo + row;
-                    float y = val;
-                    if (PAIR) y = v_silu(gate_val[u]) * val;
-                    if (EPI == BAMD_EPI_ADD) y = val + res[o];
-                    out[o] = y;
-                }
-            }
-        }
+// the row policy of a K-quant: block_terms / chain_step / finish_row of the decode path over the Q8_K image q8 | S | yd; one accumulator (a pair of chains), no
+// temporaries.  Behind a wave's last chunk the row's last record is read again (step 0)
+// (the unnamed RowAcc & and kq_none & parameters: valu_segment hands every policy three accumulators and three temporaries, because the storage of the 32-weight
+// block types has to be declared there for their kernels to stay what they are, bamd_prefill_valu.h; a K-quant needs one accumulator, the rest is never touched)
+struct kq_none {};
+template <int TYPE, typename REC> struct KqRow {
+    typedef REC Rec;
+    typedef RowAcc Acc;
+    typedef kq_none Work;
+    static constexpr int RECB = BAMD_RECB_OF(TYPE);
+    static constexpr bool NULL_TAIL = false;
+    static __device__ __forceinline__ void zero(RowAcc & A, RowAcc &, RowAcc &) { A.acc = 0.f; A.accm = 0.f; }
+    static __device__ __forceinline__ void step(const REC & R, int ci, int lane, const unsigned char * au, int nb, RowAcc & A, RowAcc &, RowAcc &, kq_none &, kq_none &, kq_none &) {
+        const uint32_t * q8 = (const uint32_t *) au; const int * S = (const int *) (q8 + nb * 64); const float * yd = (const float *) (S + nb * 8);
+        const Terms T = block_terms(R, ci, lane, q8, S, yd);
+        chain_step<TYPE>(A, T.d, T.fs, T.dmin, T.pm);
     }
+    static __device__ __forceinline__ float finish(const RowAcc & A, const RowAcc &, const RowAcc &) { return finish_row<TYPE>(A); }
+};
+// the type list (BAMD_VALU_MM_KERNEL_BODY): ring depth 4 when it divides the row (it does for every K % 1024 == 0), else 1
+#define BAMD_KQ_TYPES_D(SEG, D) { \
+    if (t == BAMD_Q4_K)      SEG(D, KqRow<BAMD_Q4_K, RecQ4K>); \
+    else if (t == BAMD_Q5_K) SEG(D, KqRow<BAMD_Q5_K, RecQ5K>); \
+    else if (t == BAMD_Q6_K) SEG(D, KqRow<BAMD_Q6_K, RecQ6K>); \
+    else if (t == BAMD_Q3_K) SEG(D, KqRow<BAMD_Q3_K, RecQ3K>); \
+    else if (t == BAMD_Q2_K) SEG(D, KqRow<BAMD_Q2_K, RecQ2K>); \
+    else __builtin_trap();                       /* the launcher checks the types: never a silent read as another format */ \
 }
+#define BAMD_KQ_TYPES(SEG) if ((nb & 3) == 0) BAMD_KQ_TYPES_D(SEG, 4) else BAMD_KQ_TYPES_D(SEG, 1)
 
 // (Rounds 2-5 kept a first generation of matrix-core mat-mul kernels here — every wave expanding its own 16 rows — and a second one in bamd_prefill2.hip;
 // round 6 measured what bounds them (profiles/r06_prefill_ceiling.txt) and kept ONE: bamd_prefill2.hip.  This file keeps the integer-dot kernel — the second
 // implementation the matrix-core kernels are tested against, and what a matrix without a side table runs on — and the plumbing.)
 
-// grid (token tiles, row slots): consecutive workgroups share the weights (L2) and differ in the token tile.  TT tokens per tile: BAMD_TT = 8 while their Q8_K
-// activations fit the LDS (K <= 17920), 4 beyond (K <= 35840: the 70B ffn_down at K = 28672 — round 6; before, a 70B-width model without side tables had no batched
-// kernel at all and evaluated prompts token by token)
 template <int EPI, int TT>
 __global__ void __launch_bounds__(512) matmul_batch_kernel(bamd_mm_args a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int nb = a.K >> 8;
-    const size_t bb = BAMD_BLOB_BYTES(nb);
-    const int t0 = blockIdx.x * TT;
-    const int nt = a.T - t0 < TT ? a.T - t0 : TT;
-    {   // this tile's activations -> LDS (rows past T: repeat the last token; results discarded)
-        const int n16 = (int) (bb / 16);
-        for (int i = threadIdx.x; i < n16 * TT; i += blockDim.x) {
-            const int u = i / n16, k = i - u * n16;
-            const int tu = t0 + (u < nt ? u : nt - 1);
-            ((uint4 *) smem)[(size_t) u * n16 + k] = ((const uint4 *) (a.blob + (size_t) tu * bb))[k];
-        }
-    }
-    __syncthreads();
-    const int wave = wave_id(), nwaves = blockDim.x >> 6;
-    const int slot = blockIdx.y + gridDim.y * wave, stride = gridDim.y * nwaves;
-    constexpr bool PAIR = EPI == BAMD_EPI_SILU_MUL;
-    int off = 0;
-    const int nseg = PAIR ? 1 : a.nseg;
-    for (int s = 0; s < nseg; ++s) {
-        const int nrg = a.seg[s].nrows >> 3;
-        const int k0 = off <= slot ? 0 : (off - slot + stride - 1) / stride;
-        const int g0 = slot + k0 * stride;
-        const int count = g0 < off + nrg ? (off + nrg - 1 - g0) / stride + 1 : 0;
-        if (count > 0) {
-            const int t = a.seg[s].type;
-            const uint8_t * wA = (const uint8_t *) a.seg[s].w;
-            const uint8_t * wB = PAIR ? (const uint8_t *) a.seg[1].w : wA;
-            const int nv = a.seg[s].nvalid > 0 ? a.seg[s].nvalid : a.seg[s].nrows;
-            // ring depth 4 when it divides the row (it does for every K % 1024 == 0), else 1
-            if ((nb & 3) == 0) {
-                if (t == BAMD_Q4_K)      batch_segment<BAMD_Q4_K, RecQ4K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q5_K) batch_segment<BAMD_Q5_K, RecQ5K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q6_K) batch_segment<BAMD_Q6_K, RecQ6K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q3_K) batch_segment<BAMD_Q3_K, RecQ3K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q2_K) batch_segment<BAMD_Q2_K, RecQ2K, 4, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else __builtin_trap();                       // the launcher checks the types: never a silent read as another format
-            } else {
-                if (t == BAMD_Q4_K)      batch_segment<BAMD_Q4_K, RecQ4K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q5_K) batch_segment<BAMD_Q5_K, RecQ5K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q6_K) batch_segment<BAMD_Q6_K, RecQ6K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q3_K) batch_segment<BAMD_Q3_K, RecQ3K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else if (t == BAMD_Q2_K) batch_segment<BAMD_Q2_K, RecQ2K, 1, EPI, TT>(wA, wB, nb, g0 - off, count, stride, a.seg[s].out, a.res, a.ldo, t0, nt, smem, bb, nv);
-                else __builtin_trap();                       // the launcher checks the types: never a silent read as another format
-            }
-        }
-        off += nrg;
-    }
+    BAMD_VALU_MM_KERNEL_BODY(BAMD_KQ_TYPES)
 }
 
 // batched prefill: one workgroup per token of the micro-batch
@@ -211,19 +124,10 @@ void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, in
 int bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s) {
     if (a.nseg > 0 && bamd_is_flt(a.seg[0].type)) return bamd_launch_matmul_batch_flt(a, epi, n_cu, s);      // f32 / bf16 activations (bamd_prefill_flt.hip)
     if (a.nseg > 0 && bamd_is_b32(a.seg[0].type)) return bamd_launch_matmul_batch_b32(a, epi, n_cu, s);      // Q8_0 / Q8_1 activations: kernels of their own; a launch that mixes the forms has none
-    int nrg = 0;
-    if (epi == BAMD_EPI_SILU_MUL) nrg = a.seg[0].nrows >> 3; else for (int i = 0; i < a.nseg; ++i) nrg += a.seg[i].nrows >> 3;
-    const int tt = (size_t) BAMD_TT * BAMD_BLOB_BYTES(a.K >> 8) <= 160 * 1024 ? BAMD_TT : 4;     // tokens per tile: 8 while their activations fit the LDS, else 4
-    const size_t lds = (size_t) tt * BAMD_BLOB_BYTES(a.K >> 8);
-    if (lds > 160 * 1024) return 1;                           // K > 35840: would need a K-split of the activation tile
+    valu_mm_geom g;
+    if (!valu_mm_geometry(a, epi, n_cu, g)) return 1;                 // K > 35840
     for (int i = 0; i < a.nseg; ++i) if (!bamd_is_kquant(a.seg[i].type)) return 1;
-    const int tiles = (a.T + tt - 1) / tt;
-    // row slots: enough workgroups to fill the chip a few times over, at least one row-group per wave
-    int gy = (4 * (n_cu > 0 ? n_cu : 256) + tiles - 1) / tiles;
-    if (gy * 8 > nrg) gy = (nrg + 7) / 8;
-    if (gy < 1) gy = 1;
-    dim3 grid(tiles, gy);
-#define BAMD_MB(EPI_) do { if (tt == BAMD_TT) hipLaunchKernelGGL((matmul_batch_kernel<EPI_, BAMD_TT>), grid, dim3(512), lds, s, a); else hipLaunchKernelGGL((matmul_batch_kernel<EPI_, 4>), grid, dim3(512), lds, s, a); } while (0)
+#define BAMD_MB(EPI_) do { if (g.tt == BAMD_TT) hipLaunchKernelGGL((matmul_batch_kernel<EPI_, BAMD_TT>), g.grid, dim3(512), g.lds, s, a); else hipLaunchKernelGGL((matmul_batch_kernel<EPI_, 4>), g.grid, dim3(512), g.lds, s, a); } while (0)
     switch (epi) {
         case BAMD_EPI_STORE:    BAMD_MB(BAMD_EPI_STORE); break;
         case BAMD_EPI_ADD:      BAMD_MB(BAMD_EPI_ADD); break;

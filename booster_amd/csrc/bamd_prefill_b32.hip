@@ -31,10 +31,7 @@ __global__ void __launch_bounds__(512) quantize_batch_b32_kernel(const float * _
         uint8_t * o = blob16 + (size_t) t * BAMD_BLOB16_BYTES(nb);
         for (int i = threadIdx.x; i < nb * 64; i += blockDim.x) {          // q8[ci*64 + e*8 + c] = block c, chunk e, 4 int8 (never -128)
             const int ci = i >> 6, e = (i >> 3) & 7, c = i & 7;
-            const uint32_t w = q8[i];
-            const unsigned short h0 = f2h((float) (int8_t) (w)), h1 = f2h((float) (int8_t) (w >> 8)), h2 = f2h((float) (int8_t) (w >> 16)), h3 = f2h((float) (int8_t) (w >> 24));
-            uint2 v; v.x = (uint32_t) h0 | ((uint32_t) h1 << 16); v.y = (uint32_t) h2 | ((uint32_t) h3 << 16);
-            *(uint2 *) (o + (size_t) ci * BAMD_B16_REC + c * 64 + (e & 3) * 16 + (e >> 2) * 8) = v;
+            *(uint2 *) (o + (size_t) ci * BAMD_B16_REC + c * 64 + (e & 3) * 16 + (e >> 2) * 8) = i8x4_halves(q8[i]);
         }
         if (MIN) {
             const uint32_t * yp = (const uint32_t *) ys;                   // {f16 d, f16 s} of block i

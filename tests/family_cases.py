@@ -97,7 +97,7 @@ def classes(t):
 
 def batch_classes(t):
     """the batch kernel of the 32-weight block types takes ring depth 2 where nb is even, but at token tiles of 8 not in the kernel that has IQ4_NL and not in the
-    gate/up instance of Q4_1 / Q5_1 (bamd_prefill_b32.h): the class tile4even, an even nb on the tiles-of-4 side, is where batch_segment_b32<.., 2, .., 4> runs for
+    gate/up instance of Q4_1 / Q5_1 (bamd_prefill_b32.h): the class tile4even, an even nb on the tiles-of-4 side, is where valu_segment<B32Row<..>, 2, .., 4> runs for
     every type, and the only place where an IQ4_NL launch takes depth 2"""
     c = collections.OrderedDict((k, v) for k, v in COMMON.items() if k != "nb1")
     if t not in FLOAT_TYPES:                     # the float batch kernel keeps no blobs in LDS: no such switch
