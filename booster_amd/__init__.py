@@ -76,11 +76,12 @@ def lib():
         L.bamd_profile_step.argtypes = [vp, ci, vp, vp, vp]; L.bamd_profile_step_kinds.argtypes = [vp, ci, vp, vp, vp]
         L.bamd_timeline_step.argtypes = [vp, ci, ci, vp, ci, C.POINTER(ci)]
         L.bamd_set_prefill_batch.argtypes = [ci]; L.bamd_set_prefill_batch.restype = None
-        for n in ("lowbit", "q0", "q1", "nl", "flt"):                    # the switches of csrc/bamd_prefill_family.h
+        for n in ("lowbit", "q0", "q1", "nl", "flt", "bf16"):                 # the switches of csrc/bamd_prefill_family.h
             getattr(L, "bamd_set_prefill_" + n).argtypes = [ci]; getattr(L, "bamd_set_prefill_" + n).restype = None
         L.bamd_set_attn_scratch_mb.argtypes = [ci]; L.bamd_set_attn_scratch_mb.restype = None
         L.bamd_attention_batch_plan.argtypes = [ci, ci, ci, ci, ci, ci, C.c_size_t, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
         L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong
+        L.bamd_prefill_bf16_fallback_tiles.argtypes = []; L.bamd_prefill_bf16_fallback_tiles.restype = C.c_ulonglong
         L.bamd_model_prefill_aux_bytes.argtypes = [vp]; L.bamd_model_prefill_aux_bytes.restype = i64
         L.bamd_bench_matvec.argtypes = [ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_float)]
         L.bamd_op_quantize_q8_K.argtypes = [vp, i64, vp, cf, vp]
@@ -159,9 +160,21 @@ def set_prefill_nl(on):
 
 def set_prefill_flt(on):
     """True: F32 / F16 matrices evaluate prompts on the f32 matrix-core kernel; False (default, also env BAMD_PREFILL_FLT): on the VALU kernel.  Read at each
-    launch, not at model load (the kernel needs no side tables), so it also applies to models loaded before.  BF16 matrices stay on the VALU kernel.  Same bits
+    launch, not at model load (the kernel needs no side tables), so it also applies to models loaded before.  BF16 matrices: set_prefill_bf16.  Same bits
     either way."""
     lib().bamd_set_prefill_flt(int(bool(on)))
+
+
+def set_prefill_bf16(on):
+    """True: BF16 matrices evaluate prompts on the f32 matrix-core kernel (fma chains where the exponent ranges of the matrix and of the tokens prove every
+    product exact in f32, the two-rounding VALU step per workgroup otherwise); False (default, also env BAMD_PREFILL_BF16): on the VALU kernel.  Independent of
+    set_prefill_flt and read at each launch like it.  Same bits either way."""
+    lib().bamd_set_prefill_bf16(int(bool(on)))
+
+
+def prefill_bf16_fallback_tiles():
+    """tests and tools: workgroups of the BF16 matrix-core kernel that took the two-rounding VALU step since the library was loaded (waits for the device)"""
+    return int(lib().bamd_prefill_bf16_fallback_tiles())
 
 
 def set_attn_scratch_mb(mb):

@@ -12,14 +12,14 @@ LIB = os.path.join(HERE, "lib", "libbooster_amd.so")
 # the kernels of a decode step are ALSO built as raw gfx950 code objects (same sources, same flags) and embedded in the library: bamd_aql.cpp loads them through
 # HSA and replays a step from the library's own AQL queue (csrc/bamd_aql.h)
 DECODE_KERNEL_SOURCES = ["bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_colaunch.hip"]
-SOURCES = ["bamd_aql.cpp", "bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_attention_mfma.hip", "bamd_attention_gs.hip", "bamd_colaunch.hip", "bamd_prefill.hip", "bamd_prefill_b32.hip", "bamd_prefill_b32_nl.hip", "bamd_prefill_flt.hip", "bamd_prefill2.hip", "bamd_prefill2_b32.hip", "bamd_prefill2_flt.hip", "bamd_prefill_family.cpp", "bamd_sampler.hip", "bamd_engine.cpp", "bamd_ops.cpp", "bamd_gguf.cpp", "bamd_vocab.cpp", "bamd_bridge.cpp"]
-HEADERS = ["bamd_aql.h", "bamd_engine_internal.h", "bamd_formats.h", "bamd_kernels.h", "bamd_device.h", "bamd_b32_device.h", "bamd_prefill_b32.h", "bamd_prefill_valu.h", "bamd_prefill_family.h", "bamd_flt_device.h", "bamd_matvec_b32.h", "bamd_matvec_core.h", "bamd_mv_select.h", "bamd_attn_fused.h", "bamd_attn_batch.h", "bamd_mfma_common.h", "bamd_gguf.h", "bamd_vocab.h", "bamd_unicode_tables.h", "../../include/bamd.h", "../../include/booster_bridge.h"]
+SOURCES = ["bamd_aql.cpp", "bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_attention_mfma.hip", "bamd_attention_gs.hip", "bamd_colaunch.hip", "bamd_prefill.hip", "bamd_prefill_b32.hip", "bamd_prefill_b32_nl.hip", "bamd_prefill_flt.hip", "bamd_prefill2.hip", "bamd_prefill2_b32.hip", "bamd_prefill2_flt.hip", "bamd_prefill2_bf16.hip", "bamd_prefill_family.cpp", "bamd_sampler.hip", "bamd_engine.cpp", "bamd_ops.cpp", "bamd_gguf.cpp", "bamd_vocab.cpp", "bamd_bridge.cpp"]
+HEADERS = ["bamd_aql.h", "bamd_engine_internal.h", "bamd_formats.h", "bamd_kernels.h", "bamd_device.h", "bamd_b32_device.h", "bamd_prefill_b32.h", "bamd_prefill_valu.h", "bamd_prefill_family.h", "bamd_flt_device.h", "bamd_bf16_range.h", "bamd_matvec_b32.h", "bamd_matvec_core.h", "bamd_mv_select.h", "bamd_attn_fused.h", "bamd_attn_batch.h", "bamd_mfma_common.h", "bamd_gguf.h", "bamd_vocab.h", "bamd_unicode_tables.h", "../../include/bamd.h", "../../include/booster_bridge.h"]
 # -ffp-contract=off: the numerics contract (bit-parity with the reference CPU path) forbids implicit FMA fusion.
 # -fno-slp-vectorize (decode kernels only, NO_SLP): SLP packs neighbouring f32 multiplies into v_pk_mul_f32, whose operands need
 # even-aligned register pairs: the copies it adds sit right behind the loads (a full s_waitcnt before the weight ring could be
 # requested) and packed f32 is no faster there.  The prefill kernels keep SLP: their f32 chains run on float4 accumulators, where
 # v_pk_fma_f32 halves the instruction count (same IEEE fma per element).
-NO_SLP = ("bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_colaunch.hip", "bamd_attention_gs.hip")
+NO_SLP = ("bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_colaunch.hip", "bamd_attention_gs.hip", "bamd_prefill2_bf16.hip")
 # gfx950 kernarg preload for the decode mat-vec kernels: their leading scalar parameters (BAMD_LEAD_PARAMS: activation / weight pointers, K, eps)
 # arrive in SGPRs at wave launch, so the first requests do not wait for an s_load of the argument block (+0.3 % decode, measured)
 KERNARG_PRELOAD = {"bamd_matvec_fast_a.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"], "bamd_matvec_fast_b.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}

@@ -95,6 +95,7 @@ struct DevMat {                      // one quantised matrix resident in HBM
     int type = 0, nrows = 0, K = 0;  // nrows = rows in the GGUF
     int nrows_pad = 0;               // rows of the stream (next multiple of 8; missing rows are zero records)
     size_t bytes = 0;
+    uint32_t bf16_range = BAMD_BF16_RANGE_UNKNOWN;   // BF16: the exponent range of its weights (bamd_bf16_range.h), measured once when the stream is packed
 };
 struct DevLayer {
     float * attn_norm = nullptr, * ffn_norm = nullptr;
@@ -175,6 +176,7 @@ struct bamd_context {
     int bcap = 0;
     float * attn_bscr = nullptr; size_t attn_bscr_bytes = 0, attn_bscr_failed = 0;   // score rows of the batched prefill attention: the matrix-core kernel beyond BAMD_AM_MAXPOS = 512 positions, every kernel beyond the LDS (ensure_attn_scratch: grow-only under the budget; absent = the VALU kernels with their rows in LDS, token by token beyond)
     float * bx = nullptr, * bx2 = nullptr, * bqkv = nullptr, * batt = nullptr, * bh = nullptr; unsigned char * bblob = nullptr, * bblob16 = nullptr;
+    uint32_t * bbfr = nullptr;      // beside bblob: one range word per token of its bf16 rows (bamd_bf16_range.h)
     std::vector<void *> allocs;
 };
 
@@ -217,6 +219,7 @@ static int upload_mat(bamd_model * m, const GgufTensor * t, DevMat & d, bool kee
         else { if (dev_alloc(m->allocs, &d.stream, stream_bytes)) return 1; if (d.nrows_pad != d.nrows) HIPC(hipMemsetAsync(d.stream, 0, stream_bytes, s)); }
         bamd_launch_repack(rawdev, d.stream, d.type, d.nrows, d.K, s);
         HIPC(hipGetLastError());
+        if (d.type == BAMD_BF16 && bamd_bf16_weight_range(d.stream, stream_bytes, &d.bf16_range, s)) return fail("tensor " + t->name + ": measuring the exponent range failed");
         m->weight_bytes += (int64_t) t->nbytes;
     }
     HIPC(hipStreamSynchronize(s));     // staging buffer is reused by the next tensor
@@ -494,16 +497,18 @@ static unsigned long long * tl_next(bamd_context * c) {
 static void seg_of(bamd_mv_seg & sg, const DevMat & d, float * out) { sg.w = d.stream; sg.out = out; sg.type = d.type; sg.nrows = d.nrows_pad; sg.nvalid = d.nrows; }
 // wq | wk | wv share one allocation and their outputs are contiguous (q | k | v from `out`): equal-typed neighbours are ONE segment, one weight stream.  The only place that rule is written down: the decode step,
 // the batched prefill and the prefill side tables (DevLayer::aux_qkv) take their segments from here.  nrows / nvalid: as seg_of counts the first matrix + the GGUF rows of each one merged into it; rows_pad: stream rows
-static int qkv_segments(const DevLayer & ly, float * out, bamd_mv_seg sg[3], int rows_pad[3] = nullptr) {
+// bf16_range: the range word of each segment's weights (the union over the matrices merged into it)
+static int qkv_segments(const DevLayer & ly, float * out, bamd_mv_seg sg[3], int rows_pad[3] = nullptr, uint32_t bf16_range[3] = nullptr) {
     const DevMat * mats[3] = { &ly.wq, &ly.wk, &ly.wv };
-    int n = 0, off = 0, pad[3];
+    int n = 0, off = 0, pad[3]; uint32_t wr[3] = { BAMD_BF16_RANGE_UNKNOWN, BAMD_BF16_RANGE_UNKNOWN, BAMD_BF16_RANGE_UNKNOWN };
     for (int j = 0; j < 3; ++j) {
         const DevMat & d = *mats[j];
-        if (j && d.type == mats[j - 1]->type) { sg[n - 1].nrows += d.nrows; sg[n - 1].nvalid += d.nrows; pad[n - 1] += d.nrows_pad; }
-        else { seg_of(sg[n], d, out ? out + off : nullptr); pad[n++] = d.nrows_pad; }
+        if (j && d.type == mats[j - 1]->type) { sg[n - 1].nrows += d.nrows; sg[n - 1].nvalid += d.nrows; pad[n - 1] += d.nrows_pad; wr[n - 1] = bamd_bf16_range_join(wr[n - 1], d.bf16_range); }
+        else { seg_of(sg[n], d, out ? out + off : nullptr); wr[n] = d.bf16_range; pad[n++] = d.nrows_pad; }
         off += d.nrows;
     }
     if (rows_pad) memcpy(rows_pad, pad, sizeof pad);
+    if (bf16_range) memcpy(bf16_range, wr, sizeof wr);
     return n;
 }
 
@@ -874,7 +879,7 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
         items.push_back({ ly.wu.stream, ly.wu.type, ly.wu.nrows_pad, m->E, &ly.aux_u });
         items.push_back({ ly.wd.stream, ly.wd.type, ly.wd.nrows_pad, m->F, &ly.aux_d });
     }
-    // F32 / F16 matrices with BAMD_PREFILL_FLT on: their matrix-core kernel has no side table (bamd_batch_mm reads the switch at each launch), so they ask for
+    // F32 / F16 matrices with BAMD_PREFILL_FLT on, BF16 ones with BAMD_PREFILL_BF16 on: their matrix-core kernel has no side table (bamd_batch_mm reads the switch at each launch), so they ask for
     // nothing here; a model of such matrices only has nothing to build and nothing to report
     const size_t n_all = items.size();
     items.erase(std::remove_if(items.begin(), items.end(), [](const Item & it) { return bamd_prefill_mfma_type_notable(it.type); }), items.end());
@@ -921,6 +926,7 @@ static int ensure_batch_buffers(bamd_context * c) {
         dev_alloc(c->allocs, (void **) &c->bqkv, T * (m->E + 2 * Ekv) * 4) || dev_alloc(c->allocs, (void **) &c->batt, T * m->E * 4) ||
         dev_alloc(c->allocs, (void **) &c->bh, T * m->F * 4) ||
         dev_alloc(c->allocs, (void **) &c->bblob, T * std::max(bamd_blob_bytes(std::max(m->E, m->F)), flt_bytes)) ||      // (an unquantised matrix takes its activations as f32 / bf16 rows)
+        dev_alloc(c->allocs, (void **) &c->bbfr, T * 4) ||
         dev_alloc(c->allocs, (void **) &c->bblob16, T * bamd_blob16_bytes(std::max(m->E, m->F)))) return 1;     // (one stride for every form: the K-quant record's 608 B hold the 544 B of the Q8_0 form and the 576 B of the Q8_1 form)
     c->bcap = (int) T;
     return 0;
@@ -928,11 +934,13 @@ static int ensure_batch_buffers(bamd_context * c) {
 // one batched mat-mul: K-quant segments with a side table on the matrix-core kernels, the rest on the integer-dot kernel (identical bits either way).
 // aux[i]: side table of segment i (null: none); blob16: the f16 activations of the matrix-core kernel.  The ONE place this routing is written down: the
 // prompt path below and the op-level entry point (bamd_op_mul_mat_batch_seg) both come through here
-int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s) {
+int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s, const bamd_bf16_ranges * bf) {
     const int T = a.T;
-    // (F32 / F16 with BAMD_PREFILL_FLT on: no side table — the switch is read here, at each launch; their kernel takes the f32 rows of a.blob.  BF16 never)
-    auto on_mfma = [&](int i) { return g_prefill_mfma && (bamd_prefill_mfma_type_notable(a.seg[i].type) || (aux[i] && bamd_prefill_mfma_type(a.seg[i].type))); };
+    // (F32 / F16 with BAMD_PREFILL_FLT on: no side table — the switch is read here, at each launch; their kernel takes the f32 rows of a.blob.  BF16 with
+    // BAMD_PREFILL_BF16 on: the same, with the bf16 rows and the range words beside them)
+    auto on_mfma = [&](int i) { return g_prefill_mfma && ((bamd_prefill_mfma_type_notable(a.seg[i].type) && (a.seg[i].type != BAMD_BF16 || bf)) || (aux[i] && bamd_prefill_mfma_type(a.seg[i].type))); };
     auto mm_mfma = [&](const bamd_mv_seg & sg, const void * ax, int nv, float * out, const float * res, int e) {
+        if (sg.type == BAMD_BF16) return bamd_launch_matmul_mfma_bf16(sg.w, bf->w[&sg - a.seg], nv, sg.nrows, a.K, a.blob, bf->x, T, out, res, e, a.ldo, s);
         if (sg.type == BAMD_F32 || sg.type == BAMD_F16) return bamd_launch_matmul_mfma_flt(sg.w, sg.type, nv, sg.nrows, a.K, a.blob, T, out, res, e, a.ldo, s);
         return bamd_launch_matmul_mfma2(sg.w, ax, sg.type, nv, sg.nrows, a.K, blob16, T, out, res, e, a.ldo, s);
     };
@@ -960,7 +968,11 @@ int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * con
     }
     return 0;
 }
-static int batch_mm(bamd_context * c, const bamd_mm_args & a, int epi, hipStream_t s, const void * const * aux) { return bamd_batch_mm(a, epi, c->bblob16, aux, c->m->n_cu, s); }
+static int batch_mm(bamd_context * c, const bamd_mm_args & a, int epi, hipStream_t s, const void * const * aux, uint32_t w0 = BAMD_BF16_RANGE_UNKNOWN, uint32_t w1 = BAMD_BF16_RANGE_UNKNOWN,
+                    uint32_t w2 = BAMD_BF16_RANGE_UNKNOWN) {
+    const bamd_bf16_ranges bf = { c->bbfr, { w0, w1, w2 } };
+    return bamd_batch_mm(a, epi, c->bblob16, aux, c->m->n_cu, s, &bf);
+}
 // first stage: tokens already in c->forced; later stages: hidden_in [T][E] f32 on this device.  Last stage: leaves the hidden state of
 // the LAST token in c->x (for lm_head); other stages: writes hidden_out [T][E] (possibly on the next device: peer copy).
 static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_t s, const void * hidden_in = nullptr, void * hidden_out = nullptr) {
@@ -978,14 +990,14 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         // q,k,v                                                            (llama.cpp:8810-8835)
         // (the activation form of each mat-mul follows its weights: Q8_0 blocks for Q4_0 / Q5_0 / Q8_0, Q8_1 blocks for Q4_1 / Q5_1, else Q8_K; the load refused a QKV launch that would need both)
         // (one quantisation and one mat-mul per activation form: qkv_groups)
-        bamd_mv_seg qs[3]; int gf[4];
-        const int ng = qkv_groups(qs, qkv_segments(ly, c->bqkv, qs), gf);
+        bamd_mv_seg qs[3]; int gf[4]; uint32_t qr[3 + 2] = { 0 };
+        const int ng = qkv_groups(qs, qkv_segments(ly, c->bqkv, qs, nullptr, qr), gf);
         for (int g = 0; g < ng; ++g) {
-            bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(qs[gf[g]].type));
+            bamd_launch_quantize_batch(c->bx, ly.attn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(qs[gf[g]].type), c->bbfr);
             memset(&a, 0, sizeof a);
             for (int i = gf[g]; i < gf[g + 1]; ++i) a.seg[a.nseg++] = qs[i];
             a.blob = c->bblob; a.K = E; a.T = T; a.ldo = ldq;
-            if (batch_mm(c, a, BAMD_EPI_STORE, s, ly.aux_qkv + gf[g])) return fail("batched mat-mul: unsupported shape");
+            if (batch_mm(c, a, BAMD_EPI_STORE, s, ly.aux_qkv + gf[g], qr[gf[g]], qr[gf[g] + 1], qr[gf[g] + 2])) return fail("batched mat-mul: unsupported shape");
         }
         // RoPE, KV store, attention with the T>1 semantics                  (llama.cpp:8837-8849, :8318-8353)
         bamd_attn_args t; memset(&t, 0, sizeof t);
@@ -997,20 +1009,20 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         const size_t bud = attn_scratch_budget(), blk = bud && bud < c->attn_bscr_bytes ? bud : c->attn_bscr_bytes;   // (a budget lowered after the block grew still bounds the slices)
         if (bamd_launch_attention_batch(t, gq, T, s, 0, blk)) return fail("batched attention: unsupported head configuration");
         // x2 = x + Wo . att
-        bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wo.type));
+        bamd_launch_quantize_batch(c->batt, nullptr, 0.f, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wo.type), c->bbfr);
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wo, c->bx2); a.nseg = 1; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = E; a.res = c->bx;
-        { const void * ax[3] = { ly.aux_o, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }
+        { const void * ax[3] = { ly.aux_o, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax, ly.wo.bf16_range)) return fail("batched mat-mul: unsupported shape"); }
         // h = silu(Wg . a) * (Wu . a)
-        bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wg.type));
+        bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wg.type), c->bbfr);
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wg, c->bh); seg_of(a.seg[1], ly.wu, c->bh); a.nseg = 2; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = F;
-        { const void * ax[3] = { ly.aux_g, ly.aux_u, nullptr }; if (batch_mm(c, a, BAMD_EPI_SILU_MUL, s, ax)) return fail("batched mat-mul: unsupported shape"); }
+        { const void * ax[3] = { ly.aux_g, ly.aux_u, nullptr }; if (batch_mm(c, a, BAMD_EPI_SILU_MUL, s, ax, ly.wg.bf16_range, ly.wu.bf16_range)) return fail("batched mat-mul: unsupported shape"); }
         // x = x2 + Wd . h
-        bamd_launch_quantize_batch(c->bh, nullptr, 0.f, F, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wd.type));
+        bamd_launch_quantize_batch(c->bh, nullptr, 0.f, F, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wd.type), c->bbfr);
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wd, c->bx); a.nseg = 1; a.blob = c->bblob; a.K = F; a.T = T; a.ldo = E; a.res = c->bx2;
-        { const void * ax[3] = { ly.aux_d, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax)) return fail("batched mat-mul: unsupported shape"); }
+        { const void * ax[3] = { ly.aux_d, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax, ly.wd.bf16_range)) return fail("batched mat-mul: unsupported shape"); }
     }
     if (m->with_output) HIPC(hipMemcpyAsync(c->x, c->bx + (size_t) (T - 1) * E, (size_t) E * 4, hipMemcpyDeviceToDevice, s));
     else HIPC(hipMemcpyAsync(hidden_out, c->bx, (size_t) T * E * 4, hipMemcpyDeviceToDevice, s));

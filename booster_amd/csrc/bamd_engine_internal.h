@@ -28,6 +28,8 @@ void rope_row(float * cache, int32_t pos, int n_dims, float freq_base, float fre
 void k_shift_table(const int32_t * delta, int n_cells, int n_idx, int hd, float freq_base, float freq_scale, const float * freq_factors,
                    float ext_factor, float attn_factor, int n_ctx_orig, std::vector<int32_t> & idx, std::vector<float> & tab);
 // defined in bamd_engine.cpp: one batched prompt mat-mul, each segment routed to the matrix-core kernel (side table aux[i], f16 activations blob16) or to the
-// integer-dot kernel — the prompt path's routing, shared with bamd_op_mul_mat_batch_seg
+// integer-dot kernel — the prompt path's routing, shared with bamd_op_mul_mat_batch_seg.  bf: what BF16 segments on their matrix-core kernel need beside the blob
+// (bamd_bf16_range.h): x = [T] the tokens' range words (bamd_launch_quantize_batch), w[i] = the range word of segment i; null: such segments stay on the VALU kernel
 struct bamd_mm_args;
-int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s);
+struct bamd_bf16_ranges { const uint32_t * x; uint32_t w[3]; };
+int bamd_batch_mm(bamd_mm_args a, int epi, const void * blob16, const void * const * aux, int n_cu, hipStream_t s, const bamd_bf16_ranges * bf = nullptr);

@@ -17,6 +17,7 @@
 //   bf16 form  element k = 256b + 32i + c (c = 8a + j) at half 256b + 8c + i: chain lane c reads the eight steps of a record as one uint4
 #pragma once
 #include "bamd_device.h"
+#include "bamd_bf16_range.h"
 
 // ggml_compute_fp32_to_bf16 (ggml-impl.h:88-101), in integer arithmetic
 __device__ __forceinline__ uint32_t flt_bf16_bits(float f) {
@@ -30,8 +31,10 @@ constexpr size_t flt_lds_bytes(bool bf, int K) { return (size_t) K * (bf ? 2 : 4
 
 // Activation prologue of one workgroup: x[K] (inter-kernel data: sc1 loads) -> dst in the form's order, NORM: (x * scale) * nw first (ggml_vec_scale_f32 then
 // ggml_mul, llama.cpp:7940-7950; the sum of squares in f64 with the order guard of bamd_device.h).  Ends with a workgroup barrier.
+// rng (BF only; null: none): two LDS words the caller set to { BAMD_BF16_RANGE_NONE & 0xffff, 0 } in front of a barrier — behind the final barrier they hold the
+// lowest and the highest exponent of the bf16 patterns stored (bamd_bf16_range.h: the guard of bamd_prefill2_bf16.hip)
 template <bool NORM, bool BF>
-__device__ __forceinline__ void flt_act(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, unsigned char * dst, double * red) {
+__device__ __forceinline__ void flt_act(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, unsigned char * dst, double * red, uint32_t * rng = nullptr) {
     const int lane = threadIdx.x & 63, wave = wave_id(), nwaves = (int) (blockDim.x >> 6), n4 = K >> 2;
     const bamd_ik_rsrc rx = ik_rsrc(x);
     float scale = 1.0f;
@@ -61,6 +64,7 @@ __device__ __forceinline__ void flt_act(const float * __restrict__ x, const floa
         }
         scale = 1.0f / sqrtf(mean + eps);
     }
+    uint32_t rlo = BAMD_BF16_RANGE_NONE & 0xffffu, rhi = 0u;
     for (int k4 = threadIdx.x; k4 < n4; k4 += blockDim.x) {
         float4 v = ik_ld128f(rx, (uint32_t) k4 * 16u);
         if (NORM) {
@@ -72,11 +76,19 @@ __device__ __forceinline__ void flt_act(const float * __restrict__ x, const floa
             unsigned short * d = (unsigned short *) dst + ((k >> 8) << 8) + ((k >> 5) & 7) + ((k & 31) << 3);
             d[0] = (unsigned short) flt_bf16_bits(v.x); d[8] = (unsigned short) flt_bf16_bits(v.y);
             d[16] = (unsigned short) flt_bf16_bits(v.z); d[24] = (unsigned short) flt_bf16_bits(v.w);
+            if (rng) {                                                         // (the bits just stored)
+                bamd_bf16_range_add(rlo, rhi, flt_bf16_bits(v.x)); bamd_bf16_range_add(rlo, rhi, flt_bf16_bits(v.y));
+                bamd_bf16_range_add(rlo, rhi, flt_bf16_bits(v.z)); bamd_bf16_range_add(rlo, rhi, flt_bf16_bits(v.w));
+            }
         } else {
             const int i = k >> 3;
             float * d = (float *) dst + ((i >> 2) << 5) + ((k & 7) << 2) + (i & 3);
             d[0] = v.x; d[4] = v.y; d[8] = v.z; d[12] = v.w;
         }
+    }
+    if (BF && rng) {
+        for (int o = 32; o; o >>= 1) { const uint32_t l2 = __shfl_xor(rlo, o), h2 = __shfl_xor(rhi, o); rlo = l2 < rlo ? l2 : rlo; rhi = h2 > rhi ? h2 : rhi; }
+        if (lane == 0) { atomicMin(rng, rlo); atomicMax(rng + 1, rhi); }
     }
     __syncthreads();
 }

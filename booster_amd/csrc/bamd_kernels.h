@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/bamd.h"   // bamd_logit_penalty, bamd_shortlist_head
 #include "bamd_formats.h"
+#include "bamd_bf16_range.h"
 
 enum { BAMD_PRO_PLAIN = 0, BAMD_PRO_NORM = 1 };
 enum { BAMD_EPI_STORE = 0, BAMD_EPI_ADD = 1, BAMD_EPI_SILU_MUL = 2, BAMD_EPI_ARGMAX = 3 };
@@ -91,7 +92,8 @@ void bamd_launch_repack_flt(const void * raw, void * dst, int type, int nrows, i
 void bamd_launch_act_bf16_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s);
 // batched prompt path of that family (bamd_prefill_flt.hip; behind bamd_launch_quantize_batch / bamd_launch_matmul_batch): a token's activations are
 // bamd_flt_act_bytes(form, K) bytes, in the order the chains read them
-void bamd_launch_act_batch_flt(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s);
+// xrange (bf16 form; null: none): [T] range words of the tokens' stored patterns, for bamd_launch_matmul_mfma_bf16 (bamd_bf16_range.h)
+void bamd_launch_act_batch_flt(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, uint32_t * xrange = nullptr);
 int  bamd_launch_matmul_batch_flt(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);
 [[nodiscard]] static inline int bamd_launch_mv(const bamd_mv_args & a, int pro, int epi, int n_cu, hipStream_t s) {
     if (a.nseg > 0 && bamd_is_flt(a.seg[0].type)) return bamd_launch_matvec_flt(a, pro, epi, n_cu, s);
@@ -119,7 +121,9 @@ static inline size_t bamd_act_blob_bytes(int form, int K) { const size_t f = bam
 // form (bamd_act_form_of the consuming mat-mul's weights): BAMD_ACT_Q8_0 for Q8_0 / Q4_0 / Q5_0 weights, BAMD_ACT_Q8_1 for Q4_1 / Q5_1 — blob takes the Q8_0 / Q8_1 form
 // of the same size (bamd_prefill_b32.hip); blob16 is written, in the f16 form of bamd_prefill2_b32.hip (544 / 576 bytes of a record, the same per-token stride), only
 // while a family that reads this form is on (bamd_prefill_reads_act16, bamd_prefill_family.h; otherwise nothing reads it)
-void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K);
+// bf16_range (BAMD_ACT_BF16 only; null: none): [T] words, one per token: the exponent range of its bf16 activations (bamd_bf16_range.h), written for the guard of
+// the BF16 matrix-core kernel; the blob is the same with and without
+void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form = BAMD_ACT_Q8_K, uint32_t * bf16_range = nullptr);
 void bamd_launch_quantize_batch_b32(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, void * blob16 = nullptr);
 int  bamd_launch_matmul_batch_b32_nl(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);       // its launches with an IQ4_NL segment (bamd_prefill_b32_nl.hip); callers go through the next
 int  bamd_launch_matmul_batch_b32(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);          // every segment of the family of segment 0 (Q8_0 / Q4_0 / Q5_0, or Q4_1 / Q5_1), a.blob in its form; 1 = shape not supported
@@ -140,11 +144,19 @@ void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad,
 int  bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                                  int epi, int ldo, hipStream_t s);
 // F32 / F16 matrices on the matrix cores, exact (bamd_prefill2_flt.hip): the kernel reads the resident weight stream and the f32 activation rows of
-// bamd_launch_act_batch_flt (blob) as they are, there is no side table to build.  BF16 has no such kernel.  Epilogues as bamd_launch_matmul_mfma2; 1 = type / shape
+// bamd_launch_act_batch_flt (blob) as they are, there is no side table to build.  BF16: the kernel below.  Epilogues as bamd_launch_matmul_mfma2; 1 = type / shape
 // not supported.  bamd_prefill_mfma_count: one more launch of `type` for bamd_prefill_mfma_runs (every matrix-core launcher; the counters live in bamd_prefill2.hip)
 int  bamd_launch_matmul_mfma_flt(const void * w_stream, int type, int nrows, int nrows_pad, int K, const void * blob, int T, float * out, const float * res, int epi, int ldo,
                                  hipStream_t s);
 void bamd_prefill_mfma_count(int type);
+// BF16 matrices on the matrix cores, exact (bamd_prefill2_bf16.hip; BAMD_PREFILL_BF16): the resident weight stream and the bf16 activation rows of
+// bamd_launch_act_batch_flt as they are, no side table.  wrange: the range word of the matrix (bamd_bf16_weight_range over its stream: synchronises s, load time
+// only), xrange: [T] the tokens' range words, written by the activation pass — a workgroup whose ranges do not prove every product exact in f32 runs the VALU
+// step instead and is counted (bamd_bf16_fallback_tiles_all: synchronises every device that launched, sums the counters).  1 = shape not supported
+int  bamd_bf16_weight_range(const void * w_stream, size_t bytes, uint32_t * word, hipStream_t s);
+int  bamd_launch_matmul_mfma_bf16(const void * w_stream, uint32_t wrange, int nrows, int nrows_pad, int K, const void * blob, const uint32_t * xrange, int T, float * out,
+                                  const float * res, int epi, int ldo, hipStream_t s);
+unsigned long long bamd_bf16_fallback_tiles_all(void);
 int  bamd_launch_matmul_batch(const bamd_mm_args & a, int epi, int n_cu, hipStream_t s);      // 1 = shape not supported
 void bamd_launch_embed_batch(const int32_t * tokens, int T, const void * embd, int embd_type, int E, int V, float * x, hipStream_t s);
 // impl: 0 = the matrix-core kernel where it covers the shape, else the VALU kernels (the engine); 1 = the VALU kernels only; 2 = the matrix-core

@@ -117,7 +117,8 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_vec_argmax
     return 0;
 }
 // batched mat-mul of T activation rows against one matrix through the prefill kernels: impl 0 = integer-dot kernel, 2 = matrix-core kernel (1 and 3 were the generations removed in round 6)
-// (F32 / F16 / BF16: impl 0 = the VALU kernel; impl 2 = the f32 matrix-core kernel, for F32 / F16 only and only while BAMD_PREFILL_FLT is on)
+// (F32 / F16 / BF16: impl 0 = the VALU kernel; impl 2 = the f32 matrix-core kernel, for F32 / F16 only while BAMD_PREFILL_FLT is on, for BF16 only while
+// BAMD_PREFILL_BF16 is on)
 extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const float * x, int T, const float * norm_w,
                                                                               float eps, const float * residual, float * y, int impl) {
     if (need_device()) return 1;
@@ -131,10 +132,16 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     if (!raw || !str || !dx || !dy || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     HIPC(hipMemset(str, 0, wbp));
     bamd_launch_repack(raw, str, type, nrows, k, nullptr);
-    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(type));
-    const bool flt_mfma = impl == 2 && bamd_prefill_mfma_type_notable(type);      // F32 / F16 with BAMD_PREFILL_FLT on: bamd_prefill2_flt.hip, no side table
+    const bool flt_mfma = impl == 2 && bamd_prefill_mfma_type_notable(type);      // F32 / F16 with BAMD_PREFILL_FLT on: bamd_prefill2_flt.hip, no side table; BF16 with BAMD_PREFILL_BF16 on: bamd_prefill2_bf16.hip
+    uint32_t * xr = flt_mfma && type == BAMD_BF16 ? (uint32_t *) t.up(nullptr, (size_t) T * 4) : nullptr;      // the tokens' range words, beside the blob
+    if (flt_mfma && type == BAMD_BF16 && !xr) return fail("device alloc failed");
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(type), xr);
     if (bamd_is_flt(type) && impl != 0 && !flt_mfma) return fail(impl == 2 ? "MFMA path: unsupported type/shape (F32 / F16 / BF16 have no matrix-core kernel)" : "batched mat-mul: impl must be 0 for F32 / F16 / BF16");
-    if (flt_mfma) {
+    if (flt_mfma && type == BAMD_BF16) {
+        uint32_t wr = BAMD_BF16_RANGE_UNKNOWN;                             // measured where the stream is packed, as the loader does
+        if (bamd_bf16_weight_range(str, wbp, &wr, nullptr)) return fail("measuring the exponent range failed");
+        if (bamd_launch_matmul_mfma_bf16(str, wr, nrows, nrows_pad, k, blob, xr, T, dy, dres, dres ? BAMD_EPI_ADD : BAMD_EPI_STORE, nrows, nullptr)) return fail("MFMA path: unsupported type/shape");
+    } else if (flt_mfma) {
         if (bamd_launch_matmul_mfma_flt(str, type, nrows, nrows_pad, k, blob, T, dy, dres, dres ? BAMD_EPI_ADD : BAMD_EPI_STORE, nrows, nullptr)) return fail("MFMA path: unsupported type/shape");
     } else if (impl == 2) {                                             // the matrix-core kernel: side table built here, as the engine builds it at model load
         if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K with the switch off (bamd_prefill_mfma_type): the integer-dot kernel only
@@ -355,6 +362,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_attention_batch(co
 // out: nrows padded to 8 per segment, nvalid the real rows, segment i's output `rows[0] + .. + rows[i - 1]` floats behind `out`
 struct SegFixture {
     bamd_mv_seg seg[3]; int nseg = 0, total = 0;
+    uint32_t bf16_range[3] = { BAMD_BF16_RANGE_UNKNOWN, BAMD_BF16_RANGE_UNKNOWN, BAMD_BF16_RANGE_UNKNOWN };      // of the BF16 segments (bamd_bf16_range.h)
     int build(Tmp & t, int n, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, float * out, bool same_out = false) {
         if (n < 1 || n > 3 || k <= 0 || k % 256) return fail("bad segment count / row length");
         for (int i = 0; i < n; ++i) {
@@ -365,6 +373,7 @@ struct SegFixture {
             if (!raw || !str) return fail("device alloc/copy failed");
             HIPC(hipMemset(str, 0, wbp));
             bamd_launch_repack(raw, str, types[i], rows[i], k, nullptr);
+            if (types[i] == BAMD_BF16 && bamd_bf16_weight_range(str, wbp, &bf16_range[i], nullptr)) return fail("measuring the exponent range failed");
             seg[i].w = str; seg[i].out = same_out ? out : out + total; seg[i].type = types[i]; seg[i].nrows = pad; seg[i].nvalid = rows[i];
             total += rows[i];
         }
@@ -395,7 +404,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_fused_qkv(int nseg
 // + residual; SILU_MUL: gate and up into the same columns), routed by bamd_batch_mm.  impl 0: no side tables (integer-dot kernel); impl 2: a side table for
 // every segment whose type has a matrix-core kernel, built as build_prefill_aux builds them — the others stay on the integer-dot kernel.  F32 / F16 segments need
 // no table: while BAMD_PREFILL_FLT is on, bamd_batch_mm sends them to their matrix-core kernel (at impl 0 as well, as the engine would); while it is off, and for
-// BF16 always, impl 2 is refused for the unquantised family
+// BF16 while BAMD_PREFILL_BF16 is off, impl 2 is refused for the unquantised family
 extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(int nseg, const int32_t * types, const void * const * w_raw, const int32_t * rows, int k, const float * x,
                                                                                   int T, const float * norm_w, float eps, int ldo, const float * residual, int epi, int impl, float * y) {
     if (need_device()) return 1;
@@ -412,7 +421,9 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(
     if (!dy || !dx || !blob || !blob16 || (norm_w && !dw) || (residual && !dres)) return fail("device alloc/copy failed");
     SegFixture f; if (f.build(t, nseg, types, w_raw, rows, k, dy, epi == BAMD_EPI_SILU_MUL)) return 1;
     for (int i = 1; i < nseg; ++i) if (bamd_act_form_of(f.seg[i].type) != bamd_act_form_of(f.seg[0].type)) return fail(bamd_is_flt(f.seg[i].type) || bamd_is_flt(f.seg[0].type) ? "batched mat-mul: segments that need different activation forms (Q8_K, Q8_0, Q8_1, F32, BF16)" : bamd_is_q1(f.seg[i].type) || bamd_is_q1(f.seg[0].type) ? "batched mat-mul: segments that need different activation forms (Q8_K, Q8_0, Q8_1)" : "batched mat-mul: segments that need both activation forms (Q8_K and Q8_0)");
-    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(f.seg[0].type));
+    bamd_bf16_ranges bf = { (const uint32_t *) t.up(nullptr, (size_t) T * 4), { f.bf16_range[0], f.bf16_range[1], f.bf16_range[2] } };
+    if (!bf.x) return fail("device alloc failed");
+    bamd_launch_quantize_batch(dx, dw, eps, k, T, blob, blob16, nullptr, bamd_act_form_of(f.seg[0].type), (uint32_t *) bf.x);
     const void * aux[3] = { nullptr, nullptr, nullptr };
     // (F32 / F16 with BAMD_PREFILL_FLT on have a matrix-core kernel without a side table: bamd_batch_mm routes them by the switch alone)
     if (impl == 2 && bamd_is_flt(f.seg[0].type) && !bamd_prefill_mfma_type_notable(f.seg[0].type)) return fail("MFMA path: unsupported type/shape (F32 / F16 / BF16 have no matrix-core kernel)");
@@ -427,7 +438,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch_seg(
     bamd_mm_args a; memset(&a, 0, sizeof a);
     for (int i = 0; i < nseg; ++i) a.seg[i] = f.seg[i];
     a.nseg = nseg; a.blob = (const uint8_t *) blob; a.K = k; a.T = T; a.ldo = ldo; a.res = epi == BAMD_EPI_ADD ? dres : nullptr;
-    if (bamd_batch_mm(a, epi, blob16, aux, n_cu0(), nullptr)) return fail("batched mat-mul: unsupported shape");
+    if (bamd_batch_mm(a, epi, blob16, aux, n_cu0(), nullptr, &bf)) return fail("batched mat-mul: unsupported shape");
     return finish(y, dy, ob);
 }
 

@@ -115,8 +115,8 @@ __global__ void __launch_bounds__(256) embed_batch_kernel(const int32_t * __rest
 // ---- batched prefill launchers ------------------------------------------------------------------------------------------
 size_t bamd_blob_bytes(int K) { return BAMD_BLOB_BYTES(K >> 8); }
 size_t bamd_blob16_bytes(int K) { return BAMD_BLOB16_BYTES(K >> 8); }
-void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form) {
-    if (form == BAMD_ACT_F32 || form == BAMD_ACT_BF16) { bamd_launch_act_batch_flt(form, x, nw, eps, K, T, blob, s); return; }
+void bamd_launch_quantize_batch(const float * x, const float * nw, float eps, int K, int T, void * blob, void * blob16, hipStream_t s, int form, uint32_t * bf16_range) {
+    if (form == BAMD_ACT_F32 || form == BAMD_ACT_BF16) { bamd_launch_act_batch_flt(form, x, nw, eps, K, T, blob, s, bf16_range); return; }
     if (form == BAMD_ACT_Q8_1 || form == BAMD_ACT_Q8_0) { bamd_launch_quantize_batch_b32(form, x, nw, eps, K, T, blob, s, bamd_prefill_reads_act16(form) ? blob16 : nullptr); return; }
     if (nw) hipLaunchKernelGGL((quantize_batch_kernel<true>),  dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);
     else    hipLaunchKernelGGL((quantize_batch_kernel<false>), dim3(T), dim3(512), act_lds_bytes(K), s, x, nw, eps, K, (uint8_t *) blob, (uint8_t *) blob16);

@@ -1,6 +1,6 @@
 // bamd_prefill2_flt.hip — the exact matrix-core prompt mat-mul for F32 / F16 weights x f32 activations, behind the switch BAMD_PREFILL_FLT=1 /
-// bamd_set_prefill_flt (default off; the families and their switches: bamd_prefill_family.h).  BF16 weights stay on the VALU kernel of bamd_prefill_flt.hip: their chain is add(mul(w, x), c) with two roundings, which
-// an fma chain does not restate below 2^-126.
+// bamd_set_prefill_flt (default off; the families and their switches: bamd_prefill_family.h).  BF16 weights have a kernel and a switch of their own (bamd_prefill2_bf16.hip, BAMD_PREFILL_BF16): their chain
+// is add(mul(w, x), c) with two roundings, which an fma chain restates only where every product is exact in f32 — that kernel proves it from exponent ranges.
 //
 // Arithmetic: the contract of bamd_flt_device.h.  One output = ONE 8-lane accumulator, lane j: acc_j = fmaf(w[8i + j], x[8i + j], acc_j) for i = 0 .. K/8 - 1,
 // then hsum8_tinyblas' tree over the eight lanes.  v_mfma_f32_16x16x4_f32 is the sequential chain D = fma(a3, b3, fma(a2, b2, fma(a1, b1, fma(a0, b0, C))))

@@ -32,13 +32,15 @@ BAMD_API void bamd_set_prefill_q0(int on) { bamd_prefill_family_set(BAMD_PF_Q0, 
 BAMD_API void bamd_set_prefill_q1(int on) { bamd_prefill_family_set(BAMD_PF_Q1, on); }
 BAMD_API void bamd_set_prefill_nl(int on) { bamd_prefill_family_set(BAMD_PF_NL, on); }
 BAMD_API void bamd_set_prefill_flt(int on) { bamd_prefill_family_set(BAMD_PF_FLT, on); }
+BAMD_API void bamd_set_prefill_bf16(int on) { bamd_prefill_family_set(BAMD_PF_BF16, on); }
+BAMD_API unsigned long long bamd_prefill_bf16_fallback_tiles(void) { return bamd_bf16_fallback_tiles_all(); }
 
 // Called for a matrix without a side table (bamd_prefill_aux_bytes = 0).  With every switch off the sentences read as they did before the switches existed.  The
 // composed ones name the family's switch only where a sibling among the 32-weight block families (Q0 / Q1 / NL) is on — somebody switched one on and not this one;
 // the first such sibling in table order is named.  A type whose own family is on comes here only with a shape its kernel does not take (the load refuses those)
 #define INT_DOT "side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel (token by token where K > 35840)"
 std::string bamd_prefill_reason(int type) {
-    if (bamd_is_flt(type))      // (with FLT on, F32 / F16 need no table: only BF16 gets here)
+    if (bamd_is_flt(type))      // (with FLT on, F32 / F16 need no table: only BF16 gets here — and BF16 itself not while its own switch, BAMD_PREFILL_BF16, is on)
         return bamd_prefill_family_on(BAMD_PF_FLT) ? "the model holds a BF16 matrix: these have no matrix-core kernel (BAMD_PREFILL_FLT covers F32 / F16 only), and side tables are all-or-nothing per model, so every prompt mat-mul of the other types runs on the VALU kernels"
                                                    : "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels";
     if (type == BAMD_IQ4_NL) return "the model holds an IQ4_NL matrix: these have no matrix-core kernel (BAMD_PREFILL_Q0 covers Q4_0 / Q5_0 / Q8_0 only), and " INT_DOT "; BAMD_PREFILL_NL, the switch of the IQ4_NL matrix-core kernel, is off";

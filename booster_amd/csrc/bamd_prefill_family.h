@@ -7,19 +7,20 @@
 //   LOWBIT  Q3_K / Q2_K: the eight-wave kernel of bamd_prefill2.hip with a policy struct of their own
 //   Q0, Q1  Q8_0 / Q4_0 / Q5_0 and Q4_1 / Q5_1: one kernel template, bamd_prefill2_b32.hip
 //   NL      IQ4_NL: the Q4_0 record and side table; the same template with two accumulator sets and a 16-token tile
-//   FLT     F32 / F16 (bamd_prefill2_flt.hip); BF16 has no matrix-core kernel
+//   FLT     F32 / F16 (bamd_prefill2_flt.hip)
+//   BF16    BF16 (bamd_prefill2_bf16.hip): fma chains where exponent ranges prove every product exact, the two-rounding VALU step per workgroup otherwise
 // Families WITH A SIDE TABLE are asked three times: when a model builds its tables at load (all or nothing per model: one matrix without a table and every prompt
 // mat-mul stays on the integer-dot kernel — llama.cpp writes Q4_0 / Q5_0 files made with an importance matrix with Q4_1 / Q5_1 ffn_down matrices in their first
 // layers, so such a file needs BOTH Q0 and Q1), at each launch (a table built earlier is ignored while its family is off) and by the batch quantiser (the f16
-// activation records of the 32-weight block kernels are written only while a family reads them).  FLT has no table: its kernel reads the resident weight stream
-// and the f32 activation rows as they are, so it is asked at each launch only and applies to models loaded before.
+// activation records of the 32-weight block kernels are written only while a family reads them).  FLT and BF16 have no table: their kernels read the resident
+// weight stream and the f32 / bf16 activation rows as they are, so they are asked at each launch only and apply to models loaded before.
 // To add a family: its row here, its kernel's branch in the launcher (bamd_launch_matmul_mfma2 / bamd_batch_mm), its literal sentence in bamd_prefill_reason if the
 // composed one does not fit, its exported setter and the Python wrapper of that (booster_amd/__init__.py).
 #pragma once
 #include <string>
 #include "bamd_formats.h"
 
-enum bamd_prefill_family { BAMD_PF_K = 0, BAMD_PF_LOWBIT, BAMD_PF_Q0, BAMD_PF_Q1, BAMD_PF_NL, BAMD_PF_FLT, BAMD_PF_COUNT };
+enum bamd_prefill_family { BAMD_PF_K = 0, BAMD_PF_LOWBIT, BAMD_PF_Q0, BAMD_PF_Q1, BAMD_PF_NL, BAMD_PF_FLT, BAMD_PF_BF16, BAMD_PF_COUNT };
 // env: the switch's environment variable (null: always on); types: bit t = bamd_type t belongs to the family (every type is < 32); table: its kernels read a
 // load-time side table (bamd_prefill_aux_bytes); names: the types as the load-time message names them (null: the family has no composed sentence)
 struct bamd_prefill_family_row { const char * env; uint32_t types; bool table; const char * names; };
@@ -30,14 +31,15 @@ static const bamd_prefill_family_row bamd_prefill_families[BAMD_PF_COUNT] = {
     { "BAMD_PREFILL_Q1",     1u << BAMD_Q4_1 | 1u << BAMD_Q5_1,                   true,  "Q4_1 / Q5_1" },
     { "BAMD_PREFILL_NL",     1u << BAMD_IQ4_NL,                                   true,  "IQ4_NL" },
     { "BAMD_PREFILL_FLT",    1u << BAMD_F32 | 1u << BAMD_F16,                     false, nullptr },
+    { "BAMD_PREFILL_BF16",   1u << BAMD_BF16,                                     false, nullptr },
 };
 int  bamd_prefill_family_on(int f);
 void bamd_prefill_family_set(int f, int on);
-uint32_t bamd_prefill_types_on(bool table);      // the types of the families that are on now, with (table = true) or without a side table: six compares per call
+uint32_t bamd_prefill_types_on(bool table);      // the types of the families that are on now, with (table = true) or without a side table: seven compares per call
 static inline bool bamd_prefill_type_in(uint32_t mask, int type) { return type >= 0 && type < 32 && (mask >> type & 1u); }
 // "this weight type has a matrix-core prompt mat-mul with a side table now": side-table sizes, the launcher and the engine's routing ask here
 static inline bool bamd_prefill_mfma_type(int type) { return bamd_prefill_type_in(bamd_prefill_types_on(true), type); }
-// "this weight type has a matrix-core prompt mat-mul WITHOUT a side table now" (F32 / F16 while FLT is on)
+// "this weight type has a matrix-core prompt mat-mul WITHOUT a side table now" (F32 / F16 while FLT is on, BF16 while BF16 is on)
 static inline bool bamd_prefill_mfma_type_notable(int type) { return bamd_prefill_type_in(bamd_prefill_types_on(false), type); }
 // "a family that is on reads the f16 activation records of this activation form" (Q8_0 form: Q0 or NL; Q8_1 form: Q1)
 bool bamd_prefill_reads_act16(int form);

@@ -1,24 +1,33 @@
 // bamd_prefill_flt.hip — batched prompt path of the unquantised weight family (F32 / F16 / BF16): the activation pass for T rows and a VALU mat-mul for 1..512
 // tokens.  Every output runs the chain of the mat-vec (bamd_flt_device.h) — the reference's per-element chain does not depend on the number of tokens either
-// (tinyBLAS tiles differ only in which outputs share a loop) — so a batched prompt gives the bits of token by token.  F32 / F16: bamd_prefill2_flt.hip runs the same chains on the matrix cores (BAMD_PREFILL_FLT).
+// (tinyBLAS tiles differ only in which outputs share a loop) — so a batched prompt gives the bits of token by token.  F32 / F16: bamd_prefill2_flt.hip runs the same chains on the matrix cores (BAMD_PREFILL_FLT); BF16: bamd_prefill2_bf16.hip (BAMD_PREFILL_BF16).
 #include "bamd_flt_device.h"
 #include "bamd_kernels.h"
 
 // one workgroup per token: RMSNorm * norm_w (or the plain row) -> the row in the form's order (f32: 4 K bytes, bf16: 2 K bytes per token)
+// xrange (bf16 form only; null: none): [T] the range word of every token's stored patterns (bamd_bf16_range.h), for the guard of bamd_prefill2_bf16.hip
 template <bool NORM, bool BF>
-__global__ void __launch_bounds__(512) act_batch_flt_kernel(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, unsigned char * __restrict__ blob) {
+__global__ void __launch_bounds__(512) act_batch_flt_kernel(const float * __restrict__ x, const float * __restrict__ nw, float eps, int K, unsigned char * __restrict__ blob, uint32_t * __restrict__ xrange) {
     __shared__ double red[16];
     const size_t t = blockIdx.x;
-    flt_act<NORM, BF>(x + t * (size_t) K, nw, eps, K, blob + t * (size_t) K * (BF ? 2 : 4), red);
+    if constexpr (BF) {
+        __shared__ uint32_t rng[2];
+        if (xrange) {                                     // (kernel-uniform)
+            if (threadIdx.x == 0) { rng[0] = BAMD_BF16_RANGE_NONE & 0xffffu; rng[1] = 0u; }
+            __syncthreads();
+        }
+        flt_act<NORM, true>(x + t * (size_t) K, nw, eps, K, blob + t * (size_t) K * 2, red, xrange ? rng : nullptr);
+        if (xrange && threadIdx.x == 0) xrange[t] = rng[0] | rng[1] << 16;
+    } else flt_act<NORM, false>(x + t * (size_t) K, nw, eps, K, blob + t * (size_t) K * 4, red);
 }
-void bamd_launch_act_batch_flt(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s) {
+void bamd_launch_act_batch_flt(int form, const float * x, const float * nw, float eps, int K, int T, void * blob, hipStream_t s, uint32_t * xrange) {
     unsigned char * b = (unsigned char *) blob;
     if (form == BAMD_ACT_BF16) {
-        if (nw) hipLaunchKernelGGL((act_batch_flt_kernel<true, true>),  dim3(T), dim3(512), 0, s, x, nw, eps, K, b);
-        else    hipLaunchKernelGGL((act_batch_flt_kernel<false, true>), dim3(T), dim3(512), 0, s, x, nw, eps, K, b);
+        if (nw) hipLaunchKernelGGL((act_batch_flt_kernel<true, true>),  dim3(T), dim3(512), 0, s, x, nw, eps, K, b, xrange);
+        else    hipLaunchKernelGGL((act_batch_flt_kernel<false, true>), dim3(T), dim3(512), 0, s, x, nw, eps, K, b, xrange);
     } else {
-        if (nw) hipLaunchKernelGGL((act_batch_flt_kernel<true, false>),  dim3(T), dim3(512), 0, s, x, nw, eps, K, b);
-        else    hipLaunchKernelGGL((act_batch_flt_kernel<false, false>), dim3(T), dim3(512), 0, s, x, nw, eps, K, b);
+        if (nw) hipLaunchKernelGGL((act_batch_flt_kernel<true, false>),  dim3(T), dim3(512), 0, s, x, nw, eps, K, b, (uint32_t *) nullptr);
+        else    hipLaunchKernelGGL((act_batch_flt_kernel<false, false>), dim3(T), dim3(512), 0, s, x, nw, eps, K, b, (uint32_t *) nullptr);
     }
 }
 

@@ -218,9 +218,17 @@ void bamd_set_prefill_nl(int on);
 /* Matrix-core prompt mat-muls for F32 / F16 weights (env BAMD_PREFILL_FLT): 0 (default) = such matrices evaluate prompts on the VALU kernel; 1 = on
  * v_mfma_f32_16x16x4_f32, the same fma chains.  UNLIKE the four switches above this one is read at each launch, not at model load: the kernel reads the resident
  * weights and the f32 activation rows as they are, there is no side table (bamd_model_prefill_aux_bytes stays 0 for such a model), so it takes effect for models and
- * contexts that exist already.  BF16 weights stay on the VALU kernel either way (their chain is a multiply and an add, not an fma).  Bit-identical results. */
+ * contexts that exist already.  BF16 weights have a switch of their own (below).  Bit-identical results. */
 void bamd_set_prefill_flt(int on);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL) since the library was loaded */
+/* Matrix-core prompt mat-muls for BF16 weights (env BAMD_PREFILL_BF16): 0 (default) = such matrices evaluate prompts on the VALU kernel; 1 = on
+ * v_mfma_f32_16x16x4_f32.  A bf16 x bf16 product is exact in f32 unless it falls below 2^-149 or overflows, and there the reference's multiply-then-add is the
+ * fma of the instruction; a workgroup whose exponent ranges (one word per matrix, computed at load; one per token, written by the activation pass) do not prove
+ * that runs the two-rounding step on the vector ALUs inside the same launch.  Independent of bamd_set_prefill_flt; read at each launch like it, no side table,
+ * and with it on a BF16 matrix no longer keeps a model's other types from their side tables.  Bit-identical results. */
+void bamd_set_prefill_bf16(int on);
+/* Tests and tools: workgroups of that kernel that took the two-rounding step since the library was loaded.  Waits for every device that launched one. */
+unsigned long long bamd_prefill_bf16_fallback_tiles(void);
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL, 30 BF16) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */

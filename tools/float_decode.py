@@ -1,7 +1,8 @@
 """Greedy decode rate and prompt rate of the synthetic Llama-3-8B file as an unquantised GGUF — F16, BF16 and F32 — beside the Q8_0 file, in one job on one card.
 GPU box only.  Decode: per file a 128-token prompt, then generate_greedy of 128 steps, five repetitions after a warm-up.  Prompt: N tokens in micro-batches of
-512, five repetitions after a warm-up (BF16: the float family's VALU kernel; Q8_0 on the integer-dot kernel).  An F16 / F32 file is measured with
-set_prefill_flt off (VALU kernel) and on (f32 matrix-core kernel, bamd_prefill2_flt.hip) on ONE model and context — the switch is read at each launch —
+512, five repetitions after a warm-up (Q8_0 on the integer-dot kernel).  An F16 / F32 file is measured with set_prefill_flt, a BF16 file with
+set_prefill_bf16, off (VALU kernel) and on (f32 matrix-core kernel, bamd_prefill2_flt.hip / bamd_prefill2_bf16.hip) on ONE model and context — the switch is read
+at each launch; for BF16 the workgroups that fell back to the two-rounding step are printed too (prefill_bf16_fallback_tiles; expected 0) —
 ALTERNATING between the two, as tools/legacy_decode.py does for its switch: median and range of each, whether the switched-on median clears the switched-off
 maximum by more than the switched-off spread, and the share of the f32 MFMA peak (157.3 TFLOP/s) that the layer mat-muls' FLOP over the whole prompt time amount to.
 Beside every decode median: the bytes streamed per token (every matrix once) and the share of the 8 TB/s token roofline the rate amounts to.
@@ -45,8 +46,11 @@ def float_file(name, d="/dev/shm"):
     return p
 
 
-def prompt_pair(path, n_prompt, reps=5):
-    """switched-off and switched-on prompt rates of one F16 / F32 file, alternating on one model and context: ([off], [on], matrix-core launches counted while on)"""
+def prompt_pair(path, n_prompt, reps=5, setter=None, types=(0, 1)):
+    """switched-off and switched-on prompt rates of one float file (setter: its family's switch; types: what it counts), alternating on one model and context:
+    ([off], [on], matrix-core launches counted while on)"""
+    setter = setter or b.set_prefill_flt
+    counted = lambda: sum(b.prefill_mfma_runs(t) for t in types)
     m = b.Model(path)
     ctx = b.Context(m, 4096)
     prompt = [(7919 * i + 13) % m.n_vocab for i in range(n_prompt)]
@@ -55,19 +59,19 @@ def prompt_pair(path, n_prompt, reps=5):
     try:
         for rep in range(reps + 1):                             # the first pair warms up
             for k in (0, 1):
-                b.set_prefill_flt(bool(k))
-                before = b.prefill_mfma_runs(0) + b.prefill_mfma_runs(1)
+                setter(bool(k))
+                before = counted()
                 b.lib().bamd_kv_cache_clear(ctx.h)
                 t0 = time.perf_counter()
                 for i in range(0, n_prompt, 512):
                     ctx.decode(prompt[i:i + 512], i)
                 if rep:
                     rates[k].append(n_prompt / (time.perf_counter() - t0))
-                ran = b.prefill_mfma_runs(0) + b.prefill_mfma_runs(1) - before
+                ran = counted() - before
                 assert (ran > 0) == bool(k), "the switch did not select the kernel"
                 runs += ran
     finally:
-        b.set_prefill_flt(False)
+        setter(False)
     assert m.prefill_aux_bytes() == 0
     ctx.close(); m.close()
     return rates[0], rates[1], runs
@@ -93,6 +97,11 @@ def measure(name, p, n_prompt, only_prompt=False):
     if n_prompt and name in ("F16", "F32"):
         off, on, _ = prompt_pair(p, n_prompt)
         print_pair(name, n_prompt, p, off, on)
+    elif n_prompt and name == "BF16":
+        fb = b.prefill_bf16_fallback_tiles()
+        off, on, runs = prompt_pair(p, n_prompt, setter=b.set_prefill_bf16, types=(30,))
+        print_pair(name, n_prompt, p, off, on)
+        print("prompt BF16  %d matrix-core launches while on, %d of their workgroups took the two-rounding VALU step" % (runs, b.prefill_bf16_fallback_tiles() - fb), flush=True)
     elif n_prompt:
         r, aux = prompt_rate(p, n_prompt, reps=5)
         print("prompt %-5s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n_prompt, statistics.median(r), min(r), max(r),
