@@ -16,6 +16,7 @@ _lib = None
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
 Q2_K, Q3_K = 10, 11
 IQ4_NL = 20
+IQ4_XS = 23
 
 
 class BamdError(RuntimeError):

@@ -174,12 +174,7 @@ template <int TYPE> __device__ __forceinline__ void load_rec(RecB32<TYPE> & R, b
 // low nibbles = elements 0-15, high = 16-31); Q5_0 (nibble | bit 4) - 16 = (x + 0x70) ^ 0x80 (ggml-quants.c:4655-4658: a clear qh bit ORs 0xF0 into the nibble).  No
 // inter-byte carry.  With a minimum: unsigned and without an offset (ggml-quants.c:4364, :5021-5024).  IQ4_NL: kvalues_iq4nl[nibble] (_mm_shuffle_epi8, :11656-11659) as
 // byte permutes of the table in registers: its halves 0-7 and 8-15 selected by the nibble's low three bits, then of each byte pair the half its bit 3 names
-// kvalues_iq4nl[nibble] for the four nibbles of a dword (one per byte), as int8: the ONLY place the table stands (the matrix-core kernel, bamd_prefill2_b32.hip, calls it too)
-__device__ __forceinline__ uint32_t b32_iq4nl_values(uint32_t nib) {     // {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}, four to a dword
-    const uint32_t sel = nib & 0x07070707u;
-    const uint32_t lo = __builtin_amdgcn_perm(0xf6eaddcfu, 0xbfad9881u, sel), hi = __builtin_amdgcn_perm(0x71594535u, 0x26190d01u, sel);
-    return __builtin_amdgcn_perm(hi, lo, ((nib >> 1) & 0x04040404u) | 0x03020100u);
-}
+// (b32_iq4nl_values: bamd_device.h, where the table stands, beside its by-index spelling iq4nl_value; IQ4_XS and the matrix-core kernel, bamd_prefill2_b32.hip, call it too)
 template <int TYPE> __device__ __forceinline__ uint32_t b32_weights(const RecB32<TYPE> & R, int c, int e) {
     const uint32_t raw = c < 4 ? BAMD_B32_COMP(R.q0, c) : BAMD_B32_COMP(R.q1, c - 4);
     if (TYPE == BAMD_Q8_0) return raw;

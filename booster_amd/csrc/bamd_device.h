@@ -544,6 +544,7 @@ struct RecQ5K { uint4 qs, hd; uint32_t qh, mn47; };
 struct RecQ6K { uint4 ql; uint2 qh, sc; uint32_t d; };
 struct RecQ3K { uint2 qs; uint32_t hm, sc0, sc1, sc2, d; }; // sc0..2: the file's 12 packed scale bytes of the row
 struct RecQ2K { uint2 qs; uint4 sc; uint32_t dd; };          // sc: scales[16] (low nibble scale, high nibble min); dd = d | dmin << 16
+struct RecIQ4XS { uint4 q0, q1; uint2 hd; };                 // q0 / q1: the nibble dwords of 32-blocks 0-3 / 4-7 (shared by lanes e and e + 4); hd.x = d | scales_h << 16, hd.y = scales_l[4]
 
 // Pin a loaded register at its point of use: without this, LLVM folds the first ALU op on a ring register into
 // the loop PHI (i.e. executes it right after the load, one iteration early), which forces s_waitcnt vmcnt(0) at
@@ -561,6 +562,7 @@ __device__ __forceinline__ void pin_rec(RecQ5K & R) { pin(R.qs); pin(R.hd); pin(
 __device__ __forceinline__ void pin_rec(RecQ6K & R) { pin(R.ql); pin(R.qh); pin(R.sc); pin(R.d); }
 __device__ __forceinline__ void pin_rec(RecQ3K & R) { pin(R.qs); pin(R.hm); pin(R.sc0); pin(R.sc1); pin(R.sc2); pin(R.d); }
 __device__ __forceinline__ void pin_rec(RecQ2K & R) { pin(R.qs); pin(R.sc); pin(R.dd); }
+__device__ __forceinline__ void pin_rec(RecIQ4XS & R) { pin(R.q0); pin(R.q1); pin(R.hd); }
 
 // Weight records are fetched with BUFFER loads: the matrix is one 128-bit resource descriptor in scalar registers, the record a scalar
 // byte offset (soffset), the lane's share a constant 32-bit vector offset + an immediate — no vector instruction computes an address
@@ -644,6 +646,11 @@ __device__ __forceinline__ void load_rec(RecQ2K & R, bamd_rsrc rs, int soff, int
     R.sc = bl128(rs, 512u + (l >> 3) * 16u, soff);
     R.dd = bl32(rs, 640u + (l >> 3) * 4u, soff);
 }
+__device__ __forceinline__ void load_rec(RecIQ4XS & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane, vo = ((l >> 3) * 4u + (l & 3u)) * 32u;       // lanes e and e + 4 share the nibble bytes (the Q4_0 record's geometry)
+    R.q0 = bl128(rs, vo, soff); R.q1 = bl128(rs, vo + 16u, soff);
+    R.hd = bl64(rs, 1024u + (l >> 3) * 8u, soff);
+}
 // load_rec request by request: a record takes RecLoads<REC>::value requests and load_rec_part<P> is request P of them, in load_rec's order (the staged
 // ring fill of the mode-A prologues deals single requests over ActPro's stage points).  Keep the two in step
 template <typename REC> struct RecLoads;
@@ -652,6 +659,7 @@ template <> struct RecLoads<RecQ5K> { static constexpr int value = BAMD_XSCALES 
 template <> struct RecLoads<RecQ6K> { static constexpr int value = 4; };
 template <> struct RecLoads<RecQ3K> { static constexpr int value = 6; };
 template <> struct RecLoads<RecQ2K> { static constexpr int value = 3; };
+template <> struct RecLoads<RecIQ4XS> { static constexpr int value = 3; };
 template <int P> __device__ __forceinline__ void load_rec_part(RecQ4K & R, bamd_rsrc rs, int soff, int lane) {
     const uint32_t l = (uint32_t) lane;
     if (P == 0) R.qs = bl128(rs, l * 16u, soff);
@@ -694,6 +702,12 @@ template <int P> __device__ __forceinline__ void load_rec_part(RecQ2K & R, bamd_
     if (P == 0) R.qs = bl64(rs, l * 8u, soff);
     if (P == 1) R.sc = bl128(rs, 512u + (l >> 3) * 16u, soff);
     if (P == 2) R.dd = bl32(rs, 640u + (l >> 3) * 4u, soff);
+}
+template <int P> __device__ __forceinline__ void load_rec_part(RecIQ4XS & R, bamd_rsrc rs, int soff, int lane) {
+    const uint32_t l = (uint32_t) lane, vo = ((l >> 3) * 4u + (l & 3u)) * 32u;
+    if (P == 0) R.q0 = bl128(rs, vo, soff);
+    if (P == 1) R.q1 = bl128(rs, vo + 16u, soff);
+    if (P == 2) R.hd = bl64(rs, 1024u + (l >> 3) * 8u, soff);
 }
 // 6-bit scale/min unpack, ggml-quants.c:6928-6933
 __device__ __forceinline__ void unpack_k4(const uint4 & hd, uint32_t & sc03, uint32_t & sc47, uint32_t & mn03, uint32_t & mn47) {
@@ -854,6 +868,54 @@ __device__ __forceinline__ Terms block_terms(const RecQ2K & R, int ci, int lane,
     return T;
 }
 
+// kvalues_iq4nl[nibble] (ggml-quants.c:3548; _mm_shuffle_epi8 in the reference's dots) for the four nibbles of a dword (one per byte), as int8, by byte permutes
+// of the table in registers: its halves 0-7 and 8-15 selected by the nibble's low three bits, then of each byte pair the half its bit 3 names.  The table stands HERE
+// and nowhere else, in two spellings side by side: four 32-bit permute operands (this function: IQ4_NL — bamd_b32_device.h, bamd_prefill2_b32.hip — and IQ4_XS below)
+// and the same sixteen bytes as two 64-bit constants (iq4nl_value: the embedding rows of both types)
+__device__ __forceinline__ uint32_t b32_iq4nl_values(uint32_t nib) {     // {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113}, four to a dword
+    const uint32_t sel = nib & 0x07070707u;
+    const uint32_t lo = __builtin_amdgcn_perm(0xf6eaddcfu, 0xbfad9881u, sel), hi = __builtin_amdgcn_perm(0x71594535u, 0x26190d01u, sel);
+    return __builtin_amdgcn_perm(hi, lo, ((nib >> 1) & 0x04040404u) | 0x03020100u);
+}
+// one value by index (the embedding rows): the same two halves as 64-bit constants, a byte per entry
+__device__ __forceinline__ int iq4nl_value(int nib) { return (int) (int8_t) ((nib < 8 ? 0xf6eaddcfbfad9881ull : 0x7159453526190d01ull) >> ((nib & 7) * 8)); }
+// IQ4_XS (ggml_vec_dot_iq4_xs_q8_K, AVX2 branch, ggml-quants.c:11855-11890).  SIMD lane e of sumi1 + sumi2 sums, over the eight 32-blocks ib, (ls_ib - 32) x the
+// 4-byte product sum of the table values of weights 32 ib + 4 e .. + 3 with the Q8_K bytes at the same positions: lanes 0-3 the low nibbles of qs[16 ib + 4 e ..],
+// lanes 4-7 the high nibbles of qs[16 ib + 4 (e - 4) ..] (:11872-11875) — Q4_0's geometry, activation chunk c = ib.
+// The product sum is mul_add_epi8 (:10958-10962) = maddubs(sign(x, x), sign(y, x)): the activation byte y is negated where the table value x is negative, and
+// -(-128) wraps to -128, so against an activation byte of -128 a negative value w would contribute w x 128 and not w x (-128).  That byte does not exist here:
+// quantize_row_q8_K scales by -127 / max (:3613-3618: the -128 form is commented out there) and so does ActPro::quantize_batch above, every Q8_K byte lies in
+// -127 .. 127, and on those mul_add_epi8 is the plain signed dot.  (tests/iq4xs_ref.py restates the wrap and holds it to the reference on hand-made Q8_K blocks
+// that do hold -128; a quantiser that ever stores that byte needs the correction dot4(w, a) + 256 * sum of w over the bytes with a == -128 and w < 0 HERE.)
+// Pair sums stay below 2 * 127 * 127 (no int16 saturation in maddubs), |sum| <= 8 * 4 * 127 * 127 * 32 < 2^24: exact integers in any order, exact as a float.
+// the eight scales ls - 32 of the row as int8, four to a dword (blocks 0-3, 4-7): low nibbles out of scales_l, bits 4-5 out of scales_h (bit pair ib of the half to
+// bit 8 ib + 4: four shifted copies ORed — v_lshl_or_b32; not a multiply, whose overlapping copies would carry — and the mask keeps each pair where it belongs), then - 32 per byte without a carry
+__device__ __forceinline__ void iq4xs_scales(const uint2 & hd, uint32_t & s0, uint32_t & s1) {
+    const uint32_t lo = hd.y & 0x0f0f0f0fu, hi = (hd.y >> 4) & 0x0f0f0f0fu, sh = hd.x >> 16;
+    const uint32_t g0 = sh & 0xffu, g1 = sh >> 8;
+    const uint32_t h0 = ((g0 << 4) | (g0 << 10) | (g0 << 16) | (g0 << 22)) & 0x30303030u, h1 = ((g1 << 4) | (g1 << 10) | (g1 << 16) | (g1 << 22)) & 0x30303030u;
+    s0 = __builtin_amdgcn_perm(hi, lo, 0x05010400u) | h0; s1 = __builtin_amdgcn_perm(hi, lo, 0x07030602u) | h1;
+    s0 = (s0 + 0x60606060u) ^ 0x80808080u; s1 = (s1 + 0x60606060u) ^ 0x80808080u;
+}
+#define BAMD_IQ4XS_WQ(wq, R, sh) do { \
+        wq[0] = b32_iq4nl_values(((R).q0.x >> (sh)) & 0x0f0f0f0fu); wq[1] = b32_iq4nl_values(((R).q0.y >> (sh)) & 0x0f0f0f0fu); \
+        wq[2] = b32_iq4nl_values(((R).q0.z >> (sh)) & 0x0f0f0f0fu); wq[3] = b32_iq4nl_values(((R).q0.w >> (sh)) & 0x0f0f0f0fu); \
+        wq[4] = b32_iq4nl_values(((R).q1.x >> (sh)) & 0x0f0f0f0fu); wq[5] = b32_iq4nl_values(((R).q1.y >> (sh)) & 0x0f0f0f0fu); \
+        wq[6] = b32_iq4nl_values(((R).q1.z >> (sh)) & 0x0f0f0f0fu); wq[7] = b32_iq4nl_values(((R).q1.w >> (sh)) & 0x0f0f0f0fu); } while (0)
+__device__ __forceinline__ Terms block_terms(const RecIQ4XS & R, int ci, int lane, const uint32_t * q8, const int * S, const float * yd) {
+    (void) S;
+    const int e = lane & 7;
+    Terms T;
+    T.d = yd[ci] * h2f(R.hd.x & 0xffffu);
+    T.dmin = 0.f; T.pm = 0.f;
+    const uint4 a0 = *(const uint4 *) (q8 + ci * 64 + e * 8), a1 = *(const uint4 *) (q8 + ci * 64 + e * 8 + 4);
+    uint32_t s0, s1; iq4xs_scales(R.hd, s0, s1);
+    uint32_t wq[8]; const int sh = (e >> 2) * 4; BAMD_IQ4XS_WQ(wq, R, sh);
+    const uint32_t aq[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+    T.fs = (float) dotscale8<true>(wq, aq, s0, s1);
+    return T;
+}
+
 // ---- block_terms in two halves: what depends on the weight record only (PreTerms, computed while a co-launched workgroup waits for its
 //      activations: bamd_colaunch.hip) and the rest.  Same operations on the same values as block_terms above, in the same order per result.
 template <int TYPE> struct PreTerms;
@@ -974,6 +1036,24 @@ template <> struct PreTerms<BAMD_Q2_K> {
     }
 };
 
+template <> struct PreTerms<BAMD_IQ4_XS> {
+    uint32_t wq[8], s0, s1; float dh;
+    __device__ __forceinline__ void prep(const RecIQ4XS & R, int lane) {
+        dh = h2f(R.hd.x & 0xffffu); iq4xs_scales(R.hd, s0, s1);
+        const int sh = ((lane & 7) >> 2) * 4; BAMD_IQ4XS_WQ(wq, R, sh);
+    }
+    __device__ __forceinline__ Terms finish(int ci, int lane, const uint32_t * q8, const int * S, const float * yd) const {
+        (void) S;
+        const int e = lane & 7;
+        Terms T;
+        T.d = yd[ci] * dh; T.dmin = 0.f; T.pm = 0.f;
+        const uint4 a0 = *(const uint4 *) (q8 + ci * 64 + e * 8), a1 = *(const uint4 *) (q8 + ci * 64 + e * 8 + 4);
+        const uint32_t aq[8] = { a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w };
+        T.fs = (float) dotscale8<true>(wq, aq, s0, s1);
+        return T;
+    }
+};
+
 // one step of the reference's per-lane f32 chains (the ONLY place their order is defined)
 template <int TYPE>
 __device__ __forceinline__ void chain_step(RowAcc & A, float d, float fs, float dmin, float pm) {
@@ -998,7 +1078,7 @@ __device__ __forceinline__ float finish_row(const RowAcc & A) {
         return v + m;
     }
     if (TYPE == BAMD_Q5_K) return v + A.accm;
-    return v;                                                                  // Q6_K, Q3_K, Q2_K: one chain
+    return v;                                                                  // Q6_K, Q3_K, Q2_K, IQ4_XS: one chain
 }
 
 // ggml_v_expf (AVX2), one lane — ggml.c:2490-2522
@@ -1075,7 +1155,7 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
             ik_st(x + i, (float) q * d);
         }
     } else if (embd_type == BAMD_IQ4_NL) {
-        // dequantize_row_iq4_nl (ggml-quants.c:3550-3566): y = d * kvalues_iq4nl[nibble], one f32 product; the table (:3548) as two 64-bit constants, a byte per entry
+        // dequantize_row_iq4_nl (ggml-quants.c:3550-3566): y = d * kvalues_iq4nl[nibble], one f32 product
         const uint8_t * row = embd + (size_t) tok * (E >> 5) * 18;
         for (int i = threadIdx.x; i < E; i += blockDim.x) {
             const uint8_t * b = row + (size_t) (i >> 5) * 18;
@@ -1083,7 +1163,7 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
             const float d = h2f(*(const unsigned short *) b);
             const uint8_t v = b[2 + (n & 15)];
             const int nib = n < 16 ? (v & 0xF) : (v >> 4);
-            const int q = (int) (int8_t) ((nib < 8 ? 0xf6eaddcfbfad9881ull : 0x7159453526190d01ull) >> ((nib & 7) * 8));
+            const int q = iq4nl_value(nib);
             ik_st(x + i, d * (float) q);
         }
     } else if (bamd_is_q1(embd_type)) {
@@ -1146,6 +1226,16 @@ __device__ __forceinline__ void embed_row(const uint8_t * embd, int embd_type, i
                 const int q = (int) (int8_t) ((b[16 + 32 * half + l] >> (2 * j)) & 3);
                 const float t = dl * (float) q;
                 y = t - ml;
+            } else if (embd_type == BAMD_IQ4_XS) {              // dequantize_row_iq4_xs (ggml-quants.c:3568-3589): dl = d * (ls - 32), rounded; y = dl * value: TWO f32 products
+                const float d = h2f(*(const unsigned short *) b);
+                const uint32_t sh = *(const unsigned short *) (b + 2);
+                const int ib = n >> 5, l = n & 31;
+                const int ls = (int) (((b[4 + (ib >> 1)] >> (4 * (ib & 1))) & 0xF) | (((sh >> (2 * ib)) & 3u) << 4));
+                const uint8_t v = b[8 + 16 * ib + (l & 15)];
+                const int nib = l < 16 ? (v & 0xF) : (v >> 4);
+                const int q = iq4nl_value(nib);
+                const float dl = d * (float) (ls - 32);
+                y = dl * (float) q;
             } else {
                 const float d = h2f(*(const unsigned short *) (b + 208));
                 const int half = n >> 7, nn = n & 127, cc = nn >> 5, l = nn & 31;

@@ -199,7 +199,7 @@ static int upload_mat(bamd_model * m, const GgufTensor * t, DevMat & d, bool kee
                       void * stream_dst = nullptr) {
     if (t->ne.size() != 2) return fail("tensor " + t->name + ": expected 2 dims");
     d.type = t->type; d.K = (int) t->ne[0]; d.nrows = (int) t->ne[1]; d.bytes = t->nbytes;
-    if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL)");
+    if (!bamd_has_record(d.type)) return fail("tensor " + t->name + ": type " + std::to_string(d.type) + " not supported (F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL, IQ4_XS)");
     if (bamd_has_record(d.type) && d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
     if (want_stream) {
         if (d.K % 256) return fail("tensor " + t->name + ": row length not a multiple of 256");
@@ -236,7 +236,9 @@ static int upload_f32(bamd_model * m, const GgufTensor * t, float ** p, int n, h
 static void build_prefill_aux(bamd_model * m, hipStream_t s);
 // The ONE attn_q | attn_k | attn_v whose matrices need two activation forms and that loads: the pair llama.cpp's IQ4_NL recipe writes.  llama_tensor_get_type
 // (src/llama.cpp:15544-15546) makes attn_v Q5_K wherever n_gqa >= 4 (Llama-3, Mistral, the 8B shape) while attn_q and attn_k stay IQ4_NL: Q8_0 activations
-// for the first two, Q8_K for the third.  The engine runs such a layer's QKV as one launch per form (qkv_groups); every other mix stays refused at load
+// for the first two, Q8_K for the third.  The engine runs such a layer's QKV as one launch per form (qkv_groups); every other mix stays refused at load.
+// (bamd_is_kquant holds IQ4_XS too, so an IQ4_XS attn_v beside IQ4_NL attn_q / attn_k passes here as well: no recipe writes it and no test covers it; it takes the
+// same two launches, the second on the generic Q8_K kernel)
 static bool qkv_recipe_mix(int tq, int tk, int tv) { return tq == BAMD_IQ4_NL && tk == BAMD_IQ4_NL && bamd_is_kquant(tv); }
 static int model_load_impl(bamd_model * m, const char * path, int device, int lf, int ll, int with_embd, int with_output) {
     // the file is read and its header validated before any device is touched: a bad file is reported as such on any machine

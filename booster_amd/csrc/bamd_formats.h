@@ -16,7 +16,10 @@
 //   Q4_1  20 B = {f16 d, f16 m, u8 qs[16]}             nibbles as Q4_0; value = nibble * d + m
 //   Q5_1  24 B = {f16 d, f16 m, u8 qh[4], u8 qs[16]}   nibbles and qh as Q5_0; value = (5 bits) * d + m
 // and IQ4_NL (ggml-common.h block_iq4_nl), byte for byte the geometry of Q4_0, its nibble an index into a table of 16 signed values; Q8_0 activations:
-//   IQ4_NL 18 B = {f16 d, u8 qs[16]}            nibbles as Q4_0; value = kvalues_iq4nl[nibble] * d, the table -127 .. 113 (ggml-quants.c:3548; here b32_weights, bamd_b32_device.h)
+//   IQ4_NL 18 B = {f16 d, u8 qs[16]}            nibbles as Q4_0; value = kvalues_iq4nl[nibble] * d, the table -127 .. 113 (ggml-quants.c:3548; here b32_iq4nl_values and, by index, iq4nl_value: bamd_device.h)
+// and IQ4_XS (ggml-common.h:393-398), the same table under K-quant clothes: a 256-weight super-block of eight 32-blocks with 6-bit scales, Q8_K activations:
+//   IQ4_XS 136 B = {f16 d, u16 scales_h, u8 scales_l[4], u8 qs[128]}   32-block ib: ls = (scales_l[ib/2] >> 4*(ib%2) & 0xf) | (scales_h >> 2*ib & 3) << 4, used as ls - 32;
+//                                               qs[16 ib + j]: low nibble = weight 32 ib + j, high nibble = weight 32 ib + 16 + j (each 32-block a Q4_0 / IQ4_NL block)
 //
 // Wave-stream layout (our design; the GGUF file itself is untouched).  A matrix [nrows][K] is cut into
 // row-groups of 8 rows; for each row-group the K/256 super-blocks follow one another as RECORDS, and a record
@@ -53,6 +56,8 @@
 //   F16  record 4096 B: the same ownership, request q = 0..3 holds i = 8q .. 8q+7 (eight halves)
 //   BF16 record 4096 B: a row has 32 chain lanes c = 8a + j (accumulator a = 0..3, lane j of ggml_vec_dot_bf16's AVX2 branch, ggml.c:2007-2026), chain lane c owns
 //                       w[r][32i + c], i = 0..7: request q = 0..3 holds rows 2q (wave lanes 0-31) and 2q + 1 (lanes 32-63), eight bf16 per lane
+//   IQ4_XS record 1088 B: [qs  : (r*4 + (e&3))*32 -> 8 dwords c=0..7 = file qs[16c + 4(e&3) .. +3]: the Q4_0 geometry, lanes e and e+4 read the SAME 32 bytes ] 1024 B
+//                       [hdr  : r*8     -> file bytes 0..7 (d, scales_h, scales_l[4]): one 8-byte load per lane        ]   64 B
 //   (Q3_K / Q2_K: 3.4375 / 2.625 bits per weight leave a lane 8 B of qs per super-block, so its widest load is 8 bytes; records are 16-byte multiples)
 //
 // Record bytes = 8 x file block bytes, so HBM traffic per weight is exactly the GGUF's bits per weight, every
@@ -69,7 +74,7 @@
 #define BAMD_HD
 #endif
 
-enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_BF16 = 30, BAMD_Q4_0 = 2, BAMD_Q4_1 = 3, BAMD_Q5_0 = 6, BAMD_Q5_1 = 7, BAMD_Q8_0 = 8, BAMD_Q2_K = 10, BAMD_Q3_K = 11, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14, BAMD_IQ4_NL = 20 };
+enum bamd_type { BAMD_F32 = 0, BAMD_F16 = 1, BAMD_BF16 = 30, BAMD_Q4_0 = 2, BAMD_Q4_1 = 3, BAMD_Q5_0 = 6, BAMD_Q5_1 = 7, BAMD_Q8_0 = 8, BAMD_Q2_K = 10, BAMD_Q3_K = 11, BAMD_Q4_K = 12, BAMD_Q5_K = 13, BAMD_Q6_K = 14, BAMD_IQ4_NL = 20, BAMD_IQ4_XS = 23 };
 
 BAMD_HD static inline int bamd_is_q0(int t) { return t == BAMD_Q8_0 || t == BAMD_Q4_0 || t == BAMD_Q5_0; }       // 32-weight blocks, Q8_0 activations
 // the same family by record geometry and activation form, IQ4_NL included: what everything but the matrix-core prompt kernels and split-K asks (those two have
@@ -82,7 +87,7 @@ BAMD_HD static inline int bamd_is_flt(int t) { return t == BAMD_F32 || t == BAMD
 enum bamd_act_form { BAMD_ACT_NONE = 0, BAMD_ACT_Q8_K = 1, BAMD_ACT_Q8_0 = 2, BAMD_ACT_Q8_1 = 3, BAMD_ACT_F32 = 4, BAMD_ACT_BF16 = 5 };
 // (the load-time repack kernel asks the first of the two: IQ4_NL reaches it as Q4_0, bamd_launch_repack)
 BAMD_HD static inline int bamd_block_bytes_repack(int t) {
-    return t == BAMD_Q4_1 ? 20 : t == BAMD_Q5_1 ? 24 : t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : t == BAMD_Q3_K ? 110 : t == BAMD_Q2_K ? 84 : t == BAMD_Q8_0 ? 34 : t == BAMD_Q4_0 ? 18 : t == BAMD_Q5_0 ? 22 : 0;
+    return t == BAMD_Q4_1 ? 20 : t == BAMD_Q5_1 ? 24 : t == BAMD_Q4_K ? 144 : t == BAMD_Q5_K ? 176 : t == BAMD_Q6_K ? 210 : t == BAMD_Q3_K ? 110 : t == BAMD_Q2_K ? 84 : t == BAMD_IQ4_XS ? 136 : t == BAMD_Q8_0 ? 34 : t == BAMD_Q4_0 ? 18 : t == BAMD_Q5_0 ? 22 : 0;
 }
 BAMD_HD static inline int bamd_block_bytes(int t) { return t == BAMD_IQ4_NL ? 18 : bamd_block_bytes_repack(t); }
 BAMD_HD static inline int bamd_block_weights(int t) { return bamd_takes_q8_0(t) || bamd_is_q1(t) ? 32 : BAMD_QK_K; }
@@ -97,6 +102,7 @@ BAMD_HD static inline int bamd_block_weights(int t) { return bamd_takes_q8_0(t) 
 #define BAMD_RECB_Q6K 1680
 #define BAMD_RECB_Q3K 880
 #define BAMD_RECB_Q2K 672
+#define BAMD_RECB_IQ4XS 1088
 #define BAMD_RECB_Q80 2176
 #define BAMD_RECB_Q40 1152
 #define BAMD_RECB_Q50 1408
@@ -106,13 +112,15 @@ BAMD_HD static inline int bamd_block_weights(int t) { return bamd_takes_q8_0(t) 
 #define BAMD_RECB_F16 4096
 #define BAMD_RECB_BF16 4096
 // record bytes as a constant expression of a kernel's TYPE template argument; a type without a record does not compile
-#define BAMD_RECB_OF(T_) ((T_) == BAMD_Q4_K ? BAMD_RECB_Q4K : (T_) == BAMD_Q5_K ? BAMD_RECB_Q5K : (T_) == BAMD_Q6_K ? BAMD_RECB_Q6K : (T_) == BAMD_Q3_K ? BAMD_RECB_Q3K : (T_) == BAMD_Q2_K ? BAMD_RECB_Q2K : (T_) == BAMD_Q8_0 ? BAMD_RECB_Q80 : (T_) == BAMD_Q4_0 ? BAMD_RECB_Q40 : (T_) == BAMD_Q5_0 ? BAMD_RECB_Q50 : (T_) == BAMD_Q4_1 ? BAMD_RECB_Q41 : (T_) == BAMD_Q5_1 ? BAMD_RECB_Q51 : (T_) == BAMD_IQ4_NL ? BAMD_RECB_Q40 : -1)
-BAMD_HD static inline int bamd_record_bytes_quant(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? BAMD_RECB_Q6K : t == BAMD_Q3_K ? BAMD_RECB_Q3K : t == BAMD_Q2_K ? BAMD_RECB_Q2K : t == BAMD_Q8_0 ? BAMD_RECB_Q80 : t == BAMD_Q4_0 ? BAMD_RECB_Q40 : t == BAMD_Q5_0 ? BAMD_RECB_Q50 : t == BAMD_Q4_1 ? BAMD_RECB_Q41 : t == BAMD_Q5_1 ? BAMD_RECB_Q51 : 0; }   // the quantised types only (what the load-time repack of bamd_matvec.hip asks)
+#define BAMD_RECB_OF(T_) ((T_) == BAMD_Q4_K ? BAMD_RECB_Q4K : (T_) == BAMD_Q5_K ? BAMD_RECB_Q5K : (T_) == BAMD_Q6_K ? BAMD_RECB_Q6K : (T_) == BAMD_Q3_K ? BAMD_RECB_Q3K : (T_) == BAMD_Q2_K ? BAMD_RECB_Q2K : (T_) == BAMD_IQ4_XS ? BAMD_RECB_IQ4XS : (T_) == BAMD_Q8_0 ? BAMD_RECB_Q80 : (T_) == BAMD_Q4_0 ? BAMD_RECB_Q40 : (T_) == BAMD_Q5_0 ? BAMD_RECB_Q50 : (T_) == BAMD_Q4_1 ? BAMD_RECB_Q41 : (T_) == BAMD_Q5_1 ? BAMD_RECB_Q51 : (T_) == BAMD_IQ4_NL ? BAMD_RECB_Q40 : -1)
+BAMD_HD static inline int bamd_record_bytes_quant(int t) { return t == BAMD_Q4_K ? BAMD_RECB_Q4K : t == BAMD_Q5_K ? BAMD_RECB_Q5K : t == BAMD_Q6_K ? BAMD_RECB_Q6K : t == BAMD_Q3_K ? BAMD_RECB_Q3K : t == BAMD_Q2_K ? BAMD_RECB_Q2K : t == BAMD_IQ4_XS ? BAMD_RECB_IQ4XS : t == BAMD_Q8_0 ? BAMD_RECB_Q80 : t == BAMD_Q4_0 ? BAMD_RECB_Q40 : t == BAMD_Q5_0 ? BAMD_RECB_Q50 : t == BAMD_Q4_1 ? BAMD_RECB_Q41 : t == BAMD_Q5_1 ? BAMD_RECB_Q51 : 0; }   // the quantised types only (what the load-time repack of bamd_matvec.hip asks)
 BAMD_HD static inline int bamd_record_bytes_repack(int t) { return t == BAMD_F32 ? BAMD_RECB_F32 : t == BAMD_F16 ? BAMD_RECB_F16 : t == BAMD_BF16 ? BAMD_RECB_BF16 : bamd_record_bytes_quant(t); }   // (what the repack of bamd_matvec_flt.hip asks)
 BAMD_HD static inline int bamd_record_bytes(int t) { return t == BAMD_IQ4_NL ? BAMD_RECB_Q40 : bamd_record_bytes_repack(t); }   // wave-stream record: 8 rows x 256 weights
 // bytes of the wave-stream copy of a quantised matrix [nrows_pad (multiple of 8)][K]
 BAMD_HD static inline size_t bamd_stream_bytes(int t, int64_t k, int64_t nrows_pad) { return (size_t) (nrows_pad / 8) * (size_t) (k / BAMD_QK_K) * (size_t) bamd_record_bytes(t); }
-BAMD_HD static inline int bamd_is_kquant(int t) { return t == BAMD_Q4_K || t == BAMD_Q5_K || t == BAMD_Q6_K || t == BAMD_Q3_K || t == BAMD_Q2_K; }
+// the 256-weight super-block types with Q8_K activations; IQ4_XS is one of them by record, activation form and chain (it has no dmin, no side table and no
+// matrix-core prompt kernel: whoever means one of those asks for the type, bamd_prefill_family.h)
+BAMD_HD static inline int bamd_is_kquant(int t) { return t == BAMD_Q4_K || t == BAMD_Q5_K || t == BAMD_Q6_K || t == BAMD_Q3_K || t == BAMD_Q2_K || t == BAMD_IQ4_XS; }
 BAMD_HD static inline size_t bamd_row_bytes(int t, int64_t k) {
     return t == BAMD_F32 ? (size_t) k * 4 : t == BAMD_F16 || t == BAMD_BF16 ? (size_t) k * 2 : (size_t) (k / bamd_block_weights(t)) * bamd_block_bytes(t);
 }

@@ -49,6 +49,12 @@ __global__ void repack_kernel(const uint8_t * __restrict__ raw, uint8_t * __rest
             for (int t = 0; t < 16; ++t) rec[512 + r * 16 + t] = src[t];
             for (int t = 0; t < 4; ++t) rec[640 + r * 4 + t] = src[80 + t];
         }
+    } else if (type == BAMD_IQ4_XS) {
+        // the eight 32-blocks' nibble bytes in the Q4_0 record's geometry (row r, quarter l: eight dwords c = 0..7), then the block's first eight bytes as they are
+        for (int c = 0; c < 8; ++c)
+            for (int l = 0; l < 4; ++l)
+                for (int t = 0; t < 4; ++t) rec[(r * 4 + l) * 32 + c * 4 + t] = src[8 + 16 * c + 4 * l + t];
+        for (int t = 0; t < 8; ++t) rec[1024 + r * 8 + t] = src[t];
     } else if (type == BAMD_Q6_K) {
         const uint8_t * ql = src, * qh = src + 128, * sc = src + 192;
         for (int e = 0; e < 8; ++e) {
@@ -172,6 +178,7 @@ __global__ void __launch_bounds__(512) matvec_kernel(bamd_mv_args a) {
             else if (t == BAMD_Q6_K) stream_dispatch_depth<BAMD_Q6_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
             else if (t == BAMD_Q3_K) stream_dispatch_depth<BAMD_Q3_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
             else if (t == BAMD_Q2_K) stream_dispatch_depth<BAMD_Q2_K, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
+            else if (t == BAMD_IQ4_XS) stream_dispatch_depth<BAMD_IQ4_XS, EPI, PRO>(wA, wB, nb, g0 - off, count, stride, out, res, pa, !pro_done, best, nv);
             else __builtin_trap();                           // unreachable: bamd_launch_matvec refuses any other type on the host; never a silent read as another format
             pro_done = true;
         }
@@ -243,6 +250,7 @@ __global__ void __launch_bounds__(512) matvec_split_kernel(bamd_mv_args a) {
             else if (t == BAMD_Q6_K) split_dispatch<BAMD_Q6_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
             else if (t == BAMD_Q3_K) split_dispatch<BAMD_Q3_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
             else if (t == BAMD_Q2_K) split_dispatch<BAMD_Q2_K, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
+            else if (t == BAMD_IQ4_XS) split_dispatch<BAMD_IQ4_XS, EPI, PRO>(w, nb, g0 - off, count, stride, a.seg[s].out, a.res, pa, !pro_done, part0, rgctr, nv);
             else __builtin_trap();
             pro_done = true;
         }

@@ -11,6 +11,7 @@ template <> struct RecOf<BAMD_Q5_K> { typedef RecQ5K type; };
 template <> struct RecOf<BAMD_Q6_K> { typedef RecQ6K type; };
 template <> struct RecOf<BAMD_Q3_K> { typedef RecQ3K type; };
 template <> struct RecOf<BAMD_Q2_K> { typedef RecQ2K type; };
+template <> struct RecOf<BAMD_IQ4_XS> { typedef RecIQ4XS type; };
 
 // The fields a launch needs for its FIRST requests travel as leading scalar kernel parameters: with -amdgpu-kernarg-preload-count the
 // hardware places them in SGPRs at wave launch (gfx950 kernarg preload), so the activation and ring requests do not wait for an s_load of

@@ -20,8 +20,8 @@ template <int A, int B> struct cpair { static constexpr int a = A, b = B; };
 template <typename... PS> struct pairs {};
 template <int... VS, typename F> inline bool with_const(consts<VS...>, int v, F && f) { return (... || (v == VS && f(std::integral_constant<int, VS>()))); }
 template <typename... PS, typename F> inline bool with_pair(pairs<PS...>, int x, int y, F && f) { return (... || (x == PS::a && y == PS::b && f(PS()))); }
-typedef consts<BAMD_Q4_K, BAMD_Q5_K, BAMD_Q6_K, BAMD_Q3_K, BAMD_Q2_K> kquants_all;
-typedef consts<BAMD_Q4_K, BAMD_Q5_K, BAMD_Q6_K> kquants_456;       // the families the low-bit types have no instance of
+typedef consts<BAMD_Q4_K, BAMD_Q5_K, BAMD_Q6_K, BAMD_Q3_K, BAMD_Q2_K, BAMD_IQ4_XS> kquants_all;      // (new types at the END: kernels are laid out in instantiation order)
+typedef consts<BAMD_Q4_K, BAMD_Q5_K, BAMD_Q6_K> kquants_456;       // the families the low-bit types and IQ4_XS have no instance of
 template <typename F> inline bool with_kquant(int type, F && f) { return with_const(kquants_all(), type, f); }
 
 // fast kernels: row-groups per wave slot (mode A) / per workgroup (mode B), quotient and remainder

@@ -144,7 +144,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_mul_mat_batch(int 
     } else if (flt_mfma) {
         if (bamd_launch_matmul_mfma_flt(str, type, nrows, nrows_pad, k, blob, T, dy, dres, dres ? BAMD_EPI_ADD : BAMD_EPI_STORE, nrows, nullptr)) return fail("MFMA path: unsupported type/shape");
     } else if (impl == 2) {                                             // the matrix-core kernel: side table built here, as the engine builds it at model load
-        if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K with the switch off (bamd_prefill_mfma_type): the integer-dot kernel only
+        if (!bamd_prefill_aux_bytes(type, nrows_pad, k)) return fail("MFMA path: unsupported type/shape");      // Q2_K / Q3_K with the switch off (bamd_prefill_mfma_type), IQ4_XS always: the integer-dot kernel only
         void * aux = t.up(nullptr, bamd_prefill_aux_bytes(type, nrows_pad, k));
         if (!aux) return fail("device alloc failed");
         bamd_launch_prefill_aux(str, type, nrows_pad, k, aux, nullptr);
@@ -588,7 +588,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_bench_matvec(int type
         if (type == BAMD_Q6_K) { p[208] = 0x00; p[209] = 0x1c; }
         else if (type == BAMD_Q3_K) { p[108] = 0x00; p[109] = 0x1c; }
         else if (type == BAMD_Q2_K) { p[80] = 0; p[81] = 0x1c; p[82] = 0; p[83] = 0x1c; }
-        else if (bamd_takes_q8_0(type)) { p[0] = 0; p[1] = 0x1c; }
+        else if (bamd_takes_q8_0(type) || type == BAMD_IQ4_XS) { p[0] = 0; p[1] = 0x1c; }      // (IQ4_XS: d alone, scales_h stays random)
         else if (bamd_is_q1(type)) { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
         else { p[0] = 0; p[1] = 0x1c; p[2] = 0; p[3] = 0x1c; }
     }

@@ -88,6 +88,7 @@ template <int TYPE, typename REC> struct KqRow {
     else if (t == BAMD_Q6_K) SEG(D, KqRow<BAMD_Q6_K, RecQ6K>); \
     else if (t == BAMD_Q3_K) SEG(D, KqRow<BAMD_Q3_K, RecQ3K>); \
     else if (t == BAMD_Q2_K) SEG(D, KqRow<BAMD_Q2_K, RecQ2K>); \
+    else if (t == BAMD_IQ4_XS) SEG(D, KqRow<BAMD_IQ4_XS, RecIQ4XS>); \
     else __builtin_trap();                       /* the launcher checks the types: never a silent read as another format */ \
 }
 #define BAMD_KQ_TYPES(SEG) if ((nb & 3) == 0) BAMD_KQ_TYPES_D(SEG, 4) else BAMD_KQ_TYPES_D(SEG, 1)

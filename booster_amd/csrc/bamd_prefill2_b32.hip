@@ -42,7 +42,7 @@
 //   * one output = TWO sets of eight chains, acc[l & 1]_e = fma(f32(d_w) * f32(d_x), (float) dot4_e, acc[l & 1]_e), dot4_e = the dot of kvalues_iq4nl[nibble] with
 //     bytes 4e .. 4e+3 of the activation block, closed by a_e = acc[0]_e + acc[1]_e and b32_finish_row's tree over a_e.  A record is eight consecutive blocks, so
 //     l & 1 = c & 1 with c the block's index in the record: a compile-time index of the unrolled half step, the choice of the set costs no instruction;
-//   * weight operand: the nibble dword through b32_iq4nl_values (bamd_b32_device.h, the one place the table stands), ^ 0x80808080 gives u = value + 128 (1 .. 241),
+//   * weight operand: the nibble dword through b32_iq4nl_values (bamd_device.h, where the table stands), ^ 0x80808080 gives u = value + 128 (1 .. 241),
 //     and (0x6400 | u) - 1152 is the table value, exact in f16 — the Q8_0 constant.  |w| <= 127, |x| <= 127: every four-term sum is an integer <= 64 516 < 2^24;
 //   * tile: two sets at the 16-row x 32-token wave tile would be 128 accumulator registers, the shape recorded above as spilling.  A wave owns 16 rows x ONE token
 //     tile of 16 with all eight e and both parities, 64 registers again, and a workgroup is four waves = 64 rows x 16 tokens: half the stage (8 960 B) and two

@@ -44,6 +44,7 @@ std::string bamd_prefill_reason(int type) {
         return bamd_prefill_family_on(BAMD_PF_FLT) ? "the model holds a BF16 matrix: these have no matrix-core kernel (BAMD_PREFILL_FLT covers F32 / F16 only), and side tables are all-or-nothing per model, so every prompt mat-mul of the other types runs on the VALU kernels"
                                                    : "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels";
     if (type == BAMD_IQ4_NL) return "the model holds an IQ4_NL matrix: these have no matrix-core kernel (BAMD_PREFILL_Q0 covers Q4_0 / Q5_0 / Q8_0 only), and " INT_DOT "; BAMD_PREFILL_NL, the switch of the IQ4_NL matrix-core kernel, is off";
+    if (type == BAMD_IQ4_XS) return "the model holds an IQ4_XS matrix: these have no matrix-core kernel, and " INT_DOT;      // (in no family: no matrix-core kernel is built for the type)
     int own = 0;
     while (own < BAMD_PF_COUNT && !bamd_prefill_type_in(R[own].types, type)) ++own;
     if (own == BAMD_PF_COUNT || !R[own].names || bamd_prefill_family_on(own)) return "a matrix type / shape without a matrix-core kernel";

@@ -27,6 +27,7 @@ GGML_TYPES = {
     13: (256, 176),   # Q5_K
     14: (256, 210),   # Q6_K
     20: (32, 18),     # IQ4_NL
+    23: (256, 136),   # IQ4_XS
     30: (1, 2),       # BF16
 }
 F32, F16, Q4_K, Q5_K, Q6_K = 0, 1, 12, 13, 14
@@ -34,9 +35,11 @@ Q2_K, Q3_K = 10, 11
 Q4_0, Q5_0, Q8_0 = 2, 6, 8
 Q4_1, Q5_1 = 3, 7
 IQ4_NL = 20
+IQ4_XS = 23
 BF16 = 30
 FTYPE_MOSTLY_IQ4_NL = 25      # general.file_type of a file written under iq4_nl_type (LLAMA_FTYPE_MOSTLY_IQ4_NL)
-TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 20: "IQ4_NL", 30: "BF16"}
+FTYPE_MOSTLY_IQ4_XS = 30      # ... under iq4_xs_type (LLAMA_FTYPE_MOSTLY_IQ4_XS)
+TYPE_NAMES = {0: "F32", 1: "F16", 2: "Q4_0", 3: "Q4_1", 6: "Q5_0", 7: "Q5_1", 8: "Q8_0", 10: "Q2_K", 11: "Q3_K", 12: "Q4_K", 13: "Q5_K", 14: "Q6_K", 20: "IQ4_NL", 23: "IQ4_XS", 30: "BF16"}
 
 # gguf KV value types
 T_U8, T_I8, T_U16, T_I16, T_U32, T_I32, T_F32, T_BOOL, T_STR, T_ARR, T_U64, T_I64, T_F64 = range(13)
@@ -207,6 +210,8 @@ def random_kquant_tensor(ttype, row_len, n_rows, rng, amp=1.0):
         return random_q1_tensor(ttype, row_len, n_rows, rng, amp)
     if ttype == IQ4_NL:
         return random_iq4_nl_tensor(row_len, n_rows, rng, amp)
+    if ttype == IQ4_XS:
+        return random_iq4_xs_tensor(row_len, n_rows, rng, amp)
     be, bb = GGML_TYPES[ttype]
     nblk = n_rows * (row_len // be)
     blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
@@ -255,6 +260,19 @@ def random_iq4_nl_tensor(row_len, n_rows, rng, amp=1.0):
     nblk = n_rows * (row_len // be)
     blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
     rms = 67.4                                                   # of the sixteen table values -127 .. 113, drawn uniformly
+    d = (amp / np.sqrt(row_len) / rms) * rng.uniform(0.5, 1.5, size=nblk)
+    blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
+    return blk.reshape(-1)
+
+
+def random_iq4_xs_tensor(row_len, n_rows, rng, amp=1.0):
+    """Random raw IQ4_XS blocks {f16 d, u16 scales_h, u8 scales_l[4], u8 qs[128]} for an [n_rows, row_len] matrix: every nibble pattern in qs, every bit
+    pattern in scales_h / scales_l (so every 6-bit scale ls = 0 .. 63, used as ls - 32), finite positive f16 d sized so that the dequantised values
+    d * (ls - 32) * kvalues_iq4nl[nibble] have standard deviation ~ amp / sqrt(row_len)."""
+    be, bb = GGML_TYPES[IQ4_XS]
+    nblk = n_rows * (row_len // be)
+    blk = rng.integers(0, 256, size=(nblk, bb), dtype=np.uint8)
+    rms = 18.5 * 67.4                                            # of ls - 32 in -32 .. 31 times the sixteen table values, both drawn uniformly
     d = (amp / np.sqrt(row_len) / rms) * rng.uniform(0.5, 1.5, size=nblk)
     blk[:, 0:2] = d.astype(np.float16).view(np.uint8).reshape(-1, 2)
     return blk.reshape(-1)
@@ -359,6 +377,20 @@ def iq4_nl_type(name, il, n_layer, n_gqa=4, imatrix=False):
     return IQ4_NL
 
 
+def iq4_xs_type(name, il, n_layer, n_gqa=4, imatrix=False):
+    """llama.cpp's IQ4_XS recipe for the Llama architecture (llama_tensor_get_type): attn_v Q5_K where n_gqa >= 4 (llama.cpp:15544-15546), else IQ4_XS;
+    ffn_down Q5_K in the layers il < n_layer / 8 unless the file was made with an importance matrix (:15611-15613); output.weight Q6_K; everything
+    else — attn_q, attn_k, attn_output, ffn_gate, ffn_up, token_embd — IQ4_XS (the default type of the ftype, :15807-15808).  (A tied embedding is
+    written as the output matrix: Q6_K, embd_type of write_synthetic_llama.)"""
+    if name == "output":
+        return Q6_K
+    if name == "attn_v":
+        return Q5_K if n_gqa >= 4 else IQ4_XS
+    if name == "ffn_down":
+        return Q5_K if il < n_layer // 8 and not imatrix else IQ4_XS
+    return IQ4_XS
+
+
 def q4_k_m_type(name, il, n_layer):
     """Tensor type under llama.cpp's Q4_K_M recipe for the tensors we use (reference: llama.cpp:15442-15444,
     :15547-15555, :15603-15610, use_more_bits :15466-15480; SURVEY §8 header)."""
@@ -406,7 +438,7 @@ def q2_k_type(name, il, n_layer, n_gqa=4):
 
 def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_ctx_train=8192, seed=7,
                           type_fn=None, rope_freqs=False, embd_type=Q4_K, reuse_layers=False, vocab=None, n_split=0, rope_scaling=None, tied=False, file_type=None):
-    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / IQ4_NL) blocks, or unquantised F32 / F16 / BF16 matrices
+    """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / IQ4_NL / IQ4_XS) blocks, or unquantised F32 / F16 / BF16 matrices
     (embd_type may be one of those too).
     reuse_layers: generate each (tensor kind, type) once and reuse the bytes in every layer (fast path for the
     multi-GB benchmark model; the arithmetic and the bytes streamed per token are unchanged).
@@ -434,7 +466,7 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
             bb = GGML_TYPES[t][1]; n = min(64, rows)
             return ([(k * rows // n) * cols * bb + (k % 32) * bb for k in range(n)], il + 1)
         be, bb = GGML_TYPES[t]; nb = cols // be
-        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32, Q4_0: 2, Q5_0: 6, Q8_0: 2, Q4_1: 4, Q5_1: 8, IQ4_NL: 2}[t]      # qs / qs / ql / qs / qs / qs / qs / qs / qs / qs / qs
+        qoff = {Q4_K: 16, Q5_K: 48, Q6_K: 0, Q2_K: 16, Q3_K: 32, Q4_0: 2, Q5_0: 6, Q8_0: 2, Q4_1: 4, Q5_1: 8, IQ4_NL: 2, IQ4_XS: 8}[t]      # qs / qs / ql / qs / qs / qs / qs / qs / qs / qs / qs / qs
         n = min(64, rows)
         return ([(k * rows // n) * nb * bb + qoff + (k % 32) for k in range(n)], il + 1)
 

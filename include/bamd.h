@@ -20,7 +20,7 @@ typedef struct bamd_model   bamd_model;
 typedef struct bamd_context bamd_context;
 
 /* ggml tensor type ids, as stored in GGUF (cpp/ggml/include/ggml.h:360-375) */
-enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q2_K = 10, BAMD_TYPE_Q3_K = 11, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14, BAMD_TYPE_IQ4_NL = 20, BAMD_TYPE_BF16 = 30 };
+enum { BAMD_TYPE_F32 = 0, BAMD_TYPE_F16 = 1, BAMD_TYPE_Q2_K = 10, BAMD_TYPE_Q3_K = 11, BAMD_TYPE_Q4_K = 12, BAMD_TYPE_Q5_K = 13, BAMD_TYPE_Q6_K = 14, BAMD_TYPE_IQ4_NL = 20, BAMD_TYPE_IQ4_XS = 23, BAMD_TYPE_BF16 = 30 };
 
 const char * bamd_last_error(void);
 
@@ -228,7 +228,7 @@ void bamd_set_prefill_flt(int on);
 void bamd_set_prefill_bf16(int on);
 /* Tests and tools: workgroups of that kernel that took the two-rounding step since the library was loaded.  Waits for every device that launched one. */
 unsigned long long bamd_prefill_bf16_fallback_tiles(void);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL, 30 BF16) since the library was loaded */
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL, 30 BF16; 23 IQ4_XS has no such kernel and stays 0) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */

@@ -19,6 +19,7 @@ alternate set_prefill_nl(False) / (True) like the lines above (integer-dot kerne
 file under set_prefill_q0 as the nearest twin and the Q4_K_M file.
 
     python tools/legacy_decode.py --iq4nl [--prompt 2048] [--only-prompt]
+    python tools/legacy_decode.py --iq4xs [--prompt 2048] [--only-prompt]
 """
 import importlib.util
 import os
@@ -136,9 +137,36 @@ def main_iq4nl():
             print_pair(name, n, *prompt_pair(p, n, q0=False, nl=True))
 
 
+def main_iq4xs():
+    """--iq4xs: the 8B shape under the IQ4_XS recipe as llama.cpp writes it (Q5_K attn_v, Q5_K ffn_down in layers 0-3, Q6_K output; everything is Q8_K, five
+    launches per layer) beside IQ4_NL, Q4_0 and Q4_K_M in the same job; with --prompt N the prompt rate on the integer-dot kernel (the type has no matrix-core
+    kernel, so its model builds no side tables) beside Q4_K_M on the matrix cores"""
+    def load(name):
+        _s = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "golden", name + ".py"))
+        g = importlib.util.module_from_spec(_s)
+        _s.loader.exec_module(g)
+        return g
+    gn, gx = load("gen_iq4nl_fixtures"), load("gen_iq4xs_fixtures")
+    gn.CONFIGS["8b_iq4nl"] = (gen.L3_8B, dict(imatrix=False), False, 128, 64, 512)                  # models only: no fixture of them is stored
+    gx.CONFIGS["8b_iq4xs"] = (gen.L3_8B, dict(imatrix=False), False, 128, 64, 512)
+    only_prompt = "--only-prompt" in sys.argv
+    files = [("Q4_K_M", q4_k_m_file())] + ([] if only_prompt else [("Q4_0", gen.ensure_model("8b_q4_0")), ("IQ4_NL", gn.ensure_model("8b_iq4nl"))]) + [("IQ4_XS", gx.ensure_model("8b_iq4xs"))]
+    for name, p in [] if only_prompt else files:
+        r = decode_rate(p)
+        print("decode %-7s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, statistics.median(r), min(r), max(r)), flush=True)
+    if "--prompt" in sys.argv:
+        n = int(sys.argv[sys.argv.index("--prompt") + 1])
+        for name, p in [f for f in files if f[0] in ("Q4_K_M", "IQ4_XS")]:
+            r, aux = prompt_rate(p, n, reps=5)
+            print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
+                  "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+
+
 def main():
     if "--legacy1" in sys.argv:
         return main_legacy1()
+    if "--iq4xs" in sys.argv:
+        return main_iq4xs()
     if "--iq4nl" in sys.argv:
         return main_iq4nl()
     files = [("Q4_K_M", q4_k_m_file()), ("Q8_0", gen.ensure_model("8b_q8_0")), ("Q4_0", gen.ensure_model("8b_q4_0")), ("Q5_0", gen.ensure_model("8b_q5_0"))]

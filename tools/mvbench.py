@@ -1,6 +1,6 @@
 """Micro-benchmark of mat-vec launch shapes, back to back on one matrix (GPU box only).
 
-    python tools/mvbench.py [8b | 70b | modea | ceiling | l2-7b | l32 | lowbit | legacy | legacy1 | iq4nl]
+    python tools/mvbench.py [8b | 70b | modea | ceiling | l2-7b | l32 | lowbit | legacy | legacy1 | iq4nl | iq4xs]
 
 8b (default): the launch shapes of Llama-3-8B Q4_K_M, both launch modes where both exist, and prologue-only launches; modea: the mode-A
 kernels only (a quick A/B target for kernel edits); ceiling: streaming rate by matrix size, Infinity-Cache-resident (75 MB) up to HBM-bound
@@ -8,14 +8,16 @@ kernels only (a quick A/B target for kernel edits); ceiling: streaming rate by m
 down at the 8B widths for Q2_K, Q3_K and Q4_K side by side (a Q3_K launch moves 0.76, a Q2_K launch 0.58 of the bytes of its Q4_K twin); legacy: the launch
 kinds of the 8B widths for Q8_0, Q4_0 and Q5_0 in both launch modes where both exist, beside Q4_K, with the fraction of 8 TB/s each reaches; legacy1: the same launch kinds for Q4_1 and Q5_1 (one wave per row-group: they have no split-K) beside
 their Q4_0 / Q5_0 twins; iq4nl: the launch kinds of the 8B shape under the IQ4_NL recipe (QKV as its two launches: attn_q | attn_k IQ4_NL 5120 x 4096 and attn_v
-Q5_K 1024 x 4096, and as the one launch of a uniform file) beside their Q4_0 and Q4_K twins."""
+Q5_K 1024 x 4096, and as the one launch of a uniform file) beside their Q4_0 and Q4_K twins; iq4xs: the launch kinds of the 8B widths for IQ4_XS in both launch modes
+where both exist, beside their IQ4_NL (mode 1) and Q4_K twins, and the Q4_K / Q6_K launches of the headline model on the generic kernels (mode + 16), which now
+dispatch one more type."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import booster_amd as b
 
-BB = {10: 84, 11: 110, 12: 144, 13: 176, 14: 210, 8: 8 * 34, 2: 8 * 18, 6: 8 * 22, 3: 8 * 20, 7: 8 * 24, 20: 8 * 18}       # bytes per row and 256 weights
+BB = {10: 84, 11: 110, 12: 144, 13: 176, 14: 210, 8: 8 * 34, 2: 8 * 18, 6: 8 * 22, 3: 8 * 20, 7: 8 * 24, 20: 8 * 18, 23: 136}       # bytes per row and 256 weights
 # (name, type, rows, K, prologue (1 = RMSNorm), epilogue (0 store, 1 +residual, 2 silu(gate)*up, 3 arg-max), modes)
 SETS = {
     "8b": [("prologue-only K4096", 12, 8, 4096, 0, 0, (1, 2)), ("prologue-only norm K4096", 12, 8, 4096, 1, 0, (1, 2)), ("prologue-only K14336", 12, 8, 14336, 0, 0, (1, 2)),
@@ -47,6 +49,12 @@ SETS = {
              [("%s %s" % (nm, tn), t, rows, k, pro, epi, (1,)) for nm, rows, k, pro, epi in (("qkv", 6144, 4096, 1, 0), ("wo", 4096, 4096, 0, 1), ("gate/up", 14336, 4096, 1, 2),
                                                                                               ("down", 4096, 14336, 0, 1), ("lm_head", 128256, 4096, 1, 3))
               for t, tn in ((20, "iq4_nl"), (2, "q4_0"), (12, "q4k"))],
+    "iq4xs": [("%s %s" % (nm, tn), t, rows, k, pro, epi, tuple(m for m in modes if m < 2 or t != 20)) for nm, rows, k, pro, epi, modes in (
+                  ("qkv", 6144, 4096, 1, 0, (0, 1, 2)), ("wo", 4096, 4096, 0, 1, (0, 1, 2)), ("gate/up", 14336, 4096, 1, 2, (0,)), ("down", 4096, 14336, 0, 1, (0, 1, 2)), ("lm_head", 128256, 4096, 1, 3, (0,)))
+              for t, tn in ((23, "iq4_xs"), (20, "iq4_nl"), (12, "q4k"))] +
+             [("generic %s" % nm, t, rows, k, pro, epi, modes) for nm, t, rows, k, pro, epi, modes in (
+                  ("qkv q4k", 12, 6144, 4096, 1, 0, (17, 18)), ("wo q4k", 12, 4096, 4096, 0, 1, (17, 18)), ("gate/up q4k", 12, 14336, 4096, 1, 2, (17,)), ("down q6k", 14, 4096, 14336, 0, 1, (17, 18)),
+                  ("lm_head q6k", 14, 128256, 4096, 1, 3, (17,)))],
 }
 
 
@@ -56,7 +64,7 @@ def main():
         mb = rows * (k // 256) * BB[t] * (2 if epi == 2 else 1) / 1e6
         for mode in modes:
             us = b.bench_matvec(t, rows, k, pro, epi, mode, 300 if which != "ceiling" else 100)
-            print("%-38s mode %d: %8.2f us  %7.1f MB  %7.1f GB/s" % (name, mode, us, mb, mb / us * 1e3) + ("  %.3f of 8 TB/s" % (mb / us / 8.0) if which in ("legacy", "legacy1", "iq4nl") else ""))
+            print("%-38s mode %d: %8.2f us  %7.1f MB  %7.1f GB/s" % (name, mode, us, mb, mb / us * 1e3) + ("  %.3f of 8 TB/s" % (mb / us / 8.0) if which in ("legacy", "legacy1", "iq4nl", "iq4xs") else ""))
 
 
 if __name__ == "__main__":
