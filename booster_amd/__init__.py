@@ -173,6 +173,13 @@ def set_prefill_bf16(on):
     lib().bamd_set_prefill_bf16(int(bool(on)))
 
 
+def set_prefill_xs(on):
+    """True: models loaded from now on build side tables for their IQ4_XS layer matrices and evaluate prompts on the matrix-core kernel of the type; False
+    (default, also env BAMD_PREFILL_XS): such a model evaluates prompts on the integer-dot kernel.  Independent of the other switches: llama.cpp's IQ4_XS files
+    hold IQ4_XS, Q5_K and Q6_K layer matrices and need this one alone.  Same bits either way."""
+    lib().bamd_set_prefill_xs(int(bool(on)))
+
+
 def prefill_bf16_fallback_tiles():
     """tests and tools: workgroups of the BF16 matrix-core kernel that took the two-rounding VALU step since the library was loaded (waits for the device)"""
     return int(lib().bamd_prefill_bf16_fallback_tiles())

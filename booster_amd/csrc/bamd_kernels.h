@@ -140,6 +140,14 @@ int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type,
 // the side of the three entry points above for the 32-weight block formats, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 and IQ4_NL (the Q4_0 table), one kernel template
 // (bamd_prefill2_b32.hip); callers go through those
 size_t bamd_prefill_aux_bytes_b32(int type, int nrows_pad, int K);
+// IQ4_XS (bamd_prefill2_xs.hip): builder / consumer bytes of a (row block, super-block) of its side table, the table's kernel (ph, ch: the two parts), the LDS
+// attribute of its kernel, and the launch itself (bamd_mma2_args: bamd_prefill2_body.h)
+size_t bamd_prefill_xs_ph_sb(void);
+size_t bamd_prefill_xs_ch_sb(void);
+void bamd_launch_prefill_aux_xs(const void * w_stream, int nrows_pad, int K, void * ph, void * ch, hipStream_t s);
+int  bamd_prefill_mfma_supported_xs(void);
+struct bamd_mma2_args;
+void bamd_launch_matmul_mfma_xs(const bamd_mma2_args & a, int epi, dim3 grid, hipStream_t s);
 void bamd_launch_prefill_aux_b32(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma_b32(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                                  int epi, int ldo, hipStream_t s);

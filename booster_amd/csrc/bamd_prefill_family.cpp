@@ -33,6 +33,7 @@ BAMD_API void bamd_set_prefill_q1(int on) { bamd_prefill_family_set(BAMD_PF_Q1, 
 BAMD_API void bamd_set_prefill_nl(int on) { bamd_prefill_family_set(BAMD_PF_NL, on); }
 BAMD_API void bamd_set_prefill_flt(int on) { bamd_prefill_family_set(BAMD_PF_FLT, on); }
 BAMD_API void bamd_set_prefill_bf16(int on) { bamd_prefill_family_set(BAMD_PF_BF16, on); }
+BAMD_API void bamd_set_prefill_xs(int on) { bamd_prefill_family_set(BAMD_PF_XS, on); }
 BAMD_API unsigned long long bamd_prefill_bf16_fallback_tiles(void) { return bamd_bf16_fallback_tiles_all(); }
 
 // Called for a matrix without a side table (bamd_prefill_aux_bytes = 0).  With every switch off the sentences read as they did before the switches existed.  The
@@ -44,7 +45,7 @@ std::string bamd_prefill_reason(int type) {
         return bamd_prefill_family_on(BAMD_PF_FLT) ? "the model holds a BF16 matrix: these have no matrix-core kernel (BAMD_PREFILL_FLT covers F32 / F16 only), and side tables are all-or-nothing per model, so every prompt mat-mul of the other types runs on the VALU kernels"
                                                    : "the model holds an F32 / F16 / BF16 matrix: these have no matrix-core kernel, and side tables are all-or-nothing per model, so every prompt mat-mul runs on the VALU kernels";
     if (type == BAMD_IQ4_NL) return "the model holds an IQ4_NL matrix: these have no matrix-core kernel (BAMD_PREFILL_Q0 covers Q4_0 / Q5_0 / Q8_0 only), and " INT_DOT "; BAMD_PREFILL_NL, the switch of the IQ4_NL matrix-core kernel, is off";
-    if (type == BAMD_IQ4_XS) return "the model holds an IQ4_XS matrix: these have no matrix-core kernel, and " INT_DOT;      // (in no family: no matrix-core kernel is built for the type)
+    if (type == BAMD_IQ4_XS && !bamd_prefill_family_on(BAMD_PF_XS)) return "the model holds an IQ4_XS matrix: these have no matrix-core kernel, and " INT_DOT;      // (the sentence from before the type had a kernel; its switch, BAMD_PREFILL_XS, is off)
     int own = 0;
     while (own < BAMD_PF_COUNT && !bamd_prefill_type_in(R[own].types, type)) ++own;
     if (own == BAMD_PF_COUNT || !R[own].names || bamd_prefill_family_on(own)) return "a matrix type / shape without a matrix-core kernel";

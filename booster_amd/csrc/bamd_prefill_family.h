@@ -9,6 +9,8 @@
 //   NL      IQ4_NL: the Q4_0 record and side table; the same template with two accumulator sets and a 16-token tile
 //   FLT     F32 / F16 (bamd_prefill2_flt.hip)
 //   BF16    BF16 (bamd_prefill2_bf16.hip): fma chains where exponent ranges prove every product exact, the two-rounding VALU step per workgroup otherwise
+//   XS      IQ4_XS (bamd_prefill2_xs.hip): the eight-wave kernel body of bamd_prefill2_body.h with a policy struct of its own, the Q8_K f16 token records as they are
+// (llama.cpp's IQ4_XS files hold IQ4_XS, Q5_K and Q6_K layer matrices: XS alone gives such a model its tables)
 // Families WITH A SIDE TABLE are asked three times: when a model builds its tables at load (all or nothing per model: one matrix without a table and every prompt
 // mat-mul stays on the integer-dot kernel — llama.cpp writes Q4_0 / Q5_0 files made with an importance matrix with Q4_1 / Q5_1 ffn_down matrices in their first
 // layers, so such a file needs BOTH Q0 and Q1), at each launch (a table built earlier is ignored while its family is off) and by the batch quantiser (the f16
@@ -20,7 +22,7 @@
 #include <string>
 #include "bamd_formats.h"
 
-enum bamd_prefill_family { BAMD_PF_K = 0, BAMD_PF_LOWBIT, BAMD_PF_Q0, BAMD_PF_Q1, BAMD_PF_NL, BAMD_PF_FLT, BAMD_PF_BF16, BAMD_PF_COUNT };
+enum bamd_prefill_family { BAMD_PF_K = 0, BAMD_PF_LOWBIT, BAMD_PF_Q0, BAMD_PF_Q1, BAMD_PF_NL, BAMD_PF_FLT, BAMD_PF_BF16, BAMD_PF_XS, BAMD_PF_COUNT };
 // env: the switch's environment variable (null: always on); types: bit t = bamd_type t belongs to the family (every type is < 32); table: its kernels read a
 // load-time side table (bamd_prefill_aux_bytes); names: the types as the load-time message names them (null: the family has no composed sentence)
 struct bamd_prefill_family_row { const char * env; uint32_t types; bool table; const char * names; };
@@ -32,10 +34,11 @@ static const bamd_prefill_family_row bamd_prefill_families[BAMD_PF_COUNT] = {
     { "BAMD_PREFILL_NL",     1u << BAMD_IQ4_NL,                                   true,  "IQ4_NL" },
     { "BAMD_PREFILL_FLT",    1u << BAMD_F32 | 1u << BAMD_F16,                     false, nullptr },
     { "BAMD_PREFILL_BF16",   1u << BAMD_BF16,                                     false, nullptr },
+    { "BAMD_PREFILL_XS",     1u << BAMD_IQ4_XS,                                   true,  "IQ4_XS" },
 };
 int  bamd_prefill_family_on(int f);
 void bamd_prefill_family_set(int f, int on);
-uint32_t bamd_prefill_types_on(bool table);      // the types of the families that are on now, with (table = true) or without a side table: seven compares per call
+uint32_t bamd_prefill_types_on(bool table);      // the types of the families that are on now, with (table = true) or without a side table: eight compares per call
 static inline bool bamd_prefill_type_in(uint32_t mask, int type) { return type >= 0 && type < 32 && (mask >> type & 1u); }
 // "this weight type has a matrix-core prompt mat-mul with a side table now": side-table sizes, the launcher and the engine's routing ask here
 static inline bool bamd_prefill_mfma_type(int type) { return bamd_prefill_type_in(bamd_prefill_types_on(true), type); }

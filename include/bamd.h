@@ -228,7 +228,12 @@ void bamd_set_prefill_flt(int on);
 void bamd_set_prefill_bf16(int on);
 /* Tests and tools: workgroups of that kernel that took the two-rounding step since the library was loaded.  Waits for every device that launched one. */
 unsigned long long bamd_prefill_bf16_fallback_tiles(void);
-/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL, 30 BF16; 23 IQ4_XS has no such kernel and stays 0) since the library was loaded */
+/* Matrix-core prompt mat-muls for IQ4_XS weights (env BAMD_PREFILL_XS): 0 (default) = a model that holds such a layer matrix builds no side tables and evaluates
+ * its prompts on the integer-dot kernel; 1 = side tables (the rows' 6-bit block scales split into two exact f16 operands and d as f32: 68 B per row and 256
+ * weights) and a policy of the eight-wave K-quant kernel body of its own.  Independent of every other switch; llama.cpp's IQ4_XS files hold IQ4_XS, Q5_K and Q6_K
+ * layer matrices and need this one alone.  Taken at model load, like bamd_set_prefill_lowbit.  Bit-identical results. */
+void bamd_set_prefill_xs(int on);
+/* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS, 30 BF16) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */

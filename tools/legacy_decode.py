@@ -40,15 +40,15 @@ _spec.loader.exec_module(gen)
 gen.CONFIGS.setdefault("8b_q5_0", (gen.L3_8B, "q5_0", 128, 64, 512))          # a model only: no fixture of it is stored
 
 
-def set_switches(q0, q1, nl=False):
-    b.set_prefill_q0(bool(q0)); b.set_prefill_q1(bool(q1)); b.set_prefill_nl(bool(nl))
+def set_switches(q0, q1, nl=False, xs=False):
+    b.set_prefill_q0(bool(q0)); b.set_prefill_q1(bool(q1)); b.set_prefill_nl(bool(nl)); b.set_prefill_xs(bool(xs))
 
 
-def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True, nl=False):
-    """switched-off and switched-on rates of one file, alternating: ([off], [on], side-table bytes of the switched-on model).  q0 / q1 / nl: what "on" sets;
+def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True, nl=False, xs=False):
+    """switched-off and switched-on rates of one file, alternating: ([off], [on], side-table bytes of the switched-on model).  q0 / q1 / nl / xs: what "on" sets;
     tables: whether "on" is enough for this file to get side tables"""
     set_switches(False, False); m0 = b.Model(path)
-    set_switches(q0, q1, nl)
+    set_switches(q0, q1, nl, xs)
     try:
         m1 = b.Model(path)
     finally:
@@ -59,7 +59,7 @@ def prompt_pair(path, n_prompt, reps=5, q0=True, q1=False, tables=True, nl=False
     rates = ([], [])
     for rep in range(reps + 1):                                 # the first pair warms up
         for k, ctx in enumerate(ctxs):
-            set_switches(q0 and k, q1 and k, nl and k)                 # the routing asks the switches as well as the tables
+            set_switches(q0 and k, q1 and k, nl and k, xs and k)                 # the routing asks the switches as well as the tables
             b.lib().bamd_kv_cache_clear(ctx.h)
             t0 = time.perf_counter()
             for i in range(0, n_prompt, 512):
@@ -139,8 +139,9 @@ def main_iq4nl():
 
 def main_iq4xs():
     """--iq4xs: the 8B shape under the IQ4_XS recipe as llama.cpp writes it (Q5_K attn_v, Q5_K ffn_down in layers 0-3, Q6_K output; everything is Q8_K, five
-    launches per layer) beside IQ4_NL, Q4_0 and Q4_K_M in the same job; with --prompt N the prompt rate on the integer-dot kernel (the type has no matrix-core
-    kernel, so its model builds no side tables) beside Q4_K_M on the matrix cores"""
+    launches per layer) beside IQ4_NL, Q4_0 and Q4_K_M in the same job; with --prompt N the prompt rate with set_prefill_xs(False) (integer-dot kernel, no side
+    tables) and (True) (side tables, the IQ4_XS policy of the eight-wave matrix-core kernel: bamd_prefill2_xs.hip), alternating like the lines of the other
+    families, beside Q4_K_M on the matrix cores"""
     def load(name):
         _s = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "golden", name + ".py"))
         g = importlib.util.module_from_spec(_s)
@@ -156,10 +157,10 @@ def main_iq4xs():
         print("decode %-7s %5.2f GB: median %7.1f tok/s  (range %.1f - %.1f, 5 x 128 steps after a 128-token prompt)" % (name, os.path.getsize(p) / 1e9, statistics.median(r), min(r), max(r)), flush=True)
     if "--prompt" in sys.argv:
         n = int(sys.argv[sys.argv.index("--prompt") + 1])
-        for name, p in [f for f in files if f[0] in ("Q4_K_M", "IQ4_XS")]:
-            r, aux = prompt_rate(p, n, reps=5)
-            print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (name, n, statistics.median(r), min(r), max(r),
-                  "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+        r, aux = prompt_rate(files[0][1], n, reps=5)
+        print("prompt %-7s %d tokens: median %7.1f tok/s  (range %.1f - %.1f; %s)" % (files[0][0], n, statistics.median(r), min(r), max(r),
+              "matrix-core kernels" if aux > 0 else "integer-dot kernel"), flush=True)
+        print_pair("IQ4_XS", n, *prompt_pair(files[-1][1], n, q0=False, xs=True))
 
 
 def main():
