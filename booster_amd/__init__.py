@@ -58,7 +58,7 @@ def lib():
         L.bamd_last_error.restype = C.c_char_p
         L.bamd_model_load.restype = vp; L.bamd_model_load.argtypes = [C.c_char_p, ci, ci, ci, ci, ci]
         L.bamd_model_free.argtypes = [vp]
-        for n in ("bamd_model_n_vocab", "bamd_model_n_embd", "bamd_model_n_layer", "bamd_model_n_ctx_train"):
+        for n in ("bamd_model_n_vocab", "bamd_model_n_embd", "bamd_model_n_layer", "bamd_model_n_ctx_train", "bamd_model_n_expert", "bamd_model_n_expert_used"):
             getattr(L, n).argtypes = [vp]
         L.bamd_model_weight_bytes.restype = i64; L.bamd_model_weight_bytes.argtypes = [vp]
         L.bamd_model_tensor_raw.restype = i64; L.bamd_model_tensor_raw.argtypes = [vp, C.c_char_p, vp, i64]
@@ -92,6 +92,7 @@ def lib():
         L.bamd_op_mul_mat_vec.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, vp, ci]
         L.bamd_op_mul_mat_vec_argmax.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, ci, C.POINTER(C.c_int32)]
         L.bamd_op_ffn_gate_up.argtypes = [ci, vp, vp, ci, ci, vp, vp, cf, vp]
+        L.bamd_op_moe_ffn.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, cf, vp, vp, vp]
         L.bamd_op_mul_mat_batch.argtypes = [ci, vp, ci, ci, vp, ci, vp, cf, vp, vp, ci]
         L.bamd_op_get_row.argtypes = [ci, vp, ci, ci, ci, vp]
         L.bamd_op_attention.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
@@ -238,6 +239,8 @@ class Model:
         self.n_vocab = lib().bamd_model_n_vocab(self.h)
         self.n_embd = lib().bamd_model_n_embd(self.h)
         self.n_layer = lib().bamd_model_n_layer(self.h)
+        self.n_expert = lib().bamd_model_n_expert(self.h)               # 0: a dense model
+        self.n_expert_used = lib().bamd_model_n_expert_used(self.h)
         self.weight_bytes = lib().bamd_model_weight_bytes(self.h)
 
     def tensor_raw(self, name):
@@ -482,6 +485,17 @@ def op_ffn_gate_up(ttype, wg_raw, wu_raw, nrows, k, x, norm_w=None, eps=0.0):
     y = np.zeros(nrows, np.float32)
     _chk(lib().bamd_op_ffn_gate_up(ttype, _p(wg_raw), _p(wu_raw), nrows, k, _p(x), _p(nw), eps, _p(y)))
     return y
+
+
+def op_moe_ffn(gate_inp, type_gu, gate_exps, up_exps, type_d, down_exps, E, F, n_expert, n_used, x, norm_w, eps):
+    """the mixture-of-experts feed-forward of one token through the decode step's three launches: (y = x + MoE output, selected expert ids, their weights).
+    gate_inp f32 [n_expert][E]; gate_exps / up_exps / down_exps: the GGUF bytes of the 3-D expert tensors (expert after expert)"""
+    gi = np.ascontiguousarray(gate_inp, np.float32)
+    ge, ue, de = (np.ascontiguousarray(a, np.uint8) for a in (gate_exps, up_exps, down_exps))
+    x = np.ascontiguousarray(x, np.float32); nw = np.ascontiguousarray(norm_w, np.float32)
+    y = np.zeros(E, np.float32); sel = np.zeros(n_used, np.int32); w = np.zeros(n_used, np.float32)
+    _chk(lib().bamd_op_moe_ffn(_p(gi), type_gu, _p(ge), _p(ue), type_d, _p(de), E, F, n_expert, n_used, _p(x), _p(nw), eps, _p(y), _p(sel), _p(w)))
+    return y, sel, w
 
 
 def op_get_row(ttype, w_raw, nrows, k, row):

@@ -102,6 +102,10 @@ struct DevLayer {
     DevMat wq, wk, wv, wo, wg, wu, wd;
     // prefill side tables (bamd_prefill2.hip), built at model load (build_prefill_aux): one per QKV segment (qkv_segments), wo, gate, up, down
     void * aux_qkv[3] = { nullptr, nullptr, nullptr }, * aux_o = nullptr, * aux_g = nullptr, * aux_u = nullptr, * aux_d = nullptr;
+    // mixture-of-experts layers (bamd_model::n_expert > 0; wg / wu / wd stay empty): the F32 router matrix and the three expert tensors, each repacked as n_expert
+    // consecutive wave-stream matrices stride_* bytes apart; bytes_*: the GGUF bytes of ONE expert's matrix
+    void * gate_inp = nullptr, * exp_g = nullptr, * exp_u = nullptr, * exp_d = nullptr;
+    int type_gu = 0, type_d = 0; size_t stride_gu = 0, stride_d = 0, bytes_gu = 0, bytes_d = 0;
 };
 
 struct bamd_model {
@@ -109,6 +113,7 @@ struct bamd_model {
     int E = 0, H = 0, Hkv = 0, hd = 0, L = 0, F = 0, V = 0, n_ctx_train = 0, n_rot = 0;
     float eps = 1e-5f, rope_theta = 10000.f, rope_freq_scale = 1.f, rope_ext_factor = 0.f, rope_attn_factor = 1.f;
     int rope_n_ctx_orig = 0;
+    int n_expert = 0, n_expert_used = 0;   // llama.expert_count / llama.expert_used_count (0: a dense model)
     int layer_first = 0, layer_last = 0;
     bool with_embd = true, with_output = true;
     std::vector<float> rope_freqs;   // host copy (optional)
@@ -142,6 +147,7 @@ struct bamd_context {
     std::vector<unsigned short *> kc, vc;
     float * rope = nullptr, * rope_cur = nullptr;   // rope_cur [hd]: the cos / sin row of the current step's position (step_begin_kernel -> attn_qk_kernel)
     float * x = nullptr, * x2 = nullptr, * q = nullptr, * k = nullptr, * v = nullptr, * att = nullptr, * h = nullptr, * scores = nullptr, * probs = nullptr;
+    int32_t * moe_sel = nullptr; float * moe_w = nullptr;   // mixture-of-experts models: the router's selection of the current layer (h then holds one row per slot)
     int n_ctx_pad = 0;              // KV row stride: n_ctx rounded up to 64 (V^T rows are stored in 64-position blocks)
     float * logits = nullptr;        // device
     float * logits_host = nullptr;   // pinned
@@ -239,7 +245,27 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s);
 // for the first two, Q8_K for the third.  The engine runs such a layer's QKV as one launch per form (qkv_groups); every other mix stays refused at load.
 // (bamd_is_kquant holds IQ4_XS too, so an IQ4_XS attn_v beside IQ4_NL attn_q / attn_k passes here as well: no recipe writes it and no test covers it; it takes the
 // same two launches, the second on the generic Q8_K kernel)
-static bool qkv_recipe_mix(int tq, int tk, int tv) { return tq == BAMD_IQ4_NL && tk == BAMD_IQ4_NL && bamd_is_kquant(tv); }
+// The second one: the recipes for an 8-expert model write attn_k and attn_v as Q8_0 beside a K-quant attn_q (src/llama.cpp:15556-15567): Q8_K activations for the
+// first, Q8_0 for the merged k | v segment — two launches as well
+static bool qkv_recipe_mix(int tq, int tk, int tv, int n_expert) {
+    return (tq == BAMD_IQ4_NL && tk == BAMD_IQ4_NL && bamd_is_kquant(tv)) || (n_expert == 8 && bamd_is_kquant(tq) && tk == BAMD_Q8_0 && tv == BAMD_Q8_0);
+}
+// one 3-D expert tensor [K, nrows, n_expert] -> n_expert consecutive wave-stream matrices
+static int upload_experts(bamd_model * m, const GgufTensor * t, const std::string & name, int K, int nrows, void ** dst, int * type, size_t * stride, size_t * bytes, void * staging, hipStream_t s) {
+    if (!t) return fail("missing tensor " + name);
+    if (t->ne.size() != 3 || (int) t->ne[0] != K || (int) t->ne[1] != nrows || (int) t->ne[2] != m->n_expert)
+        return fail("tensor " + name + ": expected [" + std::to_string(K) + ", " + std::to_string(nrows) + ", " + std::to_string(m->n_expert) + "]");
+    if (!bamd_is_kquant(t->type)) return fail("tensor " + name + ": expert matrices of type " + std::to_string(t->type) + " are not supported (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS)");
+    *type = t->type; *stride = bamd_stream_bytes(t->type, K, nrows); *bytes = t->nbytes / (size_t) m->n_expert;
+    if (*stride >= (size_t) 0x7fffffff) return fail("tensor " + name + ": one expert's wave-stream copy exceeds 2 GiB (32-bit record offsets)");
+    if (dev_alloc(m->allocs, dst, *stride * (size_t) m->n_expert)) return 1;
+    HIPC(hipMemcpyAsync(staging, t->data, t->nbytes, hipMemcpyHostToDevice, s));
+    for (int e = 0; e < m->n_expert; ++e) bamd_launch_repack((const char *) staging + (size_t) e * *bytes, (char *) *dst + (size_t) e * *stride, t->type, nrows, K, s);
+    HIPC(hipGetLastError());
+    m->weight_bytes += (int64_t) t->nbytes;
+    HIPC(hipStreamSynchronize(s));     // staging buffer is reused by the next tensor
+    return 0;
+}
 static int model_load_impl(bamd_model * m, const char * path, int device, int lf, int ll, int with_embd, int with_output) {
     // the file is read and its header validated before any device is touched: a bad file is reported as such on any machine
     m->file.reset(new GgufFile());
@@ -286,6 +312,16 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
                                            : "n_embd and n_ff must be multiples of 256 (n_embd " + std::to_string(m->E) + ", n_ff " + std::to_string(m->F) +
                                              ": a row length that is a multiple of 32 but not of 256 is a valid Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 tensor (or IQ4_NL one), but a wave-stream record holds 256 weights per row)");
     if (m->E > 32768 || m->F > 131072) return fail("n_embd / n_ff beyond what the kernels' LDS budgets were sized for");
+    if (g.get_u32("llama.expert_count", u)) m->n_expert = (int) u;
+    if (g.get_u32("llama.expert_used_count", u)) m->n_expert_used = (int) u;
+    if (m->n_expert > 0) {      // llm_load_tensors' MoE branch (llama.cpp:6102-6142): what the routed kernels take, everything else refused by name
+        if (m->n_expert % 8 || m->n_expert > 64) return fail("llama.expert_count " + std::to_string(m->n_expert) + ": the router takes a multiple of 8 experts, at most 64");
+        if (m->n_expert_used < 1 || m->n_expert_used > 8) return fail("llama.expert_used_count " + std::to_string(m->n_expert_used) + ": 1 .. 8 experts per token are supported");
+        if (!bamd_moe_shape_supported(m->E, 256, m->n_expert, 1))           // the smallest feed-forward: what is left is the router's own limit
+            return fail("mixture of experts: the router keeps the f32 activations of n_embd " + std::to_string(m->E) + " in the LDS of one workgroup, and they do not fit");
+        if (!bamd_moe_shape_supported(m->E, m->F, m->n_expert, m->n_expert_used))
+            return fail("mixture of experts: the Q8_K activations of " + std::to_string(m->n_expert_used) + " slots of n_ff " + std::to_string(m->F) + " do not fit the LDS of a CU (routed down launch)");
+    }
     if (ll < 0 || ll > m->L) ll = m->L;
     if (lf < 0 || lf > ll) return fail("bad layer range");
     m->layer_first = lf; m->layer_last = ll; m->with_embd = with_embd != 0; m->with_output = with_output != 0;
@@ -340,6 +376,7 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
             }
             int mi = 0;
             for (auto & mm : mats) {
+                if (m->n_expert > 0 && mi >= 4) break;                       // the feed-forward of a mixture-of-experts layer: below
                 const GgufTensor * t = g.tensor(p + mm.n + ".weight");
                 if (!t) { rc = fail("missing tensor " + p + mm.n + ".weight"); break; }
                 void * dst = nullptr;
@@ -349,15 +386,32 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
             }
             if (rc) break;
             if (ly.wq.nrows != m->E || ly.wq.K != m->E || ly.wk.nrows != m->Hkv * m->hd || ly.wk.K != m->E || ly.wv.nrows != m->Hkv * m->hd || ly.wv.K != m->E ||
-                ly.wo.nrows != m->E || ly.wo.K != m->E || ly.wg.nrows != m->F || ly.wg.K != m->E || ly.wu.nrows != m->F || ly.wu.K != m->E ||
-                ly.wd.nrows != m->E || ly.wd.K != m->F) { rc = fail("layer " + std::to_string(il) + ": unexpected tensor shapes"); break; }
-            if (ly.wg.type != ly.wu.type) { rc = fail("ffn_gate and ffn_up must share one quantisation type"); break; }
+                ly.wo.nrows != m->E || ly.wo.K != m->E) { rc = fail("layer " + std::to_string(il) + ": unexpected tensor shapes"); break; }
+            if (m->n_expert > 0) {
+                if (g.tensor(p + "ffn_gate.0.weight")) { rc = fail("tensor " + p + "ffn_gate.0.weight: the per-expert tensor layout of early Mixtral conversions is not supported (convert to merged " + p + "ffn_gate_exps.weight)"); break; }
+                const GgufTensor * gi = g.tensor(p + "ffn_gate_inp.weight");
+                if (!gi) { rc = fail("missing tensor " + p + "ffn_gate_inp.weight"); break; }
+                if (gi->type != BAMD_F32 || gi->ne.size() != 2 || (int) gi->ne[0] != m->E || (int) gi->ne[1] != m->n_expert) { rc = fail("tensor " + p + "ffn_gate_inp.weight: expected f32 [" + std::to_string(m->E) + ", " + std::to_string(m->n_expert) + "]"); break; }
+                if (dev_alloc(m->allocs, &ly.gate_inp, bamd_stream_bytes(BAMD_F32, m->E, m->n_expert))) { rc = 1; break; }
+                if (hipMemcpyAsync(staging, gi->data, gi->nbytes, hipMemcpyHostToDevice, s) != hipSuccess) { rc = fail("tensor " + p + "ffn_gate_inp.weight: upload failed"); break; }
+                bamd_launch_repack(staging, ly.gate_inp, BAMD_F32, m->n_expert, m->E, s);
+                if (hipStreamSynchronize(s) != hipSuccess) { rc = fail("tensor " + p + "ffn_gate_inp.weight: repack failed"); break; }
+                m->weight_bytes += (int64_t) gi->nbytes;
+                const GgufTensor * tg = g.tensor(p + "ffn_gate_exps.weight"), * tu = g.tensor(p + "ffn_up_exps.weight");
+                if (tg && tu && tg->type != tu->type) { rc = fail("ffn_gate_exps and ffn_up_exps must share one quantisation type"); break; }     // before anything is uploaded
+                if ((rc = upload_experts(m, tg, p + "ffn_gate_exps.weight", m->E, m->F, &ly.exp_g, &ly.type_gu, &ly.stride_gu, &ly.bytes_gu, staging, s))) break;
+                if ((rc = upload_experts(m, tu, p + "ffn_up_exps.weight", m->E, m->F, &ly.exp_u, &ly.type_gu, &ly.stride_gu, &ly.bytes_gu, staging, s))) break;  // one type: the same values again
+                if ((rc = upload_experts(m, g.tensor(p + "ffn_down_exps.weight"), p + "ffn_down_exps.weight", m->F, m->E, &ly.exp_d, &ly.type_d, &ly.stride_d, &ly.bytes_d, staging, s))) break;
+            } else {
+                if (ly.wg.nrows != m->F || ly.wg.K != m->E || ly.wu.nrows != m->F || ly.wu.K != m->E || ly.wd.nrows != m->E || ly.wd.K != m->F) { rc = fail("layer " + std::to_string(il) + ": unexpected tensor shapes"); break; }
+                if (ly.wg.type != ly.wu.type) { rc = fail("ffn_gate and ffn_up must share one quantisation type"); break; }
+            }
             // the fused QKV launch quantises its activations ONCE: Q8_K for K-quant segments, Q8_0 for Q4_0 / Q5_0 / Q8_0 ones, Q8_1 for Q4_1 / Q5_1 ones
             // (bamd_act_form_of).  No llama.cpp recipe mixes the
             // families inside attn_q | attn_k | attn_v; a file that does is refused here rather than run with the wrong form.  The one exception is the pair
             // qkv_recipe_mix names, which the decode step and the batched prompt path run as one launch per form (qkv_groups).  IQ4_NL beside Q8_0 / Q4_0 / Q5_0
             // (one form, but no recipe writes it either) is refused in the same words: what loads is what a recipe writes
-            for (int j = 1; j < 3 && !rc && !qkv_recipe_mix(ly.wq.type, ly.wk.type, ly.wv.type); ++j)
+            for (int j = 1; j < 3 && !rc && !qkv_recipe_mix(ly.wq.type, ly.wk.type, ly.wv.type, m->n_expert); ++j)
                 if (bamd_act_form_of(mats[j].d->type) != bamd_act_form_of(mats[0].d->type) || (mats[j].d->type == BAMD_IQ4_NL) != (mats[0].d->type == BAMD_IQ4_NL))
                     rc = fail(p + mats[0].n + ".weight (type " + std::to_string(mats[0].d->type) + ") and " + p + mats[j].n + ".weight (type " + std::to_string(mats[j].d->type) +
                               ") need different activation formats (" + (bamd_is_flt(mats[0].d->type) || bamd_is_flt(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1 / F32 / BF16" : bamd_is_q1(mats[0].d->type) || bamd_is_q1(mats[j].d->type) ? "Q8_K / Q8_0 / Q8_1" : "Q8_K / Q8_0") + ") in one fused launch: not supported");
@@ -392,6 +446,8 @@ extern "C" __attribute__((visibility("default"))) int bamd_model_n_vocab(const b
 extern "C" __attribute__((visibility("default"))) int64_t bamd_model_prefill_aux_bytes(const bamd_model * m) { return m->aux_ok ? m->aux_bytes : 0; }
 extern "C" __attribute__((visibility("default"))) int bamd_model_n_embd(const bamd_model * m) { return m->E; }
 extern "C" __attribute__((visibility("default"))) int bamd_model_n_layer(const bamd_model * m) { return m->L; }
+extern "C" __attribute__((visibility("default"))) int bamd_model_n_expert(const bamd_model * m) { return m->n_expert; }
+extern "C" __attribute__((visibility("default"))) int bamd_model_n_expert_used(const bamd_model * m) { return m->n_expert_used; }
 extern "C" __attribute__((visibility("default"))) int bamd_model_n_ctx_train(const bamd_model * m) { return m->n_ctx_train; }
 extern "C" __attribute__((visibility("default"))) int64_t bamd_model_weight_bytes(const bamd_model * m) { return m->weight_bytes; }
 extern "C" __attribute__((visibility("default"))) int64_t bamd_model_tensor_raw(const bamd_model * m, const char * name, void * dst, int64_t cap) {
@@ -435,8 +491,9 @@ static int context_init(bamd_context * c, bamd_model * m, int n_ctx) {
     }
     if (dev_alloc(c->allocs, (void **) &c->x, (size_t) m->E * 4) || dev_alloc(c->allocs, (void **) &c->x2, (size_t) m->E * 4) ||
         dev_alloc(c->allocs, (void **) &c->q, (size_t) (m->E + 2 * Ekv) * 4) || dev_alloc(c->allocs, (void **) &c->att, (size_t) m->E * 4) ||
-        dev_alloc(c->allocs, (void **) &c->h, (size_t) m->F * 4) || dev_alloc(c->allocs, (void **) &c->scores, (size_t) m->H * c->n_ctx_pad * 4) || dev_alloc(c->allocs, (void **) &c->probs, (size_t) m->H * c->n_ctx_pad * 4) ||
+        dev_alloc(c->allocs, (void **) &c->h, (size_t) std::max(m->n_expert_used, 1) * m->F * 4) || dev_alloc(c->allocs, (void **) &c->scores, (size_t) m->H * c->n_ctx_pad * 4) || dev_alloc(c->allocs, (void **) &c->probs, (size_t) m->H * c->n_ctx_pad * 4) ||
         dev_alloc(c->allocs, (void **) &c->logits, (size_t) m->V * 4) || dev_alloc(c->allocs, (void **) &c->st, sizeof(bamd_step_state))) return 1;
+    if (m->n_expert > 0 && (dev_alloc(c->allocs, (void **) &c->moe_sel, 64) || dev_alloc(c->allocs, (void **) &c->moe_w, 64))) return 1;
     c->k = c->q + m->E; c->v = c->k + Ekv;                           // q | k | v contiguous: rows of the fused QKV mat-vec
     HIPC(hipMemsetAsync(c->st, 0, sizeof(bamd_step_state), c->stream));
     if (dev_alloc(c->allocs, (void **) &c->co_gran, (size_t) m->H * m->hd * 8 + 64)) return 1;
@@ -587,6 +644,22 @@ static int enqueue_layers(bamd_context * c, int prefill_mode, hipStream_t s, Ste
             if (tm) tm->begin(s, 0, (double) ly.wo.bytes, 3);
             if (bamd_launch_mv(a, BAMD_PRO_PLAIN, BAMD_EPI_ADD, m->n_cu, s)) return fail("mat-vec launch: a matrix type without a kernel");
             if (tm) tm->end(s);
+        }
+        if (m->n_expert > 0) {
+            // 4 + 5 of a mixture-of-experts layer (llm_build_moe_ffn, llama.cpp:8087-8186): router | routed gate/up -> h[slot] | routed down + combine -> x.
+            // The bytes counted are those of the n_expert_used experts a token streams
+            bamd_moe_args ma; memset(&ma, 0, sizeof ma);
+            ma.x = c->x2; ma.normw = ly.ffn_norm; ma.eps = m->eps; ma.E = m->E; ma.F = m->F; ma.n_expert = m->n_expert; ma.n_used = m->n_expert_used;
+            ma.gate_inp = ly.gate_inp; ma.wg = ly.exp_g; ma.wu = ly.exp_u; ma.wd = ly.exp_d; ma.type_gu = ly.type_gu; ma.type_d = ly.type_d;
+            ma.stride_gu = ly.stride_gu; ma.stride_d = ly.stride_d; ma.sel = c->moe_sel; ma.w = c->moe_w; ma.h = c->h; ma.out = c->x;
+            if (tm) tm->begin(s, 0, 0.0, 4);
+            if (bamd_launch_moe_router(ma, s)) return fail("mixture-of-experts router launch: unsupported shape");
+            if (tm) { tm->end(s); tm->begin(s, 0, 2.0 * (double) ly.bytes_gu * m->n_expert_used, 4); }
+            if (bamd_launch_moe_gate_up(ma, m->n_cu, s)) return fail("routed gate/up launch: a matrix type without a kernel");
+            if (tm) { tm->end(s); tm->begin(s, 0, (double) ly.bytes_d * m->n_expert_used, 5); }
+            if (bamd_launch_moe_down(ma, m->n_cu, s)) return fail("routed down launch: a matrix type without a kernel");
+            if (tm) tm->end(s);
+            continue;
         }
         // 4. h = silu(Wg . a) * (Wu . a),  a = Q8_K(rms_norm(x2) * ffn_norm)  (llama.cpp:8869-8885)
         memset(&a, 0, sizeof a);
@@ -855,6 +928,7 @@ static bool ensure_attn_scratch(bamd_context * c, int T, int n_past, hipStream_t
 static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStream_t s) {
     const bamd_model * m = c->m;
     const int gq = m->H / m->Hkv;
+    if (m->n_expert > 0) return false;       // a mixture-of-experts model has no batched expert mat-muls: its micro-batches go token by token through the routed decode kernels (same bits)
     if (!(g_prefill_batch && g_attn_fused && m->hd <= 256 && (m->hd & 63) == 0 && gq >= 1 && gq <= 8)) return false;
     // every mat-mul needs a kernel: the matrix-core kernels take every K-quant at any K when the model has its side tables; the integer-dot kernel
     // takes any K-quant while 4 tokens of Q8_K activations fit the LDS (K <= 35840; tiles of 8 tokens up to K = 17920)
@@ -868,6 +942,7 @@ static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStre
 // multi-gigabyte allocation after the contexts existed, and a partial failure mixed kernel generations: ADVICE r5).  The QKV segments are the ones
 // enqueue_prefill_batch launches (qkv_segments).  All or nothing.
 static void build_prefill_aux(bamd_model * m, hipStream_t s) {
+    if (m->n_expert > 0) { m->aux_why = "a mixture-of-experts model evaluates its prompts token by token through the routed decode kernels (no batched expert mat-muls yet): no side tables are built"; return; }
     if (!g_prefill_aux) { m->aux_why = "switched off (BAMD_PREFILL_AUX=0)"; return; }
     if (!bamd_prefill_mfma_supported()) { m->aux_why = "the device refuses the matrix-core kernels' LDS size"; return; }
     struct Item { const void * w; int type, nrows, K; void ** slot; };

@@ -69,6 +69,25 @@ struct bamd_mm_args {
     const float * res;             // BAMD_EPI_ADD: residual, indexed like seg[0].out
 };
 
+// the mixture-of-experts feed-forward of one token (bamd_moe.hip): router | routed gate/up | routed down + combine
+struct bamd_moe_args {
+    const float * x;               // f32 [E]: the residual behind attention (ffn_inp)
+    const float * normw; float eps;
+    int E, F, n_expert, n_used;
+    const void * gate_inp;         // F32 wave stream [n_expert][E]
+    const void * wg, * wu, * wd;   // n_expert consecutive wave-stream matrices each: gate / up [F][E] (stride_gu bytes apart), down [E][F] (stride_d)
+    int type_gu, type_d;           // K-quant types (bamd_is_kquant)
+    size_t stride_gu, stride_d;
+    int32_t * sel; float * w;      // [n_used]: the selected experts and their normalised weights, router -> the other two launches
+    float * h;                     // [n_used][F]: silu(gate) * up of every slot, gate/up -> down
+    float * out;                   // [E] = x + sum over the slots of (down_s * w_s); must not alias x
+    int tile;                      // output row-groups per workgroup of the down launch (set by its launcher)
+};
+int  bamd_moe_shape_supported(int E, int F, int n_expert, int n_used);     // the limits the three launchers check (the loader refuses everything else by name)
+[[nodiscard]] int bamd_launch_moe_router(const bamd_moe_args & a, hipStream_t s);                // 1 = shape not supported (nothing launched), here and below
+[[nodiscard]] int bamd_launch_moe_gate_up(const bamd_moe_args & a, int n_cu, hipStream_t s);     // 1 also for a type without a K-quant stream
+[[nodiscard]] int bamd_launch_moe_down(const bamd_moe_args & a, int n_cu, hipStream_t s);
+
 #define BAMD_TL_WG 512                 /* workgroups recorded per launch (phase stamps, BAMD_TIMING builds) */
 #define BAMD_TL_WG_WORDS 24            /* per workgroup: [wave 0: 8 phases][wave 7: 8 phases][exit stamp of each of 8 waves] */
 #define BAMD_TL_SLOT_WORDS (BAMD_TL_WG * BAMD_TL_WG_WORDS)

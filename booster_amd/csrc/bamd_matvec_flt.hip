@@ -164,13 +164,9 @@ __global__ void __launch_bounds__(512) act_bf16_test_kernel(const float * x, con
     const unsigned short * a = (const unsigned short *) smem;
     for (int k = threadIdx.x; k < K; k += blockDim.x) out[k] = a[((k >> 8) << 8) + ((k >> 5) & 7) + ((k & 31) << 3)];
 }
-// a workgroup that keeps more than 64 KiB of activations in LDS (K beyond 16 128 as f32): HIP launches need the kernel's limit raised (an own-queue packet carries
-// its LDS size itself)
-template <typename KERNEL> static void flt_allow_lds(KERNEL kernel, size_t lds) {
-    if (lds > 64 * 1024 && !bamd_aql_rec) (void) hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) BAMD_LDS_CU_BYTES);
-}
+// a workgroup keeps more than 64 KiB of activations in LDS when K goes beyond 16 128 as f32: bamd_allow_lds (bamd_mv_select.h)
 void bamd_launch_act_bf16_test(const float * x, const float * nw, float eps, int K, int norm, void * out, hipStream_t s) {
-    flt_allow_lds(act_bf16_test_kernel, flt_lds_bytes(true, K));
+    bamd_allow_lds(act_bf16_test_kernel, flt_lds_bytes(true, K));
     BAMD_LAUNCH(act_bf16_test_kernel, dim3(1), dim3(512), flt_lds_bytes(true, K), s, x, nw, eps, K, norm, (unsigned short *) out);
 }
 
@@ -192,9 +188,9 @@ int bamd_launch_matvec_flt(const bamd_mv_args & a, int pro, int epi, int n_cu, h
     typedef consts<BAMD_PRO_NORM, BAMD_PRO_PLAIN> pros;
     typedef consts<BAMD_EPI_STORE, BAMD_EPI_ADD, BAMD_EPI_SILU_MUL, BAMD_EPI_ARGMAX> epis;
     if (bf) return with_const(pros(), pro, [&](auto P) -> bool { return with_const(epis(), epi, [&](auto E) -> bool {
-        flt_allow_lds(matvec_flt_kernel<true, decltype(P)::value, decltype(E)::value>, lds);
+        bamd_allow_lds(matvec_flt_kernel<true, decltype(P)::value, decltype(E)::value>, lds);
         BAMD_LAUNCH((matvec_flt_kernel<true, decltype(P)::value, decltype(E)::value>), dim3(grid), dim3(512), lds, s, a); return true; }); }) ? 0 : 1;
     return with_const(pros(), pro, [&](auto P) -> bool { return with_const(epis(), epi, [&](auto E) -> bool {
-        flt_allow_lds(matvec_flt_kernel<false, decltype(P)::value, decltype(E)::value>, lds);
+        bamd_allow_lds(matvec_flt_kernel<false, decltype(P)::value, decltype(E)::value>, lds);
         BAMD_LAUNCH((matvec_flt_kernel<false, decltype(P)::value, decltype(E)::value>), dim3(grid), dim3(512), lds, s, a); return true; }); }) ? 0 : 1;
 }

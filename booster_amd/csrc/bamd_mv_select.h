@@ -53,6 +53,10 @@ constexpr int split_fast_nbuf(int nbw, int m, bool compact) { return compact ? 2
 //   [mv_terms_off, mv_park_off)       16 arg-max slots (mode A)          | split-K kernels: their term buffers start HERE (no arg-max epilogue) and run
 //   [mv_park_off, ..)                 the gate/up kernels' park areas    | to mv_lds_terms: `row_groups` parked row-groups of nb records each
 #define BAMD_LDS_CU_BYTES (160 * 1024)                                     /* one gfx950 CU */
+// a workgroup that asks for more than 64 KiB of dynamic LDS: HIP launches need the kernel's limit raised (an own-queue packet carries its LDS size itself)
+template <typename KERNEL> static void bamd_allow_lds(KERNEL kernel, size_t lds) {
+    if (lds > 64 * 1024 && !bamd_aql_rec) (void) hipFuncSetAttribute((const void *) kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) BAMD_LDS_CU_BYTES);
+}
 constexpr size_t mv_terms_off(int nb) { return BAMD_ACT_RED_OFF(nb) + 16 * sizeof(double); }
 constexpr size_t mv_park_off(int nb) { return act_lds_bytes(nb << 8); }
 // a parked record: one float4 {d, fs, dmin, pm} per lane (1024 bytes), or compact {fs, pm} per lane + {d, dmin} per row (576 bytes)

@@ -161,6 +161,38 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_ffn_gate_up(int ty
                                    float eps, float * y) {
     return op_matvec(type, wg_raw, wu_raw, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_SILU_MUL, 0);
 }
+// the three MoE launches of a decode step (enqueue_layers) on experts packed as the loader packs them: n_expert consecutive wave-stream matrices per tensor
+extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d,
+                                                                        const void * down_exps, int E, int F, int n_expert, int n_used, const float * x, const float * norm_w,
+                                                                        float eps, float * y, int32_t * sel, float * w) {
+    if (need_device()) return 1;
+    if (!bamd_is_kquant(type_gu) || !bamd_is_kquant(type_d)) return fail("moe_ffn: expert matrices must be of a K-quant type (Q2_K .. Q6_K, IQ4_XS)");
+    if (E <= 0 || F <= 0 || E % 256 || F % 256) return fail("moe_ffn: E and F must be positive multiples of 256");
+    if (!bamd_moe_shape_supported(E, F, n_expert, n_used)) return fail("moe_ffn: n_expert must be a multiple of 8 (at most 64), 1 <= n_used <= 8, and the n_used Q8_K activation vectors of F must fit the LDS of a CU");
+    Tmp t;
+    const size_t gub = bamd_row_bytes(type_gu, E) * (size_t) F, db = bamd_row_bytes(type_d, F) * (size_t) E;             // GGUF bytes of one expert
+    const size_t gus = bamd_stream_bytes(type_gu, E, F), ds = bamd_stream_bytes(type_d, F, E), gis = bamd_stream_bytes(BAMD_F32, E, n_expert);
+    void * rg = t.up(gate_exps, gub * n_expert), * ru = t.up(up_exps, gub * n_expert), * rd = t.up(down_exps, db * n_expert), * ri = t.up(gate_inp, (size_t) n_expert * E * 4);
+    void * sg = t.up(nullptr, gus * n_expert), * su = t.up(nullptr, gus * n_expert), * sd = t.up(nullptr, ds * n_expert), * si = t.up(nullptr, gis);
+    float * dx = (float *) t.up(x, (size_t) E * 4), * dw = (float *) t.up(norm_w, (size_t) E * 4), * dy = (float *) t.up(nullptr, (size_t) E * 4), * dh = (float *) t.up(nullptr, (size_t) n_used * F * 4);
+    int32_t * dsel = (int32_t *) t.up(nullptr, 64); float * dwt = (float *) t.up(nullptr, 64);
+    if (!rg || !ru || !rd || !ri || !sg || !su || !sd || !si || !dx || !dw || !dy || !dh || !dsel || !dwt) return fail("device alloc/copy failed");
+    for (int e = 0; e < n_expert; ++e) {
+        bamd_launch_repack((const char *) rg + e * gub, (char *) sg + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack((const char *) ru + e * gub, (char *) su + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack((const char *) rd + e * db, (char *) sd + e * ds, type_d, E, F, nullptr);
+    }
+    bamd_launch_repack(ri, si, BAMD_F32, n_expert, E, nullptr);
+    bamd_moe_args a; memset(&a, 0, sizeof a);
+    a.x = dx; a.normw = dw; a.eps = eps; a.E = E; a.F = F; a.n_expert = n_expert; a.n_used = n_used; a.gate_inp = si; a.wg = sg; a.wu = su; a.wd = sd;
+    a.type_gu = type_gu; a.type_d = type_d; a.stride_gu = gus; a.stride_d = ds; a.sel = dsel; a.w = dwt; a.h = dh; a.out = dy;
+    const int cus = n_cu0();
+    if (bamd_launch_moe_router(a, nullptr) || bamd_launch_moe_gate_up(a, cus, nullptr) || bamd_launch_moe_down(a, cus, nullptr)) return fail("moe_ffn: shape without a kernel");
+    if (finish(y, dy, (size_t) E * 4)) return 1;
+    HIPC(hipMemcpy(sel, dsel, (size_t) n_used * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(w, dwt, (size_t) n_used * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" __attribute__((visibility("default"))) int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y) {
     if (need_device()) return 1;
     if (type != BAMD_F32 && type != BAMD_F16 && !bamd_has_record(type)) return fail("bad type");

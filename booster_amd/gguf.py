@@ -409,6 +409,22 @@ def q4_k_m_type_70b(name, il, n_layer=80):
     return Q5_K if (name == "attn_v" and t == Q4_K) else t
 
 
+def mixtral_q4_k_m_type(name, il, n_layer):
+    """llama.cpp's Q4_K_M recipe for an 8-expert model (llama_tensor_get_type with n_expert == 8): attn_k and attn_v Q8_0 (llama.cpp:15556-15567), attn_output
+    Q5_K (:15628-15634), ffn_down_exps Q6_K under use_more_bits, else Q4_K; output Q6_K; the router ffn_gate_inp stays F32; everything else Q4_K."""
+    if name == "ffn_gate_inp":
+        return F32
+    if name == "output":
+        return Q6_K
+    if name in ("attn_k", "attn_v"):
+        return Q8_0
+    if name == "attn_output":
+        return Q5_K
+    if name == "ffn_down_exps":
+        return q4_k_m_type("ffn_down", il, n_layer)
+    return Q4_K
+
+
 def q3_k_m_type(name, il, n_layer):
     """llama.cpp's Q3_K_M recipe for the Llama architecture (llama_tensor_get_type, llama.cpp:15435-15660): attn_v Q5_K in layers 0-1, else Q4_K;
     attn_output Q4_K; ffn_down Q5_K for il < n_layer / 16, else Q4_K (the use_more_bits cases of the recipe give Q4_K as well); output Q6_K;
@@ -437,13 +453,17 @@ def q2_k_type(name, il, n_layer, n_gqa=4):
 
 
 def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_ctx_train=8192, seed=7,
-                          type_fn=None, rope_freqs=False, embd_type=Q4_K, reuse_layers=False, vocab=None, n_split=0, rope_scaling=None, tied=False, file_type=None):
+                          type_fn=None, rope_freqs=False, embd_type=Q4_K, reuse_layers=False, vocab=None, n_split=0, rope_scaling=None, tied=False, file_type=None,
+                          n_expert=0, n_expert_used=0):
     """Write a synthetic Llama-architecture GGUF (tokenizer.ggml.model = no_vocab) with random K-quant (or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0 / IQ4_NL / IQ4_XS) blocks, or unquantised F32 / F16 / BF16 matrices
     (embd_type may be one of those too).
     reuse_layers: generate each (tensor kind, type) once and reuse the bytes in every layer (fast path for the
     multi-GB benchmark model; the arithmetic and the bytes streamed per token are unchanged).
     tied: no output.weight — the reader falls back to token_embd.weight (Llama-3.2; llama.cpp:6070-6076).
-    file_type: general.file_type (the LLAMA_FTYPE of the recipe, e.g. FTYPE_MOSTLY_IQ4_NL); None writes no such key, as before."""
+    file_type: general.file_type (the LLAMA_FTYPE of the recipe, e.g. FTYPE_MOSTLY_IQ4_NL); None writes no such key, as before.
+    n_expert > 0: a Mixtral-style mixture of experts — llama.expert_count / llama.expert_used_count, and per layer the F32 router ffn_gate_inp [E, n_expert] and
+    the merged expert tensors ffn_gate_exps / ffn_up_exps [E, F, n_expert], ffn_down_exps [F, E, n_expert] in place of ffn_gate / ffn_up / ffn_down (type_fn is
+    asked for those names)."""
     rng = np.random.default_rng(seed)
     _cache = {}
 
@@ -496,6 +516,9 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
         if "attn_factor" in rope_scaling:
             w.add_f32("llama.rope.scaling.attn_factor", float(rope_scaling["attn_factor"]))
     w.add_u32("llama.vocab_size", V)
+    if n_expert:
+        w.add_u32("llama.expert_count", n_expert)
+        w.add_u32("llama.expert_used_count", n_expert_used)
     if vocab is None:
         w.add_str("tokenizer.ggml.model", "no_vocab")
     else:
@@ -536,6 +559,12 @@ def write_synthetic_llama(path, E, H, Hkv, L, F, V, theta=500000.0, eps=1e-5, n_
             t = type_fn(nm, il)
             w.add_tensor(p + nm + ".weight", [cols, rows], t, kq(t, cols, rows, amp, nm), layer_patch(t, cols, rows, il))
         w.add_tensor(p + "ffn_norm.weight", [E], F32, norm())
+        if n_expert:
+            w.add_tensor(p + "ffn_gate_inp.weight", [E, n_expert], F32, (rng.standard_normal((n_expert, E)) * (2.0 / np.sqrt(E))).astype(np.float32))
+            for nm, rows, cols, amp in (("ffn_gate_exps", F, E, 1.5), ("ffn_up_exps", F, E, 1.5), ("ffn_down_exps", E, F, 1.0)):
+                t = type_fn(nm, il)
+                w.add_tensor(p + nm + ".weight", [cols, rows, n_expert], t, kq(t, cols, rows * n_expert, amp, nm), layer_patch(t, cols, rows * n_expert, il))
+            continue
         for nm, rows, cols, amp in (("ffn_gate", F, E, 1.5), ("ffn_up", F, E, 1.5), ("ffn_down", E, F, 1.0)):
             t = type_fn(nm, il)
             w.add_tensor(p + nm + ".weight", [cols, rows], t, kq(t, cols, rows, amp, nm), layer_patch(t, cols, rows, il))

@@ -36,6 +36,8 @@ void         bamd_model_free(bamd_model * m);                           /* llama
 int          bamd_model_n_vocab(const bamd_model * m);                  /* llama_n_vocab */
 int          bamd_model_n_embd(const bamd_model * m);                   /* llama_n_embd */
 int          bamd_model_n_layer(const bamd_model * m);                  /* llama_n_layer (whole model) */
+int          bamd_model_n_expert(const bamd_model * m);                 /* llama.expert_count (0: a dense model) */
+int          bamd_model_n_expert_used(const bamd_model * m);            /* llama.expert_used_count */
 int          bamd_model_n_ctx_train(const bamd_model * m);              /* llama_n_ctx_train */
 int64_t      bamd_model_weight_bytes(const bamd_model * m);             /* bytes of matmul weights resident on this stage */
 int64_t      bamd_model_prefill_aux_bytes(const bamd_model * m);        /* bytes of the prompt mat-muls' side tables built at load; 0 = none (prompts on the integer-dot kernel) */
@@ -243,7 +245,9 @@ long long bamd_prefill_mfma_runs(int type);
  * KV bytes read).  Entry 3: ms[3] = what an EMPTY event pair reads on that stream (to subtract per launch).
  * Arrays must hold 4 entries. */
 int bamd_profile_step(bamd_context * c, int pos, int * launches, double * ms, double * bytes);
-/* the same per launch kind — arrays of 8: [0] fused QKV, [1] attention, [2] other, [3] wo, [4] gate/up, [5] ffn_down, [6] lm_head, [7] an empty event pair */
+/* the same per launch kind — arrays of 8: [0] fused QKV, [1] attention, [2] other, [3] wo, [4] gate/up, [5] ffn_down, [6] lm_head, [7] an empty event pair.
+ * A mixture-of-experts layer counts its router and its routed gate/up launch under [4] and its routed down launch under [5], with the bytes of the
+ * expert_used_count experts a token streams */
 int bamd_profile_step_kinds(bamd_context * c, int pos, int * launches, double * ms, double * bytes);
 
 /* Micro-benchmark: `iters` back-to-back launches of one mat-vec shape on random resident weights (pro: 0 plain,
@@ -274,6 +278,12 @@ int bamd_op_mul_mat_batch(int type, const void * w_raw, int nrows, int k, const 
 /* y[nrows] = silu(Wg . a) * (Wu . a)  (llm_build_ffn LLM_FFN_SILU/LLM_FFN_PAR, llama.cpp:7960-8085) */
 int bamd_op_ffn_gate_up(int type, const void * wg_raw, const void * wu_raw, int nrows, int k, const float * x, const float * norm_w,
                         float eps, float * y);
+/* the mixture-of-experts feed-forward of one token (llm_build_moe_ffn, llama.cpp:8087-8186, behind the ffn RMSNorm) through the three launches of a
+ * decode step (router | routed gate/up | routed down + combine): gate_inp = F32 [n_expert][E]; gate_exps / up_exps = n_expert matrices [F][E] of type_gu,
+ * down_exps = n_expert matrices [E][F] of type_d, GGUF-layout blocks, expert after expert (the 3-D tensors as they lie in the file); K-quant types only.
+ * n_expert a multiple of 8, at most 64; 1 <= n_used <= 8.  y[E] = x + MoE output, sel[n_used] = the selected experts, w[n_used] = their normalised weights */
+int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
+                    int n_expert, int n_used, const float * x, const float * norm_w, float eps, float * y, int32_t * sel, float * w);
 /* one row of a GGUF matrix dequantised (ggml_compute_forward_get_rows_q, ggml.c:13186) */
 int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y);
 /* single-token attention of one layer (llm_build_kv, llama.cpp:8318): ropes q/k with the table row `pos`, stores
