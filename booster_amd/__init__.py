@@ -93,6 +93,8 @@ def lib():
         L.bamd_op_mul_mat_vec_argmax.argtypes = [ci, vp, ci, ci, vp, vp, cf, vp, ci, C.POINTER(C.c_int32)]
         L.bamd_op_ffn_gate_up.argtypes = [ci, vp, vp, ci, ci, vp, vp, cf, vp]
         L.bamd_op_moe_ffn.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, cf, vp, vp, vp]
+        L.bamd_op_moe_ffn_batch.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, ci, vp, cf, vp, vp, vp]
+        L.bamd_moe_batch_runs.argtypes = []; L.bamd_moe_batch_runs.restype = C.c_longlong
         L.bamd_op_mul_mat_batch.argtypes = [ci, vp, ci, ci, vp, ci, vp, cf, vp, vp, ci]
         L.bamd_op_get_row.argtypes = [ci, vp, ci, ci, ci, vp]
         L.bamd_op_attention.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
@@ -203,6 +205,11 @@ def attention_batch_plan(Hkv, gq, hd, T, ld, impl=0, budget_bytes=0):
 def prefill_mfma_runs(t):
     """matrix-core prompt mat-mul launches of weight type t (GGUF type id) since the library was loaded"""
     return int(lib().bamd_prefill_mfma_runs(int(t)))
+
+
+def moe_batch_runs():
+    """grouped gate/up launches of the batched mixture-of-experts feed-forward since the library was loaded: one per layer and prompt micro-batch"""
+    return int(lib().bamd_moe_batch_runs())
 
 
 def set_aql(on):
@@ -495,6 +502,19 @@ def op_moe_ffn(gate_inp, type_gu, gate_exps, up_exps, type_d, down_exps, E, F, n
     x = np.ascontiguousarray(x, np.float32); nw = np.ascontiguousarray(norm_w, np.float32)
     y = np.zeros(E, np.float32); sel = np.zeros(n_used, np.int32); w = np.zeros(n_used, np.float32)
     _chk(lib().bamd_op_moe_ffn(_p(gi), type_gu, _p(ge), _p(ue), type_d, _p(de), E, F, n_expert, n_used, _p(x), _p(nw), eps, _p(y), _p(sel), _p(w)))
+    return y, sel, w
+
+
+def op_moe_ffn_batch(gate_inp, type_gu, gate_exps, up_exps, type_d, down_exps, E, F, n_expert, n_used, x, norm_w, eps):
+    """op_moe_ffn for a micro-batch x [T, E] through the seven launches of a prompt micro-batch, bit-identical per token: (y [T, E], sel [T, n_used], w [T, n_used])"""
+    gi = np.ascontiguousarray(gate_inp, np.float32)
+    ge, ue, de = (np.ascontiguousarray(a, np.uint8) for a in (gate_exps, up_exps, down_exps))
+    x = np.ascontiguousarray(x, np.float32); nw = np.ascontiguousarray(norm_w, np.float32)
+    if x.ndim != 2 or x.shape[1] != E:
+        raise ValueError("op_moe_ffn_batch: x must be [T, E]")
+    T = x.shape[0]
+    y = np.zeros((T, E), np.float32); sel = np.zeros((T, n_used), np.int32); w = np.zeros((T, n_used), np.float32)
+    _chk(lib().bamd_op_moe_ffn_batch(_p(gi), type_gu, _p(ge), _p(ue), type_d, _p(de), E, F, n_expert, n_used, _p(x), T, _p(nw), eps, _p(y), _p(sel), _p(w)))
     return y, sel, w
 
 

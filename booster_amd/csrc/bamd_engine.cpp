@@ -182,6 +182,7 @@ struct bamd_context {
     int bcap = 0;
     float * attn_bscr = nullptr; size_t attn_bscr_bytes = 0, attn_bscr_failed = 0;   // score rows of the batched prefill attention: the matrix-core kernel beyond BAMD_AM_MAXPOS = 512 positions, every kernel beyond the LDS (ensure_attn_scratch: grow-only under the budget; absent = the VALU kernels with their rows in LDS, token by token beyond)
     float * bx = nullptr, * bx2 = nullptr, * bqkv = nullptr, * batt = nullptr, * bh = nullptr; unsigned char * bblob = nullptr, * bblob16 = nullptr;
+    float * bprod = nullptr, * bw = nullptr; int32_t * bsel = nullptr, * blists = nullptr, * btiles = nullptr;      // a mixture-of-experts model's micro-batch (bamd_moe_batch.hip)
     uint32_t * bbfr = nullptr;      // beside bblob: one range word per token of its bf16 rows (bamd_bf16_range.h)
     std::vector<void *> allocs;
 };
@@ -925,24 +926,29 @@ static bool ensure_attn_scratch(bamd_context * c, int T, int n_past, hipStream_t
     return need <= c->attn_bscr_bytes || lds_ok;
 }
 // a micro-batch of T tokens behind n_past cached positions has batched kernels for every operation (and the scratch block its attention needs: allocated here)
+#define BAMD_MOE_BATCH_MIN_T 8
 static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStream_t s) {
     const bamd_model * m = c->m;
     const int gq = m->H / m->Hkv;
-    if (m->n_expert > 0) return false;       // a mixture-of-experts model has no batched expert mat-muls: its micro-batches go token by token through the routed decode kernels (same bits)
+    // a mixture-of-experts model: the grouped expert mat-muls (bamd_moe_batch.hip) want four Q8_K images of both E and F in the LDS; otherwise its micro-batches go
+    // token by token through the routed decode kernels (same bits).  So do its prompts of fewer than 8 tokens: seven launches per layer for a tile or two of pairs
+    // measured slower than the routed launches at 2 and 4 tokens and faster from 8 on (profiles/moe_prefill.txt, the 8x7B shape)
+    if (m->n_expert > 0 && (T < BAMD_MOE_BATCH_MIN_T || !bamd_moe_batch_supported(m->E, m->F, m->n_expert, m->n_expert_used))) return false;
     if (!(g_prefill_batch && g_attn_fused && m->hd <= 256 && (m->hd & 63) == 0 && gq >= 1 && gq <= 8)) return false;
     // every mat-mul needs a kernel: the matrix-core kernels take every K-quant at any K when the model has its side tables; the integer-dot kernel
     // takes any K-quant while 4 tokens of Q8_K activations fit the LDS (K <= 35840; tiles of 8 tokens up to K = 17920)
     // (the unquantised family: its VALU kernel takes any K the load accepted)
     auto ok = [&](int type, int K) { return bamd_is_flt(type) || (g_prefill_mfma && m->aux_ok && bamd_prefill_mfma_type(type)) || 4 * bamd_blob_bytes(K) <= 160 * 1024; };
     for (const DevLayer & ly : m->layers)
-        if (!ok(ly.wq.type, m->E) || !ok(ly.wk.type, m->E) || !ok(ly.wv.type, m->E) || !ok(ly.wo.type, m->E) || !ok(ly.wg.type, m->E) || !ok(ly.wu.type, m->E) || !ok(ly.wd.type, m->F)) return false;
+        if (!ok(ly.wq.type, m->E) || !ok(ly.wk.type, m->E) || !ok(ly.wv.type, m->E) || !ok(ly.wo.type, m->E) ||
+            (m->n_expert == 0 && (!ok(ly.wg.type, m->E) || !ok(ly.wu.type, m->E) || !ok(ly.wd.type, m->F)))) return false;
     return ensure_attn_scratch(c, T, n_past, s);
 }
 // prefill side tables of every layer matrix (bamd_prefill2.hip), built at model load (round 6; round 5 built them lazily inside the first batched evaluation — a
 // multi-gigabyte allocation after the contexts existed, and a partial failure mixed kernel generations: ADVICE r5).  The QKV segments are the ones
 // enqueue_prefill_batch launches (qkv_segments).  All or nothing.
 static void build_prefill_aux(bamd_model * m, hipStream_t s) {
-    if (m->n_expert > 0) { m->aux_why = "a mixture-of-experts model evaluates its prompts token by token through the routed decode kernels (no batched expert mat-muls yet): no side tables are built"; return; }
+    if (m->n_expert > 0) { m->aux_why = "a mixture-of-experts model batches its expert mat-muls on the integer-dot kernel, which has no matrix-core variant, and its QKV / wo mat-muls stay on the integer-dot kernel too: no side tables are built"; return; }
     if (!g_prefill_aux) { m->aux_why = "switched off (BAMD_PREFILL_AUX=0)"; return; }
     if (!bamd_prefill_mfma_supported()) { m->aux_why = "the device refuses the matrix-core kernels' LDS size"; return; }
     struct Item { const void * w; int type, nrows, K; void ** slot; };
@@ -995,16 +1001,21 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
 static int ensure_batch_buffers(bamd_context * c) {
     if (c->bcap) return 0;
     bamd_model * m = c->m;
-    const size_t T = BAMD_PREFILL_CAP, Ekv = (size_t) m->Hkv * m->hd;
+    const size_t T = BAMD_PREFILL_CAP, Ekv = (size_t) m->Hkv * m->hd, NU = (size_t) std::max(m->n_expert_used, 1);
+    const size_t moe_blob = m->n_expert > 0 ? bamd_moe_batch_blob_bytes((int) T, m->E, m->F, m->n_expert_used) : 0;
     size_t flt_bytes = 0;
     for (const DevLayer & ly : m->layers)
         for (const DevMat * d : { &ly.wq, &ly.wk, &ly.wv, &ly.wo, &ly.wg, &ly.wu, &ly.wd }) flt_bytes = std::max(flt_bytes, bamd_flt_act_bytes(bamd_act_form_of(d->type), d->K));
     if (dev_alloc(c->allocs, (void **) &c->bx, T * m->E * 4) || dev_alloc(c->allocs, (void **) &c->bx2, T * m->E * 4) ||
         dev_alloc(c->allocs, (void **) &c->bqkv, T * (m->E + 2 * Ekv) * 4) || dev_alloc(c->allocs, (void **) &c->batt, T * m->E * 4) ||
-        dev_alloc(c->allocs, (void **) &c->bh, T * m->F * 4) ||
-        dev_alloc(c->allocs, (void **) &c->bblob, T * std::max(bamd_blob_bytes(std::max(m->E, m->F)), flt_bytes)) ||      // (an unquantised matrix takes its activations as f32 / bf16 rows)
+        dev_alloc(c->allocs, (void **) &c->bh, T * NU * m->F * 4) ||       // (a mixture-of-experts model: a row of h and a Q8_K image of it per (token, slot) pair)
+        dev_alloc(c->allocs, (void **) &c->bblob, std::max(T * std::max(bamd_blob_bytes(std::max(m->E, m->F)), flt_bytes), moe_blob)) ||      // (an unquantised matrix takes its activations as f32 / bf16 rows)
         dev_alloc(c->allocs, (void **) &c->bbfr, T * 4) ||
         dev_alloc(c->allocs, (void **) &c->bblob16, T * bamd_blob16_bytes(std::max(m->E, m->F)))) return 1;     // (one stride for every form: the K-quant record's 608 B hold the 544 B of the Q8_0 form and the 576 B of the Q8_1 form)
+    // the grouped expert mat-muls' products, selections, weights, pair lists and tile table (bamd_moe_batch.hip)
+    if (m->n_expert > 0 && (dev_alloc(c->allocs, (void **) &c->bprod, T * NU * m->E * 4) || dev_alloc(c->allocs, (void **) &c->bsel, T * NU * 4) ||
+                            dev_alloc(c->allocs, (void **) &c->bw, T * NU * 4) || dev_alloc(c->allocs, (void **) &c->blists, T * NU * 4) ||
+                            dev_alloc(c->allocs, (void **) &c->btiles, bamd_moe_batch_tiles_bytes((int) T, m->n_expert, m->n_expert_used)))) return 1;
     c->bcap = (int) T;
     return 0;
 }
@@ -1090,6 +1101,16 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
         memset(&a, 0, sizeof a);
         seg_of(a.seg[0], ly.wo, c->bx2); a.nseg = 1; a.blob = c->bblob; a.K = E; a.T = T; a.ldo = E; a.res = c->bx;
         { const void * ax[3] = { ly.aux_o, nullptr, nullptr }; if (batch_mm(c, a, BAMD_EPI_ADD, s, ax, ly.wo.bf16_range)) return fail("batched mat-mul: unsupported shape"); }
+        if (m->n_expert > 0) {
+            // x = x2 + the mixture-of-experts feed-forward of every token: router | grouping | Q8_K | grouped gate/up | Q8_K of h | grouped down | combine
+            bamd_moe_batch_args ma; memset(&ma, 0, sizeof ma);
+            ma.m.x = c->bx2; ma.m.normw = ly.ffn_norm; ma.m.eps = m->eps; ma.m.E = E; ma.m.F = F; ma.m.n_expert = m->n_expert; ma.m.n_used = m->n_expert_used;
+            ma.m.gate_inp = ly.gate_inp; ma.m.wg = ly.exp_g; ma.m.wu = ly.exp_u; ma.m.wd = ly.exp_d; ma.m.type_gu = ly.type_gu; ma.m.type_d = ly.type_d;
+            ma.m.stride_gu = ly.stride_gu; ma.m.stride_d = ly.stride_d; ma.m.sel = c->bsel; ma.m.w = c->bw; ma.m.h = c->bh; ma.m.out = c->bx;
+            ma.T = T; ma.prod = c->bprod; ma.lists = c->blists; ma.tiles = c->btiles; ma.blob = c->bblob;
+            if (bamd_launch_moe_ffn_batch(ma, m->n_cu, s)) return fail("batched mixture-of-experts feed-forward: unsupported shape");
+            continue;
+        }
         // h = silu(Wg . a) * (Wu . a)
         bamd_launch_quantize_batch(c->bx2, ly.ffn_norm, m->eps, E, T, c->bblob, c->bblob16, s, bamd_act_form_of(ly.wg.type), c->bbfr);
         memset(&a, 0, sizeof a);

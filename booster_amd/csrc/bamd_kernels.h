@@ -87,6 +87,21 @@ int  bamd_moe_shape_supported(int E, int F, int n_expert, int n_used);     // th
 [[nodiscard]] int bamd_launch_moe_router(const bamd_moe_args & a, hipStream_t s);                // 1 = shape not supported (nothing launched), here and below
 [[nodiscard]] int bamd_launch_moe_gate_up(const bamd_moe_args & a, int n_cu, hipStream_t s);     // 1 also for a type without a K-quant stream
 [[nodiscard]] int bamd_launch_moe_down(const bamd_moe_args & a, int n_cu, hipStream_t s);
+// the same feed-forward for a micro-batch of T tokens (bamd_moe_batch.hip): batched router | grouping | Q8_K of the normed rows | grouped gate/up | Q8_K of h |
+// grouped down | combine.  A pair is (token t, slot s), its id t * n_used + s
+struct bamd_moe_batch_args {
+    bamd_moe_args m;               // as above with x / out [T][E], sel / w [T][n_used], h [T * n_used][F] (row = pair id); tile unused
+    int T;
+    float * prod;                  // [T * n_used][E]: every pair's down output times its weight, grouped down -> combine
+    int32_t * lists;               // [T * n_used]: the pair ids expert after expert, ascending within an expert
+    int32_t * tiles;               // bamd_moe_batch_tiles_bytes: word 0 = tiles in use, from word 4 on {expert, first entry of lists, pairs <= tt, 0} per tile
+    uint8_t * blob;                // bamd_moe_batch_blob_bytes: the Q8_K images of the T normed rows, then of the T * n_used rows of h
+    int tt;                        // pairs per tile (set by the launcher)
+};
+int    bamd_moe_batch_supported(int E, int F, int n_expert, int n_used);      // bamd_moe_shape_supported, and four Q8_K images of the longer of E and F fit the LDS of a CU
+size_t bamd_moe_batch_tiles_bytes(int T, int n_expert, int n_used);
+size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used);
+[[nodiscard]] int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a, int n_cu, hipStream_t s);      // 1 = shape or type without a kernel (nothing launched)
 
 #define BAMD_TL_WG 512                 /* workgroups recorded per launch (phase stamps, BAMD_TIMING builds) */
 #define BAMD_TL_WG_WORDS 24            /* per workgroup: [wave 0: 8 phases][wave 7: 8 phases][exit stamp of each of 8 waves] */

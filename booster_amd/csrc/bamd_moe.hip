@@ -12,58 +12,17 @@
 //   ggml_compute_forward_argsort_f32        ggml/src/ggml.c:15185-15199: an exchange sort, not stable — the loops themselves are restated (router_select)
 //   ggml_sum_rows / ggml_div / ggml_mul     f64 sum rounded to f32, f32 division; every expert output times its weight, rounded, then added left to right
 //   ggml_compute_forward_mul_mat_id         ggml/src/ggml.c:12494: one vec_dot of a whole row per output, each slot's activations quantised on their own
-#include "bamd_matvec_core.h"
-#include "bamd_flt_device.h"
+#include "bamd_moe_device.h"
 
-// LDS of the router behind the f32 activation vector [E] and the 16 reduction slots of flt_act: logits | probabilities in sort order | expert ids
-#define BAMD_MOE_MAX_EXPERT 64
-#define BAMD_MOE_MAX_USED 8
-constexpr size_t moe_router_lds(int E) { return (size_t) E * 4 + 16 * sizeof(double) + 3 * BAMD_MOE_MAX_EXPERT * 4; }
 // LDS of the down launch: one Q8_K blob (q8 | S | yd) per slot, then the weighted outputs [n_used][tile * 8]
 constexpr size_t moe_down_slot_bytes(int F) { return BAMD_ACT_RED_OFF(F >> 8); }
 constexpr size_t moe_down_lds(int F, int n_used, int tile) { return (size_t) n_used * moe_down_slot_bytes(F) + (size_t) n_used * tile * 8 * 4; }
 #define BAMD_MOE_DOWN_TILE_MAX 8
 
-__device__ __forceinline__ int moe_expert_of(const int32_t * sel, int slot, int n_expert) {
-    int e = __builtin_amdgcn_readfirstlane(ik_ld(sel + slot));
-    e = e < 0 ? 0 : e; return e < n_expert ? e : n_expert - 1;      // the router only writes ids below n_expert; an id is an address, so it is bounded here too
-}
-
 // ===========================================================================================================
 // 1. router
 // ===========================================================================================================
-// softmax over n logits (n % 8 == 0), the first n_used entries of the descending exchange sort, and their normalised weights: ONE lane, in the reference's order
-__device__ __forceinline__ void router_select(const float * lg, float * pv, int * idx, int n, int n_used, int32_t * sel, float * w) {
-    float mx = -INFINITY;
-    for (int i = 0; i < n; ++i) mx = mx > lg[i] ? mx : lg[i];                // ggml_vec_max_f32
-    double sum = 0.0;
-    for (int i = 0; i < n; i += 8) {                                         // ggml_vec_soft_max_f32, AVX2 branch
-        float v[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) { v[t] = v_expf(lg[i + t] - mx); pv[i + t] = v[t]; }
-        const float a0 = v[0] + v[4], a1 = v[1] + v[5], a2 = v[2] + v[6], a3 = v[3] + v[7];
-        const float b0 = a0 + a2, b1 = a1 + a3;
-        sum += (double) (b0 + b1);
-    }
-    const float sc = (float) (1.0 / sum);                                     // ggml.c:13768-13769: 1.0 / sum in f64, ggml_vec_scale_f32 takes it as f32
-    for (int i = 0; i < n; ++i) { pv[i] = pv[i] * sc; idx[i] = i; }
-    // ggml.c:15190-15199 with order DESC: for j, for k > j: if (p[idx[j]] < p[idx[k]]) swap(idx[j], idx[k]).  pv[] holds p[idx[]] and is swapped along, entry j stays
-    // in registers over its inner loop.  Outer iteration j leaves entry j final and touches no entry below j: the first n_used iterations give the first n_used
-    // entries of the whole sort (ggml_top_k is a view of them), ties included
-    for (int j = 0; j < n_used; ++j) {
-        float cv = pv[j]; int ci = idx[j];
-        for (int k = j + 1; k < n; ++k) {
-            const float kv = pv[k];
-            if (cv < kv) { const int ki = idx[k]; idx[k] = ci; pv[k] = cv; ci = ki; cv = kv; }
-        }
-        idx[j] = ci; pv[j] = cv;
-    }
-    double ws = 0.0;                                                          // ggml_sum_rows: ggml_vec_sum_f32 in f64, stored as f32
-    for (int s = 0; s < n_used; ++s) ws += (double) pv[s];
-    const float wsum = (float) ws;
-    for (int s = 0; s < n_used; ++s) { ik_st(sel + s, (int32_t) idx[s]); ik_st(w + s, pv[s] / wsum); }
-}
-
+// (the one-lane selection behind it, router_select: bamd_moe_device.h, shared with the batched router)
 __global__ void __launch_bounds__(512) moe_router_kernel(bamd_moe_args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int K = a.E, lane = threadIdx.x & 63, wave = wave_id();

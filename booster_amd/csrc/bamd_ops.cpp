@@ -193,6 +193,42 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn(const floa
     HIPC(hipMemcpy(w, dwt, (size_t) n_used * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+// the seven MoE launches of a prompt micro-batch (enqueue_prefill_batch) on experts packed the same way: x [T][E] -> y [T][E], sel / w [T][n_used]
+extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn_batch(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d,
+                                                                              const void * down_exps, int E, int F, int n_expert, int n_used, const float * x, int T,
+                                                                              const float * norm_w, float eps, float * y, int32_t * sel, float * w) {
+    if (need_device()) return 1;
+    if (!bamd_is_kquant(type_gu) || !bamd_is_kquant(type_d)) return fail("moe_ffn_batch: expert matrices must be of a K-quant type (Q2_K .. Q6_K, IQ4_XS)");
+    if (E <= 0 || F <= 0 || E % 256 || F % 256) return fail("moe_ffn_batch: E and F must be positive multiples of 256");
+    if (T < 1 || T > BAMD_PREFILL_CAP) return fail("moe_ffn_batch: 1 <= T <= 512");
+    if (!bamd_moe_batch_supported(E, F, n_expert, n_used)) return fail("moe_ffn_batch: the limits of moe_ffn, and four Q8_K activation vectors of the longer of E and F must fit the LDS of a CU");
+    Tmp t;
+    const size_t gub = bamd_row_bytes(type_gu, E) * (size_t) F, db = bamd_row_bytes(type_d, F) * (size_t) E;             // GGUF bytes of one expert
+    const size_t gus = bamd_stream_bytes(type_gu, E, F), ds = bamd_stream_bytes(type_d, F, E), gis = bamd_stream_bytes(BAMD_F32, E, n_expert);
+    const size_t np = (size_t) T * n_used;
+    void * rg = t.up(gate_exps, gub * n_expert), * ru = t.up(up_exps, gub * n_expert), * rd = t.up(down_exps, db * n_expert), * ri = t.up(gate_inp, (size_t) n_expert * E * 4);
+    void * sg = t.up(nullptr, gus * n_expert), * su = t.up(nullptr, gus * n_expert), * sd = t.up(nullptr, ds * n_expert), * si = t.up(nullptr, gis);
+    float * dx = (float *) t.up(x, (size_t) T * E * 4), * dw = (float *) t.up(norm_w, (size_t) E * 4), * dy = (float *) t.up(nullptr, (size_t) T * E * 4);
+    float * dh = (float *) t.up(nullptr, np * F * 4), * dprod = (float *) t.up(nullptr, np * E * 4), * dwt = (float *) t.up(nullptr, np * 4);
+    int32_t * dsel = (int32_t *) t.up(nullptr, np * 4), * lists = (int32_t *) t.up(nullptr, np * 4), * tiles = (int32_t *) t.up(nullptr, bamd_moe_batch_tiles_bytes(T, n_expert, n_used));
+    void * blob = t.up(nullptr, bamd_moe_batch_blob_bytes(T, E, F, n_used));
+    if (!rg || !ru || !rd || !ri || !sg || !su || !sd || !si || !dx || !dw || !dy || !dh || !dprod || !dwt || !dsel || !lists || !tiles || !blob) return fail("device alloc/copy failed");
+    for (int e = 0; e < n_expert; ++e) {
+        bamd_launch_repack((const char *) rg + e * gub, (char *) sg + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack((const char *) ru + e * gub, (char *) su + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack((const char *) rd + e * db, (char *) sd + e * ds, type_d, E, F, nullptr);
+    }
+    bamd_launch_repack(ri, si, BAMD_F32, n_expert, E, nullptr);
+    bamd_moe_batch_args a; memset(&a, 0, sizeof a);
+    a.m.x = dx; a.m.normw = dw; a.m.eps = eps; a.m.E = E; a.m.F = F; a.m.n_expert = n_expert; a.m.n_used = n_used; a.m.gate_inp = si; a.m.wg = sg; a.m.wu = su; a.m.wd = sd;
+    a.m.type_gu = type_gu; a.m.type_d = type_d; a.m.stride_gu = gus; a.m.stride_d = ds; a.m.sel = dsel; a.m.w = dwt; a.m.h = dh; a.m.out = dy;
+    a.T = T; a.prod = dprod; a.lists = lists; a.tiles = tiles; a.blob = (uint8_t *) blob;
+    if (bamd_launch_moe_ffn_batch(a, n_cu0(), nullptr)) return fail("moe_ffn_batch: shape without a kernel");
+    if (finish(y, dy, (size_t) T * E * 4)) return 1;
+    HIPC(hipMemcpy(sel, dsel, np * 4, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(w, dwt, np * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" __attribute__((visibility("default"))) int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y) {
     if (need_device()) return 1;
     if (type != BAMD_F32 && type != BAMD_F16 && !bamd_has_record(type)) return fail("bad type");

@@ -237,6 +237,8 @@ unsigned long long bamd_prefill_bf16_fallback_tiles(void);
 void bamd_set_prefill_xs(int on);
 /* matrix-core prompt mat-mul launches of weight type `type` (GGUF type id: 0 F32, 1 F16, 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K .. 14 Q6_K, 20 IQ4_NL, 23 IQ4_XS, 30 BF16) since the library was loaded */
 long long bamd_prefill_mfma_runs(int type);
+/* grouped gate/up launches of the batched mixture-of-experts feed-forward (one per layer and prompt micro-batch of a model with experts) since the library was loaded */
+long long bamd_moe_batch_runs(void);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* One eager single-token step at position `pos` with a HIP-event pair around every kernel launch.
@@ -284,6 +286,11 @@ int bamd_op_ffn_gate_up(int type, const void * wg_raw, const void * wu_raw, int 
  * n_expert a multiple of 8, at most 64; 1 <= n_used <= 8.  y[E] = x + MoE output, sel[n_used] = the selected experts, w[n_used] = their normalised weights */
 int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
                     int n_expert, int n_used, const float * x, const float * norm_w, float eps, float * y, int32_t * sel, float * w);
+/* the same for a micro-batch of T tokens (1 <= T <= 512) through the seven launches of a prompt micro-batch (batched router | grouping | Q8_K | grouped gate/up |
+ * Q8_K of h | grouped down | combine), bit-identical per token to bamd_op_moe_ffn: x [T][E], y [T][E], sel / w [T][n_used].  Also: four Q8_K activation
+ * vectors of the longer of E and F must fit the LDS of a CU (E, F <= 35840) */
+int bamd_op_moe_ffn_batch(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
+                          int n_expert, int n_used, const float * x, int T, const float * norm_w, float eps, float * y, int32_t * sel, float * w);
 /* one row of a GGUF matrix dequantised (ggml_compute_forward_get_rows_q, ggml.c:13186) */
 int bamd_op_get_row(int type, const void * w_raw, int nrows, int k, int row, float * y);
 /* single-token attention of one layer (llm_build_kv, llama.cpp:8318): ropes q/k with the table row `pos`, stores
