@@ -95,6 +95,7 @@ def lib():
         L.bamd_op_moe_ffn.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, cf, vp, vp, vp]
         L.bamd_op_moe_ffn_batch.argtypes = [vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, ci, vp, cf, vp, vp, vp]
         L.bamd_moe_batch_runs.argtypes = []; L.bamd_moe_batch_runs.restype = C.c_longlong
+        L.bamd_moe_batch_mfma_runs.argtypes = []; L.bamd_moe_batch_mfma_runs.restype = C.c_longlong
         L.bamd_op_mul_mat_batch.argtypes = [ci, vp, ci, ci, vp, ci, vp, cf, vp, vp, ci]
         L.bamd_op_get_row.argtypes = [ci, vp, ci, ci, ci, vp]
         L.bamd_op_attention.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
@@ -210,6 +211,18 @@ def prefill_mfma_runs(t):
 def moe_batch_runs():
     """grouped gate/up launches of the batched mixture-of-experts feed-forward since the library was loaded: one per layer and prompt micro-batch"""
     return int(lib().bamd_moe_batch_runs())
+
+
+def set_prefill_moe(on):
+    """True: mixture-of-experts models loaded from now on build side tables (QKV, wo and one per Q4_K / Q5_K / Q6_K expert matrix) and run the grouped expert
+    mat-muls of a batched prompt on the matrix cores; False (default, also env BAMD_PREFILL_MOE): on the integer-dot kernel, without tables.  The 8-expert
+    recipes' Q8_0 attn_k / attn_v need set_prefill_q0 as well.  Same bits either way."""
+    lib().bamd_set_prefill_moe(int(bool(on)))
+
+
+def moe_batch_mfma_runs():
+    """grouped gate/up launches of the matrix-core mixture-of-experts path since the library was loaded (moe_batch_runs counts the integer-dot ones only)"""
+    return int(lib().bamd_moe_batch_mfma_runs())
 
 
 def set_aql(on):

@@ -948,19 +948,32 @@ static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStre
 // multi-gigabyte allocation after the contexts existed, and a partial failure mixed kernel generations: ADVICE r5).  The QKV segments are the ones
 // enqueue_prefill_batch launches (qkv_segments).  All or nothing.
 static void build_prefill_aux(bamd_model * m, hipStream_t s) {
-    if (m->n_expert > 0) { m->aux_why = "a mixture-of-experts model batches its expert mat-muls on the integer-dot kernel, which has no matrix-core variant, and its QKV / wo mat-muls stay on the integer-dot kernel too: no side tables are built"; return; }
+    if (m->n_expert > 0 && !bamd_prefill_moe_on()) { m->aux_why = "a mixture-of-experts model batches its expert mat-muls on the integer-dot kernel, which has no matrix-core variant, and its QKV / wo mat-muls stay on the integer-dot kernel too: no side tables are built"; return; }
     if (!g_prefill_aux) { m->aux_why = "switched off (BAMD_PREFILL_AUX=0)"; return; }
     if (!bamd_prefill_mfma_supported()) { m->aux_why = "the device refuses the matrix-core kernels' LDS size"; return; }
-    struct Item { const void * w; int type, nrows, K; void ** slot; };
+    struct Item { const void * w; int type, nrows, K; void ** slot; int count; size_t wstride; };      // count tables, one per matrix w + i * wstride, in one allocation
     std::vector<Item> items;
     for (DevLayer & ly : m->layers) {
         bamd_mv_seg seg[3]; int rows[3];
         const int n = qkv_segments(ly, nullptr, seg, rows);
-        for (int i = 0; i < n; ++i) items.push_back({ seg[i].w, seg[i].type, rows[i], m->E, &ly.aux_qkv[i] });
-        items.push_back({ ly.wo.stream, ly.wo.type, ly.wo.nrows_pad, m->E, &ly.aux_o });
-        items.push_back({ ly.wg.stream, ly.wg.type, ly.wg.nrows_pad, m->E, &ly.aux_g });
-        items.push_back({ ly.wu.stream, ly.wu.type, ly.wu.nrows_pad, m->E, &ly.aux_u });
-        items.push_back({ ly.wd.stream, ly.wd.type, ly.wd.nrows_pad, m->F, &ly.aux_d });
+        for (int i = 0; i < n; ++i) items.push_back({ seg[i].w, seg[i].type, rows[i], m->E, &ly.aux_qkv[i], 1, 0 });
+        items.push_back({ ly.wo.stream, ly.wo.type, ly.wo.nrows_pad, m->E, &ly.aux_o, 1, 0 });
+        if (m->n_expert > 0) {
+            // BAMD_PREFILL_MOE: a table per expert for the grouped matrix-core mat-muls (bamd_moe_batch_mfma.hip), which take Q4_K / Q5_K / Q6_K experts
+            for (int t : { ly.type_gu, ly.type_d })
+                if (t != BAMD_Q4_K && t != BAMD_Q5_K && t != BAMD_Q6_K) {
+                    m->aux_why = std::string("the model holds ") + (t == BAMD_Q2_K ? "Q2_K" : t == BAMD_Q3_K ? "Q3_K" : "IQ4_XS") + " expert matrices: the grouped matrix-core mat-muls (BAMD_PREFILL_MOE) take Q4_K / Q5_K / Q6_K experts, and "
+                                 "side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel";
+                    return;
+                }
+            items.push_back({ ly.exp_g, ly.type_gu, m->F, m->E, &ly.aux_g, m->n_expert, ly.stride_gu });
+            items.push_back({ ly.exp_u, ly.type_gu, m->F, m->E, &ly.aux_u, m->n_expert, ly.stride_gu });
+            items.push_back({ ly.exp_d, ly.type_d, m->E, m->F, &ly.aux_d, m->n_expert, ly.stride_d });
+            continue;
+        }
+        items.push_back({ ly.wg.stream, ly.wg.type, ly.wg.nrows_pad, m->E, &ly.aux_g, 1, 0 });
+        items.push_back({ ly.wu.stream, ly.wu.type, ly.wu.nrows_pad, m->E, &ly.aux_u, 1, 0 });
+        items.push_back({ ly.wd.stream, ly.wd.type, ly.wd.nrows_pad, m->F, &ly.aux_d, 1, 0 });
     }
     // F32 / F16 matrices with BAMD_PREFILL_FLT on, BF16 ones with BAMD_PREFILL_BF16 on: their matrix-core kernel has no side table (bamd_batch_mm reads the switch at each launch), so they ask for
     // nothing here; a model of such matrices only has nothing to build and nothing to report
@@ -971,7 +984,7 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     for (const Item & it : items) {
         const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K);
         if (!b) { m->aux_why = bamd_prefill_reason(it.type); return; }      // (the sentences: bamd_prefill_family.cpp)
-        need += b + 4096;
+        need += b * it.count + 4096;
     }
     if (items.empty()) return;
     size_t free_b = 0, total_b = 0;
@@ -985,14 +998,15 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     std::vector<void *> got;
     for (const Item & it : items) {
         void * p = nullptr;
-        if (hipMalloc(&p, bamd_prefill_aux_bytes(it.type, it.nrows, it.K)) != hipSuccess) {
+        const size_t b = bamd_prefill_aux_bytes(it.type, it.nrows, it.K);
+        if (hipMalloc(&p, b * it.count) != hipSuccess) {
             (void) hipGetLastError();
             for (void * q : got) hipFree(q);
             for (const Item & jt : items) *jt.slot = nullptr;
             m->aux_why = "allocation failed"; m->aux_bytes = 0; return;
         }
-        got.push_back(p); *it.slot = p; m->aux_bytes += (int64_t) bamd_prefill_aux_bytes(it.type, it.nrows, it.K);
-        bamd_launch_prefill_aux(it.w, it.type, it.nrows, it.K, p, s);
+        got.push_back(p); *it.slot = p; m->aux_bytes += (int64_t) (b * it.count);
+        for (int i = 0; i < it.count; ++i) bamd_launch_prefill_aux((const char *) it.w + i * it.wstride, it.type, it.nrows, it.K, (char *) p + i * b, s);
     }
     for (void * q : got) m->allocs.push_back(q);
     hipStreamSynchronize(s);
@@ -1003,6 +1017,7 @@ static int ensure_batch_buffers(bamd_context * c) {
     bamd_model * m = c->m;
     const size_t T = BAMD_PREFILL_CAP, Ekv = (size_t) m->Hkv * m->hd, NU = (size_t) std::max(m->n_expert_used, 1);
     const size_t moe_blob = m->n_expert > 0 ? bamd_moe_batch_blob_bytes((int) T, m->E, m->F, m->n_expert_used) : 0;
+    const size_t moe_blob16 = m->n_expert > 0 && m->aux_ok ? bamd_moe_batch_blob16_bytes((int) T, m->E, m->F, m->n_expert_used) : 0;      // (a model with tables: the f16 records of the pairs' rows of h)
     size_t flt_bytes = 0;
     for (const DevLayer & ly : m->layers)
         for (const DevMat * d : { &ly.wq, &ly.wk, &ly.wv, &ly.wo, &ly.wg, &ly.wu, &ly.wd }) flt_bytes = std::max(flt_bytes, bamd_flt_act_bytes(bamd_act_form_of(d->type), d->K));
@@ -1011,7 +1026,7 @@ static int ensure_batch_buffers(bamd_context * c) {
         dev_alloc(c->allocs, (void **) &c->bh, T * NU * m->F * 4) ||       // (a mixture-of-experts model: a row of h and a Q8_K image of it per (token, slot) pair)
         dev_alloc(c->allocs, (void **) &c->bblob, std::max(T * std::max(bamd_blob_bytes(std::max(m->E, m->F)), flt_bytes), moe_blob)) ||      // (an unquantised matrix takes its activations as f32 / bf16 rows)
         dev_alloc(c->allocs, (void **) &c->bbfr, T * 4) ||
-        dev_alloc(c->allocs, (void **) &c->bblob16, T * bamd_blob16_bytes(std::max(m->E, m->F)))) return 1;     // (one stride for every form: the K-quant record's 608 B hold the 544 B of the Q8_0 form and the 576 B of the Q8_1 form)
+        dev_alloc(c->allocs, (void **) &c->bblob16, std::max(T * bamd_blob16_bytes(std::max(m->E, m->F)), moe_blob16))) return 1;     // (one stride for every form: the K-quant record's 608 B hold the 544 B of the Q8_0 form and the 576 B of the Q8_1 form)
     // the grouped expert mat-muls' products, selections, weights, pair lists and tile table (bamd_moe_batch.hip)
     if (m->n_expert > 0 && (dev_alloc(c->allocs, (void **) &c->bprod, T * NU * m->E * 4) || dev_alloc(c->allocs, (void **) &c->bsel, T * NU * 4) ||
                             dev_alloc(c->allocs, (void **) &c->bw, T * NU * 4) || dev_alloc(c->allocs, (void **) &c->blists, T * NU * 4) ||
@@ -1108,6 +1123,10 @@ static int enqueue_prefill_batch(bamd_context * c, int T, int n_past, hipStream_
             ma.m.gate_inp = ly.gate_inp; ma.m.wg = ly.exp_g; ma.m.wu = ly.exp_u; ma.m.wd = ly.exp_d; ma.m.type_gu = ly.type_gu; ma.m.type_d = ly.type_d;
             ma.m.stride_gu = ly.stride_gu; ma.m.stride_d = ly.stride_d; ma.m.sel = c->bsel; ma.m.w = c->bw; ma.m.h = c->bh; ma.m.out = c->bx;
             ma.T = T; ma.prod = c->bprod; ma.lists = c->blists; ma.tiles = c->btiles; ma.blob = c->bblob;
+            if (g_prefill_mfma && m->aux_ok) {      // per-expert side tables (build_prefill_aux): the grouped mat-muls on the matrix cores while BAMD_PREFILL_MOE is on
+                ma.blob16 = c->bblob16; ma.aux_g = ly.aux_g; ma.aux_u = ly.aux_u; ma.aux_d = ly.aux_d;
+                ma.aux_stride_gu = bamd_prefill_aux_bytes(ly.type_gu, F, E); ma.aux_stride_d = bamd_prefill_aux_bytes(ly.type_d, E, F);
+            }
             if (bamd_launch_moe_ffn_batch(ma, m->n_cu, s)) return fail("batched mixture-of-experts feed-forward: unsupported shape");
             continue;
         }

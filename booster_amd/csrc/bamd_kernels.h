@@ -89,7 +89,7 @@ int  bamd_moe_shape_supported(int E, int F, int n_expert, int n_used);     // th
 [[nodiscard]] int bamd_launch_moe_down(const bamd_moe_args & a, int n_cu, hipStream_t s);
 // the same feed-forward for a micro-batch of T tokens (bamd_moe_batch.hip): batched router | grouping | Q8_K of the normed rows | grouped gate/up | Q8_K of h |
 // grouped down | combine.  A pair is (token t, slot s), its id t * n_used + s
-struct bamd_moe_batch_args {
+struct bamd_moe_group_args {       // what the grouped integer-dot kernels take as their kernel argument
     bamd_moe_args m;               // as above with x / out [T][E], sel / w [T][n_used], h [T * n_used][F] (row = pair id); tile unused
     int T;
     float * prod;                  // [T * n_used][E]: every pair's down output times its weight, grouped down -> combine
@@ -98,6 +98,17 @@ struct bamd_moe_batch_args {
     uint8_t * blob;                // bamd_moe_batch_blob_bytes: the Q8_K images of the T normed rows, then of the T * n_used rows of h
     int tt;                        // pairs per tile (set by the launcher)
 };
+struct bamd_moe_batch_args : bamd_moe_group_args {
+    // the matrix-core path (bamd_moe_batch_mfma.hip; taken while all four are set and BAMD_PREFILL_MOE is on): the f16 records of the same rows as blob
+    // (bamd_moe_batch_blob16_bytes) and per tensor n_expert side tables of bamd_prefill_aux_bytes(type, rows, K), a fixed stride apart
+    uint8_t * blob16;
+    const void * aux_g, * aux_u, * aux_d;
+    size_t aux_stride_gu, aux_stride_d;
+};
+size_t bamd_moe_batch_blob16_bytes(int T, int E, int F, int n_used);
+int    bamd_moe_batch_mfma_ready(const bamd_moe_batch_args & a);              // 1 = bamd_launch_moe_ffn_batch takes the matrix-core kernels for these arguments under the current switch
+void   bamd_launch_moe_gate_up_mfma(const bamd_moe_batch_args & a, hipStream_t s);      // its launches 4 (gate, then up) and 6 on the matrix cores
+void   bamd_launch_moe_down_mfma(const bamd_moe_batch_args & a, hipStream_t s);
 int    bamd_moe_batch_supported(int E, int F, int n_expert, int n_used);      // bamd_moe_shape_supported, and four Q8_K images of the longer of E and F fit the LDS of a CU
 size_t bamd_moe_batch_tiles_bytes(int T, int n_expert, int n_used);
 size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used);

@@ -12,6 +12,7 @@
 // Tiles of one expert are adjacent in blockIdx.x: the workgroups that share a row slot's weights run together and meet in L2, as in the dense kernel.
 // Per (row, pair) the arithmetic is the chain of the decode path: the row policy KqRow (bamd_prefill_kq.h) over the pair's Q8_K image, every weight record
 // unpacked once for the TT pairs of a tile; the products are scaled before any add and added in slot order.  What is restated: bamd_moe.hip.
+// Launches 4 and 6 have a matrix-core variant behind BAMD_PREFILL_MOE (bamd_moe_batch_mfma.hip: tiles of 64 pairs, the f16 records in place of the Q8_K images).
 #include "bamd_moe_device.h"
 #include "bamd_prefill_kq.h"
 
@@ -159,7 +160,7 @@ __device__ __forceinline__ void moe_group_segment(const uint8_t * __restrict__ w
 // grid (tile, row slot), 8 waves; wave v of row slot y walks the row-groups y + gridDim.y * v, + gridDim.y * 8, ..  GU: K = E, rows = F, the image of a pair is
 // its TOKEN's (pair / n_used); else K = F, rows = E, the image is the pair's own row of h
 template <int TYPE, bool GU, int TT>
-__global__ void __launch_bounds__(512) moe_group_mm_kernel(bamd_moe_batch_args a) {
+__global__ void __launch_bounds__(512) moe_group_mm_kernel(bamd_moe_group_args a) {      // (the launch arguments without the matrix-core path's: the argument block, and with it the code object, stays what it was)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef KqRow<TYPE, typename RecOf<TYPE>::type> P;
     const int npairs = a.T * a.m.n_used;
@@ -227,6 +228,10 @@ size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used) {
     const size_t x = (size_t) T * bamd_blob_bytes(E), h = (size_t) T * n_used * bamd_blob_bytes(F);
     return x > h ? x : h;
 }
+size_t bamd_moe_batch_blob16_bytes(int T, int E, int F, int n_used) {
+    const size_t x = (size_t) T * bamd_blob16_bytes(E), h = (size_t) T * n_used * bamd_blob16_bytes(F);
+    return x > h ? x : h;
+}
 
 template <bool GU>
 static bool launch_group_mm(const bamd_moe_batch_args & a, int n_cu, hipStream_t s) {
@@ -247,12 +252,21 @@ int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a0, int n_cu, hipStrea
     if (!bamd_moe_batch_supported(m.E, m.F, m.n_expert, m.n_used) || a0.T < 1 || a0.T * m.n_used > BAMD_MOE_BATCH_MAX_PAIRS) return 1;
     if (m.stride_gu >= (size_t) 0x7fffffff || m.stride_d >= (size_t) 0x7fffffff || !bamd_is_kquant(m.type_gu) || !bamd_is_kquant(m.type_d)) return 1;
     bamd_moe_batch_args a = a0;
-    a.tt = moe_batch_tt(m.E, m.F);
+    const bool mfma = bamd_moe_batch_mfma_ready(a0);      // launches 4 and 6 on the matrix cores (bamd_moe_batch_mfma.hip): tiles of 64 pairs, f16 records only
+    a.tt = mfma ? 64 : moe_batch_tt(m.E, m.F);
     const int npairs = a.T * m.n_used;
     const size_t rlds = moe_router_lds(m.E);
     bamd_allow_lds(moe_router_batch_kernel, rlds);
     hipLaunchKernelGGL(moe_router_batch_kernel, dim3(a.T), dim3(512), rlds, s, m);
     hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(512), 0, s, (const int32_t *) m.sel, npairs, m.n_expert, a.tt, a.lists, a.tiles);
+    if (mfma) {
+        bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, nullptr, a.blob16, s);
+        bamd_launch_moe_gate_up_mfma(a, s);
+        bamd_launch_quantize_batch(m.h, nullptr, 0.f, m.F, npairs, nullptr, a.blob16, s);
+        bamd_launch_moe_down_mfma(a, s);
+        hipLaunchKernelGGL(moe_combine_kernel, dim3(a.T), dim3(256), 0, s, (const float *) a.prod, m.x, m.E, m.n_used, m.out);
+        return 0;
+    }
     bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, a.blob, nullptr, s);
     if (!launch_group_mm<true>(a, n_cu, s)) return 1;
     g_moe_batch_runs += 1;

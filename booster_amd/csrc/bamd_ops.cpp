@@ -223,6 +223,19 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn_batch(cons
     a.m.x = dx; a.m.normw = dw; a.m.eps = eps; a.m.E = E; a.m.F = F; a.m.n_expert = n_expert; a.m.n_used = n_used; a.m.gate_inp = si; a.m.wg = sg; a.m.wu = su; a.m.wd = sd;
     a.m.type_gu = type_gu; a.m.type_d = type_d; a.m.stride_gu = gus; a.m.stride_d = ds; a.m.sel = dsel; a.m.w = dwt; a.m.h = dh; a.m.out = dy;
     a.T = T; a.prod = dprod; a.lists = lists; a.tiles = tiles; a.blob = (uint8_t *) blob;
+    // BAMD_PREFILL_MOE on and expert types with a grouped matrix-core kernel: the per-expert side tables and the f16 records, built here as the engine builds them at model load
+    const size_t ag = bamd_prefill_aux_bytes(type_gu, F, E), ad = bamd_prefill_aux_bytes(type_d, E, F);
+    if (bamd_prefill_moe_on() && bamd_prefill_mfma_supported() && ag && ad) {
+        void * xg = t.up(nullptr, ag * n_expert), * xu = t.up(nullptr, ag * n_expert), * xd = t.up(nullptr, ad * n_expert);
+        a.blob16 = (uint8_t *) t.up(nullptr, bamd_moe_batch_blob16_bytes(T, E, F, n_used));
+        if (!xg || !xu || !xd || !a.blob16) return fail("device alloc failed");
+        for (int e = 0; e < n_expert; ++e) {
+            bamd_launch_prefill_aux((const char *) sg + e * gus, type_gu, F, E, (char *) xg + e * ag, nullptr);
+            bamd_launch_prefill_aux((const char *) su + e * gus, type_gu, F, E, (char *) xu + e * ag, nullptr);
+            bamd_launch_prefill_aux((const char *) sd + e * ds, type_d, E, F, (char *) xd + e * ad, nullptr);
+        }
+        a.aux_g = xg; a.aux_u = xu; a.aux_d = xd; a.aux_stride_gu = ag; a.aux_stride_d = ad;
+    }
     if (bamd_launch_moe_ffn_batch(a, n_cu0(), nullptr)) return fail("moe_ffn_batch: shape without a kernel");
     if (finish(y, dy, (size_t) T * E * 4)) return 1;
     HIPC(hipMemcpy(sel, dsel, np * 4, hipMemcpyDeviceToHost));

@@ -34,6 +34,9 @@ BAMD_API void bamd_set_prefill_nl(int on) { bamd_prefill_family_set(BAMD_PF_NL, 
 BAMD_API void bamd_set_prefill_flt(int on) { bamd_prefill_family_set(BAMD_PF_FLT, on); }
 BAMD_API void bamd_set_prefill_bf16(int on) { bamd_prefill_family_set(BAMD_PF_BF16, on); }
 BAMD_API void bamd_set_prefill_xs(int on) { bamd_prefill_family_set(BAMD_PF_XS, on); }
+static int & moe_state() { static int on = [] { const char * e = getenv("BAMD_PREFILL_MOE"); return (e && e[0] == '1') ? 1 : 0; }(); return on; }
+int bamd_prefill_moe_on(void) { return moe_state(); }
+BAMD_API void bamd_set_prefill_moe(int on) { moe_state() = on ? 1 : 0; }
 BAMD_API unsigned long long bamd_prefill_bf16_fallback_tiles(void) { return bamd_bf16_fallback_tiles_all(); }
 
 // Called for a matrix without a side table (bamd_prefill_aux_bytes = 0).  With every switch off the sentences read as they did before the switches existed.  The

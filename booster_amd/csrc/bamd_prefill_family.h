@@ -44,6 +44,9 @@ static inline bool bamd_prefill_type_in(uint32_t mask, int type) { return type >
 static inline bool bamd_prefill_mfma_type(int type) { return bamd_prefill_type_in(bamd_prefill_types_on(true), type); }
 // "this weight type has a matrix-core prompt mat-mul WITHOUT a side table now" (F32 / F16 while FLT is on, BF16 while BF16 is on)
 static inline bool bamd_prefill_mfma_type_notable(int type) { return bamd_prefill_type_in(bamd_prefill_types_on(false), type); }
+// the switch of the mixture-of-experts matrix-core path (BAMD_PREFILL_MOE / bamd_set_prefill_moe, default off: bamd_moe_batch_mfma.hip).  It selects by model
+// kind, not by weight type, so it is no row of the table above
+int  bamd_prefill_moe_on(void);
 // "a family that is on reads the f16 activation records of this activation form" (Q8_0 form: Q0 or NL; Q8_1 form: Q1)
 bool bamd_prefill_reads_act16(int form);
 // why a matrix of `type` has no side table under the current switches: the sentence of the load-time message (BAMD_PREFILL_VERBOSE=1)

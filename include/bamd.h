@@ -239,6 +239,15 @@ void bamd_set_prefill_xs(int on);
 long long bamd_prefill_mfma_runs(int type);
 /* grouped gate/up launches of the batched mixture-of-experts feed-forward (one per layer and prompt micro-batch of a model with experts) since the library was loaded */
 long long bamd_moe_batch_runs(void);
+/* Matrix-core prompt mat-muls for mixture-of-experts models (env BAMD_PREFILL_MOE): 0 (default) = such a model builds no side tables: its grouped expert mat-muls
+ * and its QKV / wo mat-muls run on the integer-dot kernels; 1 = side tables for QKV, wo and one per expert matrix (Q4_K / Q5_K / Q6_K experts; 104 B per row and 256 weights, Q6_K 72 B,
+ * under the budget check of BAMD_PREFILL_AUX_RESERVE_GB), and every batched micro-batch runs the grouped gate, up and down mat-muls on the matrix
+ * cores.  It selects by model kind, not by weight type: the 8-expert recipes' Q8_0 attn_k / attn_v need bamd_set_prefill_q0 as well (side tables are
+ * all-or-nothing per model).  The tables are decided at model load, the launch path follows the switch at each micro-batch.  Bit-identical results. */
+void bamd_set_prefill_moe(int on);
+/* grouped gate/up launches of that matrix-core path since the library was loaded (bamd_moe_batch_runs counts the integer-dot ones only; bamd_prefill_mfma_runs
+ * of the expert type counts every grouped matrix-core launch) */
+long long bamd_moe_batch_mfma_runs(void);
 
 /* ---- measurement -------------------------------------------------------------------------------------- */
 /* One eager single-token step at position `pos` with a HIP-event pair around every kernel launch.

@@ -5,7 +5,12 @@ Then the same alternation for prompts of 2, 4, 8 and 16 tokens: where the batche
 launches per layer come from a run of its own under the profiler's kernel trace (--once: one batched 512-token micro-batch, eager, every launch a kernel of a
 stable name).
 
-    python tools/moe_prefill.py [--once]
+--moe: the matrix-core path of the grouped expert mat-muls (bamd_moe_batch_mfma.hip) against the integer-dot one.  Side tables are decided at model load, so
+the file is loaded twice, with set_prefill_moe(False) and (True) — set_prefill_q0(True) in both arms: the recipe's Q8_0 attn_k / attn_v — and batched prompts of
+2048, 8, 16, 32, 64, 128 and 512 tokens alternate between the two models; the side-table bytes and the free memory around the second load are printed.  With
+--once: one 512-token micro-batch of the model with tables.
+
+    python tools/moe_prefill.py [--moe] [--once]
 """
 import os
 import statistics
@@ -36,7 +41,48 @@ def alternate(ctx, prompt, reps=5):
     return got
 
 
+def main_moe():
+    path, arms = gen.ensure_model("8x7b"), {}
+    b.set_prefill_q0(True)
+    try:
+        for on in (False, True) if "--once" not in sys.argv else (True,):
+            b.set_prefill_moe(on)
+            free0 = torch_free()
+            m = b.Model(path)
+            arms[on] = (m, b.Context(m, 2048))
+            print("set_prefill_moe(%s): side tables %.2f GiB, device memory free before the load %.2f GiB, after %.2f GiB"
+                  % (on, m.prefill_aux_bytes() / 2.0 ** 30, free0 / 2.0 ** 30, torch_free() / 2.0 ** 30), flush=True)
+        prompt = [(7919 * i + 13) % arms[True][0].n_vocab for i in range(2048)]
+        if "--once" in sys.argv:
+            arms[True][1].decode(prompt[:512], 0)
+            return
+        for n in (2048, 8, 16, 32, 64, 128, 512):
+            got = {False: [], True: []}
+            for rep in range(6):                              # (rep 0: the warm-up of both)
+                for on in (False, True):
+                    b.set_prefill_moe(on)
+                    runs = b.moe_batch_mfma_runs()
+                    r = rate(arms[on][1], prompt[:n], True)
+                    assert (b.moe_batch_mfma_runs() > runs) == on
+                    if rep:
+                        got[on].append(r)
+            for on, name in ((False, "integer-dot"), (True, "matrix cores")):
+                print("prompt of %4d tokens, experts on %-12s median %8.1f tok/s  (range %.1f - %.1f, 5 alternating evaluations after a warm-up)"
+                      % (n, name, statistics.median(got[on]), min(got[on]), max(got[on])), flush=True)
+    finally:
+        b.set_prefill_moe(os.environ.get("BAMD_PREFILL_MOE", "")[:1] == "1"); b.set_prefill_q0(os.environ.get("BAMD_PREFILL_Q0", "")[:1] == "1")
+        for m, ctx in arms.values():
+            ctx.close(); m.close()
+
+
+def torch_free():
+    import torch
+    return torch.cuda.mem_get_info()[0]
+
+
 def main():
+    if "--moe" in sys.argv:
+        return main_moe()
     m = b.Model(gen.ensure_model("8x7b"))
     ctx = b.Context(m, 2048)
     prompt = [(7919 * i + 13) % m.n_vocab for i in range(2048)]
