@@ -81,6 +81,8 @@ def lib():
             getattr(L, "bamd_set_prefill_" + n).argtypes = [ci]; getattr(L, "bamd_set_prefill_" + n).restype = None
         L.bamd_set_attn_scratch_mb.argtypes = [ci]; L.bamd_set_attn_scratch_mb.restype = None
         L.bamd_attention_batch_plan.argtypes = [ci, ci, ci, ci, ci, ci, C.c_size_t, C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_size_t)]
+        L.bamd_set_attn_mfma_ext.argtypes = [ci]; L.bamd_set_attn_mfma_ext.restype = None
+        L.bamd_attn_batch_mfma_runs.argtypes = []; L.bamd_attn_batch_mfma_runs.restype = C.c_longlong
         L.bamd_prefill_mfma_runs.argtypes = [ci]; L.bamd_prefill_mfma_runs.restype = C.c_longlong
         L.bamd_prefill_bf16_fallback_tiles.argtypes = []; L.bamd_prefill_bf16_fallback_tiles.restype = C.c_ulonglong
         L.bamd_model_prefill_aux_bytes.argtypes = [vp]; L.bamd_model_prefill_aux_bytes.restype = i64
@@ -201,6 +203,18 @@ def attention_batch_plan(Hkv, gq, hd, T, ld, impl=0, budget_bytes=0):
     if lib().bamd_attention_batch_plan(Hkv, gq, hd, T, ld, impl, budget_bytes, C.byref(tps), C.byref(ns), C.byref(sb)) != 0:
         return None
     return tps.value, ns.value, sb.value
+
+
+def set_attn_mfma_ext(on):
+    """True: the matrix-core prompt attention also takes head_dim 64 (every ratio 1 .. 8) and the ratios 3 / 5 / 6 / 7 at head_dim 128; False (default, also env
+    BAMD_ATTN_MFMA_EXT): head_dim 128 with 1 / 2 / 4 / 8 query heads per KV head only, everything else on the VALU kernels.  Read by the slice plan and the launcher
+    at each call, so it also applies to models and contexts that exist already.  Same bits either way."""
+    lib().bamd_set_attn_mfma_ext(int(bool(on)))
+
+
+def attn_batch_mfma_runs():
+    """matrix-core batched-attention launches (every instance) since the library was loaded: one per layer, micro-batch and token slice"""
+    return int(lib().bamd_attn_batch_mfma_runs())
 
 
 def prefill_mfma_runs(t):

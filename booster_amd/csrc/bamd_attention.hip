@@ -477,16 +477,20 @@ static void launch_attn_fused(const bamd_attn_args & a, int gq, dim3 grid, size_
 // The ONE place this is written down (as bamd_batch_mm is for the mat-mul routing): the launcher below, the engine's allocation and the op-level entry point
 // all ask here.  Host code, no device.
 //   kernel   head_dim 128, gq 1 / 2 / 4 / 8, T >= 2, impl != 1: the matrix-core kernel — LONG (scratch block) beyond BAMD_AM_MAXPOS = 512 positions;
+//            with BAMD_ATTN_MFMA_EXT / bamd_set_attn_mfma_ext on (read here at each call) also head_dim 64 and every gq 1 .. 8 at both (bamd_attention_mfma_ext.hip);
 //            else while two rows of ld floats fit BAMD_ATTN_LDS_MAX: the VALU kernels with their rows in LDS (no scratch); else attn_batch_gs_kernel (scratch block; bamd_attention_gs.hip)
 //   tile     the tokens a workgroup row of the grid covers: 16 / gq (matrix cores) or 1 (VALU); a tile's workgroups (one per KV head) take gq x tile x ld floats
 //            each = Hkv x gq x tile x ld x 4 bytes per tile.  A slice is a whole number of tiles; slices are balanced (ceil(tiles / n) each).
 //   budget   bytes the scratch block may take; 0 = the default: Hkv x gq x 512 x 18432 x 4, the scratch of a 512-token micro-batch at ld 18432 — the most a
 //            context could ask for before the plan existed, so with it every ld <= 18432 is ONE slice of the size bamd_attention_batch_mfma_scratch gives.
+//            (At gq 3 / 5 / 6 / 7 a matrix-core tile carries 16 - (16 / gq) * gq dead columns and its scratch is still 16 columns: 512 tokens at gq 3 are 103 tiles
+//            = 1648 columns against the budget's 1536, so near ld 18432 such a micro-batch is TWO slices under the default budget.)
 // 1 = no plan: bad shape, impl 2 where the matrix-core kernel declines, or a budget that cannot hold one tile (it does not loop).  Where the rows still fit the
 // LDS and the budget cannot hold a matrix-core tile, impl 0 plans the VALU kernels (scratch 0): what runs when the block cannot be allocated.
 #define BAMD_ATTN_PLAN_T 512
 #define BAMD_ATTN_PLAN_LD 18432
 static bool attn_batch_on_mfma(int gq, int hd, int T, int impl) {
+    if (bamd_attention_batch_mfma_ext_on()) return impl != 1 && bamd_attention_batch_mfma_on() && (hd == 64 || hd == 128) && T >= 2 && gq >= 1 && gq <= 8;
     return impl != 1 && bamd_attention_batch_mfma_on() && hd == 128 && T >= 2 && (gq == 1 || gq == 2 || gq == 4 || gq == 8);
 }
 extern "C" __attribute__((visibility("default"))) int bamd_attention_batch_plan(int Hkv, int gq, int hd, int T, int ld, int impl, size_t budget_bytes, int * tokens_per_slice,
@@ -515,7 +519,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_attention_batch_plan(
 
 // the launches behind the KV store while the rows fit the LDS and one launch covers the micro-batch
 static int launch_attention_batch_lds(const bamd_attn_args & a, int gq, int T, hipStream_t s, int impl, int ld) {
-    if (impl != 1 && bamd_launch_attention_batch_mfma(a, gq, T, s) == 0) return 0;   // head_dim 128 (beyond 512 positions with a.batch_scratch): the matrix-core kernel (bamd_attention_mfma.hip)
+    if (impl != 1 && bamd_launch_attention_batch_mfma(a, gq, T, s) == 0) return 0;   // head_dim 128 (beyond 512 positions with a.batch_scratch): the matrix-core kernel (bamd_attention_mfma.hip; more shapes behind BAMD_ATTN_MFMA_EXT)
     if (impl == 2) return 1;
     // as many query heads of a KV head per workgroup as have their score rows fit the LDS (ld floats each: the probabilities replace
     // the scores in place); a single head per workgroup runs on attn_fused_kernel (separate rows: 2 x ld floats)

@@ -15,37 +15,16 @@
 // fetched serves 16 columns, the matrix pipe does the multiply-adds (the VALU kernel, attn_batch_kernel, spent ~3 vector instructions per
 // multiply-add and was 55 % of a long prompt), and the workgroup -> KV head mapping keeps one head's K / V in one XCD's L2.
 // head_dim 128; the score / probability rows of the 16 columns live in LDS up to BAMD_AM_MAXPOS cached positions, in a global scratch block beyond (LONG);
-// other shapes: attn_batch_kernel.
-#include "bamd_device.h"
+// head_dim 64 and gq 3 / 5 / 6 / 7: bamd_attention_mfma_ext.hip behind BAMD_ATTN_MFMA_EXT (default off; the switch, the launch counter and the launcher of both files are
+// at the end of this one); other shapes: attn_batch_kernel.
+#include "bamd_attn_mfma.h"
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-#define BAMD_AM_NW 4                           /* waves per workgroup: FOUR, at <= 256 VGPRs and <= 56 KB of LDS, so that TWO workgroups share a CU — one workgroup is a chain of
-                                                  dependent phases (q / K requests, scores, softmax, V requests, P.V: ~19 us of latency even for a short sequence, measured
-                                                  phase by phase), and only a second resident workgroup fills the matrix pipe while the first one waits */
 #define BAMD_AM_DT (8 / BAMD_AM_NW)            /* 16-row tiles of V^T (of the 128 rows of a head) per wave in the P.V pass */
-#define BAMD_AM_VROW 144                       /* bytes per staged V^T row (64 positions x f16 = 128 B, padded: 36 dwords -> 16 rows on 16 distinct banks) */
 #define BAMD_AM_QBYTES (16 * 128 * 2)          /* q of the 16 columns, f16, chain-major */
 #define BAMD_AM_VBYTES (BAMD_AM_NW * BAMD_AM_DT * 16 * BAMD_AM_VROW)   /* one staged block per wave and row tile */
-#define BAMD_AM_RBYTES 1024                    /* column maxima per wave + 1 / sum per column */
-#define BAMD_AM_MAXPOS 512                     /* positions whose score rows stay in LDS (64 B each: 32 KB); beyond: global scratch + chunks (LONG) */
-#define BAMD_AM_CHUNK 512                      /* LONG: positions staged through LDS at a time in the P.V pass */
 #ifndef BAMD_AM_KD
 #define BAMD_AM_KD 2                           /* tiles of 16 K rows in flight per wave (pass 1) */
 #endif
-
-// score / probability storage [position][column] in LDS, laid out for the three access patterns (64 banks of 4 bytes):
-//   row(p) = the positions of a group of 32 reordered as [p & 7][(p >> 3) & 3]: the four positions p, p + 8, p + 16, p + 24 that the four k-groups of a
-//            P.V MFMA read together sit in rows with different (row & 3) = different quarters of the banks;
-//   column n of a row is stored at n ^ ((row >> 2) & 15): consecutive positions of one column (the softmax pass) hit distinct banks.
-__device__ __forceinline__ int am_sidx(int p, int n) {
-    const int row = (p & ~31) | ((p & 7) << 2) | ((p >> 3) & 3);
-    return row * 16 + (n ^ ((row >> 2) & 15));
-}
-// LONG: the scratch block of a workgroup holds its 16 score rows as [position / 4][column][4]: the four consecutive positions a lane of pass 1 produces for
-// its column are one 16-byte store, and the 16 columns of a position quad are 256 contiguous bytes
-__device__ __forceinline__ size_t am_gidx(int p, int n) { return ((size_t) (p >> 2) * 16 + n) * 4 + (p & 3); }
-__device__ __forceinline__ float h2f_lo(uint32_t w) { return __half2float(__ushort_as_half((unsigned short) (w & 0xffffu))); }
-__device__ __forceinline__ float h2f_hi(uint32_t w) { return __half2float(__ushort_as_half((unsigned short) (w >> 16))); }
 
 // LONG: more positions than BAMD_AM_MAXPOS — the scores / exp values of the 16 columns live in a global scratch block of this workgroup
 // ([16 columns][ld] f32: written by pass 1, exponentiated in place by pass 2) and pass 3 walks them in chunks of BAMD_AM_CHUNK positions staged
@@ -277,9 +256,24 @@ __global__ void __launch_bounds__(64 * BAMD_AM_NW) __attribute__((amdgpu_waves_p
     }
 }
 
+// ---- host: the switches, the counter, the launcher -----------------------------------------------------------------------------------------------------------
+#define BAMD_API extern "C" __attribute__((visibility("default")))
+// BAMD_ATTN_MFMA_EXT / bamd_set_attn_mfma_ext (default off): head_dim 64, and the ratios 3 / 5 / 6 / 7, on the instances of bamd_attention_mfma_ext.hip.  Read by the
+// slice plan and by the launcher at each call (no load-time state: the engine sizes the scratch block per micro-batch through the plan)
+static int & ext_state() { static int on = [] { const char * e = getenv("BAMD_ATTN_MFMA_EXT"); return (e && e[0] == '1') ? 1 : 0; }(); return on; }
+int bamd_attention_batch_mfma_ext_on(void) { return ext_state(); }
+BAMD_API void bamd_set_attn_mfma_ext(int on) { ext_state() = on ? 1 : 0; }
+static long long g_attn_batch_mfma_runs = 0;
+BAMD_API long long bamd_attn_batch_mfma_runs(void) { return g_attn_batch_mfma_runs; }
+// which kernel takes (hd, gq): 1 = this file's instances (as ever), 2 = the extension's (switch on), 0 = none
+static int am_family(int hd, int gq) {
+    if (hd == 128 && (gq == 1 || gq == 2 || gq == 4 || gq == 8 || gq == 16)) return 1;
+    return ext_state() && (hd == 64 || hd == 128) && gq >= 1 && gq <= 8 ? 2 : 0;
+}
+
 // 0 = launched (after the KV store); 1 = shape not covered: the caller takes attn_batch_kernel
-size_t bamd_attention_batch_mfma_scratch(int Hkv, int gq, int T, int ld) {       // bytes of a.batch_scratch a micro-batch of T tokens needs when ld > BAMD_AM_MAXPOS (else 0)
-    if (ld <= BAMD_AM_MAXPOS || (gq != 1 && gq != 2 && gq != 4 && gq != 8 && gq != 16)) return 0;
+size_t bamd_attention_batch_mfma_scratch(int Hkv, int gq, int T, int ld) {       // bytes of a.batch_scratch a micro-batch of T tokens needs when ld > BAMD_AM_MAXPOS (else 0): 16 columns per workgroup, dead ones included
+    if (ld <= BAMD_AM_MAXPOS || !(am_family(128, gq) || am_family(64, gq))) return 0;
     const int tt = 16 / gq;
     return (size_t) Hkv * ((T + tt - 1) / tt) * 16 * (size_t) ld * 4;
 }
@@ -288,8 +282,8 @@ int bamd_attention_batch_mfma_on(void) {
     return on ? 1 : 0;
 }
 int bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hipStream_t s, int t0, int Ts) {
-    if (!bamd_attention_batch_mfma_on() || a.hd != 128 || !a.batch || T < 2) return 1;
-    if (gq != 1 && gq != 2 && gq != 4 && gq != 8 && gq != 16) return 1;
+    const int fam = am_family(a.hd, gq);
+    if (!bamd_attention_batch_mfma_on() || !fam || !a.batch || T < 2) return 1;
     const int npos = a.lds_ld ? a.lds_ld : a.n_ctx;                            // the caller's bound on the padded sequence length of this micro-batch (multiple of 64)
     if ((npos & 63) || npos > a.n_ctx) return 1;
     const bool lng = npos > BAMD_AM_MAXPOS;
@@ -299,6 +293,11 @@ int bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hi
     const int tt = 16 / gq;
     if (Ts <= 0) Ts = T - t0;
     if (t0 < 0 || t0 % tt || t0 + Ts > T) return 1;
+    if (fam == 2) {
+        if (bamd_launch_attention_batch_mfma_ext(a, gq, T, s, t0, Ts, lng, dbg)) return 1;
+        g_attn_batch_mfma_runs += 1;
+        return 0;
+    }
     const dim3 grid(a.Hkv * ((Ts + tt - 1) / tt)), block(64 * BAMD_AM_NW);
 #define BAMD_AM_GO(GQ_) do { if (lng) hipLaunchKernelGGL((attn_batch_mfma_kernel<GQ_, true>), grid, block, lds, s, a, T, dbg, t0); \
                              else     hipLaunchKernelGGL((attn_batch_mfma_kernel<GQ_, false>), grid, block, lds, s, a, T, dbg, t0); } while (0)
@@ -310,5 +309,6 @@ int bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, hi
         default: BAMD_AM_GO(16); break;
     }
 #undef BAMD_AM_GO
+    g_attn_batch_mfma_runs += 1;
     return 0;
 }

@@ -224,6 +224,8 @@ int  bamd_launch_attention_batch_mfma(const bamd_attn_args & a, int gq, int T, h
 size_t bamd_attention_batch_mfma_scratch(int Hkv, int gq, int T, int ld);                         // bytes of a.batch_scratch it needs for sequences of up to ld positions (0: none)
 void bamd_launch_attention_batch_gs(const bamd_attn_args & a, int gq, int t0, int Ts, hipStream_t s);   // the VALU kernel with its rows in a.batch_scratch (beyond the LDS; gq 1..8 checked by the caller)
 int  bamd_attention_batch_mfma_on(void);                                                           // 0: switched off (BAMD_ATTN_MFMA=0)
+int  bamd_attention_batch_mfma_ext_on(void);                                                       // 1: head_dim 64 and gq 3 / 5 / 6 / 7 on the matrix cores too (BAMD_ATTN_MFMA_EXT / bamd_set_attn_mfma_ext)
+int  bamd_launch_attention_batch_mfma_ext(const bamd_attn_args & a, int gq, int T, hipStream_t s, int t0, int Ts, bool lng, int dbg);   // those instances (bamd_attention_mfma_ext.hip), behind bamd_launch_attention_batch_mfma's checks
 // the slice plan of a micro-batch's attention: bamd_attention_batch_plan (include/bamd.h; defined in bamd_attention.hip, host code only)
 void bamd_launch_sampler_shortlist(float * logits, const bamd_logit_penalty * pen, int n_pen, const uint8_t * halve_class, int halve,
                                    const float * cutoff_of, int V, bamd_shortlist_head * head, int32_t * ids, float * vals, int cap, hipStream_t s);

@@ -199,6 +199,14 @@ void bamd_set_attn_scratch_mb(int mb);
  * a whole number of the kernel's token tiles (16 / gq on the matrix cores, 1 on the VALU); scratch_bytes (<= budget) is what one slice needs (0: none).
  * Returns 1 when there is no plan: bad shape, impl 2 where the matrix-core kernel declines, or a budget below one tile. */
 int bamd_attention_batch_plan(int Hkv, int gq, int hd, int T, int ld, int impl, size_t budget_bytes, int * tokens_per_slice, int * n_slices, size_t * scratch_bytes);
+/* Matrix-core prompt attention for more head shapes (env BAMD_ATTN_MFMA_EXT): 0 (default) = the matrix-core kernel takes head_dim 128 with 1, 2, 4 or 8 query
+ * heads per KV head, every other shape runs on the VALU kernels; 1 = also head_dim 64 at every ratio 1 .. 8 (Llama-3.2-1B, TinyLlama, SmolLM) and the ratios
+ * 3, 5, 6, 7 at head_dim 128 (Llama-3.2-3B), in token tiles of 16 / gq (integer division).  Read by the slice plan and the launcher at each call, like
+ * bamd_set_prefill_flt: no load-time state, it applies to models and contexts that exist already.  BAMD_ATTN_MFMA=0 still switches every matrix-core attention
+ * kernel off.  Bit-identical results. */
+void bamd_set_attn_mfma_ext(int on);
+/* matrix-core batched-attention launches (every instance, with and without that switch) since the library was loaded: one per layer, micro-batch and token slice */
+long long bamd_attn_batch_mfma_runs(void);
 /* Matrix-core prompt mat-muls for Q3_K / Q2_K weights, process-wide: 0 (default, also env BAMD_PREFILL_LOWBIT) = a model that holds such a matrix builds
  * no side tables and evaluates its prompts on the integer-dot kernel; 1 = these types have side tables and kernels like Q4_K / Q5_K / Q6_K.  A model takes the
  * value at load (its tables exist or not); with the switch off again a model that has tables runs its prompts on the integer-dot kernel.  Bit-identical results. */
