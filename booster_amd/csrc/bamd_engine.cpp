@@ -247,16 +247,18 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s);
 // (bamd_is_kquant holds IQ4_XS too, so an IQ4_XS attn_v beside IQ4_NL attn_q / attn_k passes here as well: no recipe writes it and no test covers it; it takes the
 // same two launches, the second on the generic Q8_K kernel)
 // The second one: the recipes for an 8-expert model write attn_k and attn_v as Q8_0 beside a K-quant attn_q (src/llama.cpp:15556-15567): Q8_K activations for the
-// first, Q8_0 for the merged k | v segment — two launches as well
+// first, Q8_0 for the merged k | v segment — two launches as well.  The 8-expert Q4_1 / Q5_1 recipes write the same pair with a Q4_1 / Q5_1 attn_q: Q8_1 activations
+// for it, Q8_0 for k | v.  Under Q4_0 / Q5_0 / Q8_0 all three take Q8_0 activations: one launch, no mix; under IQ4_NL too (the launch with an IQ4_NL segment,
+// bamd_matvec_b32_nl.hip), and an IQ4_NL attn_q beside Q8_0 k | v is what that 8-expert recipe writes, so it loads here and nowhere else
 static bool qkv_recipe_mix(int tq, int tk, int tv, int n_expert) {
-    return (tq == BAMD_IQ4_NL && tk == BAMD_IQ4_NL && bamd_is_kquant(tv)) || (n_expert == 8 && bamd_is_kquant(tq) && tk == BAMD_Q8_0 && tv == BAMD_Q8_0);
+    return (tq == BAMD_IQ4_NL && tk == BAMD_IQ4_NL && bamd_is_kquant(tv)) || (n_expert == 8 && (bamd_is_kquant(tq) || bamd_is_q1(tq) || tq == BAMD_IQ4_NL) && tk == BAMD_Q8_0 && tv == BAMD_Q8_0);
 }
 // one 3-D expert tensor [K, nrows, n_expert] -> n_expert consecutive wave-stream matrices
 static int upload_experts(bamd_model * m, const GgufTensor * t, const std::string & name, int K, int nrows, void ** dst, int * type, size_t * stride, size_t * bytes, void * staging, hipStream_t s) {
     if (!t) return fail("missing tensor " + name);
     if (t->ne.size() != 3 || (int) t->ne[0] != K || (int) t->ne[1] != nrows || (int) t->ne[2] != m->n_expert)
         return fail("tensor " + name + ": expected [" + std::to_string(K) + ", " + std::to_string(nrows) + ", " + std::to_string(m->n_expert) + "]");
-    if (!bamd_is_kquant(t->type)) return fail("tensor " + name + ": expert matrices of type " + std::to_string(t->type) + " are not supported (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS)");
+    if (!bamd_is_kquant(t->type) && !bamd_is_b32(t->type)) return fail("tensor " + name + ": expert matrices of type " + std::to_string(t->type) + " are not supported (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
     *type = t->type; *stride = bamd_stream_bytes(t->type, K, nrows); *bytes = t->nbytes / (size_t) m->n_expert;
     if (*stride >= (size_t) 0x7fffffff) return fail("tensor " + name + ": one expert's wave-stream copy exceeds 2 GiB (32-bit record offsets)");
     if (dev_alloc(m->allocs, dst, *stride * (size_t) m->n_expert)) return 1;
@@ -962,7 +964,8 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
             // BAMD_PREFILL_MOE: a table per expert for the grouped matrix-core mat-muls (bamd_moe_batch_mfma.hip), which take Q4_K / Q5_K / Q6_K experts
             for (int t : { ly.type_gu, ly.type_d })
                 if (t != BAMD_Q4_K && t != BAMD_Q5_K && t != BAMD_Q6_K) {
-                    m->aux_why = std::string("the model holds ") + (t == BAMD_Q2_K ? "Q2_K" : t == BAMD_Q3_K ? "Q3_K" : "IQ4_XS") + " expert matrices: the grouped matrix-core mat-muls (BAMD_PREFILL_MOE) take Q4_K / Q5_K / Q6_K experts, and "
+                    m->aux_why = std::string("the model holds ") + (t == BAMD_Q2_K ? "Q2_K" : t == BAMD_Q3_K ? "Q3_K" : t == BAMD_IQ4_XS ? "IQ4_XS" : t == BAMD_Q8_0 ? "Q8_0" : t == BAMD_Q4_0 ? "Q4_0" : t == BAMD_Q5_0 ? "Q5_0" :
+                                                                        t == BAMD_Q4_1 ? "Q4_1" : t == BAMD_Q5_1 ? "Q5_1" : "IQ4_NL") + " expert matrices, which have no matrix-core grouped kernel: the grouped matrix-core mat-muls (BAMD_PREFILL_MOE) take Q4_K / Q5_K / Q6_K experts, and "
                                  "side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel";
                     return;
                 }

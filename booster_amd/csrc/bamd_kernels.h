@@ -76,7 +76,7 @@ struct bamd_moe_args {
     int E, F, n_expert, n_used;
     const void * gate_inp;         // F32 wave stream [n_expert][E]
     const void * wg, * wu, * wd;   // n_expert consecutive wave-stream matrices each: gate / up [F][E] (stride_gu bytes apart), down [E][F] (stride_d)
-    int type_gu, type_d;           // K-quant types (bamd_is_kquant)
+    int type_gu, type_d;           // independent of each other: a K-quant (bamd_is_kquant) or a 32-weight block type (bamd_is_b32)
     size_t stride_gu, stride_d;
     int32_t * sel; float * w;      // [n_used]: the selected experts and their normalised weights, router -> the other two launches
     float * h;                     // [n_used][F]: silu(gate) * up of every slot, gate/up -> down
@@ -85,8 +85,16 @@ struct bamd_moe_args {
 };
 int  bamd_moe_shape_supported(int E, int F, int n_expert, int n_used);     // the limits the three launchers check (the loader refuses everything else by name)
 [[nodiscard]] int bamd_launch_moe_router(const bamd_moe_args & a, hipStream_t s);                // 1 = shape not supported (nothing launched), here and below
-[[nodiscard]] int bamd_launch_moe_gate_up(const bamd_moe_args & a, int n_cu, hipStream_t s);     // 1 also for a type without a K-quant stream
-[[nodiscard]] int bamd_launch_moe_down(const bamd_moe_args & a, int n_cu, hipStream_t s);
+[[nodiscard]] int bamd_launch_moe_gate_up(const bamd_moe_args & a, int n_cu, hipStream_t s);     // 1 also for a type without a routed kernel; routes by the family of type_gu
+[[nodiscard]] int bamd_launch_moe_down(const bamd_moe_args & a, int n_cu, hipStream_t s);        // the same by type_d
+// the routed launches of the 32-weight block families (bamd_moe_b32.h; a code object per family: Q8_0 / Q4_0 / Q5_0, Q4_1 / Q5_1, IQ4_NL), behind the two above, which
+// check shape and strides; tiles: the grid's row-group tiles of a slot; the down launch takes a.tile set and sizes its LDS by the Q8_0 / Q8_1 images
+int bamd_launch_moe_gate_up_b32_q0(const bamd_moe_args & a, int tiles, hipStream_t s);
+int bamd_launch_moe_gate_up_b32_q1(const bamd_moe_args & a, int tiles, hipStream_t s);
+int bamd_launch_moe_gate_up_b32_nl(const bamd_moe_args & a, int tiles, hipStream_t s);
+int bamd_launch_moe_down_b32_q0(const bamd_moe_args & a, hipStream_t s);
+int bamd_launch_moe_down_b32_q1(const bamd_moe_args & a, hipStream_t s);
+int bamd_launch_moe_down_b32_nl(const bamd_moe_args & a, hipStream_t s);
 // the same feed-forward for a micro-batch of T tokens (bamd_moe_batch.hip): batched router | grouping | Q8_K of the normed rows | grouped gate/up | Q8_K of h |
 // grouped down | combine.  A pair is (token t, slot s), its id t * n_used + s
 struct bamd_moe_group_args {       // what the grouped integer-dot kernels take as their kernel argument
@@ -113,6 +121,8 @@ int    bamd_moe_batch_supported(int E, int F, int n_expert, int n_used);      //
 size_t bamd_moe_batch_tiles_bytes(int T, int n_expert, int n_used);
 size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used);
 [[nodiscard]] int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a, int n_cu, hipStream_t s);      // 1 = shape or type without a kernel (nothing launched)
+// its launches 4 (gu != 0: type_gu) and 6 (type_d) for a 32-weight block type (bamd_moe_batch_b32.hip), a.blob in that type's form; grid, lds and a.tt from the caller
+int bamd_launch_moe_group_mm_b32(const bamd_moe_batch_args & a, int gu, dim3 grid, size_t lds, hipStream_t s);
 
 #define BAMD_TL_WG 512                 /* workgroups recorded per launch (phase stamps, BAMD_TIMING builds) */
 #define BAMD_TL_WG_WORDS 24            /* per workgroup: [wave 0: 8 phases][wave 7: 8 phases][exit stamp of each of 8 waves] */

@@ -185,6 +185,8 @@ int bamd_launch_moe_gate_up(const bamd_moe_args & a, int n_cu, hipStream_t s) {
     const int nrg = a.F >> 3, cus = n_cu > 0 ? n_cu : 256;
     const int per_wave = (nrg * a.n_used + 8 * cus - 1) / (8 * cus);
     const int tiles = (nrg + 8 * per_wave - 1) / (8 * per_wave);
+    // the 32-weight block families: bamd_moe_b32.h, a code object each
+    if (bamd_is_b32(a.type_gu)) return bamd_is_q1(a.type_gu) ? bamd_launch_moe_gate_up_b32_q1(a, tiles, s) : a.type_gu == BAMD_IQ4_NL ? bamd_launch_moe_gate_up_b32_nl(a, tiles, s) : bamd_launch_moe_gate_up_b32_q0(a, tiles, s);
     return with_kquant(a.type_gu, [&](auto T) -> bool {
         BAMD_LAUNCH((moe_gate_up_kernel<decltype(T)::value>), dim3(tiles, a.n_used), dim3(512), act_lds_bytes(a.E), s, a); return true; }) ? 0 : 1;
 }
@@ -192,6 +194,7 @@ int bamd_launch_moe_down(const bamd_moe_args & a0, int n_cu, hipStream_t s) {
     if (!bamd_moe_shape_supported(a0.E, a0.F, a0.n_expert, a0.n_used) || a0.stride_d >= (size_t) 0x7fffffff) return 1;
     bamd_moe_args a = a0;
     a.tile = moe_down_tile(a.E, n_cu);
+    if (bamd_is_b32(a.type_d)) return bamd_is_q1(a.type_d) ? bamd_launch_moe_down_b32_q1(a, s) : a.type_d == BAMD_IQ4_NL ? bamd_launch_moe_down_b32_nl(a, s) : bamd_launch_moe_down_b32_q0(a, s);
     const int nrg = a.E >> 3, grid = (nrg + a.tile - 1) / a.tile;
     const size_t lds = moe_down_lds(a.F, a.n_used, a.tile);
     return with_kquant(a.type_d, [&](auto T) -> bool {

@@ -241,6 +241,7 @@ static bool launch_group_mm(const bamd_moe_batch_args & a, int n_cu, hipStream_t
     if (gy * 8 > nrg) gy = (nrg + 7) / 8;
     const dim3 grid(moe_batch_tile_bound(a.T, a.m.n_expert, a.m.n_used, a.tt), gy);
     const size_t lds = moe_group_lds(K, a.tt);
+    if (bamd_is_b32(GU ? a.m.type_gu : a.m.type_d)) return bamd_launch_moe_group_mm_b32(a, GU, grid, lds, s) == 0;      // the 32-weight block types: bamd_moe_batch_b32.hip
     return with_kquant(GU ? a.m.type_gu : a.m.type_d, [&](auto T) -> bool {
         constexpr int TYPE = decltype(T)::value;
         if (a.tt == BAMD_TT) { bamd_allow_lds(moe_group_mm_kernel<TYPE, GU, BAMD_TT>, lds); hipLaunchKernelGGL((moe_group_mm_kernel<TYPE, GU, BAMD_TT>), grid, dim3(512), lds, s, a); }
@@ -250,7 +251,7 @@ static bool launch_group_mm(const bamd_moe_batch_args & a, int n_cu, hipStream_t
 int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a0, int n_cu, hipStream_t s) {
     const bamd_moe_args & m = a0.m;
     if (!bamd_moe_batch_supported(m.E, m.F, m.n_expert, m.n_used) || a0.T < 1 || a0.T * m.n_used > BAMD_MOE_BATCH_MAX_PAIRS) return 1;
-    if (m.stride_gu >= (size_t) 0x7fffffff || m.stride_d >= (size_t) 0x7fffffff || !bamd_is_kquant(m.type_gu) || !bamd_is_kquant(m.type_d)) return 1;
+    if (m.stride_gu >= (size_t) 0x7fffffff || m.stride_d >= (size_t) 0x7fffffff || !(bamd_is_kquant(m.type_gu) || bamd_is_b32(m.type_gu)) || !(bamd_is_kquant(m.type_d) || bamd_is_b32(m.type_d))) return 1;
     bamd_moe_batch_args a = a0;
     const bool mfma = bamd_moe_batch_mfma_ready(a0);      // launches 4 and 6 on the matrix cores (bamd_moe_batch_mfma.hip): tiles of 64 pairs, f16 records only
     a.tt = mfma ? 64 : moe_batch_tt(m.E, m.F);
@@ -267,10 +268,11 @@ int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a0, int n_cu, hipStrea
         hipLaunchKernelGGL(moe_combine_kernel, dim3(a.T), dim3(256), 0, s, (const float *) a.prod, m.x, m.E, m.n_used, m.out);
         return 0;
     }
-    bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, a.blob, nullptr, s);
+    // launches 3 and 5 in the form of the mat-mul that reads them: Q8_K, or Q8_0 / Q8_1 (bamd_launch_quantize_batch_b32) at the same stride
+    bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, a.blob, nullptr, s, bamd_act_form_of(m.type_gu));
     if (!launch_group_mm<true>(a, n_cu, s)) return 1;
     g_moe_batch_runs += 1;
-    bamd_launch_quantize_batch(m.h, nullptr, 0.f, m.F, npairs, a.blob, nullptr, s);
+    bamd_launch_quantize_batch(m.h, nullptr, 0.f, m.F, npairs, a.blob, nullptr, s, bamd_act_form_of(m.type_d));
     if (!launch_group_mm<false>(a, n_cu, s)) return 1;
     hipLaunchKernelGGL(moe_combine_kernel, dim3(a.T), dim3(256), 0, s, (const float *) a.prod, m.x, m.E, m.n_used, m.out);
     return 0;

@@ -161,12 +161,14 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_ffn_gate_up(int ty
                                    float eps, float * y) {
     return op_matvec(type, wg_raw, wu_raw, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_SILU_MUL, 0);
 }
+// what an expert tensor may be: a K-quant or a 32-weight block type, gate/up and down independently of each other (bamd_launch_moe_gate_up / _down route by family)
+static bool moe_expert_type(int t) { return bamd_is_kquant(t) || bamd_is_b32(t); }
 // the three MoE launches of a decode step (enqueue_layers) on experts packed as the loader packs them: n_expert consecutive wave-stream matrices per tensor
 extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d,
                                                                         const void * down_exps, int E, int F, int n_expert, int n_used, const float * x, const float * norm_w,
                                                                         float eps, float * y, int32_t * sel, float * w) {
     if (need_device()) return 1;
-    if (!bamd_is_kquant(type_gu) || !bamd_is_kquant(type_d)) return fail("moe_ffn: expert matrices must be of a K-quant type (Q2_K .. Q6_K, IQ4_XS)");
+    if (!moe_expert_type(type_gu) || !moe_expert_type(type_d)) return fail("moe_ffn: expert matrices must be of a type with a routed kernel (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
     if (E <= 0 || F <= 0 || E % 256 || F % 256) return fail("moe_ffn: E and F must be positive multiples of 256");
     if (!bamd_moe_shape_supported(E, F, n_expert, n_used)) return fail("moe_ffn: n_expert must be a multiple of 8 (at most 64), 1 <= n_used <= 8, and the n_used Q8_K activation vectors of F must fit the LDS of a CU");
     Tmp t;
@@ -198,7 +200,7 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn_batch(cons
                                                                               const void * down_exps, int E, int F, int n_expert, int n_used, const float * x, int T,
                                                                               const float * norm_w, float eps, float * y, int32_t * sel, float * w) {
     if (need_device()) return 1;
-    if (!bamd_is_kquant(type_gu) || !bamd_is_kquant(type_d)) return fail("moe_ffn_batch: expert matrices must be of a K-quant type (Q2_K .. Q6_K, IQ4_XS)");
+    if (!moe_expert_type(type_gu) || !moe_expert_type(type_d)) return fail("moe_ffn_batch: expert matrices must be of a type with a routed kernel (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
     if (E <= 0 || F <= 0 || E % 256 || F % 256) return fail("moe_ffn_batch: E and F must be positive multiples of 256");
     if (T < 1 || T > BAMD_PREFILL_CAP) return fail("moe_ffn_batch: 1 <= T <= 512");
     if (!bamd_moe_batch_supported(E, F, n_expert, n_used)) return fail("moe_ffn_batch: the limits of moe_ffn, and four Q8_K activation vectors of the longer of E and F must fit the LDS of a CU");

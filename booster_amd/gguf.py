@@ -425,6 +425,22 @@ def mixtral_q4_k_m_type(name, il, n_layer):
     return Q4_K
 
 
+def mixtral_b32_type(dense_fn):
+    """llama.cpp's Q4_0 / Q5_0 / Q8_0 / Q4_1 / Q5_1 / IQ4_NL recipes for an 8-expert model (llama_tensor_get_type with n_expert == 8), from the dense recipe of the
+    ftype (q4_0_type, q4_0_imatrix_type, q5_0_type, q8_0_type, q4_1_type, q5_1_type, iq4_nl_type, ..): attn_k and attn_v Q8_0 (llama.cpp:15556-15567);
+    attn_output Q5_K under IQ4_NL and the ftype's own type under the others (:15628-15634); ffn_down_exps by the dense ffn_down rule (:15611-15624); the router
+    ffn_gate_inp stays F32; output, token_embd and everything else as the dense recipe has them.  Returns type_fn(name, il, n_layer)."""
+    def fn(name, il, n_layer):
+        if name == "ffn_gate_inp":
+            return F32
+        if name in ("attn_k", "attn_v"):
+            return Q8_0
+        if name == "attn_output" and dense_fn in (iq4_nl_type, iq4_xs_type):
+            return Q5_K
+        return dense_fn(name.replace("_exps", ""), il, n_layer)
+    return fn
+
+
 def q3_k_m_type(name, il, n_layer):
     """llama.cpp's Q3_K_M recipe for the Llama architecture (llama_tensor_get_type, llama.cpp:15435-15660): attn_v Q5_K in layers 0-1, else Q4_K;
     attn_output Q4_K; ffn_down Q5_K for il < n_layer / 16, else Q4_K (the use_more_bits cases of the recipe give Q4_K as well); output Q6_K;

@@ -299,13 +299,14 @@ int bamd_op_ffn_gate_up(int type, const void * wg_raw, const void * wu_raw, int 
                         float eps, float * y);
 /* the mixture-of-experts feed-forward of one token (llm_build_moe_ffn, llama.cpp:8087-8186, behind the ffn RMSNorm) through the three launches of a
  * decode step (router | routed gate/up | routed down + combine): gate_inp = F32 [n_expert][E]; gate_exps / up_exps = n_expert matrices [F][E] of type_gu,
- * down_exps = n_expert matrices [E][F] of type_d, GGUF-layout blocks, expert after expert (the 3-D tensors as they lie in the file); K-quant types only.
+ * down_exps = n_expert matrices [E][F] of type_d, GGUF-layout blocks, expert after expert (the 3-D tensors as they lie in the file); K-quant types and Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL, type_gu and type_d independent.
  * n_expert a multiple of 8, at most 64; 1 <= n_used <= 8.  y[E] = x + MoE output, sel[n_used] = the selected experts, w[n_used] = their normalised weights */
 int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
                     int n_expert, int n_used, const float * x, const float * norm_w, float eps, float * y, int32_t * sel, float * w);
 /* the same for a micro-batch of T tokens (1 <= T <= 512) through the seven launches of a prompt micro-batch (batched router | grouping | Q8_K | grouped gate/up |
  * Q8_K of h | grouped down | combine), bit-identical per token to bamd_op_moe_ffn: x [T][E], y [T][E], sel / w [T][n_used].  Also: four Q8_K activation
- * vectors of the longer of E and F must fit the LDS of a CU (E, F <= 35840) */
+ * vectors of the longer of E and F must fit the LDS of a CU (E, F <= 35840).  The same expert types as bamd_op_moe_ffn, type_gu and type_d independent: launches 3 / 4
+ * and 5 / 6 quantise and multiply in the form of their own tensor (Q8_K, or Q8_0 / Q8_1 for the 32-weight block types, which have no matrix-core grouped kernel) */
 int bamd_op_moe_ffn_batch(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
                           int n_expert, int n_used, const float * x, int T, const float * norm_w, float eps, float * y, int32_t * sel, float * w);
 /* one row of a GGUF matrix dequantised (ggml_compute_forward_get_rows_q, ggml.c:13186) */

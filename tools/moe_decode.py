@@ -6,7 +6,10 @@ after a warm-up — median and range.  Launch kinds: bamd_profile_step_kinds (ev
 steps after a warm-up, medians.  The router and the routed gate/up share kind 4 there; the split of the three routed launches comes from a run of its own
 under the profiler's kernel trace (--only-moe --steps-only: eager steps only, every launch a kernel of a stable name).
 
-    python tools/moe_decode.py [--only-moe] [--steps-only]
+--recipe NAME[,NAME..]: the same shape under other 8-expert recipes, one after another in this process: q4_k_m (the default), and q4_0, q5_0, q8_0, q4_1, q5_1,
+iq4_nl (gguf.mixtral_b32_type: experts of the 32-weight block formats, the routed launches of bamd_moe_b32.h; the Q8_0 file is about 50 GB).
+
+    python tools/moe_decode.py [--only-moe] [--steps-only] [--recipe q4_k_m,q4_0,q8_0]
 """
 import importlib.util
 import os
@@ -25,6 +28,29 @@ gen = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(gen)
 # a model only: no fixture of it is stored
 gen.CONFIGS["8x7b"] = (dict(E=4096, H=32, Hkv=8, L=32, F=14336, V=32000, theta=1000000.0), dict(n_expert=8, n_expert_used=2), "mixtral", 128, 128, 512)
+
+SHAPE_8X7B = gen.CONFIGS["8x7b"][0]
+_spec = importlib.util.spec_from_file_location("gen_moe_b32_fixtures", os.path.join(ROOT, "tests", "golden", "gen_moe_b32_fixtures.py"))
+gen32 = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(gen32)
+B32_RECIPES = {"q4_0": gguf.q4_0_type, "q5_0": gguf.q5_0_type, "q8_0": gguf.q8_0_type, "q4_1": gguf.q4_1_type, "q5_1": gguf.q5_1_type, "iq4_nl": gguf.iq4_nl_type}
+for _r, _fn in B32_RECIPES.items():
+    gen32.CONFIGS["8x7b_" + _r] = (SHAPE_8X7B, dict(n_expert=8, n_expert_used=2), _fn, 128, 128, 512)
+
+
+def recipes():
+    """the names behind --recipe, in order (default: q4_k_m)"""
+    names = sys.argv[sys.argv.index("--recipe") + 1].lower().split(",") if "--recipe" in sys.argv else ["q4_k_m"]
+    for r in names:
+        if r != "q4_k_m" and r not in B32_RECIPES:
+            raise SystemExit("--recipe: %s is none of q4_k_m, %s" % (r, ", ".join(B32_RECIPES)))
+    return names
+
+
+def model_of(recipe):
+    """the 8x7B-shaped file under `recipe`, written on first use"""
+    return gen.ensure_model("8x7b") if recipe == "q4_k_m" else gen32.ensure_model("8x7b_" + recipe)
+
 
 HBM_BYTES_PER_S = 8.0e12                                       # MI355X: 8 TB/s
 KINDS = ["qkv", "attention", "other", "wo", "router + routed gate/up", "routed down + combine", "lm_head"]
@@ -61,8 +87,7 @@ def step_kinds(path, n_prompt=128, reps=5):
 
 
 def main():
-    moe = gen.ensure_model("8x7b")
-    files = [("Mixtral-8x7B shape, Q4_K_M", moe)] + ([] if "--only-moe" in sys.argv else [("Llama-3-8B dense, Q4_K_M", q4_k_m_file())])
+    files = [("Mixtral-8x7B shape, %s" % r.upper(), model_of(r)) for r in recipes()] + ([] if "--only-moe" in sys.argv else [("Llama-3-8B dense, Q4_K_M", q4_k_m_file())])
     for name, p in files:
         total, used, n_expert = streamed_bytes(p)
         print("%-28s file %5.2f GB, matrices %5.2f GB, streamed per token %5.2f GB" % (name, os.path.getsize(p) / 1e9, total / 1e9, used / 1e9), flush=True)

@@ -10,7 +10,10 @@ the file is loaded twice, with set_prefill_moe(False) and (True) — set_prefill
 2048, 8, 16, 32, 64, 128 and 512 tokens alternate between the two models; the side-table bytes and the free memory around the second load are printed.  With
 --once: one 512-token micro-batch of the model with tables.
 
-    python tools/moe_prefill.py [--moe] [--once]
+--recipe NAME[,NAME..] (without --moe): the same measurement under other 8-expert recipes, one after another (tools/moe_decode.py lists them); experts of the
+32-weight block formats take the grouped mat-muls of bamd_moe_batch_b32.hip.
+
+    python tools/moe_prefill.py [--moe] [--once] [--recipe q4_k_m,q4_0,q8_0]
 """
 import os
 import statistics
@@ -18,7 +21,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from moe_decode import b, gen  # noqa: E402  (its 8x7b entry of the generator's CONFIGS)
+from moe_decode import b, gen, model_of, recipes  # noqa: E402  (its 8x7b entry of the generator's CONFIGS)
 
 
 def rate(ctx, prompt, batched):
@@ -83,7 +86,12 @@ def torch_free():
 def main():
     if "--moe" in sys.argv:
         return main_moe()
-    m = b.Model(gen.ensure_model("8x7b"))
+    for recipe in recipes():
+        main_recipe(recipe)
+
+
+def main_recipe(recipe):
+    m = b.Model(model_of(recipe))
     ctx = b.Context(m, 2048)
     prompt = [(7919 * i + 13) % m.n_vocab for i in range(2048)]
     try:
@@ -94,8 +102,8 @@ def main():
             got = alternate(ctx, prompt[:n])
             for batched, name in ((True, "batched"), (False, "token by token")):
                 r = got[batched]
-                print("prompt of %4d tokens, %-14s median %8.1f tok/s  (range %.1f - %.1f, 5 alternating evaluations after a warm-up)"
-                      % (n, name, statistics.median(r), min(r), max(r)), flush=True)
+                print("%-7s prompt of %4d tokens, %-14s median %8.1f tok/s  (range %.1f - %.1f, 5 alternating evaluations after a warm-up)"
+                      % (recipe, n, name, statistics.median(r), min(r), max(r)), flush=True)
     finally:
         b.set_prefill_batch(True)
         ctx.close(); m.close()
