@@ -261,9 +261,12 @@ int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a0, int n_cu, hipStrea
     hipLaunchKernelGGL(moe_router_batch_kernel, dim3(a.T), dim3(512), rlds, s, m);
     hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(512), 0, s, (const int32_t *) m.sel, npairs, m.n_expert, a.tt, a.lists, a.tiles);
     if (mfma) {
-        bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, nullptr, a.blob16, s);
+        // the f16 records in the form of the tensor that reads them (Q8_K, or the Q8_0 / Q8_1 form of a 32-weight block type at the same stride).  The quantiser of
+        // the latter two always writes its int8 image as well, so it gets a.blob; the Q8_K one writes the records alone
+        const int fgu = bamd_act_form_of(m.type_gu), fd = bamd_act_form_of(m.type_d);
+        bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, fgu == BAMD_ACT_Q8_K ? nullptr : a.blob, a.blob16, s, fgu);
         bamd_launch_moe_gate_up_mfma(a, s);
-        bamd_launch_quantize_batch(m.h, nullptr, 0.f, m.F, npairs, nullptr, a.blob16, s);
+        bamd_launch_quantize_batch(m.h, nullptr, 0.f, m.F, npairs, fd == BAMD_ACT_Q8_K ? nullptr : a.blob, a.blob16, s, fd);
         bamd_launch_moe_down_mfma(a, s);
         hipLaunchKernelGGL(moe_combine_kernel, dim3(a.T), dim3(256), 0, s, (const float *) a.prod, m.x, m.E, m.n_used, m.out);
         return 0;

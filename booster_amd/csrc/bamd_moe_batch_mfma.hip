@@ -1,6 +1,8 @@
 // bamd_moe_batch_mfma.hip — the grouped, gathered expert mat-muls of a mixture-of-experts prompt micro-batch on the matrix cores, behind the switch BAMD_PREFILL_MOE /
 // bamd_set_prefill_moe (default off: bamd_prefill_family.cpp): launches 4 and 6 of bamd_moe_batch.hip with the arithmetic of bamd_prefill2.hip, bit-identical per
-// (row, pair) to the grouped integer-dot kernel (moe_group_mm_kernel), and so to the routed decode launches and to llm_build_moe_ffn.  Expert types Q4_K, Q5_K, Q6_K.
+// (row, pair) to the grouped integer-dot kernel (moe_group_mm_kernel), and so to the routed decode launches and to llm_build_moe_ffn.  Expert types Q4_K, Q5_K, Q6_K
+// here; Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL, while their own family switch is on as well, in bamd_moe_batch_b32_mfma.hip (the arithmetic of bamd_prefill2_b32.hip).
+// The host side below routes PER TENSOR: gate / up and down pick their kernel independently and read one tile table (bamd_moe_batch_mfma.h: arguments, bounded reads).
 //   * A tile is 64 weight rows x up to 64 pairs (token, slot) of ONE expert: moe_group_kernel run with tt = 64 writes the pair lists and the tile table.  Grid
 //     (tile bound T n_used / 64 + n_expert, row blocks of 64); the tiles of an expert are adjacent in blockIdx.x, so the workgroups that build fragments from the
 //     same expert rows run together and meet in L2.  A workgroup whose tile index is past tiles[0] exits before its first barrier; what the table and the lists
@@ -16,32 +18,8 @@
 //     kernels keep the code objects they have (profiles/moe_batch_mfma_codeobj.txt).  What is shared are the headers' helpers: the LDS map, XStage's issue, X2Hdr,
 //     x_hsum8, the DMA wrappers.
 #include "bamd_prefill2_body.h"
+#include "bamd_moe_batch_mfma.h"
 
-enum { MOE_GATE = 0, MOE_UP = 1, MOE_DOWN = 2 };
-struct bamd_moe_mma_args {
-    const uint8_t * w; size_t wstride;              // expert 0's wave stream, bytes between experts
-    const uint8_t * aux; size_t astride, ch_off;    // expert 0's side table, bytes between tables, offset of a table's consumer part
-    const uint8_t * blob16;                         // f16 activation records: [T] rows of K = E (gate / up), [T * n_used] rows of K = F (down)
-    const int32_t * lists, * tiles;                 // what moe_group_kernel wrote with tt = 64
-    float * out; const float * wgt;                 // [npairs][nrows]: h (gate / up) or prod (down); down: w[pair]
-    int K, nrows, npairs, n_used, n_expert;
-};
-
-// the tile of this workgroup: false = past the table.  Entries bounded as moe_group_mm_kernel bounds them
-__device__ __forceinline__ bool moe_tile(const bamd_moe_mma_args & a, int & ex, int & first, int & nt) {
-    if ((int) blockIdx.x >= __builtin_amdgcn_readfirstlane(a.tiles[0])) return false;
-    const int32_t * te = a.tiles + 4 + 4 * blockIdx.x;
-    ex = __builtin_amdgcn_readfirstlane(te[0]); first = __builtin_amdgcn_readfirstlane(te[1]); nt = __builtin_amdgcn_readfirstlane(te[2]);
-    ex = ex < 0 ? 0 : ex; ex = ex < a.n_expert ? ex : a.n_expert - 1;
-    nt = nt < 1 ? 1 : nt; nt = nt < 64 ? nt : 64; nt = nt < a.npairs ? nt : a.npairs;
-    first = first < 0 ? 0 : first; first = first <= a.npairs - nt ? first : a.npairs - nt;
-    return true;
-}
-// pair id of slot u of the tile (slots past the count: the last pair again)
-__device__ __forceinline__ int moe_pair(const bamd_moe_mma_args & a, int first, int nt, int u) {
-    int p = a.lists[first + (u < nt ? u : nt - 1)];
-    p = p < 0 ? 0 : p; return p < a.npairs ? p : a.npairs - 1;
-}
 // x_rec_off of the gathered tile: byte offset into blob16 of record chunk idx (slot idx / 38, its chunk idx % 38)
 template <int MODE>
 __device__ __forceinline__ uint32_t moe_rec_off(const bamd_moe_mma_args & a, int first, int nt, int idx, size_t b16) {
@@ -78,7 +56,7 @@ __global__ void __launch_bounds__(1024) moe_mfma3_q4k_kernel(bamd_moe_mma_args a
     constexpr uint32_t RECB = Q5 ? BAMD_RECB_Q5K : BAMD_RECB_Q4K;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int ex, first, nt;
-    if (!moe_tile(a, ex, first, nt)) return;
+    if (!moe_tile(a, blockIdx.x, ex, first, nt)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), m = lane & 15, g = lane >> 4;
     const int rt = wave >> 2, tt = wave & 3;
     const int nb = a.K >> 8;
@@ -279,7 +257,7 @@ __global__ void __launch_bounds__(512) moe_mfma2_q6k_kernel(bamd_moe_mma_args a)
     typedef MoeQ6K F;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     int ex, first, nt;
-    if (!moe_tile(a, ex, first, nt)) return;
+    if (!moe_tile(a, blockIdx.x, ex, first, nt)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), m = lane & 15, g = lane >> 4;
     const int rt = wave >> 1, tp = wave & 1;
     const int nb = a.K >> 8;
@@ -382,7 +360,8 @@ __global__ void __launch_bounds__(512) moe_mfma2_q6k_kernel(bamd_moe_mma_args a)
 // ==== host side ===========================================================================================================================================
 static long long g_moe_batch_mfma_runs = 0;
 extern "C" __attribute__((visibility("default"))) long long bamd_moe_batch_mfma_runs(void) { return g_moe_batch_mfma_runs; }
-static inline bool moe_mfma_type(int type) { return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K; }
+// per tensor: a K-quant with a grouped kernel here, or a 32-weight block type whose own family switch is on (its kernel: bamd_moe_batch_b32_mfma.hip)
+static inline bool moe_mfma_type(int type) { return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || (bamd_is_b32(type) && bamd_prefill_mfma_type(type)); }
 // builder part of a table (bamd_launch_prefill_aux lays it out in front of the consumer part): 4 KiB (Q6_K: 8 KiB) per row block and super-block, two of slack
 static inline size_t moe_ph_bytes(int type, int nrows, int K) { return ((size_t) (nrows / 64) * (size_t) (K >> 8) + 2) * (type == BAMD_Q6_K ? 8192 : 4096); }
 
@@ -394,8 +373,9 @@ static void launch_moe_mma(const bamd_moe_batch_args & b, const void * w, const 
     bamd_moe_mma_args a;
     a.w = (const uint8_t *) w; a.wstride = GU ? m.stride_gu : m.stride_d; a.aux = (const uint8_t *) aux; a.astride = astride;
     a.K = GU ? m.E : m.F; a.nrows = GU ? m.F : m.E; a.npairs = b.T * m.n_used; a.n_used = m.n_used; a.n_expert = m.n_expert;
-    a.ch_off = moe_ph_bytes(type, a.nrows, a.K);
+    a.ch_off = bamd_is_b32(type) ? 0 : moe_ph_bytes(type, a.nrows, a.K);
     a.blob16 = (const uint8_t *) b.blob16; a.lists = b.lists; a.tiles = b.tiles; a.out = GU ? m.h : b.prod; a.wgt = m.w;
+    if (bamd_is_b32(type)) { bamd_launch_moe_mma_b32(a, type, MODE, a.npairs / 64 + m.n_expert, s); bamd_prefill_mfma_count(type); return; }
     const dim3 grid(a.npairs / 64 + m.n_expert, a.nrows / 64);
     auto launch = [&](auto kernel, int threads, size_t lds) { bamd_allow_lds(kernel, lds); hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, a); };
     if (type == BAMD_Q6_K)      launch(moe_mfma2_q6k_kernel<MODE>, 512, X_LDS_BYTES);
@@ -405,6 +385,7 @@ static void launch_moe_mma(const bamd_moe_batch_args & b, const void * w, const 
 }
 int bamd_moe_batch_mfma_ready(const bamd_moe_batch_args & a) {
     const bamd_moe_args & m = a.m;
+    if ((bamd_is_b32(m.type_gu) || bamd_is_b32(m.type_d)) && !a.blob) return 0;      // the Q8_0 / Q8_1 quantiser writes its int8 image beside the f16 records
     return bamd_prefill_moe_on() && a.blob16 && a.aux_g && a.aux_u && a.aux_d && moe_mfma_type(m.type_gu) && moe_mfma_type(m.type_d) && !(m.E & 255) && !(m.F & 255) &&
            a.T * m.n_used <= 4096 && (size_t) a.T * m.n_used * BAMD_BLOB16_BYTES((m.E > m.F ? m.E : m.F) >> 8) < ((size_t) 1 << 32);
 }

@@ -251,7 +251,8 @@ long long bamd_moe_batch_runs(void);
  * and its QKV / wo mat-muls run on the integer-dot kernels; 1 = side tables for QKV, wo and one per expert matrix (Q4_K / Q5_K / Q6_K experts; 104 B per row and 256 weights, Q6_K 72 B,
  * under the budget check of BAMD_PREFILL_AUX_RESERVE_GB), and every batched micro-batch runs the grouped gate, up and down mat-muls on the matrix
  * cores.  It selects by model kind, not by weight type: the 8-expert recipes' Q8_0 attn_k / attn_v need bamd_set_prefill_q0 as well (side tables are
- * all-or-nothing per model).  The tables are decided at model load, the launch path follows the switch at each micro-batch.  Bit-identical results. */
+ * all-or-nothing per model), and experts of Q8_0 / Q4_0 / Q5_0, Q4_1 / Q5_1 or IQ4_NL go to the matrix cores only while their own family's switch
+ * (bamd_set_prefill_q0 / _q1 / _nl) is on too: their per-expert table is the dense one of that family (32 B per row and 256 weights, Q4_1 / Q5_1 64 B).  The tables are decided at model load, the launch path follows the switch at each micro-batch.  Bit-identical results. */
 void bamd_set_prefill_moe(int on);
 /* grouped gate/up launches of that matrix-core path since the library was loaded (bamd_moe_batch_runs counts the integer-dot ones only; bamd_prefill_mfma_runs
  * of the expert type counts every grouped matrix-core launch) */
@@ -306,7 +307,9 @@ int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps,
 /* the same for a micro-batch of T tokens (1 <= T <= 512) through the seven launches of a prompt micro-batch (batched router | grouping | Q8_K | grouped gate/up |
  * Q8_K of h | grouped down | combine), bit-identical per token to bamd_op_moe_ffn: x [T][E], y [T][E], sel / w [T][n_used].  Also: four Q8_K activation
  * vectors of the longer of E and F must fit the LDS of a CU (E, F <= 35840).  The same expert types as bamd_op_moe_ffn, type_gu and type_d independent: launches 3 / 4
- * and 5 / 6 quantise and multiply in the form of their own tensor (Q8_K, or Q8_0 / Q8_1 for the 32-weight block types, which have no matrix-core grouped kernel) */
+ * and 5 / 6 quantise and multiply in the form of their own tensor (Q8_K, or Q8_0 / Q8_1 for the 32-weight block types).  With bamd_set_prefill_moe on, launches 4 / 6
+ * run on the matrix cores while BOTH tensors have a grouped matrix-core kernel now: Q4_K / Q5_K / Q6_K, or a 32-weight block type whose own family switch
+ * (bamd_set_prefill_q0 / _q1 / _nl) is on as well; otherwise both stay on the integer-dot kernels */
 int bamd_op_moe_ffn_batch(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
                           int n_expert, int n_used, const float * x, int T, const float * norm_w, float eps, float * y, int32_t * sel, float * w);
 /* one row of a GGUF matrix dequantised (ggml_compute_forward_get_rows_q, ggml.c:13186) */

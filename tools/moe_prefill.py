@@ -5,13 +5,14 @@ Then the same alternation for prompts of 2, 4, 8 and 16 tokens: where the batche
 launches per layer come from a run of its own under the profiler's kernel trace (--once: one batched 512-token micro-batch, eager, every launch a kernel of a
 stable name).
 
---moe: the matrix-core path of the grouped expert mat-muls (bamd_moe_batch_mfma.hip) against the integer-dot one.  Side tables are decided at model load, so
+--moe: the matrix-core path of the grouped expert mat-muls (bamd_moe_batch_mfma.hip, bamd_moe_batch_b32_mfma.hip) against the integer-dot one.  Side tables are decided at model load, so
 the file is loaded twice, with set_prefill_moe(False) and (True) — set_prefill_q0(True) in both arms: the recipe's Q8_0 attn_k / attn_v — and batched prompts of
 2048, 8, 16, 32, 64, 128 and 512 tokens alternate between the two models; the side-table bytes and the free memory around the second load are printed.  With
 --once: one 512-token micro-batch of the model with tables.
 
---recipe NAME[,NAME..] (without --moe): the same measurement under other 8-expert recipes, one after another (tools/moe_decode.py lists them); experts of the
-32-weight block formats take the grouped mat-muls of bamd_moe_batch_b32.hip.
+--recipe NAME[,NAME..]: the same measurement under other 8-expert recipes, one after another (tools/moe_decode.py lists them); experts of the 32-weight block
+formats take the grouped mat-muls of bamd_moe_batch_b32.hip.  With --moe: the two arms of that recipe's file, its family switches (SWITCHES below) on in BOTH
+arms — such experts go to the matrix cores (bamd_moe_batch_b32_mfma.hip) only while set_prefill_moe AND their own family's switch are on.
 
     python tools/moe_prefill.py [--moe] [--once] [--recipe q4_k_m,q4_0,q8_0]
 """
@@ -21,7 +22,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from moe_decode import b, gen, model_of, recipes  # noqa: E402  (its 8x7b entry of the generator's CONFIGS)
+from moe_decode import b, model_of, recipes  # noqa: E402  (the 8x7b entries of the generators' CONFIGS)
 
 
 def rate(ctx, prompt, batched):
@@ -44,9 +45,15 @@ def alternate(ctx, prompt, reps=5):
     return got
 
 
-def main_moe():
-    path, arms = gen.ensure_model("8x7b"), {}
-    b.set_prefill_q0(True)
+# the family switches a recipe's file needs beside set_prefill_moe for its side tables (all or nothing per model): q0 for the Q8_0 attn_k / attn_v of every recipe
+SWITCHES = {"q4_k_m": ("q0",), "q4_0": ("q0",), "q5_0": ("q0",), "q8_0": ("q0",), "q4_1": ("q0", "q1"), "q5_1": ("q0", "q1"), "iq4_nl": ("q0", "nl")}
+
+
+def main_moe(recipe):
+    path, arms = model_of(recipe), {}
+    for name in SWITCHES[recipe]:
+        getattr(b, "set_prefill_" + name)(True)
+    print("recipe %s, switches on in both arms: %s" % (recipe, ", ".join(SWITCHES[recipe])), flush=True)
     try:
         for on in (False, True) if "--once" not in sys.argv else (True,):
             b.set_prefill_moe(on)
@@ -73,7 +80,8 @@ def main_moe():
                 print("prompt of %4d tokens, experts on %-12s median %8.1f tok/s  (range %.1f - %.1f, 5 alternating evaluations after a warm-up)"
                       % (n, name, statistics.median(got[on]), min(got[on]), max(got[on])), flush=True)
     finally:
-        b.set_prefill_moe(os.environ.get("BAMD_PREFILL_MOE", "")[:1] == "1"); b.set_prefill_q0(os.environ.get("BAMD_PREFILL_Q0", "")[:1] == "1")
+        for name in ("moe",) + SWITCHES[recipe]:
+            getattr(b, "set_prefill_" + name)(os.environ.get("BAMD_PREFILL_" + name.upper(), "")[:1] == "1")
         for m, ctx in arms.values():
             ctx.close(); m.close()
 
@@ -84,10 +92,8 @@ def torch_free():
 
 
 def main():
-    if "--moe" in sys.argv:
-        return main_moe()
     for recipe in recipes():
-        main_recipe(recipe)
+        main_moe(recipe) if "--moe" in sys.argv else main_recipe(recipe)
 
 
 def main_recipe(recipe):
