@@ -230,7 +230,8 @@ def moe_batch_runs():
 def set_prefill_moe(on):
     """True: mixture-of-experts models loaded from now on build side tables (QKV, wo and one per Q4_K / Q5_K / Q6_K expert matrix) and run the grouped expert
     mat-muls of a batched prompt on the matrix cores; False (default, also env BAMD_PREFILL_MOE): on the integer-dot kernel, without tables.  The 8-expert
-    recipes' Q8_0 attn_k / attn_v need set_prefill_q0 as well.  Same bits either way."""
+    recipes' Q8_0 attn_k / attn_v need set_prefill_q0 as well; experts of another type go to the matrix cores while their own family's switch is on too
+    (set_prefill_lowbit: Q3_K / Q2_K, set_prefill_xs: IQ4_XS, set_prefill_q0 / _q1 / _nl: the 32-weight block types).  Same bits either way."""
     lib().bamd_set_prefill_moe(int(bool(on)))
 
 

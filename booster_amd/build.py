@@ -12,8 +12,8 @@ LIB = os.path.join(HERE, "lib", "libbooster_amd.so")
 # the kernels of a decode step are ALSO built as raw gfx950 code objects (same sources, same flags) and embedded in the library: bamd_aql.cpp loads them through
 # HSA and replays a step from the library's own AQL queue (csrc/bamd_aql.h)
 DECODE_KERNEL_SOURCES = ["bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_colaunch.hip", "bamd_moe.hip", "bamd_moe_b32_q0.hip", "bamd_moe_b32_q1.hip", "bamd_moe_b32_nl.hip"]
-SOURCES = ["bamd_aql.cpp", "bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_attention_mfma.hip", "bamd_attention_mfma_ext.hip", "bamd_attention_gs.hip", "bamd_colaunch.hip", "bamd_moe.hip", "bamd_moe_b32_q0.hip", "bamd_moe_b32_q1.hip", "bamd_moe_b32_nl.hip", "bamd_moe_batch.hip", "bamd_moe_batch_b32.hip", "bamd_moe_batch_mfma.hip", "bamd_moe_batch_b32_mfma.hip", "bamd_prefill.hip", "bamd_prefill_b32.hip", "bamd_prefill_b32_nl.hip", "bamd_prefill_flt.hip", "bamd_prefill2.hip", "bamd_prefill2_b32.hip", "bamd_prefill2_flt.hip", "bamd_prefill2_bf16.hip", "bamd_prefill2_xs.hip", "bamd_prefill_family.cpp", "bamd_sampler.hip", "bamd_engine.cpp", "bamd_ops.cpp", "bamd_gguf.cpp", "bamd_vocab.cpp", "bamd_bridge.cpp"]
-HEADERS = ["bamd_aql.h", "bamd_engine_internal.h", "bamd_formats.h", "bamd_kernels.h", "bamd_device.h", "bamd_b32_device.h", "bamd_prefill_b32.h", "bamd_prefill_valu.h", "bamd_prefill_kq.h", "bamd_moe_device.h", "bamd_moe_b32.h", "bamd_prefill_family.h", "bamd_flt_device.h", "bamd_bf16_range.h", "bamd_matvec_b32.h", "bamd_matvec_core.h", "bamd_mv_select.h", "bamd_attn_fused.h", "bamd_attn_batch.h", "bamd_attn_mfma.h", "bamd_mfma_common.h", "bamd_prefill2_body.h", "bamd_prefill2_b32.h", "bamd_moe_batch_mfma.h", "bamd_gguf.h", "bamd_vocab.h", "bamd_unicode_tables.h", "../../include/bamd.h", "../../include/booster_bridge.h"]
+SOURCES = ["bamd_aql.cpp", "bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip", "bamd_matvec_b32_nl.hip", "bamd_matvec_flt.hip", "bamd_matvec_fast_a.hip", "bamd_matvec_fast_b.hip", "bamd_attention.hip", "bamd_attention_mfma.hip", "bamd_attention_mfma_ext.hip", "bamd_attention_gs.hip", "bamd_colaunch.hip", "bamd_moe.hip", "bamd_moe_b32_q0.hip", "bamd_moe_b32_q1.hip", "bamd_moe_b32_nl.hip", "bamd_moe_batch.hip", "bamd_moe_batch_b32.hip", "bamd_moe_batch_mfma.hip", "bamd_moe_batch_b32_mfma.hip", "bamd_moe_batch_kq_mfma.hip", "bamd_moe_batch_xs_mfma.hip", "bamd_prefill.hip", "bamd_prefill_b32.hip", "bamd_prefill_b32_nl.hip", "bamd_prefill_flt.hip", "bamd_prefill2.hip", "bamd_prefill2_b32.hip", "bamd_prefill2_flt.hip", "bamd_prefill2_bf16.hip", "bamd_prefill2_xs.hip", "bamd_prefill_family.cpp", "bamd_sampler.hip", "bamd_engine.cpp", "bamd_ops.cpp", "bamd_gguf.cpp", "bamd_vocab.cpp", "bamd_bridge.cpp"]
+HEADERS = ["bamd_aql.h", "bamd_engine_internal.h", "bamd_formats.h", "bamd_kernels.h", "bamd_device.h", "bamd_b32_device.h", "bamd_prefill_b32.h", "bamd_prefill_valu.h", "bamd_prefill_kq.h", "bamd_moe_device.h", "bamd_moe_b32.h", "bamd_prefill_family.h", "bamd_flt_device.h", "bamd_bf16_range.h", "bamd_matvec_b32.h", "bamd_matvec_core.h", "bamd_mv_select.h", "bamd_attn_fused.h", "bamd_attn_batch.h", "bamd_attn_mfma.h", "bamd_mfma_common.h", "bamd_prefill2_body.h", "bamd_prefill2_b32.h", "bamd_prefill2_lowbit.h", "bamd_prefill2_xs.h", "bamd_moe_batch_mfma.h", "bamd_moe_batch_kq_mfma.h", "bamd_gguf.h", "bamd_vocab.h", "bamd_unicode_tables.h", "../../include/bamd.h", "../../include/booster_bridge.h"]
 # -ffp-contract=off: the numerics contract (bit-parity with the reference CPU path) forbids implicit FMA fusion.
 # -fno-slp-vectorize (decode kernels only, NO_SLP): SLP packs neighbouring f32 multiplies into v_pk_mul_f32, whose operands need
 # even-aligned register pairs: the copies it adds sit right behind the loads (a full s_waitcnt before the weight ring could be
@@ -25,8 +25,10 @@ NO_SLP = ("bamd_matvec.hip", "bamd_matvec_b32_q0.hip", "bamd_matvec_b32_q1.hip",
 KERNARG_PRELOAD = {"bamd_matvec_fast_a.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"], "bamd_matvec_fast_b.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
 # the Q8_0 / Q4_0 / Q5_0, the Q4_1 / Q5_1 and the IQ4_NL instances of the prompt kernel, dense and grouped (mixture-of-experts), chain every MFMA result on the VALU: results in VGPRs (the default puts them in AGPRs and copies each one out)
 MFMA_VGPR_FORM = {"bamd_prefill2_b32.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "bamd_moe_batch_b32_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
-# the IQ4_XS prompt kernel is built without packed f32 instructions: its chain FMAs are scalar v_fma_f32 (same IEEE fma per element)
-NO_PACKED_F32 = {"bamd_prefill2_xs.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# the IQ4_XS prompt kernels, dense and grouped (mixture-of-experts), are built without packed f32 instructions: their chain FMAs are scalar v_fma_f32 (same IEEE fma
+# per element).  The grouped Q3_K / Q2_K instances (bamd_moe_batch_kq_mfma.hip) get the plain FLAGS of the dense ones in bamd_prefill2.hip: SLP and packed f32 kept
+_NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+NO_PACKED_F32 = {"bamd_prefill2_xs.hip": _NO_PK, "bamd_moe_batch_xs_mfma.hip": _NO_PK}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result", "-Wno-unused-value"]
 
 

@@ -961,16 +961,9 @@ static void build_prefill_aux(bamd_model * m, hipStream_t s) {
         for (int i = 0; i < n; ++i) items.push_back({ seg[i].w, seg[i].type, rows[i], m->E, &ly.aux_qkv[i], 1, 0 });
         items.push_back({ ly.wo.stream, ly.wo.type, ly.wo.nrows_pad, m->E, &ly.aux_o, 1, 0 });
         if (m->n_expert > 0) {
-            // BAMD_PREFILL_MOE: a table per expert for the grouped matrix-core mat-muls, which take Q4_K / Q5_K / Q6_K experts (bamd_moe_batch_mfma.hip) and the
-            // 32-weight block types (bamd_moe_batch_b32_mfma.hip).  One of the latter whose own family switch is off falls out below, at its table size of zero,
-            // with the sentence that names the switch
-            for (int t : { ly.type_gu, ly.type_d })
-                if (t != BAMD_Q4_K && t != BAMD_Q5_K && t != BAMD_Q6_K && !bamd_is_b32(t)) {
-                    m->aux_why = std::string("the model holds ") + (t == BAMD_Q2_K ? "Q2_K" : t == BAMD_Q3_K ? "Q3_K" : "IQ4_XS") + " expert matrices, which have no matrix-core grouped kernel: the grouped matrix-core mat-muls "
-                                 "(BAMD_PREFILL_MOE) take Q4_K / Q5_K / Q6_K experts and, with BAMD_PREFILL_Q0 / _Q1 / _NL on, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL experts, and "
-                                 "side tables are all-or-nothing per model, so every prompt mat-mul runs on the integer-dot kernel";
-                    return;
-                }
+            // BAMD_PREFILL_MOE: a table per expert for the grouped matrix-core mat-muls, which take Q4_K / Q5_K / Q6_K experts (bamd_moe_batch_mfma.hip), Q3_K / Q2_K /
+            // IQ4_XS ones (bamd_moe_batch_kq_mfma.hip) and the 32-weight block types (bamd_moe_batch_b32_mfma.hip).  A type of the latter two groups whose own family
+            // switch is off falls out below, at its table size of zero, with the sentence that names the switch
             items.push_back({ ly.exp_g, ly.type_gu, m->F, m->E, &ly.aux_g, m->n_expert, ly.stride_gu });
             items.push_back({ ly.exp_u, ly.type_gu, m->F, m->E, &ly.aux_u, m->n_expert, ly.stride_gu });
             items.push_back({ ly.exp_d, ly.type_d, m->E, m->F, &ly.aux_d, m->n_expert, ly.stride_d });

@@ -189,6 +189,8 @@ int  bamd_launch_matmul_batch_b32(const bamd_mm_args & a, int epi, int n_cu, hip
 int  bamd_prefill_mfma_supported(void);      // the current device accepts the kernels' LDS size (asked at model load)
 // which weight types have such a kernel now, and the switches they are behind (bamd_prefill_mfma_type and its kin): bamd_prefill_family.h
 size_t bamd_prefill_aux_bytes(int type, int nrows_pad, int K);
+size_t bamd_prefill_aux_ph_bytes(int type, int nrows_pad, int K);      // K-quants: bytes of a table's builder part = offset of its consumer part
+int    bamd_moe_mma_kq_supported(void);                                // the grouped Q3_K / Q2_K / IQ4_XS kernels' LDS attribute (bamd_moe_batch_kq_mfma.hip)
 void bamd_launch_prefill_aux(const void * w_stream, int type, int nrows_pad, int K, void * aux, hipStream_t s);
 int  bamd_launch_matmul_mfma2(const void * w_stream, const void * aux, int type, int nrows, int nrows_pad, int K, const void * blob16, int T, float * out, const float * res,
                               int epi, int ldo, hipStream_t s);

@@ -1,7 +1,8 @@
 // bamd_moe_batch_mfma.hip — the grouped, gathered expert mat-muls of a mixture-of-experts prompt micro-batch on the matrix cores, behind the switch BAMD_PREFILL_MOE /
 // bamd_set_prefill_moe (default off: bamd_prefill_family.cpp): launches 4 and 6 of bamd_moe_batch.hip with the arithmetic of bamd_prefill2.hip, bit-identical per
 // (row, pair) to the grouped integer-dot kernel (moe_group_mm_kernel), and so to the routed decode launches and to llm_build_moe_ffn.  Expert types Q4_K, Q5_K, Q6_K
-// here; Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL, while their own family switch is on as well, in bamd_moe_batch_b32_mfma.hip (the arithmetic of bamd_prefill2_b32.hip).
+// here; while their own family switch is on as well, Q3_K / Q2_K / IQ4_XS in bamd_moe_batch_kq_mfma.hip / bamd_moe_batch_xs_mfma.hip (the dense eight-wave body under
+// its policies, with dead slot tiles skipped) and Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL in bamd_moe_batch_b32_mfma.hip (the arithmetic of bamd_prefill2_b32.hip).
 // The host side below routes PER TENSOR: gate / up and down pick their kernel independently and read one tile table (bamd_moe_batch_mfma.h: arguments, bounded reads).
 //   * A tile is 64 weight rows x up to 64 pairs (token, slot) of ONE expert: moe_group_kernel run with tt = 64 writes the pair lists and the tile table.  Grid
 //     (tile bound T n_used / 64 + n_expert, row blocks of 64); the tiles of an expert are adjacent in blockIdx.x, so the workgroups that build fragments from the
@@ -16,33 +17,9 @@
 //   * Two kernel shapes, as the dense path: sixteen waves with one 16 x 16 tile each for Q4_K / Q5_K (the step of matmul_mfma3_q4k_kernel), eight waves with 16 x 32
 //     each for Q6_K (the half step of matmul_mfma2_kernel under X2Q6K: split scale, two chained MFMAs).  The bodies are written out here, not shared: the dense
 //     kernels keep the code objects they have (profiles/moe_batch_mfma_codeobj.txt).  What is shared are the headers' helpers: the LDS map, XStage's issue, X2Hdr,
-//     x_hsum8, the DMA wrappers.
+//     x_hsum8, the DMA wrappers; moe_rec_off and moe_store (bamd_moe_batch_mfma.h) serve the eight-wave kernels of the other files as well.
 #include "bamd_prefill2_body.h"
 #include "bamd_moe_batch_mfma.h"
-
-// x_rec_off of the gathered tile: byte offset into blob16 of record chunk idx (slot idx / 38, its chunk idx % 38)
-template <int MODE>
-__device__ __forceinline__ uint32_t moe_rec_off(const bamd_moe_mma_args & a, int first, int nt, int idx, size_t b16) {
-    const int u = idx / BAMD_B16_Q, q = idx - u * BAMD_B16_Q, p = moe_pair(a, first, nt, u);
-    return (uint32_t) ((size_t) (MODE == MOE_DOWN ? p : p / a.n_used) * b16 + (size_t) q * 16);
-}
-// rows row0 .. row0 + 3 of pair p: 16 consecutive, 16-byte aligned bytes (nrows is a multiple of 256)
-template <int MODE>
-__device__ __forceinline__ void moe_store(const bamd_moe_mma_args & a, int p, int row0, const float (&val)[4]) {
-    float * o = a.out + (size_t) p * a.nrows + row0;
-    bamd_f4 y = { val[0], val[1], val[2], val[3] };
-    if (MODE == MOE_UP) {
-        const bamd_f4 r = *(const bamd_f4 *) o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) y[i] = v_silu(r[i]) * val[i];
-    }
-    if (MODE == MOE_DOWN) {
-        const float wp = a.wgt[p];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) y[i] = val[i] * wp;
-    }
-    *(bamd_f4 *) o = y;
-}
 
 // ==== sixteen waves, Q4_K / Q5_K: the LDS map, staging plan, builder and step of matmul_mfma3_q4k_kernel (bamd_prefill2.hip has the reasons) ======================
 #define X3_BLK (X_BS_BYTES + X3_CHS + 4096 + 32)           /* records (38 KiB) | headers (3 KiB) | operands (4 KiB) | 32 bytes of zeros: 46 112 B */
@@ -360,10 +337,10 @@ __global__ void __launch_bounds__(512) moe_mfma2_q6k_kernel(bamd_moe_mma_args a)
 // ==== host side ===========================================================================================================================================
 static long long g_moe_batch_mfma_runs = 0;
 extern "C" __attribute__((visibility("default"))) long long bamd_moe_batch_mfma_runs(void) { return g_moe_batch_mfma_runs; }
-// per tensor: a K-quant with a grouped kernel here, or a 32-weight block type whose own family switch is on (its kernel: bamd_moe_batch_b32_mfma.hip)
-static inline bool moe_mfma_type(int type) { return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || (bamd_is_b32(type) && bamd_prefill_mfma_type(type)); }
-// builder part of a table (bamd_launch_prefill_aux lays it out in front of the consumer part): 4 KiB (Q6_K: 8 KiB) per row block and super-block, two of slack
-static inline size_t moe_ph_bytes(int type, int nrows, int K) { return ((size_t) (nrows / 64) * (size_t) (K >> 8) + 2) * (type == BAMD_Q6_K ? 8192 : 4096); }
+// per tensor: a K-quant with a grouped kernel here, or a type whose own family switch is on: Q3_K / Q2_K / IQ4_XS (bamd_moe_batch_kq_mfma.hip) and the 32-weight
+// block types (bamd_moe_batch_b32_mfma.hip)
+static inline bool moe_kq_type(int type) { return type == BAMD_Q3_K || type == BAMD_Q2_K || type == BAMD_IQ4_XS; }
+static inline bool moe_mfma_type(int type) { return type == BAMD_Q4_K || type == BAMD_Q5_K || type == BAMD_Q6_K || ((bamd_is_b32(type) || moe_kq_type(type)) && bamd_prefill_mfma_type(type)); }
 
 template <int MODE>
 static void launch_moe_mma(const bamd_moe_batch_args & b, const void * w, const void * aux, size_t astride, hipStream_t s) {
@@ -373,9 +350,10 @@ static void launch_moe_mma(const bamd_moe_batch_args & b, const void * w, const 
     bamd_moe_mma_args a;
     a.w = (const uint8_t *) w; a.wstride = GU ? m.stride_gu : m.stride_d; a.aux = (const uint8_t *) aux; a.astride = astride;
     a.K = GU ? m.E : m.F; a.nrows = GU ? m.F : m.E; a.npairs = b.T * m.n_used; a.n_used = m.n_used; a.n_expert = m.n_expert;
-    a.ch_off = bamd_is_b32(type) ? 0 : moe_ph_bytes(type, a.nrows, a.K);
+    a.ch_off = bamd_is_b32(type) ? 0 : bamd_prefill_aux_ph_bytes(type, a.nrows, a.K);      // the builder part, as bamd_launch_prefill_aux lays it out in front of the consumer part
     a.blob16 = (const uint8_t *) b.blob16; a.lists = b.lists; a.tiles = b.tiles; a.out = GU ? m.h : b.prod; a.wgt = m.w;
     if (bamd_is_b32(type)) { bamd_launch_moe_mma_b32(a, type, MODE, a.npairs / 64 + m.n_expert, s); bamd_prefill_mfma_count(type); return; }
+    if (moe_kq_type(type)) { bamd_launch_moe_mma_kq(a, type, MODE, a.npairs / 64 + m.n_expert, s); bamd_prefill_mfma_count(type); return; }
     const dim3 grid(a.npairs / 64 + m.n_expert, a.nrows / 64);
     auto launch = [&](auto kernel, int threads, size_t lds) { bamd_allow_lds(kernel, lds); hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, a); };
     if (type == BAMD_Q6_K)      launch(moe_mfma2_q6k_kernel<MODE>, 512, X_LDS_BYTES);

@@ -429,13 +429,18 @@ def mixtral_b32_type(dense_fn):
     """llama.cpp's Q4_0 / Q5_0 / Q8_0 / Q4_1 / Q5_1 / IQ4_NL recipes for an 8-expert model (llama_tensor_get_type with n_expert == 8), from the dense recipe of the
     ftype (q4_0_type, q4_0_imatrix_type, q5_0_type, q8_0_type, q4_1_type, q5_1_type, iq4_nl_type, ..): attn_k and attn_v Q8_0 (llama.cpp:15556-15567);
     attn_output Q5_K under IQ4_NL and the ftype's own type under the others (:15628-15634); ffn_down_exps by the dense ffn_down rule (:15611-15624); the router
-    ffn_gate_inp stays F32; output, token_embd and everything else as the dense recipe has them.  Returns type_fn(name, il, n_layer)."""
+    ffn_gate_inp stays F32; output, token_embd and everything else as the dense recipe has them.  Returns type_fn(name, il, n_layer).
+    The same rules give the 8-expert forms of the Q3_K_M, Q2_K and IQ4_XS recipes from q3_k_m_type, q2_k_type and iq4_xs_type: attn_k and attn_v Q8_0 (:15556-15567,
+    behind whatever the ftype chose for attn_v); attn_output Q5_K, these three ftypes being on the list at :15629-15633 (the dense Q4_K / Q3_K of :15636-15638 is the
+    other branch); ffn_down_exps by the ftype's ffn_down rule with the layer parsed from the tensor name (layer_info, :15446-15460) — Q3_K_M: Q5_K for
+    il < n_layer / 16, else Q4_K (:15591-15595); Q2_K: Q3_K (:15584); IQ4_XS: Q5_K for il < n_layer / 8 without an importance matrix, else IQ4_XS (:15611-15613);
+    ffn_gate_exps / ffn_up_exps keep the ftype's default type (:15653-15667 change them for IQ3_XS only)."""
     def fn(name, il, n_layer):
         if name == "ffn_gate_inp":
             return F32
         if name in ("attn_k", "attn_v"):
             return Q8_0
-        if name == "attn_output" and dense_fn in (iq4_nl_type, iq4_xs_type):
+        if name == "attn_output" and dense_fn in (iq4_nl_type, iq4_xs_type, q3_k_m_type, q2_k_type):
             return Q5_K
         return dense_fn(name.replace("_exps", ""), il, n_layer)
     return fn

@@ -252,7 +252,8 @@ long long bamd_moe_batch_runs(void);
  * under the budget check of BAMD_PREFILL_AUX_RESERVE_GB), and every batched micro-batch runs the grouped gate, up and down mat-muls on the matrix
  * cores.  It selects by model kind, not by weight type: the 8-expert recipes' Q8_0 attn_k / attn_v need bamd_set_prefill_q0 as well (side tables are
  * all-or-nothing per model), and experts of Q8_0 / Q4_0 / Q5_0, Q4_1 / Q5_1 or IQ4_NL go to the matrix cores only while their own family's switch
- * (bamd_set_prefill_q0 / _q1 / _nl) is on too: their per-expert table is the dense one of that family (32 B per row and 256 weights, Q4_1 / Q5_1 64 B).  The tables are decided at model load, the launch path follows the switch at each micro-batch.  Bit-identical results. */
+ * (bamd_set_prefill_q0 / _q1 / _nl) is on too: their per-expert table is the dense one of that family (32 B per row and 256 weights, Q4_1 / Q5_1 64 B).  Q3_K / Q2_K and IQ4_XS
+ * experts likewise, with bamd_set_prefill_lowbit / bamd_set_prefill_xs and the dense tables of those types.  The tables are decided at model load, the launch path follows the switch at each micro-batch.  Bit-identical results. */
 void bamd_set_prefill_moe(int on);
 /* grouped gate/up launches of that matrix-core path since the library was loaded (bamd_moe_batch_runs counts the integer-dot ones only; bamd_prefill_mfma_runs
  * of the expert type counts every grouped matrix-core launch) */

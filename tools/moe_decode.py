@@ -7,7 +7,8 @@ steps after a warm-up, medians.  The router and the routed gate/up share kind 4 
 under the profiler's kernel trace (--only-moe --steps-only: eager steps only, every launch a kernel of a stable name).
 
 --recipe NAME[,NAME..]: the same shape under other 8-expert recipes, one after another in this process: q4_k_m (the default), and q4_0, q5_0, q8_0, q4_1, q5_1,
-iq4_nl (gguf.mixtral_b32_type: experts of the 32-weight block formats, the routed launches of bamd_moe_b32.h; the Q8_0 file is about 50 GB).
+iq4_nl (gguf.mixtral_b32_type: experts of the 32-weight block formats, the routed launches of bamd_moe_b32.h; the Q8_0 file is about 50 GB), and q3_k_m, q2_k,
+iq4_xs (the same function over the dense K-quant recipes: Q3_K / Q2_K / IQ4_XS gate and up experts, Q4_K / Q3_K / Q5_K and IQ4_XS down experts).
 
     python tools/moe_decode.py [--only-moe] [--steps-only] [--recipe q4_k_m,q4_0,q8_0]
 """
@@ -34,6 +35,7 @@ _spec = importlib.util.spec_from_file_location("gen_moe_b32_fixtures", os.path.j
 gen32 = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(gen32)
 B32_RECIPES = {"q4_0": gguf.q4_0_type, "q5_0": gguf.q5_0_type, "q8_0": gguf.q8_0_type, "q4_1": gguf.q4_1_type, "q5_1": gguf.q5_1_type, "iq4_nl": gguf.iq4_nl_type}
+B32_RECIPES.update({"q3_k_m": gguf.q3_k_m_type, "q2_k": gguf.q2_k_type, "iq4_xs": gguf.iq4_xs_type})      # (K-quant experts through the same 8-expert rules)
 for _r, _fn in B32_RECIPES.items():
     gen32.CONFIGS["8x7b_" + _r] = (SHAPE_8X7B, dict(n_expert=8, n_expert_used=2), _fn, 128, 128, 512)
 

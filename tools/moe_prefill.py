@@ -5,14 +5,15 @@ Then the same alternation for prompts of 2, 4, 8 and 16 tokens: where the batche
 launches per layer come from a run of its own under the profiler's kernel trace (--once: one batched 512-token micro-batch, eager, every launch a kernel of a
 stable name).
 
---moe: the matrix-core path of the grouped expert mat-muls (bamd_moe_batch_mfma.hip, bamd_moe_batch_b32_mfma.hip) against the integer-dot one.  Side tables are decided at model load, so
+--moe: the matrix-core path of the grouped expert mat-muls (bamd_moe_batch_mfma.hip, bamd_moe_batch_kq_mfma.hip, bamd_moe_batch_b32_mfma.hip) against the integer-dot one.  Side tables are decided at model load, so
 the file is loaded twice, with set_prefill_moe(False) and (True) — set_prefill_q0(True) in both arms: the recipe's Q8_0 attn_k / attn_v — and batched prompts of
 2048, 8, 16, 32, 64, 128 and 512 tokens alternate between the two models; the side-table bytes and the free memory around the second load are printed.  With
 --once: one 512-token micro-batch of the model with tables.
 
 --recipe NAME[,NAME..]: the same measurement under other 8-expert recipes, one after another (tools/moe_decode.py lists them); experts of the 32-weight block
 formats take the grouped mat-muls of bamd_moe_batch_b32.hip.  With --moe: the two arms of that recipe's file, its family switches (SWITCHES below) on in BOTH
-arms — such experts go to the matrix cores (bamd_moe_batch_b32_mfma.hip) only while set_prefill_moe AND their own family's switch are on.
+arms — such experts, and Q3_K / Q2_K / IQ4_XS ones (recipes q3_k_m, q2_k, iq4_xs: switches lowbit / xs), go to the matrix cores only while set_prefill_moe AND
+their own family's switch are on.
 
     python tools/moe_prefill.py [--moe] [--once] [--recipe q4_k_m,q4_0,q8_0]
 """
@@ -46,7 +47,8 @@ def alternate(ctx, prompt, reps=5):
 
 
 # the family switches a recipe's file needs beside set_prefill_moe for its side tables (all or nothing per model): q0 for the Q8_0 attn_k / attn_v of every recipe
-SWITCHES = {"q4_k_m": ("q0",), "q4_0": ("q0",), "q5_0": ("q0",), "q8_0": ("q0",), "q4_1": ("q0", "q1"), "q5_1": ("q0", "q1"), "iq4_nl": ("q0", "nl")}
+SWITCHES = {"q4_k_m": ("q0",), "q4_0": ("q0",), "q5_0": ("q0",), "q8_0": ("q0",), "q4_1": ("q0", "q1"), "q5_1": ("q0", "q1"), "iq4_nl": ("q0", "nl"),
+            "q3_k_m": ("q0", "lowbit"), "q2_k": ("q0", "lowbit"), "iq4_xs": ("q0", "xs")}
 
 
 def main_moe(recipe):
