@@ -258,12 +258,12 @@ static int upload_experts(bamd_model * m, const GgufTensor * t, const std::strin
     if (!t) return fail("missing tensor " + name);
     if (t->ne.size() != 3 || (int) t->ne[0] != K || (int) t->ne[1] != nrows || (int) t->ne[2] != m->n_expert)
         return fail("tensor " + name + ": expected [" + std::to_string(K) + ", " + std::to_string(nrows) + ", " + std::to_string(m->n_expert) + "]");
-    if (!bamd_is_kquant(t->type) && !bamd_is_b32(t->type)) return fail("tensor " + name + ": expert matrices of type " + std::to_string(t->type) + " are not supported (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
+    if (!bamd_is_kquant(t->type) && !bamd_is_b32(t->type) && !bamd_is_flt(t->type)) return fail("tensor " + name + ": expert matrices of type " + std::to_string(t->type) + " are not supported (F32, F16, BF16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
     *type = t->type; *stride = bamd_stream_bytes(t->type, K, nrows); *bytes = t->nbytes / (size_t) m->n_expert;
     if (*stride >= (size_t) 0x7fffffff) return fail("tensor " + name + ": one expert's wave-stream copy exceeds 2 GiB (32-bit record offsets)");
     if (dev_alloc(m->allocs, dst, *stride * (size_t) m->n_expert)) return 1;
     HIPC(hipMemcpyAsync(staging, t->data, t->nbytes, hipMemcpyHostToDevice, s));
-    for (int e = 0; e < m->n_expert; ++e) bamd_launch_repack((const char *) staging + (size_t) e * *bytes, (char *) *dst + (size_t) e * *stride, t->type, nrows, K, s);
+    for (int e = 0; e < m->n_expert; ++e) bamd_launch_repack_expert((const char *) staging + (size_t) e * *bytes, (char *) *dst + (size_t) e * *stride, t->type, nrows, K, s);
     HIPC(hipGetLastError());
     m->weight_bytes += (int64_t) t->nbytes;
     HIPC(hipStreamSynchronize(s));     // staging buffer is reused by the next tensor
@@ -404,7 +404,11 @@ static int model_load_impl(bamd_model * m, const char * path, int device, int lf
                 if (tg && tu && tg->type != tu->type) { rc = fail("ffn_gate_exps and ffn_up_exps must share one quantisation type"); break; }     // before anything is uploaded
                 if ((rc = upload_experts(m, tg, p + "ffn_gate_exps.weight", m->E, m->F, &ly.exp_g, &ly.type_gu, &ly.stride_gu, &ly.bytes_gu, staging, s))) break;
                 if ((rc = upload_experts(m, tu, p + "ffn_up_exps.weight", m->E, m->F, &ly.exp_u, &ly.type_gu, &ly.stride_gu, &ly.bytes_gu, staging, s))) break;  // one type: the same values again
-                if ((rc = upload_experts(m, g.tensor(p + "ffn_down_exps.weight"), p + "ffn_down_exps.weight", m->F, m->E, &ly.exp_d, &ly.type_d, &ly.stride_d, &ly.bytes_d, staging, s))) break;
+                // an unquantised ffn_down_exps keeps n_used images of 2 (F16 / BF16) or 4 (F32) bytes a value in the LDS of a CU: more than the Q8_K ones the header was checked with
+                const GgufTensor * td = g.tensor(p + "ffn_down_exps.weight");
+                if (td && bamd_is_flt(td->type) && !bamd_moe_shape_supported(m->E, m->F, m->n_expert, m->n_expert_used, td->type)) {
+                    rc = fail("tensor " + p + "ffn_down_exps.weight: the " + (td->type == BAMD_F32 ? "f32" : td->type == BAMD_F16 ? "f16" : "bf16") + " activations of " + std::to_string(m->n_expert_used) + " slots of n_ff " + std::to_string(m->F) + " do not fit the LDS of a CU (routed down launch)"); break; }
+                if ((rc = upload_experts(m, td, p + "ffn_down_exps.weight", m->F, m->E, &ly.exp_d, &ly.type_d, &ly.stride_d, &ly.bytes_d, staging, s))) break;
             } else {
                 if (ly.wg.nrows != m->F || ly.wg.K != m->E || ly.wu.nrows != m->F || ly.wu.K != m->E || ly.wd.nrows != m->E || ly.wd.K != m->F) { rc = fail("layer " + std::to_string(il) + ": unexpected tensor shapes"); break; }
                 if (ly.wg.type != ly.wu.type) { rc = fail("ffn_gate and ffn_up must share one quantisation type"); break; }
@@ -936,6 +940,8 @@ static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStre
     // token by token through the routed decode kernels (same bits).  So do its prompts of fewer than 8 tokens: seven launches per layer for a tile or two of pairs
     // measured slower than the routed launches at 2 and 4 tokens and faster from 8 on (profiles/moe_prefill.txt, the 8x7B shape)
     if (m->n_expert > 0 && (T < BAMD_MOE_BATCH_MIN_T || !bamd_moe_batch_supported(m->E, m->F, m->n_expert, m->n_expert_used))) return false;
+    // (unquantised experts: four images of the row in the tensor's own form, 2 or 4 bytes a value — an F32 ffn_down_exps of the 8x7B shape goes token by token)
+    if (m->n_expert > 0) for (const DevLayer & ly : m->layers) if (!bamd_moe_batch_supported(m->E, m->F, m->n_expert, m->n_expert_used, ly.type_gu, ly.type_d)) return false;
     if (!(g_prefill_batch && g_attn_fused && m->hd <= 256 && (m->hd & 63) == 0 && gq >= 1 && gq <= 8)) return false;
     // every mat-mul needs a kernel: the matrix-core kernels take every K-quant at any K when the model has its side tables; the integer-dot kernel
     // takes any K-quant while 4 tokens of Q8_K activations fit the LDS (K <= 35840; tiles of 8 tokens up to K = 17920)
@@ -951,6 +957,8 @@ static bool prefill_batch_supported(bamd_context * c, int T, int n_past, hipStre
 // enqueue_prefill_batch launches (qkv_segments).  All or nothing.
 static void build_prefill_aux(bamd_model * m, hipStream_t s) {
     if (m->n_expert > 0 && !bamd_prefill_moe_on()) { m->aux_why = "a mixture-of-experts model batches its expert mat-muls on the integer-dot kernel, which has no matrix-core variant, and its QKV / wo mat-muls stay on the integer-dot kernel too: no side tables are built"; return; }
+    for (const DevLayer & ly : m->layers) if (m->n_expert > 0 && (bamd_is_flt(ly.type_gu) || bamd_is_flt(ly.type_d))) {
+        m->aux_why = "F32 / F16 / BF16 experts have no matrix-core grouped kernel: their grouped mat-muls run on the VALU kernel (bamd_moe_batch_flt.hip), and the model's QKV / wo mat-muls stay off the matrix cores too: no side tables are built"; return; }
     if (!g_prefill_aux) { m->aux_why = "switched off (BAMD_PREFILL_AUX=0)"; return; }
     if (!bamd_prefill_mfma_supported()) { m->aux_why = "the device refuses the matrix-core kernels' LDS size"; return; }
     struct Item { const void * w; int type, nrows, K; void ** slot; int count; size_t wstride; };      // count tables, one per matrix w + i * wstride, in one allocation
@@ -1014,7 +1022,8 @@ static int ensure_batch_buffers(bamd_context * c) {
     if (c->bcap) return 0;
     bamd_model * m = c->m;
     const size_t T = BAMD_PREFILL_CAP, Ekv = (size_t) m->Hkv * m->hd, NU = (size_t) std::max(m->n_expert_used, 1);
-    const size_t moe_blob = m->n_expert > 0 ? bamd_moe_batch_blob_bytes((int) T, m->E, m->F, m->n_expert_used) : 0;
+    size_t moe_blob = m->n_expert > 0 ? bamd_moe_batch_blob_bytes((int) T, m->E, m->F, m->n_expert_used) : 0;
+    if (m->n_expert > 0) for (const DevLayer & ly : m->layers) moe_blob = std::max(moe_blob, bamd_moe_batch_blob_bytes((int) T, m->E, m->F, m->n_expert_used, ly.type_gu, ly.type_d));   // (unquantised experts: larger images)
     const size_t moe_blob16 = m->n_expert > 0 && m->aux_ok ? bamd_moe_batch_blob16_bytes((int) T, m->E, m->F, m->n_expert_used) : 0;      // (a model with tables: the f16 records of the pairs' rows of h)
     size_t flt_bytes = 0;
     for (const DevLayer & ly : m->layers)

@@ -76,14 +76,16 @@ struct bamd_moe_args {
     int E, F, n_expert, n_used;
     const void * gate_inp;         // F32 wave stream [n_expert][E]
     const void * wg, * wu, * wd;   // n_expert consecutive wave-stream matrices each: gate / up [F][E] (stride_gu bytes apart), down [E][F] (stride_d)
-    int type_gu, type_d;           // independent of each other: a K-quant (bamd_is_kquant) or a 32-weight block type (bamd_is_b32)
+    int type_gu, type_d;           // independent of each other: a K-quant (bamd_is_kquant), a 32-weight block type (bamd_is_b32) or an unquantised one (bamd_is_flt)
     size_t stride_gu, stride_d;
     int32_t * sel; float * w;      // [n_used]: the selected experts and their normalised weights, router -> the other two launches
     float * h;                     // [n_used][F]: silu(gate) * up of every slot, gate/up -> down
     float * out;                   // [E] = x + sum over the slots of (down_s * w_s); must not alias x
     int tile;                      // output row-groups per workgroup of the down launch (set by its launcher)
 };
-int  bamd_moe_shape_supported(int E, int F, int n_expert, int n_used);     // the limits the three launchers check (the loader refuses everything else by name)
+// the limits the three launchers check (the loader refuses everything else by name).  type_d: the down launch keeps n_used activation images of F values in the LDS
+// of a CU, Q8_K ones (every quantised type is checked at that size) or, for an unquantised type_d, 2 (F16 / BF16) or 4 (F32) bytes a value
+int  bamd_moe_shape_supported(int E, int F, int n_expert, int n_used, int type_d = BAMD_Q4_K);
 [[nodiscard]] int bamd_launch_moe_router(const bamd_moe_args & a, hipStream_t s);                // 1 = shape not supported (nothing launched), here and below
 [[nodiscard]] int bamd_launch_moe_gate_up(const bamd_moe_args & a, int n_cu, hipStream_t s);     // 1 also for a type without a routed kernel; routes by the family of type_gu
 [[nodiscard]] int bamd_launch_moe_down(const bamd_moe_args & a, int n_cu, hipStream_t s);        // the same by type_d
@@ -95,6 +97,13 @@ int bamd_launch_moe_gate_up_b32_nl(const bamd_moe_args & a, int tiles, hipStream
 int bamd_launch_moe_down_b32_q0(const bamd_moe_args & a, hipStream_t s);
 int bamd_launch_moe_down_b32_q1(const bamd_moe_args & a, hipStream_t s);
 int bamd_launch_moe_down_b32_nl(const bamd_moe_args & a, hipStream_t s);
+// the routed launches and the expert repack of the unquantised types F16 / F32 / BF16 (bamd_moe_flt.hip), behind the same two; an expert matrix of these types is
+// NOT packed as a dense one (F16 / F32: 32 chain lanes per row, bamd_moe_flt_device.h), so whoever packs an expert tensor calls bamd_launch_repack_expert, which
+// hands every other type to bamd_launch_repack
+void bamd_launch_repack_expert(const void * raw, void * dst, int type, int nrows, int K, hipStream_t s);
+int  bamd_moe_flt_down_fits(int type, int F, int n_used);                 // the n_used images of F values and the largest product tile fit the LDS of a CU
+int  bamd_launch_moe_gate_up_flt(const bamd_moe_args & a, int tiles, hipStream_t s);
+int  bamd_launch_moe_down_flt(const bamd_moe_args & a, hipStream_t s);
 // the same feed-forward for a micro-batch of T tokens (bamd_moe_batch.hip): batched router | grouping | Q8_K of the normed rows | grouped gate/up | Q8_K of h |
 // grouped down | combine.  A pair is (token t, slot s), its id t * n_used + s
 struct bamd_moe_group_args {       // what the grouped integer-dot kernels take as their kernel argument
@@ -117,12 +126,20 @@ size_t bamd_moe_batch_blob16_bytes(int T, int E, int F, int n_used);
 int    bamd_moe_batch_mfma_ready(const bamd_moe_batch_args & a);              // 1 = bamd_launch_moe_ffn_batch takes the matrix-core kernels for these arguments under the current switch
 void   bamd_launch_moe_gate_up_mfma(const bamd_moe_batch_args & a, hipStream_t s);      // its launches 4 (gate, then up) and 6 on the matrix cores
 void   bamd_launch_moe_down_mfma(const bamd_moe_batch_args & a, hipStream_t s);
-int    bamd_moe_batch_supported(int E, int F, int n_expert, int n_used);      // bamd_moe_shape_supported, and four Q8_K images of the longer of E and F fit the LDS of a CU
+// bamd_moe_shape_supported, and four Q8_K images of the longer of E and F fit the LDS of a CU; for an unquantised type_gu / type_d also four images of E / of F in
+// its form (bamd_moe_flt_group_tt).  The blob holds the images of the T normed rows, then of the T * n_used rows of h, each in the form of the launch that reads it
+int    bamd_moe_batch_supported(int E, int F, int n_expert, int n_used, int type_gu = BAMD_Q4_K, int type_d = BAMD_Q4_K);
 size_t bamd_moe_batch_tiles_bytes(int T, int n_expert, int n_used);
-size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used);
+size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used, int type_gu = BAMD_Q4_K, int type_d = BAMD_Q4_K);
 [[nodiscard]] int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a, int n_cu, hipStream_t s);      // 1 = shape or type without a kernel (nothing launched)
 // its launches 4 (gu != 0: type_gu) and 6 (type_d) for a 32-weight block type (bamd_moe_batch_b32.hip), a.blob in that type's form; grid, lds and a.tt from the caller
 int bamd_launch_moe_group_mm_b32(const bamd_moe_batch_args & a, int gu, dim3 grid, size_t lds, hipStream_t s);
+// the unquantised types (bamd_moe_batch_flt.hip): an image is K values of 2 (F16 / BF16) or 4 (F32) bytes; launches 3 / 5 (nw null: no norm) write `rows` of them
+// into blob, launches 4 / 6 read them.  bamd_moe_flt_group_tt: pairs per tile at which the images of row length K fit the LDS of a CU, 8, 4 or 0 (none)
+static inline size_t bamd_moe_flt_image_bytes(int type, int K) { return (size_t) K * (type == BAMD_F32 ? 4 : 2); }
+int bamd_moe_flt_group_tt(int type, int K);
+int bamd_launch_moe_act_batch_flt(int type, const float * x, const float * nw, float eps, int K, int rows, void * blob, hipStream_t s);
+int bamd_launch_moe_group_mm_flt(const bamd_moe_batch_args & a, int gu, dim3 grid, hipStream_t s);
 
 #define BAMD_TL_WG 512                 /* workgroups recorded per launch (phase stamps, BAMD_TIMING builds) */
 #define BAMD_TL_WG_WORDS 24            /* per workgroup: [wave 0: 8 phases][wave 7: 8 phases][exit stamp of each of 8 waves] */

@@ -167,10 +167,10 @@ static int moe_down_tile(int E, int n_cu) {
     const int t = (nrg + cus - 1) / cus;
     return t < 1 ? 1 : t < BAMD_MOE_DOWN_TILE_MAX ? t : BAMD_MOE_DOWN_TILE_MAX;
 }
-int bamd_moe_shape_supported(int E, int F, int n_expert, int n_used) {
+int bamd_moe_shape_supported(int E, int F, int n_expert, int n_used, int type_d) {
     bamd_moe_args a; memset(&a, 0, sizeof a); a.E = E; a.F = F; a.n_expert = n_expert; a.n_used = n_used;
     return moe_shape_ok(a) && E <= bamd_flt_max_k(BAMD_F32) && moe_router_lds(E) <= (size_t) BAMD_LDS_CU_BYTES &&
-           moe_down_lds(F, n_used, BAMD_MOE_DOWN_TILE_MAX) <= (size_t) BAMD_LDS_CU_BYTES;
+           (bamd_is_flt(type_d) ? bamd_moe_flt_down_fits(type_d, F, n_used) : moe_down_lds(F, n_used, BAMD_MOE_DOWN_TILE_MAX) <= (size_t) BAMD_LDS_CU_BYTES);
 }
 int bamd_launch_moe_router(const bamd_moe_args & a, hipStream_t s) {
     if (!bamd_moe_shape_supported(a.E, a.F, a.n_expert, a.n_used)) return 1;
@@ -180,20 +180,22 @@ int bamd_launch_moe_router(const bamd_moe_args & a, hipStream_t s) {
     return 0;
 }
 int bamd_launch_moe_gate_up(const bamd_moe_args & a, int n_cu, hipStream_t s) {
-    if (!bamd_moe_shape_supported(a.E, a.F, a.n_expert, a.n_used) || a.stride_gu >= (size_t) 0x7fffffff) return 1;
+    if (!bamd_moe_shape_supported(a.E, a.F, a.n_expert, a.n_used, a.type_d) || a.stride_gu >= (size_t) 0x7fffffff) return 1;
     // pairs per wave so that slots x tiles fills the chip's wave slots once: tiles = the row-group pairs of a slot over (8 waves x pairs per wave)
     const int nrg = a.F >> 3, cus = n_cu > 0 ? n_cu : 256;
     const int per_wave = (nrg * a.n_used + 8 * cus - 1) / (8 * cus);
     const int tiles = (nrg + 8 * per_wave - 1) / (8 * per_wave);
+    if (bamd_is_flt(a.type_gu)) return bamd_launch_moe_gate_up_flt(a, tiles, s);      // F16 / F32 / BF16 experts: bamd_moe_flt.hip
     // the 32-weight block families: bamd_moe_b32.h, a code object each
     if (bamd_is_b32(a.type_gu)) return bamd_is_q1(a.type_gu) ? bamd_launch_moe_gate_up_b32_q1(a, tiles, s) : a.type_gu == BAMD_IQ4_NL ? bamd_launch_moe_gate_up_b32_nl(a, tiles, s) : bamd_launch_moe_gate_up_b32_q0(a, tiles, s);
     return with_kquant(a.type_gu, [&](auto T) -> bool {
         BAMD_LAUNCH((moe_gate_up_kernel<decltype(T)::value>), dim3(tiles, a.n_used), dim3(512), act_lds_bytes(a.E), s, a); return true; }) ? 0 : 1;
 }
 int bamd_launch_moe_down(const bamd_moe_args & a0, int n_cu, hipStream_t s) {
-    if (!bamd_moe_shape_supported(a0.E, a0.F, a0.n_expert, a0.n_used) || a0.stride_d >= (size_t) 0x7fffffff) return 1;
+    if (!bamd_moe_shape_supported(a0.E, a0.F, a0.n_expert, a0.n_used, a0.type_d) || a0.stride_d >= (size_t) 0x7fffffff) return 1;
     bamd_moe_args a = a0;
     a.tile = moe_down_tile(a.E, n_cu);
+    if (bamd_is_flt(a.type_d)) return bamd_launch_moe_down_flt(a, s);
     if (bamd_is_b32(a.type_d)) return bamd_is_q1(a.type_d) ? bamd_launch_moe_down_b32_q1(a, s) : a.type_d == BAMD_IQ4_NL ? bamd_launch_moe_down_b32_nl(a, s) : bamd_launch_moe_down_b32_q0(a, s);
     const int nrg = a.E >> 3, grid = (nrg + a.tile - 1) / a.tile;
     const size_t lds = moe_down_lds(a.F, a.n_used, a.tile);

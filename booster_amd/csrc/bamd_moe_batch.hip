@@ -220,12 +220,15 @@ extern "C" __attribute__((visibility("default"))) long long bamd_moe_batch_runs(
 // pairs per tile, the dense kernel's rule on the longer of the two row lengths (ONE tile table serves both mat-muls): 8 while their images fit the LDS, else 4
 static int moe_batch_tt(int E, int F) { return moe_group_lds(E > F ? E : F, BAMD_TT) <= (size_t) BAMD_LDS_CU_BYTES ? BAMD_TT : 4; }
 static int moe_batch_tile_bound(int T, int n_expert, int n_used, int tt) { return T * n_used / tt + n_expert; }
-int bamd_moe_batch_supported(int E, int F, int n_expert, int n_used) {
-    return bamd_moe_shape_supported(E, F, n_expert, n_used) && moe_group_lds(E > F ? E : F, 4) <= (size_t) BAMD_LDS_CU_BYTES;
+int bamd_moe_batch_supported(int E, int F, int n_expert, int n_used, int type_gu, int type_d) {
+    if (bamd_is_flt(type_gu) && !bamd_moe_flt_group_tt(type_gu, E)) return 0;      // the unquantised types: four images in their own form (bamd_moe_batch_flt.hip)
+    if (bamd_is_flt(type_d) && !bamd_moe_flt_group_tt(type_d, F)) return 0;
+    return bamd_moe_shape_supported(E, F, n_expert, n_used, type_d) && moe_group_lds(E > F ? E : F, 4) <= (size_t) BAMD_LDS_CU_BYTES;
 }
 size_t bamd_moe_batch_tiles_bytes(int T, int n_expert, int n_used) { return (size_t) (1 + moe_batch_tile_bound(T, n_expert, n_used, 4)) * 16; }
-size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used) {
-    const size_t x = (size_t) T * bamd_blob_bytes(E), h = (size_t) T * n_used * bamd_blob_bytes(F);
+size_t bamd_moe_batch_blob_bytes(int T, int E, int F, int n_used, int type_gu, int type_d) {
+    const size_t x = (size_t) T * (bamd_is_flt(type_gu) ? bamd_moe_flt_image_bytes(type_gu, E) : bamd_blob_bytes(E));
+    const size_t h = (size_t) T * n_used * (bamd_is_flt(type_d) ? bamd_moe_flt_image_bytes(type_d, F) : bamd_blob_bytes(F));
     return x > h ? x : h;
 }
 size_t bamd_moe_batch_blob16_bytes(int T, int E, int F, int n_used) {
@@ -241,6 +244,7 @@ static bool launch_group_mm(const bamd_moe_batch_args & a, int n_cu, hipStream_t
     if (gy * 8 > nrg) gy = (nrg + 7) / 8;
     const dim3 grid(moe_batch_tile_bound(a.T, a.m.n_expert, a.m.n_used, a.tt), gy);
     const size_t lds = moe_group_lds(K, a.tt);
+    if (bamd_is_flt(GU ? a.m.type_gu : a.m.type_d)) return bamd_launch_moe_group_mm_flt(a, GU, grid, s) == 0;           // the unquantised types: bamd_moe_batch_flt.hip
     if (bamd_is_b32(GU ? a.m.type_gu : a.m.type_d)) return bamd_launch_moe_group_mm_b32(a, GU, grid, lds, s) == 0;      // the 32-weight block types: bamd_moe_batch_b32.hip
     return with_kquant(GU ? a.m.type_gu : a.m.type_d, [&](auto T) -> bool {
         constexpr int TYPE = decltype(T)::value;
@@ -250,11 +254,15 @@ static bool launch_group_mm(const bamd_moe_batch_args & a, int n_cu, hipStream_t
 }
 int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a0, int n_cu, hipStream_t s) {
     const bamd_moe_args & m = a0.m;
-    if (!bamd_moe_batch_supported(m.E, m.F, m.n_expert, m.n_used) || a0.T < 1 || a0.T * m.n_used > BAMD_MOE_BATCH_MAX_PAIRS) return 1;
-    if (m.stride_gu >= (size_t) 0x7fffffff || m.stride_d >= (size_t) 0x7fffffff || !(bamd_is_kquant(m.type_gu) || bamd_is_b32(m.type_gu)) || !(bamd_is_kquant(m.type_d) || bamd_is_b32(m.type_d))) return 1;
+    if (!bamd_moe_batch_supported(m.E, m.F, m.n_expert, m.n_used, m.type_gu, m.type_d) || a0.T < 1 || a0.T * m.n_used > BAMD_MOE_BATCH_MAX_PAIRS) return 1;
+    if (m.stride_gu >= (size_t) 0x7fffffff || m.stride_d >= (size_t) 0x7fffffff || !(bamd_is_kquant(m.type_gu) || bamd_is_b32(m.type_gu) || bamd_is_flt(m.type_gu)) ||
+        !(bamd_is_kquant(m.type_d) || bamd_is_b32(m.type_d) || bamd_is_flt(m.type_d))) return 1;
     bamd_moe_batch_args a = a0;
     const bool mfma = bamd_moe_batch_mfma_ready(a0);      // launches 4 and 6 on the matrix cores (bamd_moe_batch_mfma.hip): tiles of 64 pairs, f16 records only
     a.tt = mfma ? 64 : moe_batch_tt(m.E, m.F);
+    // ONE tile table serves both mat-muls: an unquantised tensor whose eight images do not fit the LDS brings the tile of both down to 4 pairs
+    if (bamd_is_flt(m.type_gu) && bamd_moe_flt_group_tt(m.type_gu, m.E) < a.tt) a.tt = 4;
+    if (bamd_is_flt(m.type_d) && bamd_moe_flt_group_tt(m.type_d, m.F) < a.tt) a.tt = 4;
     const int npairs = a.T * m.n_used;
     const size_t rlds = moe_router_lds(m.E);
     bamd_allow_lds(moe_router_batch_kernel, rlds);
@@ -271,11 +279,14 @@ int bamd_launch_moe_ffn_batch(const bamd_moe_batch_args & a0, int n_cu, hipStrea
         hipLaunchKernelGGL(moe_combine_kernel, dim3(a.T), dim3(256), 0, s, (const float *) a.prod, m.x, m.E, m.n_used, m.out);
         return 0;
     }
-    // launches 3 and 5 in the form of the mat-mul that reads them: Q8_K, or Q8_0 / Q8_1 (bamd_launch_quantize_batch_b32) at the same stride
-    bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, a.blob, nullptr, s, bamd_act_form_of(m.type_gu));
+    // launches 3 and 5 in the form of the mat-mul that reads them: Q8_K, or Q8_0 / Q8_1 (bamd_launch_quantize_batch_b32) at the same stride, or the f16 / f32 / bf16
+    // image of an unquantised expert tensor (bamd_launch_moe_act_batch_flt) at its own
+    if (bamd_is_flt(m.type_gu)) { if (bamd_launch_moe_act_batch_flt(m.type_gu, m.x, m.normw, m.eps, m.E, a.T, a.blob, s)) return 1; }
+    else bamd_launch_quantize_batch(m.x, m.normw, m.eps, m.E, a.T, a.blob, nullptr, s, bamd_act_form_of(m.type_gu));
     if (!launch_group_mm<true>(a, n_cu, s)) return 1;
     g_moe_batch_runs += 1;
-    bamd_launch_quantize_batch(m.h, nullptr, 0.f, m.F, npairs, a.blob, nullptr, s, bamd_act_form_of(m.type_d));
+    if (bamd_is_flt(m.type_d)) { if (bamd_launch_moe_act_batch_flt(m.type_d, m.h, nullptr, 0.f, m.F, npairs, a.blob, s)) return 1; }
+    else bamd_launch_quantize_batch(m.h, nullptr, 0.f, m.F, npairs, a.blob, nullptr, s, bamd_act_form_of(m.type_d));
     if (!launch_group_mm<false>(a, n_cu, s)) return 1;
     hipLaunchKernelGGL(moe_combine_kernel, dim3(a.T), dim3(256), 0, s, (const float *) a.prod, m.x, m.E, m.n_used, m.out);
     return 0;

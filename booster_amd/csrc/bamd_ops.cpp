@@ -161,16 +161,16 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_ffn_gate_up(int ty
                                    float eps, float * y) {
     return op_matvec(type, wg_raw, wu_raw, nrows, k, x, norm_w, eps, nullptr, y, BAMD_EPI_SILU_MUL, 0);
 }
-// what an expert tensor may be: a K-quant or a 32-weight block type, gate/up and down independently of each other (bamd_launch_moe_gate_up / _down route by family)
-static bool moe_expert_type(int t) { return bamd_is_kquant(t) || bamd_is_b32(t); }
+// what an expert tensor may be: a K-quant, a 32-weight block type or an unquantised one, gate/up and down independently of each other (bamd_launch_moe_gate_up / _down route by family)
+static bool moe_expert_type(int t) { return bamd_is_kquant(t) || bamd_is_b32(t) || bamd_is_flt(t); }
 // the three MoE launches of a decode step (enqueue_layers) on experts packed as the loader packs them: n_expert consecutive wave-stream matrices per tensor
 extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d,
                                                                         const void * down_exps, int E, int F, int n_expert, int n_used, const float * x, const float * norm_w,
                                                                         float eps, float * y, int32_t * sel, float * w) {
     if (need_device()) return 1;
-    if (!moe_expert_type(type_gu) || !moe_expert_type(type_d)) return fail("moe_ffn: expert matrices must be of a type with a routed kernel (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
+    if (!moe_expert_type(type_gu) || !moe_expert_type(type_d)) return fail("moe_ffn: expert matrices must be of a type with a routed kernel (F32, F16, BF16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
     if (E <= 0 || F <= 0 || E % 256 || F % 256) return fail("moe_ffn: E and F must be positive multiples of 256");
-    if (!bamd_moe_shape_supported(E, F, n_expert, n_used)) return fail("moe_ffn: n_expert must be a multiple of 8 (at most 64), 1 <= n_used <= 8, and the n_used Q8_K activation vectors of F must fit the LDS of a CU");
+    if (!bamd_moe_shape_supported(E, F, n_expert, n_used, type_d)) return fail("moe_ffn: n_expert must be a multiple of 8 (at most 64), 1 <= n_used <= 8, and the n_used activation vectors of F (Q8_K; f16 / f32 / bf16 for an unquantised type_d) must fit the LDS of a CU");
     Tmp t;
     const size_t gub = bamd_row_bytes(type_gu, E) * (size_t) F, db = bamd_row_bytes(type_d, F) * (size_t) E;             // GGUF bytes of one expert
     const size_t gus = bamd_stream_bytes(type_gu, E, F), ds = bamd_stream_bytes(type_d, F, E), gis = bamd_stream_bytes(BAMD_F32, E, n_expert);
@@ -180,9 +180,9 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn(const floa
     int32_t * dsel = (int32_t *) t.up(nullptr, 64); float * dwt = (float *) t.up(nullptr, 64);
     if (!rg || !ru || !rd || !ri || !sg || !su || !sd || !si || !dx || !dw || !dy || !dh || !dsel || !dwt) return fail("device alloc/copy failed");
     for (int e = 0; e < n_expert; ++e) {
-        bamd_launch_repack((const char *) rg + e * gub, (char *) sg + e * gus, type_gu, F, E, nullptr);
-        bamd_launch_repack((const char *) ru + e * gub, (char *) su + e * gus, type_gu, F, E, nullptr);
-        bamd_launch_repack((const char *) rd + e * db, (char *) sd + e * ds, type_d, E, F, nullptr);
+        bamd_launch_repack_expert((const char *) rg + e * gub, (char *) sg + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack_expert((const char *) ru + e * gub, (char *) su + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack_expert((const char *) rd + e * db, (char *) sd + e * ds, type_d, E, F, nullptr);
     }
     bamd_launch_repack(ri, si, BAMD_F32, n_expert, E, nullptr);
     bamd_moe_args a; memset(&a, 0, sizeof a);
@@ -200,10 +200,10 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn_batch(cons
                                                                               const void * down_exps, int E, int F, int n_expert, int n_used, const float * x, int T,
                                                                               const float * norm_w, float eps, float * y, int32_t * sel, float * w) {
     if (need_device()) return 1;
-    if (!moe_expert_type(type_gu) || !moe_expert_type(type_d)) return fail("moe_ffn_batch: expert matrices must be of a type with a routed kernel (Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
+    if (!moe_expert_type(type_gu) || !moe_expert_type(type_d)) return fail("moe_ffn_batch: expert matrices must be of a type with a routed kernel (F32, F16, BF16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, IQ4_XS, Q8_0, Q4_0, Q5_0, Q4_1, Q5_1, IQ4_NL)");
     if (E <= 0 || F <= 0 || E % 256 || F % 256) return fail("moe_ffn_batch: E and F must be positive multiples of 256");
     if (T < 1 || T > BAMD_PREFILL_CAP) return fail("moe_ffn_batch: 1 <= T <= 512");
-    if (!bamd_moe_batch_supported(E, F, n_expert, n_used)) return fail("moe_ffn_batch: the limits of moe_ffn, and four Q8_K activation vectors of the longer of E and F must fit the LDS of a CU");
+    if (!bamd_moe_batch_supported(E, F, n_expert, n_used, type_gu, type_d)) return fail("moe_ffn_batch: the limits of moe_ffn, and four Q8_K activation vectors of the longer of E and F (for an unquantised type, four of its own row length in its own form) must fit the LDS of a CU");
     Tmp t;
     const size_t gub = bamd_row_bytes(type_gu, E) * (size_t) F, db = bamd_row_bytes(type_d, F) * (size_t) E;             // GGUF bytes of one expert
     const size_t gus = bamd_stream_bytes(type_gu, E, F), ds = bamd_stream_bytes(type_d, F, E), gis = bamd_stream_bytes(BAMD_F32, E, n_expert);
@@ -213,12 +213,12 @@ extern "C" __attribute__((visibility("default"))) int bamd_op_moe_ffn_batch(cons
     float * dx = (float *) t.up(x, (size_t) T * E * 4), * dw = (float *) t.up(norm_w, (size_t) E * 4), * dy = (float *) t.up(nullptr, (size_t) T * E * 4);
     float * dh = (float *) t.up(nullptr, np * F * 4), * dprod = (float *) t.up(nullptr, np * E * 4), * dwt = (float *) t.up(nullptr, np * 4);
     int32_t * dsel = (int32_t *) t.up(nullptr, np * 4), * lists = (int32_t *) t.up(nullptr, np * 4), * tiles = (int32_t *) t.up(nullptr, bamd_moe_batch_tiles_bytes(T, n_expert, n_used));
-    void * blob = t.up(nullptr, bamd_moe_batch_blob_bytes(T, E, F, n_used));
+    void * blob = t.up(nullptr, bamd_moe_batch_blob_bytes(T, E, F, n_used, type_gu, type_d));
     if (!rg || !ru || !rd || !ri || !sg || !su || !sd || !si || !dx || !dw || !dy || !dh || !dprod || !dwt || !dsel || !lists || !tiles || !blob) return fail("device alloc/copy failed");
     for (int e = 0; e < n_expert; ++e) {
-        bamd_launch_repack((const char *) rg + e * gub, (char *) sg + e * gus, type_gu, F, E, nullptr);
-        bamd_launch_repack((const char *) ru + e * gub, (char *) su + e * gus, type_gu, F, E, nullptr);
-        bamd_launch_repack((const char *) rd + e * db, (char *) sd + e * ds, type_d, E, F, nullptr);
+        bamd_launch_repack_expert((const char *) rg + e * gub, (char *) sg + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack_expert((const char *) ru + e * gub, (char *) su + e * gus, type_gu, F, E, nullptr);
+        bamd_launch_repack_expert((const char *) rd + e * db, (char *) sd + e * ds, type_d, E, F, nullptr);
     }
     bamd_launch_repack(ri, si, BAMD_F32, n_expert, E, nullptr);
     bamd_moe_batch_args a; memset(&a, 0, sizeof a);

@@ -446,6 +446,16 @@ def mixtral_b32_type(dense_fn):
     return fn
 
 
+def mixtral_float_type(ttype):
+    """convert_hf_to_gguf --outtype f16 / bf16 / f32 on an 8-expert model: every matrix — the merged expert tensors, token_embd and output included — of the one
+    type F16, BF16 or F32; the router ffn_gate_inp and the norms stay F32 as the converter writes them.  Returns type_fn(name, il, n_layer)."""
+    assert ttype in (F16, BF16, F32)
+
+    def fn(name, il, n_layer):
+        return F32 if name == "ffn_gate_inp" else ttype
+    return fn
+
+
 def q3_k_m_type(name, il, n_layer):
     """llama.cpp's Q3_K_M recipe for the Llama architecture (llama_tensor_get_type, llama.cpp:15435-15660): attn_v Q5_K in layers 0-1, else Q4_K;
     attn_output Q4_K; ffn_down Q5_K for il < n_layer / 16, else Q4_K (the use_more_bits cases of the recipe give Q4_K as well); output Q6_K;

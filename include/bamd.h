@@ -301,14 +301,16 @@ int bamd_op_ffn_gate_up(int type, const void * wg_raw, const void * wu_raw, int 
                         float eps, float * y);
 /* the mixture-of-experts feed-forward of one token (llm_build_moe_ffn, llama.cpp:8087-8186, behind the ffn RMSNorm) through the three launches of a
  * decode step (router | routed gate/up | routed down + combine): gate_inp = F32 [n_expert][E]; gate_exps / up_exps = n_expert matrices [F][E] of type_gu,
- * down_exps = n_expert matrices [E][F] of type_d, GGUF-layout blocks, expert after expert (the 3-D tensors as they lie in the file); K-quant types and Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL, type_gu and type_d independent.
- * n_expert a multiple of 8, at most 64; 1 <= n_used <= 8.  y[E] = x + MoE output, sel[n_used] = the selected experts, w[n_used] = their normalised weights */
+ * down_exps = n_expert matrices [E][F] of type_d, GGUF-layout blocks, expert after expert (the 3-D tensors as they lie in the file); K-quant types, Q8_0 / Q4_0 / Q5_0 / Q4_1 / Q5_1 / IQ4_NL and the
+ * unquantised F32 / F16 / BF16 (0 / 1 / 30), type_gu and type_d independent.  An unquantised type_d keeps n_used rows of F values, 2 (F16 / BF16) or 4 (F32) bytes
+ * each, in the LDS of a CU.  n_expert a multiple of 8, at most 64; 1 <= n_used <= 8.  y[E] = x + MoE output, sel[n_used] = the selected experts, w[n_used] = their normalised weights */
 int bamd_op_moe_ffn(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
                     int n_expert, int n_used, const float * x, const float * norm_w, float eps, float * y, int32_t * sel, float * w);
 /* the same for a micro-batch of T tokens (1 <= T <= 512) through the seven launches of a prompt micro-batch (batched router | grouping | Q8_K | grouped gate/up |
  * Q8_K of h | grouped down | combine), bit-identical per token to bamd_op_moe_ffn: x [T][E], y [T][E], sel / w [T][n_used].  Also: four Q8_K activation
  * vectors of the longer of E and F must fit the LDS of a CU (E, F <= 35840).  The same expert types as bamd_op_moe_ffn, type_gu and type_d independent: launches 3 / 4
- * and 5 / 6 quantise and multiply in the form of their own tensor (Q8_K, or Q8_0 / Q8_1 for the 32-weight block types).  With bamd_set_prefill_moe on, launches 4 / 6
+ * and 5 / 6 quantise and multiply in the form of their own tensor (Q8_K, or Q8_0 / Q8_1 for the 32-weight block types, or the f16 / f32 / bf16 rows of an unquantised type, four of which must fit the LDS; those types have no
+ * matrix-core grouped kernel).  With bamd_set_prefill_moe on, launches 4 / 6
  * run on the matrix cores while BOTH tensors have a grouped matrix-core kernel now: Q4_K / Q5_K / Q6_K, or a 32-weight block type whose own family switch
  * (bamd_set_prefill_q0 / _q1 / _nl) is on as well; otherwise both stay on the integer-dot kernels */
 int bamd_op_moe_ffn_batch(const float * gate_inp, int type_gu, const void * gate_exps, const void * up_exps, int type_d, const void * down_exps, int E, int F,
